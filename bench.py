@@ -7,7 +7,11 @@ metric is quoted on fwd+bwd at 416x416, which fits one GPU).
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the MFMA
+Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of one of the --steps timed steps.
+`--dump-outputs DIR` writes what the last timed step returned (loss[5], ious, object mask; the forward output with
+--forward-only) and a fixed, seeded sample of the parameters it updated as DIR/<name>.npy (float32): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+`roofline` is for the dominant kernel (the MFMA
 implicit-GEMM convolution: forward, dgrad and wgrad launches): algorithmic FLOPs of those
 launches / the union of their HIP-event intervals, measured on the launch streams inside the timed region.
 `cpu_baseline` is the oracle's PyTorch-CPU restatement of the same train step on a
@@ -189,6 +193,30 @@ def sustained(run, sync_all, steps, batch, world):
     sync_all()
     el = time.perf_counter() - t0
     return {"steps": steps, "ms_per_step": el / steps * 1e3, "images_per_s": world * batch * steps / el}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32, or float64 where the array is float64), at most 64 MB"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        assert total <= 64 << 20, "--dump-outputs: more than 64 MB"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def param_sample(params, k=1 << 20, seed=0):
+    """a fixed, seeded sample of k entries of a flat parameter buffer (sorted indices, the same for every run)"""
+    import numpy as np
+    import torch
+    n = params.numel()
+    if n <= k:
+        return params
+    idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    return params[torch.as_tensor(idx, device=params.device)]
 
 
 def extra_leg(name, net, run, spec, flop_mult, bs, size, dtype, steps=20, warmup=3):
@@ -582,7 +610,13 @@ def main():
     ap.add_argument("--own-stream", action="store_true", help="run on a torch side stream instead of the default (NULL) stream")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) | gloo (single-GPU functional test)")
     ap.add_argument("--all-ranks-on-gpu0", action="store_true", help="functional test of the N>1 path on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy; --model detector only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.model != "detector":
+        ap.error("--dump-outputs: --model detector only")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -682,10 +716,20 @@ def main():
                 sampled += 1
             elif i % stride == 1 or stride == 1:
                 net.profile_enable(0)
-        run()
+        last = run()
     sync_all()
     elapsed = time.perf_counter() - t0
     st1 = scaler.state() if scaler is not None else None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last step, taken before anything else runs on the network:
+        # the train step's (loss[5], ious, object mask) and a sample of the parameters its Adam update wrote, or the
+        # forward's output
+        if args.forward_only:
+            dump_outputs(args.dump_outputs, {"output": last})
+        else:
+            loss, ious, mask = last
+            dump_outputs(args.dump_outputs, {"loss": loss, "ious": ious, "object_mask": mask,
+                                             "params_sample": param_sample(net.params)})
     busy = net.profile_busy() if args.kernel_events == "timed" else None
     prof = net.profile_collect() if args.kernel_events == "timed" else None
     net.profile_enable(0)
