@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of library builds / environment switches (box-to-box spread is +-5 %: never compare across gpurun calls).
 #   scripts/ab_layers.sh "NAME=ENV..." ...   each arm: a label, '=', then env assignments (may be empty), e.g.
-#   scripts/ab_layers.sh "new=" "r2=Y2_LIB_PATH=tensorflow_yolo2_amd/libyolo2_hip_r2.so" "bordered=Y2_HALO_COMPACT=0"
+#   scripts/ab_layers.sh "new=" "r2=Y2_LIB_PATH=tensorflow_yolo2_amd/libyolo2_hip_r2.so" "noks=Y2_NO_KSPLIT=1"
 # Runs scripts/profile_layers.py for every arm, twice, interleaved; prints the per-layer fwd / dgrad / wgrad columns side by side.
 cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out/ab

@@ -1,6 +1,6 @@
 #!/bin/bash
 # LDS / issue counters of the convolution kernels at one shape, for each environment arm ("name=ENV..."), same box.
-#   scripts/pmc_conv.sh "13 1024 1024 3" "cpt=Y2_HALO_COMPACT=1" "bord=Y2_HALO_COMPACT=0"
+#   scripts/pmc_conv.sh "13 1024 1024 3" "base=" "noxcd=Y2_XCD_CONV=0"
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 shape="$1"; shift

@@ -228,25 +228,13 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_halo_kernel(ConvArgs a, int 
     conv_epilogue<T, WP, WC, TP, TC>(a, acc, smem, w, lane, m0, n0, pt, ct);
 }
 
-// worst-case rows of the A image over all tiles of the launch
-static int halo_rows(int H, int W, int BP, int RPI) {
-    const int pitch = W + 1;
-    const int rows_cross = (BP - 1) / W + 1;
-    const int img_cross = (BP - 1) / (H * W) + 1;
-    const int span = (BP - 1) + rows_cross + img_cross * pitch;
-    const int nrows = span + 2 * (pitch + 1) + 1;
-    return (nrows + RPI - 1) / RPI * RPI;
-}
-
 template <typename T, int WP, int WC, int TP, int TC, int BKB, int NSB, bool ADB, int ABL = 0>
-static hipError_t halo_launch(const ConvArgs& a, hipStream_t s) {
+static hipError_t halo_launch(const ConvArgs& a, int arows, hipStream_t s) {
     typedef HaloCfg<T, WP, WC, TP, TC, BKB, NSB, ADB> Cfg;
     typedef EpiCfg<T, WP, WC, TP, TC> Epi;
-    if ((a.C * (int)sizeof(T)) % BKB != 0) return hipErrorInvalidValue;
-    const int arows = halo_rows(a.H, a.W, Cfg::BP, Cfg::RPI);
     size_t lds = (size_t)Cfg::NA * arows * BKB + (size_t)NSB * Cfg::BSTAGE;
     if (lds < (size_t)Epi::LDS) lds = Epi::LDS;
-    if (lds > 160 * 1024) return hipErrorOutOfMemory;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;      // (plan_conv only picks tiles that fit)
     auto kern = conv_halo_kernel<T, WP, WC, TP, TC, BKB, NSB, ADB, ABL>;
     static size_t attr = 0;
     if (lds > attr) {
@@ -264,57 +252,266 @@ static hipError_t halo_launch(const ConvArgs& a, hipStream_t s) {
 template <typename T, int WP, int WC, int TP, int TC, int BKB, int NSB, int ABL = 0>
 static hipError_t halo_pick(const ConvArgs& a, hipStream_t s) {
     typedef HaloCfg<T, WP, WC, TP, TC, BKB, NSB, true> Cfg;
+    if ((a.C * (int)sizeof(T)) % BKB != 0) return hipErrorInvalidValue;
     const int nchunks = a.C * (int)sizeof(T) / BKB;
-    const size_t arows = halo_rows(a.H, a.W, Cfg::BP, Cfg::RPI);
-    const size_t lds2 = 2 * arows * BKB + (size_t)NSB * Cfg::BSTAGE;
-    if (nchunks > 1 && lds2 <= 150 * 1024) return halo_launch<T, WP, WC, TP, TC, BKB, NSB, true, ABL>(a, s);
-    return halo_launch<T, WP, WC, TP, TC, BKB, NSB, false, ABL>(a, s);
+    const int arows = halo_image_rows(a.H, a.W, Cfg::BP, Cfg::RPI);
+    const size_t lds2 = 2 * (size_t)arows * BKB + (size_t)NSB * Cfg::BSTAGE;
+    if (nchunks > 1 && lds2 <= 150 * 1024) return halo_launch<T, WP, WC, TP, TC, BKB, NSB, true, ABL>(a, arows, s);
+    return halo_launch<T, WP, WC, TP, TC, BKB, NSB, false, ABL>(a, arows, s);
 }
 
+#ifdef Y2_DEVBUILD
+hipError_t launch_conv_halo_variant(int variant, const ConvArgs& a, hipStream_t s, int* bp, bool run);
+#endif
+
+// the tiles plan_conv picks from (halo_tile, below)
 template <typename T>
-static hipError_t halo_T(const ConvArgs& a, hipStream_t s, int* bp) {
-    const int kb = a.C * (int)sizeof(T);
-    const bool k128 = (kb % 128) == 0;
-    if (!k128 && (kb % 64) != 0) return hipErrorInvalidValue;
-    *bp = a.Cout > 64 ? 128 : 256;
-    if (a.Cout > 64) {
-        // measured on the Darknet-19 shapes (scripts/bench_conv.py): big pixel tiles (the filter
-        // ring is re-streamed once per pixel tile) with 8 waves; fall back when LDS runs out
-        hipError_t e = hipErrorOutOfMemory;
-        if (a.W <= 13 && a.M >= 384 * 8) {
-            *bp = 384;
-            // 384 x 128 tiles would leave half the CUs idle when Cout <= 512 (the 1024 -> 512 dgrads
-            // at 13x13: 116 blocks); 384 x 64 tiles fill them (232 blocks, 184 -> 133 us)
-            const bool narrow = ((a.M + 383) / 384) * ((a.Cout + 127) / 128) < 160 && k128;
-            if (narrow) e = halo_pick<T, 4, 2, 3, 1, 128, 2>(a, s);
-            else e = k128 ? halo_pick<T, 4, 2, 3, 2, 128, 2>(a, s) : halo_pick<T, 4, 2, 3, 2, 64, 2>(a, s);
-        } else if (a.M >= 256 * 8) {
-            *bp = 256;
-            e = halo_pick<T, 4, 2, 2, 2, 64, 2>(a, s);
-        }
-        if (e != hipErrorOutOfMemory) return e;
-        (void)hipGetLastError();
-        *bp = 128;
-        return halo_pick<T, 2, 2, 2, 2, 64, 2>(a, s);
-    } else if (a.Cout > 32) {
-        return k128 ? halo_pick<T, 4, 1, 2, 2, 128, 3>(a, s) : halo_pick<T, 4, 1, 2, 2, 64, 3>(a, s);
-    } else {
-        return k128 ? halo_pick<T, 4, 1, 2, 1, 128, 3>(a, s) : halo_pick<T, 4, 1, 2, 1, 64, 3>(a, s);
+static hipError_t halo_run(int cfg, const ConvArgs& a, hipStream_t s) {
+#define HT(WP, WC, TP, TC, BKB, NSB) \
+    case conv_tile(WP, WC, TP, TC, BKB, NSB): return halo_pick<T, WP, WC, TP, TC, BKB, NSB>(a, s);
+    switch (cfg) {
+        HT(4, 2, 3, 1, 128, 2)
+        HT(4, 2, 3, 2, 128, 2)
+        HT(4, 2, 3, 2, 64, 2)
+        HT(4, 2, 2, 2, 64, 2)
+        HT(2, 2, 2, 2, 64, 2)
+        HT(4, 1, 2, 2, 128, 3)
+        HT(4, 1, 2, 2, 64, 3)
+        HT(4, 1, 2, 1, 128, 3)
+        HT(4, 1, 2, 1, 64, 3)
     }
+#undef HT
+    return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv_halo(int dtype, const ConvArgs& a, hipStream_t s, int* bp) {
-    if (a.taps != 9) return hipErrorInvalidValue;
+hipError_t launch_conv_halo(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    if (a.taps != 9 || p.kind != CK_HALO) return hipErrorInvalidValue;
+#ifdef Y2_DEVBUILD
+    if (p.cfg < conv_tile(0, 0, 0, 0, 64, 0)) return dtype == 1 ? launch_conv_halo_variant(p.cfg, a, s, nullptr, true) : hipErrorInvalidValue;
+#endif
     switch (dtype) {
-        case 0: return halo_T<float>(a, s, bp);
-        case 1: return halo_T<half_t>(a, s, bp);
-        case 2: return halo_T<bf16_t>(a, s, bp);
+        case 0: return halo_run<float>(p.cfg, a, s);
+        case 1: return halo_run<half_t>(p.cfg, a, s);
+        case 2: return halo_run<bf16_t>(p.cfg, a, s);
     }
     return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------
+// Kernel policy of the convolution launches (forward and dgrad): plan_conv (below) decides the kernel family, its tile, the filter
+// pack the kernel reads, the K split of small launches and the BN record size -- host arithmetic only.  The bind-time
+// filter pack (net.hip), the dgrad's BN-backward fuse decision, the inference-fold eligibility and launch_conv all read
+// the same answer, and launch_conv refuses filters packed in another layout than the plan's.
+//
+// Measured on MI355X (scripts/bench_conv.py and profile_layers.py):
+//   3x3, rows <= 52 / 104 / the 208-wide 32-channel dgrad : conv_haloq (halo image + register filters)
+//   3x3, what conv_haloq's K-chunk sizes do not divide     : conv_halo  (halo image + LDS filter ring)
+//   3x3 208-wide forward, and every 1x1                    : conv_igemm (per-tap staging)
+//   the 208-wide 32 <-> 64 and the 128-cout 104-wide layers (16-bit) : conv_rf (filters resident in registers)
+// ---------------------------------------------------------------------------
+constexpr int kLdsMax = 160 * 1024;
+
+int halo_image_rows(int H, int W, int BP, int RPI, int pool) {
+    const int pitch = W + 1;
+    if (pool) {     // a run of BP / 4 windows touches at most ceil((Wo - 1 + BP / 4) / Wo) row pairs
+        const int Wo = W / 2, Ho = H / 2, nwin = BP / 4;
+        const int pairs = (nwin + 2 * Wo - 2) / Wo;
+        const int img_cross = (nwin - 1) / (Ho * Wo) + 1;
+        const int nrows = 2 * pairs * pitch + img_cross * pitch + 2 * (pitch + 1) + 1;
+        return (nrows + RPI - 1) / RPI * RPI;
+    }
+    const int rows_cross = (BP - 1) / W + 1;
+    const int img_cross = (BP - 1) / (H * W) + 1;
+    const int span = (BP - 1) + rows_cross + img_cross * pitch;
+    const int nrows = span + 2 * (pitch + 1) + 1;
+    return (nrows + RPI - 1) / RPI * RPI;
+}
+static int image_rows(const ConvTile& t, const ConvArgs& a, int pool) {
+    return halo_image_rows(a.H, a.W, t.bp(), 64 / (t.bkb / 16), pool);
+}
+// bytes of what the kernels store (the epilogue patch): f32 and the fp32-wide split modes 4, f16 / bf16 and dtype 5 2
+static int out_size(int dtype) { return (dtype == 0 || dtype == 3 || dtype == 4) ? 4 : 2; }
+
+// ---- conv_rf.hip
+// 0: not this form (16-bit launches only: row_bytes = input channels * 2).
+//   1: 32 -> 64 on 208-wide maps (forward of the second layer)      8 waves x 32 pixels x 64 couts, one workgroup per CU
+//   2: 64 -> 32 on 208-wide maps (its dgrad)                        8 waves x 32 pixels x 32 couts, one workgroup per CU
+static int rf_config(int taps, int W, int row_bytes, int Cout, int M) {
+    static const bool off = getenv("Y2_NO_CONV_RF") != nullptr;
+    if (off || taps != 9 || W <= 104 || W + 2 >= 256 || M < 256 * 1024) return 0;
+    if (row_bytes == 64 && Cout > 32 && Cout <= 64) return 1;
+    if (row_bytes == 128 && Cout <= 32) return 2;
+    return 0;
+}
+// 3: the 128-cout form: forward (with statistics), plain, and dgrad with the fused BN-backward reduce
+static int rfn_config(int taps, int W, int row_bytes, int Cout, int M, int dgrad) {
+    static const bool off = getenv("Y2_NO_CONV_RF") != nullptr;
+    static const bool nodg = getenv("Y2_NO_CONV_RFN_DGRAD") != nullptr;
+    if (off || (dgrad && nodg) || taps != 9 || W <= 52 || W + 2 > 128 || M < 128 * 1024) return 0;
+    if (row_bytes == 128 && Cout > 64 && Cout <= 128) return 3;
+    return 0;
+}
+
+// ---- K split of small launches (conv_haloq_kernel / conv_igemm_kernel <.., KS>): the depth fills ~one round of the chip
+static int ks_depth(int wgs, int wgs_max, int nchunks) {
+    static const bool off = getenv("Y2_NO_KSPLIT") != nullptr;
+    if (off || wgs >= wgs_max || nchunks < 4) return 1;
+    int d = 256 / wgs;
+    d = d > 8 ? 8 : d;
+    d = d > nchunks / 2 ? nchunks / 2 : d;
+    return d < 2 ? 1 : d;
+}
+size_t conv_ks_scratch_floats(int taps, int M, int ldy, int row_bytes) {
+    if ((taps != 9 && taps != 1) || M >= 384 * 8 || (row_bytes % 128) != 0 || ldy <= 64) return 0;
+    return (size_t)8 * M * ldy;
+}
+// what the launch can take of the split: the refusals of the K-split form, then the depth its scratch holds
+static int ks_clamp(int depth, const ConvArgs& a) {
+    if (depth < 2 || !a.ks_scratch || a.bw_psum || a.nonfinite || (a.ldy % 4) != 0) return 1;
+    while (depth > 1 && (size_t)depth * a.M * a.ldy > a.ks_floats) --depth;
+    return depth < 2 ? 1 : depth;
+}
+
+// ---- conv_haloq.hip tiles
+constexpr int HQ_384x128_M16 = conv_tile(4, 2, 3, 2, 128, 1), HQ_256x128_M16 = conv_tile(4, 2, 2, 2, 128, 1),
+              HQ_384x64 = conv_tile(4, 2, 3, 1, 128, 0), HQ_512x128 = conv_tile(4, 2, 4, 2, 128, 0),
+              HQ_256x128 = conv_tile(4, 2, 2, 2, 128, 0), HQ_512x64 = conv_tile(4, 2, 4, 1, 128, 0),
+              HQ_256x64 = conv_tile(4, 2, 2, 1, 128, 0);
+// Tile choice of conv_haloq on the short-row layers.  Rounds 1-3 tuned the launch policy on the 416x416 batch-64 shapes
+// only: 384 x 128 tiles (384 x 64 where fewer than 160 of them exist).  At 224x224 batch 128 (configs[2]) that puts 264
+// workgroups of the 14x14 layers on 256 CUs -- two rounds, the second with eight workgroups -- and 136 / 272 on the
+// 7x7 ones: those layers ran at 0.5-0.6 PFLOP/s against 1.0-1.1 for their 26x26 / 13x13 siblings
+// (profiles/r04_layers_c3_round_start.txt).  Cost model fitted to a sweep of six tile shapes over the six 3x3 shapes
+// of configs[2] (scripts/sweep_c3.sh, profiles/r04_sweep_c3_tiles.txt; rms error 7 %):
+//     time ~ rounds * BP * BC / (eff(tile) * (1 + (1 - fill)))     rounds = ceil(workgroups / 256), fill = wgs / (rounds * 256)
+// (one 8-wave workgroup per CU; a partly filled chip runs each workgroup faster: clocks and L2 share).  The legacy
+// choice stays unless the model sees more than 8 % in another tile, so every configs[3] layer keeps its kernel.
+static double hq_cost(int M, int Cout, int bp, int bc, double eff) {
+    const long n = (long)((M + bp - 1) / bp) * ((Cout + bc - 1) / bc);
+    const long r = (n + 255) / 256;
+    const double fill = (double)n / (double)(r * 256);
+    return (double)r * bp * bc / (eff * (2.0 - fill));
+}
+// 0: not this class (W <= 52, more than 64 couts, 128-byte K chunks, 3072 pixels and more).  The 52-wide layers joined
+// in round 3 (with the leaner tap step of that round conv_haloq beats conv_halo's LDS filter ring there).
+// elem_size 6 = the split-operand mode (fp32 output, but its 16x16-tile kernel runs the epilogue in two passes over
+// halves of the wave's couts -- conv_haloq.hip EPI2 -- so the 384 x 128 tile is available; the 512 x 128 one is not);
+// the exact-f32 mode takes the two-pass epilogue too (round 5)
+static int haloq_tile_choice(int W, int row_bytes, int Cout, int M, int elem_size) {
+    if (!(W <= 52 && Cout > 64 && M >= 384 * 8 && (row_bytes % 128) == 0)) return 0;
+    const bool narrow = ((M + 383) / 384) * ((Cout + 127) / 128) < 160;
+    const bool split = elem_size == 6 || elem_size == 4;
+    const int legacy = narrow ? HQ_384x64 : HQ_384x128_M16;
+    struct Cand { int id, bp, bc; double eff; bool split_ok; };
+    static const Cand cand[] = {{HQ_384x128_M16, 384, 128, 1.00, true}, {HQ_256x128_M16, 256, 128, 0.95, true},
+                                {HQ_384x64, 384, 64, 0.80, true},        {HQ_512x128, 512, 128, 1.02, false},
+                                {HQ_256x128, 256, 128, 0.92, true},      {HQ_512x64, 512, 64, 0.90, true},
+                                {HQ_256x64, 256, 64, 0.74, true}};
+    double lc = 0.0, bc = 0.0;
+    int best = legacy;
+    for (const Cand& c : cand)
+        if (c.id == legacy) lc = bc = hq_cost(M, Cout, c.bp, c.bc, c.eff);
+    for (const Cand& c : cand) {
+        if (split ? !c.split_ok : c.id == HQ_256x128_M16) continue;
+        const double v = hq_cost(M, Cout, c.bp, c.bc, c.eff);
+        if (v < bc) { bc = v; best = c.id; }
+    }
+    return bc < 0.92 * lc ? best : legacy;
+}
+// LDS of the single-buffered image and of the epilogue patch (16x16 tiles with fp32 outputs: two passes over halves of the
+// couts where the whole patch does not fit, conv_haloq16_kernel EPI2)
+static bool haloq_fits(int tile, const ConvArgs& a, int ysz) {
+    const ConvTile t(tile);
+    const bool epi2 = ysz == 4 && t.aux && t.tc % 2 == 0 && epi_lds(4, t.wp, t.wc, t.tp, t.tc) > kLdsMax;
+    const int epi = epi_lds(ysz, t.wp, t.wc, t.tp, epi2 ? t.tc / 2 : t.tc);
+    return (size_t)image_rows(t, a, a.aff_pool) * t.bkb <= (size_t)kLdsMax && epi <= kLdsMax;
+}
+static int haloq_tile(int dtype, const ConvArgs& a, int kb) {
+    const bool k128 = (kb % 128) == 0, split = dtype_split(dtype);
+    const int ysz = out_size(dtype), bkb = k128 ? 128 : 64;
+    if (a.W > 52) {
+        // long rows (104, 208): 512-pixel tiles amortise the two-row halo; one K-chunk per tile where it fits.
+        // (split-operand forward, round 6: the fp32 epilogue patch sizes the LDS either way, so the two-plane form takes
+        //  128-byte chunks -- 32 channels of both planes, half the tap steps of the 64-byte form; the hi-plane dgrads of
+        //  f16x2f keep the 64-byte chunks: one 128-byte chunk is their whole K -- no second image to load behind the
+        //  first -- and measured 216 against 200 us)
+        // (64-byte K chunks on the 64-cout tiles, so that the 512-pixel image at W = 104 can be double-buffered, measured
+        //  12 % SLOWER than the single-buffered 128-byte ones: half the MFMAs per tap step for the same step overhead)
+        const int t = a.Cout > 64 ? conv_tile(4, 2, 2, 2, dtype == 3 && k128 ? 128 : 64, 0)
+                                  : (a.Cout > 32 ? conv_tile(4, 2, 4, 1, bkb, 0) : conv_tile(8, 1, 2, 1, bkb, 0));
+        if (haloq_fits(t, a, ysz)) return t;
+    }
+    if (a.Cout > 64) {
+        // the tile (and with it the filter pack: 16-row fragments for the 16x16 tiles, 32-row ones otherwise) is decided
+        // here for bind and launch time alike.  (Round 2 fell through to a 32x32-tile kernel on the 16-row pack in the f32
+        // mode -- wrong outputs from batch 24 up at 416x416.)
+        const int t = haloq_tile_choice(a.W, kb, a.Cout, a.M, split ? 6 : ysz);
+        if (t) return t;
+        // Fewer than 3072 pixels (the reference's own training shape, 224x224 at batch 24: 1176 on the 7x7 maps; single
+        // images: 49): the launch is a stream of the FILTERS through a few workgroups, each bound by its serial K loop
+        // (~110 ns per tap step: 72 us for K = 9216 whatever the tile).  64-cout tiles double the workgroups of the 128 x 128
+        // form of rounds 1-3 on the same fragment pack: 7x7 1024 -> 1024 at batch 24 148 -> 81 us, one image 147 -> 72
+        // (profiles/r04_sweep_small_m.txt; 128 x 64, 256 x 32 and 256 x 64 tie -- what is left there is a K split)
+        if (k128 && a.M < 384 * 8) return HQ_256x64;
+        // what the cost model does not cover (64-byte K chunks; long rows that did not fit above)
+        const int big = a.M >= 384 * 8 ? conv_tile(4, 2, 3, 2, bkb, 0) : (a.M >= 256 * 8 ? conv_tile(4, 2, 2, 2, bkb, 0) : 0);
+        if (big && haloq_fits(big, a, ysz)) return big;
+        return conv_tile(2, 2, 2, 2, 64, 0);
+    }
+    return a.Cout > 32 ? conv_tile(4, 1, 2, 2, bkb, 0) : conv_tile(4, 1, 2, 1, bkb, 0);
+}
+
+// ---- conv_halo.hip tiles (16-bit and f32 launches of the 3x3 layers up to 52 wide that conv_haloq does not take)
+static bool halo_fits(int tile, const ConvArgs& a, int sz) {
+    const ConvTile t(tile);
+    const size_t lds = (size_t)image_rows(t, a, 0) * t.bkb + (size_t)t.aux * t.bc() * t.bkb;
+    return lds <= (size_t)kLdsMax && epi_lds(sz, t.wp, t.wc, t.tp, t.tc) <= kLdsMax;
+}
+static int halo_tile(int dtype, const ConvArgs& a, int kb) {
+    const bool k128 = (kb % 128) == 0;
+    const int bkb = k128 ? 128 : 64;
+    if (a.Cout > 64) {
+        // measured on the Darknet-19 shapes (scripts/bench_conv.py): big pixel tiles (the filter ring is re-streamed
+        // once per pixel tile) with 8 waves; 128 x 128 where LDS runs out
+        int t = 0;
+        if (a.W <= 13 && a.M >= 384 * 8) {
+            // 384 x 128 tiles would leave half the CUs idle when Cout <= 512 (the 1024 -> 512 dgrads at 13x13: 116
+            // blocks); 384 x 64 tiles fill them (232 blocks, 184 -> 133 us)
+            const bool narrow = ((a.M + 383) / 384) * ((a.Cout + 127) / 128) < 160 && k128;
+            t = narrow ? conv_tile(4, 2, 3, 1, 128, 2) : conv_tile(4, 2, 3, 2, bkb, 2);
+        } else if (a.M >= 256 * 8) {
+            t = conv_tile(4, 2, 2, 2, 64, 2);
+        }
+        if (t && halo_fits(t, a, (int)dtype_size(dtype))) return t;
+        return conv_tile(2, 2, 2, 2, 64, 2);
+    }
+    return a.Cout > 32 ? conv_tile(4, 1, 2, 2, bkb, 3) : conv_tile(4, 1, 2, 1, bkb, 3);
+}
+
+// ---- conv_igemm.hip tiles
+static int igemm_tile(int dtype, const ConvArgs& a, int kb) {
+    bool k128 = (kb % 128) == 0;
+    // round 6: a two-plane (PL2) chunk of 128 bytes is [64 B hi | 64 B lo] = 32 channels of BOTH planes, so the 32-channel
+    // layer of the split-operand forward (208x208 32 -> 64) takes ONE K step per tap instead of two of half the depth -- half
+    // the barriers and stage waits per matrix instruction
+    static const bool no_pl2 = getenv("Y2_NO_CONV_PL2") != nullptr;
+    if (dtype == 3 && !no_pl2 && kb == 64) k128 = true;
+    const int bkb = k128 ? 128 : 64;
+    // 2 LDS stages and two blocks per CU beat deeper rings here (global->LDS fill rate, not latency, bounds this kernel);
+    // 8 waves of 64x32 beat 4 waves of 64x64 by ~5-8 %
+    if (a.Cout > 64) {
+        // round 6: launches of at most one workgroup per CU have nobody to hide a stage's latency behind -- a ring of three
+        // stages keeps two K steps in flight (LDS is free at one workgroup per CU).  Same box, alternating: the ResNet swap's
+        // step 9.90 / 10.00 -> 9.66 / 9.82 ms (its 14x14 / 7x7 units and the 28x28 ones with 128 couts), configs[2] 4.47 -> 4.45;
+        // four stages 9.89 / 9.83.  No configs[3] launch has so few workgroups.
+        constexpr long kCUs = 256;     // the MI355X's CU count, as measured (not the device's own count on other parts)
+        const long wgs = (long)((a.M + 127) / 128) * ((a.Cout + 127) / 128);
+        return conv_tile(2, 4, 2, 1, bkb, !dtype_split(dtype) && k128 && wgs <= kCUs ? 3 : 2);
+    }
+    return a.Cout > 32 ? conv_tile(4, 1, 2, 2, bkb, 2) : conv_tile(4, 1, 2, 1, bkb, 2);
+}
+
 #ifdef Y2_DEVBUILD
-hipError_t launch_conv_halo_variant(int variant, const ConvArgs& a, hipStream_t s, int* bp);
 // development library only (make dev): Y2DEV_CONV="W:Cout:variant,..." forces a halo variant for (W, Cout), f16
 static int dev_rule(int W, int Cout) {
     static int n = -1;
@@ -336,85 +533,65 @@ static int dev_rule(int W, int Cout) {
 }
 #endif
 
-// filter fragments straight to registers (conv_haloq.hip) -- the filter pack must match (pack.hip,
-// PackLayer::wf_frag / wd_frag).
-// Measured (scripts/bench_conv.py, rotating buffers; round 3: scripts/ab_layers.sh): wins up to 52x52 and again at
-// 104x104 (big 512-pixel tiles); at 208x208 only the 32-channel dgrad gains.
-// 0: K-contiguous rows (conv_halo / conv_igemm); 1: 32-row MFMA fragments (conv_haloq, 32x32x16 tiles);
-// 2: 16-row fragments (conv_haloq on 16x16x32 tiles: the 384 x 128 tile class up to 26x26, +3-4 %).
-// row_bytes = input channels * element size of the launch (forward: cin_s, dgrad: ldy).
-// Tile choice of conv_haloq on the short-row layers.  Rounds 1-3 tuned the launch policy on the 416x416 batch-64 shapes
-// only: 384 x 128 tiles (384 x 64 where fewer than 160 of them exist).  At 224x224 batch 128 (configs[2]) that puts 264
-// workgroups of the 14x14 layers on 256 CUs -- two rounds, the second with eight workgroups -- and 136 / 272 on the
-// 7x7 ones: those layers ran at 0.5-0.6 PFLOP/s against 1.0-1.1 for their 26x26 / 13x13 siblings
-// (profiles/r04_layers_c3_round_start.txt).  Cost model fitted to a sweep of six tile shapes over the six 3x3 shapes
-// of configs[2] (scripts/sweep_c3.sh, profiles/r04_sweep_c3_tiles.txt; rms error 7 %):
-//     time ~ rounds * BP * BC / (eff(tile) * (1 + (1 - fill)))     rounds = ceil(workgroups / 256), fill = wgs / (rounds * 256)
-// (one 8-wave workgroup per CU; a partly filled chip runs each workgroup faster: clocks and L2 share).  The legacy
-// choice stays unless the model sees more than 8 % in another tile, so every configs[3] layer keeps its kernel.
-static double hq_cost(int M, int Cout, int bp, int bc, double eff) {
-    const long n = (long)((M + bp - 1) / bp) * ((Cout + bc - 1) / bc);
-    const long r = (n + 255) / 256;
-    const double fill = (double)n / (double)(r * 256);
-    return (double)r * bp * bc / (eff * (2.0 - fill));
-}
-int haloq_tile_choice(int W, int row_bytes, int Cout, int M, int elem_size) {
-    static const bool no52 = getenv("Y2_NO_HALOQ_52") != nullptr;
-    static const bool legacy_only = getenv("Y2_LEGACY_TILES") != nullptr;     // A/B switch: rounds 1-3 policy
-    const int wsmall = no52 ? 26 : 52;
-    if (!(W <= wsmall && Cout > 64 && M >= 384 * 8 && (row_bytes % 128) == 0)) return HQ_NONE;
-    const bool narrow = ((M + 383) / 384) * ((Cout + 127) / 128) < 160;
-    // the f32 epilogue patch of a 384 x 128 (and 512 x 128) tile does not fit LDS: 256 x 128 on 16x16 tiles there.
-    // elem_size 6 = the split-operand mode (fp32 output, but its 16x16-tile kernel runs the epilogue in two passes over
-    // halves of the wave's couts -- conv_haloq.hip EPI2 -- so the 384 x 128 tile is available; the 512 x 128 one is not)
-    // (round 5, later: the exact-f32 mode takes the two-pass epilogue too -- Y2_F32_TILE_256=1 restores its 256 x 128 tiles)
-    static const bool f32_256 = getenv("Y2_F32_TILE_256") != nullptr;
-    const bool split = elem_size == 6 || (elem_size == 4 && !f32_256);
-    const int legacy = narrow ? HQ_384x64 : ((elem_size == 4 && f32_256) ? HQ_256x128_M16 : HQ_384x128_M16);
-    if (legacy_only) return legacy;
-    struct Cand { int id, bp, bc; double eff; bool f32_ok, split_ok; };
-    static const Cand cand[] = {{HQ_384x128_M16, 384, 128, 1.00, false, true}, {HQ_256x128_M16, 256, 128, 0.95, true, true},
-                                {HQ_384x64, 384, 64, 0.80, true, true},        {HQ_512x128, 512, 128, 1.02, false, false},
-                                {HQ_256x128, 256, 128, 0.92, true, true},      {HQ_512x64, 512, 64, 0.90, true, true},
-                                {HQ_256x64, 256, 64, 0.74, true, true}};
-    double lc = 0.0, bc = 0.0;
-    int best = legacy;
-    for (const Cand& c : cand)
-        if (c.id == legacy) lc = bc = hq_cost(M, Cout, c.bp, c.bc, c.eff);
-    for (const Cand& c : cand) {
-        if (split ? !c.split_ok : (elem_size == 4 ? !c.f32_ok : c.id == HQ_256x128_M16)) continue;
-        const double v = hq_cost(M, Cout, c.bp, c.bc, c.eff);
-        if (v < bc) { bc = v; best = c.id; }
+ConvPlan plan_conv(int dtype, const ConvArgs& a) {
+    ConvPlan p{CK_IGEMM, 0, 0, 0, 1};
+    const int kb = a.C * dtype_kbytes(dtype);       // bytes of one operand plane per pixel: what the K chunks divide
+    const bool split = dtype_split(dtype);
+    const int rf = rf_config(a.taps, a.W, kb, a.Cout, a.M), rfn = rfn_config(a.taps, a.W, kb, a.Cout, a.M, a.is_dgrad);
+    if ((dtype == 1 || dtype == 2) && ((!a.bw_psum && rf) || rfn)) {
+        p.kind = rf && !a.bw_psum ? CK_RF : CK_RFN;
+        p.cfg = p.kind == CK_RF ? rf : rfn;
+        return p;
     }
-    return bc < 0.92 * lc ? best : legacy;
-}
-
-int conv_filter_layout(int taps, int W, int row_bytes, int Cout, int M, int dgrad, int elem_size, int split) {
-    if (taps == 1) {
-        if (split) return 0;
-        // round 6: the deep-ring 1x1 kernel (conv_gemm1.hip) reads 32-row fragments, 16-bit types
-        if (elem_size == 2 && conv_gemm1_ok(taps, row_bytes, Cout, M)) return 1;
-        // 1x1 on conv_haloq (one tap per K-chunk, compact image): 128-byte K chunks, more than 64 output channels, enough
-        // pixels for 384-pixel tiles; 384 x 64 tiles on 32x32 MFMAs (layout 1) where 384 x 128 tiles would leave CUs
-        // idle, else 384 x 128 on 16x16 MFMAs (layout 2).  Opt-in (Y2_HALOQ_1X1=1): measured no faster than conv_igemm
-        // (conv_haloq.hip, haloq_T1)
-        static const bool on = getenv("Y2_HALOQ_1X1") && atoi(getenv("Y2_HALOQ_1X1")) != 0;
-        if (!on || (row_bytes % 128) != 0 || Cout <= 64 || M < 384 * 8) return 0;
-        const bool narrow = ((M + 383) / 384) * ((Cout + 127) / 128) < 160;
-        return narrow ? 1 : 2;
+    // conv_haloq: 3x3 up to 104 wide and the 208-wide 32-cout dgrad, where the register-filter form does not apply (not
+    // in the split-operand mode: three filter planes per product do not fit the register file; those shapes run here).
+    // Measured (scripts/bench_conv.py, rotating buffers; round 3: scripts/ab_layers.sh): wins up to 52x52 and again at
+    // 104x104 (big 512-pixel tiles); at 208x208 only the 32-channel dgrad gains.
+    if (a.taps == 9 && !(!split && (rf || rfn)) && (a.W <= 104 || a.Cout <= 32)) {
+        p.kind = CK_HALOQ;
+        p.cfg = haloq_tile(dtype, a, kb);
+        p.filter_layout = ConvTile(p.cfg).aux ? 2 : 1;
+        p.block_pixels = ConvTile(p.cfg).bp();
+        if (p.cfg == HQ_256x64 && !split && a.M < 384 * 8) {
+            const int depth = ks_clamp(ks_depth(((a.M + 255) / 256) * ((a.Cout + 63) / 64), 128, kb / 128), a);
+            // the split image (not double-buffered by the launcher when it does not fit) must fit LDS
+            if (depth >= 2 && (size_t)image_rows(ConvTile(p.cfg), a, 0) * 128 <= (size_t)kLdsMax) {
+                p.kind = CK_HALOQ_KS;
+                p.ks_depth = depth;
+                p.block_pixels = 128;     // records of conv_ks_stats_kernel
+            }
+        }
+        return p;
     }
-    if (taps != 9) return 0;
-    // register-resident filters: fetched from K-contiguous rows (not in the split-operand mode: three filter planes per
-    // product do not fit the register file; those shapes run on conv_haloq there)
-    if (!split && (conv_rf_config(taps, W, row_bytes, Cout, M) || conv_rfn_config(taps, W, row_bytes, Cout, M, dgrad))) return 0;
-    // Round 3: the 52-wide layers run on conv_haloq too (with the leaner tap step of this round it beats conv_halo's
-    // LDS filter ring there: 128 -> 256 @52x52 forward 130.6 -> 126.2 us, dgrad 130.4 -> 114.0, same box;
-    // Y2_NO_HALOQ_52=1 restores round 2's split for A/B)
-    static const bool no52 = getenv("Y2_NO_HALOQ_52") != nullptr;
-    const int wsmall = no52 ? 26 : 52;
-    if (!(W <= wsmall || (W > 52 && W <= 104) || (W > 104 && Cout <= 32))) return 0;
-    const int tile = haloq_tile_choice(W, row_bytes, Cout, M, split ? 6 : elem_size);
-    return (tile == HQ_384x128_M16 || tile == HQ_256x128_M16) ? 2 : 1;
+#ifdef Y2_DEVBUILD
+    if (a.taps == 9 && dtype == 1 && dev_rule(a.W, a.Cout) >= 0) {
+        p.kind = CK_HALO;
+        p.cfg = dev_rule(a.W, a.Cout);
+        (void)launch_conv_halo_variant(p.cfg, a, 0, &p.block_pixels, false);      // only *bp: the launch refuses an unknown variant
+        return p;
+    }
+#endif
+    if (a.taps == 9 && a.W <= 52 && !split) {
+        p.kind = CK_HALO;
+        p.cfg = halo_tile(dtype, a, kb);
+        p.block_pixels = ConvTile(p.cfg).bp();
+        return p;
+    }
+    p.cfg = igemm_tile(dtype, a, kb);
+    p.block_pixels = ConvTile(p.cfg).bp();
+    // small 1x1 launches: K split over workgroups below 48 workgroups of the 128 x 128 tile (single images, the
+    // reference's batch 24 at 7x7: 40).  (Measured: at 52 .. 208 workgroups -- the ResNet swap's 7x7 units at batch 32 --
+    // the split is neutral to slightly negative: its partial tiles and the two extra launches cost what the shorter K
+    // loops save; configs[0] gains 2.5 %.)  Its BN records cover 128 pixels, as the 128-cout tiles' do.
+    if (a.taps == 1 && dtype <= 2 && a.M < 384 * 8 && kb % 128 == 0 && a.Cout > 64) {
+        const int depth = ks_clamp(ks_depth(((a.M + 127) / 128) * ((a.Cout + 127) / 128), 48, kb / 128), a);
+        if (depth >= 2) {
+            p.kind = CK_IGEMM_KS;
+            p.cfg = conv_tile(2, 4, 2, 1, 128, 2);
+            p.ks_depth = depth;
+        }
+    }
+    return p;
 }
 
 // Inference batch norm folded into the epilogue (ConvArgs::aff_*): every kernel on the shared epilogue
@@ -423,11 +600,10 @@ bool conv_affine_ok(int dtype, const ConvArgs& a) {
     static const bool off = getenv("Y2_NO_INFER_FOLD") != nullptr;
     if (off || a.bw_psum || a.part_mean || a.is_dgrad) return false;
     if (dtype_split(dtype)) return false;      // f16x2: the consumer's tensor is split (two planes); two-pass form
-    const int rowb = a.C * (int)dtype_size(dtype);
     // conv_rf.hip: the 128-cout forward form stores wave-private row segments and folds too; the 208-wide
     // 32 <-> 64 forms (pooled layers in Darknet-19) keep the two-pass form
-    if (dtype != 0 && conv_rf_config(a.taps, a.W, rowb, a.Cout, a.M)) return false;
-    if (dtype != 0 && conv_rfn_config(a.taps, a.W, rowb, a.Cout, a.M, 0) && (a.ldy % 8) != 0) return false;
+    const ConvPlan p = plan_conv(dtype, a);
+    if (p.kind == CK_RF || (p.kind == CK_RFN && (a.ldy % 8) != 0)) return false;
     return a.M > 0 && (unsigned)a.M < 0x7FFFFFFFu;
 }
 
@@ -436,55 +612,40 @@ bool conv_affine_ok(int dtype, const ConvArgs& a) {
 // Y2_NO_POOL_FOLD=1: A/B switch.
 bool conv_affine_pool_ok(int dtype, const ConvArgs& a) {
     static const bool off = getenv("Y2_NO_POOL_FOLD") != nullptr;
-    static const bool compact = getenv("Y2_HALO_COMPACT") && atoi(getenv("Y2_HALO_COMPACT")) != 0;
-    if (off || compact || !conv_affine_ok(dtype, a)) return false;
+    if (off || !conv_affine_ok(dtype, a)) return false;
     if (a.taps != 9 || (a.H & 1) || (a.W & 1) || a.M < 384 * 8) return false;
-    return conv_filter_layout(a.taps, a.W, a.C * dtype_kbytes(dtype), a.Cout, a.M, 0, (int)dtype_size(dtype), 0) != 0;
+    return plan_conv(dtype, a).kind == CK_HALOQ;
 }
 
-// Kernel policy (measured on MI355X, scripts/bench_conv.py and profile_layers.py):
-//   3x3, rows <= 52 / 104 / the 208-wide 32-channel dgrad : conv_haloq (halo image + register filters)
-//   3x3, what conv_haloq's K-chunk sizes do not divide     : conv_halo  (halo image + LDS filter ring)
-//   3x3 208-wide forward, and every 1x1                    : conv_igemm (per-tap staging)
-// *block_pixels receives the pixel-tile size used (= rows per BN partial record)
-hipError_t launch_conv(int dtype, const ConvArgs& a0, hipStream_t s, int* block_pixels, int* records) {
+hipError_t launch_conv(int dtype, const ConvArgs& a0, hipStream_t s, int filter_layout, int* block_pixels, int* records) {
     // XCD-aware workgroup order: measured +1..4 % on every 3x3 layer up to 104x104 (common.h xcd_block)
     static const int xcd_mode = getenv("Y2_XCD_CONV") ? atoi(getenv("Y2_XCD_CONV")) : 1;
     ConvArgs a = a0;
     a.xcd = xcd_mode;
-    int bp = conv_block_pixels(a.Cout);
+    const ConvPlan p = plan_conv(dtype, a);
+    if (filter_layout != p.filter_layout) return hipErrorInvalidValue;     // the filters were packed for another kernel
+    int bp = p.block_pixels, rec = 0;
     hipError_t e;
-    const int rowb = a.C * dtype_kbytes(dtype);         // bytes of one operand plane per pixel: what the K chunks divide
-    const int esz = (int)dtype_size(dtype);             // stored element: sizes the epilogue patch
-    const bool split = dtype_split(dtype);
-    if ((dtype == 1 || dtype == 2) && ((!a.bw_psum && conv_rf_config(a.taps, a.W, rowb, a.Cout, a.M)) ||
-                       conv_rfn_config(a.taps, a.W, rowb, a.Cout, a.M, a.is_dgrad))) {
-        int rec = 0;
-        e = launch_conv_rf(dtype, a, s, &bp, &rec);
-        if (block_pixels) *block_pixels = bp;
-        if (records) *records = rec;
-        return e;
+    switch (p.kind) {
+        case CK_RF: case CK_RFN: e = launch_conv_rf(dtype, p, a, s, &bp, &rec); break;
+        case CK_HALOQ: case CK_HALOQ_KS: e = launch_conv_haloq(dtype, p, a, s); break;
+        case CK_HALO: e = launch_conv_halo(dtype, p, a, s); break;
+        default: e = launch_conv_igemm(dtype, p, a, s); break;
     }
-    if (a.taps == 1 && (dtype == 1 || dtype == 2) && conv_gemm1_ok(a.taps, rowb, a.Cout, a.M)) e = launch_conv_gemm1(dtype, a, s, &bp);
-    else if (conv_filter_layout(a.taps, a.W, rowb, a.Cout, a.M, a.is_dgrad, esz, split)) e = launch_conv_haloq(dtype, a, s, &bp);
-#ifdef Y2_DEVBUILD
-    else if (a.taps == 9 && dtype == 1 && dev_rule(a.W, a.Cout) >= 0)
-        e = launch_conv_halo_variant(dev_rule(a.W, a.Cout), a, s, &bp);
-#endif
-    else if (a.taps == 9 && a.W <= 52 && !split) e = launch_conv_halo(dtype, a, s, &bp);
-    else e = launch_conv_igemm(dtype, a, s);
+    if (p.kind != CK_RF && p.kind != CK_RFN) rec = (a.M + bp - 1) / bp;
     if (block_pixels) *block_pixels = bp;
-    if (records) *records = (a.M + bp - 1) / bp;
+    if (records) *records = rec;
     return e;
 }
 
 #ifdef Y2_DEVBUILD
 // development variants (f16) for scripts/bench_conv.py
+// (run = false: only *bp, for plan_conv's Y2DEV_CONV rule)
 #define HV(id, WP, TPARGS...) \
-    case id: if (bp) *bp = halo_bp<WP, TPARGS>(); return halo_pick<T, WP, TPARGS>(a, s);
+    case id: if (bp) *bp = halo_bp<WP, TPARGS>(); return run ? halo_pick<T, WP, TPARGS>(a, s) : hipSuccess;
 template <int WP, int WC, int TP, int TC, int BKB, int NSB, int ABL = 0>
 static constexpr int halo_bp() { return WP * TP * 32; }
-hipError_t launch_conv_halo_variant(int variant, const ConvArgs& a, hipStream_t s, int* bp) {
+hipError_t launch_conv_halo_variant(int variant, const ConvArgs& a, hipStream_t s, int* bp, bool run) {
     typedef half_t T;
     switch (variant) {
         HV(86, 4, 2, 4, 1, 64, 2)       // 512 x 64, 8 waves, 64-byte chunks

@@ -12,25 +12,7 @@
 // ahead.  Only the halo image lives in LDS, so the workgroup barrier falls once per K-chunk
 // (nine tap steps), and the LDS serves a single fragment stream.
 //
-// COMPACT image (CPT; Y2_HALO_COMPACT=1 -- built, measured, NOT the default): the LDS rows follow the NHW pixel index,
-// not the bordered cell index, and every border tap reads one of 16 zero rows.  The bordered image skips a cell at
-// every image-row wrap, so the 16 LDS rows of a ds_read_b128 lane group ({0-3,12-15,20-27}, ...) stop being
-// distinct mod 16 whenever a 32-pixel fragment crosses an image row -- at W = 13 / 26 always: a 2-way bank conflict
-// on nearly every fragment read (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.50 measured, 0.50 in a bank
-// simulation of the address stream).  In pixel order a tap shift is uniform (kh W + kw) wherever the tap stays
-// inside the image, so a lane group's rows are lambda0 + {0-3,12-15,20-27}: all 16 residues, conflict-free under
-// the row-keyed XOR swizzle for every tap; a tap that leaves the image reads zero row (lambda & 15): the bank
-// position the in-image cell would have had.  The DMA source of an LDS row is a per-row cell index computed once
-// per workgroup (table in LDS); border cells are not staged.  16x16 MFMA tiles mix two k-chunks in a lane group:
-// there the pixel columns of a 16-pixel fragment are dealt so that the first chunk's lanes take the even pixels
-// and the other's the odd ones (perm16), conflict-free for odd and even lambda0 alike; the epilogue patch is
-// written through the same map.  MEASURED (13x13, 1024 -> 1024, batch 64, same box, round 3): conflict ratio
-// 0.50 -> 0.02, LDS-active cycles halved -- and the kernel 4 % SLOWER (181 vs 174 us): the per-(fragment, tap)
-// border select costs 36 more VALU instructions per tap step (87 vs 51 beside 48 MFMAs), and this loop is bound by
-// vector ISSUE, not by the LDS: SQ_WAIT_INST_LDS is 0.9 % of the wave cycles with the conflicts in place.  The
-// conflicts were never on the critical path; the bordered image (uniform shift, no select) stays the default.
-//
-// What did pay in round 3 (both images): the next tap's fragment addresses are computed one step ahead and pinned
+// What paid in round 3: the next tap's fragment addresses are computed one step ahead and pinned
 // between the MFMAs (mfma_interleave), k-group g of a fragment row is address ^ (g * 64) instead of a second swizzle,
 // and the filter fragments are loaded by inline asm with hand-counted vmcnt (frag_load) -- together -3 % on the
 // 13x13 / 26x26 layers against the round-2 kernel on the same box.
@@ -42,8 +24,6 @@
 namespace y2 {
 
 template <int V> struct IntC { static constexpr int value = V; };
-
-constexpr int kZeroRows = 16;   // compact image: zero rows in front of the image buffers (one per bank position)
 
 // Filter-fragment load the compiler does not see: 16 bytes per lane from a per-lane 64-bit address + immediate.  hipcc waits vmcnt(0) at the first use of ANY load it knows of while an LDS-DMA is in flight
 // (cdna_hip_programming.md, "Three .s-level traps" (b)): with plain loads every other tap step began by draining the
@@ -77,15 +57,14 @@ Y2_DEV u32x4 lds_read16(uint32_t lds_addr) {
 // few workgroups (~110 ns per tap step, 72 us for K = 9216 whatever the tile), not by anything a roofline names.
 // PL2 (f16x2 mode): as conv_haloq16_kernel -- an LDS image row is [BKB/2 bytes of the hi plane | BKB/2 of the lo plane], the
 // first half of a row's 32-byte k-groups is x_hi, the second half x_lo, and a tap step runs the three plane products
-template <typename T, int WP, int WC, int TP, int TC, int BKB, bool ADB, bool CPT, int TAPS, bool KS = false, bool PL2 = false>
+template <typename T, int WP, int WC, int TP, int TC, int BKB, bool ADB, bool KS = false, bool PL2 = false>
 __global__ __launch_bounds__(WP* WC * 64) void conv_haloq_kernel(ConvArgs a, int arows) {
-    static_assert(TAPS == 9 || (TAPS == 1 && CPT), "1x1 filters run on the compact image (no halo, no border taps)");
     typedef typename Elem<T>::frag frag_t;
     typedef typename Types<T>::op_t OT;      // f16x2 mode: the operands are half planes of fp32-width rows (common.h)
     typedef typename Types<T>::out_t YT;
     constexpr bool SPLIT = Types<T>::kSplit;
     static_assert(!(SPLIT && KS), "the K split of small launches is not built for the split-operand mode");
-    static_assert(!PL2 || (SPLIT && Types<T>::kPasses == 3 && !CPT && (BKB == 128 || BKB == 64)), "the two-plane form: split operands, bordered image");
+    static_assert(!PL2 || (SPLIT && Types<T>::kPasses == 3 && (BKB == 128 || BKB == 64)), "the two-plane form: split operands");
     constexpr int NW = WP * WC, BP = WP * TP * 32, BC = WC * TC * 32, SZ = sizeof(T);
     constexpr int LPR = BKB / 16, RPI = 64 / LPR, RPB = 256 / BKB, KG = BKB / 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -114,61 +93,25 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq_kernel(ConvArgs a, int
     // pooled layers in the inference fold (ConvArgs::aff_pool): the tile's positions are in window-major order
     auto pixq = [&](int q) -> int { return a.aff_pool ? pool_order_pixel(q, a.H, a.W) : q; };
     const int p_last = (m0 + BP - 1 < a.M) ? m0 + BP - 1 : a.M - 1;
-    const long lo = CPT ? 0 : bpos(pixq(m0)) - pitch - 1;
-    const int nrows = CPT ? arows : (int)(bpos(pixq(p_last)) + pitch + 1 - lo) + 1;
+    const long lo = bpos(pixq(m0)) - pitch - 1;
+    const int nrows = (int)(bpos(pixq(p_last)) + pitch + 1 - lo) + 1;
     const int npieces = (nrows + RPI - 1) / RPI;
     const int abytes = arows * BKB;
     const int rowbytes = a.C * SZ;
     const int npl = a.C * (int)sizeof(OT) / BKB;     // K chunks per operand plane (f16x2: three plane passes, common.h)
-    // compact image: [16 zero rows][image buffer(s): row lambda = pixel (m0 - W - 1 + lambda)][cell index per row]
-    char* const img0 = smem + (CPT ? kZeroRows * BKB : 0);
-    const uint32_t* const cell_tab = (const uint32_t*)(img0 + (ADB ? 2 : 1) * abytes);
-    if (CPT) {
-        uint32_t* tab = (uint32_t*)(img0 + (ADB ? 2 : 1) * abytes);
-        for (int r = tid; r < arows; r += NW * 64) {
-            int q = m0 - (TAPS == 9 ? a.W + 1 : 0) + r;
-            q = q < 0 ? 0 : (q > a.M - 1 ? a.M - 1 : q);      // rows outside the tensor are never read as image cells
-            tab[r] = (uint32_t)bpos(q);
-        }
-        for (int o = tid * 16; o < kZeroRows * BKB; o += NW * 64 * 16) *(u32x4*)(smem + o) = u32x4{0u, 0u, 0u, 0u};
-        __syncthreads();
-    }
-
     const int smem_lds = (int)(uintptr_t)(__attribute__((address_space(3))) char*)smem;   // LDS address of smem
     const int lrow = lane / LPR, lslot = lane % LPR;
     constexpr int KGH = KG / 2;                            // PL2: 32-byte k-groups per plane and chunk
     auto issueA = [&](int c, int ab) {
         const char* xs = xg + lo * (long)rowbytes + (PL2 ? (long)c * (BKB / 2) : (long)split_act_chunk<SPLIT>(c, npl) * BKB);
-        char* dst = img0 + ab * abytes;
-        if (CPT) {
-            // eight table entries first, then their DMAs: an LDS-DMA is an LDS write to the compiler, so a table read
-            // placed behind one waits for it -- piece by piece that was a chain of LDS latencies per chunk
-            for (int i0 = w; i0 < npieces; i0 += 8 * NW) {
-                uint32_t cell[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int i = i0 + k * NW;
-                    cell[k] = cell_tab[(i < npieces ? i : i0) * RPI + lrow];
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int i = i0 + k * NW;
-                    if (i < npieces) {
-                        const int row = i * RPI + lrow;
-                        const uint32_t sw = (uint32_t)((lslot ^ ((row / RPB) % LPR)) * 16);
-                        glds16(xs + (size_t)cell[k] * (size_t)rowbytes + sw, dst + i * 1024);
-                    }
-                }
-            }
-        } else {
-            for (int i = w; i < npieces; i += NW) {
-                const int row = i * RPI + lrow;
-                const uint32_t src = (uint32_t)(lslot ^ ((row / RPB) % LPR));     // 16-byte chunk of the row this slot holds
-                // PL2: the first LPR / 2 chunks come from the hi plane, the others from the lo plane (a.C halves further on)
-                const uint32_t off = (uint32_t)row * (uint32_t)rowbytes +
-                                     (PL2 ? (src % (LPR / 2)) * 16u + (src / (LPR / 2)) * (uint32_t)(a.C * 2) : src * 16u);
-                glds16(xs + off, dst + i * 1024);
-            }
+        char* dst = smem + ab * abytes;
+        for (int i = w; i < npieces; i += NW) {
+            const int row = i * RPI + lrow;
+            const uint32_t src = (uint32_t)(lslot ^ ((row / RPB) % LPR));     // 16-byte chunk of the row this slot holds
+            // PL2: the first LPR / 2 chunks come from the hi plane, the others from the lo plane (a.C halves further on)
+            const uint32_t off = (uint32_t)row * (uint32_t)rowbytes +
+                                 (PL2 ? (src % (LPR / 2)) * 16u + (src / (LPR / 2)) * (uint32_t)(a.C * 2) : src * 16u);
+            glds16(xs + off, dst + i * 1024);
         }
     };
     // filter fragments: [cout tile of 32][tap][k-group of 32 bytes][lane][16 B]
@@ -176,7 +119,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq_kernel(ConvArgs a, int
     const char* wbase[TC];                               // this lane's 16 bytes of the wave's cout tiles
 #pragma unroll
     for (int i = 0; i < TC; ++i)
-        wbase[i] = (const char*)a.w + ((size_t)(n0 / 32 + wc * TC + i) * TAPS * kgrow * 64 + lane) * 16;
+        wbase[i] = (const char*)a.w + ((size_t)(n0 / 32 + wc * TC + i) * 9 * kgrow * 64 + lane) * 16;
     static_assert(KG <= 4, "immediate offsets of the fragment loads");
     auto loadB = [&](int c, int t, u32x4 (&fb)[TC][KG]) {
         if constexpr (PL2) {      // k-groups c KGH .. of the hi plane, then the same of the lo plane (kgrow / 2 groups further on)
@@ -205,31 +148,22 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq_kernel(ConvArgs a, int
     const int kA = w < npieces ? (npieces - 1 - w) / NW + 1 : 0;   // LDS-DMA pieces this wave issues per issueA
 
     const int r32 = lane & 31, hh = lane >> 5;
-    int rowtlB[TP], fmk[TP];   // byte offset of the top-left tap's image row; CPT: which borders the pixel touches
+    int rowtlB[TP];            // byte offset of the top-left tap's image row
 #pragma unroll
     for (int j = 0; j < TP; ++j) {
         int p = m0 + (wp * TP + j) * 32 + r32;
         if (p > a.M - 1) p = a.M - 1;
-        if (CPT) {
-            const int rem = p % hw, h = rem / a.W, ww = rem - h * a.W;
-            fmk[j] = (ww == 0 ? 1 : 0) | (ww == a.W - 1 ? 2 : 0) | (h == 0 ? 4 : 0) | (h == a.H - 1 ? 8 : 0);
-            rowtlB[j] = (p - m0) * BKB;
-        } else {
-            fmk[j] = 0;
-            rowtlB[j] = (int)(bpos(pixq(p)) - pitch - 1 - lo) * BKB;
-        }
+        rowtlB[j] = (int)(bpos(pixq(p)) - pitch - 1 - lo) * BKB;
     }
-    // LDS byte offset (from smem) and swizzle key of every pixel fragment row for tap (kh_, kw_) of chunk cc.  A tap that
-    // leaves the image reads zero row (lambda & 15): the bank position of the cell the uniform shift points at
+    // LDS byte offset (from smem) and swizzle key of every pixel fragment row for tap (kh_, kw_) of chunk cc
     auto tap_addr = [&](int kh_, int kw_, int cc, int (&ao)[TP]) {
-        const int shiftB = (kh_ * (CPT ? a.W : pitch) + kw_) * BKB;
-        const int tapm = TAPS == 9 ? ((kw_ == 0 ? 1 : 0) | (kw_ == 2 ? 2 : 0) | (kh_ == 0 ? 4 : 0) | (kh_ == 2 ? 8 : 0)) : 0;
-        const int bufB = smem_lds + (CPT ? kZeroRows * BKB : 0) + (ADB ? (cc & 1) : 0) * abytes;
+        const int shiftB = (kh_ * pitch + kw_) * BKB;
+        const int bufB = smem_lds + (ADB ? (cc & 1) : 0) * abytes;
 #pragma unroll
         for (int j = 0; j < TP; ++j) {
             const int lamB = rowtlB[j] + shiftB;
             const int sw = (lamB >> 8) & (LPR - 1);              // (row / RPB) % LPR: RPB rows = one 256-byte bank row
-            const int rowB = (CPT && (fmk[j] & tapm)) ? smem_lds + (lamB & (15 * BKB)) : lamB + bufB;
+            const int rowB = lamB + bufB;
             // address of k-group 0; group g sits at this address ^ (g * 32): (2g + hh) ^ sw = (hh ^ sw) ^ 2g
             ao[j] = rowB + ((hh ^ sw) << 4);
         }
@@ -250,7 +184,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq_kernel(ConvArgs a, int
         nchunks = c_begin + per < nchunks ? c_begin + per : nchunks;
         if (c_begin > nchunks) c_begin = nchunks;
     }
-    const int steps = (nchunks - c_begin) * TAPS;
+    const int steps = (nchunks - c_begin) * 9;
     u32x4 fbq[2][TC][KG];
     int aoffq[2][TP];                          // fragment-row addresses of the current / the next tap step
     if (steps > 0) {
@@ -274,7 +208,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq_kernel(ConvArgs a, int
         // next step's filter fragments first (so they never queue behind an image), then the next image
         int tn = t + 1, cn = c, khn = kh, kwn = kw + 1;
         if (kwn == 3) { kwn = 0; ++khn; }
-        if (tn == TAPS) { tn = 0; ++cn; khn = 0; kwn = 0; }
+        if (tn == 9) { tn = 0; ++cn; khn = 0; kwn = 0; }
         const bool more = s + 1 < steps;
         if (more) loadB(cn, tn, fbq[P ^ 1]);
         const bool dma = ADB && t == 0 && c + 1 < nchunks;
@@ -348,7 +282,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq_kernel(ConvArgs a, int
             }
         }
         if (++kw == 3) { kw = 0; ++kh; }
-        if (++t == TAPS) { t = 0; kh = 0; kw = 0; ++c; }
+        if (++t == 9) { t = 0; kh = 0; kw = 0; ++c; }
     };
     for (int s = 0; s < steps; s += 2) {
         step(IntC<0>{}, s);
@@ -464,9 +398,8 @@ __global__ __launch_bounds__(256) void conv_ks_stats_kernel(ConvArgs a) {
 // plane products of its 32 channels on them (w_hi x_hi, w_hi x_lo, w_lo x_hi) instead of the K loop running three plane
 // passes: the hi plane is staged, read from LDS and its filter fragments fetched ONCE instead of twice (2/3 of the LDS-DMA
 // bytes, fragment reads, filter loads, tap steps and barriers per matrix instruction).
-template <typename T, int WP, int WC, int TP, int TC, int BKB, bool ADB, bool CPT, int TAPS, bool PL2 = false>
+template <typename T, int WP, int WC, int TP, int TC, int BKB, bool ADB, bool PL2 = false>
 __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, int arows) {
-    static_assert(TAPS == 9 || (TAPS == 1 && CPT), "1x1 filters run on the compact image (no halo, no border taps)");
     typedef typename Elem<T>::frag frag_t;
     typedef typename Types<T>::op_t OT;      // f16x2 mode: the operands are half planes of fp32-width rows (common.h)
     typedef typename Types<T>::out_t YT;
@@ -474,7 +407,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, i
     constexpr int NW = WP * WC, BP = WP * TP * 32, BC = WC * TC * 32, SZ = sizeof(T);
     constexpr int LPR = BKB / 16, RPI = 64 / LPR, RPB = 256 / BKB, KG = BKB / 64;   // k-groups of 64 bytes
     constexpr int TP16 = 2 * TP, TC16 = 2 * TC;
-    static_assert(!PL2 || (SPLIT && Types<T>::kPasses == 3 && BKB == 128 && !CPT), "the two-plane form: split operands, 128-byte image rows");
+    static_assert(!PL2 || (SPLIT && Types<T>::kPasses == 3 && BKB == 128), "the two-plane form: split operands, 128-byte image rows");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -495,67 +428,31 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, i
     // pooled layers in the inference fold (ConvArgs::aff_pool): the tile's positions are in window-major order
     auto pixq = [&](int q) -> int { return a.aff_pool ? pool_order_pixel(q, a.H, a.W) : q; };
     const int p_last = (m0 + BP - 1 < a.M) ? m0 + BP - 1 : a.M - 1;
-    const long lo = CPT ? 0 : bpos(pixq(m0)) - pitch - 1;
-    const int nrows = CPT ? arows : (int)(bpos(pixq(p_last)) + pitch + 1 - lo) + 1;
+    const long lo = bpos(pixq(m0)) - pitch - 1;
+    const int nrows = (int)(bpos(pixq(p_last)) + pitch + 1 - lo) + 1;
     const int npieces = (nrows + RPI - 1) / RPI;
     const int abytes = arows * BKB;
     const int rowbytes = a.C * SZ;
     const int npl = a.C * (int)sizeof(OT) / BKB;     // K chunks per operand plane (f16x2: three plane passes, common.h)
-    // compact image: [16 zero rows][image buffer(s): row lambda = pixel (m0 - W - 1 + lambda)][cell index per row]
-    char* const img0 = smem + (CPT ? kZeroRows * BKB : 0);
-    const uint32_t* const cell_tab = (const uint32_t*)(img0 + (ADB ? 2 : 1) * abytes);
-    if (CPT) {
-        uint32_t* tab = (uint32_t*)(img0 + (ADB ? 2 : 1) * abytes);
-        for (int r = tid; r < arows; r += NW * 64) {
-            int q = m0 - (TAPS == 9 ? a.W + 1 : 0) + r;
-            q = q < 0 ? 0 : (q > a.M - 1 ? a.M - 1 : q);      // rows outside the tensor are never read as image cells
-            tab[r] = (uint32_t)bpos(q);
-        }
-        for (int o = tid * 16; o < kZeroRows * BKB; o += NW * 64 * 16) *(u32x4*)(smem + o) = u32x4{0u, 0u, 0u, 0u};
-        __syncthreads();
-    }
-
     const int smem_lds = (int)(uintptr_t)(__attribute__((address_space(3))) char*)smem;   // LDS address of smem
     const int lrow = lane / LPR, lslot = lane % LPR;
     auto issueA = [&](int c, int ab) {
         const char* xs = xg + lo * (long)rowbytes + (PL2 ? (long)c * 64 : (long)split_act_chunk<SPLIT>(c, npl) * BKB);
-        char* dst = img0 + ab * abytes;
-        if (CPT) {
-            // eight table entries first, then their DMAs: an LDS-DMA is an LDS write to the compiler, so a table read
-            // placed behind one waits for it -- piece by piece that was a chain of LDS latencies per chunk
-            for (int i0 = w; i0 < npieces; i0 += 8 * NW) {
-                uint32_t cell[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int i = i0 + k * NW;
-                    cell[k] = cell_tab[(i < npieces ? i : i0) * RPI + lrow];
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int i = i0 + k * NW;
-                    if (i < npieces) {
-                        const int row = i * RPI + lrow;
-                        const uint32_t sw = (uint32_t)((lslot ^ ((row / RPB) % LPR)) * 16);
-                        glds16(xs + (size_t)cell[k] * (size_t)rowbytes + sw, dst + i * 1024);
-                    }
-                }
-            }
-        } else {
-            for (int i = w; i < npieces; i += NW) {
-                const int row = i * RPI + lrow;
-                const uint32_t src = (uint32_t)(lslot ^ ((row / RPB) % LPR));     // 16-byte chunk of the row this slot holds
-                // PL2: chunks 0-3 come from the hi plane, 4-7 from the lo plane (a.C halves further on)
-                const uint32_t off = (uint32_t)row * (uint32_t)rowbytes +
-                                     (PL2 ? (src & 3u) * 16u + (src >> 2) * (uint32_t)(a.C * 2) : src * 16u);
-                glds16(xs + off, dst + i * 1024);
-            }
+        char* dst = smem + ab * abytes;
+        for (int i = w; i < npieces; i += NW) {
+            const int row = i * RPI + lrow;
+            const uint32_t src = (uint32_t)(lslot ^ ((row / RPB) % LPR));     // 16-byte chunk of the row this slot holds
+            // PL2: chunks 0-3 come from the hi plane, 4-7 from the lo plane (a.C halves further on)
+            const uint32_t off = (uint32_t)row * (uint32_t)rowbytes +
+                                 (PL2 ? (src & 3u) * 16u + (src >> 2) * (uint32_t)(a.C * 2) : src * 16u);
+            glds16(xs + off, dst + i * 1024);
         }
     };
     const int kgrow = rowbytes / 64;                     // 64-byte k-groups per tap
     const char* wbase[TC16];                             // this lane's 16 bytes of the wave's cout tiles
 #pragma unroll
     for (int i = 0; i < TC16; ++i)
-        wbase[i] = (const char*)a.w + ((size_t)(n0 / 16 + wc * TC16 + i) * TAPS * kgrow * 64 + lane) * 16;
+        wbase[i] = (const char*)a.w + ((size_t)(n0 / 16 + wc * TC16 + i) * 9 * kgrow * 64 + lane) * 16;
     static_assert(KG <= 4, "immediate offsets of the fragment loads");
     auto loadB = [&](int c, int t, u32x4 (&fb)[TC16][KG]) {
         if constexpr (PL2) {      // k-group c of the hi plane and of the lo plane (kgrow / 2 groups further on)
@@ -582,32 +479,22 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, i
     const int kA = w < npieces ? (npieces - 1 - w) / NW + 1 : 0;   // LDS-DMA pieces this wave issues per issueA
 
     const int r16 = lane & 15, kc = lane >> 4;
-    const int c16 = CPT ? perm16(r16) : r16;      // pixel offset of this lane's MFMA column
-    int rowtlB[TP16], fmk[TP16];   // byte offset of the top-left tap's image row; CPT: which borders the pixel touches
+    int rowtlB[TP16];          // byte offset of the top-left tap's image row
 #pragma unroll
     for (int j = 0; j < TP16; ++j) {
-        int p = m0 + (wp * TP16 + j) * 16 + c16;
+        int p = m0 + (wp * TP16 + j) * 16 + r16;
         if (p > a.M - 1) p = a.M - 1;
-        if (CPT) {
-            const int rem = p % hw, h = rem / a.W, ww = rem - h * a.W;
-            fmk[j] = (ww == 0 ? 1 : 0) | (ww == a.W - 1 ? 2 : 0) | (h == 0 ? 4 : 0) | (h == a.H - 1 ? 8 : 0);
-            rowtlB[j] = (p - m0) * BKB;
-        } else {
-            fmk[j] = 0;
-            rowtlB[j] = (int)(bpos(pixq(p)) - pitch - 1 - lo) * BKB;
-        }
+        rowtlB[j] = (int)(bpos(pixq(p)) - pitch - 1 - lo) * BKB;
     }
-    // LDS byte offset (from smem) and swizzle key of every pixel fragment row for tap (kh_, kw_) of chunk cc.  A tap that
-    // leaves the image reads zero row (lambda & 15): the bank position of the cell the uniform shift points at
+    // LDS byte offset (from smem) and swizzle key of every pixel fragment row for tap (kh_, kw_) of chunk cc
     auto tap_addr = [&](int kh_, int kw_, int cc, int (&ao)[TP16]) {
-        const int shiftB = (kh_ * (CPT ? a.W : pitch) + kw_) * BKB;
-        const int tapm = TAPS == 9 ? ((kw_ == 0 ? 1 : 0) | (kw_ == 2 ? 2 : 0) | (kh_ == 0 ? 4 : 0) | (kh_ == 2 ? 8 : 0)) : 0;
-        const int bufB = smem_lds + (CPT ? kZeroRows * BKB : 0) + (ADB ? (cc & 1) : 0) * abytes;
+        const int shiftB = (kh_ * pitch + kw_) * BKB;
+        const int bufB = smem_lds + (ADB ? (cc & 1) : 0) * abytes;
 #pragma unroll
         for (int j = 0; j < TP16; ++j) {
             const int lamB = rowtlB[j] + shiftB;
             const int sw = (lamB >> 8) & (LPR - 1);              // (row / RPB) % LPR: RPB rows = one 256-byte bank row
-            const int rowB = (CPT && (fmk[j] & tapm)) ? smem_lds + (lamB & (15 * BKB)) : lamB + bufB;
+            const int rowB = lamB + bufB;
             // address of k-group 0; group g sits at this address ^ (g * 64): (4g + kc) ^ sw = (kc ^ sw) ^ 4g
             ao[j] = rowB + ((kc ^ sw) << 4);
         }
@@ -620,7 +507,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, i
         for (int j = 0; j < TP16; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int nchunks = PL2 ? a.C * (int)sizeof(OT) / 64 : Types<T>::kPasses * npl;
-    const int steps = nchunks * TAPS;
+    const int steps = nchunks * 9;
     u32x4 fbq[2][TC16][KG];
     int aoffq[2][TP16];                        // fragment-row addresses of the current / the next tap step
     issueA(0, 0);
@@ -641,7 +528,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, i
         }
         int tn = t + 1, cn = c, khn = kh, kwn = kw + 1;
         if (kwn == 3) { kwn = 0; ++khn; }
-        if (tn == TAPS) { tn = 0; ++cn; khn = 0; kwn = 0; }
+        if (tn == 9) { tn = 0; ++cn; khn = 0; kwn = 0; }
         const bool more = s + 1 < steps;
         if (more) loadB(cn, tn, fbq[P ^ 1]);
         const bool dma = ADB && t == 0 && c + 1 < nchunks;
@@ -705,7 +592,7 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, i
             }
         }
         if (++kw == 3) { kw = 0; ++kh; }
-        if (++t == TAPS) { t = 0; kh = 0; kw = 0; ++c; }
+        if (++t == 9) { t = 0; kh = 0; kw = 0; ++c; }
     };
     for (int s = 0; s < steps; s += 2) {
         step(IntC<0>{}, s);
@@ -730,69 +617,37 @@ __global__ __launch_bounds__(WP* WC * 64) void conv_haloq16_kernel(ConvArgs a, i
 #pragma unroll
                 for (int j = 0; j < TP16; ++j) acch[i][j] = acc[h * (TC16 / 2) + i][j];
             if (h) __syncthreads();      // pass 0's patch and the statistics scratch that aliases it are dead
-            conv_epilogue16<YT, WP, WC, TP, TC / 2, CPT, Types<T>::kBwF32>(a, acch, smem, w, lane, m0, n0, pt, ct, TC * 32, h * (TC / 2) * 32);
+            conv_epilogue16<YT, WP, WC, TP, TC / 2, Types<T>::kBwF32>(a, acch, smem, w, lane, m0, n0, pt, ct, TC * 32, h * (TC / 2) * 32);
         }
     } else {
-        conv_epilogue16<YT, WP, WC, TP, TC, CPT, Types<T>::kBwF32>(a, acc, smem, w, lane, m0, n0, pt, ct);
+        conv_epilogue16<YT, WP, WC, TP, TC, Types<T>::kBwF32>(a, acc, smem, w, lane, m0, n0, pt, ct);
     }
 }
 
-// compact image: pixels [m0 - W - 1, m0 + BP + W], rounded up to whole 16-row groups
-static int haloq_rows_compact(int W, int BP, int taps = 9) { return (BP + (taps == 9 ? 2 * W + 2 : 0) + 15) / 16 * 16; }
-static bool halo_compact() {
-    static const bool on = getenv("Y2_HALO_COMPACT") && atoi(getenv("Y2_HALO_COMPACT")) != 0;
-    return on;
-}
-// pool: the tile's pixels in window-major order (ConvArgs::aff_pool) -- a run of BP / 4 windows touches at most
-// ceil((Wo - 1 + BP / 4) / Wo) row pairs
-static int haloq_rows(int H, int W, int BP, int RPI, int pool = 0) {
-    if (pool) {
-        const int pitch = W + 1, Wo = W / 2, Ho = H / 2, nwin = BP / 4;
-        const int pairs = (nwin + 2 * Wo - 2) / Wo;
-        const int img_cross = (nwin - 1) / (Ho * Wo) + 1;
-        const int nrows = 2 * pairs * pitch + img_cross * pitch + 2 * (pitch + 1) + 1;
-        return (nrows + RPI - 1) / RPI * RPI;
-    }
-    const int pitch = W + 1;
-    const int rows_cross = (BP - 1) / W + 1;
-    const int img_cross = (BP - 1) / (H * W) + 1;
-    const int span = (BP - 1) + rows_cross + img_cross * pitch;
-    const int nrows = span + 2 * (pitch + 1) + 1;
-    return (nrows + RPI - 1) / RPI * RPI;
-}
-
-template <int BKB>
-static size_t haloq_lds(int arows, bool adb, bool cpt) {
-    return (size_t)(adb ? 2 : 1) * arows * BKB + (cpt ? (size_t)kZeroRows * BKB + (size_t)arows * 4 : 0);
-}
-template <typename T, int WP, int WC, int TP, int TC, int BKB, bool ADB, bool M16, bool CPT, int TAPS = 9>
-static hipError_t haloq_launch(const ConvArgs& a, hipStream_t s) {
+template <typename T, int WP, int WC, int TP, int TC, int BKB, bool ADB, bool M16>
+static hipError_t haloq_launch(const ConvArgs& a, int arows, hipStream_t s) {
     typedef typename Types<T>::out_t YT_;
     constexpr bool EPI2 = sizeof(YT_) == 4 && M16 && (TC % 2 == 0) && EpiCfg<YT_, WP, WC, TP, TC>::LDS > 160 * 1024;
     typedef EpiCfg<YT_, WP, WC, TP, EPI2 ? TC / 2 : TC> Epi;     // (EPI2: the epilogue runs in two passes, conv_haloq16_kernel)
-    constexpr int BP = WP * TP * 32, BC = WC * TC * 32, RPI = 64 / (BKB / 16);
-    if ((a.C * (int)sizeof(typename Types<T>::op_t)) % BKB != 0) return hipErrorInvalidValue;
-    const int arows = CPT ? haloq_rows_compact(a.W, BP, TAPS) : haloq_rows(a.H, a.W, BP, RPI, a.aff_pool);
-    if (CPT && a.aff_pool) return hipErrorInvalidValue;
-    if (CPT && arows > 0xFFFF) return hipErrorOutOfMemory;
-    size_t lds = haloq_lds<BKB>(arows, ADB, CPT);
+    constexpr int BP = WP * TP * 32, BC = WC * TC * 32;
+    size_t lds = (size_t)(ADB ? 2 : 1) * arows * BKB;
     if (lds < (size_t)Epi::LDS) lds = Epi::LDS;
-    if (lds > 160 * 1024) return hipErrorOutOfMemory;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;      // (plan_conv only picks tiles that fit)
     void (*kern)(ConvArgs, int);
     // f16x2 on the 16x16 tiles: both operand planes per K chunk (conv_haloq16_kernel PL2); Y2_NO_CONV_PL2=1: three plane passes
     static const bool no_pl2 = getenv("Y2_NO_CONV_PL2") != nullptr;
-    constexpr bool kPL2 = Types<T>::kPasses == 3 && M16 && BKB == 128 && !CPT && TAPS == 9;
+    constexpr bool kPL2 = Types<T>::kPasses == 3 && M16 && BKB == 128;
     bool pl2 = false;
     if constexpr (M16) {
-        kern = conv_haloq16_kernel<T, WP, WC, TP, TC, BKB, ADB, CPT, TAPS>;
+        kern = conv_haloq16_kernel<T, WP, WC, TP, TC, BKB, ADB>;
         if constexpr (kPL2) {
-            if (!no_pl2) { kern = conv_haloq16_kernel<T, WP, WC, TP, TC, BKB, ADB, CPT, TAPS, true>; pl2 = true; }
+            if (!no_pl2) { kern = conv_haloq16_kernel<T, WP, WC, TP, TC, BKB, ADB, true>; pl2 = true; }
         }
     } else {
-        kern = conv_haloq_kernel<T, WP, WC, TP, TC, BKB, ADB, CPT, TAPS>;
-        constexpr bool kPL2q = Types<T>::kPasses == 3 && !CPT && TAPS == 9 && (BKB == 128 || BKB == 64);
+        kern = conv_haloq_kernel<T, WP, WC, TP, TC, BKB, ADB>;
+        constexpr bool kPL2q = Types<T>::kPasses == 3 && (BKB == 128 || BKB == 64);
         if constexpr (kPL2q) {
-            if (!no_pl2) { kern = conv_haloq_kernel<T, WP, WC, TP, TC, BKB, ADB, CPT, TAPS, false, true>; pl2 = true; }
+            if (!no_pl2) { kern = conv_haloq_kernel<T, WP, WC, TP, TC, BKB, ADB, false, true>; pl2 = true; }
         }
     }
     static size_t attr[2] = {0, 0};
@@ -807,74 +662,17 @@ static hipError_t haloq_launch(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// double-buffer the image when there is more than one K-chunk and LDS allows it
 template <typename T, int WP, int WC, int TP, int TC, int BKB, bool M16 = false>
 static hipError_t haloq_pick(const ConvArgs& a, hipStream_t s) {
     constexpr int BP = WP * TP * 32, RPI = 64 / (BKB / 16);
+    if ((a.C * (int)sizeof(typename Types<T>::op_t)) % BKB != 0) return hipErrorInvalidValue;
     const int nchunks = a.C * (int)sizeof(typename Types<T>::op_t) / BKB * Types<T>::kPasses;
-    if (halo_compact()) {
-        const int arows = haloq_rows_compact(a.W, BP);
-        if (nchunks > 1 && haloq_lds<BKB>(arows, true, true) <= 150 * 1024)
-            return haloq_launch<T, WP, WC, TP, TC, BKB, true, M16, true>(a, s);
-        return haloq_launch<T, WP, WC, TP, TC, BKB, false, M16, true>(a, s);
-    }
-    const size_t arows = haloq_rows(a.H, a.W, BP, RPI, a.aff_pool);
-    if (nchunks > 1 && 2 * arows * BKB <= 150 * 1024) return haloq_launch<T, WP, WC, TP, TC, BKB, true, M16, false>(a, s);
-    return haloq_launch<T, WP, WC, TP, TC, BKB, false, M16, false>(a, s);
+    const int arows = halo_image_rows(a.H, a.W, BP, RPI, a.aff_pool);
+    if (nchunks > 1 && 2 * (size_t)arows * BKB <= 150 * 1024) return haloq_launch<T, WP, WC, TP, TC, BKB, true, M16>(a, arows, s);
+    return haloq_launch<T, WP, WC, TP, TC, BKB, false, M16>(a, arows, s);
 }
 
-// 1x1 filters (round 3, Y2_HALOQ_1X1=1 -- built, measured, NOT the default): the same kernels with ONE tap per K-chunk on
-// the compact image (rows = the tile's pixels, no halo, no border taps, conflict-free); the pixel tile crosses LDS once
-// per cout tile, the filter fragments come straight from L2: 131 FLOP per staged byte (384 x 128 tile) against 65 of
-// conv_igemm's 128 x 128 tiles.  MEASURED against conv_igemm on the same box (C4 shapes, fwd / dgrad us): 52x52 256->128
-// 41.5 / 70.2 vs 42.3 / 63.9; 26x26 512->256 29.7 / 44.7 vs 31.5 / 42.2; 13x13 1024->512 30.8 / 31.6 vs 27.8 / 35.3 --
-// a wash: with one tap per chunk every 0.4-us step waits for its own 48-KB image piece (the nine-tap loop had nine steps
-// to hide it), and at 13x13 the 384 x 64 tiles that fill the chip halve the reuse again.  These layers are bound by
-// the per-CU global->LDS fill rate and by M (10,816 pixels): the fix is a K split across workgroups, not another tile.
-template <typename T, int WP, int WC, int TP, int TC, bool M16>
-static hipError_t haloq_pick1(const ConvArgs& a, hipStream_t s) {
-    constexpr int BP = WP * TP * 32, BKB = 128;
-    const int nchunks = a.C * (int)sizeof(T) / BKB;
-    const int arows = haloq_rows_compact(a.W, BP, 1);
-    if (nchunks > 1 && haloq_lds<BKB>(arows, true, true) <= 150 * 1024)
-        return haloq_launch<T, WP, WC, TP, TC, BKB, true, M16, true, 1>(a, s);
-    return haloq_launch<T, WP, WC, TP, TC, BKB, false, M16, true, 1>(a, s);
-}
-template <typename T>
-static hipError_t haloq_T1(const ConvArgs& a, hipStream_t s, int* bp) {
-    const int kb = a.C * (int)sizeof(T);
-    if ((kb % 128) != 0 || a.Cout <= 64) return hipErrorInvalidValue;
-    *bp = 384;
-    if (conv_filter_layout(1, a.W, kb, a.Cout, a.M, a.is_dgrad, (int)sizeof(T)) == 2) {
-        if (sizeof(T) == 4) {     // the f32 epilogue patch of a 384 x 128 tile does not fit LDS
-            *bp = 256;
-            return haloq_pick1<T, 4, 2, 2, 2, true>(a, s);
-        }
-        return haloq_pick1<T, 4, 2, 3, 2, true>(a, s);
-    }
-    return haloq_pick1<T, 4, 2, 3, 1, false>(a, s);
-}
-
-// K split of a small launch (see conv_haloq_kernel<.., KS>): fewer than 128 workgroups of the 256 x 64 tile and at least
-// four 128-byte K chunks; the depth fills ~one round of the chip.  hipErrorNotSupported: not this form.
-static int haloq_ks_depth(int M, int Cout, int nchunks) {
-    static const bool off = getenv("Y2_NO_KSPLIT") != nullptr;
-    const int wgs = ((M + 255) / 256) * ((Cout + 63) / 64);
-    if (off || wgs >= 128 || nchunks < 4) return 1;
-    int d = 256 / wgs;
-    d = d > 8 ? 8 : d;
-    d = d > nchunks / 2 ? nchunks / 2 : d;
-    return d < 2 ? 1 : d;
-}
-int conv_igemm_ks_depth(int M, int Cout, int row_bytes);      // conv_igemm.hip: the 1x1 launches' K split (round 6)
-int conv_ks_depth(int taps, int M, int Cout, int row_bytes) {
-    if (taps == 1) return conv_igemm_ks_depth(M, Cout, row_bytes);
-    if (taps != 9 || M >= 384 * 8 || (row_bytes % 128) != 0 || Cout <= 64 || halo_compact()) return 1;
-    return haloq_ks_depth(M, Cout, row_bytes / 128);
-}
-size_t conv_ks_scratch_floats(int taps, int M, int ldy, int row_bytes) {
-    if ((taps != 9 && taps != 1) || M >= 384 * 8 || (row_bytes % 128) != 0 || ldy <= 64) return 0;
-    return (size_t)8 * M * ldy;
-}
 // partial tiles -> result (+ statistics records of 128 pixels) of a K-split launch of either kernel family
 template <typename T>
 static hipError_t ks_finish_T(const ConvArgs& a, int depth, hipStream_t s) {
@@ -892,23 +690,21 @@ hipError_t launch_conv_ks_finish(int dtype, const ConvArgs& a, int depth, hipStr
     }
     return hipErrorInvalidValue;
 }
+// K split of a small launch (see conv_haloq_kernel<.., KS>) on the 256 x 64 tile: ks_depth workgroups per tile
 template <typename T>
-static hipError_t haloq_ks(const ConvArgs& a0, hipStream_t s, int* bp) {
+static hipError_t haloq_ks(const ConvPlan& p, const ConvArgs& a0, hipStream_t s) {
     constexpr int WP = 4, WC = 2, TP = 2, TC = 1, BKB = 128, BP = WP * TP * 32, BC = WC * TC * 32, RPI = 64 / (BKB / 16);
-    const int nchunks = a0.C * (int)sizeof(T) / BKB;
-    int depth = haloq_ks_depth(a0.M, a0.Cout, nchunks);
-    if (depth < 2 || !a0.ks_scratch || a0.bw_psum || a0.nonfinite || halo_compact() || (a0.ldy % 4) != 0)
-        return hipErrorNotSupported;
-    while (depth > 1 && (size_t)depth * a0.M * a0.ldy > a0.ks_floats) --depth;
-    if (depth < 2) return hipErrorNotSupported;
+    const int depth = p.ks_depth;
+    if (p.cfg != conv_tile(WP, WC, TP, TC, BKB, 0) || depth < 2 || (a0.C * (int)sizeof(T)) % BKB != 0) return hipErrorInvalidValue;
     ConvArgs a = a0;
     a.ks_splits = depth;
-    const int arows = haloq_rows(a.H, a.W, BP, RPI);
+    const int nchunks = a.C * (int)sizeof(T) / BKB;
+    const int arows = halo_image_rows(a.H, a.W, BP, RPI);
     const bool adb = (nchunks + depth - 1) / depth > 1 && 2 * (size_t)arows * BKB <= 150 * 1024;
-    const size_t lds = haloq_lds<BKB>(arows, adb, false);
-    if (lds > 160 * 1024) return hipErrorNotSupported;
-    void (*kern)(ConvArgs, int) = adb ? conv_haloq_kernel<T, WP, WC, TP, TC, BKB, true, false, 9, true>
-                                      : conv_haloq_kernel<T, WP, WC, TP, TC, BKB, false, false, 9, true>;
+    const size_t lds = (size_t)(adb ? 2 : 1) * arows * BKB;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    void (*kern)(ConvArgs, int) = adb ? conv_haloq_kernel<T, WP, WC, TP, TC, BKB, true, true>
+                                      : conv_haloq_kernel<T, WP, WC, TP, TC, BKB, false, true>;
     static size_t attr[2] = {0, 0};
     if (lds > attr[adb]) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -917,117 +713,53 @@ static hipError_t haloq_ks(const ConvArgs& a0, hipStream_t s, int* bp) {
     }
     const int tiles = ((a.M + BP - 1) / BP) * ((a.Cout + BC - 1) / BC);
     hipLaunchKernelGGL(kern, dim3(tiles * depth), dim3(WP * WC * 64), lds, s, a, arows);
-    const long quads = (long)a.M * (a.ldy / 4);
-    hipLaunchKernelGGL(conv_ks_finish_kernel<T>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a, depth);
-    if (a.part_mean && !a.aff_out)
-        hipLaunchKernelGGL(conv_ks_stats_kernel<T>, dim3((a.ldy + 63) / 64, (a.M + kKsRec - 1) / kKsRec), dim3(256), 0, s, a);
-    *bp = kKsRec;    // batch-norm records of the launch (launch_conv: records = ceil(M / bp))
-    return hipGetLastError();
+    return ks_finish_T<T>(a, depth, s);
 }
 
+// the tiles plan_conv picks from (conv_halo.hip haloq_tile)
 template <typename T>
-static hipError_t haloq_T(const ConvArgs& a, hipStream_t s, int* bp) {
-    typedef typename Types<T>::out_t YT;        // the epilogue patch is sized by what is stored
-    const int kb = a.C * (int)sizeof(typename Types<T>::op_t);      // bytes of one operand plane per pixel
-    const bool k128 = (kb % 128) == 0;
-    if (!k128 && (kb % 64) != 0) return hipErrorInvalidValue;
-    if (a.W > 52) {
-        // long rows (104, 208): 512-pixel tiles amortise the two-row halo; one K-chunk per tile where it fits
-        hipError_t e = hipErrorOutOfMemory;
-        if (a.Cout > 64) {
-            *bp = 256;
-            // (split-operand forward, round 6: the fp32 epilogue patch sizes the LDS either way, so the two-plane form takes
-            //  128-byte chunks -- 32 channels of both planes, half the tap steps of the 64-byte form; Y2_HALOQ_104_K64=1: A/B)
-            static const bool k64 = getenv("Y2_HALOQ_104_K64") != nullptr;
-            // (the hi-plane dgrads of f16x2f keep the 64-byte chunks: one 128-byte chunk is their whole K -- no second image to
-            //  load behind the first -- and measured 216 against 200 us)
-            if (Types<T>::kPasses == 3 && k128 && !k64) e = haloq_pick<T, 4, 2, 2, 2, 128>(a, s);
-            else e = haloq_pick<T, 4, 2, 2, 2, 64>(a, s);
-        } else if (a.Cout > 32) {
-            *bp = 512;
-            // (64-byte K chunks here, so that the 512-pixel image at W = 104 can be double-buffered, measured 12 %
-            //  SLOWER than the single-buffered 128-byte ones: half the MFMAs per tap step for the same step overhead)
-            e = k128 ? haloq_pick<T, 4, 2, 4, 1, 128>(a, s) : haloq_pick<T, 4, 2, 4, 1, 64>(a, s);
-        } else {
-            *bp = 512;
-            e = k128 ? haloq_pick<T, 8, 1, 2, 1, 128>(a, s) : haloq_pick<T, 8, 1, 2, 1, 64>(a, s);
-        }
-        if (e != hipErrorOutOfMemory) return e;
-        (void)hipGetLastError();
-    }
-    if (a.Cout > 64) {
-        hipError_t e = hipErrorOutOfMemory;
-        const int tile = haloq_tile_choice(a.W, kb, a.Cout, a.M, Types<T>::kSplit ? 6 : (int)sizeof(YT));
-        if (tile != HQ_NONE) {
-            // the tile (and with it the filter pack: 16-row fragments for the _M16 kernels, 32-row ones otherwise) is
-            // decided by ONE function for bind and launch time (conv_halo.hip haloq_tile_choice).  (Round 2 fell through
-            // to a 32x32-tile kernel on the 16-row pack in the f32 mode -- wrong outputs from batch 24 up at 416x416.)
-            switch (tile) {
-                case HQ_384x128_M16:
-                    *bp = 384;       // (fp32 outputs: the epilogue runs in two passes, conv_haloq16_kernel EPI2)
-                    return haloq_pick<T, 4, 2, 3, 2, 128, true>(a, s);
-                case HQ_256x128_M16: *bp = 256; return haloq_pick<T, 4, 2, 2, 2, 128, true>(a, s);
-                case HQ_384x64: *bp = 384; return haloq_pick<T, 4, 2, 3, 1, 128>(a, s);
-                case HQ_512x128:
-                    if constexpr (sizeof(YT) == 2) { *bp = 512; return haloq_pick<T, 4, 2, 4, 2, 128>(a, s); }
-                    return hipErrorInvalidValue;
-                case HQ_256x128: *bp = 256; return haloq_pick<T, 4, 2, 2, 2, 128>(a, s);
-                case HQ_512x64: *bp = 512; return haloq_pick<T, 4, 2, 4, 1, 128>(a, s);
-                case HQ_256x64: *bp = 256; return haloq_pick<T, 4, 2, 2, 1, 128>(a, s);
-            }
+static hipError_t haloq_run(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    if constexpr (!Types<T>::kSplit)
+        if (p.kind == CK_HALOQ_KS) return haloq_ks<T>(p, a, s);
+    if (p.kind != CK_HALOQ) return hipErrorInvalidValue;
+#define HQ(WP, WC, TP, TC, BKB, M16) \
+    case conv_tile(WP, WC, TP, TC, BKB, M16): return haloq_pick<T, WP, WC, TP, TC, BKB, M16>(a, s);
+    switch (p.cfg) {
+        HQ(4, 2, 3, 2, 128, 1)      // 16x16 MFMA tiles (fp32 outputs: the epilogue runs in two passes, EPI2)
+        HQ(4, 2, 2, 2, 128, 1)
+        HQ(4, 2, 3, 1, 128, 0)
+        HQ(4, 2, 2, 2, 128, 0)
+        HQ(4, 2, 2, 2, 64, 0)
+        HQ(4, 2, 4, 1, 128, 0)
+        HQ(4, 2, 4, 1, 64, 0)
+        HQ(4, 2, 2, 1, 128, 0)
+        HQ(4, 2, 3, 2, 128, 0)
+        HQ(4, 2, 3, 2, 64, 0)
+        HQ(8, 1, 2, 1, 128, 0)
+        HQ(8, 1, 2, 1, 64, 0)
+        HQ(2, 2, 2, 2, 64, 0)
+        HQ(4, 1, 2, 2, 128, 0)
+        HQ(4, 1, 2, 2, 64, 0)
+        HQ(4, 1, 2, 1, 128, 0)
+        HQ(4, 1, 2, 1, 64, 0)
+        case conv_tile(4, 2, 4, 2, 128, 0):      // 16-bit outputs only (the patch of the fp32 ones does not fit LDS)
+            if constexpr (sizeof(typename Types<T>::out_t) == 2) return haloq_pick<T, 4, 2, 4, 2, 128>(a, s);
             return hipErrorInvalidValue;
-        }
-        // Fewer than 3072 pixels (the reference's own training shape, 224x224 at batch 24: 1176 on the 7x7 maps; single
-        // images: 49): the launch is a stream of the FILTERS through a few workgroups, each bound by its serial K loop
-        // (~110 ns per tap step: 72 us for K = 9216 whatever the tile).  64-cout tiles double the workgroups of the 128 x 128
-        // form of rounds 1-3 on the same fragment pack: 7x7 1024 -> 1024 at batch 24 148 -> 81 us, one image 147 -> 72
-        // (profiles/r04_sweep_small_m.txt; 128 x 64, 256 x 32 and 256 x 64 tie -- what is left there is a K split)
-        if (k128 && a.M < 384 * 8) {
-            if constexpr (!Types<T>::kSplit) {
-                const hipError_t e = haloq_ks<T>(a, s, bp);
-                if (e != hipErrorNotSupported) return e;
-            }
-            *bp = 256;
-            return haloq_pick<T, 4, 2, 2, 1, 128>(a, s);
-        }
-        if (a.M >= 384 * 8) {   // what the cost model does not cover (64-byte K chunks; long rows that did not fit above)
-            *bp = 384;
-            e = k128 ? haloq_pick<T, 4, 2, 3, 2, 128>(a, s) : haloq_pick<T, 4, 2, 3, 2, 64>(a, s);
-        } else if (a.M >= 256 * 8) {
-            *bp = 256;
-            e = k128 ? haloq_pick<T, 4, 2, 2, 2, 128>(a, s) : haloq_pick<T, 4, 2, 2, 2, 64>(a, s);
-        }
-        if (e != hipErrorOutOfMemory) return e;
-        (void)hipGetLastError();
-        *bp = 128;
-        return haloq_pick<T, 2, 2, 2, 2, 64>(a, s);
-    } else if (a.Cout > 32) {
-        *bp = 256;
-        return k128 ? haloq_pick<T, 4, 1, 2, 2, 128>(a, s) : haloq_pick<T, 4, 1, 2, 2, 64>(a, s);
-    } else {
-        *bp = 256;
-        return k128 ? haloq_pick<T, 4, 1, 2, 1, 128>(a, s) : haloq_pick<T, 4, 1, 2, 1, 64>(a, s);
     }
+#undef HQ
+    return hipErrorInvalidValue;
 }
 
 // filters must be packed in fragment order (pack.hip, PackLayer::wf_frag / wd_frag)
-hipError_t launch_conv_haloq(int dtype, const ConvArgs& a, hipStream_t s, int* bp) {
-    if (a.taps == 1) {
-        switch (dtype) {
-            case 0: return haloq_T1<float>(a, s, bp);
-            case 1: return haloq_T1<half_t>(a, s, bp);
-            case 2: return haloq_T1<bf16_t>(a, s, bp);
-        }
-        return hipErrorInvalidValue;
-    }
+hipError_t launch_conv_haloq(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
     if (a.taps != 9) return hipErrorInvalidValue;
     switch (dtype) {
-        case 0: return haloq_T<float>(a, s, bp);
-        case 1: return haloq_T<half_t>(a, s, bp);
-        case 2: return haloq_T<bf16_t>(a, s, bp);
-        case 3: return haloq_T<hsplit_t>(a, s, bp);
-        case 4: return haloq_T<hsplith_t>(a, s, bp);     // f16x2f backward launches: the hi planes of split tensors
-        case 5: return haloq_T<hsplithh_t>(a, s, bp);    // ... with dA stored in f16 (common.h hsplithh_t)
+        case 0: return haloq_run<float>(p, a, s);
+        case 1: return haloq_run<half_t>(p, a, s);
+        case 2: return haloq_run<bf16_t>(p, a, s);
+        case 3: return haloq_run<hsplit_t>(p, a, s);
+        case 4: return haloq_run<hsplith_t>(p, a, s);     // f16x2f backward launches: the hi planes of split tensors
+        case 5: return haloq_run<hsplithh_t>(p, a, s);    // ... with dA stored in f16 (common.h hsplithh_t)
     }
     return hipErrorInvalidValue;
 }

@@ -311,33 +311,14 @@ static hipError_t launch_cfg(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// K split of a small 1x1 launch (conv_igemm_kernel<.., KS>): fewer than 48 workgroups of the 128 x 128 tile (single images,
-// the reference's batch 24 at 7x7: 40) and at least four K steps; the depth fills about one round of the chip.  < 2: not this
-// form.  (Measured: at 52 .. 208 workgroups -- the ResNet swap's 7x7 units at batch 32 -- the split is neutral to slightly
-// negative: its partial tiles and the two extra launches cost what the shorter K loops save; configs[0] gains 2.5 %.)
-static int igemm_ks_depth(int M, int Cout, int nK) {
-    static const bool off = getenv("Y2_NO_KSPLIT") != nullptr;
-    const int wgs = ((M + 127) / 128) * ((Cout + 127) / 128);
-    if (off || wgs >= 48 || nK < 4) return 1;
-    int d = 256 / wgs;
-    d = d > 8 ? 8 : d;
-    d = d > nK / 2 ? nK / 2 : d;
-    return d < 2 ? 1 : d;
-}
-int conv_igemm_ks_depth(int M, int Cout, int row_bytes) {
-    if (M >= 384 * 8 || (row_bytes % 128) != 0 || Cout <= 64) return 1;
-    return igemm_ks_depth(M, Cout, row_bytes / 128);
-}
 hipError_t launch_conv_ks_finish(int dtype, const ConvArgs& a, int depth, hipStream_t s);      // conv_haloq.hip
 
+// K split of a small 1x1 launch (conv_igemm_kernel<.., KS>) on the 128 x 128 tile: ks_depth workgroups per tile
 template <typename T>
-static hipError_t launch_ks(const ConvArgs& a0, hipStream_t s, int dtype) {
+static hipError_t launch_ks(const ConvPlan& p, const ConvArgs& a0, hipStream_t s, int dtype) {
     typedef ConvCfg<T, 2, 4, 2, 1, 128, 2> Cfg;
-    const int nK = a0.C * (int)sizeof(T) / 128;
-    int depth = igemm_ks_depth(a0.M, a0.Cout, nK);
-    if (depth < 2 || !a0.ks_scratch || a0.bw_psum || a0.nonfinite || (a0.ldy % 4) != 0) return hipErrorNotSupported;
-    while (depth > 1 && (size_t)depth * a0.M * a0.ldy > a0.ks_floats) --depth;
-    if (depth < 2) return hipErrorNotSupported;
+    const int depth = p.ks_depth;
+    if (p.cfg != conv_tile(2, 4, 2, 1, 128, 2) || depth < 2 || (a0.C * (int)sizeof(T)) % 128 != 0) return hipErrorInvalidValue;
     ConvArgs a = a0;
     a.ks_splits = depth;
     void (*kern)(ConvArgs) = conv_igemm_kernel<T, 2, 4, 2, 1, 128, 2, 0, false, true>;
@@ -353,57 +334,46 @@ static hipError_t launch_ks(const ConvArgs& a0, hipStream_t s, int dtype) {
     return e != hipSuccess ? e : launch_conv_ks_finish(dtype, a, depth, s);
 }
 
-// tile choice by output-channel count; rows-per-partial (BP) is reported back
+// the tiles plan_conv picks from (conv_halo.hip igemm_tile)
 template <typename T>
-static hipError_t launch_T(const ConvArgs& a, hipStream_t s) {
-    const int kb = a.C * (int)sizeof(typename Types<T>::op_t);  // bytes per tap per pixel (of one operand plane)
-    bool k128 = (kb % 128) == 0;
-    if (!k128 && (kb % 64) != 0) return hipErrorInvalidValue;
-    // round 6: a two-plane (PL2) chunk of 128 bytes is [64 B hi | 64 B lo] = 32 channels of BOTH planes, so the 32-channel
-    // layer of the split-operand forward (208x208 32 -> 64) takes ONE K step per tap instead of two of half the depth -- half
-    // the barriers and stage waits per matrix instruction.  Y2_IGEMM_PL2_64=1 restores the 64-byte chunks (A/B).
-    if constexpr (Types<T>::kPasses == 3) {
-        static const bool no_pl2 = getenv("Y2_NO_CONV_PL2") != nullptr, keep64 = getenv("Y2_IGEMM_PL2_64") != nullptr;
-        if (!no_pl2 && !keep64 && kb == 64) k128 = true;
+static hipError_t igemm_run(int cfg, const ConvArgs& a, hipStream_t s) {
+    if ((a.C * (int)sizeof(typename Types<T>::op_t)) % 64 != 0) return hipErrorInvalidValue;
+#define IG(WP, WC, TP, TC, BKB, NS) \
+    case conv_tile(WP, WC, TP, TC, BKB, NS): return launch_cfg<T, WP, WC, TP, TC, BKB, NS>(a, s);
+    switch (cfg) {
+        IG(2, 4, 2, 1, 128, 2)
+        IG(2, 4, 2, 1, 64, 2)
+        IG(4, 1, 2, 2, 128, 2)
+        IG(4, 1, 2, 2, 64, 2)
+        IG(4, 1, 2, 1, 128, 2)
+        IG(4, 1, 2, 1, 64, 2)
+        case conv_tile(2, 4, 2, 1, 128, 3):      // three-stage ring of the launches of at most one workgroup per CU
+            if constexpr (!Types<T>::kSplit) return launch_cfg<T, 2, 4, 2, 1, 128, 3>(a, s);
+            return hipErrorInvalidValue;
     }
-    // 2 LDS stages and two blocks per CU beat deeper rings here (global->LDS fill rate, not
-    // latency, bounds this kernel); 8 waves of 64x32 beat 4 waves of 64x64 by ~5-8 %
-    if (a.Cout > 64) {
-        // round 6: launches of at most one workgroup per CU have nobody to hide a stage's latency behind -- a ring of three
-        // stages keeps two K steps in flight (LDS is free at one workgroup per CU).  Same box, alternating: the ResNet swap's
-        // step 9.90 / 10.00 -> 9.66 / 9.82 ms (its 14x14 / 7x7 units and the 28x28 ones with 128 couts), configs[2] 4.47 -> 4.45;
-        // four stages 9.89 / 9.83.  No configs[3] launch has so few workgroups.  Y2_IGEMM_DEEP=2 | 4: A/B.
-        if constexpr (!Types<T>::kSplit) {
-            static const int deep = getenv("Y2_IGEMM_DEEP") ? atoi(getenv("Y2_IGEMM_DEEP")) : 3;
-            const long wgs = (long)((a.M + 127) / 128) * ((a.Cout + 127) / 128);
-            if (k128 && deep >= 3 && wgs <= 256)
-                return deep >= 4 ? launch_cfg<T, 2, 4, 2, 1, 128, 4>(a, s) : launch_cfg<T, 2, 4, 2, 1, 128, 3>(a, s);
-        }
-        return k128 ? launch_cfg<T, 2, 4, 2, 1, 128, 2>(a, s) : launch_cfg<T, 2, 4, 2, 1, 64, 2>(a, s);
-    } else if (a.Cout > 32) {
-        return k128 ? launch_cfg<T, 4, 1, 2, 2, 128, 2>(a, s) : launch_cfg<T, 4, 1, 2, 2, 64, 2>(a, s);
-    } else {
-        return k128 ? launch_cfg<T, 4, 1, 2, 1, 128, 2>(a, s) : launch_cfg<T, 4, 1, 2, 1, 64, 2>(a, s);
-    }
+#undef IG
+    return hipErrorInvalidValue;
 }
 
-int conv_block_pixels(int Cout) { return Cout > 64 ? 128 : 256; }
 int conv_block_couts(int Cout) { return Cout > 64 ? 128 : (Cout > 32 ? 64 : 32); }
 
-hipError_t launch_conv_igemm(int dtype, const ConvArgs& a, hipStream_t s) {
+hipError_t launch_conv_igemm(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    if (p.kind == CK_IGEMM_KS) {
+        switch (dtype) {
+            case 0: return launch_ks<float>(p, a, s, dtype);
+            case 1: return launch_ks<half_t>(p, a, s, dtype);
+            case 2: return launch_ks<bf16_t>(p, a, s, dtype);
+        }
+        return hipErrorInvalidValue;
+    }
+    if (p.kind != CK_IGEMM) return hipErrorInvalidValue;
     switch (dtype) {
-        case 0: case 1: case 2:
-            // small 1x1 launches: K split over workgroups (the batch-norm records of that form cover 128 pixels each, the
-            // default record size of this kernel's 128-cout tiles: launch_conv's record count does not change)
-            if (a.taps == 1 && conv_igemm_ks_depth(a.M, a.Cout, a.C * (int)dtype_size(dtype)) >= 2) {
-                const hipError_t e = dtype == 0 ? launch_ks<float>(a, s, dtype)
-                                                : (dtype == 1 ? launch_ks<half_t>(a, s, dtype) : launch_ks<bf16_t>(a, s, dtype));
-                if (e != hipErrorNotSupported) return e;
-            }
-            return dtype == 0 ? launch_T<float>(a, s) : (dtype == 1 ? launch_T<half_t>(a, s) : launch_T<bf16_t>(a, s));
-        case 3: return launch_T<hsplit_t>(a, s);
-        case 4: return launch_T<hsplith_t>(a, s);        // f16x2f backward launches: the hi planes of split tensors
-        case 5: return launch_T<hsplithh_t>(a, s);       // ... with dA stored in f16 (common.h hsplithh_t)
+        case 0: return igemm_run<float>(p.cfg, a, s);
+        case 1: return igemm_run<half_t>(p.cfg, a, s);
+        case 2: return igemm_run<bf16_t>(p.cfg, a, s);
+        case 3: return igemm_run<hsplit_t>(p.cfg, a, s);
+        case 4: return igemm_run<hsplith_t>(p.cfg, a, s);      // f16x2f backward launches: the hi planes of split tensors
+        case 5: return igemm_run<hsplithh_t>(p.cfg, a, s);     // ... with dA stored in f16 (common.h hsplithh_t)
     }
     return hipErrorInvalidValue;
 }

@@ -807,25 +807,6 @@ static hipError_t rfn_launch(const ConvArgs& a, hipStream_t s, int* bp, int* rec
     return hipGetLastError();
 }
 
-// 0: not this form (16-bit launches only: row_bytes = input channels * 2).
-//   1: 32 -> 64 on 208-wide maps (forward of the second layer)      8 waves x 32 pixels x 64 couts, one workgroup per CU
-//   2: 64 -> 32 on 208-wide maps (its dgrad)                        8 waves x 32 pixels x 32 couts, one workgroup per CU
-int conv_rf_config(int taps, int W, int row_bytes, int Cout, int M) {
-    static const bool off = getenv("Y2_NO_CONV_RF") != nullptr;
-    if (off || taps != 9 || W <= 104 || W + 2 >= 256 || M < 256 * 1024) return 0;
-    if (row_bytes == 64 && Cout > 32 && Cout <= 64) return 1;
-    if (row_bytes == 128 && Cout <= 32) return 2;
-    return 0;
-}
-// the 128-cout form: forward (with statistics), plain, and dgrad with the fused BN-backward reduce
-int conv_rfn_config(int taps, int W, int row_bytes, int Cout, int M, int dgrad) {
-    static const bool off = getenv("Y2_NO_CONV_RF") != nullptr;
-    static const bool nodg = getenv("Y2_NO_CONV_RFN_DGRAD") != nullptr;
-    if (off || (dgrad && nodg) || taps != 9 || W <= 52 || W + 2 > 128 || M < 128 * 1024) return 0;
-    if (row_bytes == 128 && Cout > 64 && Cout <= 128) return 3;
-    return 0;
-}
-
 template <typename T>
 static hipError_t rf_T(int cfg, const ConvArgs& a, hipStream_t s, int* bp, int* records) {
     // measured (scripts/profile_layers.py): the lead of the fragment reads (1..4 steps) does not matter -- two waves
@@ -840,11 +821,11 @@ static hipError_t rf_T(int cfg, const ConvArgs& a, hipStream_t s, int* bp, int* 
     if (cfg == 3) return rfn_launch<T, 64, 2, 4, 2, 2, 4, 1>(a, s, bp, records);
     return hipErrorInvalidValue;
 }
-hipError_t launch_conv_rf(int dtype, const ConvArgs& a, hipStream_t s, int* bp, int* records) {
-    int cfg = conv_rf_config(a.taps, a.W, a.C * (int)dtype_size(dtype), a.Cout, a.M);
-    if (!cfg) cfg = conv_rfn_config(a.taps, a.W, a.C * (int)dtype_size(dtype), a.Cout, a.M, a.is_dgrad);
-    if (dtype == 1) return rf_T<half_t>(cfg, a, s, bp, records);
-    if (dtype == 2) return rf_T<bf16_t>(cfg, a, s, bp, records);
+// the configs of plan_conv (conv_halo.hip rf_config / rfn_config)
+hipError_t launch_conv_rf(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* bp, int* records) {
+    if (p.kind != (p.cfg == 3 ? CK_RFN : CK_RF)) return hipErrorInvalidValue;
+    if (dtype == 1) return rf_T<half_t>(p.cfg, a, s, bp, records);
+    if (dtype == 2) return rf_T<bf16_t>(p.cfg, a, s, bp, records);
     return hipErrorInvalidValue;
 }
 

@@ -63,15 +63,13 @@ struct ConvArgs {
     // + shift) at the pooled position of aff_out [N][H/2+2][W/2+2][ldy]: bn_act_kernel's pool_window arithmetic
     int aff_pool = 0;
     // K split over workgroups for launches of a few hundred to a few thousand pixels (conv_haloq.hip: haloq_ks): the
-    // caller lends ks_floats floats of scratch; the launcher decides whether and how deep to split (ks_splits is its own)
+    // caller lends ks_floats floats of scratch; plan_conv decides whether and how deep to split (ks_splits: the launcher's)
     float* ks_scratch = nullptr;
     size_t ks_floats = 0;
     int ks_splits = 0;
 };
 // scratch floats a launch of M pixels x ldy couts may ask for (0: the K split never applies)
 size_t conv_ks_scratch_floats(int taps, int M, int ldy, int row_bytes);
-// split depth a launch of this shape takes when it is lent scratch (< 2: it runs un-split)
-int conv_ks_depth(int taps, int M, int Cout, int row_bytes);
 inline void conv_div_magic(uint32_t d, uint32_t* mag, int* sh) {
     int l = 0;
     while ((1u << l) < d) ++l;                    // ceil(log2 d)
@@ -87,28 +85,49 @@ inline void conv_set_affine(ConvArgs& a, const float* scale, const float* shift,
 bool conv_affine_ok(int dtype, const ConvArgs& a);
 // ... and which POOLED layers do (ConvArgs::aff_pool; conv_affine_ok holds too)
 bool conv_affine_pool_ok(int dtype, const ConvArgs& a);
-hipError_t launch_conv_igemm(int dtype, const ConvArgs& a, hipStream_t s);   // per-tap staging (used for 1x1)
-// 1x1 (round 6, conv_gemm1.hip): filter fragments straight from L2 (pack layout 1), the pixel tile in a deep LDS ring
-bool conv_gemm1_ok(int taps, int row_bytes, int Cout, int M);
-hipError_t launch_conv_gemm1(int dtype, const ConvArgs& a, hipStream_t s, int* block_pixels);
-hipError_t launch_conv_halo(int dtype, const ConvArgs& a, hipStream_t s, int* block_pixels);  // 3x3: LDS halo image
-hipError_t launch_conv_haloq(int dtype, const ConvArgs& a, hipStream_t s, int* block_pixels); // + filters via registers
-// filter layout launch_conv expects (0/1/2).  row_bytes = bytes of one operand plane per pixel (dtype_kbytes), elem_size
-// = dtype_size (sizes the epilogue patch), split = dtype_split
-int conv_filter_layout(int taps, int W, int row_bytes, int Cout, int M, int dgrad = 0, int elem_size = 2, int split = 0);
-// Pixel x cout tile of conv_haloq on the short-row 3x3 layers (W <= 52, more than 64 couts, 128-byte K chunks), chosen by
-// a cost model of the workgroup rounds on the 256 CUs (conv_halo.hip: haloq_tile_choice).  ONE function decides both the
-// kernel (launch time) and the filter pack it reads (bind time): HQ_384x128_M16 reads 16-row fragments (layout 2),
-// every other tile 32-row fragments (layout 1).
-enum HqTile { HQ_NONE = 0, HQ_384x128_M16, HQ_256x128_M16, HQ_384x64, HQ_512x128, HQ_256x128, HQ_512x64, HQ_256x64 };
-int haloq_tile_choice(int W, int row_bytes, int Cout, int M, int elem_size);
-// policy; *records = rows of the BN partial list written (one per pixel tile)
-hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t s, int* block_pixels = nullptr, int* records = nullptr);
-// 3x3, filters resident in registers, persistent workgroups over the bordered pixel space (conv_rf.hip)
-int conv_rf_config(int taps, int W, int row_bytes, int Cout, int M);   // 0: not this form
-int conv_rfn_config(int taps, int W, int row_bytes, int Cout, int M, int dgrad);
-hipError_t launch_conv_rf(int dtype, const ConvArgs& a, hipStream_t s, int* block_pixels, int* records);
-int conv_block_pixels(int Cout);
+
+// ---- conv kernel policy (conv_halo.hip): plan_conv decides every forward / dgrad launch, the launchers execute its answer
+enum ConvKind {
+    CK_RF,          // conv_rf.hip: filters resident in registers, 208-wide 32 <-> 64 layers (cfg 1, 2)
+    CK_RFN,         //   ... the 128-cout form (cfg 3)
+    CK_HALOQ,       // conv_haloq.hip: halo image in LDS, filter fragments straight to registers
+    CK_HALOQ_KS,    //   ... K split over workgroups + conv_ks_finish (launches of a few hundred pixels)
+    CK_HALO,        // conv_halo.hip: halo image + LDS filter ring
+    CK_IGEMM,       // conv_igemm.hip: per-tap staging (every 1x1, the 208-wide 3x3 forwards)
+    CK_IGEMM_KS,    //   ... K split of the small 1x1 launches
+};
+struct ConvPlan {
+    ConvKind kind;
+    int cfg;            // rf: config 1-3; the other kinds: a conv_tile() (development build: a conv_halo variant number)
+    int filter_layout;  // what the filter pack must hold: 0 K-contiguous rows, 1 32-row / 2 16-row MFMA fragments
+    int block_pixels;   // pixels per BN partial record (rf kinds: set by the launch, a persistent grid)
+    int ks_depth;       // K splits of the *_KS kinds (after the scratch-size clamp), else 1
+};
+// a kernel tile as one int: waves over pixels x couts, 32-wide MFMA units per wave, K-chunk bytes (64 / 128) and one
+// family field (haloq: 16x16 MFMA tiles; halo, igemm: stages of the ring)
+constexpr int conv_tile(int wp, int wc, int tp, int tc, int bkb, int aux) {
+    return wp | wc << 4 | tp << 8 | tc << 12 | (bkb / 64) << 16 | aux << 20;
+}
+struct ConvTile {
+    int wp, wc, tp, tc, bkb, aux;
+    explicit ConvTile(int t)
+        : wp(t & 15), wc((t >> 4) & 15), tp((t >> 8) & 15), tc((t >> 12) & 15), bkb(((t >> 16) & 15) * 64), aux(t >> 20) {}
+    int bp() const { return wp * tp * 32; }
+    int bc() const { return wc * tc * 32; }
+};
+// no HIP calls, no side effects
+ConvPlan plan_conv(int dtype, const ConvArgs& a);
+// plan_conv + the launch; filter_layout = the layout the filters were packed in (hipErrorInvalidValue unless the plan's).
+// *records = rows of the BN partial list written
+hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t s, int filter_layout, int* block_pixels = nullptr,
+                       int* records = nullptr);
+// the family launchers (launch_conv's switch): hipErrorInvalidValue for a plan they cannot run
+hipError_t launch_conv_rf(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* block_pixels, int* records);
+hipError_t launch_conv_haloq(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv_halo(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv_igemm(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
+// rows of the LDS image of the halo kernels over all tiles of a launch (pool: window-major tiles, ConvArgs::aff_pool)
+int halo_image_rows(int H, int W, int BP, int RPI, int pool = 0);
 int conv_block_couts(int Cout);
 
 // ---- first layer (Cin = 3, stored as 4 channels)
@@ -340,7 +359,7 @@ struct PackLayer {
     int taps, Cin, Cout, Cout_pad, Kc, Cin_pad, Cdy;
     int wf_bx, wf_by, wf_blocks, wd_blocks, first_block;
     int opt_first;      // first tile block of this layer in launch_opt_pack's grid (tiles only)
-    int wf_frag, wd_frag;   // conv_filter_layout(): 0 K-contiguous rows, 1 / 2 MFMA-fragment order (32 / 16 rows)
+    int wf_frag, wd_frag;   // ConvPlan::filter_layout: 0 K-contiguous rows, 1 / 2 MFMA-fragment order (32 / 16 rows)
 };
 void pack_layer_plan(PackLayer& L, int first_block, int elem_size);
 hipError_t launch_pack_all(int dtype, const PackLayer* tab_dev, int nlayers, int total_blocks, hipStream_t s);

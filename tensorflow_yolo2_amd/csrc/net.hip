@@ -49,9 +49,14 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 static inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
 static inline size_t part_rows_bound(int N, int H, int W, int cout) {
-    size_t bp = conv_block_pixels(cout);
-    if (bp > 64) bp = 64;     // the smallest pixel tile of any kernel form (conv_rf.hip: 64 bordered positions)
+    const size_t bp = 64;     // the smallest pixel tile of any kernel form (conv_rf.hip: 64 bordered positions)
     return ((size_t)N * (H + 1) * (W + 1) + bp - 1) / bp;
+}
+// ConvPlan::filter_layout of a launch of this shape: what its filter pack must hold
+static int conv_layout(int dtype, int taps, int H, int W, int M, int C, int Cout, int ldy, int dgrad) {
+    ConvArgs a{};
+    a.H = H; a.W = W; a.M = M; a.C = C; a.Cout = Cout; a.ldy = ldy; a.taps = taps; a.is_dgrad = dgrad;
+    return plan_conv(dtype, a).filter_layout;
 }
 
 
@@ -73,6 +78,7 @@ struct Layer {
     int cout_pad;    // rows of packed forward filter
     int cin_pad;     // rows of packed dgrad filter
     bool first3;     // Cin = 3 special layer
+    int wf_frag = 0, wd_frag = 0;   // layouts of the forward / dgrad filter packs (ConvPlan::filter_layout)
     float slope = 0.1f;   // activation slope (y2_set_layer_options): 0.1 leaky (the reference), 0 ReLU, 1 none
     size_t pW, pb, pg, pbeta;  // float offsets into params / grads
     size_t smm, smv;           // float offsets into state
@@ -527,7 +533,7 @@ int y2_bind(y2_ctx* c, float* params, float* grads, float* state, void* workspac
     c->packtab.clear();
     int nb = 0, ntile = 0;
     for (size_t l = 0; l < c->L.size(); ++l) {
-        const Layer& y = c->L[l];
+        Layer& y = c->L[l];
         if (y.first3) continue;
         PackLayer p{};
         p.W = params + y.pW;
@@ -536,9 +542,9 @@ int y2_bind(y2_ctx* c, float* params, float* grads, float* state, void* workspac
         p.wd = training ? (void*)(c->ws + y.wd) : nullptr;   // layer 0 too: y2_backward_input wants its dgrad
         p.taps = y.k * y.k; p.Cin = y.cin; p.Cout = y.cout; p.Cout_pad = y.cout_pad; p.Kc = y.cin_s;
         p.Cin_pad = y.cin_pad; p.Cdy = y.ldy;
-        const int kb = dtype_kbytes(c->dtype), split = dtype_split(c->dtype) ? 1 : 0;
-        p.wf_frag = conv_filter_layout(p.taps, y.W, y.cin_s * kb, y.cout, y.M, 0, (int)c->sz(), split);   // forward launch
-        p.wd_frag = conv_filter_layout(p.taps, y.W, y.ldy * kb, y.cin, y.M, 1, (int)c->sz(), split);   // dgrad launch: Cout = cin
+        const int split = dtype_split(c->dtype) ? 1 : 0;
+        p.wf_frag = y.wf_frag = conv_layout(c->dtype, p.taps, y.H, y.W, y.M, y.cin_s, y.cout, y.ldy, 0);       // forward launch
+        p.wd_frag = y.wd_frag = conv_layout(c->bwd_dtype, p.taps, y.H, y.W, y.M, y.ldy, y.cin, y.cin, 1);     // dgrad: Cout = cin
         pack_layer_plan(p, nb, split ? 2 : (int)c->sz());     // (f16x2: the pack kernels run their 16-bit form on two planes)
         nb += p.wf_blocks + p.wd_blocks;
         p.opt_first = ntile;
@@ -803,7 +809,7 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
                 a.aff_pool = y.pool == 1 ? 1 : 0;
                 folded = true;
             }
-            { PROF(CAT_CONV_FWD); HIPCHK(launch_conv(c->dtype, a, s, &bp, &rec)); }
+            { PROF(CAT_CONV_FWD); HIPCHK(launch_conv(c->dtype, a, s, y.wf_frag, &bp, &rec)); }
             P = rec;
             if (training && y.pool == 2) {
                 PROF(CAT_BN_FWD);
@@ -1114,7 +1120,14 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
                 // keeps its own recomputing reduce
                 // (a launch of a few hundred pixels splits its K range over workgroups instead -- conv_haloq.hip haloq_ks --
                 //  and leaves the reduce to the standalone kernel: 7x7 1024 -> 512 at batch 24: 81 us fused and un-split)
-                const bool ks = c->ks_floats && conv_ks_depth(a.taps, a.M, a.Cout, a.C * dtype_kbytes(c->dtype)) >= 2;
+                // f16x2f: dA is consumed once, by the batch-norm backward pass of the layer below, which rounds its own result
+                // to f16 for the next contraction: store it in f16 (launch dtype 5) wherever that consumer is one of the
+                // fp32-wide batch-norm kernels (not the 3-channel layer's own kernels, not an external input gradient)
+                static const bool da32 = getenv("Y2_F16X2F_DA32") != nullptr;      // A/B switch: fp32 dA everywhere
+                const bool half_out = c->bwd_dtype == 4 && !da32 && l > 0 && !z.first3;
+                const int ldt = half_out ? 5 : c->bwd_dtype;
+                const ConvKind kind = plan_conv(ldt, a).kind;
+                const bool ks = kind == CK_HALOQ_KS || kind == CK_IGEMM_KS;
                 const bool fuse = !no_fuse && !ks && l > 0 && l - 1 >= layer_lo && !z.first3 && z.ldy == y.cin;
                 if (l == 1 && z.first3 && c->fopt.on && c->fopt.ctrl && c->lin1() && forked)
                     a.nonfinite = (unsigned*)(c->ws + c->o_nfflag);   // this launch stores dA_0: the early guard's view of layer 0
@@ -1125,12 +1138,7 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
                     a.bw_slope = z.slope;
                 }
                 int rec = 0;
-                // f16x2f: dA is consumed once, by the batch-norm backward pass of the layer below, which rounds its own result
-                // to f16 for the next contraction: store it in f16 (launch dtype 5) wherever that consumer is one of the
-                // fp32-wide batch-norm kernels (not the 3-channel layer's own kernels, not an external input gradient)
-                static const bool da32 = getenv("Y2_F16X2F_DA32") != nullptr;      // A/B switch: fp32 dA everywhere
-                const bool half_out = c->bwd_dtype == 4 && !da32 && l > 0 && !z.first3;
-                { PROF(CAT_DGRAD); HIPCHK(launch_conv(half_out ? 5 : c->bwd_dtype, a, s, &bp, &rec)); }
+                { PROF(CAT_DGRAD); HIPCHK(launch_conv(ldt, a, s, y.wd_frag, &bp, &rec)); }
                 if (fuse) fused_P = rec;
                 c->dA_cur ^= 1;
                 c->dA_half = half_out ? 1 : 0;
@@ -1519,14 +1527,14 @@ int y2_conv2d(const float* x, const float* w, const float* bias, float* y, int N
     char* ws = (char*)workspace;
     PadGeom g{N, H, W, p.Cin_p};
     char* xp = ws + p.xp + g.base_off(sz);
-    HIPCHK(op_pack_bordered(dtype, x, ws + p.xp, p.wf - p.xp, g, Cin, s));
-    HIPCHK(launch_pack_weights(dtype, w, ws + p.wf, nullptr, k * k, Cin, Cout, p.Cout_pad, p.Cin_p, 0, 0,
-                               conv_filter_layout(k * k, W, p.Cin_p * dtype_kbytes(dtype), Cout, N * H * W, 0, (int)sz, dtype_split(dtype)), s));
     ConvArgs a{};
     a.x = xp; a.w = ws + p.wf; a.y = ws + p.y; a.bias = bias;
     a.N = N; a.H = H; a.W = W; a.C = p.Cin_p; a.M = N * H * W; a.Cout = Cout; a.ldy = p.ldy; a.taps = k * k;
     if (p.ks_floats) { a.ks_scratch = (float*)(ws + p.ks); a.ks_floats = p.ks_floats; }
-    HIPCHK(launch_conv(dtype, a, s));
+    const int layout = plan_conv(dtype, a).filter_layout;
+    HIPCHK(op_pack_bordered(dtype, x, ws + p.xp, p.wf - p.xp, g, Cin, s));
+    HIPCHK(launch_pack_weights(dtype, w, ws + p.wf, nullptr, k * k, Cin, Cout, p.Cout_pad, p.Cin_p, 0, 0, layout, s));
+    HIPCHK(launch_conv(dtype, a, s, layout));
     HIPCHK(launch_cast_to_f32(dtype, ws + p.y, y, (size_t)N * H * W, Cout, p.ldy, s));
     return Y2_OK;
 }
@@ -1547,14 +1555,14 @@ int y2_conv2d_backward(const float* x, const float* w, const float* dy, float* d
     HIPCHK(op_pack_bordered(dtype, x, ws + p.xp, p.wf - p.xp, gx, Cin, s));
     HIPCHK(op_pack_bordered(dtype, dy, ws + p.dyp, p.dx - p.dyp, gy, Cout, s));
     if (dx) {
-        HIPCHK(launch_pack_weights(dtype, w, nullptr, ws + p.wd, k * k, Cin, Cout, 0, 0, p.Cin_pad, p.Cdy,
-                                   conv_filter_layout(k * k, W, p.Cdy * dtype_kbytes(dtype), p.Cin_p, N * H * W, 1, (int)sz, dtype_split(dtype)), s));
         ConvArgs a{};
         a.x = dyp; a.w = ws + p.wd; a.y = ws + p.dx;
         a.N = N; a.H = H; a.W = W; a.C = p.Cdy; a.M = N * H * W; a.Cout = p.Cin_p; a.ldy = p.Cin_p; a.taps = k * k;
         a.is_dgrad = 1;
         if (p.ks_floats) { a.ks_scratch = (float*)(ws + p.ks); a.ks_floats = p.ks_floats; }
-        HIPCHK(launch_conv(ldt, a, s));
+        const int layout = plan_conv(ldt, a).filter_layout;
+        HIPCHK(launch_pack_weights(dtype, w, nullptr, ws + p.wd, k * k, Cin, Cout, 0, 0, p.Cin_pad, p.Cdy, layout, s));
+        HIPCHK(launch_conv(ldt, a, s, layout));
         HIPCHK(launch_cast_to_f32(dtype, ws + p.dx, dx, (size_t)N * H * W, Cin, p.Cin_p, s));
     }
     if (dw) {

@@ -57,18 +57,16 @@ def test_hand_counted_fragment_loads_never_meet_a_spill():
     assert len(kernels) > 100, len(kernels)
     bad = []
     for name, vgpr, spill, scratch in kernels:
-        m = re.search(r"ELb([01])ELb([01])ELi(\d)E", name)
-        compact = bool(m and m.group(2) == "1")          # Y2_HALO_COMPACT / Y2_HALOQ_1X1: opt-in variants, not the default path
-        if (spill or scratch) and not compact:
+        if spill or scratch:
             bad.append((name, vgpr, spill, scratch))
         assert vgpr <= 512, (name, vgpr)                  # the unified VGPR / AGPR file of a SIMD
-    assert not bad, "default-path conv_haloq kernels must not spill or own scratch: %r" % bad[:4]
+    assert not bad, "conv_haloq kernels must not spill or own scratch: %r" % bad[:4]
 
 
 def test_no_product_kernel_spills():
     """every object of the product library: no kernel spills a register, and none owns scratch
     memory except the loss kernel's indexed per-thread arrays (one thread per grid cell: 120 TF ops on ~30 values, by
-    design) and the opt-in compact-image variants of conv_haloq (Y2_HALO_COMPACT / Y2_HALOQ_1X1, reported above).  Round 4
+    design).  Round 4
     shipped a 16-wave weight-gradient tile with 2,651 scratch instructions: the development variants were compiled into
     the product library because their `#ifdef Y2_DEV` guard tested the name of the `__device__ __forceinline__` macro of
     common.h, which is always defined -- the guard is `Y2_DEVBUILD` now and the product objects hold the policy's kernels
@@ -83,9 +81,6 @@ def test_no_product_kernel_spills():
             continue
         for name, vgpr, spill, scratch in kernel_metadata(obj):
             total += 1
-            m = re.search(r"conv_haloq(16)?_kernel.*ELb([01])ELb([01])ELi(\d)E", name)
-            if m and m.group(3) == "1":             # compact image: opt-in
-                continue
             if spill or (scratch and "yolo_loss_kernel" not in name):
                 bad.append((os.path.basename(obj), name, vgpr, spill, scratch))
     assert total > 500, total
