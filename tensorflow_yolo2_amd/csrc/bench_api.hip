@@ -55,8 +55,7 @@ extern "C" __attribute__((visibility("default"))) int y2dev_bench_wgrad(int N, i
     g.splitk = splitk; g.scale = 1.f;
     g.xcd = getenv("Y2_XCD_WGRAD") ? atoi(getenv("Y2_XCD_WGRAD")) : 1;
     auto run = [&]() {
-        if (variant >= 100) return launch_wgrad_variant(variant, g, 0);
-        return variant >= 2 ? launch_wgrad9_variant(variant, g, 0) : (variant == 1 ? launch_wgrad9(1, g, 0) : launch_wgrad(1, g, 0));
+        return variant >= 2 && variant < 100 ? launch_wgrad9_variant(variant, g, 0) : launch_wgrad_variant(variant, g, 0);
     };
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);

@@ -269,76 +269,141 @@ size_t conv1_wgrad_lin_scratch_floats();   // acc: totals + per-block partials
 hipError_t launch_conv1_wgrad_lin(int dtype, const Conv1WgradLinArgs& a, hipStream_t s);
 hipError_t launch_conv1_dw_finalize(const Conv1DwFinalizeArgs& a, hipStream_t s);
 
-// ---- weight-gradient GEMM  dW[t][ci][co] += sum_p X[p+t][ci] * dY[p][co]
+// ---- weight-gradient GEMM  dW[t][ci][co] = scale * sum_p X[p+t][ci] * dY[p][co]
 struct WgradArgs {
     const void* x;      // zero-bordered [N][H+2][W+2][Cin]
     const void* dy;     // zero-bordered [N][H+2][W+2][Cdy]
-    float* dW;          // [taps][Cin][Cout] fp32 (HWIO), accumulated with atomics
+    float* dW;          // [taps][Cin][Cout] fp32 (HWIO)
     int N, H, W, M;
     int Cin, Cdy, Cout; // Cdy = channel stride of dy (>= Cout)
     int taps;
-    int splitk;
+    int splitk;         // 0: plan_wgrad decides (the launchers pass the plan's)
     float scale;
     int xcd = 0;        // XCD-aware workgroup order (common.h xcd_block)
-    // split-K partial tiles: with a slab of at least splitk * taps*Cin*Cout floats the splits store their partials
-    // there (plain stores) and wgrad_split_finish sums them in a fixed order into dW -- deterministic, and no
+    // split-K partial tiles: with a slab of at least splitk * taps*Cin*Cout floats per launch the splits store their
+    // partials there (plain stores) and wgrad_reduce_kernel sums them in a fixed order into dW -- deterministic, and no
     // zero-fill of dW; without one they are added into a zeroed dW with float atomics (≈1.3 TB/s chip-wide)
     float* slab = nullptr;
     size_t slab_floats = 0;
-    // f16x2 mode: x / dy are split tensors.  The launchers run the 16-bit kernels once per operand-plane pair (hi hi,
-    // lo hi, hi lo -- `quads` = 3) with xpitch / ypitch = elements of the operand type per pixel (2 Cin / 2 Cdy) and
-    // every launch's partial tiles in its own range of the slab; ONE fixed-order sum over quads * splitk partials
+    // f16x2 mode: x / dy are split tensors, read by the 16-bit kernels with xpitch / ypitch = elements of the operand
+    // type per pixel (2 Cin / 2 Cdy).  Where no two-plane tile fits, one launch per operand-plane pair (hi hi, lo hi,
+    // hi lo -- `quads` = 3), every launch's partial tiles in its own range of the slab; ONE fixed-order sum over
+    // quads * splitk partials
     int xpitch = 0, ypitch = 0;     // 0: Cin / Cdy
-    int quads = 1;
-    // Round 5: the split-K sum INSIDE the weight-gradient kernel (wgrad_finish.h).  tile_cnt != null (>= cnt_ints zeroed
-    // ints, self-cleaning): every block adds 1 to its tile's counter after its partial tile is in the slab; the block
-    // that completes a group of <= 16 partials sums that group in index order (a fixed tree of groups: deterministic
-    // whoever arrives last, no spin-wait, so no co-residency requirement) and the one that completes the top group
-    // writes dW -- the separate wgrad_reduce launches (18 per detector step) disappear.
-    int* tile_cnt = nullptr;
-    size_t cnt_ints = 0;
-    int part0 = 0;          // slab slot of this launch's split 0 (quads: q * splitk); set by wgrad_launch_quads
-    int cnt_stride = 0;     // counters per tile (wgrad_cnt_per_tile); 0: the separate sum kernel runs after the launch
-    int fin_lds_off = 0;    // byte offset of the finish flag in the dynamic LDS (behind the staging buffers: the ring form
-                            // needs the buffers at an aligned LDS base, so no static __shared__ in these kernels)
+    int quads = 1;          // plane-pair launches (WgradPlan::launches); set by the launchers
+    int part0 = 0;          // slab slot of this launch's split 0 (q * splitk); set by wgrad_run
 };
-constexpr int kWgFinG = 16;      // partials per group of the in-kernel sum
-// counters per tile for `parts` partials: one per group of every level of the tree
-inline int wgrad_cnt_per_tile(int parts) {
-    int c = 0;
-    for (int n = parts; ; n = (n + kWgFinG - 1) / kWgFinG) {
-        if (n <= kWgFinG) return c + 1;
-        c += (n + kWgFinG - 1) / kWgFinG;
-    }
-}
-// f16x2: the split form of a (x, dy) pair for the 16-bit kernels (dtype 3 -> 1)
+// f16x2: the split form of a (x, dy) pair for the 16-bit kernels (dtype 3, 4 -> 1)
 inline int wgrad_split_args(int dtype, WgradArgs& a) {
     if (!a.xpitch) a.xpitch = a.Cin;
     if (!a.ypitch) a.ypitch = a.Cdy;
     if (!dtype_split(dtype)) return dtype;
     a.xpitch = 2 * a.Cin; a.ypitch = 2 * a.Cdy;
-    a.quads = dtype >= 4 ? 1 : 3;      // f16x2f: the hi-plane pair alone -- the f16 kernels on cells of twice the pitch
     return 1;
 }
-// one launch per operand-plane pair (WgradArgs::quads): hi hi, x lo, dy lo -- each with its own slab range
+
+// ---- weight-gradient policy (wgrad.hip): plan_wgrad decides every launch, the family launchers execute its answer
+enum WgradKind {
+    WK_NONE,        // no kernel takes the shape: the launch returns hipErrorInvalidValue
+    WK_TAP,         // wgrad.hip wgrad_kernel: one tap per block
+    WK_NINE,        // wgrad9.hip wgrad9_kernel: all nine taps per block, the X window staged per K step
+    WK_RING,        // wgrad9.hip wgrad9r_kernel: all nine taps per block, the X rows in an LDS ring (16-bit, long rows)
+};
+enum WgradSum {
+    WS_DIRECT,      // one partial per dW element: the kernel stores it
+    WS_REDUCE1,     // partials in the slab, slot q * splitk + split; wgrad_reduce_kernel<1> (up to 8 partials)
+    WS_REDUCE16,    //   ... wgrad_reduce_kernel<16> (more)
+    WS_ATOMIC,      // float atomics into a zeroed dW (no slab lent, too small, or Y2_NO_WGRAD_SLAB)
+};
+// a kernel tile as one int: WI x WO waves over ci x co; per wave TI x TO 32-wide MFMA units (per-tap kernel) or one ci unit
+// and CW co units for its TG-th share of the taps (nine-tap kernels); K steps of KS x 64 pixels (f32: 32); NS LDS stages
+// (the ring: its two dY buffers); PL2: both operand planes of the f16x2 mode staged, the three plane products in one block
+constexpr int wgrad_tile(int wi, int wo, int ti, int to, int tg, int ks, int cw, int ns, int pl2) {
+    return wi | wo << 3 | ti << 6 | to << 9 | tg << 12 | ks << 15 | cw << 18 | ns << 21 | pl2 << 24;
+}
+struct WgTile {
+    int wi, wo, ti, to, tg, ks, cw, ns, pl2;
+    constexpr explicit WgTile(int t)
+        : wi(t & 7), wo((t >> 3) & 7), ti((t >> 6) & 7), to((t >> 9) & 7), tg((t >> 12) & 7), ks((t >> 15) & 7),
+          cw((t >> 18) & 7), ns((t >> 21) & 7), pl2(t >> 24) {}
+    constexpr int bi() const { return 32 * wi * ti; }
+    constexpr int bo() const { return 32 * wo * to * cw; }
+    constexpr int nw() const { return wi * wo * tg; }
+    constexpr int npl() const { return pl2 ? 2 : 1; }
+    constexpr int bkp(int sz) const { return (sz == 2 ? 64 : 32) * ks; }     // pixels per K step
+};
+// LDS of a block, one formula per family (sz = bytes of an operand element).  plan_wgrad sizes the launch with them; the
+// launchers check them against their kernel's staging layout at compile time.
+//   per-tap: NS stages of [X: BKP x BI][dY: BKP x BO] per plane
+constexpr int wg_lds(int sz, WgTile t) { return t.npl() * t.ns * t.bkp(sz) * (t.bi() + t.bo()) * sz; }
+//   nine-tap: NS stages of [X window: wrows x BI][dY: BKP x BO] per plane.  The window is the K step plus the 3x3 reach,
+//   in whole 1-KiB pieces (deeper rings count the loads in flight, so there every wave issues the same number of pieces)
+constexpr int wg9_wrows(int sz, WgTile t, int W) {
+    const int gran = (1024 / (t.bi() * sz)) * (t.ns > 2 ? t.nw() : 1);
+    return (t.bkp(sz) + 2 * (W + 1) + 2 + gran - 1) / gran * gran;
+}
+constexpr int wg9_lds(int sz, WgTile t, int wrows) { return t.ns * t.npl() * (wrows * t.bi() * sz + t.bkp(sz) * t.bo() * sz); }
+//   ring: a ring of 2^lg X rows and NS dY buffers per plane; the window spans G groups of BKP rows, and group st + G is in
+//   flight during step st, so the ring holds at least BKP * (G + 1) rows
+constexpr int wg9r_groups(int sz, WgTile t, int W) { return (t.bkp(sz) + 2 * (W + 1) + 2 + t.bkp(sz) - 1) / t.bkp(sz); }
+constexpr int wg9r_lg(int sz, WgTile t, int W) {
+    int lg = 7;
+    while ((1 << lg) < t.bkp(sz) * (wg9r_groups(sz, t, W) + 1)) ++lg;
+    return lg;
+}
+constexpr long wg9r_lds(int sz, WgTile t, int lg) {
+    return (long)t.npl() * (((long)t.bi() * sz << lg) + (long)t.ns * t.bkp(sz) * t.bo() * sz);
+}
+struct WgradPlan {
+    WgradKind kind;
+    int tile;           // wgrad_tile
+    int launches;       // 1, or 3 on operand-plane pairs (f16x2 where no PL2 tile fits)
+    int splitk;
+    WgradSum sum;
+    int blocks;         // workgroups of one launch: dW tiles x splitk
+    int lds;            // dynamic LDS bytes of a block
+    int wrows;          // WK_NINE: X window rows per K step
+    int ring_lg, ring_g;    // WK_RING: log2 of the ring's rows, groups of BKP rows per window
+};
+// no HIP calls, no side effects
+WgradPlan plan_wgrad(int dtype, const WgradArgs& a);
+// plan_wgrad + the launch (xcd order from Y2_XCD_WGRAD)
+hipError_t launch_wgrad_auto(int dtype, const WgradArgs& a, hipStream_t s);
+// the family launchers: hipErrorInvalidValue for a plan they cannot run
+hipError_t launch_wgrad(int dtype, const WgradPlan& p, const WgradArgs& a, hipStream_t s);      // WK_TAP
+hipError_t launch_wgrad9(int dtype, const WgradPlan& p, const WgradArgs& a, hipStream_t s);     // WK_NINE, WK_RING
+// the slab's fixed-order sum into dW (WS_REDUCE1 / WS_REDUCE16)
+hipError_t wgrad_reduce(const WgradPlan& p, const WgradArgs& a, hipStream_t s);
+// what every family launcher does with its kernel: the LDS attribute (lds_attr: the largest size set so far for this
+// kernel), the zero-filled dW of the atomics route, one launch per operand-plane pair with its own slab slots, the sum
 template <typename K, typename... Extra>
-inline hipError_t wgrad_launch_quads(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, const WgradArgs& a, Extra... extra) {
-    for (int q = 0; q < a.quads; ++q) {
+inline hipError_t wgrad_run(K kern, int& lds_attr, const WgradPlan& p, const WgradArgs& a0, int threads, hipStream_t s,
+                            Extra... extra) {
+    if (p.lds > 160 * 1024 || p.blocks <= 0) return hipErrorInvalidValue;
+    if (p.lds > lds_attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+        if (e != hipSuccess) return e;
+        lds_attr = p.lds;
+    }
+    WgradArgs a = a0;
+    a.splitk = p.splitk;
+    a.quads = p.launches;
+    const bool slab = p.sum == WS_REDUCE1 || p.sum == WS_REDUCE16;
+    if (!slab) a.slab = nullptr;
+    if (p.sum == WS_ATOMIC) {
+        hipError_t e = hipMemsetAsync(a.dW, 0, (size_t)a.taps * a.Cin * a.Cout * sizeof(float), s);
+        if (e != hipSuccess) return e;
+    }
+    for (int q = 0; q < p.launches; ++q) {
         WgradArgs b = a;
         if (q == 1) b.x = (const char*)a.x + (size_t)a.Cin * 2;
         if (q == 2) b.dy = (const char*)a.dy + (size_t)a.Cdy * 2;
-        b.part0 = q * a.splitk;
-        hipLaunchKernelGGL(kern, grid, block, lds, s, b, extra...);
+        b.part0 = q * p.splitk;
+        hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(threads), p.lds, s, b, extra...);
     }
-    return hipGetLastError();
+    hipError_t e = hipGetLastError();
+    return e != hipSuccess || !slab ? e : wgrad_reduce(p, a, s);
 }
-hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t s);       // one tap per block
-hipError_t launch_wgrad9(int dtype, const WgradArgs& a, hipStream_t s);      // 3x3: nine taps per block
-hipError_t launch_wgrad_auto(int dtype, const WgradArgs& a, hipStream_t s);
-// around a split-K launch (a.splitk resolved): chooses slab or atomics (zero-filling dW for the latter) / sums the slab
-int wgrad_finish_max_parts();      // Y2_WGRAD_FINISH (0 = the in-kernel sum is off: the default)
-hipError_t wgrad_split_prepare(WgradArgs& a, hipStream_t s);
-hipError_t wgrad_split_finish(const WgradArgs& a, hipStream_t s);
 
 // ---- packing
 hipError_t launch_pack_input(int dtype, const float* img, void* x4, int N, int H, int W, hipStream_t s);
@@ -527,7 +592,5 @@ hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
 // per-(device, stream) scratch of the graph-level operators (split partial sums); grows on demand, never shrinks
 void* op_scratch(hipStream_t s, size_t bytes);
 int op_scratch_error();      // code of the last null return of op_scratch on this thread (its message is already in y2_last_error)
-int* op_counters(hipStream_t s, size_t ints);      // zeroed, self-cleaning tile counters (WgradArgs::tile_cnt)
-constexpr size_t kWgCntInts = 65536;
 
 }  // namespace y2

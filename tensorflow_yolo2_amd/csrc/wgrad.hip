@@ -11,21 +11,12 @@
 // per-pixel index arithmetic is needed (row addresses are affine in k).  The
 // tap shift is a constant offset on X; guard bands around the tensors keep the
 // shifted reads in finite memory.
-// Split-K over blocks; partial tiles are accumulated into the fp32 HWIO
-// gradient with float atomics (256-byte row segments per wave-instruction).
+// Split-K over blocks; the partial tiles go to a slab and a fixed-order sum (wgrad_reduce_kernel), or are added into
+// the fp32 HWIO gradient with float atomics (plan_wgrad, at the end of this file, decides).
 #include <stdlib.h>
 #include "common.h"
 #include "conv_epilogue.h"
 #include "kernels.h"
-#include "wgrad_finish.h"
-// The in-kernel split-K sum (wgrad_finish.h) measured slower in every form (profiles/r05_ab_wgrad_finish.txt) and its mere
-// presence cost the weight gradients 1.8 % (2.53 vs 2.49 ms per step, same box): it is compiled into the DEVELOPMENT
-// library only (make dev, Y2_WGRAD_FINISH=<max partials>); the product kernels store their partials plainly.
-#ifdef Y2_DEVBUILD
-#define Y2_FIN_STORE(p, v) do { if (a.cnt_stride) slab_store((p), (v)); else *(p) = (v); } while (0)
-#else
-#define Y2_FIN_STORE(p, v) (*(p) = (v))
-#endif
 
 namespace y2 {
 
@@ -45,7 +36,6 @@ struct WgCfg {
     static constexpr int IPWX = NIX / NW, IPWY = NIY / NW;
     static constexpr int XS = BKP * ROWX, YS = BKP * ROWY;
     static constexpr int STAGE = XS + YS;
-    static constexpr int LDS = NS * STAGE;
     static_assert(NIX % NW == 0 && NIY % NW == 0, "staging must split evenly over waves");
 };
 
@@ -67,7 +57,6 @@ __global__ __launch_bounds__(WI* WO * 64) void wgrad_kernel(WgradArgs a) {
     constexpr int ROWX = Cfg::ROWX, ROWY = Cfg::ROWY;
     constexpr int NPL = PL2 ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* const s_fin = (int*)(smem + NPL * Cfg::LDS);      // the finish flag sits behind the staging buffers (wgrad_finish.h)
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wi = w / WO, wo = w % WO;
@@ -217,96 +206,61 @@ __global__ __launch_bounds__(WI* WO * 64) void wgrad_kernel(WgradArgs a) {
                 if (ci < a.Cin && co < a.Cout) {
                     const size_t o = ((size_t)tap * a.Cin + ci) * a.Cout + co;
                     if (a.splitk == 1 && a.quads == 1) a.dW[o] = acc[i][j][q] * a.scale;
-                    else if (a.slab) { float* sp = a.slab + (size_t)(a.part0 + split) * a.taps * a.Cin * a.Cout + o; Y2_FIN_STORE(sp, acc[i][j][q]); }
+                    else if (a.slab) a.slab[(size_t)(a.part0 + split) * a.taps * a.Cin * a.Cout + o] = acc[i][j][q];
                     else atomicAdd(a.dW + o, acc[i][j][q] * a.scale);
                 }
             }
         }
-#ifdef Y2_DEVBUILD
-    if (a.slab && a.cnt_stride) {     // the split-K sum rides in this kernel (wgrad_finish.h; development library only)
-        const size_t nn = (size_t)a.taps * a.Cin * a.Cout;
-        splitk_finish(s_fin, a.tile_cnt + (size_t)((tap * nIT + it) * nOT + ot) * a.cnt_stride, a.part0 + split, a.splitk * a.quads,
-                      [&](int first, int stride, int count, bool final) __attribute__((always_inline)) {
-#pragma unroll 1
-            for (int i = 0; i < TI; ++i)
-#pragma unroll 1
-                for (int j = 0; j < TO; ++j) {
-                    const int co = co0 + (wo * TO + j) * 32 + r32;
-#pragma unroll 1
-                    for (int q = 0; q < 16; ++q) {
-                        const int ci = ci0 + (wi * TI + i) * 32 + acc_row(q, hh);
-                        if (ci < a.Cin && co < a.Cout) {
-                            const size_t o = ((size_t)tap * a.Cin + ci) * a.Cout + co;
-                            const float v = splitk_sum_slots(a.slab + (size_t)first * nn + o, (size_t)stride * nn, count);
-                            if (final) a.dW[o] = v * a.scale;
-                            else slab_store(a.slab + (size_t)first * nn + o, v);
-                        }
-                    }
-                }
-        });
-    }
-#endif
 }
 
-template <typename T, int WI, int WO, int TI, int TO, int NS = 2, bool PL2 = false>
-static hipError_t wg_launch(WgradArgs a, hipStream_t s, int target1 = 256) {
-    typedef WgCfg<T, WI, WO, TI, TO, NS> Cfg;
-    static_assert(Cfg::LDS <= 160 * 1024, "LDS");
-    if constexpr (sizeof(T) == 2 && !PL2 && 2 * Cfg::LDS <= 160 * 1024) {
-        // f16x2 mode: both planes staged, the three plane products in one block (one partial per split instead of three)
-        static const bool quads_form = getenv("Y2_SPLIT_WGRAD_QUADS") != nullptr;
-        if (a.quads == 3 && !quads_form) {
-            a.quads = 1;
-            return wg_launch<T, WI, WO, TI, TO, NS, true>(a, s, 256);      // twice the LDS: one block per CU
-        }
+// the per-tap family: one tile of the plan
+template <typename T, int WI, int WO, int TI, int TO, int NS, bool PL2>
+static hipError_t wg_run(const WgradPlan& p, const WgradArgs& a, hipStream_t s) {
+    if constexpr (PL2 && sizeof(T) != 2) {
+        return hipErrorInvalidValue;      // two planes: 16-bit operands
+    } else {
+        typedef WgCfg<T, WI, WO, TI, TO, NS> Cfg;
+        static_assert(wg_lds(sizeof(T), WgTile(wgrad_tile(WI, WO, TI, TO, 1, 1, 1, NS, PL2))) == (PL2 ? 2 : 1) * NS * Cfg::STAGE,
+                      "wg_lds is the kernel's staging");
+        static int attr = 0;
+        return wgrad_run(wgrad_kernel<T, WI, WO, TI, TO, NS, PL2>, attr, p, a, Cfg::NT, s);
     }
-    constexpr int LDSB = (PL2 ? 2 : 1) * Cfg::LDS;
-    // (the finish flag of the opt-in in-kernel sum sits behind the staging buffers: 16 more bytes only when it is on --
-    //  a request of exactly 1/2 or 1/3 of the CU's LDS must stay that)
-    const int fin16 = (wgrad_finish_max_parts() > 0 && LDSB + 16 <= 160 * 1024) ? 16 : 0;
-    if (!fin16) a.tile_cnt = nullptr;      // no room (or no wish) for the finish flag: the separate sum kernel
-    auto kern = wgrad_kernel<T, WI, WO, TI, TO, NS, PL2>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           LDSB + 16 <= 160 * 1024 ? LDSB + 16 : LDSB);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    const int nIT = (a.Cin + Cfg::BI - 1) / Cfg::BI, nOT = (a.Cout + Cfg::BO - 1) / Cfg::BO;
-    const long Mp = (long)bbody_pixels(a.N, a.H, a.W);
-    const long ksteps = (Mp + Cfg::BKP - 1) / Cfg::BKP;
-    const int tiles = a.taps * nIT * nOT;
-    if (a.splitk <= 0) {
-        // 1x1: with float atomics the partial tiles cost as much as the streaming reads and one block per CU was
-        // the optimum; through the slab two per CU are (scripts/bench_wgrad.py: 38 -> 33.5 us at 26x26 / 13x13);
-        // 3x3 fallback: ~6 per CU
-        const int target = a.taps == 1 ? (a.slab && target1 == 256 && !PL2 ? 512 : target1) : 1536;
-        long sk = (target + tiles - 1) / tiles;
-        const long maxsk = (ksteps + 7) / 8;         // at least 8 K steps per block
-        if (sk > maxsk) sk = maxsk;
-        if (sk < 1) sk = 1;
-        a.splitk = (int)sk;
-    }
-    hipError_t e = wgrad_split_prepare(a, s);
-    if (e != hipSuccess) return e;
-    e = wgrad_launch_quads(kern, dim3(tiles * a.splitk), dim3(Cfg::NT), LDSB + fin16, s, a);
-    return e != hipSuccess ? e : wgrad_split_finish(a, s);
 }
 
 template <typename T>
-static hipError_t wg_T(const WgradArgs& a, hipStream_t s) {
-    const int bi = a.Cin >= 128 ? 128 : a.Cin;       // Cin is 32, 64 or a multiple of 128
-    const int bo = a.Cdy >= 128 ? 128 : (a.Cdy >= 64 ? 64 : 32);
-    if (bi == 128 && bo == 128) return wg_launch<T, 2, 2, 2, 2>(a, s);
-    if (bi == 128 && bo == 64) return wg_launch<T, 2, 2, 2, 1>(a, s);
-    if (bi == 128 && bo == 32) return wg_launch<T, 4, 1, 1, 1>(a, s);
-    if (bi == 64 && bo == 128) return wg_launch<T, 2, 2, 1, 2>(a, s);
-    if (bi == 64 && bo == 64) return wg_launch<T, 2, 2, 1, 1>(a, s);
-    if (bi == 64 && bo == 32) return wg_launch<T, 2, 1, 1, 1>(a, s);
-    if (bi == 32 && bo == 128) return wg_launch<T, 1, 4, 1, 1>(a, s);
-    if (bi == 32 && bo == 64) return wg_launch<T, 1, 2, 1, 1>(a, s);
-    if (bi == 32 && bo == 32) return wg_launch<T, 1, 1, 1, 1>(a, s);
+static hipError_t wg_T(const WgradPlan& p, const WgradArgs& a, hipStream_t s) {
+#define WT(WI, WO, TI, TO, NS, PL2) \
+    case wgrad_tile(WI, WO, TI, TO, 1, 1, 1, NS, PL2): return wg_run<T, WI, WO, TI, TO, NS, PL2>(p, a, s);
+#define WT2(WI, WO, TI, TO) WT(WI, WO, TI, TO, 2, 0) WT(WI, WO, TI, TO, 2, 1)
+    switch (p.tile) {
+        WT2(2, 2, 2, 2)
+        WT2(2, 2, 2, 1)
+        WT2(4, 1, 1, 1)
+        WT2(2, 2, 1, 2)
+        WT2(2, 2, 1, 1)
+        WT2(2, 1, 1, 1)
+        WT2(1, 4, 1, 1)
+        WT2(1, 2, 1, 1)
+        WT2(1, 1, 1, 1)
+#ifdef Y2_DEVBUILD
+        WT(2, 2, 2, 2, 3, 0)
+        WT(2, 2, 2, 2, 4, 0)
+        WT(2, 2, 2, 2, 5, 0)
+#endif
+    }
+#undef WT2
+#undef WT
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_wgrad(int dtype, const WgradPlan& p, const WgradArgs& a0, hipStream_t s) {
+    if (p.kind != WK_TAP) return hipErrorInvalidValue;
+    WgradArgs a = a0;
+    switch (wgrad_split_args(dtype, a)) {
+        case 0: return wg_T<float>(p, a, s);
+        case 1: return wg_T<half_t>(p, a, s);
+        case 2: return wg_T<bf16_t>(p, a, s);
+    }
     return hipErrorInvalidValue;
 }
 
@@ -358,81 +312,299 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     if (sl == 0 && i < n4) ((f32x4*)dW)[i] = t * scale;
 }
 
-int wgrad_finish_max_parts() {
-#ifdef Y2_DEVBUILD
-    static const int v = getenv("Y2_WGRAD_FINISH") ? atoi(getenv("Y2_WGRAD_FINISH")) : 0;
-    return v;
-#else
-    return 0;      // the in-kernel sum exists in the development library only (see the top of this file)
-#endif
-}
-hipError_t wgrad_split_prepare(WgradArgs& a, hipStream_t s) {
-    a.cnt_stride = 0;
-    if (a.splitk * a.quads <= 1) return hipSuccess;
-    const size_t n = (size_t)a.taps * a.Cin * a.Cout;
-    static const bool no_slab = getenv("Y2_NO_WGRAD_SLAB") != nullptr;      // A/B switch: float atomics instead
-    // In-kernel sum (wgrad_finish.h): built and measured in round 5, NOT the default.  Y2_WGRAD_FINISH=<max parts> turns it on
-    // for launches of up to that many partials per tile.  Same box, configs[3] step: separate sum launches 8.78 ms; in-kernel
-    // with agent-scope fences 10.9 ms (every fence writes back / invalidates a whole L2 under the dgrad kernels); with
-    // sc1 atomics instead of fences 9.71 ms (the ONE block that completes a group of 16 partials of a 64-KB tile reads
-    // 1 MB through 4-byte sc1 loads, a few in flight per lane: a serial tail per tile where the separate kernel spreads
-    // the same reads over the whole chip in 6 us)
-    const bool sum_kernel = a.splitk * a.quads > wgrad_finish_max_parts();
-    if (!no_slab && a.slab && (n & 3) == 0 && (size_t)a.splitk * a.quads * n <= a.slab_floats) {
-        // in-kernel sum (wgrad_finish.h) where the caller lent counters: one set per dW tile.  The tile count is bounded by
-        // the smallest tiles any kernel form uses (32 x 32 per tap)
-        const int cps = wgrad_cnt_per_tile(a.splitk * a.quads);
-        const size_t tiles_max = (size_t)a.taps * ((a.Cin + 31) / 32) * ((a.Cout + 31) / 32);
-        if (a.tile_cnt && !sum_kernel && tiles_max * cps <= a.cnt_ints) a.cnt_stride = cps;
-        return hipSuccess;
-    }
-    a.slab = nullptr;      // atomics into a zeroed dW
-    return hipMemsetAsync(a.dW, 0, n * sizeof(float), s);
-}
-hipError_t wgrad_split_finish(const WgradArgs& a, hipStream_t s) {
-    const int parts = a.splitk * a.quads;       // f16x2: the three operand-plane pairs are summed like splits
-    if (parts <= 1 || !a.slab || a.cnt_stride) return hipSuccess;     // (cnt_stride: summed inside the launch)
+hipError_t wgrad_reduce(const WgradPlan& p, const WgradArgs& a, hipStream_t s) {
+    const int parts = p.splitk * p.launches;      // f16x2: the three operand-plane pairs are summed like splits
     const size_t n4 = (size_t)a.taps * a.Cin * a.Cout / 4;
-    if (parts <= 8) {
+    if (p.sum == WS_REDUCE1) {
         hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a.slab, a.dW, n4,
                            parts, n4, a.scale);
-    } else {
+    } else if (p.sum == WS_REDUCE16) {
         hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, s, a.slab, a.dW, n4,
                            parts, n4, a.scale);
+    } else {
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-#ifdef Y2_DEVBUILD
-// development variants (f16, 128 x 128 tiles): stages x blocks target of the 1x1 form
-hipError_t launch_wgrad_variant(int variant, const WgradArgs& a0, hipStream_t s) {
-    WgradArgs a = a0;
-    wgrad_split_args(1, a);
-    typedef half_t T;
-    switch (variant) {
-        case 100: return wg_launch<T, 2, 2, 2, 2, 2>(a, s, 256);
-        case 101: return wg_launch<T, 2, 2, 2, 2, 3>(a, s, 256);
-        case 102: return wg_launch<T, 2, 2, 2, 2, 4>(a, s, 256);
-        case 103: return wg_launch<T, 2, 2, 2, 2, 2>(a, s, 512);
-        case 104: return wg_launch<T, 2, 2, 2, 2, 3>(a, s, 512);
-        case 105: return wg_launch<T, 2, 2, 2, 2, 5>(a, s, 256);
-        case 106: return wg_launch<T, 2, 2, 2, 2, 4>(a, s, 128);
-        case 107: return wg_launch<T, 2, 2, 2, 2, 2>(a, s, 768);
-    }
-    return hipErrorInvalidValue;
-}
-#endif
+// ---------------------------------------------------------------------------
+// Kernel policy of the weight gradients: plan_wgrad (below) decides the kernel family, its tile, the operand-plane-pair
+// launches, the split-K depth, the route of the partial sums and the dynamic LDS -- host arithmetic only, every LDS fit
+// computed here.  launch_wgrad_auto runs its answer.
+//
+// Measured per shape (scripts/bench_wgrad.py):
+//   3x3, rows of 52 and more (16-bit)  : wgrad9r_kernel (ring: 64 new X rows staged per K step instead of the window)
+//   3x3, the other rows                : wgrad9_kernel  (nine taps per block on one staged X window)
+//   1x1, and 3x3 windows LDS cannot hold : wgrad_kernel (one tap per block)
+// ---------------------------------------------------------------------------
+constexpr int kWgLdsMax = 160 * 1024;
 
-hipError_t launch_wgrad(int dtype, const WgradArgs& a0, hipStream_t s) {
-    WgradArgs a = a0;
-    if (a.Cin % 32 != 0 || (a.Cin > 128 && a.Cin % 128 != 0)) return hipErrorInvalidValue;
-    dtype = wgrad_split_args(dtype, a);
-    switch (dtype) {
-        case 0: return wg_T<float>(a, s);
-        case 1: return wg_T<half_t>(a, s);
-        case 2: return wg_T<bf16_t>(a, s);
-    }
-    return hipErrorInvalidValue;
+static long k_steps(const WgradArgs& a, int bkp) { return ((long)bbody_pixels(a.N, a.H, a.W) + bkp - 1) / bkp; }
+static int dw_tiles(const WgradArgs& a, const WgTile& t, int taps) {
+    return taps * ((a.Cin + t.bi() - 1) / t.bi()) * ((a.Cout + t.bo() - 1) / t.bo());
 }
+static int clamp_split(long sk, long maxsk) {
+    if (sk > maxsk) sk = maxsk;
+    return sk < 1 ? 1 : (int)sk;
+}
+// blocks per CU that LDS allows, at most 3
+static int blocks_per_cu(long lds) {
+    const long bpc = kWgLdsMax / lds;
+    return bpc > 3 ? 3 : (bpc < 1 ? 1 : (int)bpc);
+}
+
+// the route of the partial sums, once the split is fixed
+static void plan_sum(WgradPlan& p, const WgradArgs& a) {
+    static const bool no_slab = getenv("Y2_NO_WGRAD_SLAB") != nullptr;      // A/B switch: float atomics instead
+    const int parts = p.splitk * p.launches;
+    const size_t n = (size_t)a.taps * a.Cin * a.Cout;
+    if (parts <= 1) p.sum = WS_DIRECT;
+    else if (!no_slab && a.slab && (n & 3) == 0 && (size_t)parts * n <= a.slab_floats) p.sum = parts <= 8 ? WS_REDUCE1 : WS_REDUCE16;
+    else p.sum = WS_ATOMIC;
+}
+
+// per-tap kernel.  Split-K target: 1x1 with float atomics -- the partial tiles cost as much as the streaming reads -- one
+// block per CU was the optimum, through the slab two per CU are (38 -> 33.5 us at 26x26 / 13x13): 512 blocks where the
+// caller lends a slab (read before the slab's size is checked: such a split can still end on atomics), target1 (256)
+// otherwise and for the two-plane tiles; 3x3: ~6 per CU
+static WgradPlan plan_tap(const WgradArgs& a, int sz, int tile, int launches, int target1) {
+    const WgTile t(tile);
+    WgradPlan p{};
+    if (wg_lds(sz, t) > kWgLdsMax) return p;
+    p.kind = WK_TAP;
+    p.tile = tile;
+    p.launches = launches;
+    p.lds = wg_lds(sz, t);
+    const int tiles = dw_tiles(a, t, a.taps);
+    p.splitk = a.splitk;
+    if (p.splitk <= 0) {
+        const int target = a.taps == 1 ? (a.slab && target1 == 256 && !t.pl2 ? 512 : target1) : 1536;
+        p.splitk = clamp_split((target + tiles - 1) / tiles, (k_steps(a, t.bkp(sz)) + 7) / 8);      // >= 8 K steps per block
+    }
+    p.blocks = tiles * p.splitk;
+    plan_sum(p, a);
+    return p;
+}
+
+// nine-tap kernel.  Split-K: short image rows (big dW, K = a few thousand steps): two blocks per CU measured best; long rows
+// (tiny dW, K = 10^5 steps): ~3 blocks per CU to cover the HBM stream -- but never more blocks than LDS lets a CU hold at
+// once (round 4: 28x28 128 -> 256 at batch 128 asked for 768 blocks of 64 KB, 1.5 rounds of the chip: 91 us against 82
+// with 512).  blocks_target > 0: that many blocks instead
+static WgradPlan plan_nine(const WgradArgs& a, int sz, int tile, int launches, int blocks_target) {
+    const WgTile t(tile);
+    WgradPlan p{};
+    const int wrows = wg9_wrows(sz, t, a.W);
+    const int lds = wg9_lds(sz, t, wrows);
+    if (lds > kWgLdsMax) return p;
+    p.kind = WK_NINE;
+    p.tile = tile;
+    p.launches = launches;
+    p.wrows = wrows;
+    const int tiles = dw_tiles(a, t, 1);
+    p.splitk = a.splitk;
+    if (p.splitk <= 0) {
+        long sk = a.W <= 26 ? (512 + tiles / 2) / tiles : (256L * blocks_per_cu(lds) + tiles - 1) / tiles;
+        if (blocks_target > 0) sk = (blocks_target + tiles / 2) / tiles;
+        p.splitk = clamp_split(sk, (k_steps(a, t.bkp(sz)) + 7) / 8);
+    }
+    p.blocks = tiles * p.splitk;
+    // With no more blocks than CUs, ask for > half of a CU's LDS: the dispatcher then cannot
+    // co-locate two blocks on one CU while another CU idles (measured: it does otherwise).
+    p.lds = p.blocks <= 256 && lds < 84 * 1024 ? 84 * 1024 : lds;
+    plan_sum(p, a);
+    return p;
+}
+
+// ring kernel.  Split-K: one full wave of resident blocks (256 CUs x blocks per CU by LDS, at most 3: measured best on every
+// long-row shape -- 1.5 waves of blocks cost 30 % at 104x104), or blocks_target > 0
+static WgradPlan plan_ring(const WgradArgs& a, int sz, int tile, int launches, int blocks_target) {
+    const WgTile t(tile);
+    WgradPlan p{};
+    const int lg = wg9r_lg(sz, t, a.W);
+    const long lds = wg9r_lds(sz, t, lg);
+    if (lds > kWgLdsMax) return p;
+    p.kind = WK_RING;
+    p.tile = tile;
+    p.launches = launches;
+    p.lds = (int)lds;
+    p.ring_lg = lg;
+    p.ring_g = wg9r_groups(sz, t, a.W);
+    const int tiles = dw_tiles(a, t, 1);
+    p.splitk = a.splitk;
+    if (p.splitk <= 0) {
+        const long target = blocks_target > 0 ? blocks_target : 256L * blocks_per_cu(lds);
+        // the G-group prologue must stay a small part of a block
+        p.splitk = clamp_split(target / tiles, (k_steps(a, t.bkp(sz)) + 4 * p.ring_g - 1) / (4 * p.ring_g));
+    }
+    p.blocks = tiles * p.splitk;
+    plan_sum(p, a);
+    return p;
+}
+
+static constexpr int nine_tile(int wi, int wo, int ns, int tg, int ks = 1, int cw = 1, int pl2 = 0) {
+    return wgrad_tile(wi, wo, 1, 1, tg, ks, cw, ns, pl2);
+}
+static constexpr int ring_tile(int wi, int wo, int ks, int pl2 = 0) { return wgrad_tile(wi, wo, 1, 1, 2, ks, 1, 2, pl2); }
+
+// 3x3: the nine-tap families; WK_NONE where no tile fits LDS.  launches = 3 (f16x2): the two-plane tiles first.
+// Measured (scripts/bench_wgrad.py): narrow co tiles with the taps split over two waves -- many small blocks, two waves per
+// SIMD -- beat 64x64 tiles on every Darknet-19 shape
+static WgradPlan plan_nine_taps(const WgradArgs& a, int sz, int launches) {
+    WgradPlan p{};
+#ifdef Y2_DEVBUILD
+    static const int minw = getenv("Y2DEV_WG9R_MINW") ? atoi(getenv("Y2DEV_WG9R_MINW")) : 52;
+#else
+    constexpr int minw = 52;
+#endif
+    const int wi = a.Cin >= 64 ? 2 : 1, wo = a.Cin < 64 && a.Cdy >= 64 ? 2 : 1;    // 64 x 32, 32 x 64 or 32 x 32 tiles
+    if (sz == 2 && a.W >= minw) {
+        // long rows.  f16x2: both planes in the ring, 64-pixel K steps (the two rings of the 128-pixel form leave no room
+        // at 104 / 208)
+        if (launches == 3 && (p = plan_ring(a, sz, ring_tile(wi, wo, 1, 1), 1, 0)).kind) return p;
+        // 64 ci x 32 co tiles with 128-pixel K steps measured best at 52 and 104 (3-7 % over 64-pixel steps); 32-channel
+        // inputs (208x208): 32 ci x 64 co tiles with 128-pixel K steps where that ring still leaves two blocks per CU
+        // (112x112 at batch 128: 90 us against 129; at 208x208 its 96 KB allow one block and the 64-pixel form wins,
+        // 160 against 184)
+        int ks = wi == 2 ? 2 : 1;
+        if (wo == 2 && wg9r_lds(sz, WgTile(ring_tile(1, 2, 2)), wg9r_lg(sz, WgTile(ring_tile(1, 2, 2)), a.W)) <= 80 * 1024) ks = 2;
+        if ((p = plan_ring(a, sz, ring_tile(wi, wo, ks), launches, 0)).kind) return p;
+    }
+    // f16x2: both operand planes staged per K step, 64-pixel K steps so that two blocks still share a CU's LDS
+    if (sz == 2 && launches == 3 && a.Cin >= 64 && (p = plan_nine(a, sz, nine_tile(2, 1, 2, 2, 1, 1, 1), 1, 0)).kind) return p;
+    // split-K shapes (fewer than 512 dW tiles): K steps of 128 pixels -- half the barriers and a 1.2x instead of 1.4x window at
+    // 13x13 (6-8 % faster at 26x26 and on the 512-channel 13x13 layers; the 1024 x 1024 layers, one block per tile, are 2 %
+    // faster with 64)
+    if (a.Cin >= 64 && sz == 2 && dw_tiles(a, WgTile(nine_tile(2, 1, 2, 2)), 1) < 512 &&
+        (p = plan_nine(a, sz, nine_tile(2, 1, 2, 2, 2), launches, 0)).kind)
+        return p;
+    return plan_nine(a, sz, nine_tile(wi, wo, 2, 2), launches, 0);
+}
+
+// 1x1, and the 3x3 windows no nine-tap tile holds: Cin is 32, 64 or a multiple of 128
+static WgradPlan plan_per_tap(const WgradArgs& a, int sz, int launches) {
+    if (a.Cin % 32 != 0 || (a.Cin > 128 && a.Cin % 128 != 0)) return WgradPlan{};
+    const int bi = a.Cin >= 128 ? 128 : a.Cin;
+    const int bo = a.Cdy >= 128 ? 128 : (a.Cdy >= 64 ? 64 : 32);
+    int wi = 1, wo = 1, ti = 1, to = 1;        // 32 x 32
+    if (bi == 128 && bo == 128) wi = 2, wo = 2, ti = 2, to = 2;
+    else if (bi == 128 && bo == 64) wi = 2, wo = 2, ti = 2;
+    else if (bi == 128) wi = 4;
+    else if (bi == 64 && bo == 128) wi = 2, wo = 2, to = 2;
+    else if (bi == 64 && bo == 64) wi = 2, wo = 2;
+    else if (bi == 64) wi = 2;
+    else if (bi == 32 && bo == 128) wo = 4;
+    else if (bi == 32 && bo == 64) wo = 2;
+    else if (bi != 32) return WgradPlan{};
+    // f16x2: both planes staged, the three plane products in one block (one partial per split instead of three) where
+    // twice the LDS fits: one block per CU
+    if (sz == 2 && launches == 3) {
+        const WgradPlan p = plan_tap(a, sz, wgrad_tile(wi, wo, ti, to, 1, 1, 1, 2, 1), 1, 256);
+        if (p.kind) return p;
+    }
+    return plan_tap(a, sz, wgrad_tile(wi, wo, ti, to, 1, 1, 1, 2, 0), launches, 256);
+}
+
+WgradPlan plan_wgrad(int dtype, const WgradArgs& a) {
+    const int sz = dtype_kbytes(dtype);
+    const int launches = dtype == 3 ? 3 : 1;      // f16x2 (not f16x2f: the hi planes alone) -- unless a PL2 tile fits
+    if (a.Cin % 32 != 0) return WgradPlan{};
+    if (a.taps == 9) {
+        const WgradPlan p = plan_nine_taps(a, sz, launches);
+        if (p.kind) return p;
+    }
+    return plan_per_tap(a, sz, launches);
+}
+
+hipError_t launch_wgrad_auto(int dtype, const WgradArgs& a0, hipStream_t s) {
+    static const int xcd_mode = getenv("Y2_XCD_WGRAD") ? atoi(getenv("Y2_XCD_WGRAD")) : 1;
+    WgradArgs a = a0;
+    a.xcd = xcd_mode;
+    const WgradPlan p = plan_wgrad(dtype, a);
+    if (p.kind == WK_TAP) return launch_wgrad(dtype, p, a, s);
+    return launch_wgrad9(dtype, p, a, s);
+}
+
+#ifdef Y2_DEVBUILD
+// development variants (f16) for scripts/bench_wgrad.py: forced plans run by the family launchers.
+// 0 / 1: the product policy within the per-tap / nine-tap families; >= 100: per-tap 128 x 128 tiles, stages x the blocks
+// target of the 1x1 form
+struct WgVariant {
+    int id;
+    WgradKind kind;
+    int tile;
+    int target;     // WK_TAP: target1 of plan_tap; the nine-tap families: blocks_target
+};
+static constexpr int tap_tile(int ns) { return wgrad_tile(2, 2, 2, 2, 1, 1, 1, ns, 0); }
+static const WgVariant kWgVariants[] = {
+    {100, WK_TAP, tap_tile(2), 256}, {101, WK_TAP, tap_tile(3), 256}, {102, WK_TAP, tap_tile(4), 256},
+    {103, WK_TAP, tap_tile(2), 512}, {104, WK_TAP, tap_tile(3), 512}, {105, WK_TAP, tap_tile(5), 256},
+    {106, WK_TAP, tap_tile(4), 128}, {107, WK_TAP, tap_tile(2), 768},
+    // explicit block shapes: nine_tile(WI, WO, NS, TG, KS, CW)
+    {2, WK_NINE, nine_tile(2, 1, 2, 1), 0},
+    {3, WK_NINE, nine_tile(1, 2, 2, 1), 0},
+    {4, WK_NINE, nine_tile(1, 1, 2, 1), 0},
+    {5, WK_NINE, nine_tile(2, 2, 2, 1), 0},
+    {6, WK_NINE, nine_tile(2, 2, 2, 1), 0},
+    {7, WK_NINE, nine_tile(2, 2, 3, 1), 0},
+    {8, WK_NINE, nine_tile(2, 2, 4, 1), 0},
+    {9, WK_NINE, nine_tile(2, 2, 2, 2), 0},       // two tap groups, 8 waves
+    {10, WK_NINE, nine_tile(2, 2, 3, 2), 0},
+    {11, WK_NINE, nine_tile(2, 1, 2, 2), 0},      // 64 x 32 tiles, 4 waves
+    {12, WK_NINE, nine_tile(1, 1, 2, 2), 0},      // 32 x 32 tiles, 2 waves
+    {13, WK_NINE, nine_tile(1, 2, 2, 2), 0},      // 32 x 64 tiles, 4 waves
+    {14, WK_NINE, nine_tile(2, 1, 3, 2), 0},      // 64 x 32, 3 stages
+    {16, WK_NINE, nine_tile(2, 1, 2, 1), 0},      // 64 x 32 tiles, 2 waves (no tap split)
+    {50, WK_NINE, nine_tile(2, 1, 2, 2, 2), 0},   // 64 x 32, K step of 128 pixels
+    {51, WK_NINE, nine_tile(2, 2, 2, 2, 2), 0},   // 64 x 64, 8 waves, K step 128
+    {52, WK_NINE, nine_tile(1, 2, 2, 2, 2), 0},
+    // two co sub-tiles per wave
+    {60, WK_NINE, nine_tile(2, 2, 2, 2, 1, 2), 256},   // 64 ci x 128 co, 8 waves, one block per CU
+    {61, WK_NINE, nine_tile(2, 2, 2, 2, 2, 2), 256},   // same, K step 128
+    {62, WK_NINE, nine_tile(2, 1, 2, 2, 1, 2), 512},   // 64 ci x 64 co, 4 waves, two blocks per CU
+    {63, WK_NINE, nine_tile(2, 1, 2, 2, 2, 2), 512},
+    {64, WK_NINE, nine_tile(4, 1, 2, 2, 1, 2), 256},   // 128 ci x 64 co, 8 waves
+    {65, WK_NINE, nine_tile(4, 1, 2, 2, 2, 2), 256},
+    {66, WK_NINE, nine_tile(2, 2, 3, 2, 1, 2), 256},   // 3 stages
+    {67, WK_NINE, nine_tile(4, 2, 2, 2, 1, 2), 256},   // 128 ci x 128 co, 16 waves
+    {68, WK_NINE, nine_tile(2, 1, 3, 2, 1, 2), 512},
+    {69, WK_NINE, nine_tile(2, 2, 2, 2, 1, 2), 512},   // 64 x 128, two blocks per CU
+    // ring form (long rows): ring_tile(WI, WO, KS)
+    {30, WK_RING, ring_tile(2, 1, 1), 768},       // 64 x 32, 4 waves
+    {31, WK_RING, ring_tile(1, 2, 1), 768},       // 32 x 64, 4 waves
+    {32, WK_RING, ring_tile(1, 1, 1), 768},       // 32 x 32, 2 waves
+    {33, WK_RING, ring_tile(2, 2, 1), 768},       // 64 x 64, 8 waves
+    {34, WK_RING, ring_tile(2, 1, 1), 512},
+    {35, WK_RING, ring_tile(1, 2, 1), 512},
+    {36, WK_RING, ring_tile(2, 2, 1), 512},
+    {37, WK_RING, ring_tile(2, 1, 1), 1024},
+    {38, WK_RING, ring_tile(1, 2, 1), 1024},
+    {39, WK_RING, ring_tile(2, 2, 1), 1024},
+    {40, WK_RING, ring_tile(1, 2, 1), 384},
+    {41, WK_RING, ring_tile(1, 2, 1), 256},
+    {42, WK_RING, ring_tile(2, 1, 1), 384},
+    {43, WK_RING, ring_tile(2, 1, 1), 256},
+    {44, WK_RING, ring_tile(1, 2, 2), 0},         // ring, K step 128
+    {45, WK_RING, ring_tile(2, 1, 2), 0},
+    {46, WK_RING, ring_tile(1, 2, 2), 512},
+    {47, WK_RING, ring_tile(2, 1, 2), 512},
+};
+static hipError_t run_variant(int variant, const WgradArgs& a, hipStream_t s) {
+    WgradPlan p{};
+    if (variant == 0) p = plan_per_tap(a, 2, 1);
+    else if (variant == 1 && a.taps == 9 && a.Cin % 32 == 0) p = plan_nine_taps(a, 2, 1);
+    for (const WgVariant& v : kWgVariants) {
+        if (v.id != variant) continue;
+        if (v.kind == WK_TAP) p = plan_tap(a, 2, v.tile, 1, v.target);
+        else if (a.taps == 9) p = v.kind == WK_NINE ? plan_nine(a, 2, v.tile, 1, v.target) : plan_ring(a, 2, v.tile, 1, v.target);
+    }
+    return p.kind == WK_TAP ? launch_wgrad(1, p, a, s) : launch_wgrad9(1, p, a, s);
+}
+hipError_t launch_wgrad_variant(int variant, const WgradArgs& a, hipStream_t s) {
+    return variant < 2 || variant >= 100 ? run_variant(variant, a, s) : hipErrorInvalidValue;
+}
+hipError_t launch_wgrad9_variant(int variant, const WgradArgs& a, hipStream_t s) {
+    return variant >= 2 && variant < 100 ? run_variant(variant, a, s) : hipErrorInvalidValue;
+}
+#endif  // Y2_DEVBUILD
 
 }  // namespace y2

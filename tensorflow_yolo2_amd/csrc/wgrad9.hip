@@ -13,15 +13,6 @@
 #include "common.h"
 #include "conv_epilogue.h"
 #include "kernels.h"
-#include "wgrad_finish.h"
-// The in-kernel split-K sum (wgrad_finish.h) measured slower in every form (profiles/r05_ab_wgrad_finish.txt) and its mere
-// presence cost the weight gradients 1.8 % (2.53 vs 2.49 ms per step, same box): it is compiled into the DEVELOPMENT
-// library only (make dev, Y2_WGRAD_FINISH=<max partials>); the product kernels store their partials plainly.
-#ifdef Y2_DEVBUILD
-#define Y2_FIN_STORE(p, v) do { if (a.cnt_stride) slab_store((p), (v)); else *(p) = (v); } while (0)
-#else
-#define Y2_FIN_STORE(p, v) (*(p) = (v))
-#endif
 
 namespace y2 {
 
@@ -59,10 +50,10 @@ Y2_DEV int wg9_swz(int row) {
 // PL2 (f16x2 mode, round 5): x and dy are SPLIT tensors -- a cell is [C halves hi][C halves lo] -- and the block forms all
 // three plane products itself: both planes of the X window and of the dY tile are staged per K step (2x the LDS of the
 // one-plane form) and every fragment pair feeds three MFMAs, hi hi + lo hi + hi lo, into ONE accumulator.  Against
-// three launches on plane pairs (WgradArgs::quads, the first form of the mode): 2/3 of the staging and of the LDS
+// three launches on plane pairs (WgradArgs::quads; where no two-plane tile fits): 2/3 of the staging and of the LDS
 // fragment reads per MFMA, one partial tile per split instead of three.
 template <typename T, int WI, int WO, int NS, int TG, int T0, int NTAP, int KS = 1, int CW = 1, bool PL2 = false>
-Y2_DEV void wg9_body(const WgradArgs& a, int wrows, char* smem, int* s_fin) {
+Y2_DEV void wg9_body(const WgradArgs& a, int wrows, char* smem) {
     typedef Wg9Cfg<T, WI, WO, TG, KS, CW> Cfg;
     constexpr int NW = Cfg::NW, SZ = Cfg::SZ, BI = Cfg::BI, BO = Cfg::BO, BKP = Cfg::BKP;
     constexpr int ROWX = Cfg::ROWX, ROWY = Cfg::ROWY;
@@ -143,7 +134,7 @@ Y2_DEV void wg9_body(const WgradArgs& a, int wrows, char* smem, int* s_fin) {
 #pragma unroll
     for (int t = 0; t < NTAP; ++t) shift[t] = ((T0 + t) / 3) * pitch + ((T0 + t) % 3);
 
-    // loads per wave per stage (the launcher makes the X window a multiple of RPIX*NW rows)
+    // loads per wave per stage (the plan makes the X window a multiple of RPIX*NW rows: wg9_wrows)
     const int lps = NPL * (xpieces / NW + Cfg::NIY / NW);
 #pragma unroll
     for (int s0 = 0; s0 < NS - 1; ++s0)
@@ -246,48 +237,22 @@ Y2_DEV void wg9_body(const WgradArgs& a, int wrows, char* smem, int* s_fin) {
                 if (ci < a.Cin) {
                     const size_t o = ((size_t)(T0 + t) * a.Cin + ci) * a.Cout + co;
                     if (a.splitk == 1 && a.quads == 1) a.dW[o] = acc[t][j][q] * a.scale;
-                    else if (a.slab) { float* sp = a.slab + (size_t)(a.part0 + split) * 9 * a.Cin * a.Cout + o; Y2_FIN_STORE(sp, acc[t][j][q]); }
+                    else if (a.slab) a.slab[(size_t)(a.part0 + split) * 9 * a.Cin * a.Cout + o] = acc[t][j][q];
                     else atomicAdd(a.dW + o, acc[t][j][q] * a.scale);
                 }
             }
     }
-#ifdef Y2_DEVBUILD
-    if (a.slab && a.cnt_stride) {     // the split-K sum rides in this kernel (wgrad_finish.h; development library only)
-        const size_t n9 = (size_t)9 * a.Cin * a.Cout;
-        splitk_finish(s_fin, a.tile_cnt + (size_t)(it * nOT + ot) * a.cnt_stride, a.part0 + split, a.splitk * a.quads,
-                      [&](int first, int stride, int count, bool final) __attribute__((always_inline)) {
-#pragma unroll 1
-            for (int j = 0; j < CW; ++j) {
-                const int co = co0 + (wo * CW + j) * 32 + r32;
-                if (co >= a.Cout) continue;
-#pragma unroll 1
-                for (int t = 0; t < NTAP; ++t)
-#pragma unroll 1
-                    for (int q = 0; q < 16; ++q) {
-                        const int ci = ci0 + wi * 32 + acc_row(q, hh);
-                        if (ci < a.Cin) {
-                            const size_t o = ((size_t)(T0 + t) * a.Cin + ci) * a.Cout + co;
-                            const float v = splitk_sum_slots(a.slab + (size_t)first * n9 + o, (size_t)stride * n9, count);
-                            if (final) a.dW[o] = v * a.scale;
-                            else slab_store(a.slab + (size_t)first * n9 + o, v);
-                        }
-                    }
-            }
-        });
-    }
-#endif
 }
 
 template <typename T, int WI, int WO, int NS, int TG, int KS = 1, int CW = 1, bool PL2 = false>
 __global__ __launch_bounds__(WI* WO* TG * 64) void wgrad9_kernel(WgradArgs a, int wrows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* const s_fin = (int*)(smem + a.fin_lds_off);
     if constexpr (TG == 1) {
-        wg9_body<T, WI, WO, NS, 1, 0, 9, KS, CW, PL2>(a, wrows, smem, s_fin);
+        wg9_body<T, WI, WO, NS, 1, 0, 9, KS, CW, PL2>(a, wrows, smem);
     } else {
         const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        if (w < WI * WO) wg9_body<T, WI, WO, NS, 2, 0, 5, KS, CW, PL2>(a, wrows, smem, s_fin);   // same barrier count in both arms
-        else wg9_body<T, WI, WO, NS, 2, 5, 4, KS, CW, PL2>(a, wrows, smem, s_fin);
+        if (w < WI * WO) wg9_body<T, WI, WO, NS, 2, 0, 5, KS, CW, PL2>(a, wrows, smem);   // same barrier count in both arms
+        else wg9_body<T, WI, WO, NS, 2, 5, 4, KS, CW, PL2>(a, wrows, smem);
     }
 }
 
@@ -312,7 +277,7 @@ Y2_DEV typename Elem<T>::frag tr_frag_off(uint32_t o0, uint32_t o1) {
 }
 
 template <typename T, int WI, int WO, int TG, int T0, int NTAP, int KS = 1, bool PL2 = false>
-Y2_DEV void wg9r_body(const WgradArgs& a, int lgR, int G, char* smem, int* s_fin) {
+Y2_DEV void wg9r_body(const WgradArgs& a, int lgR, int G, char* smem) {
     typedef Wg9Cfg<T, WI, WO, TG, KS> Cfg;
     constexpr int NW = Cfg::NW, SZ = Cfg::SZ, BI = Cfg::BI, BO = Cfg::BO, BKP = Cfg::BKP;
     constexpr int ROWX = Cfg::ROWX, ROWY = Cfg::ROWY;
@@ -467,312 +432,126 @@ Y2_DEV void wg9r_body(const WgradArgs& a, int lgR, int G, char* smem, int* s_fin
                 if (ci < a.Cin) {
                     const size_t o = ((size_t)(T0 + t) * a.Cin + ci) * a.Cout + co;
                     if (a.splitk == 1 && a.quads == 1) a.dW[o] = acc[t][q] * a.scale;
-                    else if (a.slab) { float* sp = a.slab + (size_t)(a.part0 + split) * 9 * a.Cin * a.Cout + o; Y2_FIN_STORE(sp, acc[t][q]); }
+                    else if (a.slab) a.slab[(size_t)(a.part0 + split) * 9 * a.Cin * a.Cout + o] = acc[t][q];
                     else atomicAdd(a.dW + o, acc[t][q] * a.scale);
                 }
             }
     }
-#ifdef Y2_DEVBUILD
-    if (a.slab && a.cnt_stride) {     // the split-K sum rides in this kernel (wgrad_finish.h; development library only)
-        const size_t n9 = (size_t)9 * a.Cin * a.Cout;
-        splitk_finish(s_fin, a.tile_cnt + (size_t)(it * nOT + ot) * a.cnt_stride, a.part0 + split, a.splitk * a.quads,
-                      [&](int first, int stride, int count, bool final) __attribute__((always_inline)) {
-            if (co >= a.Cout) return;
-#pragma unroll 1
-            for (int t = 0; t < NTAP; ++t)
-#pragma unroll 1
-                for (int q = 0; q < 16; ++q) {
-                    const int ci = ci0 + wi * 32 + acc_row(q, hh);
-                    if (ci < a.Cin) {
-                        const size_t o = ((size_t)(T0 + t) * a.Cin + ci) * a.Cout + co;
-                        const float v = splitk_sum_slots(a.slab + (size_t)first * n9 + o, (size_t)stride * n9, count);
-                        if (final) a.dW[o] = v * a.scale;
-                        else slab_store(a.slab + (size_t)first * n9 + o, v);
-                    }
-                }
-        });
-    }
-#endif
 }
 
 template <typename T, int WI, int WO, int TG, int KS = 1, bool PL2 = false>
 __global__ __launch_bounds__(WI* WO* TG * 64) void wgrad9r_kernel(WgradArgs a, int lgR, int G) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* const s_fin = (int*)(smem + a.fin_lds_off);
     if constexpr (TG == 1) {
-        wg9r_body<T, WI, WO, 1, 0, 9, KS, PL2>(a, lgR, G, smem, s_fin);
+        wg9r_body<T, WI, WO, 1, 0, 9, KS, PL2>(a, lgR, G, smem);
     } else {
         const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        if (w < WI * WO) wg9r_body<T, WI, WO, 2, 0, 5, KS, PL2>(a, lgR, G, smem, s_fin);
-        else wg9r_body<T, WI, WO, 2, 5, 4, KS, PL2>(a, lgR, G, smem, s_fin);
+        if (w < WI * WO) wg9r_body<T, WI, WO, 2, 0, 5, KS, PL2>(a, lgR, G, smem);
+        else wg9r_body<T, WI, WO, 2, 5, 4, KS, PL2>(a, lgR, G, smem);
     }
 }
 
-// blocks_target: split-K so that tiles * splitk ~ blocks_target; 0 = one full wave of resident
-// blocks (256 CUs x blocks per CU by LDS, at most 3: measured best on every long-row shape --
-// 1.5 waves of blocks cost 30 % at 104x104)
-template <typename T, int WI, int WO, int TG, int KS = 1, bool PL2 = false>
-static hipError_t wg9r_launch(WgradArgs a, hipStream_t s, int blocks_target = 0) {
-    typedef Wg9Cfg<T, WI, WO, TG, KS> Cfg;
-    static_assert(Cfg::NIY % Cfg::NW == 0, "dY pieces must split evenly over waves");
-    const int pitch = a.W + 1;
-    const int wrows = Cfg::BKP + 2 * pitch + 2;
-    const int G = (wrows + Cfg::BKP - 1) / Cfg::BKP;
-    int lgR = 7;
-    while ((1 << lgR) < Cfg::BKP * (G + 1)) ++lgR;
-    // (+ 16 bytes for the finish flag of the opt-in in-kernel sum, wgrad_finish.h, only when it is on: a request of
-    //  exactly 1/2 or 1/3 of the CU's LDS must stay that -- the blocks-per-CU count below depends on it)
-    const size_t fin16 = wgrad_finish_max_parts() > 0 ? 16 : 0;
-    const size_t lds = (PL2 ? 2 : 1) * (((size_t)Cfg::ROWX << lgR) + 2 * (size_t)Cfg::YS) + fin16;
-    if (lds > 160 * 1024) return hipErrorOutOfMemory;
-    a.fin_lds_off = (int)(lds - fin16);
-    if (PL2) a.quads = 1;       // the three plane products are formed inside the block
-    auto kern = wgrad9r_kernel<T, WI, WO, TG, KS, PL2>;
-    const int nIT = (a.Cin + Cfg::BI - 1) / Cfg::BI, nOT = (a.Cout + Cfg::BO - 1) / Cfg::BO;
-    const long Mp = (long)bbody_pixels(a.N, a.H, a.W);
-    const long ksteps = (Mp + Cfg::BKP - 1) / Cfg::BKP;
-    const int tiles = nIT * nOT;
-    if (blocks_target <= 0) {
-        int bpc = (int)((160 * 1024) / lds);
-        bpc = bpc > 3 ? 3 : (bpc < 1 ? 1 : bpc);
-        blocks_target = 256 * bpc;
-    }
-    if (a.splitk <= 0) {
-        long sk = blocks_target / tiles;
-        const long maxsk = (ksteps + 4 * G - 1) / (4 * G);   // the G-group prologue must stay a small part of a block
-        if (sk > maxsk) sk = maxsk;
-        if (sk < 1) sk = 1;
-        a.splitk = (int)sk;
-    }
-    static size_t attr = 0;
-    if (lds > attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr = lds;
-    }
-    hipError_t e = wgrad_split_prepare(a, s);
-    if (e != hipSuccess) return e;
-    e = wgrad_launch_quads(kern, dim3(tiles * a.splitk), dim3(Cfg::NT), lds, s, a, lgR, G);
-    return e != hipSuccess ? e : wgrad_split_finish(a, s);
-}
 
-template <typename T, int WI, int WO, int NS, int TG = 1, int KS = 1, int CW = 1, bool PL2 = false>
-static hipError_t wg9_launch_ns(WgradArgs a, hipStream_t s, int blocks_target = 0) {
+// ---------------------------------------------------------------------------
+// The launchers of the two nine-tap families: one tile of the plan (plan_wgrad, wgrad.hip) each
+// ---------------------------------------------------------------------------
+template <typename T, int WI, int WO, int NS, int TG, int KS, int CW, bool PL2>
+static hipError_t wg9_run(const WgradPlan& p, const WgradArgs& a, hipStream_t s) {
     typedef Wg9Cfg<T, WI, WO, TG, KS, CW> Cfg;
+    constexpr WgTile t(wgrad_tile(WI, WO, 1, 1, TG, KS, CW, NS, PL2));
     static_assert(Cfg::NIY % Cfg::NW == 0, "dY pieces must split evenly over waves");
-    const int pitch = a.W + 1;
-    int wrows = Cfg::BKP + 2 * pitch + 2;
-    // deeper rings count the loads in flight, so every wave must issue the same number of pieces; two
-    // stages drain to zero and take whole pieces only
-    const int gran = NS > 2 ? Cfg::RPIX * Cfg::NW : Cfg::RPIX;
-    wrows = (wrows + gran - 1) / gran * gran;
-    const size_t fin16 = wgrad_finish_max_parts() > 0 ? 16 : 0;     // the finish flag (wgrad_finish.h), when that form is on
-    size_t lds = NS * (PL2 ? 2 : 1) * ((size_t)wrows * Cfg::ROWX + Cfg::YS) + fin16;
-    if (lds > 160 * 1024) return hipErrorOutOfMemory;
-    a.fin_lds_off = (int)(lds - fin16);
-    if (PL2) a.quads = 1;       // the three plane products are formed inside the block
-    auto kern = wgrad9_kernel<T, WI, WO, NS, TG, KS, CW, PL2>;
-    const int nIT = (a.Cin + Cfg::BI - 1) / Cfg::BI, nOT = (a.Cout + Cfg::BO - 1) / Cfg::BO;
-    const long Mp = (long)bbody_pixels(a.N, a.H, a.W);
-    const long ksteps = (Mp + Cfg::BKP - 1) / Cfg::BKP;
-    const int tiles = nIT * nOT;
-    if (a.splitk <= 0) {
-        // short image rows (big dW, K = a few thousand steps): two blocks per CU measured best;
-        // long rows (tiny dW, K = 10^5 steps): ~3 blocks per CU to cover the HBM stream -- but never more blocks than
-        // LDS lets a CU hold at once (round 4: 28x28 128 -> 256 at batch 128 asked for 768 blocks of 64 KB, 1.5
-        // rounds of the chip: 91 us against 82 with 512)
-        int bpc = (int)((160 * 1024) / lds);
-        bpc = bpc > 3 ? 3 : (bpc < 1 ? 1 : bpc);
-        const long long_rows = 256L * bpc;
-        long sk = a.W <= 26 ? (512 + tiles / 2) / tiles : (long_rows + tiles - 1) / tiles;
-        if (blocks_target > 0) sk = (blocks_target + tiles / 2) / tiles;
-        const long maxsk = (ksteps + 7) / 8;
-        if (sk > maxsk) sk = maxsk;
-        if (sk < 1) sk = 1;
-        a.splitk = (int)sk;
-    }
-    // With no more blocks than CUs, ask for > half of a CU's LDS: the dispatcher then cannot
-    // co-locate two blocks on one CU while another CU idles (measured: it does otherwise).
-    if (tiles * a.splitk <= 256 && lds < 84 * 1024) lds = 84 * 1024;
-    static size_t attr = 0;
-    if (lds > attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr = lds;
-    }
-    hipError_t e = wgrad_split_prepare(a, s);
-    if (e != hipSuccess) return e;
-    e = wgrad_launch_quads(kern, dim3(tiles * a.splitk), dim3(Cfg::NT), lds, s, a, wrows);
-    return e != hipSuccess ? e : wgrad_split_finish(a, s);
+    static_assert(wg9_lds(sizeof(T), t, 1) == NS * (PL2 ? 2 : 1) * (Cfg::ROWX + Cfg::YS), "wg9_lds is the kernel's staging");
+    static_assert(wg9_wrows(sizeof(T), t, 0) % (NS > 2 ? Cfg::RPIX * Cfg::NW : Cfg::RPIX) == 0, "whole pieces per wave");
+    static int attr = 0;
+    return wgrad_run(wgrad9_kernel<T, WI, WO, NS, TG, KS, CW, PL2>, attr, p, a, Cfg::NT, s, p.wrows);
 }
-// deepest ring that fits (4 stages where the window is small)
-template <typename T, int WI, int WO>
-static hipError_t wg9_launch(const WgradArgs& a, hipStream_t s, int ns = 0) {
-    typedef Wg9Cfg<T, WI, WO> Cfg;
-    const int gran = Cfg::RPIX * Cfg::NW;
-    const int wrows = (Cfg::BKP + 2 * (a.W + 1) + 2 + gran - 1) / gran * gran;
-    const size_t stage = (size_t)wrows * Cfg::ROWX + Cfg::YS;
-    (void)stage;
-    if (ns == 0) ns = 2;   // deeper rings measured slower on every Darknet-19 shape (bench_wgrad.py)
-    if (ns >= 4) return wg9_launch_ns<T, WI, WO, 4>(a, s);
-    if (ns == 3) return wg9_launch_ns<T, WI, WO, 3>(a, s);
-    return wg9_launch_ns<T, WI, WO, 2>(a, s);
+template <typename T, int WI, int WO, int KS, bool PL2>
+static hipError_t wg9r_run(const WgradPlan& p, const WgradArgs& a, hipStream_t s) {
+    typedef Wg9Cfg<T, WI, WO, 2, KS> Cfg;
+    constexpr WgTile t(wgrad_tile(WI, WO, 1, 1, 2, KS, 1, 2, PL2));
+    static_assert(Cfg::NIY % Cfg::NW == 0, "dY pieces must split evenly over waves");
+    static_assert(wg9r_lds(sizeof(T), t, 7) == (PL2 ? 2 : 1) * ((Cfg::ROWX << 7) + 2 * Cfg::YS), "wg9r_lds is the kernel's staging");
+    static int attr = 0;
+    return wgrad_run(wgrad9r_kernel<T, WI, WO, 2, KS, PL2>, attr, p, a, Cfg::NT, s, p.ring_lg, p.ring_g);
 }
 
 template <typename T>
-static hipError_t wg9_T(const WgradArgs& a, hipStream_t s) {
-    // measured (scripts/bench_wgrad.py): narrow co tiles with the taps split over two waves --
-    // many small blocks, two waves per SIMD -- beat 64x64 tiles on every Darknet-19 shape
-    if constexpr (sizeof(T) == 2) {
-        // long rows: the ring form stages 64 new rows per step instead of the whole window
+static hipError_t wg9_T(const WgradPlan& p, const WgradArgs& a, hipStream_t s) {
+#define W9(WI, WO, NS, TG, KS, CW, PL2) \
+    case wgrad_tile(WI, WO, 1, 1, TG, KS, CW, NS, PL2): return wg9_run<T, WI, WO, NS, TG, KS, CW, PL2>(p, a, s);
+#define WR(WI, WO, KS, PL2) \
+    case wgrad_tile(WI, WO, 1, 1, 2, KS, 1, 2, PL2): return wg9r_run<T, WI, WO, KS, PL2>(p, a, s);
+    if (p.kind == WK_NINE) {
+        switch (p.tile) {
+            W9(2, 1, 2, 2, 1, 1, 0)
+            W9(2, 1, 2, 2, 2, 1, 0)
+            W9(1, 2, 2, 2, 1, 1, 0)
+            W9(1, 1, 2, 2, 1, 1, 0)
+        }
+        if constexpr (sizeof(T) == 2) {
+            switch (p.tile) { W9(2, 1, 2, 2, 1, 1, 1) }
+        }
 #ifdef Y2_DEVBUILD
-        static const int minw = getenv("Y2DEV_WG9R_MINW") ? atoi(getenv("Y2DEV_WG9R_MINW")) : 52;
-#else
-        constexpr int minw = 52;
+        if constexpr (std::is_same<T, half_t>::value) {
+            switch (p.tile) {
+                W9(2, 1, 2, 1, 1, 1, 0)
+                W9(1, 2, 2, 1, 1, 1, 0)
+                W9(1, 1, 2, 1, 1, 1, 0)
+                W9(2, 2, 2, 1, 1, 1, 0)
+                W9(2, 2, 3, 1, 1, 1, 0)
+                W9(2, 2, 4, 1, 1, 1, 0)
+                W9(2, 2, 2, 2, 1, 1, 0)
+                W9(2, 2, 3, 2, 1, 1, 0)
+                W9(2, 1, 3, 2, 1, 1, 0)
+                W9(2, 2, 2, 2, 2, 1, 0)
+                W9(1, 2, 2, 2, 2, 1, 0)
+                W9(2, 2, 2, 2, 1, 2, 0)
+                W9(2, 2, 2, 2, 2, 2, 0)
+                W9(2, 1, 2, 2, 1, 2, 0)
+                W9(2, 1, 2, 2, 2, 2, 0)
+                W9(4, 1, 2, 2, 1, 2, 0)
+                W9(4, 1, 2, 2, 2, 2, 0)
+                W9(2, 2, 3, 2, 1, 2, 0)
+                W9(4, 2, 2, 2, 1, 2, 0)
+                W9(2, 1, 3, 2, 1, 2, 0)
+            }
+        }
 #endif
-        if (a.W >= minw) {
-            hipError_t e;
-            // f16x2 mode: both planes in the ring (PL2, see wg9_body), 64-pixel K steps (the two rings of the 128-pixel form
-            // leave no room at 104 / 208)
-            static const bool quads_form_r = getenv("Y2_SPLIT_WGRAD_QUADS") != nullptr;
-            if (a.quads == 3 && !quads_form_r) {
-                if (a.Cin >= 64) e = wg9r_launch<T, 2, 1, 2, 1, true>(a, s);
-                else if (a.Cdy >= 64) e = wg9r_launch<T, 1, 2, 2, 1, true>(a, s);
-                else e = wg9r_launch<T, 1, 1, 2, 1, true>(a, s);
-                if (e != hipErrorOutOfMemory) return e;
-                (void)hipGetLastError();
+    } else if (p.kind == WK_RING) {
+        if constexpr (sizeof(T) == 2) {      // the ring form: 16-bit elements
+            switch (p.tile) {
+                WR(2, 1, 1, 1)
+                WR(1, 2, 1, 1)
+                WR(1, 1, 1, 1)
+                WR(2, 1, 2, 0)
+                WR(1, 2, 2, 0)
+                WR(1, 2, 1, 0)
+                WR(1, 1, 1, 0)
             }
-            // 64 ci x 32 co tiles with 128-pixel K steps measured best at 52 and 104 (3-7 % over 64-pixel
-            // steps); 32-channel inputs (208x208): 32 ci x 64 co tiles, 64-pixel steps
-            if (a.Cin >= 64) e = wg9r_launch<T, 2, 1, 2, 2>(a, s);
-            else if (a.Cdy >= 64) {
-                // 128-pixel K steps where the ring of that form still leaves two blocks per CU (112x112 at batch 128:
-                // 90 us against 129; at 208x208 its 96 KB allow one block and the 64-pixel form wins, 160 against 184)
-                typedef Wg9Cfg<T, 1, 2, 2, 2> C2;
-                const int wrows2 = C2::BKP + 2 * (a.W + 1) + 2;
-                const int G2 = (wrows2 + C2::BKP - 1) / C2::BKP;
-                int lg = 7;
-                while ((1 << lg) < C2::BKP * (G2 + 1)) ++lg;
-                const size_t lds2 = ((size_t)C2::ROWX << lg) + 2 * (size_t)C2::YS;
-                e = lds2 <= 80 * 1024 ? wg9r_launch<T, 1, 2, 2, 2>(a, s) : wg9r_launch<T, 1, 2, 2>(a, s);
-            }
-            else e = wg9r_launch<T, 1, 1, 2>(a, s);
-            if (e != hipErrorOutOfMemory) return e;
-            (void)hipGetLastError();
-        }
-    }
-    if constexpr (sizeof(T) == 2) {
-        // f16x2 mode (a.quads == 3): both operand planes staged per K step, the three plane products in one block (PL2) --
-        // 64-pixel K steps so that two blocks still share a CU's LDS.  Y2_SPLIT_WGRAD_QUADS=1: three launches on plane pairs
-        static const bool quads_form = getenv("Y2_SPLIT_WGRAD_QUADS") != nullptr;
-        if (a.quads == 3 && a.Cin >= 64 && !quads_form) {
-            hipError_t e = wg9_launch_ns<T, 2, 1, 2, 2, 1, 1, true>(a, s);
-            if (e != hipErrorOutOfMemory) return e;
-            (void)hipGetLastError();
-        }
-    }
-    if (a.Cin >= 64) {
-        // split-K shapes (fewer than 512 dW tiles): K steps of 128 pixels -- half the barriers and a
-        // 1.2x instead of 1.4x window at 13x13 (6-8 % faster at 26x26 and on the 512-channel 13x13 layers;
-        // the 1024 x 1024 layers, one block per tile, are 2 % faster with 64)
-        const int tiles = ((a.Cin + 63) / 64) * ((a.Cout + 31) / 32);
-        if (sizeof(T) == 2 && tiles < 512) {
-            hipError_t e = wg9_launch_ns<T, 2, 1, 2, 2, 2>(a, s);
-            if (e != hipErrorOutOfMemory) return e;
-            (void)hipGetLastError();
-        }
-        return wg9_launch_ns<T, 2, 1, 2, 2>(a, s);     // 64 ci x 32 co, 4 waves
-    }
-    if (a.Cdy >= 64) return wg9_launch_ns<T, 1, 2, 2, 2>(a, s);     // 32 ci x 64 co, 4 waves
-    return wg9_launch_ns<T, 1, 1, 2, 2>(a, s);
-}
-
-// 3x3 only; the window grows with the image row, so this form is for short rows
-hipError_t launch_wgrad9(int dtype, const WgradArgs& a0, hipStream_t s) {
-    WgradArgs a = a0;
-    if (a.taps != 9 || a.Cin % 32 != 0) return hipErrorInvalidValue;
-    dtype = wgrad_split_args(dtype, a);
-    switch (dtype) {
-        case 0: return wg9_T<float>(a, s);
-        case 1: return wg9_T<half_t>(a, s);
-        case 2: return wg9_T<bf16_t>(a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-}  // namespace y2
-
-namespace y2 {
-// policy: all-taps kernel where the image rows are short (window ~1.5-2x the K step),
-// per-tap kernel on the large feature maps and for 1x1 filters
 #ifdef Y2_DEVBUILD
-// development variants (f16): explicit block shapes
-hipError_t launch_wgrad9_variant(int variant, const WgradArgs& a0, hipStream_t s) {
+            if constexpr (std::is_same<T, half_t>::value) {
+                switch (p.tile) {
+                    WR(2, 1, 1, 0)
+                    WR(2, 2, 1, 0)
+                }
+            }
+#endif
+        }
+    }
+#undef WR
+#undef W9
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_wgrad9(int dtype, const WgradPlan& p, const WgradArgs& a0, hipStream_t s) {
+    if ((p.kind != WK_NINE && p.kind != WK_RING) || a0.taps != 9) return hipErrorInvalidValue;
     WgradArgs a = a0;
-    wgrad_split_args(1, a);
-    switch (variant) {
-        case 2: return wg9_launch<half_t, 2, 1>(a, s);
-        case 3: return wg9_launch<half_t, 1, 2>(a, s);
-        case 4: return wg9_launch<half_t, 1, 1>(a, s);
-        case 5: return wg9_launch<half_t, 2, 2>(a, s);
-        case 6: return wg9_launch<half_t, 2, 2>(a, s, 2);
-        case 7: return wg9_launch<half_t, 2, 2>(a, s, 3);
-        case 8: return wg9_launch<half_t, 2, 2>(a, s, 4);
-        case 9: return wg9_launch_ns<half_t, 2, 2, 2, 2>(a, s);      // two tap groups, 8 waves
-        case 10: return wg9_launch_ns<half_t, 2, 2, 3, 2>(a, s);
-        case 11: return wg9_launch_ns<half_t, 2, 1, 2, 2>(a, s);     // 64 x 32 tiles, 4 waves
-        case 12: return wg9_launch_ns<half_t, 1, 1, 2, 2>(a, s);     // 32 x 32 tiles, 2 waves
-        case 13: return wg9_launch_ns<half_t, 1, 2, 2, 2>(a, s);     // 32 x 64 tiles, 4 waves
-        case 14: return wg9_launch_ns<half_t, 2, 1, 3, 2>(a, s);     // 64 x 32, 3 stages
-        case 16: return wg9_launch_ns<half_t, 2, 1, 2, 1>(a, s);     // 64 x 32 tiles, 2 waves (no tap split)
-        case 50: return wg9_launch_ns<half_t, 2, 1, 2, 2, 2>(a, s);   // 64 x 32, K step of 128 pixels
-        // two co sub-tiles per wave
-        case 60: return wg9_launch_ns<half_t, 2, 2, 2, 2, 1, 2>(a, s, 256);   // 64 ci x 128 co, 8 waves, one block per CU
-        case 61: return wg9_launch_ns<half_t, 2, 2, 2, 2, 2, 2>(a, s, 256);   // same, K step 128
-        case 62: return wg9_launch_ns<half_t, 2, 1, 2, 2, 1, 2>(a, s, 512);   // 64 ci x 64 co, 4 waves, two blocks per CU
-        case 63: return wg9_launch_ns<half_t, 2, 1, 2, 2, 2, 2>(a, s, 512);
-        case 64: return wg9_launch_ns<half_t, 4, 1, 2, 2, 1, 2>(a, s, 256);   // 128 ci x 64 co, 8 waves
-        case 65: return wg9_launch_ns<half_t, 4, 1, 2, 2, 2, 2>(a, s, 256);
-        case 66: return wg9_launch_ns<half_t, 2, 2, 3, 2, 1, 2>(a, s, 256);   // 3 stages
-        case 67: return wg9_launch_ns<half_t, 4, 2, 2, 2, 1, 2>(a, s, 256);   // 128 ci x 128 co, 16 waves
-        case 68: return wg9_launch_ns<half_t, 2, 1, 3, 2, 1, 2>(a, s, 512);
-        case 69: return wg9_launch_ns<half_t, 2, 2, 2, 2, 1, 2>(a, s, 512);   // 64 x 128, two blocks per CU
-        case 51: return wg9_launch_ns<half_t, 2, 2, 2, 2, 2>(a, s);   // 64 x 64, 8 waves, K step 128
-        case 52: return wg9_launch_ns<half_t, 1, 2, 2, 2, 2>(a, s);
-        // ring form (long rows)
-        case 30: return wg9r_launch<half_t, 2, 1, 2>(a, s, 768);     // 64 x 32, 4 waves
-        case 31: return wg9r_launch<half_t, 1, 2, 2>(a, s, 768);     // 32 x 64, 4 waves
-        case 32: return wg9r_launch<half_t, 1, 1, 2>(a, s, 768);     // 32 x 32, 2 waves
-        case 33: return wg9r_launch<half_t, 2, 2, 2>(a, s, 768);     // 64 x 64, 8 waves
-        case 34: return wg9r_launch<half_t, 2, 1, 2>(a, s, 512);
-        case 35: return wg9r_launch<half_t, 1, 2, 2>(a, s, 512);
-        case 36: return wg9r_launch<half_t, 2, 2, 2>(a, s, 512);
-        case 37: return wg9r_launch<half_t, 2, 1, 2>(a, s, 1024);
-        case 38: return wg9r_launch<half_t, 1, 2, 2>(a, s, 1024);
-        case 39: return wg9r_launch<half_t, 2, 2, 2>(a, s, 1024);
-        case 44: return wg9r_launch<half_t, 1, 2, 2, 2>(a, s);       // ring, K step 128
-        case 45: return wg9r_launch<half_t, 2, 1, 2, 2>(a, s);
-        case 46: return wg9r_launch<half_t, 1, 2, 2, 2>(a, s, 512);
-        case 47: return wg9r_launch<half_t, 2, 1, 2, 2>(a, s, 512);
-        case 40: return wg9r_launch<half_t, 1, 2, 2>(a, s, 384);
-        case 41: return wg9r_launch<half_t, 1, 2, 2>(a, s, 256);
-        case 42: return wg9r_launch<half_t, 2, 1, 2>(a, s, 384);
-        case 43: return wg9r_launch<half_t, 2, 1, 2>(a, s, 256);
+    switch (wgrad_split_args(dtype, a)) {
+        case 0: return wg9_T<float>(p, a, s);
+        case 1: return wg9_T<half_t>(p, a, s);
+        case 2: return wg9_T<bf16_t>(p, a, s);
     }
     return hipErrorInvalidValue;
 }
-#endif  // Y2_DEVBUILD
 
-hipError_t launch_wgrad_auto(int dtype, const WgradArgs& a0, hipStream_t s) {
-    static const int xcd_mode = getenv("Y2_XCD_WGRAD") ? atoi(getenv("Y2_XCD_WGRAD")) : 1;
-    WgradArgs a = a0;
-    a.xcd = xcd_mode;
-    // measured per shape (scripts/bench_wgrad.py): nine-tap blocks win on every 3x3 layer
-    if (a.taps == 9) {
-        hipError_t e = launch_wgrad9(dtype, a, s);
-        if (e != hipErrorOutOfMemory) return e;   // window too large for LDS: fall through
-        (void)hipGetLastError();
-    }
-    return launch_wgrad(dtype, a, s);
-}
 }  // namespace y2
