@@ -8,7 +8,6 @@
 //   * persistent waves; epilogue repacks through a wave-private LDS patch so the
 //     stores are whole 64-byte pixel rows, 1 KiB contiguous per wave-instruction
 //   * BN statistics as bias-shifted sums per wave, Chan-merged per block.
-#include <stdlib.h>
 #include "common.h"
 #include "kernels.h"
 
@@ -273,26 +272,25 @@ __global__ __launch_bounds__(256) void conv1_stats_kernel(Conv1Args a) {
     }
 }
 
-hipError_t launch_conv1_fwd(int dtype, const Conv1Args& a, hipStream_t s) {
-    dtype = dtype_plain(dtype);      // f16x2: the 3-channel layer reads fp32 operands (exact fp32, or Conv1Args::xs)
-    dim3 g(a.nblocks), b(256);
-    if (a.stats_only) {
-        switch (dtype) {
-            case 0:
-                if (a.xs) hipLaunchKernelGGL((conv1_stats_kernel<float, true>), g, b, 0, s, a);
-                else hipLaunchKernelGGL(conv1_stats_kernel<float>, g, b, 0, s, a);
-                break;
-            case 1: hipLaunchKernelGGL(conv1_stats_kernel<half_t>, g, b, 0, s, a); break;
-            case 2: hipLaunchKernelGGL(conv1_stats_kernel<bf16_t>, g, b, 0, s, a); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (dtype) {
+hipError_t launch_conv1_fwd(const Conv1Plan& p, const Conv1Args& a, hipStream_t s) {
+    const dim3 g(p.fwd_blocks), b(256);
+    if (p.fwd == C1F_PLAIN) {
+        switch (p.T) {
             case 0: hipLaunchKernelGGL((conv1_fwd_kernel<float, true>), g, b, 0, s, a); break;
             case 1: hipLaunchKernelGGL((conv1_fwd_kernel<half_t, true>), g, b, 0, s, a); break;
             case 2: hipLaunchKernelGGL((conv1_fwd_kernel<bf16_t, true>), g, b, 0, s, a); break;
             default: return hipErrorInvalidValue;
         }
+    } else if (p.stats == C1S_CONV) {
+        switch (p.T * 2 + p.xs_fwd) {
+            case 0: hipLaunchKernelGGL(conv1_stats_kernel<float>, g, b, 0, s, a); break;
+            case 1: hipLaunchKernelGGL((conv1_stats_kernel<float, true>), g, b, 0, s, a); break;
+            case 2: hipLaunchKernelGGL(conv1_stats_kernel<half_t>, g, b, 0, s, a); break;
+            case 4: hipLaunchKernelGGL(conv1_stats_kernel<bf16_t>, g, b, 0, s, a); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
@@ -306,13 +304,13 @@ hipError_t launch_conv1_fwd(int dtype, const Conv1Args& a, hipStream_t s) {
 // A wave tile is 2 image rows x 32 columns: two accumulators share the four input rows; the
 // wave-private LDS patch [64 px][32 co] feeds both the 1-KiB row stores of y and the 2x2 windows.
 // ---------------------------------------------------------------------------
-// TRACK 1: the window's arg-max and its conv output are kept for the backward pass (a.ysel / a.idx; f32 parity mode and
-// Y2_CONV1_YSEL=1), found by a per-position compare / select chain on the activation.
+// TRACK 1: the window's arg-max and its conv output are kept for the backward pass (a.ysel / a.idx; the f32 parity mode),
+// found by a per-position compare / select chain on the activation.
 // TRACK 0 (inference, or a training binding that stores y): the window maximum is taken BEFORE the activation -- leaky is
 // non-decreasing, so leaky(max z) = max leaky(z) bit for bit -- and that chain (88 v_cndmask + 32 v_bfi + 31 compares of
 // the ~400 vector instructions a tile cost; the kernel is bound by vector issue, not by HBM) drops out.
-// TRACK 2 (Conv1PoolArgs::idx3; training, 16-bit types): the same maximum first, then the first position that holds it by
-// equality, and 3 bits per element (position, activation branch) instead of any conv output.
+// TRACK 2 (Conv1PoolArgs::idx3; training, 16-bit types and the f16x2 mode): the same maximum first, then the first
+// position that holds it by equality, and 3 bits per element (position, activation branch) instead of any conv output.
 // XS: as conv1_stats_kernel (f16x2 mode: the SAME three-product sequence, so both passes see the same conv output).
 template <typename T, bool STOREY, int TRACK, bool XS = false>
 __global__ __launch_bounds__(256) void conv1_pool_kernel(Conv1PoolArgs a) {
@@ -521,31 +519,27 @@ __global__ __launch_bounds__(256) void conv1_pool_kernel(Conv1PoolArgs a) {
     }
 }
 
-bool conv1_pool_ok(int H, int W, int pool, int cout) { return pool && (H % 2) == 0 && (W % 2) == 0 && cout == 32; }
+// (element type, what the pass keeps, split operands): the forms plan_conv1 produces
+static constexpr int c1pool_form(int T, Conv1Keep keep, int xs) { return (T * 4 + keep) * 2 + xs; }
 
-template <typename T, bool XS = false>
-static void conv1_pool_T(const Conv1PoolArgs& a, hipStream_t s) {
-    dim3 g(a.nblocks), b(256);
-    if (a.store_y) {
-        if (a.idx3) hipLaunchKernelGGL((conv1_pool_kernel<T, true, 2, XS>), g, b, 0, s, a);
-        else if (a.ysel) hipLaunchKernelGGL((conv1_pool_kernel<T, true, 1, XS>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((conv1_pool_kernel<T, true, 0, XS>), g, b, 0, s, a);
-    } else {
-        if (a.idx3) hipLaunchKernelGGL((conv1_pool_kernel<T, false, 2, XS>), g, b, 0, s, a);
-        else if (a.ysel) hipLaunchKernelGGL((conv1_pool_kernel<T, false, 1, XS>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((conv1_pool_kernel<T, false, 0, XS>), g, b, 0, s, a);
-    }
-}
-
-hipError_t launch_conv1_pool(int dtype, const Conv1PoolArgs& a, hipStream_t s) {
-    dtype = dtype_plain(dtype);      // f16x2: fp32 operands (exact fp32, or Conv1PoolArgs::xs)
-    switch (dtype) {
-        case 0:
-            if (a.xs) conv1_pool_T<float, true>(a, s);
-            else conv1_pool_T<float>(a, s);
-            break;
-        case 1: conv1_pool_T<half_t>(a, s); break;
-        case 2: conv1_pool_T<bf16_t>(a, s); break;
+hipError_t launch_conv1_pool(const Conv1Plan& p, const Conv1PoolArgs& a, hipStream_t s) {
+    if (p.fwd != C1F_POOLED) return hipErrorInvalidValue;
+    const dim3 g(p.pool_blocks), b(256);
+    switch (c1pool_form(p.T, p.keep, p.xs_fwd)) {
+        // inference binding
+        case c1pool_form(0, C1K_NONE, 0): hipLaunchKernelGGL((conv1_pool_kernel<float, false, 0, false>), g, b, 0, s, a); break;
+        case c1pool_form(0, C1K_NONE, 1): hipLaunchKernelGGL((conv1_pool_kernel<float, false, 0, true>), g, b, 0, s, a); break;
+        case c1pool_form(1, C1K_NONE, 0): hipLaunchKernelGGL((conv1_pool_kernel<half_t, false, 0, false>), g, b, 0, s, a); break;
+        case c1pool_form(2, C1K_NONE, 0): hipLaunchKernelGGL((conv1_pool_kernel<bf16_t, false, 0, false>), g, b, 0, s, a); break;
+        // training, the linear backward does not fit: y for the recomputing reduce and conv1_wgrad
+        case c1pool_form(0, C1K_Y, 0): hipLaunchKernelGGL((conv1_pool_kernel<float, true, 0, false>), g, b, 0, s, a); break;
+        case c1pool_form(1, C1K_Y, 0): hipLaunchKernelGGL((conv1_pool_kernel<half_t, true, 0, false>), g, b, 0, s, a); break;
+        case c1pool_form(2, C1K_Y, 0): hipLaunchKernelGGL((conv1_pool_kernel<bf16_t, true, 0, false>), g, b, 0, s, a); break;
+        // training, linear backward
+        case c1pool_form(0, C1K_YSEL, 0): hipLaunchKernelGGL((conv1_pool_kernel<float, false, 1, false>), g, b, 0, s, a); break;
+        case c1pool_form(0, C1K_IDX3, 1): hipLaunchKernelGGL((conv1_pool_kernel<float, false, 2, true>), g, b, 0, s, a); break;
+        case c1pool_form(1, C1K_IDX3, 0): hipLaunchKernelGGL((conv1_pool_kernel<half_t, false, 2, false>), g, b, 0, s, a); break;
+        case c1pool_form(2, C1K_IDX3, 0): hipLaunchKernelGGL((conv1_pool_kernel<bf16_t, false, 2, false>), g, b, 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -698,10 +692,10 @@ __global__ __launch_bounds__(256) void conv1_bnbwd_reduce_kernel(Conv1BnBwdArgs 
     }
 }
 
-hipError_t launch_conv1_bnbwd_reduce(int dtype, const Conv1BnBwdArgs& a, hipStream_t s) {
-    dtype = dtype_plain(dtype);      // f16x2: the 3-channel layer computes in exact fp32
-    dim3 g(a.nblocks), b(256);
-    switch (dtype) {
+hipError_t launch_conv1_bnbwd_reduce(const Conv1Plan& p, const Conv1BnBwdArgs& a, hipStream_t s) {
+    if (p.bwd != C1B_RECOMPUTE) return hipErrorInvalidValue;
+    const dim3 g(p.pool_blocks), b(256);
+    switch (p.T) {
         case 0: hipLaunchKernelGGL(conv1_bnbwd_reduce_kernel<float>, g, b, 0, s, a); break;
         case 1: hipLaunchKernelGGL(conv1_bnbwd_reduce_kernel<half_t>, g, b, 0, s, a); break;
         case 2: hipLaunchKernelGGL(conv1_bnbwd_reduce_kernel<bf16_t>, g, b, 0, s, a); break;

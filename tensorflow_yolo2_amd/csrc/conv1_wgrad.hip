@@ -10,13 +10,8 @@
 //     overlapping 32-byte windows of the x4 row image directly (no im2col)
 //   * accumulators live in registers across all rows of the block; one LDS reduction
 //     over the 4 waves and 864 float atomics per block at the end.
-#include <stdlib.h>
 #include "common.h"
 #include "kernels.h"
-
-#ifndef Y2_C1F_MAXI
-#define Y2_C1F_MAXI 0   // register-prefetched items per thread in the fused kernel (f16/bf16)
-#endif
 
 namespace y2 {
 
@@ -109,28 +104,21 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(Conv1WgradArgs a) {
 }
 
 template <typename T>
-static hipError_t c1wg_T(const Conv1WgradArgs& a, hipStream_t s) {
-    constexpr int SZ = sizeof(T);
-    const int Wp = (a.W + 15) & ~15;
-    size_t lds = (size_t)Wp * 32 * SZ + 3 * (size_t)((((Wp + 4) * 4 * SZ) + 15) & ~15);
-    const size_t red = 4 * 48 * 32 * sizeof(float);
-    if (lds < red) lds = red;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+static hipError_t c1wg_T(const Conv1Plan& p, const Conv1WgradArgs& a, hipStream_t s) {
+    if (p.bwd_lds != c1wg_lds(sizeof(T), a.W) || p.bwd_lds > kC1LdsMax) return hipErrorInvalidValue;
     auto kern = conv1_wgrad_kernel<T>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.bwd_lds);
     if (e != hipSuccess) return e;
-    int rows = a.N * a.H;
-    int nb = rows < 512 ? rows : 512;
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(p.bwd_blocks), dim3(256), p.bwd_lds, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_conv1_wgrad(int dtype, const Conv1WgradArgs& a, hipStream_t s) {
-    dtype = dtype_plain(dtype);      // f16x2: the 3-channel layer computes in exact fp32
-    switch (dtype) {
-        case 0: return c1wg_T<float>(a, s);
-        case 1: return c1wg_T<half_t>(a, s);
-        case 2: return c1wg_T<bf16_t>(a, s);
+hipError_t launch_conv1_wgrad(const Conv1Plan& p, const Conv1WgradArgs& a, hipStream_t s) {
+    if (p.bwd != C1B_GENERIC && p.bwd != C1B_RECOMPUTE) return hipErrorInvalidValue;
+    switch (p.T) {
+        case 0: return c1wg_T<float>(p, a, s);
+        case 1: return c1wg_T<half_t>(p, a, s);
+        case 2: return c1wg_T<bf16_t>(p, a, s);
     }
     return hipErrorInvalidValue;
 }
@@ -143,7 +131,7 @@ hipError_t launch_conv1_wgrad(int dtype, const Conv1WgradArgs& a, hipStream_t s)
 // conv1), so at 416x416x64 the 709 MB tensor is never written nor re-read: the apply pass
 // (886 MB in, 709 MB out) disappears and this kernel streams y + dA (886 MB) instead of dy.
 // ---------------------------------------------------------------------------
-template <typename T, int MAXI>
+template <typename T>
 __global__ __launch_bounds__(256, 2) void conv1_wgrad_fused_kernel(Conv1WgradFusedArgs a) {
     constexpr int SZ = sizeof(T), EPC = 16 / SZ, CPP = 32 / EPC;
     constexpr int DYP = 32 * SZ, XP = 4 * SZ;
@@ -181,30 +169,12 @@ __global__ __launch_bounds__(256, 2) void conv1_wgrad_fused_kernel(Conv1WgradFus
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc1[q] = acc2[q] = 0.f;
 
-    // one work item = one pooled pixel x EPC channels: 1 dA chunk + 4 y chunks in, 4 dy chunks out.
-    // The first MAXI items per thread of the NEXT row pair are loaded into registers before the
-    // MFMA phase of the current one (HBM latency hides behind it); the rest load in place.
+    // one work item = one pooled pixel x EPC channels: 1 dA chunk + 4 y chunks in, 4 dy chunks out
     const int nitems = Wo * CPP;
-    u32x4 pda[MAXI ? MAXI : 1], py[MAXI ? MAXI : 1][4];   // raw 16-byte vectors (kept packed)
     auto item_ptrs = [&](int pr, const char*& yrow, const char*& darow) {
         const int n = pr / Ho, ho = pr - n * Ho;
         yrow = (const char*)a.y + ((size_t)(n * a.H + 2 * ho) * a.W) * DYP;
         darow = (const char*)a.dA + ((size_t)(n * Ho + ho) * Wo) * DYP;
-    };
-    auto prefetch = [&](int pr) {
-        const char *yrow, *darow;
-        item_ptrs(pr, yrow, darow);
-#pragma unroll
-        for (int k = 0; k < MAXI; ++k) {
-            const int item = tid + k * NTH;
-            if (item < nitems) {
-                const int wo = item / CPP;
-                pda[k] = *(const u32x4*)(darow + (size_t)item * 16);
-#pragma unroll
-                for (int d = 0; d < 4; ++d)
-                    py[k][d] = *(const u32x4*)(yrow + ((size_t)(d >> 1) * a.W + 2 * wo + (d & 1)) * DYP + ch * 16);
-            }
-        }
     };
     auto process = [&](const u32x4& dar, const u32x4 (&yr)[4], int item) {
         const int wo = item / CPP;
@@ -246,8 +216,6 @@ __global__ __launch_bounds__(256, 2) void conv1_wgrad_fused_kernel(Conv1WgradFus
             st_chunk<T>(dy_l + (d >> 1) * dy_bytes + (size_t)(2 * wo + (d & 1)) * DYP + ch * 16, o);
         }
     };
-    if (MAXI && blockIdx.x < prs) prefetch(blockIdx.x);
-
     for (int pr = blockIdx.x; pr < prs; pr += gridDim.x) {
         const int n = pr / Ho, ho = pr - n * Ho, h0 = 2 * ho;
         const char* xrow = (const char*)a.x4 + (bpix(n, h0, 0, a.H, a.W) - (size_t)(a.W + 2)) * XP;
@@ -258,15 +226,10 @@ __global__ __launch_bounds__(256, 2) void conv1_wgrad_fused_kernel(Conv1WgradFus
                 const int i = i0 + lane;
                 if (i < x_chunks) glds16(xrow + kh * xpitch + (size_t)i * 16, x_l + kh * x_bytes + i0 * 16);
             }
-#pragma unroll
-        for (int k = 0; k < MAXI; ++k) {
-            const int item = tid + k * NTH;
-            if (item < nitems) process(pda[k], py[k], item);
-        }
         {
             const char *yrow, *darow;
             item_ptrs(pr, yrow, darow);
-            for (int item = tid + MAXI * NTH; item < nitems; item += NTH) {
+            for (int item = tid; item < nitems; item += NTH) {
                 const int wo = item / CPP;
                 const u32x4 dav = *(const u32x4*)(darow + (size_t)item * 16);
                 u32x4 yv[4];
@@ -276,7 +239,6 @@ __global__ __launch_bounds__(256, 2) void conv1_wgrad_fused_kernel(Conv1WgradFus
                 process(dav, yv, item);
             }
         }
-        if (MAXI && pr + (int)gridDim.x < prs) prefetch(pr + gridDim.x);
         __syncthreads();   // LDS-DMA drained (vmcnt(0)) and the dy images complete
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
@@ -329,43 +291,22 @@ __global__ __launch_bounds__(256, 2) void conv1_wgrad_fused_kernel(Conv1WgradFus
     }
 }
 
-template <typename T, int MAXI>
-static hipError_t c1wgf_M(const Conv1WgradFusedArgs& a, hipStream_t s) {
-    constexpr int SZ = sizeof(T);
-    const int Wp = (a.W + 15) & ~15;
-    size_t lds = 2 * (size_t)Wp * 32 * SZ + 4 * (size_t)((((Wp + 4) * 4 * SZ) + 15) & ~15);
-    const size_t red = 4 * 48 * 32 * sizeof(float);
-    if (lds < red) lds = red;
-    if (lds > 160 * 1024) return hipErrorOutOfMemory;
-    auto kern = conv1_wgrad_fused_kernel<T, MAXI>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+template <typename T>
+static hipError_t c1wgf_T(const Conv1Plan& p, const Conv1WgradFusedArgs& a, hipStream_t s) {
+    if (p.bwd_lds != c1wgf_lds(sizeof(T), a.W) || p.bwd_lds > kC1LdsMax) return hipErrorInvalidValue;
+    auto kern = conv1_wgrad_fused_kernel<T>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.bwd_lds);
     if (e != hipSuccess) return e;
-    const int prs = a.N * (a.H / 2);
-    const int nb = prs < 512 ? prs : 512;
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(p.bwd_blocks), dim3(256), p.bwd_lds, s, a);
     return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t c1wgf_T(const Conv1WgradFusedArgs& a, hipStream_t s) {
-    // measured at 416x416x64: prefetching the next row pair into registers (MAXI 2) is no faster
-    // than loading in place with two blocks per CU (249 vs 245 us), so the simple form ships
-    if (sizeof(T) == 2 && Y2_C1F_MAXI > 0) return c1wgf_M<T, Y2_C1F_MAXI>(a, s);
-    return c1wgf_M<T, 0>(a, s);
-}
-
-bool conv1_wgrad_fused_ok(int H, int W, int pool, int ldy, int elem_size) {
-    const int Wp = (W + 15) & ~15;
-    const size_t lds = 2 * (size_t)Wp * 32 * elem_size + 4 * (size_t)((((Wp + 4) * 4 * elem_size) + 15) & ~15);
-    return pool && (H % 2) == 0 && (W % 2) == 0 && ldy == 32 && lds <= 160 * 1024;   // two dy rows + four x rows in LDS
-}
-
-hipError_t launch_conv1_wgrad_fused(int dtype, const Conv1WgradFusedArgs& a, hipStream_t s) {
-    dtype = dtype_plain(dtype);      // f16x2: the 3-channel layer computes in exact fp32
-    switch (dtype) {
-        case 0: return c1wgf_T<float>(a, s);
-        case 1: return c1wgf_T<half_t>(a, s);
-        case 2: return c1wgf_T<bf16_t>(a, s);
+hipError_t launch_conv1_wgrad_fused(const Conv1Plan& p, const Conv1WgradFusedArgs& a, hipStream_t s) {
+    if (p.bwd != C1B_FUSED) return hipErrorInvalidValue;
+    switch (p.T) {
+        case 0: return c1wgf_T<float>(p, a, s);
+        case 1: return c1wgf_T<half_t>(p, a, s);
+        case 2: return c1wgf_T<bf16_t>(p, a, s);
     }
     return hipErrorInvalidValue;
 }
@@ -382,7 +323,6 @@ hipError_t launch_conv1_wgrad_fused(int dtype, const Conv1WgradFusedArgs& a, hip
 constexpr int kLinAcc = 48 * 32 + 48 * 48;
 
 constexpr int kLinThreads = 256;   // measured: 512 threads + register prefetch of the next row pair 297 us, this form 252
-constexpr int kLinItems = 0;     // items (pooled pixel x chunk) per thread held in registers one row pair ahead
 
 // GRAM: the Gram matrix is accumulated here (rounds 2-3); false: the forward pass of this step left it in a.gram
 // (conv1_gram_kernel below: the batch-norm statistics of the layer come from it too) -- three of five MFMAs and the
@@ -446,27 +386,6 @@ __global__ __launch_bounds__(kLinThreads, 2) void conv1_wgrad_lin_kernel(Conv1Wg
     for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
 
     int nitems = Wo * CPP;
-    // the dA / ysel / idx of a row pair are requested while the MFMAs of the previous one run (two blocks of eight
-    // waves per CU: in-place loads leave the HBM latency of every row pair exposed)
-    u32x4 pda[kLinItems ? kLinItems : 1], pys[kLinItems ? kLinItems : 1];
-    unsigned pix_[kLinItems ? kLinItems : 1];
-    auto prefetch = [&](int pr) {
-        const int n = pr / Ho, ho = pr - n * Ho;
-        const size_t prow = ((size_t)n * Ho + ho) * Wo;
-#pragma unroll
-        for (int k = 0; k < kLinItems; ++k) {
-            const int item = tid + k * NTH;
-            if (item < nitems) {
-                pda[k] = *(const u32x4*)((const char*)a.dA + (prow * CPP + item) * 16);
-                if constexpr (NOSEL) {
-                    pix_[k] = a.idx3[prow * CPP + item];
-                } else {
-                    pys[k] = *(const u32x4*)((const char*)a.ysel + (prow * CPP + item) * 16);
-                    pix_[k] = a.idx[prow * CPP + item];
-                }
-            }
-        }
-    };
     auto process = [&](const u32x4& dar, const u32x4& ysr, unsigned ix, int item) {
         const int wo = item / CPP;
         Chunk<T> dav, ysv;
@@ -525,9 +444,9 @@ __global__ __launch_bounds__(kLinThreads, 2) void conv1_wgrad_lin_kernel(Conv1Wg
         const size_t prow = ((size_t)n * Ho + ho) * Wo + cbeg / 2;
         // this row pair's first kBatch items per thread: every load issued before the first one is used (left to the
         // compiler the loop below loads, waits and processes item by item: three to four exposed latencies per row pair)
-        constexpr int kBatch = kLinItems ? 0 : 4;
-        u32x4 bda[kBatch ? kBatch : 1], bys[kBatch ? kBatch : 1];
-        unsigned bix[kBatch ? kBatch : 1];
+        constexpr int kBatch = 4;
+        u32x4 bda[kBatch], bys[kBatch];
+        unsigned bix[kBatch];
 #pragma unroll
         for (int k = 0; k < kBatch; ++k) {
             const int item = tid + k * NTH;
@@ -605,11 +524,6 @@ __global__ __launch_bounds__(kLinThreads, 2) void conv1_wgrad_lin_kernel(Conv1Wg
             }
         }
 #pragma unroll
-        for (int k = 0; k < kLinItems; ++k) {
-            const int item = tid + k * NTH;
-            if (item < nitems) process(pda[k], pys[k], pix_[k], item);
-        }
-#pragma unroll
         for (int k = 0; k < kBatch; ++k) {
             const int item = tid + k * NTH;
             if (item < nitems) process(bda[k], NOSEL ? bda[k] : bys[k], bix[k], item);
@@ -619,7 +533,7 @@ __global__ __launch_bounds__(kLinThreads, 2) void conv1_wgrad_lin_kernel(Conv1Wg
             const int item = tid + (kBatch + k) * NTH;
             if (item < nitems) process(bda2[k], NOSEL ? bda2[k] : bys2[k], bix2[k], item);
         }
-        for (int item = tid + (kLinItems + kBatch + kBatch2) * NTH; item < nitems; item += NTH) {    // wider images: the rest in place
+        for (int item = tid + (kBatch + kBatch2) * NTH; item < nitems; item += NTH) {    // wider images: the rest in place
             const u32x4 dar = *(const u32x4*)((const char*)a.dA + (prow * CPP + item) * 16);
             if constexpr (NOSEL) process(dar, dar, a.idx3[prow * CPP + item], item);
             else process(dar, *(const u32x4*)((const char*)a.ysel + (prow * CPP + item) * 16), a.idx[prow * CPP + item], item);
@@ -1087,112 +1001,154 @@ __global__ __launch_bounds__(1024) void conv1_gram_stats_kernel(Conv1GramStatsAr
     }
 }
 
-size_t conv1_gram_scratch_floats() { return (size_t)kGram * (1 + kLinMid + kGramMaxBlocks); }
-bool conv1_gram_ok(int H, int W, int elem_size) {
-    const int Wp = (W + 31) & ~31;
-    const size_t lds = 2 * 6 * (size_t)((((Wp + 4) * 4 * elem_size) + 15) & ~15);
-    return elem_size == 2 && (H % 2) == 0 && lds <= 72 * 1024;
-}
 template <typename T>
-static hipError_t c1gram_T(const Conv1GramStatsArgs& a, hipStream_t s) {
-    const int Wp = (a.Wd + 31) & ~31;
-    const int RT = (a.H % 4) == 0 ? 4 : 2;
-    size_t lds = 2 * (size_t)(RT + 2) * (size_t)((((Wp + 4) * 4 * sizeof(T)) + 15) & ~15);
-    const size_t red = 4 * (size_t)kGram * sizeof(float);
-    if (lds < red) lds = red;
+static hipError_t c1gram_T(const Conv1Plan& p, const Conv1GramStatsArgs& a, hipStream_t s) {
+    if (p.gram_lds != c1gram_lds(p.gram_rt, a.Wd) || p.gram_lds > kC1LdsMax) return hipErrorInvalidValue;
     auto kern = conv1_gram_kernel<T>;
     // the attribute is set once per size class (a call per training forward was host work on the hot path and
     // is not allowed inside a stream capture)
-    static size_t attr = 0;
-    if (lds > attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static int attr = 0;
+    if (p.gram_lds > attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.gram_lds);
         if (e != hipSuccess) return e;
-        attr = lds;
+        attr = p.gram_lds;
     }
-    const int ntile = a.N * (a.H / RT);
-    const int nb = ntile < kGramMaxBlocks ? ntile : kGramMaxBlocks;
     float* part = a.mid + (size_t)kLinMid * kGram;
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, s, a.x4, a.N, a.H, a.Wd, RT, part);
-    hipLaunchKernelGGL(conv1_gram_reduce_kernel, dim3((kGram + 255) / 256, kLinMid), dim3(256), 0, s, part, nb, a.mid);
+    hipLaunchKernelGGL(kern, dim3(p.gram_blocks), dim3(256), p.gram_lds, s, a.x4, a.N, a.H, a.Wd, p.gram_rt, part);
+    hipLaunchKernelGGL(conv1_gram_reduce_kernel, dim3((kGram + 255) / 256, kLinMid), dim3(256), 0, s, part, p.gram_blocks, a.mid);
     hipLaunchKernelGGL(conv1_gram_stats_kernel<T>, dim3(1), dim3(1024), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_conv1_gram_stats(int dtype, const Conv1GramStatsArgs& a, hipStream_t s) {
-    dtype = dtype_plain(dtype);      // f16x2: the 3-channel layer computes in exact fp32
-    switch (dtype) {
-        case 1: return c1gram_T<half_t>(a, s);
-        case 2: return c1gram_T<bf16_t>(a, s);
+hipError_t launch_conv1_gram_stats(const Conv1Plan& p, const Conv1GramStatsArgs& a, hipStream_t s) {
+    if (p.stats != C1S_GRAM) return hipErrorInvalidValue;
+    switch (p.T) {
+        case 1: return c1gram_T<half_t>(p, a, s);
+        case 2: return c1gram_T<bf16_t>(p, a, s);
     }
     return hipErrorInvalidValue;
 }
 
-template <typename T, int XS = 0>
-static hipError_t c1lin_T(const Conv1WgradLinArgs& a0, hipStream_t s) {
+template <typename T, bool GRAM, bool NOSEL, int XS>
+static hipError_t c1lin_T(const Conv1Plan& p, const Conv1WgradLinArgs& a0, hipStream_t s) {
     constexpr int SZ = sizeof(T);
-    constexpr int ISZ = XS == 2 ? 2 : SZ;        // bytes per element of the LDS row images (XS 1: two half planes = 4)
+    static_assert(c1lin_lds(2, 0) >= 2 * kLinThreads * (16 / SZ) * (int)sizeof(float), "the BN partial sums fit the LDS");
+    const int wp = p.lin_nseg > 1 ? p.lin_ws : (a0.W + 15) & ~15;
+    if (p.bwd_lds != c1lin_lds(XS == 2 ? 2 : SZ, wp) || p.bwd_lds > kC1LdsMax) return hipErrorInvalidValue;
+    if (NOSEL && !(a0.Wf && a0.bias)) return hipErrorInvalidValue;
     Conv1WgradLinArgs a = a0;
-    int Wp = (a.W + 15) & ~15;
-    auto images = [](int wp) { return 2 * (size_t)wp * 32 * ISZ + 4 * (size_t)((((wp + 4) * 4 * ISZ) + 15) & ~15); };
-    size_t lds = images(Wp);
-    if (XS && lds > 80 * 1024) {     // fp32-wide row images: column segments, so that two workgroups share a CU
-        static const int want = getenv("Y2_CONV1_LIN_NSEG") ? atoi(getenv("Y2_CONV1_LIN_NSEG")) : 2;    // (A/B knob)
-        a.nseg = want < 1 ? 1 : (want > 8 ? 8 : want);
-        a.ws = ((a.W + a.nseg - 1) / a.nseg + 15) & ~15;
-        while (a.nseg > 1 && (a.nseg - 1) * a.ws >= a.W) --a.nseg;     // no empty segment
-        if (a.nseg == 1) a.ws = 0;
-        else lds = images(Wp = a.ws);
-    }
-    size_t red = 4 * (size_t)kLinAcc * sizeof(float);
-    const size_t red2 = 2 * (size_t)kLinThreads * (16 / SZ) * sizeof(float);
-    if (red < red2) red = red2;
-    if (lds < red) lds = red;
-    if (lds > 160 * 1024) return hipErrorOutOfMemory;
-    const bool nosel = a.idx3 != nullptr;
-    if (nosel && !(a.Wf && a.bias)) return hipErrorInvalidValue;
-    auto kern = nosel ? (a.gram ? conv1_wgrad_lin_kernel<T, false, true, XS> : conv1_wgrad_lin_kernel<T, true, true, XS>)
-                      : (a.gram ? conv1_wgrad_lin_kernel<T, false, false, XS> : conv1_wgrad_lin_kernel<T, true, false, XS>);
-    static size_t attr[4] = {0, 0, 0, 0};        // per kernel form of this T
-    const int form = (nosel ? 2 : 0) + (a.gram ? 1 : 0);
-    if (lds > attr[form]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    a.nseg = p.lin_nseg;
+    a.ws = p.lin_ws;
+    auto kern = conv1_wgrad_lin_kernel<T, GRAM, NOSEL, XS>;
+    static int attr = 0;
+    if (p.bwd_lds > attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.bwd_lds);
         if (e != hipSuccess) return e;
-        attr[form] = lds;
+        attr = p.bwd_lds;
     }
-    const int prs = a.N * (a.H / 2) * (a.nseg > 1 ? a.nseg : 1);
-    const int nb = prs < 512 ? prs : 512;
+    const int nb = p.bwd_blocks;
     float* part = a.acc + (size_t)kLinMid * kLinAcc;        // [nb][kLinAcc] behind the slice sums
-    if (a.nblocks_out) *a.nblocks_out = nb;
-    const int count = a.gram ? 48 * 32 : kLinAcc;
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(kLinThreads), lds, s, a, part);
+    const int count = GRAM ? kLinAcc : 48 * 32;
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(kLinThreads), p.bwd_lds, s, a, part);
     hipLaunchKernelGGL(conv1_lin_reduce_kernel, dim3((count + 255) / 256, kLinMid), dim3(256), 0, s, part, nb, a.acc, 0, count);
-    if (nosel) {
-        hipLaunchKernelGGL(conv1_lin_s2_kernel<T>, dim3(1), dim3(1024), 0, s, a.acc, a.Wf, a.bias, a.psum, nb);
-        if (a.nblocks_out) *a.nblocks_out = nb + 1;
-    }
+    if (NOSEL) hipLaunchKernelGGL(conv1_lin_s2_kernel<T>, dim3(1), dim3(1024), 0, s, a.acc, a.Wf, a.bias, a.psum, nb);
     return hipGetLastError();
 }
 
-bool conv1_wgrad_lin_ok(int H, int W, int pool, int ldy, int elem_size) {
-    const int Wp = (W + 15) & ~15;
-    size_t lds = 2 * (size_t)Wp * 32 * elem_size + 4 * (size_t)((((Wp + 4) * 4 * elem_size) + 15) & ~15);
-    const size_t red = 4 * (size_t)kLinAcc * sizeof(float);
-    if (lds < red) lds = red;
-    return pool && (H % 2) == 0 && (W % 2) == 0 && ldy == 32 && lds <= 160 * 1024;
-}
-size_t conv1_wgrad_lin_scratch_floats() { return (size_t)kLinAcc * (kLinMid + 512); }
+// (element type, what the forward kept, split operands, G built here): the forms plan_conv1 produces
+static constexpr int c1lin_form(int T, Conv1Keep keep, int xs, int gram) { return ((T * 4 + keep) * 3 + xs) * 2 + gram; }
 
-hipError_t launch_conv1_wgrad_lin(int dtype, const Conv1WgradLinArgs& a, hipStream_t s) {
-    dtype = dtype_plain(dtype);      // f16x2: fp32 operands (exact fp32, or Conv1WgradLinArgs::xs)
-    switch (dtype) {
-        case 0: return a.xs == 2 ? c1lin_T<float, 2>(a, s) : (a.xs ? c1lin_T<float, 1>(a, s) : c1lin_T<float>(a, s));
-        case 1: return c1lin_T<half_t>(a, s);
-        case 2: return c1lin_T<bf16_t>(a, s);
+hipError_t launch_conv1_wgrad_lin(const Conv1Plan& p, const Conv1WgradLinArgs& a, hipStream_t s) {
+    if (p.bwd != C1B_LINEAR) return hipErrorInvalidValue;
+    switch (c1lin_form(p.T, p.keep, p.xs_bwd, p.lin_gram)) {
+        case c1lin_form(0, C1K_YSEL, 0, 1): return c1lin_T<float, true, false, 0>(p, a, s);
+        case c1lin_form(0, C1K_IDX3, 1, 1): return c1lin_T<float, true, true, 1>(p, a, s);
+        case c1lin_form(0, C1K_IDX3, 2, 1): return c1lin_T<float, true, true, 2>(p, a, s);
+        case c1lin_form(1, C1K_IDX3, 0, 1): return c1lin_T<half_t, true, true, 0>(p, a, s);
+        case c1lin_form(1, C1K_IDX3, 0, 0): return c1lin_T<half_t, false, true, 0>(p, a, s);
+        case c1lin_form(2, C1K_IDX3, 0, 1): return c1lin_T<bf16_t, true, true, 0>(p, a, s);
+        case c1lin_form(2, C1K_IDX3, 0, 0): return c1lin_T<bf16_t, false, true, 0>(p, a, s);
     }
     return hipErrorInvalidValue;
 }
 hipError_t launch_conv1_dw_finalize(const Conv1DwFinalizeArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(conv1_dw_finalize_kernel, dim3(1), dim3(1024), 0, s, a);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The first layer's policy: every pass of the 3-channel layer (kernels.h Conv1Plan)
+// ---------------------------------------------------------------------------
+Conv1Plan plan_conv1(int dtype, int bwd_dtype, int N, int H, int W, int pool, int cout, int ldy, bool trains, bool has_next,
+                     bool training) {
+    Conv1Plan p{};
+    const int sz = (int)dtype_size(dtype);
+    const bool split = dtype_split(dtype);
+    p.T = dtype_plain(dtype);     // f16x2: fp32 operands (exact fp32, or split-operand products in registers)
+    const bool windows = pool && H % 2 == 0 && W % 2 == 0 && cout == 32 && ldy == 32;
+    // pooled: statistics-only pass (or the Gram matrix), then conv again fused with BN + leaky + pool
+    p.fwd = has_next && windows ? C1F_POOLED : C1F_PLAIN;
+    const bool pooled = p.fwd == C1F_POOLED;
+    // the linear backward: two dz rows + four x rows at the stored width in LDS
+    const bool linear = trains && pooled && c1lin_lds(sz, (W + 15) & ~15) <= kC1LdsMax;
+    // round 4: the statistics from the Gram matrix of the input patches, half-precision modes only: their stored
+    // activations carry 5e-4 of rounding noise, against which the ~1e-6 of the fp32 MFMA sums behind the Gram moments is
+    // nothing.  The f32 parity mode keeps the statistics-only convolution pass (moments of the exact fp32 outputs, double
+    // merge): a randomly initialised 20-layer stack amplifies a 1e-6 perturbation of the first scale / shift to 1e-3 at
+    // the top, enough to flip leaky / arg-max decisions the f32 tests compare element-wise with the oracle.  Its
+    // double-buffered six-row images leave room for two blocks per CU.
+    const bool gram = linear && sz == 2 && 2 * c1_images(0, 6, (W + 31) & ~31, 2) <= 72 * 1024;
+    p.stats = pooled && training ? (gram ? C1S_GRAM : C1S_CONV) : C1S_NONE;
+    // round 4, 16-bit types: the linear form keeps NO conv output, only 3 index bits per element; the f32 parity mode
+    // keeps ysel + 2 index bits.  The f16x2 mode takes the 3-bit form too (241 -> 210 us forward, 657 -> 617 us backward
+    // on one box)
+    if (!pooled) p.keep = C1K_Y;
+    else if (linear) p.keep = p.T == 0 && !split ? C1K_YSEL : C1K_IDX3;
+    else p.keep = trains ? C1K_Y : C1K_NONE;
+    // f16x2: split-operand products in registers (conv1.hip / conv1_wgrad.hip XS forms) wherever no exact-fp32 pass
+    // recomputes the conv output (the linear backward, or no backward at all); f16x2f: the backward contractions on the
+    // hi planes, as every other layer's
+    p.xs_fwd = pooled && split && (linear || !trains) ? 1 : 0;
+    p.xs_bwd = linear && split ? (bwd_dtype == 4 ? 2 : 1) : 0;
+    p.lin_gram = linear && p.stats != C1S_GRAM ? 1 : 0;
+    const bool fused = windows && c1wgf_lds(sz, W) <= kC1LdsMax;     // (a one-layer stack: a pooled one is linear)
+    p.bwd = linear ? C1B_LINEAR : (pooled ? C1B_RECOMPUTE : (fused ? C1B_FUSED : C1B_GENERIC));
+
+    const int nb = (N * H * W + 127) / 128;
+    p.fwd_blocks = nb > 1024 ? 1024 : nb;      // = statistics records (the net reserves 2048 rows; 1024 vs 2048: -4 us)
+    const int tiles = N * (H / 2) * ((W + 31) / 32);
+    p.pool_blocks = (tiles + 3) / 4 > 2048 ? 2048 : (tiles + 3) / 4;
+    p.gram_rt = H % 4 == 0 ? 4 : 2;
+    p.gram_blocks = N * (H / p.gram_rt) < kGramMaxBlocks ? N * (H / p.gram_rt) : kGramMaxBlocks;
+    p.gram_lds = c1gram_lds(p.gram_rt, W);
+    p.lin_nseg = 1;
+    if (p.bwd == C1B_LINEAR) {
+        const int isz = p.xs_bwd == 2 ? 2 : sz;
+        int wp = (W + 15) & ~15;
+        if (p.xs_bwd && c1_images(2, 4, wp, isz) > 80 * 1024) {    // fp32-wide row images: two column segments, so that
+            const int ws = ((W + 1) / 2 + 15) & ~15;                 // two workgroups share a CU (no empty segment)
+            if (ws < W) p.lin_nseg = 2, p.lin_ws = wp = ws;
+        }
+        p.bwd_lds = c1lin_lds(isz, wp);
+        const int units = N * (H / 2) * p.lin_nseg;
+        p.bwd_blocks = units < 512 ? units : 512;
+        p.lin_records = p.bwd_blocks + (p.keep == C1K_IDX3 ? 1 : 0);
+    } else if (p.bwd == C1B_FUSED) {
+        p.bwd_lds = c1wgf_lds(sz, W);
+        p.bwd_blocks = N * (H / 2) < 512 ? N * (H / 2) : 512;
+    } else {
+        p.bwd_lds = c1wg_lds(sz, W);
+        p.bwd_blocks = N * H < 512 ? N * H : 512;
+    }
+
+    const size_t mout = (size_t)N * (H / 2) * (W / 2), chunks = 32 * sz / 16;
+    p.ysel_bytes = p.keep == C1K_YSEL ? mout * 32 * sz + 256 : 0;
+    p.idx_bytes = p.keep == C1K_YSEL ? mout * chunks * sizeof(unsigned short) + 256
+                                     : (p.keep == C1K_IDX3 ? mout * chunks * sizeof(unsigned) + 256 : 0);
+    p.lin_bytes = linear ? (size_t)kLinAcc * (kLinMid + 512) * sizeof(float) : 0;     // slice sums + block partials
+    p.gram_bytes = gram ? (size_t)kGram * (1 + kLinMid + kGramMaxBlocks) * sizeof(float) : 0;
+    p.y_stored = p.keep == C1K_Y;
+    p.dy_stored = p.bwd == C1B_GENERIC || p.bwd == C1B_RECOMPUTE;
+    return p;
 }
 
 }  // namespace y2

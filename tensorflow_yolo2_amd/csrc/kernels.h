@@ -131,61 +131,116 @@ int halo_image_rows(int H, int W, int BP, int RPI, int pool = 0);
 int conv_block_couts(int Cout);
 
 // ---- first layer (Cin = 3, stored as 4 channels)
+// plan_conv1 (conv1_wgrad.hip) decides every pass of the layer; the launchers run the planned form and return
+// hipErrorInvalidValue for one the plan never produces
+enum Conv1Fwd {
+    C1F_PLAIN,      // conv1_fwd_kernel stores y (+ statistics), then the generic batch-norm passes
+    C1F_POOLED,     // statistics (Conv1Stats), then conv1_pool_kernel: conv again + BN + leaky + 2x2 max pool
+};
+enum Conv1Stats {
+    C1S_NONE,       // inference moments (or the plain route: conv1_fwd_kernel's own partials)
+    C1S_CONV,       // conv1_stats_kernel: a statistics-only conv pass + bn_finalize
+    C1S_GRAM,       // launch_conv1_gram_stats: from the Gram matrix of the input patches, kept for the backward pass
+};
+enum Conv1Keep {    // what the forward pass keeps for the backward pass
+    C1K_NONE,
+    C1K_Y,          // the conv output y [M][32]
+    C1K_YSEL,       // conv output at the window's arg-max + 2 index bits (Conv1PoolArgs::ysel / idx)
+    C1K_IDX3,       // 3 index bits per element (Conv1PoolArgs::idx3)
+};
+enum Conv1Bwd {
+    C1B_GENERIC,    // bn_bwd reduce + apply -> dy, conv1_wgrad_kernel
+    C1B_RECOMPUTE,  // conv1_bnbwd_reduce_kernel (conv output recomputed), generic apply, conv1_wgrad_kernel
+    C1B_FUSED,      // generic reduce, apply fused into conv1_wgrad_fused_kernel
+    C1B_LINEAR,     // conv1_wgrad_lin_kernel (+ the reduce) and conv1_dw_finalize: no conv output read
+};
+struct Conv1Plan {
+    int T;              // element type of the kernels: dtype_plain (the split mode's are fp32)
+    Conv1Fwd fwd;
+    Conv1Stats stats;
+    Conv1Keep keep;
+    Conv1Bwd bwd;
+    int xs_fwd;         // split-operand products of the statistics and pool passes (f16x2 mode): 0 / 1
+    int xs_bwd;         // ... of the linear backward: 0, 1 (three products), 2 (f16x2f: hi planes only)
+    int lin_gram;       // C1B_LINEAR: 1 the kernel builds G, 0 it reads the forward pass's Gram totals
+    int lin_nseg, lin_ws;       // C1B_LINEAR: column segments of a row pair and their width (Conv1WgradLinArgs)
+    int lin_records;    // C1B_LINEAR: BN-backward partial records written (the blocks, + the S2 record of C1K_IDX3)
+    int fwd_blocks;     // conv1_fwd_kernel / conv1_stats_kernel (= statistics records)
+    int pool_blocks;    // conv1_pool_kernel, conv1_bnbwd_reduce_kernel
+    int gram_rt, gram_blocks, gram_lds;     // conv1_gram_kernel: output rows per tile, grid, LDS
+    int bwd_blocks, bwd_lds;    // the weight-gradient kernel of the route
+    size_t ysel_bytes, idx_bytes, lin_bytes, gram_bytes;    // workspace of a training binding (0: not used)
+    bool y_stored, dy_stored;   // the conv output / its gradient exist in memory after the pass
+};
+// no HIP calls, no side effects.  trains: the binding trains; has_next: a layer follows; training: BN mode of the forward
+// being planned (the backward pass plans with the last forward's)
+Conv1Plan plan_conv1(int dtype, int bwd_dtype, int N, int H, int W, int pool, int cout, int ldy, bool trains, bool has_next,
+                     bool training);
+// LDS of the row-image kernels: dy_rows rows of wp pixels x 32 channels and x_rows rows of wp + 4 pixels x 4 channels
+// (isz bytes per element); the closing reductions of the waves reuse it
+constexpr int kC1LdsMax = 160 * 1024;
+constexpr int c1_images(int dy_rows, int x_rows, int wp, int isz) {
+    return dy_rows * wp * 32 * isz + x_rows * (((wp + 4) * 4 * isz + 15) & ~15);
+}
+constexpr int c1_atleast(int lds, int red) { return lds > red ? lds : red; }
+//   conv1_wgrad_kernel: one dy row + three x rows; [4 waves][48][32] floats
+constexpr int c1wg_lds(int sz, int W) { return c1_atleast(c1_images(1, 3, (W + 15) & ~15, sz), 4 * 48 * 32 * 4); }
+//   conv1_wgrad_fused_kernel: two dy rows + four x rows
+constexpr int c1wgf_lds(int sz, int W) { return c1_atleast(c1_images(2, 4, (W + 15) & ~15, sz), 4 * 48 * 32 * 4); }
+//   conv1_wgrad_lin_kernel: two dz rows + four x rows of a wp-pixel unit (isz 2 where the images hold halves);
+//   [4 waves][48*32 + 48*48] floats
+constexpr int c1lin_lds(int isz, int wp) { return c1_atleast(c1_images(2, 4, wp, isz), 4 * (48 * 32 + 48 * 48) * 4); }
+//   conv1_gram_kernel: two buffers of rt + 2 x rows (32-pixel groups, halves); [4 waves][48][48] floats
+constexpr int c1gram_lds(int rt, int W) { return c1_atleast(2 * c1_images(0, rt + 2, (W + 31) & ~31, 2), 4 * 48 * 48 * 4); }
+
 struct Conv1Args {
     const void* x4;     // [N][H+2][W+2][4]
     const void* w;      // packed [32][3][16] (kh, then kw*4+c, 12 real + 4 zero)
     void* y;            // [M][32]
     const float* bias;
-    float* part_cnt;
+    float* part_cnt;    // [Conv1Plan::fwd_blocks] statistics partials
     float* part_mean;
     float* part_m2;
     int N, H, W, M;
-    int nblocks;        // persistent grid size == number of partials
-    int stats_only;     // 1: batch-norm partials only, y is not written (first pass of the pooled form)
-    // f16x2 mode, stats_only pass: the fp32 operands are split into half planes in registers and a filter row is three f16
-    // matrix instructions (conv1.hip XS forms; set together with Conv1PoolArgs::xs / Conv1WgradLinArgs::xs)
-    int xs = 0;
 };
-hipError_t launch_conv1_fwd(int dtype, const Conv1Args& a, hipStream_t s);
-// pooled first layer, second pass: conv again + BN + leaky + 2x2 max pool -> y (optional) and the pooled output
+// C1F_PLAIN: conv1_fwd_kernel; C1F_POOLED + C1S_CONV: the statistics-only pass (y is not written; Conv1Plan::xs_fwd: the
+// fp32 operands are split into half planes in registers and a filter row is three f16 matrix instructions)
+hipError_t launch_conv1_fwd(const Conv1Plan& p, const Conv1Args& a, hipStream_t s);
+// pooled first layer, second pass: conv again + BN + leaky + 2x2 max pool -> the pooled output and what Conv1Plan::keep says
 struct Conv1PoolArgs {
     const void* x4;
     const void* w;
-    void* y;            // [M][32] (written when store_y)
+    void* y;            // [M][32] (C1K_Y)
     const float* bias;
     const float *scale, *shift;
     void* out;          // zero-bordered [N][Ho+2][Wo+2][32] of T
     int N, H, W;
-    int nblocks;
-    int store_y;
-    // training, linear form of the backward pass (conv1_wgrad.hip): instead of the conv output (64 B/pixel) keep,
-    // per pooled pixel, the conv output at the window's first arg-max (ysel [Mout][32] of T) and WHICH of the four
-    // positions it was (idx [Mout][chunks] u16: 2 bits per channel of a 16-byte chunk)
+    // C1K_YSEL: instead of the conv output (64 B/pixel) keep, per pooled pixel, the conv output at the window's first
+    // arg-max (ysel [Mout][32] of T) and WHICH of the four positions it was (idx [Mout][chunks] u16: 2 bits per channel
+    // of a 16-byte chunk)
     void* ysel = nullptr;
     unsigned short* idx = nullptr;
-    // round 4, 16-bit types: NO conv output at all is kept.  idx3 [Mout][chunks] u32 holds 3 bits per channel of a chunk:
+    // C1K_IDX3 (round 4): NO conv output at all is kept.  idx3 [Mout][chunks] u32 holds 3 bits per channel of a chunk:
     // the window position (2) and whether the activation there took the leaky branch (1: 0.1 * z >= z).  That is all the
     // backward pass needs per element (g = dA * slope, scattered to that position); its sum of g * y follows from the
     // linearity of y in the filter: sum_p dz y = sum_k W[k] X(dz)[k] + b sum dz, with X(dz) the matrix the weight
-    // gradient forms anyway (conv1_wgrad.hip conv1_lin_s2_kernel).  Set instead of ysel / idx.
+    // gradient forms anyway (conv1_wgrad.hip conv1_lin_s2_kernel)
     unsigned* idx3 = nullptr;
     int out_split = 0;  // f16x2 mode (T = float kernels): `out` is a split tensor ([32 halves hi][32 halves lo] per cell)
-    int xs = 0;         // f16x2 mode: split-operand products formed in registers (Conv1Args::xs)
 };
-// backward reduce pass of the same layer with the conv output recomputed (x4 + dA in, psum out)
+hipError_t launch_conv1_pool(const Conv1Plan& p, const Conv1PoolArgs& a, hipStream_t s);
+// C1B_RECOMPUTE: backward reduce pass of the same layer with the conv output recomputed (x4 + dA in, psum out)
 struct Conv1BnBwdArgs {
     const void* x4;
     const void* w;
     const float* bias;
     const float *scale, *shift;
     const void* dA;     // grad wrt the pooled output [N*Ho*Wo][32] of T
-    float* psum;        // [nblocks][2][32]
+    float* psum;        // [Conv1Plan::pool_blocks][2][32]
     int N, H, W;
-    int nblocks;
 };
-hipError_t launch_conv1_bnbwd_reduce(int dtype, const Conv1BnBwdArgs& a, hipStream_t s);
-bool conv1_pool_ok(int H, int W, int pool, int cout);
-hipError_t launch_conv1_pool(int dtype, const Conv1PoolArgs& a, hipStream_t s);
+hipError_t launch_conv1_bnbwd_reduce(const Conv1Plan& p, const Conv1BnBwdArgs& a, hipStream_t s);
+// C1B_GENERIC, C1B_RECOMPUTE
 struct Conv1WgradArgs {
     const void* x4;     // [N][H+2][W+2][4]
     const void* dy;     // zero-bordered [N][H+2][W+2][32]
@@ -193,8 +248,8 @@ struct Conv1WgradArgs {
     int N, H, W, M;
     float scale;        // 1 / grad_scale
 };
-hipError_t launch_conv1_wgrad(int dtype, const Conv1WgradArgs& a, hipStream_t s);
-// pooled first layer: BN-backward apply fused into the weight gradient (dy never reaches HBM)
+hipError_t launch_conv1_wgrad(const Conv1Plan& p, const Conv1WgradArgs& a, hipStream_t s);
+// C1B_FUSED: BN-backward apply fused into the weight gradient (dy never reaches HBM)
 struct Conv1WgradFusedArgs {
     const void* x4;       // [N][H+2][W+2][4]
     const void* y;        // conv output [M][32]
@@ -205,9 +260,8 @@ struct Conv1WgradFusedArgs {
     int N, H, W;
     float inv_grad_scale;
 };
-bool conv1_wgrad_fused_ok(int H, int W, int pool, int ldy, int elem_size);
-hipError_t launch_conv1_wgrad_fused(int dtype, const Conv1WgradFusedArgs& a, hipStream_t s);
-// Linear form (no conv output of the first layer in HBM at all).  With dy = scale dz - (ka + kb y):
+hipError_t launch_conv1_wgrad_fused(const Conv1Plan& p, const Conv1WgradFusedArgs& a, hipStream_t s);
+// C1B_LINEAR (no conv output of the first layer in HBM at all).  With dy = scale dz - (ka + kb y):
 //     dW = scale * X(dz) - ka * X(1) - kb * X(y),   X(v)[t][c][co] = sum_p x[p + t][c] v[p][co]
 // and y = conv(x, W) + b:  X(y) = G W + b X(1),  G = the Gram matrix of the 27-element input patches
 // (weights-independent).  The kernel accumulates X(dz) [48][32] and G [48][48] (rows kh*16 + kw*4 + c; channel 3
@@ -216,24 +270,22 @@ hipError_t launch_conv1_wgrad_fused(int dtype, const Conv1WgradFusedArgs& a, hip
 struct Conv1WgradLinArgs {
     const void* x4;             // [N][H+2][W+2][4], channel 3 = 1 inside the image
     const void* dA;             // [Mout][32] of T
-    const void* ysel;           // [Mout][32] of T
+    const void* ysel;           // [Mout][32] of T (C1K_YSEL)
     const unsigned short* idx;  // [Mout][chunks]
     const float *scale, *shift;
-    const float* gram = nullptr; // [48][48] totals of the forward pass's Gram matrix (launch_conv1_gram_stats): G is not rebuilt here
-    // Conv1PoolArgs::idx3 form (ysel / idx null): Wf (fp32 HWIO [3][3][3][32]) and bias for sum g * y = W . X(dz) + b sum dz,
-    // written as one more psum record (S1 = 0) behind the blocks' records
+    // C1K_IDX3: Wf (fp32 HWIO [3][3][3][32]) and bias for sum g * y = W . X(dz) + b sum dz, written as one more psum record
+    // (S1 = 0) behind the blocks' records
     const unsigned* idx3 = nullptr;
     const float* Wf = nullptr;
     const float* bias = nullptr;
-    float* acc;                 // 16 slice sums of [48*32 + 48*48], followed by the per-block partials (conv1_wgrad_lin_scratch_floats)
+    float* acc;                 // 16 slice sums of [48*32 + 48*48], followed by the per-block partials (Conv1Plan::lin_bytes)
     float* psum;                // out: BN-backward partial sums [blocks][2][32] (S1, S2) -- the reduce pass rides here
-    int* nblocks_out;           // host: number of partial records written
     int N, H, W;
-    int xs = 0;                 // f16x2 mode (T = float kernel): X(dz) and G from split-operand f16 products (Conv1Args::xs);
-                                // 2 (f16x2f): from the hi planes alone, one product each
-    // set by the launcher: a row pair is worked in nseg column segments of ws pixels (a multiple of 16) so that the LDS row
-    // images of the fp32-wide form leave room for two workgroups per CU
-    int nseg = 1, ws = 0;
+    // set by the launcher (Conv1Plan::lin_nseg / lin_ws): a row pair is worked in nseg column segments of ws pixels (a
+    // multiple of 16) so that the LDS row images of the fp32-wide form leave room for two workgroups per CU (8-byte
+    // aligned: one scalar load for the pair)
+    alignas(8) int nseg = 1;
+    int ws = 0;
 };
 struct Conv1DwFinalizeArgs {
     const float* acc;           // the 16 slice sums (added here)
@@ -243,11 +295,11 @@ struct Conv1DwFinalizeArgs {
     const float* coef;          // [2][32] ka, kb
     float* dW;                  // out [3][3][3][32]
     float inv_grad_scale;
-    const float* gram = nullptr; // [48][48] Gram totals of the forward pass (else: the G part of acc)
+    const float* gram = nullptr; // [48][48] Gram totals of the forward pass (Conv1Plan::lin_gram 0; else: the G part of acc)
 };
-// Forward pass of the pooled first layer, training: Gram matrix of the input patches -> batch-norm statistics of the
-// layer (conv1_wgrad.hip: replaces the statistics-only convolution pass + bn_finalize) and the totals the backward
-// pass reuses.  mid: conv1_gram_scratch_floats() floats = [1 + 16 + 768][48*48]: gram totals, slices, block partials.
+// C1S_GRAM: Gram matrix of the input patches -> batch-norm statistics of the layer (conv1_wgrad.hip: replaces the
+// statistics-only convolution pass + bn_finalize) and the totals the backward pass reuses.
+// mid: Conv1Plan::gram_bytes = [1 + 16 + 768][48*48] floats: gram totals, slices, block partials.
 struct Conv1GramStatsArgs {
     const void* x4;             // [N][H+2][W+2][4], channel 3 = 1 inside the image
     int N, H, Wd;
@@ -261,12 +313,8 @@ struct Conv1GramStatsArgs {
     float* mid;                 // slices + partials (scratch)
     float* gram;                // out: [48][48] totals
 };
-bool conv1_gram_ok(int H, int W, int elem_size);
-size_t conv1_gram_scratch_floats();
-hipError_t launch_conv1_gram_stats(int dtype, const Conv1GramStatsArgs& a, hipStream_t s);
-bool conv1_wgrad_lin_ok(int H, int W, int pool, int ldy, int elem_size);
-size_t conv1_wgrad_lin_scratch_floats();   // acc: totals + per-block partials
-hipError_t launch_conv1_wgrad_lin(int dtype, const Conv1WgradLinArgs& a, hipStream_t s);
+hipError_t launch_conv1_gram_stats(const Conv1Plan& p, const Conv1GramStatsArgs& a, hipStream_t s);
+hipError_t launch_conv1_wgrad_lin(const Conv1Plan& p, const Conv1WgradLinArgs& a, hipStream_t s);
 hipError_t launch_conv1_dw_finalize(const Conv1DwFinalizeArgs& a, hipStream_t s);
 
 // ---- weight-gradient GEMM  dW[t][ci][co] = scale * sum_p X[p+t][ci] * dY[p][co]

@@ -119,21 +119,10 @@ struct y2_ctx {
     size_t total_infer = 0, total_train = 0;
     int dA_cur = 0;
     int dA_half = 0;            // f16x2f: the dA buffer in use holds f16 values (written by a launch-dtype-5 dgrad)
-    // pooled 3-channel first layer, training: the linear form of its backward pass (conv1_wgrad.hip) -- its conv
-    // output is never stored
-    bool lin1() const { return bound_training && !L.empty() && L[0].idx0 != 0; }
-    // f16x2: the 3-channel layer's passes form split-operand products in registers (conv1.hip XS forms) wherever no
-    // exact-fp32 fallback recomputes its conv output (the linear-form backward, or no backward at all)
-    bool xs1() const {
-        static const bool off = getenv("Y2_CONV1_NO_XS") != nullptr;
-        return dtype_split(dtype) && !off && (lin1() || !bound_training);
-    }
-    bool nosel1() const { return lin1() && L[0].ysel == 0; }     // ... and not even the arg-max outputs (Conv1PoolArgs::idx3)
     size_t o_infertab = 0;      // BnInferLayer per layer (one prepare launch for all inference-mode layers)
     size_t o_packtab = 0, o_chkranges = 0, o_smallranges = 0, o_lin = 0, o_nfflag = 0, o_slab = 0;
     size_t o_ks = 0, ks_floats = 0;   // K-split partial tiles of small convolution launches (ConvArgs::ks_scratch)
     size_t o_gram = 0;          // first layer: Gram matrix of the input patches [48][48] + its slices / block partials
-    bool gram_valid = false;    // the last forward computed it (training mode, pooled first layer): backward reuses it
     size_t slab_floats = 0;     // split-K partial tiles of the weight gradients (WgradArgs::slab)
     int n_chkranges = 0, n_smallranges = 0, opt_tile_blocks = 0;
     // both range tables list the layers above the first one first: the optimizer step fused into the backward pass
@@ -177,6 +166,12 @@ struct y2_ctx {
     size_t sz() const { return dtype_size(dtype); }
     PadGeom in_geom(int l) const { return PadGeom{N, L[l].H, L[l].W, L[l].cin_s}; }
     PadGeom dy_geom(int l) const { return PadGeom{N, L[l].H, L[l].W, L[l].ldy}; }
+    // the passes of the 3-channel first layer (L[0].first3) on this binding; training: the BN mode of the forward planned
+    // (the backward pass plans with the last forward's)
+    Conv1Plan conv1_plan(bool trains, bool training) const {
+        const Layer& y = L[0];
+        return plan_conv1(dtype, bwd_dtype, N, y.H, y.W, y.pool, y.cout, y.ldy, trains, L.size() > 1, training);
+    }
 };
 
 enum { CAT_CONV_FWD = 0, CAT_CONV1_FWD, CAT_DGRAD, CAT_WGRAD, CAT_CONV1_WGRAD, CAT_BN_FWD, CAT_BN_BWD, CAT_MISC,
@@ -265,21 +260,15 @@ static void plan(y2_ctx* c) {
     for (size_t l = 0; l < c->L.size(); ++l) c->L[l].dyp = take(c->dy_geom((int)l).bytes(sz));
     for (size_t l = 0; l < c->L.size(); ++l) {   // pooled layers: conv output at the arg-max (BnActArgs::ysel)
         Layer& y = c->L[l];
-        const bool lin1 = y.first3 && c->L.size() > 1 && conv1_pool_ok(y.H, y.W, y.pool, y.cout) &&
-                          conv1_wgrad_lin_ok(y.H, y.W, y.pool, y.ldy, (int)sz);
-        // round 4, 16-bit types: the linear form keeps NO conv output of the first layer, only 3 index bits per element
-        // (kernels.h Conv1PoolArgs::idx3); Y2_CONV1_YSEL=1 (and the f32 parity mode) keep ysel + 2 index bits
-        static const bool keep_ysel = getenv("Y2_CONV1_YSEL") != nullptr;
-        // (f16x2: the layer's fp32-operand kernels form split products in registers -- conv1.hip / conv1_wgrad.hip XS forms -- and
-        //  take the 3-bit form too: 241 -> 210 us forward, 657 -> 617 us backward on one box; on the exact-fp32 matrix
-        //  instructions, Y2_CONV1_NO_XS=1, it had changed nothing.  Y2_CONV1_XS_YSEL=1 keeps ysel there for A/B)
-        static const bool xs_off = getenv("Y2_CONV1_NO_XS") != nullptr;
-        static const bool xs_sel = getenv("Y2_CONV1_XS_YSEL") != nullptr;
-        const bool nosel = lin1 && (dtype_plain(c->dtype) != 0 || (dtype_split(c->dtype) && !xs_off && !xs_sel)) && !keep_ysel;
-        y.ysel = (y.pool && (!y.first3 || (lin1 && !nosel))) ? take((size_t)c->N * y.Ho * y.Wo * y.ldy * sz + 256) : 0;
-        y.idx0 = lin1 ? take((size_t)c->N * y.Ho * y.Wo * (y.ldy * sz / 16) * (nosel ? sizeof(unsigned) : sizeof(unsigned short)) + 256) : 0;
-        if (lin1) c->o_lin = take(conv1_wgrad_lin_scratch_floats() * sizeof(float));
-        if (lin1 && conv1_gram_ok(y.H, y.W, (int)sz)) c->o_gram = take(conv1_gram_scratch_floats() * sizeof(float));
+        if (!y.first3) {
+            y.ysel = y.pool ? take((size_t)c->N * y.Ho * y.Wo * y.ldy * sz + 256) : 0;
+            continue;
+        }
+        const Conv1Plan p = c->conv1_plan(true, true);     // what the first layer keeps on a training binding
+        y.ysel = p.ysel_bytes ? take(p.ysel_bytes) : 0;
+        y.idx0 = p.idx_bytes ? take(p.idx_bytes) : 0;
+        if (p.lin_bytes) c->o_lin = take(p.lin_bytes);
+        if (p.gram_bytes) c->o_gram = take(p.gram_bytes);
     }
     // BN-backward partial sums [P][2][ldy]: P <= 2048 from the reduce kernel, or one record per 128+ pixel tile
     // of the dgrad above when the reduce is fused into that dgrad's epilogue
@@ -758,9 +747,9 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
         float* stat = (float*)(c->ws + y.stat);
         float *scale = stat, *shift = stat + y.ldy, *mean = stat + 2 * y.ldy, *invstd = stat + 3 * y.ldy;
         int P = 0;
-        bool folded = false, gram1 = false;
-        // pooled first layer: statistics-only conv, then conv again fused with BN + leaky + pool
-        const bool pool1 = y.first3 && l + 1 < nl && y.ldy == 32 && conv1_pool_ok(y.H, y.W, y.pool, y.cout);
+        bool folded = false;
+        const Conv1Plan p1 = y.first3 ? c->conv1_plan(c->bound_training, training) : Conv1Plan{};
+        const bool pool1 = y.first3 && p1.fwd == C1F_POOLED;
         if (y.first3) {
             {
                 PROF(CAT_MISC);
@@ -771,21 +760,8 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             a.x4 = xin; a.w = c->ws + y.wf; a.y = c->ws + y.y; a.bias = c->params + y.pb;
             a.part_cnt = part_cnt; a.part_mean = part_mean; a.part_m2 = part_m2;
             a.N = c->N; a.H = y.H; a.W = y.W; a.M = y.M;
-            int nb = (y.M + 127) / 128;
-            a.nblocks = nb > 1024 ? 1024 : nb;      // = statistics records (the plan reserves 2048 rows; 1024 vs 2048: -4 us)
-            P = a.nblocks;
-            a.stats_only = pool1 ? 1 : 0;
-            a.xs = (pool1 && c->xs1()) ? 1 : 0;
-            // round 4: the statistics of the pooled first layer come from the Gram matrix of the input patches (below)
-            static const bool no_gram = getenv("Y2_NO_CONV1_GRAM") != nullptr;
-            // Half-precision modes only: their stored activations carry 5e-4 of rounding noise, against which the ~1e-6
-            // of the fp32 MFMA sums behind the Gram moments is nothing.  The f32 parity mode keeps the statistics-only
-            // convolution pass (moments of the exact fp32 outputs, double merge): a randomly initialised 20-layer
-            // stack amplifies a 1e-6 perturbation of the first scale / shift to 1e-3 at the top, enough to flip
-            // leaky / arg-max decisions the f32 tests compare element-wise with the oracle.
-            gram1 = pool1 && training && c->lin1() && c->o_gram != 0 && !no_gram && dtype_plain(c->dtype) != 0;
-            if ((!pool1 || training) && !gram1) { PROF(CAT_CONV1_FWD); HIPCHK(launch_conv1_fwd(c->dtype, a, s)); }
-            c->gram_valid = gram1;
+            P = p1.fwd_blocks;
+            if (!pool1 || p1.stats == C1S_CONV) { PROF(CAT_CONV1_FWD); HIPCHK(launch_conv1_fwd(p1, a, s)); }
         } else {
             if (l == 0 && !c->ext_xin) HIPCHK(launch_pack_act(c->dtype, images, xin, c->N, y.H, y.W, y.cin, y.cin_s, s));
             ConvArgs a{};
@@ -836,7 +812,7 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             t.C = y.cout; t.ldy = y.ldy; t.out_f32 = 0;
             fin_fused = bn_fin_act_ok(t, f);
         }
-        if (gram1) {
+        if (y.first3 && p1.stats == C1S_GRAM) {
             Conv1GramStatsArgs q{};
             q.x4 = xin; q.N = c->N; q.H = y.H; q.Wd = y.W;
             q.W = c->params + y.pW; q.bias = c->params + y.pb; q.gamma = f.gamma; q.beta = f.beta;
@@ -844,7 +820,7 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             q.scale = scale; q.shift = shift; q.mean = mean; q.invstd = invstd; q.var = f.var;
             q.eps = f.eps; q.momentum = f.momentum; q.update_moving = f.update_moving; q.bessel = f.bessel;
             q.gram = (float*)(c->ws + c->o_gram); q.mid = q.gram + 48 * 48;
-            HIPCHK(launch_conv1_gram_stats(c->dtype, q, s));
+            HIPCHK(launch_conv1_gram_stats(p1, q, s));
         } else if (training && !fin_fused) HIPCHK(launch_bn_finalize(f, s));     // (inference: prepared for every layer above)
         if (pool1) {
             Conv1PoolArgs q{};
@@ -852,14 +828,10 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             q.scale = scale; q.shift = shift;
             q.out = c->ws + c->L[l + 1].xin + c->in_geom(l + 1).base_off(sz);
             q.N = c->N; q.H = y.H; q.W = y.W;
-            const int tiles = c->N * (y.H / 2) * ((y.W + 31) / 32);
-            q.nblocks = (tiles + 3) / 4 > 2048 ? 2048 : (tiles + 3) / 4;
-            q.store_y = (c->bound_training && !c->lin1()) ? 1 : 0;
             q.out_split = dtype_split(c->dtype) ? 1 : 0;
-            q.xs = c->xs1() ? 1 : 0;
-            if (c->nosel1()) q.idx3 = (unsigned*)(c->ws + y.idx0);
-            else if (c->lin1()) { q.ysel = c->ws + y.ysel; q.idx = (unsigned short*)(c->ws + y.idx0); }
-            HIPCHK(launch_conv1_pool(c->dtype, q, s));
+            if (p1.keep == C1K_IDX3) q.idx3 = (unsigned*)(c->ws + y.idx0);
+            if (p1.keep == C1K_YSEL) { q.ysel = c->ws + y.ysel; q.idx = (unsigned short*)(c->ws + y.idx0); }
+            HIPCHK(launch_conv1_pool(p1, q, s));
             continue;
         }
         BnActArgs b{};
@@ -954,6 +926,7 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
     bool forked = false;
     bool opt_early = false;   // fused optimizer: the layers above the first one were updated on the side stream
     int fused_P = 0;          // > 0: the dgrad of the layer above already reduced this layer's BN-backward sums
+    const Conv1Plan p1 = c->L[0].first3 ? c->conv1_plan(c->bound_training, c->fwd_training[0]) : Conv1Plan{};
     static const bool no_fuse = getenv("Y2_NO_BNBWD_FUSE") != nullptr;
     if (c->overlap_wgrad && !c->side) {
         static const bool off = getenv("Y2_NO_WGRAD_OVERLAP") != nullptr;
@@ -1001,10 +974,8 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
         b.hi_only = (c->bwd_dtype == 4 && !y.first3) ? 1 : 0;
         b.dA_half = c->dA_half;
         if (c->zero_bias_grad) b.dbias = nullptr;      // stays zero from y2_bind: the bias is not a variable of this graph
-        const bool fused1 = y.first3 && conv1_wgrad_fused_ok(y.H, y.W, y.pool, y.ldy, (int)c->sz());
-        const bool rec1 = y.first3 && (size_t)l + 1 < c->L.size() && y.ldy == 32 &&
-                          conv1_pool_ok(y.H, y.W, y.pool, y.cout);
-        const bool lin1 = y.first3 && c->lin1();
+        const bool fused1 = y.first3 && p1.bwd == C1B_FUSED;
+        const bool lin1 = y.first3 && p1.bwd == C1B_LINEAR;
         // f16x2: the 3-channel layer's own dy (un-pooled / odd-sized fallbacks) is consumed by fp32 kernels
         const int bn_dtype = y.first3 ? dtype_plain(c->dtype) : c->dtype;
         if (lin1 && c->fopt.on && forked && l == 0) {
@@ -1022,31 +993,23 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
                 // linear form: the reduce pass rides in the weight-gradient kernel, which does not need its result
                 Conv1WgradLinArgs g{};
                 g.x4 = c->ws + y.xin + c->in_geom(l).base_off(sz); g.dA = b.dA;
-                if (c->nosel1()) {
+                if (p1.keep == C1K_IDX3) {
                     g.idx3 = (const unsigned*)(c->ws + y.idx0); g.Wf = c->params + y.pW; g.bias = c->params + y.pb;
                 } else {
                     g.ysel = c->ws + y.ysel;
                     g.idx = (const unsigned short*)(c->ws + y.idx0);
                 }
                 g.scale = b.scale; g.shift = b.shift; g.acc = (float*)(c->ws + c->o_lin); g.psum = psum;
-                if (c->gram_valid) g.gram = (const float*)(c->ws + c->o_gram);
-                int nbl = 0;
-                g.nblocks_out = &nbl;
                 g.N = c->N; g.H = y.H; g.W = y.W;
-                // f16x2f: this layer's backward contractions on the hi planes too (conv1_wgrad.hip XS == 2); Y2_F16X2F_CONV1_XS3=1: A/B
-                static const bool xs3 = getenv("Y2_F16X2F_CONV1_XS3") != nullptr;
-                g.xs = c->xs1() ? ((c->bwd_dtype == 4 && !xs3) ? 2 : 1) : 0;
-                HIPCHK(launch_conv1_wgrad_lin(c->dtype, g, s));
-                b.P = nbl;
-            } else if (rec1) {   // pooled first layer: recompute the conv output instead of reading it (80 -> 24 B/pixel)
+                HIPCHK(launch_conv1_wgrad_lin(p1, g, s));
+                b.P = p1.lin_records;
+            } else if (y.first3 && p1.bwd == C1B_RECOMPUTE) {   // pooled first layer: recompute the conv output instead of reading it (80 -> 24 B/pixel)
                 Conv1BnBwdArgs q{};
                 q.x4 = c->ws + y.xin + c->in_geom(l).base_off(sz); q.w = c->ws + y.wf; q.bias = c->params + y.pb;
                 q.scale = b.scale; q.shift = b.shift; q.dA = b.dA; q.psum = psum;
                 q.N = c->N; q.H = y.H; q.W = y.W;
-                const int tiles = c->N * (y.H / 2) * ((y.W + 31) / 32);
-                q.nblocks = (tiles + 3) / 4 > 2048 ? 2048 : (tiles + 3) / 4;
-                b.P = q.nblocks;
-                HIPCHK(launch_conv1_bnbwd_reduce(c->dtype, q, s));
+                b.P = p1.pool_blocks;
+                HIPCHK(launch_conv1_bnbwd_reduce(p1, q, s));
             } else if (fused_P > 0) {
                 b.P = fused_P;
             } else {
@@ -1068,7 +1031,7 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
             Conv1DwFinalizeArgs f{};
             f.acc = (float*)(c->ws + c->o_lin); f.W = c->params + y.pW; f.bias = c->params + y.pb; f.scale = b.scale;
             f.coef = b.coef; f.dW = c->grads + y.pW; f.inv_grad_scale = inv_gs;
-            if (c->gram_valid) f.gram = (const float*)(c->ws + c->o_gram);
+            if (!p1.lin_gram) f.gram = (const float*)(c->ws + c->o_gram);
             PROF(CAT_CONV1_WGRAD);
             HIPCHK(launch_conv1_dw_finalize(f, s));
         } else if (fused1) {
@@ -1079,13 +1042,13 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
             g.dW = c->grads + y.pW;
             g.N = c->N; g.H = y.H; g.W = y.W; g.inv_grad_scale = inv_gs;
             HIPCHK(hipMemsetAsync(g.dW, 0, (size_t)27 * y.cout * sizeof(float), s));     // atomics
-            { PROF(CAT_CONV1_WGRAD); HIPCHK(launch_conv1_wgrad_fused(c->dtype, g, s)); }
+            { PROF(CAT_CONV1_WGRAD); HIPCHK(launch_conv1_wgrad_fused(p1, g, s)); }
         } else if (y.first3) {
             Conv1WgradArgs g{};
             g.x4 = xin; g.dy = dyp; g.dW = c->grads + y.pW;
             g.N = c->N; g.H = y.H; g.W = y.W; g.M = y.M; g.scale = inv_gs;
             HIPCHK(hipMemsetAsync(g.dW, 0, (size_t)27 * y.cout * sizeof(float), s));     // atomics
-            { PROF(CAT_CONV1_WGRAD); HIPCHK(launch_conv1_wgrad(c->dtype, g, s)); }
+            { PROF(CAT_CONV1_WGRAD); HIPCHK(launch_conv1_wgrad(p1, g, s)); }
         } else {
             WgradArgs g{};
             g.x = xin; g.dy = dyp; g.dW = c->grads + y.pW;
@@ -1126,7 +1089,7 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
                 const ConvKind kind = plan_conv(ldt, a).kind;
                 const bool ks = kind == CK_HALOQ_KS || kind == CK_IGEMM_KS;
                 const bool fuse = !no_fuse && !ks && l > 0 && l - 1 >= layer_lo && !z.first3 && z.ldy == y.cin;
-                if (l == 1 && z.first3 && c->fopt.on && c->fopt.ctrl && c->lin1() && forked)
+                if (l == 1 && z.first3 && c->fopt.on && c->fopt.ctrl && p1.bwd == C1B_LINEAR && forked)
                     a.nonfinite = (unsigned*)(c->ws + c->o_nfflag);   // this launch stores dA_0: the early guard's view of layer 0
                 if (fuse) {
                     float* zs = (float*)(c->ws + z.stat);
@@ -1247,25 +1210,24 @@ int y2_debug_read(y2_ctx* c, int l, int what, float* dst, void* stream) {
         if (c->fwd_folded[l])
             return fail(Y2_ERR_STATE, "layer %d: inference batch norm was folded into the convolution, its conv output "
                                       "is not stored (Y2_NO_INFER_FOLD=1 keeps the two-pass form)", l);
-        if (y.first3 && !c->bound_training && (size_t)l + 1 < c->L.size() && y.ldy == 32 &&
-            conv1_pool_ok(y.H, y.W, y.pool, y.cout))
+        const Conv1Plan p = y.first3 ? c->conv1_plan(c->bound_training, c->fwd_training[0]) : Conv1Plan{};
+        if (y.first3 && !p.y_stored && p.bwd != C1B_LINEAR)
             return fail(Y2_ERR_STATE, "inference binding: the pooled first layer does not store its conv output");
-        if (y.first3 && c->lin1()) {   // the linear form never stores this layer's conv output: recompute it (tests)
+        if (y.first3 && !p.y_stored) {   // the linear form never stores this layer's conv output: recompute it (tests)
+            Conv1Plan q = p;
+            q.fwd = C1F_PLAIN;
             Conv1Args a{};
             a.x4 = c->ws + y.xin + c->in_geom(l).base_off(sz); a.w = c->ws + y.wf; a.y = c->ws + y.y;
             a.bias = c->params + y.pb;
             a.part_cnt = (float*)(c->ws + c->o_part_cnt); a.part_mean = (float*)(c->ws + c->o_part_mean);
             a.part_m2 = (float*)(c->ws + c->o_part_m2);
             a.N = c->N; a.H = y.H; a.W = y.W; a.M = y.M;
-            const int nb = (y.M + 127) / 128;
-            a.nblocks = nb > 2048 ? 2048 : nb;
-            a.stats_only = 0;
-            HIPCHK(launch_conv1_fwd(c->dtype, a, s));
+            HIPCHK(launch_conv1_fwd(q, a, s));
         }
         HIPCHK(launch_cast_to_f32(c->dtype, c->ws + y.y, dst, (size_t)y.M, y.cout, y.ldy, s));
     } else if (what == 2) {
         if (!c->bound_training) return fail(Y2_ERR_STATE, "no gradients in inference binding");
-        if (y.first3 && (c->lin1() || conv1_wgrad_fused_ok(y.H, y.W, y.pool, y.ldy, (int)c->sz())))
+        if (y.first3 && !c->conv1_plan(c->bound_training, c->fwd_training[0]).dy_stored)
             return fail(Y2_ERR_STATE, "the first layer's dy is fused into its weight gradient and never stored");
         HIPCHK(launch_unpack_act(y.first3 ? dtype_plain(c->dtype) : c->dtype, c->ws + y.dyp + c->dy_geom(l).base_off(sz), dst, c->N, y.H, y.W, y.cout,
                                  y.ldy, s));

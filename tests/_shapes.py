@@ -385,7 +385,7 @@ def ulp_of(ref, dtype):
     return 2.0 ** (e - 7)
 
 
-def teacher_forced_stack(net, x, params, spec, dtype, first_stats=None, max_frac=0.01, max_ulps=4):
+def teacher_forced_stack(net, x, params, spec, dtype, first_stats=None, max_frac=0.01, max_ulps=4, is_training=True):
     """Quantised-oracle forward of a half-precision stack LAYER BY LAYER, every layer fed with what the DEVICE stored as
     that layer's input (y2_debug_read selector 0), so that a storage-rounding flip does not travel: the device forms its
     sums in fp32 and the oracle in float64; where a value sits within that difference of a rounding boundary of the
@@ -395,7 +395,8 @@ def teacher_forced_stack(net, x, params, spec, dtype, first_stats=None, max_frac
     layer) and SMALL (max_ulps of the storage type, or -- a flipped conv output -- two ulps at the tensor's maximum);
     everything else is bit-identical.  A wrong scale in the 4th digit moves 5 % (bf16) / 20 % (f16) of the elements.
     Returns (reference of the fp32 network output given the device's input of the last layer, caches of the device's
-    own function for run_stack_backward, [(layer, differing, size, worst as a fraction of the flip bound)])."""
+    own function for run_stack_backward, [(layer, differing, size, worst as a fraction of the flip bound)]).
+    is_training: the BN mode of every layer (False: the moving statistics)."""
     from oracle import nn_ref as R
     q = R.quantizer(dtype)
     report, caches = [], []
@@ -403,7 +404,8 @@ def teacher_forced_stack(net, x, params, spec, dtype, first_stats=None, max_frac
     out = None
     for l, (p, (_k, _ci, _co, pool)) in enumerate(zip(params, spec)):
         xin = q(x) if l == 0 else net.debug_read(l, 0).cpu().numpy().astype(np.float64)
-        out, cache, _ = R.conv_bn_layer(xin, p, True, pool, np.float64, False, q, given_stats=(first_stats if l == 0 else None))
+        out, cache, _ = R.conv_bn_layer(xin, p, is_training, pool, np.float64, False, q,
+                                        given_stats=(first_stats if l == 0 and is_training else None))
         caches.append(cache)
         if l + 1 < n:
             ref_a = q(out)

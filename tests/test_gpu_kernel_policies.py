@@ -37,8 +37,9 @@ def test_first_layer_statistics_from_the_gram_matrix(N, hw, kind, dtype):
     normalises with -- read back through the moving averages of ONE update from (0, 1): moving = 0.99 moving + 0.01 batch
     -- against float64 moments of the exact conv output.  `image`: a smooth, strongly correlated input with a non-zero
     mean (neighbouring pixels nearly equal, as in photographs): the case where sum y^2 - (sum y)^2 / M cancels and the
-    centred Gram form is needed.  Gate 1e-4 of the largest moment (observed ~1e-6; the round-3 statistics-only conv pass
-    it replaces is held to the same gate through Y2_NO_CONV1_GRAM in test_ab_switches_select_equivalent_paths)."""
+    centred Gram form is needed.  Gate 1e-4 of the largest moment (observed ~1e-6; the statistics-only conv pass that
+    the f32 parity mode and training forwards on an inference binding take is checked through the moving averages in
+    tests/test_gpu_ops.py test_stack_forward)."""
     if N * hw * hw > 3e6 and dtype != "f16":
         pytest.skip("the large geometries run in the benchmarked type only")
     # (f32: the parity mode keeps the statistics-only convolution pass -- net.hip -- and is held to the same gate)

@@ -149,6 +149,8 @@ def test_stack_forward(first3, training, dtype):
 @pytest.mark.parametrize("dtype", ["f32", "f16", "bf16"])
 @pytest.mark.parametrize("first3", [True, False])
 def test_stack_backward(first3, dtype):
+    """Batch statistics; with the 3-channel first layer also the moving ones (forward(x, False, False) on the training
+    binding): its linear-form backward then builds the Gram matrix of the input patches itself."""
     from tensorflow_yolo2_amd import engine as E
     spec, shape = _stack_case(first3)
     rng = np.random.default_rng(12)
@@ -156,7 +158,13 @@ def test_stack_backward(first3, dtype):
     x = rng.uniform(-1, 1, shape).astype(np.float32)
     net = E.Network(spec, shape[0], shape[1], shape[2], dtype=dtype, training=True)
     net.load_params(params)
-    out = net.forward(dev(x), True, True)
+    for batch_bn in ((True, False) if first3 else (True,)):
+        _stack_backward_case(net, x, params, spec, first3, dtype, batch_bn, rng)
+
+
+def _stack_backward_case(net, x, params, spec, first3, dtype, batch_bn, rng):
+    mode = "" if batch_bn else " moving statistics"
+    out = net.forward(dev(x), batch_bn, batch_bn)
     # f32 mode is checked against the exact reference semantics.  The half modes are
     # the exact gradient of a function that differs from the f32 one at max-pool /
     # leaky decisions (activations are STORED in half precision), so they are checked
@@ -169,8 +177,8 @@ def test_stack_backward(first3, dtype):
     # moments on both sides the stored half-precision activations agree again to the rounding of the arithmetic between
     # the storage points (the round-4 gates bf16 8e-3 / f16 2e-3 are back at 1e-6 / 1e-3).
     if q is None:
-        ref, caches, _ = R.run_stack(x, params, spec, True, np.float64)
-        gate("stack forward vs oracle f32 first3=%d" % first3, l2err(out.cpu().numpy(), ref), 4e-6)   # observed 1.5e-6
+        ref, caches, _ = R.run_stack(x, params, spec, batch_bn, np.float64)
+        gate("stack forward vs oracle f32 first3=%d%s" % (first3, mode), l2err(out.cpu().numpy(), ref), 4e-6)   # observed 1.5e-6
     else:
         # The oracle runs layer by layer on the device's stored inputs and the storage-rounding flips are gated as flips
         # (few, a few ulps: tests/_shapes.py teacher_forced_stack); the fp32 network output, given the device's input of
@@ -178,12 +186,12 @@ def test_stack_backward(first3, dtype):
         # free-running stack, round 4's 2e-3 / 8e-3)
         from _shapes import teacher_forced_stack
         first_stats = None
-        if first3:
+        if first3 and batch_bn:
             st = net.layer_statistics(0)
             first_stats = (st["mean"], st["var"])
-        ref, caches, report = teacher_forced_stack(net, x, params, spec, dtype, first_stats)
+        ref, caches, report = teacher_forced_stack(net, x, params, spec, dtype, first_stats, is_training=batch_bn)
         print("stored activations that differ from the quantised oracle (layer, count, of, worst ulps):", report)
-        gate("stack forward vs quantised oracle %s first3=%d" % (dtype, first3), l2err(out.cpu().numpy(), ref), 5e-5)
+        gate("stack forward vs quantised oracle %s first3=%d%s" % (dtype, first3, mode), l2err(out.cpu().numpy(), ref), 5e-5)
     dout = rng.standard_normal(ref.shape).astype(np.float32)
     net.backward(dev(dout))
     _, rgrads = R.run_stack_backward(params, caches, dout.astype(np.float64), np.float64, quant=q,
@@ -191,11 +199,11 @@ def test_stack_backward(first3, dtype):
     grads = net.export_grads()
     tol = {"f32": 5e-6, "f16": 4e-3, "bf16": 1e-2}[dtype]    # observed 1.7e-6 / 1.9e-3 / 4.3e-3
     for l in range(len(spec)):
-        for k in ("W", "gamma", "beta"):
-            gate("stack backward %s first3=%d" % (dtype, first3), l2err(grads[l][k], rgrads[l][k]), tol)
-        # conv bias gradient is mathematically zero under batch-stat BN: absolute check
-        scale = np.abs(rgrads[l]["gamma"]).max() + np.abs(rgrads[l]["beta"]).max()
-        assert np.abs(grads[l]["b"]).max() < 1e-2 * scale + 1e-3
+        for k in ("W", "gamma", "beta") if batch_bn else ("W", "gamma", "beta", "b"):
+            gate("stack backward %s first3=%d%s" % (dtype, first3, mode), l2err(grads[l][k], rgrads[l][k]), tol)
+        if batch_bn:   # conv bias gradient is mathematically zero under batch-stat BN: absolute check
+            scale = np.abs(rgrads[l]["gamma"]).max() + np.abs(rgrads[l]["beta"]).max()
+            assert np.abs(grads[l]["b"]).max() < 1e-2 * scale + 1e-3
 
 
 def test_stack_backward_mixed_bn_modes():
