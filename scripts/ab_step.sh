@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of the WHOLE train step under environment switches / library builds (box-to-box spread is +-5 %).
-#   scripts/ab_step.sh "NAME=ENV..." ...   e.g.  scripts/ab_step.sh "default=" "side_low=Y2_SIDE_PRIORITY=low"
+#   scripts/ab_step.sh "NAME=ENV..." ...   e.g.  scripts/ab_step.sh "default=" "no_overlap=Y2_NO_WGRAD_OVERLAP=1"
 # Three interleaved rounds of `bench.py` (20 event-bracketed steps + 200 sustained steps, no other legs), the arm order
 # rotated every round (the first run after an idle gap reads ~0.5 % slow: an arm that always runs first looks worse than
 # it is); prints the minimum of the timed and of the sustained ms per step for every arm.

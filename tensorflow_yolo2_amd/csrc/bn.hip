@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(BnActArgs a) {
 // statistics for the backward pass; then the slab's pixels as in bn_act_kernel.  One launch and ~6 us of critical
 // path less per layer than merge + apply.
 // ---------------------------------------------------------------------------
-constexpr int kSlab = 64;
+constexpr int kSlab = kBnSlab;
 Y2_DEV void fin_slab_merge(const BnFinalizeArgs& f, int cbase, double (*red)[kSlab][3], float* s_sc, float* s_sh, bool writer) {
     const int c = threadIdx.x & (kSlab - 1), sl = threadIdx.x >> 6;   // 256 threads: 4 slices
     const int cc = cbase + c;
@@ -487,10 +487,6 @@ __global__ __launch_bounds__(256) void bn_fin_act_kernel(BnActArgs a, BnFinalize
     }
 }
 
-bool bn_fin_act_ok(const BnActArgs& a, const BnFinalizeArgs& f) {
-    static const int pmax = getenv("Y2DEV_FIN_PMAX") ? atoi(getenv("Y2DEV_FIN_PMAX")) : 128;
-    return f.P > 0 && f.P <= pmax && !a.out_f32 && a.ldy % kSlab == 0 && a.C == a.ldy && f.ldp == a.ldy;
-}
 template <typename T, bool SPLIT = false>
 static hipError_t bn_fin_act_T(const BnActArgs& a, const BnFinalizeArgs& f, hipStream_t s) {
     constexpr int EPC = 16 / sizeof(T);
@@ -509,7 +505,8 @@ static hipError_t bn_fin_act_T(const BnActArgs& a, const BnFinalizeArgs& f, hipS
     return hipGetLastError();
 }
 hipError_t launch_bn_fin_act(int dtype, const BnActArgs& a, const BnFinalizeArgs& f, hipStream_t s) {
-    if (!bn_fin_act_ok(a, f)) return hipErrorInvalidValue;
+    if (f.P < 1 || f.P > kBnFinPmax || a.out_f32 || a.ldy % kSlab != 0 || a.C != a.ldy || f.ldp != a.ldy)
+        return hipErrorInvalidValue;
     switch (dtype) {
         case 0: return bn_fin_act_T<float>(a, f, s);
         case 1: return bn_fin_act_T<half_t>(a, f, s);
@@ -998,9 +995,6 @@ __global__ __launch_bounds__(256) void bn_bwd_fin_apply_kernel(BnBwdArgs a) {
     }
 }
 
-bool bn_bwd_fin_apply_ok(const BnBwdArgs& a) {
-    static const int pmax = getenv("Y2DEV_FIN_PMAX") ? atoi(getenv("Y2DEV_FIN_PMAX")) : 128;
-    return a.P > 0 && a.P <= pmax && a.ldy % kSlab == 0 && a.C == a.ldy; }
 template <typename T, bool SPLIT = false>
 static hipError_t bn_bwd_fin_apply_T(const BnBwdArgs& a, hipStream_t s) {
     constexpr int EPC = 16 / sizeof(T);
@@ -1018,7 +1012,7 @@ static hipError_t bn_bwd_fin_apply_T(const BnBwdArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 hipError_t launch_bn_bwd_fin_apply(int dtype, const BnBwdArgs& a, hipStream_t s) {
-    if (!bn_bwd_fin_apply_ok(a)) return hipErrorInvalidValue;
+    if (a.P < 1 || a.P > kBnFinPmax || a.ldy % kSlab != 0 || a.C != a.ldy) return hipErrorInvalidValue;
     switch (dtype) {
         case 0: return bn_bwd_fin_apply_T<float>(a, s);
         case 1: return bn_bwd_fin_apply_T<half_t>(a, s);
@@ -1040,7 +1034,9 @@ static int bwd_blocks(const BnBwdArgs& a) {
     if (nb < 1) nb = 1;
     return (int)nb;
 }
-int bn_bwd_partials(const BnBwdArgs& a) { return 2048; }
+int bn_bwd_reduce_records(int dtype, const BnBwdArgs& a) {
+    return dtype == 1 ? bwd_blocks<half_t>(a) : dtype == 2 ? bwd_blocks<bf16_t>(a) : bwd_blocks<float>(a);
+}
 
 template <typename T, bool APPLY, bool SPLIT = false>
 static hipError_t bn_bwd_T(const BnBwdArgs& a, hipStream_t s) {
@@ -1049,12 +1045,13 @@ static hipError_t bn_bwd_T(const BnBwdArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((bn_bwd_kernel<T, false, APPLY, SPLIT>), g, b, 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_bn_bwd_reduce(int dtype, BnBwdArgs& a, hipStream_t s) {
+hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t s) {
+    if (a.P != bn_bwd_reduce_records(dtype, a)) return hipErrorInvalidValue;
     switch (dtype) {
-        case 0: a.P = bwd_blocks<float>(a); return bn_bwd_T<float, false>(a, s);
-        case 1: a.P = bwd_blocks<half_t>(a); return bn_bwd_T<half_t, false>(a, s);
-        case 2: a.P = bwd_blocks<bf16_t>(a); return bn_bwd_T<bf16_t, false>(a, s);
-        case 3: a.P = bwd_blocks<float>(a); return bn_bwd_T<float, false>(a, s);     // f16x2: every input of the pass is fp32
+        case 0: return bn_bwd_T<float, false>(a, s);
+        case 1: return bn_bwd_T<half_t, false>(a, s);
+        case 2: return bn_bwd_T<bf16_t, false>(a, s);
+        case 3: return bn_bwd_T<float, false>(a, s);     // f16x2: every input of the pass is fp32
     }
     return hipErrorInvalidValue;
 }
@@ -1103,18 +1100,15 @@ __global__ __launch_bounds__(256) void bn_stats_sub_kernel(const T* __restrict__
     }
 }
 hipError_t launch_bn_stats_sub(int dtype, const void* y, int N, int H, int W, int ldy, float* part_cnt, float* part_mean,
-                               float* part_m2, int* records, hipStream_t s) {
+                               float* part_m2, hipStream_t s) {
     if ((H & 1) || (W & 1)) return hipErrorInvalidValue;
-    const int mout = N * (H / 2) * (W / 2);
-    const int rec = (mout + kBnSubRec - 1) / kBnSubRec;
-    const dim3 g((ldy + 63) / 64, rec), b(256);
+    const dim3 g((ldy + 63) / 64, bn_stats_sub_records(N, H, W)), b(256);
     switch (dtype) {
         case 0: case 3: hipLaunchKernelGGL(bn_stats_sub_kernel<float>, g, b, 0, s, (const float*)y, N, H, W, ldy, part_cnt, part_mean, part_m2); break;
         case 1: hipLaunchKernelGGL(bn_stats_sub_kernel<half_t>, g, b, 0, s, (const half_t*)y, N, H, W, ldy, part_cnt, part_mean, part_m2); break;
         case 2: hipLaunchKernelGGL(bn_stats_sub_kernel<bf16_t>, g, b, 0, s, (const bf16_t*)y, N, H, W, ldy, part_cnt, part_mean, part_m2); break;
         default: return hipErrorInvalidValue;
     }
-    if (records) *records = rec;
     return hipGetLastError();
 }
 

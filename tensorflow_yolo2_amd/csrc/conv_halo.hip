@@ -15,6 +15,9 @@
 // counted vmcnt and raw s_barrier (loads stay in flight across the barrier).
 #include <stdio.h>
 #include <stdlib.h>
+
+#include <algorithm>
+
 #include "common.h"
 #include "conv_epilogue.h"
 #include "kernels.h"
@@ -343,13 +346,29 @@ static int rf_config(int taps, int W, int row_bytes, int Cout, int M) {
     if (row_bytes == 128 && Cout <= 32) return 2;
     return 0;
 }
-// 3: the 128-cout form: forward (with statistics), plain, and dgrad with the fused BN-backward reduce
-static int rfn_config(int taps, int W, int row_bytes, int Cout, int M, int dgrad) {
+// the tile and LDS of each config (bw: with the fused BN-backward reduce), the template arguments of conv_rf.hip rf_T
+struct RfForm { int bp, bc, lds; };
+static RfForm rf_form(int cfg, bool bw) {
+    switch (cfg) {
+        case 1: return {256, 64, rf_lds(2, 32, 2, 8, 1, 32)};
+        case 2: return {256, 32, rf_lds(2, 64, 1, 8, 1, 32)};
+        case 3: return {128, 128, rfn_lds(2, 64, 2, 4, 2, 4, bw)};
+        default: return {64, 128, rfn_lds(2, 64, 1, 4, 2, 6, bw)};      // 4: the development build's six-slot ring
+    }
+}
+// 3: the 128-cout form: forward (with statistics), plain, and dgrad with the fused BN-backward reduce (bw), where its LDS fits
+static int rfn_config(int taps, int W, int row_bytes, int Cout, int M, int dgrad, bool bw) {
     static const bool off = getenv("Y2_NO_CONV_RF") != nullptr;
     static const bool nodg = getenv("Y2_NO_CONV_RFN_DGRAD") != nullptr;
     if (off || (dgrad && nodg) || taps != 9 || W <= 52 || W + 2 > 128 || M < 128 * 1024) return 0;
-    if (row_bytes == 128 && Cout > 64 && Cout <= 128) return 3;
-    return 0;
+    if (!(row_bytes == 128 && Cout > 64 && Cout <= 128)) return 0;
+#ifdef Y2_DEVBUILD
+    static const int alt = getenv("Y2DEV_RF_ALT") ? atoi(getenv("Y2DEV_RF_ALT")) : 0;
+    const int cfg = alt == 1 ? 4 : 3;
+#else
+    const int cfg = 3;
+#endif
+    return rf_form(cfg, bw).lds <= kLdsMax ? cfg : 0;
 }
 
 // ---- K split of small launches (conv_haloq_kernel / conv_igemm_kernel <.., KS>): the depth fills ~one round of the chip
@@ -533,14 +552,23 @@ static int dev_rule(int W, int Cout) {
 }
 #endif
 
-ConvPlan plan_conv(int dtype, const ConvArgs& a) {
+static ConvPlan plan_route(int dtype, const ConvArgs& a) {
     ConvPlan p{CK_IGEMM, 0, 0, 0, 1};
     const int kb = a.C * dtype_kbytes(dtype);       // bytes of one operand plane per pixel: what the K chunks divide
     const bool split = dtype_split(dtype);
-    const int rf = rf_config(a.taps, a.W, kb, a.Cout, a.M), rfn = rfn_config(a.taps, a.W, kb, a.Cout, a.M, a.is_dgrad);
+    const int rf = rf_config(a.taps, a.W, kb, a.Cout, a.M);
+    const int rfn = rfn_config(a.taps, a.W, kb, a.Cout, a.M, a.is_dgrad, a.bw_psum != nullptr);
     if ((dtype == 1 || dtype == 2) && ((!a.bw_psum && rf) || rfn)) {
         p.kind = rf && !a.bw_psum ? CK_RF : CK_RFN;
         p.cfg = p.kind == CK_RF ? rf : rfn;
+        // the persistent grid: two workgroups per CU where the LDS allows, whole tiles per workgroup, one record each
+        const RfForm f = rf_form(p.cfg, a.bw_psum != nullptr);
+        const int ntiles = (int)(((long)a.N * (a.H + 1) * (a.W + 1) + f.bp - 1) / f.bp);
+        const int nblk = std::min((f.lds <= 80 * 1024 ? 512 : 256) / ((a.Cout + f.bc - 1) / f.bc), ntiles);
+        p.rf_tiles = (ntiles + nblk - 1) / nblk;
+        p.records = (ntiles + p.rf_tiles - 1) / p.rf_tiles;
+        p.block_pixels = f.bp;
+        p.lds = f.lds;
         return p;
     }
     // conv_haloq: 3x3 up to 104 wide and the 208-wide 32-cout dgrad, where the register-filter form does not apply (not
@@ -593,49 +621,25 @@ ConvPlan plan_conv(int dtype, const ConvArgs& a) {
     }
     return p;
 }
-
-// Inference batch norm folded into the epilogue (ConvArgs::aff_*): every kernel on the shared epilogue
-// (conv_epilogue.h); the register-filter kernels (conv_rf.hip) keep the two-pass form.  Y2_NO_INFER_FOLD=1: A/B switch.
-bool conv_affine_ok(int dtype, const ConvArgs& a) {
-    static const bool off = getenv("Y2_NO_INFER_FOLD") != nullptr;
-    if (off || a.bw_psum || a.part_mean || a.is_dgrad) return false;
-    if (dtype_split(dtype)) return false;      // f16x2: the consumer's tensor is split (two planes); two-pass form
-    // conv_rf.hip: the 128-cout forward form stores wave-private row segments and folds too; the 208-wide
-    // 32 <-> 64 forms (pooled layers in Darknet-19) keep the two-pass form
-    const ConvPlan p = plan_conv(dtype, a);
-    if (p.kind == CK_RF || (p.kind == CK_RFN && (a.ldy % 8) != 0)) return false;
-    return a.M > 0 && (unsigned)a.M < 0x7FFFFFFFu;
+ConvPlan plan_conv(int dtype, const ConvArgs& a) {
+    ConvPlan p = plan_route(dtype, a);
+    if (p.kind != CK_RF && p.kind != CK_RFN) p.records = (a.M + p.block_pixels - 1) / p.block_pixels;
+    return p;
 }
 
-// Pooled layers in the fold (ConvArgs::aff_pool): the conv_haloq kernels on the bordered image (their tiles take any
-// pixel order inside a contiguous run of cells); whole windows only; not the K-split small launches.
-// Y2_NO_POOL_FOLD=1: A/B switch.
-bool conv_affine_pool_ok(int dtype, const ConvArgs& a) {
-    static const bool off = getenv("Y2_NO_POOL_FOLD") != nullptr;
-    if (off || !conv_affine_ok(dtype, a)) return false;
-    if (a.taps != 9 || (a.H & 1) || (a.W & 1) || a.M < 384 * 8) return false;
-    return plan_conv(dtype, a).kind == CK_HALOQ;
-}
-
-hipError_t launch_conv(int dtype, const ConvArgs& a0, hipStream_t s, int filter_layout, int* block_pixels, int* records) {
+hipError_t launch_conv(int dtype, const ConvArgs& a0, hipStream_t s, int filter_layout) {
     // XCD-aware workgroup order: measured +1..4 % on every 3x3 layer up to 104x104 (common.h xcd_block)
     static const int xcd_mode = getenv("Y2_XCD_CONV") ? atoi(getenv("Y2_XCD_CONV")) : 1;
     ConvArgs a = a0;
     a.xcd = xcd_mode;
     const ConvPlan p = plan_conv(dtype, a);
     if (filter_layout != p.filter_layout) return hipErrorInvalidValue;     // the filters were packed for another kernel
-    int bp = p.block_pixels, rec = 0;
-    hipError_t e;
     switch (p.kind) {
-        case CK_RF: case CK_RFN: e = launch_conv_rf(dtype, p, a, s, &bp, &rec); break;
-        case CK_HALOQ: case CK_HALOQ_KS: e = launch_conv_haloq(dtype, p, a, s); break;
-        case CK_HALO: e = launch_conv_halo(dtype, p, a, s); break;
-        default: e = launch_conv_igemm(dtype, p, a, s); break;
+        case CK_RF: case CK_RFN: return launch_conv_rf(dtype, p, a, s);
+        case CK_HALOQ: case CK_HALOQ_KS: return launch_conv_haloq(dtype, p, a, s);
+        case CK_HALO: return launch_conv_halo(dtype, p, a, s);
+        default: return launch_conv_igemm(dtype, p, a, s);
     }
-    if (p.kind != CK_RF && p.kind != CK_RFN) rec = (a.M + bp - 1) / bp;
-    if (block_pixels) *block_pixels = bp;
-    if (records) *records = rec;
-    return e;
 }
 
 #ifdef Y2_DEVBUILD

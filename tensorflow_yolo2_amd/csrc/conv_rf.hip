@@ -328,21 +328,23 @@ __global__ __launch_bounds__(WP * 64, 2) void conv_rf_kernel(ConvArgs a, RfGeom 
     }
 }
 
-template <typename T, int C, int NCT, int WP, int TP, int PR, int PD>
-static hipError_t rf_launch(const ConvArgs& a, hipStream_t s, int* bp, int* records) {
-    typedef RfCfg<T, C, NCT, WP, TP, PR> Cfg;
-    if (a.ldy > 128 || a.ldy % 8 != 0) return hipErrorInvalidValue;   // masked stores land in y's 256-byte slack row
+// the geometry of the persistent grid: plan_conv (conv_halo.hip), from the config's rf_form / rf_lds
+static RfGeom rf_geom(const ConvPlan& p, const ConvArgs& a) {
     RfGeom g{};
     g.pitch = a.W + 1;
     g.rows_img = a.H + 1;
-    const long qtot = (long)a.N * g.rows_img * g.pitch;
-    g.ntiles = (int)((qtot + Cfg::BP - 1) / Cfg::BP);
+    g.ntiles = (int)(((long)a.N * g.rows_img * g.pitch + p.block_pixels - 1) / p.block_pixels);
+    g.tiles_per_block = p.rf_tiles;
     g.qmax = (int)bbody_pixels(a.N, a.H, a.W);
-    const int nct = (a.Cout + Cfg::BC - 1) / Cfg::BC;
-    int nblk = (Cfg::LDS <= 80 * 1024 ? 512 : 256) / nct;    // two workgroups per CU where the LDS allows
-    if (nblk > g.ntiles) nblk = g.ntiles;
-    g.tiles_per_block = (g.ntiles + nblk - 1) / nblk;
-    nblk = (g.ntiles + g.tiles_per_block - 1) / g.tiles_per_block;
+    return g;
+}
+
+template <typename T, int C, int NCT, int WP, int TP, int PR, int PD>
+static hipError_t rf_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    typedef RfCfg<T, C, NCT, WP, TP, PR> Cfg;
+    static_assert(Cfg::LDS == rf_lds(Cfg::SZ, C, NCT, WP, TP, PR), "kernels.h rf_lds");
+    if (a.ldy > 128 || a.ldy % 8 != 0) return hipErrorInvalidValue;   // masked stores land in y's 256-byte slack row
+    if (p.block_pixels != Cfg::BP || p.lds != Cfg::LDS) return hipErrorInvalidValue;
     auto kern = conv_rf_kernel<T, C, NCT, WP, TP, PR, PD>;
     static bool attr = false;
     if (!attr) {
@@ -350,9 +352,7 @@ static hipError_t rf_launch(const ConvArgs& a, hipStream_t s, int* bp, int* reco
         if (e != hipSuccess) return e;
         attr = true;
     }
-    hipLaunchKernelGGL(kern, dim3(nblk, nct), dim3(Cfg::NT), Cfg::LDS, s, a, g);
-    if (bp) *bp = Cfg::BP;
-    if (records) *records = nblk;          // one record per workgroup
+    hipLaunchKernelGGL(kern, dim3(p.records, (a.Cout + Cfg::BC - 1) / Cfg::BC), dim3(Cfg::NT), Cfg::LDS, s, a, rf_geom(p, a));
     return hipGetLastError();
 }
 
@@ -776,23 +776,14 @@ hipError_t rf_read_stamps(unsigned long long* dst) {
 #endif
 
 template <typename T, int C, int WP, int WN, int TP, int PD, int NSLOT, int AH>
-static hipError_t rfn_launch(const ConvArgs& a, hipStream_t s, int* bp, int* records) {
+static hipError_t rfn_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
     typedef RfnCfg<T, C, WP, WN, TP, NSLOT, AH> Cfg;
+    static_assert(Cfg::LDS == rfn_lds(Cfg::SZ, C, WP, WN, TP, NSLOT, false) &&
+                  Cfg::LDS_BW == rfn_lds(Cfg::SZ, C, WP, WN, TP, NSLOT, true), "kernels.h rfn_lds");
     if (a.ldy > 128 || a.ldy % 8 != 0) return hipErrorInvalidValue;
-    RfGeom g{};
-    g.pitch = a.W + 1;
-    g.rows_img = a.H + 1;
-    if (g.pitch + 1 > Cfg::AH * Cfg::BP) return hipErrorInvalidValue;     // the halo must stay inside the AH neighbouring groups
-    const long qtot = (long)a.N * g.rows_img * g.pitch;
-    g.ntiles = (int)((qtot + Cfg::BP - 1) / Cfg::BP);
-    g.qmax = (int)bbody_pixels(a.N, a.H, a.W);
-    const int nct = (a.Cout + Cfg::BC - 1) / Cfg::BC;
+    if (a.W + 2 > Cfg::AH * Cfg::BP) return hipErrorInvalidValue;     // the halo must stay inside the AH neighbouring groups
     const int lds = a.bw_psum ? Cfg::LDS_BW : Cfg::LDS;
-    if (lds > 160 * 1024) return hipErrorOutOfMemory;
-    int nblk = (lds <= 80 * 1024 ? 512 : 256) / nct;
-    if (nblk > g.ntiles) nblk = g.ntiles;
-    g.tiles_per_block = (g.ntiles + nblk - 1) / nblk;
-    nblk = (g.ntiles + g.tiles_per_block - 1) / g.tiles_per_block;
+    if (p.block_pixels != Cfg::BP || p.lds != lds) return hipErrorInvalidValue;
     auto kern = a.bw_psum ? conv_rfn_kernel<T, C, WP, WN, TP, PD, NSLOT, AH, true>
                           : conv_rfn_kernel<T, C, WP, WN, TP, PD, NSLOT, AH, false>;
     static int attr[2] = {0, 0};
@@ -801,31 +792,30 @@ static hipError_t rfn_launch(const ConvArgs& a, hipStream_t s, int* bp, int* rec
         if (e != hipSuccess) return e;
         attr[a.bw_psum ? 1 : 0] = lds;
     }
-    hipLaunchKernelGGL(kern, dim3(nblk, nct), dim3(Cfg::NT), lds, s, a, g);
-    if (bp) *bp = Cfg::BP;
-    if (records) *records = nblk;          // one record per workgroup
+    hipLaunchKernelGGL(kern, dim3(p.records, (a.Cout + Cfg::BC - 1) / Cfg::BC), dim3(Cfg::NT), lds, s, a, rf_geom(p, a));
     return hipGetLastError();
 }
 
 template <typename T>
-static hipError_t rf_T(int cfg, const ConvArgs& a, hipStream_t s, int* bp, int* records) {
+static hipError_t rf_T(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
     // measured (scripts/profile_layers.py): the lead of the fragment reads (1..4 steps) does not matter -- two waves
     // per SIMD cover each other's LDS latency; two 4-wave workgroups per CU (64-position tiles, six-slot ring) are 5 %
     // SLOWER than one 8-wave workgroup on the 128-cout layers (a lone wave cannot keep the matrix pipe busy)
-    if (cfg == 1) return rf_launch<T, 32, 2, 8, 1, 32, 2>(a, s, bp, records);
-    if (cfg == 2) return rf_launch<T, 64, 1, 8, 1, 32, 3>(a, s, bp, records);
+    switch (p.cfg) {
+        case 1: return rf_launch<T, 32, 2, 8, 1, 32, 2>(p, a, s);
+        case 2: return rf_launch<T, 64, 1, 8, 1, 32, 3>(p, a, s);
 #ifdef Y2_DEVBUILD
-    static const int alt = getenv("Y2DEV_RF_ALT") ? atoi(getenv("Y2DEV_RF_ALT")) : 0;
-    if (cfg == 3 && alt == 1) return rfn_launch<T, 64, 1, 4, 2, 2, 6, 2>(a, s, bp, records);
+        case 4: return rfn_launch<T, 64, 1, 4, 2, 2, 6, 2>(p, a, s);     // Y2DEV_RF_ALT=1
 #endif
-    if (cfg == 3) return rfn_launch<T, 64, 2, 4, 2, 2, 4, 1>(a, s, bp, records);
+        case 3: return rfn_launch<T, 64, 2, 4, 2, 2, 4, 1>(p, a, s);
+    }
     return hipErrorInvalidValue;
 }
 // the configs of plan_conv (conv_halo.hip rf_config / rfn_config)
-hipError_t launch_conv_rf(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* bp, int* records) {
-    if (p.kind != (p.cfg == 3 ? CK_RFN : CK_RF)) return hipErrorInvalidValue;
-    if (dtype == 1) return rf_T<half_t>(p.cfg, a, s, bp, records);
-    if (dtype == 2) return rf_T<bf16_t>(p.cfg, a, s, bp, records);
+hipError_t launch_conv_rf(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    if (p.kind != (p.cfg >= 3 ? CK_RFN : CK_RF)) return hipErrorInvalidValue;
+    if (dtype == 1) return rf_T<half_t>(p, a, s);
+    if (dtype == 2) return rf_T<bf16_t>(p, a, s);
     return hipErrorInvalidValue;
 }
 

@@ -81,15 +81,11 @@ inline void conv_set_affine(ConvArgs& a, const float* scale, const float* shift,
     conv_div_magic((uint32_t)a.W, &a.aff_magW, &a.aff_shW);
     conv_div_magic((uint32_t)a.H, &a.aff_magH, &a.aff_shH);
 }
-// which launches take the folded form (else: y + the bn_act pass)
-bool conv_affine_ok(int dtype, const ConvArgs& a);
-// ... and which POOLED layers do (ConvArgs::aff_pool; conv_affine_ok holds too)
-bool conv_affine_pool_ok(int dtype, const ConvArgs& a);
 
 // ---- conv kernel policy (conv_halo.hip): plan_conv decides every forward / dgrad launch, the launchers execute its answer
 enum ConvKind {
     CK_RF,          // conv_rf.hip: filters resident in registers, 208-wide 32 <-> 64 layers (cfg 1, 2)
-    CK_RFN,         //   ... the 128-cout form (cfg 3)
+    CK_RFN,         //   ... the 128-cout form (cfg 3; development build: cfg 4, Y2DEV_RF_ALT=1)
     CK_HALOQ,       // conv_haloq.hip: halo image in LDS, filter fragments straight to registers
     CK_HALOQ_KS,    //   ... K split over workgroups + conv_ks_finish (launches of a few hundred pixels)
     CK_HALO,        // conv_halo.hip: halo image + LDS filter ring
@@ -100,9 +96,25 @@ struct ConvPlan {
     ConvKind kind;
     int cfg;            // rf: config 1-3; the other kinds: a conv_tile() (development build: a conv_halo variant number)
     int filter_layout;  // what the filter pack must hold: 0 K-contiguous rows, 1 32-row / 2 16-row MFMA fragments
-    int block_pixels;   // pixels per BN partial record (rf kinds: set by the launch, a persistent grid)
+    int block_pixels;   // pixels per tile (the BN partial records of the non-rf kinds cover one tile each)
     int ks_depth;       // K splits of the *_KS kinds (after the scratch-size clamp), else 1
+    int records;        // BN partial records a launch with statistics writes (rf kinds: one per workgroup)
+    int rf_tiles;       // rf kinds: tiles per workgroup of the persistent grid (records = workgroups over the pixels)
+    int lds;            // rf kinds: dynamic LDS bytes of a workgroup (rf_lds / rfn_lds)
 };
+// LDS of the register-filter kernels (conv_rf.hip; sz = bytes of an element, C = input channels).  plan_conv sizes the
+// persistent grid with them; the launchers check them against their kernel's layout at compile time.
+//   rf: a ring of 4 groups of bp rows, per wave an epilogue patch of pr rows + doubles S1, S2 and a count, the bias slice
+constexpr int rf_lds(int sz, int C, int nct, int wp, int tp, int pr) {
+    return 4 * wp * tp * 32 * C * sz + wp * pr * (nct * 32 * sz + 16) + wp * (2 * nct * 32 + 2) * 8 + nct * 32 * 4;
+}
+//   rfn: a ring of nslot groups, one [bp][bc] patch, the waves' statistics, row table and bias slice; bw (the fused
+//   BN-backward reduce of the layer below): + that layer's conv output tile and its scale / shift
+constexpr int rfn_lds(int sz, int C, int wp, int wn, int tp, int nslot, bool bw) {
+    const int bp = wp * tp * 32, bc = wn * 32, nw = wp * wn;
+    return nslot * bp * C * sz + bp * (bc * sz + 16) + 2 * (nw * 2 * bc + nw) * 4 + bp * 4 + bc * 4 +
+           (bw ? bp * bc * sz + 2 * bc * 4 : 0);
+}
 // a kernel tile as one int: waves over pixels x couts, 32-wide MFMA units per wave, K-chunk bytes (64 / 128) and one
 // family field (haloq: 16x16 MFMA tiles; halo, igemm: stages of the ring)
 constexpr int conv_tile(int wp, int wc, int tp, int tc, int bkb, int aux) {
@@ -117,12 +129,10 @@ struct ConvTile {
 };
 // no HIP calls, no side effects
 ConvPlan plan_conv(int dtype, const ConvArgs& a);
-// plan_conv + the launch; filter_layout = the layout the filters were packed in (hipErrorInvalidValue unless the plan's).
-// *records = rows of the BN partial list written
-hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t s, int filter_layout, int* block_pixels = nullptr,
-                       int* records = nullptr);
+// plan_conv + the launch; filter_layout = the layout the filters were packed in (hipErrorInvalidValue unless the plan's)
+hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t s, int filter_layout);
 // the family launchers (launch_conv's switch): hipErrorInvalidValue for a plan they cannot run
-hipError_t launch_conv_rf(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s, int* block_pixels, int* records);
+hipError_t launch_conv_rf(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_haloq(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_halo(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_igemm(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
@@ -554,14 +564,15 @@ struct BnActArgs {
                                    // y2_link: bottleneck units chained without an fp32 hand-over); either output form
 };
 hipError_t launch_bn_act(int dtype, const BnActArgs& a, hipStream_t s);
-// merge of a short partial list (P <= 128) + apply in one launch (64-channel slabs); bn_fin_act_ok says whether it applies
-bool bn_fin_act_ok(const BnActArgs& a, const BnFinalizeArgs& f);
+// merge of a short partial list (P <= kBnFinPmax) + apply in one launch (kBnSlab-channel slabs: C = ldy = ldp, a multiple)
+constexpr int kBnSlab = 64, kBnFinPmax = 128;
 hipError_t launch_bn_fin_act(int dtype, const BnActArgs& a, const BnFinalizeArgs& f, hipStream_t s);
 // subsampling layers (BnActArgs::pool == 2): (count, mean, M2) records of the conv output y [N*H*W][ldy] over the KEPT
-// positions (even rows and columns), one record per kBnSubRec kept pixels; *records = their number
+// positions (even rows and columns), one record per kBnSubRec kept pixels
 constexpr int kBnSubRec = 256;
+constexpr int bn_stats_sub_records(int N, int H, int W) { return (N * (H / 2) * (W / 2) + kBnSubRec - 1) / kBnSubRec; }
 hipError_t launch_bn_stats_sub(int dtype, const void* y, int N, int H, int W, int ldy, float* part_cnt, float* part_mean,
-                               float* part_m2, int* records, hipStream_t s);
+                               float* part_m2, hipStream_t s);
 
 struct BnBwdArgs {
     const void* dA;       // grad wrt layer output [M_out][ldd] of T (scaled by grad_scale)
@@ -580,17 +591,17 @@ struct BnBwdArgs {
     int pool;
     int training;         // batch statistics (1) or moving statistics (0)
     float inv_grad_scale;
-    int P;                // number of partial blocks (set by launcher)
+    int P;                // number of partial records (the reduce: bn_bwd_reduce_records)
     float slope = 0.1f;   // activation slope of the forward pass
     int hi_only = 0;      // f16x2f (split dyp): the consumers read the hi plane of dY alone -- the lo plane is not written
     int dA_half = 0;      // f16x2f (T = float kernels): dA [M_out][ldd] is f16 (written by a launch-dtype-5 dgrad, common.h hsplithh_t)
 };
-int bn_bwd_partials(const BnBwdArgs& a);
-hipError_t launch_bn_bwd_reduce(int dtype, BnBwdArgs& a, hipStream_t s);
+// records of the standalone reduce (its grid)
+int bn_bwd_reduce_records(int dtype, const BnBwdArgs& a);
+hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t s);
 hipError_t launch_bn_bwd_finalize(const BnBwdArgs& a, hipStream_t s);
 hipError_t launch_bn_bwd_apply(int dtype, const BnBwdArgs& a, hipStream_t s);
-// finalize of a short partial list (P <= 128) + apply in one launch (64-channel slabs)
-bool bn_bwd_fin_apply_ok(const BnBwdArgs& a);
+// finalize of a short partial list (P <= kBnFinPmax) + apply in one launch (kBnSlab-channel slabs: C = ldy, a multiple)
 hipError_t launch_bn_bwd_fin_apply(int dtype, const BnBwdArgs& a, hipStream_t s);
 
 // ---- loss / heads

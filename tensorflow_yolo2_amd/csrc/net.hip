@@ -52,13 +52,6 @@ static inline size_t part_rows_bound(int N, int H, int W, int cout) {
     const size_t bp = 64;     // the smallest pixel tile of any kernel form (conv_rf.hip: 64 bordered positions)
     return ((size_t)N * (H + 1) * (W + 1) + bp - 1) / bp;
 }
-// ConvPlan::filter_layout of a launch of this shape: what its filter pack must hold
-static int conv_layout(int dtype, int taps, int H, int W, int M, int C, int Cout, int ldy, int dgrad) {
-    ConvArgs a{};
-    a.H = H; a.W = W; a.M = M; a.C = C; a.Cout = Cout; a.ldy = ldy; a.taps = taps; a.is_dgrad = dgrad;
-    return plan_conv(dtype, a).filter_layout;
-}
-
 
 // zero-bordered NHWC tensor with guard bands (see wgrad.hip): geometry helper
 struct PadGeom {
@@ -86,6 +79,54 @@ struct Layer {
     size_t xin, y, stat, wf, wd, dyp, ysel, idx0;
 };
 
+// ---- what every layer's passes do (plan_net): decisions only, no pointers
+enum FwdFold { FOLD_NONE, FOLD_AFFINE, FOLD_AFFINE_POOL };   // inference BN + activation (+ 2x2 max pool) in the conv epilogue
+enum FwdStats {
+    FS_MOVING,      // inference: the moving statistics (prepared for every such layer before the loop)
+    FS_CONV,        // records of the conv pass (conv epilogue; first layer: conv1_fwd_kernel or its statistics pass)
+    FS_SUB,         // bn_stats_sub over the kept positions (pool == 2)
+    FS_GRAM,        // first layer: from the Gram matrix of the input patches (launch_conv1_gram_stats finalizes)
+};
+enum FwdApply {
+    FA_NONE,        // folded
+    FA_ACT,         // bn_finalize (batch statistics) + bn_act
+    FA_FIN_ACT,     // bn_fin_act: the merge of a short partial list rides in the apply pass
+    FA_CONV1_POOL,  // first layer: conv1_pool_kernel (conv again + BN + leaky + pool)
+};
+enum FwdOut { OUT_NEXT, OUT_EXT, OUT_F32, OUT_H32 };   // next layer's bordered input, ext_out (+ join), fp32 out, o_h32
+enum BwdReduce {
+    BR_KERNEL,      // bn_bwd_reduce
+    BR_DGRAD,       // in the epilogue of the dgrad of the layer above
+    BR_CONV1_LIN,   // first layer: in conv1_wgrad_lin_kernel
+    BR_CONV1_RECOMPUTE,     // first layer: conv1_bnbwd_reduce_kernel (conv output recomputed)
+};
+enum BwdApply { BA_FIN_APPLY, BA_FIN_THEN_APPLY, BA_FIN };   // BA_FIN: the first layer's weight gradient applies
+enum WgradRoute { WG_GENERIC, WG_CONV1, WG_CONV1_FUSED, WG_CONV1_LIN };
+struct LayerPlan {
+    int training = 0;           // BN mode: batch (1) or moving (0) statistics
+    FwdFold fold = FOLD_NONE;
+    FwdStats stats = FS_MOVING;
+    int P = 0;                  // forward statistics records
+    FwdApply apply = FA_ACT;
+    FwdOut out = OUT_NEXT;
+    // backward, layers of the pass's range
+    BwdReduce bred = BR_KERNEL;
+    int bP = 0;                 // BN-backward partial records
+    BwdApply bapply = BA_FIN_THEN_APPLY;
+    WgradRoute wgrad = WG_GENERIC;
+    bool wgrad_side = false;    // on the side stream beside the dgrads
+    bool dgrad = false;
+    int dgrad_dtype = 0;        // launch dtype; 5: f16x2f, dA stored in f16 for the batch-norm kernels of the layer below
+    bool dgrad_fuse = false;    // the epilogue reduces the BN-backward sums of the layer below (BR_DGRAD there)
+    bool dgrad_guard = false;   // ConvArgs::nonfinite: the fused optimizer's early check of the first layer reads its dA
+    ConvPlan dgrad_plan{};      // as launched
+};
+struct NetPlan {
+    int train_core = 0, train_head = 0;
+    std::vector<LayerPlan> L;
+    Conv1Plan c1{};             // L[0].first3
+};
+
 struct y2_ctx {
     int N, H, W, dtype, tail, tail_k, core_layers;
     // Y2_F16X2F (round 6): dtype == 3 (split tensors, split-operand forward) and the backward contractions -- dgrad and
@@ -110,8 +151,7 @@ struct y2_ctx {
     bool weights_dirty = true;
     bool fwd_saved = false;
     bool moving_pending = false;   // last forward ran with update_moving = 0
-    std::vector<int> fwd_training;  // per layer BN mode of the last forward
-    std::vector<int> fwd_folded;    // per layer: the last forward folded BN + leaky into the conv epilogue (no y)
+    NetPlan fwd;                    // the last forward's plan
     // shared scratch offsets
     size_t o_part_scratch = 0;
     size_t o_part_cnt, o_part_mean, o_part_m2, o_psum, o_dA0, o_dA1, o_h32, o_dh32, o_xin_last_end;
@@ -147,7 +187,6 @@ struct y2_ctx {
     // weight gradients run on a side stream beside the dgrad of the same layer (both only read dY)
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int overlap_wgrad = 1;
     // y2_backward_marks: (main, side) event pairs recorded when every layer >= mark_layers[k] is complete
     std::vector<hipEvent_t> mark_main, mark_side;
     int n_marks = 0;
@@ -195,6 +234,160 @@ struct ProfScope {
     ~ProfScope() { if (idx >= 0) (void)hipEventRecord(c->prof_recs[idx].b, s); }
 };
 #define PROF(cat) ProfScope _prof_scope(c, s, cat)
+
+// The launch arguments of layer l's forward conv (stats: it writes BN partial records) and of its dgrad (fuse: the
+// BN-backward reduce of layer l - 1 rides in its epilogue, which needs that layer's conv output, scale and shift beside
+// the dA tile it holds anyway; guard: ConvArgs::nonfinite).  The bind-time filter pack, plan_net and the executors plan
+// and launch the same arguments.
+static ConvArgs fwd_args(const y2_ctx* c, int l, bool stats, FwdFold fold) {
+    const Layer& y = c->L[l];
+    const size_t sz = c->sz();
+    ConvArgs a{};
+    a.x = (l == 0 && c->ext_xin) ? (char*)c->ext_xin : c->ws + y.xin + c->in_geom(l).base_off(sz);
+    a.w = c->ws + y.wf; a.y = c->ws + y.y; a.bias = c->params + y.pb;
+    if (stats) {
+        a.part_cnt = (float*)(c->ws + c->o_part_cnt); a.part_mean = (float*)(c->ws + c->o_part_mean);
+        a.part_m2 = (float*)(c->ws + c->o_part_m2);
+    }
+    a.N = c->N; a.H = y.H; a.W = y.W; a.C = y.cin_s; a.M = y.M; a.Cout = y.cout; a.ldy = y.ldy;
+    a.taps = y.k * y.k;
+    if (c->ks_floats) { a.ks_scratch = (float*)(c->ws + c->o_ks); a.ks_floats = c->ks_floats; }
+    if (fold != FOLD_NONE) {      // the activation goes straight into the consumer's bordered input (no y, no bn_act pass)
+        const float* stat = (const float*)(c->ws + y.stat);
+        conv_set_affine(a, stat, stat + y.ldy, c->ws + c->L[l + 1].xin + c->in_geom(l + 1).base_off(sz));
+        a.aff_slope = y.slope;
+        a.aff_pool = fold == FOLD_AFFINE_POOL ? 1 : 0;
+    }
+    return a;
+}
+static ConvArgs dgrad_args(const y2_ctx* c, int l, bool fuse, bool guard) {
+    const Layer& y = c->L[l];
+    ConvArgs a{};
+    a.x = c->ws + y.dyp + c->dy_geom(l).base_off(c->sz()); a.w = c->ws + y.wd;
+    a.N = c->N; a.H = y.H; a.W = y.W; a.C = y.ldy; a.M = y.M; a.Cout = y.cin; a.ldy = y.cin;
+    a.taps = y.k * y.k;
+    a.is_dgrad = 1;
+    if (c->ks_floats) { a.ks_scratch = (float*)(c->ws + c->o_ks); a.ks_floats = c->ks_floats; }
+    if (guard) a.nonfinite = (unsigned*)(c->ws + c->o_nfflag);
+    if (fuse) {
+        const Layer& z = c->L[l - 1];
+        float* zs = (float*)(c->ws + z.stat);
+        a.bw_y = c->ws + (z.pool ? z.ysel : z.y);   // same pixel grid as this launch's output either way
+        a.bw_scale = zs; a.bw_shift = zs + z.ldy; a.bw_psum = (float*)(c->ws + c->o_psum);
+        a.bw_slope = z.slope;
+    }
+    return a;
+}
+// f16x2f: dA is consumed once, by the batch-norm backward pass of the layer below, which rounds its own result to f16 for
+// the next contraction: store it in f16 (launch dtype 5) wherever that consumer is one of the fp32-wide batch-norm kernels
+// (not the 3-channel layer's own kernels, not an external input gradient)
+static int dgrad_dtype(const y2_ctx* c, int l) {
+    return c->bwd_dtype == 4 && l > 0 && !c->L[l - 1].first3 ? 5 : c->bwd_dtype;
+}
+
+// Every decision of a forward pass (layer_lo == layer_hi) and of a backward pass over [layer_lo, layer_hi) after a forward
+// with these BN modes: the executors below only read it.  No HIP calls.
+static NetPlan plan_net(const y2_ctx* c, int train_core, int train_head, int layer_lo, int layer_hi) {
+    static const bool no_infer_fold = getenv("Y2_NO_INFER_FOLD") != nullptr;      // A/B switches
+    static const bool no_pool_fold = getenv("Y2_NO_POOL_FOLD") != nullptr;
+    static const bool no_fin_fuse = getenv("Y2_NO_BN_FIN_FUSE") != nullptr;
+    static const bool no_bnbwd_fuse = getenv("Y2_NO_BNBWD_FUSE") != nullptr;
+    static const bool no_overlap = getenv("Y2_NO_WGRAD_OVERLAP") != nullptr;
+    const int nl = (int)c->L.size();
+    NetPlan n;
+    n.train_core = train_core; n.train_head = train_head;
+    n.L.resize(nl);
+    for (int l = 0; l < nl; ++l) {
+        const Layer& y = c->L[l];
+        LayerPlan& p = n.L[l];
+        p.training = l < c->core_layers ? train_core : train_head;
+        p.out = l + 1 < nl ? OUT_NEXT : c->ext_out ? OUT_EXT : c->tail == Y2_TAIL_AVGPOOL ? OUT_H32 : OUT_F32;
+        if (y.first3) {
+            n.c1 = c->conv1_plan(c->bound_training, p.training);
+            p.stats = !p.training ? FS_MOVING : n.c1.stats == C1S_GRAM ? FS_GRAM : FS_CONV;
+            p.P = n.c1.fwd_blocks;
+            p.apply = n.c1.fwd == C1F_POOLED ? FA_CONV1_POOL : FA_ACT;
+        } else {
+            p.stats = !p.training ? FS_MOVING : y.pool == 2 ? FS_SUB : FS_CONV;
+            const ConvPlan cp = plan_conv(c->dtype, fwd_args(c, l, p.stats == FS_CONV, FOLD_NONE));
+            p.P = p.stats == FS_SUB ? bn_stats_sub_records(c->N, y.H, y.W) : cp.records;
+            // Inference batch norm folded into the epilogue (ConvArgs::aff_*), no pool, a consumer layer: every kernel on
+            // the shared epilogue (conv_epilogue.h) and conv_rf.hip's 128-cout forward form (wave-private row segments);
+            // the 208-wide 32 <-> 64 rf forms keep the two-pass form, and so does f16x2 (the consumer's tensor has two
+            // planes).  Training bindings keep y: a later y2_backward of a frozen-core graph reads it.  Pooled layers
+            // (ConvArgs::aff_pool): the conv_haloq kernels on the bordered image (their tiles take any pixel order inside
+            // a contiguous run of cells); whole windows only; not the K-split small launches.
+            const bool fold = !p.training && l + 1 < nl && !c->bound_training && y.ldy == c->L[l + 1].cin_s &&
+                              !no_infer_fold && !dtype_split(c->dtype) && cp.kind != CK_RF &&
+                              !(cp.kind == CK_RFN && y.ldy % 8 != 0) && y.M < 0x7FFFFFFF;
+            if (fold && y.pool == 0) p.fold = FOLD_AFFINE;
+            if (fold && y.pool == 1 && !no_pool_fold && y.k == 3 && !(y.H & 1) && !(y.W & 1) && y.M >= 384 * 8 &&
+                cp.kind == CK_HALOQ)
+                p.fold = FOLD_AFFINE_POOL;
+            // the folded launch must read the filters as packed
+            if (p.fold != FOLD_NONE && plan_conv(c->dtype, fwd_args(c, l, false, p.fold)).filter_layout != y.wf_frag)
+                p.fold = FOLD_NONE;
+            p.apply = p.fold != FOLD_NONE ? FA_NONE : FA_ACT;
+        }
+        if (p.apply == FA_ACT && (p.stats == FS_CONV || p.stats == FS_SUB) && !no_fin_fuse &&
+            (p.out == OUT_NEXT || p.out == OUT_EXT) && p.P >= 1 && p.P <= kBnFinPmax && y.ldy % kBnSlab == 0 &&
+            y.cout == y.ldy)
+            p.apply = FA_FIN_ACT;
+    }
+    bool forked = false;
+    for (int l = layer_hi - 1; l >= layer_lo; --l) {
+        const Layer& y = c->L[l];
+        LayerPlan& p = n.L[l];
+        const Conv1Bwd b1 = y.first3 ? n.c1.bwd : C1B_GENERIC;
+        if (b1 == C1B_LINEAR) {
+            p.bred = BR_CONV1_LIN;
+            p.bP = n.c1.lin_records;
+        } else if (b1 == C1B_RECOMPUTE) {
+            p.bred = BR_CONV1_RECOMPUTE;
+            p.bP = n.c1.pool_blocks;
+        } else if (l + 1 < layer_hi && n.L[l + 1].dgrad_fuse) {
+            p.bred = BR_DGRAD;
+            p.bP = n.L[l + 1].dgrad_plan.records;
+        } else {
+            BnBwdArgs b{};
+            b.N = c->N; b.H = y.H; b.W = y.W; b.C = y.cout; b.ldy = y.ldy; b.ldd = y.ldy; b.pool = y.pool;
+            p.bred = BR_KERNEL;
+            p.bP = bn_bwd_reduce_records(y.first3 ? dtype_plain(c->dtype) : c->dtype, b);
+        }
+        // short partial lists: the finalize rides in the apply pass (bn.hip bn_bwd_fin_apply_kernel)
+        if (b1 == C1B_FUSED || b1 == C1B_LINEAR) p.bapply = BA_FIN;
+        else if (!no_fin_fuse && p.bP >= 1 && p.bP <= kBnFinPmax && y.ldy % kBnSlab == 0 && y.cout == y.ldy)
+            p.bapply = BA_FIN_APPLY;
+        else p.bapply = BA_FIN_THEN_APPLY;
+        if (y.first3) {
+            p.wgrad = b1 == C1B_LINEAR ? WG_CONV1_LIN : b1 == C1B_FUSED ? WG_CONV1_FUSED : WG_CONV1;
+            continue;
+        }
+        // the filter gradient only reads x and dY: it fills the bubbles of the dgrad beside it (not with per-launch
+        // bracketing).  The lowest layer forks too although nothing runs beside it: every weight gradient shares ONE
+        // split-K slab, so they must all queue on one stream
+        p.wgrad_side = !no_overlap && c->prof != 1;
+        forked = forked || p.wgrad_side;
+        p.dgrad = l > 0 || c->dinput || c->ext_dx;
+        if (!p.dgrad) continue;
+        p.dgrad_dtype = dgrad_dtype(c, l);
+        // this launch stores dA_0: the fused optimizer's early guard reads it as its view of layer 0
+        p.dgrad_guard = l == 1 && c->L[0].first3 && c->fopt.on && c->fopt.ctrl && n.c1.bwd == C1B_LINEAR && forked;
+        p.dgrad_plan = plan_conv(p.dgrad_dtype, dgrad_args(c, l, false, p.dgrad_guard));
+        // the reduce of the layer below rides in this dgrad's epilogue where the fused launch reads the filters as packed;
+        // the first layer keeps its own reduce, and a launch of a few hundred pixels splits its K range over workgroups
+        // instead (conv_haloq.hip haloq_ks; 7x7 1024 -> 512 at batch 24: 81 us fused and un-split)
+        const bool ks = p.dgrad_plan.kind == CK_HALOQ_KS || p.dgrad_plan.kind == CK_IGEMM_KS;
+        if (!no_bnbwd_fuse && !ks && l - 1 >= layer_lo && !c->L[l - 1].first3 && c->L[l - 1].ldy == y.cin) {
+            const ConvPlan f = plan_conv(p.dgrad_dtype, dgrad_args(c, l, true, p.dgrad_guard));
+            if (f.filter_layout == y.wd_frag) {
+                p.dgrad_fuse = true;
+                p.dgrad_plan = f;
+            }
+        }
+    }
+    return n;
+}
 
 static void plan(y2_ctx* c) {
     const size_t sz = c->sz();
@@ -399,8 +592,6 @@ int y2_ctx_create(y2_ctx** out, const int* spec, int num_layers, int core_layers
         return fail(Y2_ERR_ARG, "the last layer must not pool");
     }
     plan(c);
-    c->fwd_training.assign(c->L.size(), 0);
-    c->fwd_folded.assign(c->L.size(), 0);
     *out = c;
     return Y2_OK;
 }
@@ -530,8 +721,8 @@ int y2_bind(y2_ctx* c, float* params, float* grads, float* state, void* workspac
         p.taps = y.k * y.k; p.Cin = y.cin; p.Cout = y.cout; p.Cout_pad = y.cout_pad; p.Kc = y.cin_s;
         p.Cin_pad = y.cin_pad; p.Cdy = y.ldy;
         const int split = dtype_split(c->dtype) ? 1 : 0;
-        p.wf_frag = y.wf_frag = conv_layout(c->dtype, p.taps, y.H, y.W, y.M, y.cin_s, y.cout, y.ldy, 0);       // forward launch
-        p.wd_frag = y.wd_frag = conv_layout(c->bwd_dtype, p.taps, y.H, y.W, y.M, y.ldy, y.cin, y.cin, 1);     // dgrad: Cout = cin
+        p.wf_frag = y.wf_frag = plan_conv(c->dtype, fwd_args(c, (int)l, false, FOLD_NONE)).filter_layout;
+        p.wd_frag = y.wd_frag = plan_conv(dgrad_dtype(c, (int)l), dgrad_args(c, (int)l, false, false)).filter_layout;
         pack_layer_plan(p, nb, split ? 2 : (int)c->sz());     // (f16x2: the pack kernels run their 16-bit form on two planes)
         nb += p.wf_blocks + p.wd_blocks;
         p.opt_first = ntile;
@@ -732,6 +923,8 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
     float* part_mean = (float*)(c->ws + c->o_part_mean);
     float* part_m2 = (float*)(c->ws + c->o_part_m2);
     const int nl = (int)c->L.size();
+    c->fwd = plan_net(c, train_core, train_head, 0, 0);
+    const Conv1Plan& p1 = c->fwd.c1;
     if (!train_core || (!train_head && c->core_layers < nl)) {     // some layer normalises with its moving statistics
         int max_c = 0;
         for (const Layer& y : c->L) max_c = y.cout > max_c ? y.cout : max_c;
@@ -741,15 +934,10 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
     for (int l = 0; l < nl; ++l) {
         c->prof_layer = l;
         const Layer& y = c->L[l];
-        const int training = (l < c->core_layers) ? train_core : train_head;
-        c->fwd_training[l] = training;
+        const LayerPlan& p = c->fwd.L[l];
         char* xin = (l == 0 && c->ext_xin) ? (char*)c->ext_xin : c->ws + y.xin + c->in_geom(l).base_off(sz);
         float* stat = (float*)(c->ws + y.stat);
         float *scale = stat, *shift = stat + y.ldy, *mean = stat + 2 * y.ldy, *invstd = stat + 3 * y.ldy;
-        int P = 0;
-        bool folded = false;
-        const Conv1Plan p1 = y.first3 ? c->conv1_plan(c->bound_training, training) : Conv1Plan{};
-        const bool pool1 = y.first3 && p1.fwd == C1F_POOLED;
         if (y.first3) {
             {
                 PROF(CAT_MISC);
@@ -760,43 +948,21 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             a.x4 = xin; a.w = c->ws + y.wf; a.y = c->ws + y.y; a.bias = c->params + y.pb;
             a.part_cnt = part_cnt; a.part_mean = part_mean; a.part_m2 = part_m2;
             a.N = c->N; a.H = y.H; a.W = y.W; a.M = y.M;
-            P = p1.fwd_blocks;
-            if (!pool1 || p1.stats == C1S_CONV) { PROF(CAT_CONV1_FWD); HIPCHK(launch_conv1_fwd(p1, a, s)); }
+            if (p.apply != FA_CONV1_POOL || p1.stats == C1S_CONV) { PROF(CAT_CONV1_FWD); HIPCHK(launch_conv1_fwd(p1, a, s)); }
         } else {
             if (l == 0 && !c->ext_xin) HIPCHK(launch_pack_act(c->dtype, images, xin, c->N, y.H, y.W, y.cin, y.cin_s, s));
-            ConvArgs a{};
-            a.x = xin; a.w = c->ws + y.wf; a.y = c->ws + y.y; a.bias = c->params + y.pb;
-            // (subsampling layers, pool == 2: their batch norm runs over the kept positions -- launch_bn_stats_sub below)
-            if (training && y.pool != 2) { a.part_cnt = part_cnt; a.part_mean = part_mean; a.part_m2 = part_m2; }
-            a.N = c->N; a.H = y.H; a.W = y.W; a.C = y.cin_s; a.M = y.M; a.Cout = y.cout; a.ldy = y.ldy;
-            a.taps = y.k * y.k;
-            if (c->ks_floats) { a.ks_scratch = (float*)(c->ws + c->o_ks); a.ks_floats = c->ks_floats; }
-            int bp = 0, rec = 0;
-            // inference statistics, no pool, a consumer layer: scale / shift / leaky ride in the conv epilogue and the
-            // activation goes straight into the consumer's bordered input (no y, no bn_act pass).  Training
-            // bindings keep y: a later y2_backward of a frozen-core graph reads it.
-            // (round 5: pooled layers on the conv_haloq kernels too -- window-major tiles, ConvArgs::aff_pool)
-            if (!training && l + 1 < nl && !c->bound_training && y.ldy == c->L[l + 1].cin_s &&
-                (y.pool == 1 ? conv_affine_pool_ok(c->dtype, a) : (y.pool == 0 && conv_affine_ok(c->dtype, a)))) {
-                conv_set_affine(a, scale, shift, c->ws + c->L[l + 1].xin + c->in_geom(l + 1).base_off(sz));
-                a.aff_slope = y.slope;
-                a.aff_pool = y.pool == 1 ? 1 : 0;
-                folded = true;
-            }
-            { PROF(CAT_CONV_FWD); HIPCHK(launch_conv(c->dtype, a, s, y.wf_frag, &bp, &rec)); }
-            P = rec;
-            if (training && y.pool == 2) {
+            { PROF(CAT_CONV_FWD); HIPCHK(launch_conv(c->dtype, fwd_args(c, l, p.stats == FS_CONV, p.fold), s, y.wf_frag)); }
+            if (p.stats == FS_SUB) {
                 PROF(CAT_BN_FWD);
-                HIPCHK(launch_bn_stats_sub(c->dtype, c->ws + y.y, c->N, y.H, y.W, y.ldy, part_cnt, part_mean, part_m2, &P, s));
+                HIPCHK(launch_bn_stats_sub(c->dtype, c->ws + y.y, c->N, y.H, y.W, y.ldy, part_cnt, part_mean, part_m2, s));
             }
         }
-        c->fwd_folded[l] = folded ? 1 : 0;
-        if (folded) continue;
+        if (p.apply == FA_NONE) continue;
         PROF(CAT_BN_FWD);
         BnFinalizeArgs f{};
-        if (training) {
+        if (p.training) {
             f.part_cnt = part_cnt; f.part_mean = part_mean; f.part_m2 = part_m2;
-            f.P = P; f.C = y.cout; f.ldp = y.first3 ? 32 : y.ldy;
+            f.P = p.P; f.C = y.cout; f.ldp = y.first3 ? 32 : y.ldy;
             f.gamma = c->params + y.pg; f.beta = c->params + y.pbeta;
             f.moving_mean = c->state + y.smm; f.moving_var = c->state + y.smv;
             f.scale = scale; f.shift = shift; f.mean = mean; f.invstd = invstd;
@@ -804,15 +970,7 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             f.scratch = (float*)(c->ws + c->o_part_scratch);
             f.eps = c->bn_eps; f.momentum = c->bn_momentum; f.update_moving = update_moving ? 1 : 0; f.bessel = c->bessel;
         }
-        // short partial lists: the merge rides in the apply pass (bn.hip bn_fin_act_kernel)
-        static const bool no_fin_fuse = getenv("Y2_NO_BN_FIN_FUSE") != nullptr;
-        bool fin_fused = false;
-        if (training && !pool1 && !no_fin_fuse && (l + 1 < nl || c->ext_out)) {
-            BnActArgs t{};
-            t.C = y.cout; t.ldy = y.ldy; t.out_f32 = 0;
-            fin_fused = bn_fin_act_ok(t, f);
-        }
-        if (y.first3 && p1.stats == C1S_GRAM) {
+        if (p.stats == FS_GRAM) {
             Conv1GramStatsArgs q{};
             q.x4 = xin; q.N = c->N; q.H = y.H; q.Wd = y.W;
             q.W = c->params + y.pW; q.bias = c->params + y.pb; q.gamma = f.gamma; q.beta = f.beta;
@@ -821,8 +979,10 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             q.eps = f.eps; q.momentum = f.momentum; q.update_moving = f.update_moving; q.bessel = f.bessel;
             q.gram = (float*)(c->ws + c->o_gram); q.mid = q.gram + 48 * 48;
             HIPCHK(launch_conv1_gram_stats(p1, q, s));
-        } else if (training && !fin_fused) HIPCHK(launch_bn_finalize(f, s));     // (inference: prepared for every layer above)
-        if (pool1) {
+        } else if (p.stats != FS_MOVING && p.apply != FA_FIN_ACT) {
+            HIPCHK(launch_bn_finalize(f, s));     // (inference: prepared for every layer above)
+        }
+        if (p.apply == FA_CONV1_POOL) {
             Conv1PoolArgs q{};
             q.x4 = xin; q.w = c->ws + y.wf; q.y = c->ws + y.y; q.bias = c->params + y.pb;
             q.scale = scale; q.shift = shift;
@@ -838,23 +998,20 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
         b.y = c->ws + y.y; b.scale = scale; b.shift = shift;
         b.N = c->N; b.H = y.H; b.W = y.W; b.C = y.cout; b.ldy = y.ldy; b.pool = y.pool;
         b.slope = y.slope;
-        if (l + 1 < nl) {
-            b.out = c->ws + c->L[l + 1].xin + c->in_geom(l + 1).base_off(sz);
-            b.out_f32 = 0;
-        } else if (c->ext_out) {      // linked: the consumer stack's bordered input, in the arithmetic type
-            b.out = c->ext_out;
-            b.out_f32 = 0;
-            b.join_t = c->ext_join_self ? (const void*)(c->ext_xin ? (char*)c->ext_xin : c->ws + c->L[0].xin + c->in_geom(0).base_off(sz))
-                                        : c->ext_join;
-        } else {
-            b.out = (c->tail == Y2_TAIL_AVGPOOL) ? (void*)(c->ws + c->o_h32) : (void*)out;
-            b.out_f32 = 1;
-            b.join = join;
-            if (!join) b.join_t = c->ext_join_self ? (const void*)(c->ext_xin ? (char*)c->ext_xin : c->ws + c->L[0].xin + c->in_geom(0).base_off(sz))
-                                                   : c->ext_join;
+        const void* join_t = c->ext_join_self ? (const void*)(c->ext_xin ? (char*)c->ext_xin : c->ws + c->L[0].xin + c->in_geom(0).base_off(sz))
+                                              : c->ext_join;
+        switch (p.out) {
+            case OUT_NEXT: b.out = c->ws + c->L[l + 1].xin + c->in_geom(l + 1).base_off(sz); break;
+            case OUT_EXT: b.out = c->ext_out; b.join_t = join_t; break;     // linked: the consumer stack's bordered input
+            case OUT_F32: case OUT_H32:
+                b.out = p.out == OUT_H32 ? (void*)(c->ws + c->o_h32) : (void*)out;
+                b.out_f32 = 1;
+                b.join = join;
+                if (!join) b.join_t = join_t;
+                break;
         }
         if (y.pool && c->bound_training && y.ysel) b.ysel = c->ws + y.ysel;
-        if (fin_fused) HIPCHK(launch_bn_fin_act(c->dtype, b, f, s));
+        if (p.apply == FA_FIN_ACT) HIPCHK(launch_bn_fin_act(c->dtype, b, f, s));
         else HIPCHK(launch_bn_act(c->dtype, b, s));
     }
     if (c->tail == Y2_TAIL_AVGPOOL) {
@@ -876,7 +1033,7 @@ int y2_update_moving_stats(y2_ctx* c, void* stream) {
     if (!c->moving_pending) return Y2_OK;
     hipStream_t s = (hipStream_t)stream;
     for (size_t l = 0; l < c->L.size(); ++l) {
-        if (!c->fwd_training[l]) continue;
+        if (!c->fwd.L[l].training) continue;
         const Layer& y = c->L[l];
         const float* stat = (const float*)(c->ws + y.stat);
         HIPCHK(launch_bn_update_moving(stat + 2 * y.ldy, stat + 6 * y.ldy, c->state + y.smm, c->state + y.smv, y.cout,
@@ -925,38 +1082,17 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
     float* psum = (float*)(c->ws + c->o_psum);
     bool forked = false;
     bool opt_early = false;   // fused optimizer: the layers above the first one were updated on the side stream
-    int fused_P = 0;          // > 0: the dgrad of the layer above already reduced this layer's BN-backward sums
-    const Conv1Plan p1 = c->L[0].first3 ? c->conv1_plan(c->bound_training, c->fwd_training[0]) : Conv1Plan{};
-    static const bool no_fuse = getenv("Y2_NO_BNBWD_FUSE") != nullptr;
-    if (c->overlap_wgrad && !c->side) {
-        static const bool off = getenv("Y2_NO_WGRAD_OVERLAP") != nullptr;
-        if (off) c->overlap_wgrad = 0;
-        else {
-            // Y2_SIDE_PRIORITY=low|high: the weight-gradient stream at the device's least / greatest queue priority (A/B:
-            // the dgrad -> BN-backward chain on the caller's stream is the critical path of the backward pass)
-            static const char* prio = getenv("Y2_SIDE_PRIORITY");
-            int least = 0, greatest = 0;
-            // Y2_SIDE_CUS=<n>: the weight-gradient stream may use only the first n compute units of the mask (A/B: the
-            // small kernels of the dgrad -> BN-backward chain wait for wave slots behind its long-running workgroups).
-            // Such a stream synchronises with the NULL stream: the caller's stream must be another one.
-            static const int side_cus = getenv("Y2_SIDE_CUS") ? atoi(getenv("Y2_SIDE_CUS")) : 0;
-            if (side_cus > 0) {
-                uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int i = 0; i < side_cus && i < 256; ++i) mask[i >> 5] |= 1u << (i & 31);
-                HIPCHK(hipExtStreamCreateWithCUMask(&c->side, 8, mask));
-            } else if (prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-                HIPCHK(hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, prio[0] == 'l' ? least : greatest));
-            } else {
-                (void)hipGetLastError();
-                HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-            }
-            HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-        }
+    const NetPlan n = plan_net(c, c->fwd.train_core, c->fwd.train_head, layer_lo, layer_hi);
+    const Conv1Plan& p1 = n.c1;
+    if (!c->side && std::any_of(n.L.begin(), n.L.end(), [](const LayerPlan& p) { return p.wgrad_side; })) {
+        HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
     for (int l = layer_hi - 1; l >= layer_lo; --l) {
         c->prof_layer = l;
         const Layer& y = c->L[l];
+        const LayerPlan& p = n.L[l];
         float* stat = (float*)(c->ws + y.stat);
         char* dyp = c->ws + y.dyp + c->dy_geom(l).base_off(sz);
         BnBwdArgs b{};
@@ -968,17 +1104,16 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
         b.dyp = dyp;
         b.N = c->N; b.H = y.H; b.W = y.W; b.C = y.cout; b.ldy = y.ldy;
         b.ldd = y.ldy;
-        b.pool = y.pool; b.training = c->fwd_training[l]; b.inv_grad_scale = inv_gs;
+        b.pool = y.pool; b.training = p.training; b.inv_grad_scale = inv_gs;
+        b.P = p.bP;
         b.slope = y.slope;
         // f16x2f: dgrad and weight gradient read the hi plane of this dY alone (the 3-channel layer's own dy goes to fp32 kernels)
         b.hi_only = (c->bwd_dtype == 4 && !y.first3) ? 1 : 0;
         b.dA_half = c->dA_half;
         if (c->zero_bias_grad) b.dbias = nullptr;      // stays zero from y2_bind: the bias is not a variable of this graph
-        const bool fused1 = y.first3 && p1.bwd == C1B_FUSED;
-        const bool lin1 = y.first3 && p1.bwd == C1B_LINEAR;
         // f16x2: the 3-channel layer's own dy (un-pooled / odd-sized fallbacks) is consumed by fp32 kernels
         const int bn_dtype = y.first3 ? dtype_plain(c->dtype) : c->dtype;
-        if (lin1 && c->fopt.on && forked && l == 0) {
+        if (p.bred == BR_CONV1_LIN && c->fopt.on && forked && l == 0) {
             // Every gradient above this layer is complete once the side stream has passed the dgrad that was just
             // queued: check and update those layers there, beside this layer's (compute-bound) gradient kernel.
             HIPCHK(hipEventRecord(c->ev_fork, s));
@@ -989,7 +1124,7 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
         }
         {
             PROF(CAT_BN_BWD);
-            if (lin1) {
+            if (p.bred == BR_CONV1_LIN) {
                 // linear form: the reduce pass rides in the weight-gradient kernel, which does not need its result
                 Conv1WgradLinArgs g{};
                 g.x4 = c->ws + y.xin + c->in_geom(l).base_off(sz); g.dA = b.dA;
@@ -1002,31 +1137,24 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
                 g.scale = b.scale; g.shift = b.shift; g.acc = (float*)(c->ws + c->o_lin); g.psum = psum;
                 g.N = c->N; g.H = y.H; g.W = y.W;
                 HIPCHK(launch_conv1_wgrad_lin(p1, g, s));
-                b.P = p1.lin_records;
-            } else if (y.first3 && p1.bwd == C1B_RECOMPUTE) {   // pooled first layer: recompute the conv output instead of reading it (80 -> 24 B/pixel)
+            } else if (p.bred == BR_CONV1_RECOMPUTE) {   // pooled first layer: recompute the conv output instead of reading it (80 -> 24 B/pixel)
                 Conv1BnBwdArgs q{};
                 q.x4 = c->ws + y.xin + c->in_geom(l).base_off(sz); q.w = c->ws + y.wf; q.bias = c->params + y.pb;
                 q.scale = b.scale; q.shift = b.shift; q.dA = b.dA; q.psum = psum;
                 q.N = c->N; q.H = y.H; q.W = y.W;
-                b.P = p1.pool_blocks;
                 HIPCHK(launch_conv1_bnbwd_reduce(p1, q, s));
-            } else if (fused_P > 0) {
-                b.P = fused_P;
-            } else {
+            } else if (p.bred == BR_KERNEL) {
                 HIPCHK(launch_bn_bwd_reduce(bn_dtype, b, s));
             }
-            fused_P = 0;
-            // short partial lists: the finalize rides in the apply pass (bn.hip bn_bwd_fin_apply_kernel)
-            static const bool no_fin_fuse = getenv("Y2_NO_BN_FIN_FUSE") != nullptr;
-            if (!fused1 && !lin1 && !no_fin_fuse && bn_bwd_fin_apply_ok(b)) {
+            if (p.bapply == BA_FIN_APPLY) {
                 HIPCHK(launch_bn_bwd_fin_apply(bn_dtype, b, s));
             } else {
                 HIPCHK(launch_bn_bwd_finalize(b, s));
-                if (!fused1 && !lin1) HIPCHK(launch_bn_bwd_apply(bn_dtype, b, s));
+                if (p.bapply == BA_FIN_THEN_APPLY) HIPCHK(launch_bn_bwd_apply(bn_dtype, b, s));
             }
         }
         char* xin = (l == 0 && c->ext_xin) ? (char*)c->ext_xin : c->ws + y.xin + c->in_geom(l).base_off(sz);
-        if (lin1) {
+        if (p.wgrad == WG_CONV1_LIN) {
             // no conv output of this layer exists: dW = scale X(dz) - ka X(1) - kb (G W + b X(1))  (conv1_wgrad.hip)
             Conv1DwFinalizeArgs f{};
             f.acc = (float*)(c->ws + c->o_lin); f.W = c->params + y.pW; f.bias = c->params + y.pb; f.scale = b.scale;
@@ -1034,7 +1162,7 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
             if (!p1.lin_gram) f.gram = (const float*)(c->ws + c->o_gram);
             PROF(CAT_CONV1_WGRAD);
             HIPCHK(launch_conv1_dw_finalize(f, s));
-        } else if (fused1) {
+        } else if (p.wgrad == WG_CONV1_FUSED) {
             // the first layer's dy has one consumer: apply pass and weight gradient in one kernel
             Conv1WgradFusedArgs g{};
             g.x4 = xin; g.y = b.y; g.dA = b.dA;
@@ -1043,7 +1171,7 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
             g.N = c->N; g.H = y.H; g.W = y.W; g.inv_grad_scale = inv_gs;
             HIPCHK(hipMemsetAsync(g.dW, 0, (size_t)27 * y.cout * sizeof(float), s));     // atomics
             { PROF(CAT_CONV1_WGRAD); HIPCHK(launch_conv1_wgrad_fused(p1, g, s)); }
-        } else if (y.first3) {
+        } else if (p.wgrad == WG_CONV1) {
             Conv1WgradArgs g{};
             g.x4 = xin; g.dy = dyp; g.dW = c->grads + y.pW;
             g.N = c->N; g.H = y.H; g.W = y.W; g.M = y.M; g.scale = inv_gs;
@@ -1056,52 +1184,19 @@ int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* 
             g.Cin = y.cin_s; g.Cdy = y.ldy; g.Cout = y.cout; g.taps = y.k * y.k; g.splitk = 0; g.scale = inv_gs;
             g.slab = (float*)(c->ws + c->o_slab); g.slab_floats = c->slab_floats;
             hipStream_t ws_ = s;
-            if (c->overlap_wgrad && c->prof != 1) {
-                // fork: the filter gradient only reads x and dY; it fills the bubbles of the dgrad beside it.  The
-                // lowest layer forks too although nothing runs beside it: every weight gradient shares ONE split-K slab,
-                // so they must all queue on one stream (on the caller's stream it raced the side stream's sum kernel)
+            if (p.wgrad_side) {     // fork (on the caller's stream it raced the side stream's sum kernel)
                 HIPCHK(hipEventRecord(c->ev_fork, s));
                 HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
                 ws_ = c->side;
                 forked = true;
             }
             { ProfScope _p(c, ws_, CAT_WGRAD); HIPCHK(launch_wgrad_auto(c->bwd_dtype, g, ws_)); }
-            if (l > 0 || c->dinput || c->ext_dx) {
-                ConvArgs a{};
-                a.x = dyp; a.w = c->ws + y.wd; a.y = (l == 0 && c->ext_dx) ? (char*)c->ext_dx : dA[c->dA_cur ^ 1];
-                a.N = c->N; a.H = y.H; a.W = y.W; a.C = y.ldy; a.M = y.M; a.Cout = y.cin; a.ldy = y.cin;
-                a.taps = y.k * y.k;
-                a.is_dgrad = 1;
-                if (c->ks_floats) { a.ks_scratch = (float*)(c->ws + c->o_ks); a.ks_floats = c->ks_floats; }
-                int bp = 0;
-                const Layer& z = c->L[l > 0 ? l - 1 : 0];
-                // the BN-backward reduce of the layer below rides in this dgrad's epilogue (it needs that layer's
-                // conv output, scale and shift beside the dA tile the epilogue holds anyway); the first layer
-                // keeps its own recomputing reduce
-                // (a launch of a few hundred pixels splits its K range over workgroups instead -- conv_haloq.hip haloq_ks --
-                //  and leaves the reduce to the standalone kernel: 7x7 1024 -> 512 at batch 24: 81 us fused and un-split)
-                // f16x2f: dA is consumed once, by the batch-norm backward pass of the layer below, which rounds its own result
-                // to f16 for the next contraction: store it in f16 (launch dtype 5) wherever that consumer is one of the
-                // fp32-wide batch-norm kernels (not the 3-channel layer's own kernels, not an external input gradient)
-                static const bool da32 = getenv("Y2_F16X2F_DA32") != nullptr;      // A/B switch: fp32 dA everywhere
-                const bool half_out = c->bwd_dtype == 4 && !da32 && l > 0 && !z.first3;
-                const int ldt = half_out ? 5 : c->bwd_dtype;
-                const ConvKind kind = plan_conv(ldt, a).kind;
-                const bool ks = kind == CK_HALOQ_KS || kind == CK_IGEMM_KS;
-                const bool fuse = !no_fuse && !ks && l > 0 && l - 1 >= layer_lo && !z.first3 && z.ldy == y.cin;
-                if (l == 1 && z.first3 && c->fopt.on && c->fopt.ctrl && p1.bwd == C1B_LINEAR && forked)
-                    a.nonfinite = (unsigned*)(c->ws + c->o_nfflag);   // this launch stores dA_0: the early guard's view of layer 0
-                if (fuse) {
-                    float* zs = (float*)(c->ws + z.stat);
-                    a.bw_y = c->ws + (z.pool ? z.ysel : z.y);   // same pixel grid as this launch's output either way
-                    a.bw_scale = zs; a.bw_shift = zs + z.ldy; a.bw_psum = psum;
-                    a.bw_slope = z.slope;
-                }
-                int rec = 0;
-                { PROF(CAT_DGRAD); HIPCHK(launch_conv(ldt, a, s, y.wd_frag, &bp, &rec)); }
-                if (fuse) fused_P = rec;
+            if (p.dgrad) {
+                ConvArgs a = dgrad_args(c, l, p.dgrad_fuse, p.dgrad_guard);
+                a.y = (l == 0 && c->ext_dx) ? (char*)c->ext_dx : dA[c->dA_cur ^ 1];
+                { PROF(CAT_DGRAD); HIPCHK(launch_conv(p.dgrad_dtype, a, s, y.wd_frag)); }
                 c->dA_cur ^= 1;
-                c->dA_half = half_out ? 1 : 0;
+                c->dA_half = p.dgrad_dtype == 5 ? 1 : 0;
                 if (l == 0 && c->dinput)   // the stack's input gradient leaves in fp32 NHWC, loss scale divided out
                     HIPCHK(launch_cast_to_f32(c->dtype, c->ext_dx ? (const void*)c->ext_dx : (const void*)dA[c->dA_cur], c->dinput,
                                               (size_t)y.M, y.cin, y.cin, s, inv_gs));
@@ -1207,10 +1302,11 @@ int y2_debug_read(y2_ctx* c, int l, int what, float* dst, void* stream) {
         HIPCHK(launch_unpack_act(y.first3 ? dtype_plain(c->dtype) : c->dtype, c->ws + y.xin + c->in_geom(l).base_off(sz), dst, c->N, y.H, y.W, C,
                                  y.cin_s, s));
     } else if (what == 1) {
-        if (c->fwd_folded[l])
+        if (!c->fwd_saved) return fail(Y2_ERR_STATE, "run y2_forward first");
+        if (c->fwd.L[l].fold != FOLD_NONE)
             return fail(Y2_ERR_STATE, "layer %d: inference batch norm was folded into the convolution, its conv output "
                                       "is not stored (Y2_NO_INFER_FOLD=1 keeps the two-pass form)", l);
-        const Conv1Plan p = y.first3 ? c->conv1_plan(c->bound_training, c->fwd_training[0]) : Conv1Plan{};
+        const Conv1Plan& p = c->fwd.c1;
         if (y.first3 && !p.y_stored && p.bwd != C1B_LINEAR)
             return fail(Y2_ERR_STATE, "inference binding: the pooled first layer does not store its conv output");
         if (y.first3 && !p.y_stored) {   // the linear form never stores this layer's conv output: recompute it (tests)
@@ -1227,7 +1323,7 @@ int y2_debug_read(y2_ctx* c, int l, int what, float* dst, void* stream) {
         HIPCHK(launch_cast_to_f32(c->dtype, c->ws + y.y, dst, (size_t)y.M, y.cout, y.ldy, s));
     } else if (what == 2) {
         if (!c->bound_training) return fail(Y2_ERR_STATE, "no gradients in inference binding");
-        if (y.first3 && !c->conv1_plan(c->bound_training, c->fwd_training[0]).dy_stored)
+        if (y.first3 && (!c->fwd_saved || !c->fwd.c1.dy_stored))
             return fail(Y2_ERR_STATE, "the first layer's dy is fused into its weight gradient and never stored");
         HIPCHK(launch_unpack_act(y.first3 ? dtype_plain(c->dtype) : c->dtype, c->ws + y.dyp + c->dy_geom(l).base_off(sz), dst, c->N, y.H, y.W, y.cout,
                                  y.ldy, s));
