@@ -50,6 +50,17 @@ typedef struct y2_ctx y2_ctx;
  * (tests/test_gpu_f16x2f.py), at roughly a third of the backward cost of Y2_F16X2.  y2_ctx_create and the op-level
  * y2_conv2d / y2_conv2d_backward accept it. */
 #define Y2_F16X2F 4
+/* MXFP8 inference (OCP MX spec): the forward convolutions of the layers whose batch norm uses the moving statistics and
+ * whose shape measured no slower than f16 run on gfx950's block-scaled matrix pipe
+ * (v_mfma_scale_f32_32x32x64_f8f6f4, twice the f16 rate per clock) with fp32 accumulation.  Elements are OCP e4m3fn (not the fnuz encoding); each block of 32 values shares one E8M0 scale byte
+ * (2^(byte - 127)).  A block is 32 consecutive channels of one pixel (activations, NHWC) or 32 consecutive input channels
+ * of one tap and one output channel (filters, HWIO).  Scale of a block: the smallest e with amax <= 448 * 2^e -- with
+ * frexp(amax) = m * 2^E, e = E - 9 if m <= 0.875 else E - 8 -- clamped to [-127, 127]; an all-zero block takes -127.
+ * Elements: round-to-nearest-even e4m3 of v / 2^e (clamped to +-448 as a guard; subnormals kept).  Every other layer --
+ * the 3-channel image layer, layers with batch statistics -- runs exactly as in Y2_F16, whose tensors (f16) the mode
+ * stores.  Inference only: y2_bind(training = 1), the y2_backward* family and y2_conv2d_backward refuse it.
+ * y2_conv2d accepts it (fp32 x / w in, both quantised in the workspace, fp32 y out; Cin % 32 == 0). */
+#define Y2_FP8 5
 
 #define Y2_TAIL_NONE 0    /* output = last layer activation [N,Ho,Wo,Cout]       */
 #define Y2_TAIL_AVGPOOL 1 /* + average_pooling2d(k,k) + reshape -> [N,Cout]      */
@@ -383,6 +394,10 @@ int y2_conv2d(const float* x, const float* w, const float* bias, float* y, int N
               int Cout, int k, int dtype, void* workspace, void* stream);
 int y2_conv2d_backward(const float* x, const float* w, const float* dy, float* dx, float* dw, int N, int H,
                        int W, int Cin, int Cout, int k, int dtype, void* workspace, void* stream);
+
+/* ---- MXFP8 quantiser (the Y2_FP8 number format above): fp32 x [rows][C], C % 32 == 0 -> e4m3fn elements q [rows][C]
+ *      + E8M0 scales [rows][C / 32] (one per 32 consecutive values of a row), device buffers */
+int y2_mx_quantize(const float* x, size_t rows, int C, uint8_t* q, uint8_t* scales, void* stream);
 
 /* ---- host utility: CRC-32C (Castagnoli) of a host buffer, continuing from `crc` (0 to start).  The checksum of
  *      TensorFlow's V2 checkpoint files (tensor bundle + table blocks), which the reference reads and writes through

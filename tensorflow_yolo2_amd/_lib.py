@@ -16,7 +16,7 @@ if os.environ.get("Y2_DEV_LIB") == "1":
 if os.environ.get("Y2_LIB_PATH"):
     LIB_PATH = os.environ["Y2_LIB_PATH"]
 
-Y2_F32, Y2_F16, Y2_BF16, Y2_F16X2, Y2_F16X2F = 0, 1, 2, 3, 4
+Y2_F32, Y2_F16, Y2_BF16, Y2_F16X2, Y2_F16X2F, Y2_FP8 = 0, 1, 2, 3, 4, 5
 # modes whose gradients ride on the f16 loss scale (dY is stored in f16 planes)
 LOSS_SCALED = (Y2_F16, Y2_F16X2, Y2_F16X2F)
 Y2_TAIL_NONE, Y2_TAIL_AVGPOOL = 0, 1
@@ -26,7 +26,9 @@ DTYPES = {"f32": Y2_F32, "fp32": Y2_F32, "float32": Y2_F32,
           # split-operand mode: (hi, lo) f16 pairs, three MFMAs per product, fp32-width storage (include/yolo2_hip.h)
           "f16x2": Y2_F16X2,
           # round 6: f16x2 forward, backward contractions on the hi planes only (one f16 MFMA per product)
-          "f16x2f": Y2_F16X2F}
+          "f16x2f": Y2_F16X2F,
+          # MXFP8 inference: e4m3fn elements + one E8M0 scale per 32 values on the block-scaled matrix pipe
+          "fp8": Y2_FP8, "mxfp8": Y2_FP8}
 
 _vp, _i, _f, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 _pi = C.POINTER(C.c_int)
@@ -122,6 +124,7 @@ SIGNATURES = {
     "y2_conv2d_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "y2_conv2d": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "y2_conv2d_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "y2_mx_quantize": (_i, [_vp, _sz, _i, _vp, _vp, _vp]),
     "y2_crc32c": (C.c_uint32, [_vp, _sz, C.c_uint32]),
 }
 

@@ -139,6 +139,29 @@ hipError_t launch_conv_igemm(int dtype, const ConvPlan& p, const ConvArgs& a, hi
 // rows of the LDS image of the halo kernels over all tiles of a launch (pool: window-major tiles, ConvArgs::aff_pool)
 int halo_image_rows(int H, int W, int BP, int RPI, int pool = 0);
 int conv_block_couts(int Cout);
+// MXFP8 inference forms (conv_mx8.hip, public Y2_FP8): e4m3fn elements + one E8M0 scale byte per 32 values
+int mx8_block_couts();                 // output channels per workgroup: the filter pack pads Cout to a multiple of it
+int mx8_channels(int C);               // channel stride of the e4m3 tensors and filters (a multiple of the K step)
+// the MXFP8 epilogue's destination: the consumer's bordered e4m3 input q [cell][ldq] and scales sc [cell][ldq / 32]
+// (cell-0 pointers)
+struct Mx8Out {
+    uint8_t* q = nullptr;
+    uint8_t* sc = nullptr;
+    int ldq = 0;
+};
+// a: the forward launch (x = e4m3 bordered tensor at cell 0, C = its channel stride, w = packed e4m3 filters); xsc = the
+// scale plane [bordered pixel][C / 32] at cell 0, wsc = [Cout_pad][taps][C / 32]; out_f32: y is fp32, else f16 (y or aff_out);
+// qo (non-null, with the folded batch norm set): the output is quantised into the consumer's e4m3 input instead
+hipError_t launch_conv_mx8(int out_f32, const ConvArgs& a, const uint8_t* xsc, const uint8_t* wsc, const Mx8Out* qo,
+                           hipStream_t s);
+hipError_t launch_mx_unpack(const uint8_t* q, const uint8_t* sc, float* out, int N, int H, int W, int C, int Cs,
+                            hipStream_t s);
+// [rows][ldin] fp32 or f16 -> e4m3 [rows][ldq] + scales [rows][ldq / 32] (blocks beyond ldin: zero)
+hipError_t launch_mx_quantize(int in_f16, const void* x, size_t rows, int ldin, int ldq, uint8_t* q, uint8_t* sc,
+                              hipStream_t s);
+// fp32 HWIO -> e4m3 [Cout_pad][taps][C8] + scales [Cout_pad][taps][C8 / 32]
+hipError_t launch_mx_pack_filter(const float* w, int taps, int Cin, int Cout, int Cout_pad, int C8, uint8_t* q,
+                                 uint8_t* sc, hipStream_t s);
 
 // ---- first layer (Cin = 3, stored as 4 channels)
 // plan_conv1 (conv1_wgrad.hip) decides every pass of the layer; the launchers run the planned form and return

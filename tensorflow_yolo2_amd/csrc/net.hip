@@ -77,6 +77,10 @@ struct Layer {
     size_t smm, smv;           // float offsets into state
     // byte offsets into the workspace
     size_t xin, y, stat, wf, wd, dyp, ysel, idx0;
+    // Y2_FP8 contexts, layers that may run on the MXFP8 kernel (mx8_shape): channel stride of the layer's e4m3 input
+    // (mx8_channels), that bordered input and its scale plane, its e4m3 filters + scale plane
+    int cin8 = 0;
+    size_t x8 = 0, x8s = 0, w8 = 0, w8s = 0;
 };
 
 // ---- what every layer's passes do (plan_net): decisions only, no pointers
@@ -104,6 +108,9 @@ enum BwdApply { BA_FIN_APPLY, BA_FIN_THEN_APPLY, BA_FIN };   // BA_FIN: the firs
 enum WgradRoute { WG_GENERIC, WG_CONV1, WG_CONV1_FUSED, WG_CONV1_LIN };
 struct LayerPlan {
     int training = 0;           // BN mode: batch (1) or moving (0) statistics
+    bool mx8 = false;           // Y2_FP8: the forward conv runs on the MXFP8 kernel (conv_mx8.hip)
+    bool in8 = false;           // ... and reads the e4m3 input its producer wrote (else: quantise pass over the f16 input)
+    bool out8 = false;          // ... and its epilogue writes the consumer's e4m3 input (no f16 output)
     FwdFold fold = FOLD_NONE;
     FwdStats stats = FS_MOVING;
     int P = 0;                  // forward statistics records
@@ -132,6 +139,11 @@ struct y2_ctx {
     // Y2_F16X2F (round 6): dtype == 3 (split tensors, split-operand forward) and the backward contractions -- dgrad and
     // weight gradients -- read the hi planes only (launch dtype 4, common.h hsplith_t): one f16 MFMA per product
     int bwd_dtype = 0;
+    // Y2_FP8: tensors and every pass are Y2_F16's (dtype 1) except the forward convolutions plan_net gives the MXFP8 kernel;
+    // those read an e4m3 input + scale plane of their own (written by an MXFP8 producer's epilogue, else quantised from the
+    // f16 input first).  Inference only.
+    int fp8 = 0;
+    int mx8_all = 0;            // Y2_MX8_ALL=1 at y2_ctx_create (A/B only): no shape excluded for speed (mx8_shape)
     std::vector<Layer> L;
     size_t nparams = 0, nstate = 0;
     int outN, outH, outW, outC;
@@ -285,6 +297,30 @@ static int dgrad_dtype(const y2_ctx* c, int l) {
     return c->bwd_dtype == 4 && l > 0 && !c->L[l - 1].first3 ? 5 : c->bwd_dtype;
 }
 
+// Y2_FP8: THE rule of which layers run on the MXFP8 kernel.  A layer does when its batch norm uses the moving statistics
+// (inference: then nothing reads its conv output but the folded epilogue / the apply pass) and its shape may (mx8_shape):
+// not the 3-channel image layer, not a subsampling layer (pool 2, the ResNet swap's stacks), and not a shape measured
+// slower than the f16 kernels (profiles/fp8_infer_ab.json).  Every other layer runs exactly as in
+// Y2_F16.  mx8_shape alone sizes the e4m3 buffers and decides which filters get an e4m3 pack.
+// The shapes measured no slower on the MXFP8 kernel than on the f16 plan, in the plan as shipped (same-box A/B of
+// scripts/bench_fp8_infer.py, profiles/fp8_infer_ab.json).  With every eligible shape admitted the
+// 3x3 64 -> 128 pooled, 3x3 128 -> 256 pooled, 1x1 256 -> 128 and 1x1 1024 -> 1000 layers measured faster, but three of
+// them only because their producer's MXFP8 epilogue had quantised their input: admitted alone, each pays the quantise pass
+// and measured 1.16-1.84x f16.  The pooled 3x3 128 -> 256 layer stays faster with that pass on the 28x28 map (0.81-0.95x)
+// but not reliably on the 52x52 one (0.94x, then 1.12x): only the former is admitted.
+static bool mx8_speed_ok(int k, int cin, int cout, int pool, int H, int W) {
+    return k == 3 && cin == 128 && cout == 256 && pool == 1 && H * W <= 28 * 28;
+}
+static bool mx8_shape(const y2_ctx* c, int l) {
+    const Layer& y = c->L[l];
+    if (!c->fp8 || y.first3 || y.pool == 2 || y.cin % 32 != 0) return false;
+    if (c->mx8_all) return true;
+    return mx8_speed_ok(y.k, y.cin, y.cout, y.pool, y.H, y.W);
+}
+static bool mx8_layer(const y2_ctx* c, int l, int training) {
+    return !training && !c->bound_training && mx8_shape(c, l);
+}
+
 // Every decision of a forward pass (layer_lo == layer_hi) and of a backward pass over [layer_lo, layer_hi) after a forward
 // with these BN modes: the executors below only read it.  No HIP calls.
 static NetPlan plan_net(const y2_ctx* c, int train_core, int train_head, int layer_lo, int layer_hi) {
@@ -293,6 +329,7 @@ static NetPlan plan_net(const y2_ctx* c, int train_core, int train_head, int lay
     static const bool no_fin_fuse = getenv("Y2_NO_BN_FIN_FUSE") != nullptr;
     static const bool no_bnbwd_fuse = getenv("Y2_NO_BNBWD_FUSE") != nullptr;
     static const bool no_overlap = getenv("Y2_NO_WGRAD_OVERLAP") != nullptr;
+    static const bool no_mx8 = getenv("Y2_NO_MX8") != nullptr;
     const int nl = (int)c->L.size();
     NetPlan n;
     n.train_core = train_core; n.train_head = train_head;
@@ -307,6 +344,17 @@ static NetPlan plan_net(const y2_ctx* c, int train_core, int train_head, int lay
             p.stats = !p.training ? FS_MOVING : n.c1.stats == C1S_GRAM ? FS_GRAM : FS_CONV;
             p.P = n.c1.fwd_blocks;
             p.apply = n.c1.fwd == C1F_POOLED ? FA_CONV1_POOL : FA_ACT;
+        } else if (c->fp8 && !no_mx8 && mx8_layer(c, l, p.training)) {
+            // MXFP8: inference batch norm (moving statistics) only.  The shared epilogue folds it (+ leaky) into the
+            // consumer's f16 bordered input where there is a consumer and no pool; else y in f16 and the two-pass form
+            p.mx8 = true;
+            p.stats = FS_MOVING;
+            if (l + 1 < nl && y.pool == 0 && y.ldy == c->L[l + 1].cin_s && !no_infer_fold && y.M < 0x7FFFFFFF)
+                p.fold = FOLD_AFFINE;
+            p.apply = p.fold != FOLD_NONE ? FA_NONE : FA_ACT;
+            // the MXFP8 epilogue: a folded MXFP8 producer writes this layer's e4m3 input + scales directly; every other
+            // producer (the image layer, f16-planned layers, pooled layers' apply pass) leaves f16, quantised here
+            if (l > 0 && n.L[l - 1].mx8 && n.L[l - 1].fold == FOLD_AFFINE) n.L[l - 1].out8 = p.in8 = true;
         } else {
             p.stats = !p.training ? FS_MOVING : y.pool == 2 ? FS_SUB : FS_CONV;
             const ConvPlan cp = plan_conv(c->dtype, fwd_args(c, l, p.stats == FS_CONV, FOLD_NONE));
@@ -448,6 +496,18 @@ static void plan(y2_ctx* c) {
         c->ks_floats = ks;
         c->o_ks = take(ks * sizeof(float));
     }
+    for (size_t l = 0; l < c->L.size(); ++l) {   // per MXFP8-capable layer: e4m3 input + scales, e4m3 filters + scales
+        Layer& y = c->L[l];
+        if (!mx8_shape(c, (int)l)) continue;
+        {
+            y.cin8 = mx8_channels(y.cin);
+            const size_t cpad = (size_t)round_up(y.cout, mx8_block_couts());
+            y.w8 = take(cpad * y.k * y.k * y.cin8);
+            y.w8s = take(cpad * y.k * y.k * (y.cin8 / 32));
+            y.x8 = take(PadGeom{c->N, y.H, y.W, y.cin8}.bytes(1));
+            y.x8s = take(PadGeom{c->N, y.H, y.W, y.cin8 / 32}.bytes(1));
+        }
+    }
     c->total_infer = off;
     // ---- training-only buffers
     for (size_t l = 0; l < c->L.size(); ++l) c->L[l].dyp = take(c->dy_geom((int)l).bytes(sz));
@@ -514,10 +574,16 @@ int y2_darknet19_spec(int kind, int output_filter, int* spec, int max_layers) {
 int y2_ctx_create(y2_ctx** out, const int* spec, int num_layers, int core_layers, int tail, int tail_k, int batch,
                   int height, int width, int dtype) {
     if (!out || !spec || num_layers <= 0) return fail(Y2_ERR_ARG, "bad arguments");
-    if (dtype < 0 || dtype > 4) return fail(Y2_ERR_ARG, "dtype must be 0 (f32), 1 (f16), 2 (bf16), 3 (f16x2) or 4 (f16x2f)");
+    if (dtype < 0 || dtype > Y2_FP8)
+        return fail(Y2_ERR_ARG, "dtype must be 0 (f32), 1 (f16), 2 (bf16), 3 (f16x2), 4 (f16x2f) or 5 (fp8)");
     if (batch <= 0 || height <= 0 || width <= 0) return fail(Y2_ERR_ARG, "bad input shape");
     y2_ctx* c = new y2_ctx();
     c->N = batch; c->H = height; c->W = width;
+    if (dtype == Y2_FP8) {                      // Y2_F16's tensors and passes; plan_net moves the MXFP8 layers (mx8_layer)
+        c->fp8 = 1;
+        c->mx8_all = getenv("Y2_MX8_ALL") != nullptr;
+        dtype = 1;
+    }
     c->bwd_dtype = dtype;                       // what the dgrad / weight-gradient launches run in
     c->dtype = dtype = (dtype == 4 ? 3 : dtype);   // tensors, forward pass, batch norm, optimizer: the split-operand mode's
     c->tail = tail; c->tail_k = tail_k; c->core_layers = core_layers;
@@ -699,6 +765,7 @@ int y2_bind(y2_ctx* c, float* params, float* grads, float* state, void* workspac
             int training, void* stream) {
     if (!params || !state || !workspace) return fail(Y2_ERR_ARG, "null buffer");
     if (training && !grads) return fail(Y2_ERR_ARG, "training needs a gradient buffer");
+    if (training && c->fp8) return fail(Y2_ERR_ARG, "Y2_FP8 contexts are inference only: bind with training = 0");
     const size_t need = y2_workspace_bytes(c, training);
     if (workspace_bytes < need) return fail(Y2_ERR_ARG, "workspace too small: %zu < %zu", workspace_bytes, need);
     c->params = params; c->grads = grads; c->state = state;
@@ -832,6 +899,18 @@ int y2_params_changed(y2_ctx* c) {
     return Y2_OK;
 }
 
+// Y2_FP8: the e4m3 filters + scales of every layer that may run on the MXFP8 kernel (beside the f16 pack, which the
+// layers with batch statistics use)
+static int pack_mx8_weights(y2_ctx* c, hipStream_t s) {
+    if (!c->fp8) return Y2_OK;
+    for (size_t l = 0; l < c->L.size(); ++l) {
+        const Layer& y = c->L[l];
+        if (!mx8_shape(c, (int)l)) continue;
+        HIPCHK(launch_mx_pack_filter(c->params + y.pW, y.k * y.k, y.cin, y.cout, round_up(y.cout, mx8_block_couts()),
+                                     y.cin8, (uint8_t*)(c->ws + y.w8), (uint8_t*)(c->ws + y.w8s), s));
+    }
+    return Y2_OK;
+}
 static int pack_all_weights(y2_ctx* c, hipStream_t s) {
     PROF(CAT_MISC);
     if (!c->L.empty() && c->L[0].first3)
@@ -839,6 +918,8 @@ static int pack_all_weights(y2_ctx* c, hipStream_t s) {
     if (c->pack_blocks > 0)
         HIPCHK(launch_pack_all(c->dtype, (const PackLayer*)(c->ws + c->o_packtab), (int)c->packtab.size(),
                                c->pack_blocks, s));
+    int r = pack_mx8_weights(c, s);
+    if (r) return r;
     c->weights_dirty = false;
     return Y2_OK;
 }
@@ -881,6 +962,10 @@ int y2_pack_group_run(y2_ctx** ctxs, int n, const void* table_dev, int nlayers, 
     }
     if (nlayers > 0 && blocks > 0)
         HIPCHK(launch_pack_all(ctxs[0]->dtype, (const PackLayer*)table_dev, nlayers, blocks, (hipStream_t)stream));
+    for (int i = 0; i < n; ++i) {
+        const int r = pack_mx8_weights(ctxs[i], (hipStream_t)stream);
+        if (r) return r;
+    }
     for (int i = 0; i < n; ++i) ctxs[i]->weights_dirty = false;
     return Y2_OK;
 }
@@ -951,7 +1036,31 @@ static int forward_impl(y2_ctx* c, const float* images, const uint8_t* images_u8
             if (p.apply != FA_CONV1_POOL || p1.stats == C1S_CONV) { PROF(CAT_CONV1_FWD); HIPCHK(launch_conv1_fwd(p1, a, s)); }
         } else {
             if (l == 0 && !c->ext_xin) HIPCHK(launch_pack_act(c->dtype, images, xin, c->N, y.H, y.W, y.cin, y.cin_s, s));
-            { PROF(CAT_CONV_FWD); HIPCHK(launch_conv(c->dtype, fwd_args(c, l, p.stats == FS_CONV, p.fold), s, y.wf_frag)); }
+            if (p.mx8) {
+                const PadGeom g8{c->N, y.H, y.W, y.cin8}, gs{c->N, y.H, y.W, y.cin8 / 32};
+                uint8_t* x8 = (uint8_t*)(c->ws + y.x8);
+                uint8_t* x8s = (uint8_t*)(c->ws + y.x8s);
+                if (!p.in8) {   // the f16 bordered input, borders and guard bands included (zeros quantise to zeros)
+                    PROF(CAT_MISC);
+                    HIPCHK(launch_mx_quantize(1, xin - c->in_geom(l).base_off(sz), g8.front_px() + g8.body_px() + g8.back_px(),
+                                              y.cin_s, y.cin8, x8, x8s, s));
+                }
+                ConvArgs a = fwd_args(c, l, false, p.fold);
+                a.x = x8 + g8.base_off(1); a.C = y.cin8; a.w = c->ws + y.w8;
+                a.ks_scratch = nullptr; a.ks_floats = 0;
+                Mx8Out qo{};
+                if (p.out8) {   // the consumer's e4m3 input instead of its f16 one
+                    const Layer& z = c->L[l + 1];
+                    qo.q = (uint8_t*)(c->ws + z.x8) + PadGeom{c->N, z.H, z.W, z.cin8}.base_off(1);
+                    qo.sc = (uint8_t*)(c->ws + z.x8s) + PadGeom{c->N, z.H, z.W, z.cin8 / 32}.base_off(1);
+                    qo.ldq = z.cin8;
+                }
+                PROF(CAT_CONV_FWD);
+                HIPCHK(launch_conv_mx8(0, a, x8s + gs.base_off(1), (const uint8_t*)(c->ws + y.w8s), p.out8 ? &qo : nullptr, s));
+            } else {
+                PROF(CAT_CONV_FWD);
+                HIPCHK(launch_conv(c->dtype, fwd_args(c, l, p.stats == FS_CONV, p.fold), s, y.wf_frag));
+            }
             if (p.stats == FS_SUB) {
                 PROF(CAT_BN_FWD);
                 HIPCHK(launch_bn_stats_sub(c->dtype, c->ws + y.y, c->N, y.H, y.W, y.ldy, part_cnt, part_mean, part_m2, s));
@@ -1046,6 +1155,7 @@ int y2_update_moving_stats(y2_ctx* c, void* stream) {
 static int fused_opt_part(y2_ctx* c, int part, hipStream_t s);
 
 int y2_backward(y2_ctx* c, const float* dout, int layer_lo, int layer_hi, void* stream) {
+    if (c->fp8) return fail(Y2_ERR_STATE, "Y2_FP8 contexts are inference only: no backward pass (create the context with another dtype to train)");
     if (!c->ws || !c->bound_training) return fail(Y2_ERR_STATE, "bind with training=1 first");
     if (!c->fwd_saved) return fail(Y2_ERR_STATE, "run y2_forward before y2_backward");
     const int nl = (int)c->L.size();
@@ -1263,6 +1373,8 @@ size_t y2_bordered_bytes(int N, int H, int W, int C, int dtype, size_t* cell0_of
 int y2_link(y2_ctx* c, void* x_bordered, void* out_bordered, const void* join_bordered, int join_self, const void* dout_t,
             void* dx_t) {
     if (!c || c->L.empty()) return fail(Y2_ERR_ARG, "y2_link: null or empty context");
+    if (c->fp8 && (x_bordered || out_bordered || join_bordered || join_self || dout_t || dx_t))
+        return fail(Y2_ERR_ARG, "y2_link: not built for Y2_FP8 contexts");
     if (dtype_split(c->dtype) && (x_bordered || out_bordered || join_bordered || join_self || dout_t || dx_t))
         return fail(Y2_ERR_ARG, "y2_link: not built for the split-operand mode");
     const Layer& first = c->L.front();
@@ -1297,7 +1409,11 @@ int y2_debug_read(y2_ctx* c, int l, int what, float* dst, void* stream) {
     const Layer& y = c->L[l];
     hipStream_t s = (hipStream_t)stream;
     const size_t sz = c->sz();
-    if (what == 0) {
+    if (what == 0 && c->fwd_saved && l < (int)c->fwd.L.size() && c->fwd.L[l].in8) {   // written in e4m3 by its producer
+        HIPCHK(launch_mx_unpack((const uint8_t*)(c->ws + y.x8) + PadGeom{c->N, y.H, y.W, y.cin8}.base_off(1),
+                                (const uint8_t*)(c->ws + y.x8s) + PadGeom{c->N, y.H, y.W, y.cin8 / 32}.base_off(1), dst, c->N,
+                                y.H, y.W, y.cin, y.cin8, s));
+    } else if (what == 0) {
         const int C = y.first3 ? 3 : y.cin;
         HIPCHK(launch_unpack_act(y.first3 ? dtype_plain(c->dtype) : c->dtype, c->ws + y.xin + c->in_geom(l).base_off(sz), dst, c->N, y.H, y.W, C,
                                  y.cin_s, s));
@@ -1480,6 +1596,7 @@ static int fused_opt_part(y2_ctx* c, int part, hipStream_t s) {
 // update of every layer above it runs on the weight-gradient stream while the first layer's gradient is computed.
 int y2_backward_adam(y2_ctx* c, const float* dout, float* m, float* v, void* ctrl, int step, float lr, float beta1,
                      float beta2, float eps, float grad_mult, void* stream) {
+    if (c->fp8) return fail(Y2_ERR_STATE, "Y2_FP8 contexts are inference only: no backward pass (create the context with another dtype to train)");
     if (!m || !v || (!ctrl && step < 1)) return fail(Y2_ERR_ARG, "bad arguments");
     if (!c->grads) return fail(Y2_ERR_STATE, "bind with a gradient buffer first");
     c->fopt = y2_ctx::FusedOpt{true, 0, m, v, ctrl, lr, beta1, beta2, eps, grad_mult, step};
@@ -1489,6 +1606,7 @@ int y2_backward_adam(y2_ctx* c, const float* dout, float* m, float* v, void* ctr
 }
 int y2_backward_momentum(y2_ctx* c, const float* dout, float* accum, void* ctrl, float lr, float momentum,
                          float grad_mult, void* stream) {
+    if (c->fp8) return fail(Y2_ERR_STATE, "Y2_FP8 contexts are inference only: no backward pass (create the context with another dtype to train)");
     if (!accum) return fail(Y2_ERR_ARG, "bad arguments");
     if (!c->grads) return fail(Y2_ERR_STATE, "bind with a gradient buffer first");
     c->fopt = y2_ctx::FusedOpt{true, 1, accum, nullptr, ctrl, lr, momentum, 0.f, 0.f, grad_mult, 0};
@@ -1567,14 +1685,62 @@ static hipError_t op_pack_bordered(int dtype, const float* x, char* region, size
     if (e != hipSuccess) return e;
     return launch_pack_act(dtype, x, region + g.base_off(dtype_size(dtype)), g.N, g.H, g.W, C, g.C, s);
 }
+// Y2_FP8 op-level forward: x -> fp32 bordered tensor (channels padded to mx8_channels) -> e4m3 + scales; w -> e4m3
+// filters + scales; the MXFP8 kernel writes fp32 y [M][ldy]
+struct OpPlan8 {
+    int C8, Cout_pad, ldy;
+    size_t xp, x8, x8s, w8, w8s, y, total;
+};
+static OpPlan8 op_plan8(int N, int H, int W, int Cin, int Cout, int k) {
+    OpPlan8 p{};
+    p.C8 = mx8_channels(Cin);
+    p.Cout_pad = round_up(Cout, mx8_block_couts());
+    p.ldy = round_up(Cout, 32);
+    size_t off = 0;
+    auto take = [&](size_t b) { size_t o = off; off += align_up(b, 256); return o; };
+    p.xp = take(PadGeom{N, H, W, p.C8}.bytes(4));
+    p.x8 = take(PadGeom{N, H, W, p.C8}.bytes(1));
+    p.x8s = take(PadGeom{N, H, W, p.C8 / 32}.bytes(1));
+    p.w8 = take((size_t)p.Cout_pad * k * k * p.C8);
+    p.w8s = take((size_t)p.Cout_pad * k * k * (p.C8 / 32));
+    p.y = take((size_t)N * H * W * p.ldy * sizeof(float) + 256);
+    p.total = off;
+    return p;
+}
+static int conv2d_fp8(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                      int k, void* workspace, hipStream_t s) {
+    if (Cin % 32 != 0) return fail(Y2_ERR_ARG, "y2_conv2d: Y2_FP8 needs Cin %% 32 == 0 (one scale per 32 channels)");
+    const OpPlan8 p = op_plan8(N, H, W, Cin, Cout, k);
+    char* ws = (char*)workspace;
+    const PadGeom g{N, H, W, p.C8}, gs{N, H, W, p.C8 / 32};
+    const size_t rows = g.front_px() + g.body_px() + g.back_px();
+    HIPCHK(op_pack_bordered(0, x, ws + p.xp, p.x8 - p.xp, g, Cin, s));
+    HIPCHK(launch_mx_quantize(0, ws + p.xp, rows, p.C8, p.C8, (uint8_t*)(ws + p.x8), (uint8_t*)(ws + p.x8s), s));
+    HIPCHK(launch_mx_pack_filter(w, k * k, Cin, Cout, p.Cout_pad, p.C8, (uint8_t*)(ws + p.w8), (uint8_t*)(ws + p.w8s), s));
+    ConvArgs a{};
+    a.x = ws + p.x8 + g.base_off(1); a.w = ws + p.w8; a.y = ws + p.y; a.bias = bias;
+    a.N = N; a.H = H; a.W = W; a.C = p.C8; a.M = N * H * W; a.Cout = Cout; a.ldy = p.ldy; a.taps = k * k;
+    HIPCHK(launch_conv_mx8(1, a, (const uint8_t*)(ws + p.x8s) + gs.base_off(1), (const uint8_t*)(ws + p.w8s), nullptr, s));
+    HIPCHK(launch_cast_to_f32(0, ws + p.y, y, (size_t)N * H * W, Cout, p.ldy, s));
+    return Y2_OK;
+}
 size_t y2_conv2d_workspace_bytes(int N, int H, int W, int Cin, int Cout, int k, int dtype) {
+    if (dtype == Y2_FP8) return op_plan8(N, H, W, Cin, Cout, k).total;
     return op_plan(N, H, W, Cin, Cout, k, dtype).total;
+}
+// MXFP8 quantiser of fp32 [rows][C] (C % 32 == 0): e4m3 elements [rows][C] + E8M0 scales [rows][C / 32]
+int y2_mx_quantize(const float* x, size_t rows, int C, uint8_t* q, uint8_t* scales, void* stream) {
+    if (!x || !q || !scales) return fail(Y2_ERR_ARG, "null tensor");
+    if (C <= 0 || C % 32 != 0) return fail(Y2_ERR_ARG, "y2_mx_quantize: C must be a positive multiple of 32");
+    HIPCHK(launch_mx_quantize(0, x, rows, C, C, q, scales, (hipStream_t)stream));
+    return Y2_OK;
 }
 int y2_conv2d(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
               int k, int dtype, void* workspace, void* stream) {
     if (!x || !w || !y || !workspace) return fail(Y2_ERR_ARG, "null tensor");
     if (k != 1 && k != 3) return fail(Y2_ERR_ARG, "filter size must be 1 or 3");
-    if (dtype < 0 || dtype > 4) return fail(Y2_ERR_ARG, "bad dtype");
+    if (dtype < 0 || dtype > Y2_FP8) return fail(Y2_ERR_ARG, "bad dtype");
+    if (dtype == Y2_FP8) return conv2d_fp8(x, w, bias, y, N, H, W, Cin, Cout, k, workspace, (hipStream_t)stream);
     if (dtype == 4) dtype = 3;      // f16x2f: the forward pass is the split-operand mode's
     hipStream_t s = (hipStream_t)stream;
     const size_t sz = dtype_size(dtype);
@@ -1597,6 +1763,7 @@ int y2_conv2d_backward(const float* x, const float* w, const float* dy, float* d
                        int Cin, int Cout, int k, int dtype, void* workspace, void* stream) {
     if (!x || !w || !dy || !workspace) return fail(Y2_ERR_ARG, "null tensor");
     if (k != 1 && k != 3) return fail(Y2_ERR_ARG, "filter size must be 1 or 3");
+    if (dtype == Y2_FP8) return fail(Y2_ERR_ARG, "y2_conv2d_backward: Y2_FP8 is inference only (forward y2_conv2d)");
     if (dtype < 0 || dtype > 4) return fail(Y2_ERR_ARG, "bad dtype");
     const int ldt = dtype;          // launch dtype of the two contractions (4: hi planes of the split tensors)
     if (dtype == 4) dtype = 3;      // tensors and packs: the split-operand mode's

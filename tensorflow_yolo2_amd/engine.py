@@ -102,6 +102,8 @@ class Network:
         self.spec = [tuple(int(v) for v in s) for s in spec]
         self.dtype = _lib.DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
         self.training = bool(training)
+        if self.dtype == _lib.Y2_FP8 and self.training:
+            raise _lib.Y2Error("dtype 'fp8' (MXFP8) is inference only: create the Network with training=False")
         self.batch, self.height, self.width = batch, height, width
         self.core_layers = len(spec) if core_layers is None else core_layers
         flat = (C.c_int * (4 * len(spec)))(*[v for s in self.spec for v in s])
