@@ -399,6 +399,28 @@ int y2_conv2d_backward(const float* x, const float* w, const float* dy, float* d
  *      + E8M0 scales [rows][C / 32] (one per 32 consecutive values of a row), device buffers */
 int y2_mx_quantize(const float* x, size_t rows, int C, uint8_t* q, uint8_t* scales, void* stream);
 
+/* ---- device-resident input batches (img_dataset/device_voc.py): the reference's imdb.get() (src/img_dataset/
+ *      pascal_voc.py:42-86: cv2.resize to image_size, optional mirror, label grid) from ONE copy of the decoded images
+ *      kept at native resolution in device memory, for any output size.  Both calls are bit-equal to the host code of
+ *      img_dataset/pascal_voc.py (resize_bilinear_u8, encode_boxes, flip_label, the float32 cast of get_u8).
+ *      `table`: int64 [entries][5] = {byte offset of the image in `pool`, height, width, row pitch in bytes, flip};
+ *      pixels are uint8 BGR, 3 bytes per pixel, rows `pitch` bytes apart.  Offsets and pitches that are multiples of
+ *      16 (and pitch <= 4096) let the kernel stage rows with 16-byte loads; anything else is read in place, same
+ *      result.  `index`: int32 [n], the table entry of each batch slot (NULL: slot i is entry i).  All pointers are
+ *      device memory. */
+#define Y2_RESIZE_MAX_OUT_W 1024 /* columns of the kernel's coefficient table: out_w beyond it is an argument error */
+/* out [n][out_h][out_w][3] uint8: cv2.resize(img, (out_w, out_h)) INTER_LINEAR on uint8 (half-pixel centres, no
+ * antialias, 11-bit weights from float64 coefficients, (top * wy0 + bot * wy1 + 2^21) >> 22), then [:, ::-1, :] where
+ * the entry's flip is set. */
+int y2_resize_bilinear_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, int n, int out_h,
+                                int out_w, uint8_t* out, void* stream);
+/* labels [n][S][S][5 + num_class] float32 (zero-filled here): `boxes` double [entries][max_obj][5] = xmin, ymin, xmax,
+ * ymax, class index in 1-based pixels of the original image, in annotation order; `counts` int32 [entries].  Ratios
+ * image_size / width, clamp to [0, image_size - 1], centre / size, cell int(c * S / image_size), the first object of a
+ * cell wins; a flipped entry mirrors the columns and stores image_size - 1 - x. */
+int y2_encode_labels(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index, int n,
+                     int max_obj, int image_size, int S, int num_class, float* labels, void* stream);
+
 /* ---- host utility: CRC-32C (Castagnoli) of a host buffer, continuing from `crc` (0 to start).  The checksum of
  *      TensorFlow's V2 checkpoint files (tensor bundle + table blocks), which the reference reads and writes through
  *      tf.train.Saver (src/yolo2_nets/net_utils.py:64-110); used by utils/tf_bundle.py on 100-MB tensors. */

@@ -1,0 +1,208 @@
+// The input side of the detector on the device: a batch of uint8 BGR images resized from a pool of images kept at their
+// native resolution, and the [S,S,5+C] label grids of the same batch from per-image object lists.  The specification is
+// this repository's host code (img_dataset/pascal_voc.py: resize_bilinear_u8, encode_boxes, flip_label; restated in
+// oracle/data_ref.py), and both kernels are bit-equal to it: the coefficients are computed in double in the
+// specification's operation order, and the file is compiled with -ffp-contract=off (a fused multiply-add in
+// (i + 0.5) * scale - 0.5 or in frac * 2048 can move a rounding tie).
+#include <stdio.h>
+#include <stdarg.h>
+#include "common.h"
+#include "../../include/yolo2_hip.h"
+
+namespace y2 {
+int set_error(int code, const char* msg);   // net.hip (y2_last_error)
+}
+using namespace y2;
+static int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return set_error(code, buf);
+}
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxOutW = Y2_RESIZE_MAX_OUT_W;   // columns of the x-coefficient table in LDS
+constexpr int kBand = 16;                       // output rows of one workgroup
+constexpr int kRows = 4;                        // output rows produced from one staging of source rows
+constexpr int kMaxPitch = 4096;                 // widest source row (bytes) that is staged in LDS; wider rows are read in place
+constexpr int kTable = 5;                       // int64 per image: byte offset, height, width, row pitch, flip
+
+struct XCoef { int x0; short dx; short w1; };   // byte offset of the left pixel, byte distance to the right one, weight
+
+// one axis of cv2.resize INTER_LINEAR on uint8: output index o of n_out -> clamped source indices and the 11-bit
+// weight of the second one.  float64, the specification's operation order.
+Y2_DEV void lin_coef(int o, int n_in, int n_out, int& i0c, int& i1c, int& w1) {
+    const double scale = (double)n_in / (double)n_out;
+    const double f = ((double)o + 0.5) * scale - 0.5;
+    const double fl = floor(f);
+    const int i0 = (int)fl;
+    const double frac = i0 < 0 ? 0.0 : f - fl;
+    w1 = (int)rint(frac * 2048.0);
+    i0c = min(max(i0, 0), n_in - 1);
+    i1c = min(max(i0 + 1, 0), n_in - 1);
+}
+
+// VEC consecutive output bytes starting at byte b of an output row: r0 / r1 are the two source rows (LDS or global)
+template <int VEC>
+Y2_DEV uint32_t resize_bytes(const uint8_t* r0, const uint8_t* r1, const XCoef* xt, int b, int wy1) {
+    const int wy0 = 2048 - wy1;
+    int x = b / 3, c = b - 3 * x;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        const XCoef q = xt[x];
+        const int a0 = q.x0 + c, a1 = a0 + q.dx;
+        const int wx1 = q.w1, wx0 = 2048 - wx1;
+        const int top = (int)r0[a0] * wx0 + (int)r0[a1] * wx1;
+        const int bot = (int)r1[a0] * wx0 + (int)r1[a1] * wx1;
+        const int v = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;   // <= 255 * 2^22 + 2^21 < 2^31
+        packed |= (uint32_t)(v & 255) << (8 * e);
+        if (++c == 3) { c = 0; ++x; }
+    }
+    return packed;
+}
+
+// grid (ceil(out_h / kBand), n).  A workgroup owns kBand output rows of one image: the x coefficients of the image
+// (mirrored when it is flipped) are computed once into LDS; for every kRows output rows the 2 * kRows source rows they
+// blend are staged into LDS with 16-byte loads, and each lane produces VEC consecutive output bytes per store.
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t* __restrict__ pool,
+                                                             const int64_t* __restrict__ table,
+                                                             const int32_t* __restrict__ index, int out_h, int out_w,
+                                                             uint8_t* __restrict__ out) {
+    __shared__ XCoef xt[kMaxOutW];
+    __shared__ int yc[kBand][3];
+    __shared__ __attribute__((aligned(16))) uint8_t rows[2 * kRows * kMaxPitch];
+    const int tid = threadIdx.x, img = blockIdx.y;
+    const int64_t* t = table + (size_t)kTable * (index ? index[img] : img);
+    const int64_t off = t[0], pitch64 = t[3];
+    const int H = (int)t[1], W = (int)t[2], flip = (int)t[4];
+    const int band0 = blockIdx.x * kBand, nrows = min(kBand, out_h - band0);
+    if (H < 1 || W < 1) return;                 // (an empty table row: nothing to read)
+    for (int x = tid; x < out_w; x += kThreads) {
+        int x0, x1, w1;
+        lin_coef(flip ? out_w - 1 - x : x, W, out_w, x0, x1, w1);
+        xt[x] = XCoef{3 * x0, (short)(3 * (x1 - x0)), (short)w1};
+    }
+    if (tid < nrows) lin_coef(band0 + tid, H, out_h, yc[tid][0], yc[tid][1], yc[tid][2]);
+    __syncthreads();
+    const bool staged = pitch64 <= kMaxPitch && ((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W;
+    const int pitch = (int)pitch64;
+    const uint8_t* src = pool + off;
+    const int rowbytes = 3 * out_w;
+    uint8_t* obase = out + ((size_t)img * out_h + band0) * rowbytes;
+    for (int g0 = 0; g0 < nrows; g0 += kRows) {
+        const int gr = min(kRows, nrows - g0);
+        if (staged) {
+            const int chunks = pitch >> 4;
+            for (int i = tid; i < 2 * gr * chunks; i += kThreads) {
+                const int slot = i / chunks, c = i - slot * chunks;
+                const int y = yc[g0 + (slot >> 1)][slot & 1];
+                *(u32x4*)(rows + slot * pitch + 16 * c) = *(const u32x4*)(src + (size_t)y * pitch64 + 16 * c);
+            }
+            __syncthreads();
+        }
+        const int total = gr * rowbytes;
+        for (int k = tid * VEC; k < total; k += kThreads * VEC) {
+            const int j = k / rowbytes, b = k - j * rowbytes;
+            const int* y = yc[g0 + j];
+            uint32_t v;
+            if (staged)
+                v = resize_bytes<VEC>(rows + (2 * j) * pitch, rows + (2 * j + 1) * pitch, xt, b, y[2]);
+            else
+                v = resize_bytes<VEC>(src + (size_t)y[0] * pitch64, src + (size_t)y[1] * pitch64, xt, b, y[2]);
+            uint8_t* o = obase + (size_t)g0 * rowbytes + k;
+            if (VEC == 4) *(uint32_t*)o = v;
+            else *o = (uint8_t)v;
+        }
+        if (staged) __syncthreads();
+    }
+}
+
+// grid (n).  The workgroup zero-fills the image's grid; then ONE lane walks the image's objects in annotation order
+// (the first object of a cell wins, which is sequential).  double arithmetic in the specification's order, one cast
+// to float at each store.  A flipped image writes the mirrored column and image_size - 1 - x directly: the mirror is
+// a bijection of the cells, so "first wins" picks the same objects as flipping the finished grid.
+__global__ __launch_bounds__(kThreads) void encode_labels_kernel(const double* __restrict__ boxes,
+                                                                 const int32_t* __restrict__ counts,
+                                                                 const int64_t* __restrict__ table,
+                                                                 const int32_t* __restrict__ index, int max_obj,
+                                                                 int image_size, int S, int num_class,
+                                                                 float* __restrict__ labels) {
+    const int img = blockIdx.x, D = 5 + num_class;
+    const size_t e = index ? (size_t)index[img] : (size_t)img;
+    float* g = labels + (size_t)img * S * S * D;
+    for (int i = threadIdx.x; i < S * S * D; i += kThreads) g[i] = 0.0f;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int64_t* t = table + kTable * e;
+    const int im_h = (int)t[1], im_w = (int)t[2], flip = (int)t[4];
+    const double h_ratio = 1.0 * image_size / im_h, w_ratio = 1.0 * image_size / im_w;
+    const double hi = (double)(image_size - 1);
+    const int cnt = min(max(counts[e], 0), max_obj);
+    const double* bx = boxes + e * (size_t)max_obj * 5;
+    for (int o = 0; o < cnt; ++o, bx += 5) {
+        double x1 = (bx[0] - 1) * w_ratio, y1 = (bx[1] - 1) * h_ratio;
+        double x2 = (bx[2] - 1) * w_ratio, y2 = (bx[3] - 1) * h_ratio;
+        x1 = hi < x1 ? hi : x1; x1 = 0.0 > x1 ? 0.0 : x1;
+        y1 = hi < y1 ? hi : y1; y1 = 0.0 > y1 ? 0.0 : y1;
+        x2 = hi < x2 ? hi : x2; x2 = 0.0 > x2 ? 0.0 : x2;
+        y2 = hi < y2 ? hi : y2; y2 = 0.0 > y2 ? 0.0 : y2;
+        const double cx = (x2 + x1) / 2.0, cy = (y2 + y1) / 2.0;
+        int x_ind = (int)(cx * S / image_size), y_ind = (int)(cy * S / image_size);
+        if (!(x_ind >= 0 && x_ind < S && y_ind >= 0 && y_ind < S)) continue;   // (not a number in the box table)
+        if (flip) x_ind = S - 1 - x_ind;
+        float* cell = g + ((size_t)y_ind * S + x_ind) * D;
+        if (cell[0] == 1.0f) continue;
+        cell[0] = 1.0f;
+        cell[1] = (float)(flip ? hi - cx : cx);
+        cell[2] = (float)cy;
+        cell[3] = (float)(x2 - x1);
+        cell[4] = (float)(y2 - y1);
+        const int cls = (int)bx[4];
+        if (cls >= 0 && cls < num_class) cell[5 + cls] = 1.0f;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int y2_resize_bilinear_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, int n, int out_h,
+                                int out_w, uint8_t* out, void* stream) {
+    if (!pool || !table || !out) return fail(Y2_ERR_ARG, "y2_resize_bilinear_u8_batch: null pointer");
+    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "y2_resize_bilinear_u8_batch: n = %d outside 1..65535", n);
+    if (out_h < 1 || out_w < 1) return fail(Y2_ERR_ARG, "y2_resize_bilinear_u8_batch: output %d x %d", out_h, out_w);
+    if (out_w > kMaxOutW)
+        return fail(Y2_ERR_ARG, "y2_resize_bilinear_u8_batch: out_w = %d beyond Y2_RESIZE_MAX_OUT_W = %d", out_w, kMaxOutW);
+    const dim3 grid((out_h + kBand - 1) / kBand, n);
+    if (out_w % 4 == 0 && ((uintptr_t)out & 3) == 0)
+        hipLaunchKernelGGL(resize_u8_kernel<4>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, out_h,
+                           out_w, out);
+    else
+        hipLaunchKernelGGL(resize_u8_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, out_h,
+                           out_w, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_resize_bilinear_u8_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_encode_labels(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index, int n,
+                     int max_obj, int image_size, int S, int num_class, float* labels, void* stream) {
+    if (!boxes || !counts || !table || !labels) return fail(Y2_ERR_ARG, "y2_encode_labels: null pointer");
+    if (n < 1) return fail(Y2_ERR_ARG, "y2_encode_labels: n = %d", n);
+    if (max_obj < 1 || image_size < 1 || S < 1 || num_class < 0 || S > 1024)
+        return fail(Y2_ERR_ARG, "y2_encode_labels: max_obj = %d, image_size = %d, S = %d, num_class = %d", max_obj,
+                    image_size, S, num_class);
+    hipLaunchKernelGGL(encode_labels_kernel, dim3(n), dim3(kThreads), 0, (hipStream_t)stream, boxes, counts, table,
+                       index, max_obj, image_size, S, num_class, labels);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_encode_labels: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,169 @@
+"""Device-resident VOC batches: the decoded images live ONCE, at native resolution, in a uint8 pool in device memory;
+every batch -- at any input size -- is produced on the device by two kernels of libyolo2_hip.so
+(y2_resize_bilinear_u8_batch, y2_encode_labels: csrc/data.hip).  After start-up the host touches no pixel.
+
+For a fixed size, DeviceVOC(...).get(size) called k times returns bit for bit what
+pascal_voc(..., image_size=size, cell_size=size // 32, same flipped / seed / rank / world).get_u8() returns on its k-th
+call: both walk pascal_voc.ShardedOrder (one shuffle at start, stride sharding, reshuffle at the wrap), and the kernels
+are bit-equal to the host resize and label encoder.  Not in the reference (one image size, cv2 on the host every step);
+what it serves is multi-scale training from real images (pascal_train_darknet.py --devkit ... --multi-scale).
+
+Pool layout: image k starts at byte offset off[k] (a multiple of 16), rows pitch[k] = 3 * width rounded up to 16 bytes
+apart, BGR uint8; the bytes between 3 * width and the pitch are zero.  Entry table: int64 [entries][5] = {off, height,
+width, pitch, flip}; with `flipped` the entries are the images followed by their mirrored copies (same offset, flip = 1),
+the order of pascal_voc.prepare.  Box table: float64 [entries][max_obj][5] = xmin, ymin, xmax, ymax, class index in
+annotation order, and int32 counts [entries]."""
+import ctypes as C
+import os
+import zlib
+
+import numpy as np
+
+from .pascal_voc import CLASSES, ShardedOrder, imread_bgr, read_image_set
+
+ALIGN = 16
+DEFAULT_MAX_POOL_BYTES = 16 << 30
+
+
+def _round_up(v, a):
+    return (int(v) + a - 1) // a * a
+
+
+def pool_layout(shapes):
+    """(offsets, pitches, total bytes) of images of the given (height, width) shapes, 16-byte aligned"""
+    offsets, pitches, total = [], [], 0
+    for (h, w) in shapes:
+        pitch = _round_up(3 * w, ALIGN)
+        offsets.append(total)
+        pitches.append(pitch)
+        total += _round_up(h * pitch, ALIGN)
+    return offsets, pitches, total
+
+
+def build_tables(entries, offsets, pitches, flipped):
+    """entry table int64 [E][5], box table float64 [E][max_obj][5], counts int32 [E]; E = len(entries) * (2 if flipped
+    else 1), mirrored copies after the plain ones"""
+    n = len(entries)
+    copies = 2 if flipped else 1
+    max_obj = max(len(e['objs']) for e in entries)
+    table = np.zeros((n * copies, 5), np.int64)
+    boxes = np.zeros((n * copies, max_obj, 5), np.float64)
+    counts = np.zeros(n * copies, np.int32)
+    for c in range(copies):
+        for k, e in enumerate(entries):
+            table[c * n + k] = (offsets[k], e['shape'][0], e['shape'][1], pitches[k], c)
+            counts[c * n + k] = len(e['objs'])
+            if e['objs']:
+                boxes[c * n + k, :len(e['objs'])] = np.asarray(e['objs'], np.float64)
+    return table, boxes, counts
+
+
+def padded_rows(img, pitch):
+    """[H, W, 3] uint8 -> [H, pitch] uint8, zero bytes after 3 * W"""
+    h, w = img.shape[:2]
+    out = np.zeros((h, pitch), np.uint8)
+    out[:, :3 * w] = img.reshape(h, 3 * w)
+    return out
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+class DeviceVOC(ShardedOrder):
+    def __init__(self, image_set, batch_size=None, devkit_path=None, flipped=None, seed=0, rank=0, world=1,
+                 device="cuda", max_pool_bytes=DEFAULT_MAX_POOL_BYTES):
+        from .. import config as cfg
+        self.name = 'voc_2007'
+        self.devkit_path = devkit_path or os.path.join('data', 'VOCdevkit')
+        self.data_path = os.path.join(self.devkit_path, 'VOC2007')
+        assert os.path.exists(self.data_path), 'Path does not exist: {}'.format(self.data_path)
+        self.batch_size = cfg.BATCH_SIZE if batch_size is None else batch_size
+        self.classes = CLASSES
+        self.num_class = len(CLASSES)
+        self.flipped = bool(getattr(cfg, "FLIPPED", False)) if flipped is None else bool(flipped)
+        self.image_set = image_set
+        self.device = device
+        self._init_order(seed, rank, world)
+        self.image_index, self.entries = read_image_set(self.data_path, image_set)
+        assert self.entries, "no image with objects in %s" % image_set
+        self.offsets, self.pitches, self.pool_bytes = pool_layout([e['shape'] for e in self.entries])
+        if self.pool_bytes > max_pool_bytes:
+            raise MemoryError("the decoded image pool needs %d bytes (%d images), max_pool_bytes is %d"
+                              % (self.pool_bytes, len(self.entries), max_pool_bytes))
+        table, boxes, counts = build_tables(self.entries, self.offsets, self.pitches, self.flipped)
+        self.max_obj = boxes.shape[1]
+        self.pool = self._alloc_pool(self.pool_bytes)
+        for e, off, pitch in zip(self.entries, self.offsets, self.pitches):
+            img = imread_bgr(e['imname'])                  # decoded ONCE; no host copy is kept
+            assert img.shape == (e['shape'][0], e['shape'][1], 3), (e['imname'], img.shape, e['shape'])
+            self._put(self.pool, off, padded_rows(img, pitch).reshape(-1))
+        self.table, self.boxes, self.counts = self._upload(table), self._upload(boxes), self._upload(counts)
+        n = len(self.entries)
+        gt = [{'imname': self.entries[k % n]['imname'], 'flipped': k >= n, 'entry': k} for k in range(len(table))]
+        self.gt_labels = self._start_order(gt)
+        self._check_ranks_agree()
+        self._buffers = {}
+
+    # ---- the only places that touch device memory at start-up (torch supplies allocations and copies)
+    def _alloc_pool(self, nbytes):
+        import torch
+        return torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _put(self, pool, offset, flat_u8):
+        import torch
+        pool[offset:offset + flat_u8.size].copy_(torch.from_numpy(flat_u8))
+
+    def _upload(self, array):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(array)).to(self.device)
+
+    def order_digest(self):
+        """(number of entries, CRC-32 of the current order): equal on ranks that hold the same list and seed"""
+        text = "\n".join("%s %d" % (os.path.basename(g['imname']), g['flipped']) for g in self.gt_labels)
+        return len(self.gt_labels), zlib.crc32(text.encode())
+
+    def _check_ranks_agree(self):
+        """stride sharding assumes ONE list on every rank: compare its length and first shuffled order"""
+        if self.world <= 1:
+            return
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() == self.world):
+            return                                          # plain constructor arguments, no process group
+        mine = self.order_digest()
+        every = [None] * self.world
+        dist.all_gather_object(every, mine)
+        if any(tuple(d) != tuple(mine) for d in every):
+            raise RuntimeError("ranks hold different image lists or orders (entries, crc32 per rank): %r" % (every,))
+
+    def buffers(self, size):
+        """the (images, labels) tensors get(size) writes: kept per size, overwritten by the next get(size)"""
+        import torch
+        if size < 32 or size % 32:
+            raise ValueError("size %r is not a positive multiple of 32" % (size,))
+        if size not in self._buffers:
+            S = size // 32
+            self._buffers[size] = (
+                torch.empty((self.batch_size, size, size, 3), dtype=torch.uint8, device=self.device),
+                torch.empty((self.batch_size, S, S, 5 + self.num_class), dtype=torch.float32, device=self.device),
+                torch.empty(self.batch_size, dtype=torch.int32, device=self.device))
+        return self._buffers[size]
+
+    def get(self, size):
+        """(images [B, size, size, 3] uint8 BGR, labels [B, S, S, 25] float32), S = size // 32, device tensors written
+        on the current stream; asynchronous"""
+        import torch
+        from .. import _lib
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("DeviceVOC.get needs the pool on the GPU (device=%r)" % (self.device,))
+        images, labels, index = self.buffers(size)
+        host = torch.from_numpy(np.array([self._next()['entry'] for _ in range(self.batch_size)], np.int32))
+        index.copy_(host.pin_memory(), non_blocking=True)
+        lib = _lib.load()
+        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+        _lib.check(lib.y2_resize_bilinear_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index), self.batch_size,
+                                                   size, size, _ptr(images), stream))
+        _lib.check(lib.y2_encode_labels(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
+                                        self.batch_size, self.max_obj, size, size // 32, self.num_class, _ptr(labels),
+                                        stream))
+        return images, labels

@@ -36,9 +36,9 @@ def encode_boxes(objs, im_h, im_w, image_size, cell_size, num_class=20):
     return label
 
 
-def load_pascal_annotation(xml_path_or_text, image_size, cell_size, im_shape=None):
-    """(label [S,S,25], number of objects).  The reference opens the JPEG only for its
-    shape (pascal_voc.py:131-134); the XML's <size> carries the same numbers."""
+def parse_annotation(xml_path_or_text, im_shape=None):
+    """(object list [(xmin, ymin, xmax, ymax, class_index)] in annotation order, (height, width)).  The reference opens
+    the JPEG only for its shape (pascal_voc.py:131-134); the XML's <size> carries the same numbers."""
     text = xml_path_or_text
     if "<annotation" not in text:
         with open(xml_path_or_text) as f:
@@ -53,7 +53,64 @@ def load_pascal_annotation(xml_path_or_text, image_size, cell_size, im_shape=Non
         cls_ind = CLASSES.index(obj.find('name').text.lower().strip())
         objs.append((float(bb.find('xmin').text), float(bb.find('ymin').text),
                      float(bb.find('xmax').text), float(bb.find('ymax').text), cls_ind))
+    return objs, (int(im_shape[0]), int(im_shape[1]))
+
+
+def load_pascal_annotation(xml_path_or_text, image_size, cell_size, im_shape=None):
+    """(label [S,S,25], number of objects)"""
+    objs, im_shape = parse_annotation(xml_path_or_text, im_shape)
     return encode_boxes(objs, im_shape[0], im_shape[1], image_size, cell_size), len(objs)
+
+
+def read_image_set(data_path, image_set):
+    """The image list of pascal_voc.load_labels (:87-124) without the encoding: (image_index, entries), one entry
+    {'imname', 'objs', 'shape': (height, width)} per image of ImageSets/Main/<image_set>.txt that has objects
+    (images without any are dropped, :116-118), in list order."""
+    import os
+    txtname = os.path.join(data_path, 'ImageSets', 'Main', image_set + '.txt')
+    assert os.path.exists(txtname), 'Path does not exist: {}'.format(txtname)
+    with open(txtname) as f:
+        image_index = [x.strip() for x in f.readlines() if x.strip()]
+    entries = []
+    for index in image_index:
+        imname = os.path.join(data_path, 'JPEGImages', index + '.jpg')
+        xml = os.path.join(data_path, 'Annotations', index + '.xml')
+        # the reference reads the JPEG for its shape (:131-134); the header is enough
+        from PIL import Image
+        with Image.open(imname) as im:
+            w, h = im.size
+        objs, shape = parse_annotation(xml, im_shape=(h, w))
+        if len(objs) == 0:
+            continue
+        entries.append({'imname': imname, 'objs': objs, 'shape': shape})
+    return image_index, entries
+
+
+class ShardedOrder(object):
+    """The order in which a batcher walks `self.gt_labels` (pascal_voc.py:42-58,86 plus the round-6 stride sharding):
+    one shuffle at start, rank r reads positions r, r + world, ... (len // world of them per epoch), one reshuffle at
+    every wrap of the cursor.  The list entries are opaque here; a shuffle consumes the generator by the list's LENGTH
+    alone, so two batchers over lists of equal length with equal seeds walk the same permutation."""
+
+    def _init_order(self, seed, rank, world):
+        assert world >= 1 and 0 <= rank < world, (rank, world)
+        self.rank, self.world = int(rank), int(world)
+        self.rng = np.random.default_rng(seed)
+        self.cursor = 0
+
+    def _start_order(self, gt_labels):
+        self.rng.shuffle(gt_labels)
+        self.per_rank = len(gt_labels) // self.world      # positions of one epoch on every rank
+        assert self.per_rank >= 1, "fewer images (%d) than ranks (%d)" % (len(gt_labels), self.world)
+        return gt_labels
+
+    def _next(self):
+        g = self.gt_labels[self.cursor * self.world + self.rank]
+        self.cursor += 1
+        if self.cursor >= self.per_rank:
+            self.rng.shuffle(self.gt_labels)
+            self.cursor = 0
+        return g
 
 
 def resize_bilinear_u8(img, out_h, out_w):
@@ -102,7 +159,7 @@ def flip_label(label, image_size):
     return out
 
 
-class pascal_voc(object):
+class pascal_voc(ShardedOrder):
     """The batcher of src/img_dataset/pascal_voc.py:13-86 (`imdb.get()` feeds one sess.run per step,
     pascal_train_darknet.py:96-102): VOC2007 devkit layout (ImageSets/Main/<image_set>.txt, JPEGImages/<i>.jpg,
     Annotations/<i>.xml), images without objects dropped (:116-118), optional flip duplication (:72-85), one
@@ -134,45 +191,25 @@ class pascal_voc(object):
         self.class_to_ind = dict(zip(self.classes, range(self.num_class)))
         self.flipped = bool(getattr(cfg, "FLIPPED", False)) if flipped is None else bool(flipped)
         self.image_set = image_set
-        self.cursor = 0
-        assert world >= 1 and 0 <= rank < world, (rank, world)
-        self.rank, self.world = int(rank), int(world)
-        self.rng = np.random.default_rng(seed)
+        self._init_order(seed, rank, world)
         self.cache_images = cache_images
         self._cache = {}
         assert os.path.exists(self.data_path), 'Path does not exist: {}'.format(self.data_path)
         self.gt_labels = self.prepare()
-        self.per_rank = len(self.gt_labels) // self.world      # positions of one epoch on every rank
-        assert self.per_rank >= 1, "fewer images (%d) than ranks (%d)" % (len(self.gt_labels), self.world)
 
     # ---- pascal_voc.py:69-124
     def load_labels(self):
-        import os
-        txtname = os.path.join(self.data_path, 'ImageSets', 'Main', self.image_set + '.txt')
-        assert os.path.exists(txtname), 'Path does not exist: {}'.format(txtname)
-        with open(txtname) as f:
-            self.image_index = [x.strip() for x in f.readlines() if x.strip()]
-        gt_labels = []
-        for index in self.image_index:
-            imname = os.path.join(self.data_path, 'JPEGImages', index + '.jpg')
-            xml = os.path.join(self.data_path, 'Annotations', index + '.xml')
-            # the reference reads the JPEG for its shape (:131-134); the header is enough
-            from PIL import Image
-            with Image.open(imname) as im:
-                w, h = im.size
-            label, num = load_pascal_annotation(xml, self.image_size, self.cell_size, im_shape=(h, w))
-            if num == 0:
-                continue
-            gt_labels.append({'imname': imname, 'label': label, 'flipped': False})
-        return gt_labels
+        self.image_index, entries = read_image_set(self.data_path, self.image_set)
+        return [{'imname': e['imname'], 'flipped': False, 'objs': e['objs'], 'shape': e['shape'],
+                 'label': encode_boxes(e['objs'], e['shape'][0], e['shape'][1], self.image_size, self.cell_size)}
+                for e in entries]
 
     def prepare(self):
         gt_labels = self.load_labels()
         if self.flipped:
-            gt_labels = gt_labels + [{'imname': g['imname'], 'label': flip_label(g['label'], self.image_size),
-                                      'flipped': True} for g in gt_labels]
-        self.rng.shuffle(gt_labels)
-        return gt_labels
+            gt_labels = gt_labels + [dict(g, label=flip_label(g['label'], self.image_size), flipped=True)
+                                     for g in gt_labels]
+        return self._start_order(gt_labels)
 
     # ---- pascal_voc.py:60-67
     def image_read_u8(self, imname, flipped=False):
@@ -187,15 +224,7 @@ class pascal_voc(object):
         image = self.image_read_u8(imname, flipped).astype(np.float32)
         return (image / 255.0) * 2.0 - 1.0
 
-    # ---- pascal_voc.py:42-58
-    def _next(self):
-        g = self.gt_labels[self.cursor * self.world + self.rank]
-        self.cursor += 1
-        if self.cursor >= self.per_rank:
-            self.rng.shuffle(self.gt_labels)
-            self.cursor = 0
-        return g
-
+    # ---- pascal_voc.py:42-58 (the cursor: ShardedOrder._next)
     def get(self):
         images = np.zeros((self.batch_size, self.image_size, self.image_size, 3), np.float32)
         labels = np.zeros((self.batch_size, self.cell_size, self.cell_size, 25), np.float32)
