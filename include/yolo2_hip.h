@@ -421,6 +421,24 @@ int y2_resize_bilinear_u8_batch(const uint8_t* pool, const int64_t* table, const
 int y2_encode_labels(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index, int n,
                      int max_obj, int image_size, int S, int num_class, float* labels, void* stream);
 
+/* ---- training augmentation on the same pool (img_dataset/augment.py is the specification; both calls are bit-equal to
+ *      it): `params` double [n][8] in device memory, one row per BATCH SLOT = {x0, y0, cw, ch, flip, hue, sat, exp}.
+ *      x0, y0, cw, ch: a window of the source in integer pixels (columns x0 .. x0 + cw - 1), which may extend beyond
+ *      the image on any side; flip: mirror on top of the entry's (the two cancel); hue, sat, exp: float32 values of
+ *      the colour distortion, (0, 1, 1) = none.  The row {0, 0, width, height, 0, 0, 1, 1} reproduces the two calls
+ *      above.  x0, y0, cw, ch are integers; a fraction is cut off (toward zero) by both calls.  A row without a window (cw < 1 or ch < 1, or not a number) gives an image of `fill` alone and an empty
+ *      grid.  `pool`, `table`, `index`, `boxes`, `counts` as above. */
+/* out [n][out_h][out_w][3] uint8: the window (pixels outside the image = `fill`, 0..255) resized as above with cw x ch
+ * for the source size, mirrored, then through HSV in float32: hue + 6 * hue wrapped into [0, 6), min(s * sat, 1),
+ * min(v * exp, 1), (int)(x * 255 + 0.5) (augment.distort_hsv_u8).  One launch; out_w <= Y2_RESIZE_MAX_OUT_W. */
+int y2_augment_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, const double* params, int n,
+                        int out_h, int out_w, int fill, uint8_t* out, void* stream);
+/* y2_encode_labels with the boxes following the window: x = (bx - 1 - x0) * (image_size / cw), y likewise; an object
+ * whose unclamped centre lies outside [0, image_size) is dropped (augment.encode_boxes_window). */
+int y2_encode_labels_window(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
+                            const double* params, int n, int max_obj, int image_size, int S, int num_class,
+                            float* labels, void* stream);
+
 /* ---- host utility: CRC-32C (Castagnoli) of a host buffer, continuing from `crc` (0 to start).  The checksum of
  *      TensorFlow's V2 checkpoint files (tensor bundle + table blocks), which the reference reads and writes through
  *      tf.train.Saver (src/yolo2_nets/net_utils.py:64-110); used by utils/tf_bundle.py on 100-MB tensors. */

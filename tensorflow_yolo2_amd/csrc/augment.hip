@@ -1,0 +1,281 @@
+// Training augmentation on the device-resident image pool (img_dataset/device_voc.py with an Augment): one launch makes
+// the finished uint8 BGR batch -- crop / pad window of the source, bilinear resize, mirror, hue / saturation / exposure
+// distortion -- and a second one the label grids whose boxes follow the window.  The specification is the host code of
+// img_dataset/augment.py (crop_resize_u8, distort_hsv_u8, encode_boxes_window) and both kernels are bit-equal to it:
+// resize coefficients in double in the specification's operation order (as data.hip), the colour stage in float32
+// with one correctly rounded operation per specification operation.  The file is compiled with -ffp-contract=off: a
+// fused multiply-add in x * 255 + 0.5 or 1 - s * f rounds once where the specification rounds twice.
+#include "data_common.h"
+using namespace y2;
+
+namespace {
+
+constexpr int kParams = 8;                      // double per batch slot: x0, y0, cw, ch, flip, hue, sat, exp
+// XCoef here: offsets CLAMPED into the source row (every address is readable whatever the window is), and above the
+// 11-bit weight (0 .. 2048) of w1 a flag where that pixel of the window lies outside the image and reads as the fill
+constexpr int kFillLeft = 1 << 12, kFillRight = 1 << 13;
+
+// a window coordinate of the parameter row as an integer of [lo, hi] (not a number -> lo)
+Y2_DEV int win_int(double v, int lo, int hi) { return (int)fmin(fmax(v, (double)lo), (double)hi); }
+
+// window index i -> source index x0 + i clamped into [0, n), and whether it was outside
+Y2_DEV int src_index(int x0, int i, int n, bool& outside) {
+    const long long s = (long long)x0 + i;
+    outside = s < 0 || s >= n;
+    return (int)min(max(s, 0LL), (long long)n - 1);
+}
+
+// one output pixel, b | g << 8 | r << 16: r0 / r1 are the two source rows (LDS or global), f0 / f1 say that the whole
+// row lies outside the image
+Y2_DEV uint32_t resize_pixel(const uint8_t* r0, const uint8_t* r1, const XCoef q, int wy1, bool f0, bool f1, int fill) {
+    const int wy0 = 2048 - wy1;
+    const int a0 = q.x0, a1 = a0 + q.dx;
+    const int wx1 = q.w1 & 4095, wx0 = 2048 - wx1;
+    const bool fl = q.w1 & kFillLeft, fr = q.w1 & kFillRight;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int v00 = (fl || f0) ? fill : (int)r0[a0 + c], v01 = (fr || f0) ? fill : (int)r0[a1 + c];
+        const int v10 = (fl || f1) ? fill : (int)r1[a0 + c], v11 = (fr || f1) ? fill : (int)r1[a1 + c];
+        const int top = v00 * wx0 + v01 * wx1;
+        const int bot = v10 * wx0 + v11 * wx1;
+        const int v = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;   // <= 255 * 2^22 + 2^21 < 2^31
+        packed |= (uint32_t)(v & 255) << (8 * c);
+    }
+    return packed;
+}
+
+Y2_DEV uint32_t to_u8(float x) { return (uint32_t)min(max((int)(x * 255.0f + 0.5f), 0), 255); }
+
+// distort_hsv_u8 of one pixel (b | g << 8 | r << 16); unit[c] = c / 255 in float32
+Y2_DEV uint32_t distort_pixel(uint32_t bgr, const float* unit, float hue6, float sat, float exp) {
+    const float b = unit[bgr & 255], g = unit[(bgr >> 8) & 255], r = unit[(bgr >> 16) & 255];
+    float v = fmaxf(fmaxf(r, g), b);
+    const float d = v - fminf(fminf(r, g), b);
+    float s = v == 0.0f ? 0.0f : d / (v == 0.0f ? 1.0f : v);
+    const float num = v == r ? g - b : (v == g ? b - r : r - g);
+    const float qd = num / (d == 0.0f ? 1.0f : d);
+    float h = v == r ? qd : (v == g ? 2.0f + qd : 4.0f + qd);
+    h = d == 0.0f ? 0.0f : h;
+    h = h + hue6;
+    h = h < 0.0f ? h + 6.0f : h;
+    h = h >= 6.0f ? h - 6.0f : h;
+    s = fminf(s * sat, 1.0f);
+    v = fminf(v * exp, 1.0f);
+    const float i = floorf(h), f = h - i;
+    const float p = v * (1.0f - s);
+    const float q = v * (1.0f - s * f);
+    const float t = v * (1.0f - s * (1.0f - f));
+    const float r2 = (i == 0.0f || i >= 5.0f) ? v : (i == 1.0f ? q : (i == 4.0f ? t : p));
+    const float g2 = i == 0.0f ? t : ((i == 1.0f || i == 2.0f) ? v : (i == 3.0f ? q : p));
+    const float b2 = i == 2.0f ? t : ((i == 3.0f || i == 4.0f) ? v : (i >= 5.0f ? q : p));
+    return to_u8(b2) | to_u8(g2) << 8 | to_u8(r2) << 16;
+}
+
+// `gr` output rows of `groups` * VEC pixels each.  STAGED: row j blends slots 2j and 2j + 1 of the LDS staging, `pitch`
+// bytes apart (rows outside the image were staged as fill); else it reads rows y[0] and y[1] of the image in place and
+// the row flags of y[3] select the fill.  Two instantiations, so that the staged one reads LDS with LDS instructions.
+template <int VEC, bool STAGED>
+Y2_DEV void produce_rows(const uint8_t* base, int64_t pitch, const XCoef* xt, const int (*yc)[4], const float* unit, int gr,
+                         int groups, bool colour, float hue6, float sat, float exp, int fill, uint8_t* obase,
+                         int rowbytes) {
+    const int total = gr * groups;
+    for (int k = threadIdx.x; k < total; k += kThreads) {
+        const int j = k / groups, px = (k - j * groups) * VEC;
+        const int* y = yc[j];
+        const uint8_t* r0 = STAGED ? base + (2 * j) * (int)pitch : base + (size_t)y[0] * pitch;
+        const uint8_t* r1 = STAGED ? base + (2 * j + 1) * (int)pitch : base + (size_t)y[1] * pitch;
+        const bool f0 = !STAGED && (y[3] & 1), f1 = !STAGED && (y[3] & 2);
+        uint32_t pix[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) pix[e] = resize_pixel(r0, r1, xt[px + e], y[2], f0, f1, fill);
+        if (colour) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) pix[e] = distort_pixel(pix[e], unit, hue6, sat, exp);
+        }
+        uint8_t* o = obase + (size_t)j * rowbytes + 3 * px;
+        if (VEC == 4) {                         // 12 bytes at a multiple of 12 of a 4-byte aligned batch
+            uint32_t* o32 = (uint32_t*)o;
+            o32[0] = pix[0] | pix[1] << 24;
+            o32[1] = pix[1] >> 8 | pix[2] << 16;
+            o32[2] = pix[2] >> 16 | pix[3] << 8;
+        } else {
+            o[0] = (uint8_t)pix[0];
+            o[1] = (uint8_t)(pix[0] >> 8);
+            o[2] = (uint8_t)(pix[0] >> 16);
+        }
+    }
+}
+
+// grid (ceil(out_h / kBand), n), the geometry of data.hip's resize kernel.  A workgroup owns kBand output rows of one
+// batch slot: the x coefficients of its window (mirrored when exactly one of the entry's and the row's flips is set)
+// and the c / 255 table are computed once into LDS; for every kRows output rows the 2 * kRows source rows they blend are
+// staged into LDS with 16-byte loads (a row outside the image is staged as fill bytes, without a load), and each lane
+// produces VEC whole pixels -- the colour stage needs the triple -- stored as 3 * VEC bytes (VEC = 4: three dwords).
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void augment_u8_kernel(const uint8_t* __restrict__ pool,
+                                                              const int64_t* __restrict__ table,
+                                                              const int32_t* __restrict__ index,
+                                                              const double* __restrict__ params, int out_h, int out_w,
+                                                              int fill, uint8_t* __restrict__ out) {
+    __shared__ XCoef xt[kMaxOutW];
+    __shared__ int yc[kBand][4];                // source rows (clamped), weight, bit 0 / 1: row 0 / 1 is outside
+    __shared__ float unit[256];
+    __shared__ __attribute__((aligned(16))) uint8_t rows[2 * kRows * kMaxPitch];
+    const int tid = threadIdx.x, img = blockIdx.y;
+    const int64_t* t = table + (size_t)kTable * (index ? index[img] : img);
+    const double* prm = params + (size_t)kParams * img;
+    const int64_t off = t[0], pitch64 = t[3];
+    const int H = (int)t[1], W = (int)t[2];
+    const int wx0 = win_int(prm[0], -(1 << 30), 1 << 30), wy0 = win_int(prm[1], -(1 << 30), 1 << 30);
+    const int cw = win_int(prm[2], 0, 1 << 30), ch = win_int(prm[3], 0, 1 << 30);
+    const bool flip = (t[4] != 0) != (prm[4] != 0.0);
+    const float hue = (float)prm[5], sat = (float)prm[6], exp = (float)prm[7];
+    const bool colour = !(hue == 0.0f && sat == 1.0f && exp == 1.0f);
+    const float hue6 = 6.0f * hue;
+    const int band0 = blockIdx.x * kBand, nrows = min(kBand, out_h - band0);
+    if (H < 1 || W < 1) return;                 // (an empty table row: nothing to read, as data.hip)
+    if (cw < 1 || ch < 1) {                     // no window (or not a number): the slot is all fill, its grid empty
+        uint8_t* o = out + ((size_t)img * out_h + band0) * 3 * out_w;
+        for (int i = tid; i < nrows * 3 * out_w; i += kThreads) o[i] = (uint8_t)fill;
+        return;
+    }
+    for (int x = tid; x < out_w; x += kThreads) {
+        int i0, i1, w1;
+        bool o0, o1;
+        lin_coef(flip ? out_w - 1 - x : x, cw, out_w, i0, i1, w1);
+        const int c0 = src_index(wx0, i0, W, o0), c1 = src_index(wx0, i1, W, o1);
+        xt[x] = XCoef{3 * c0, (short)(3 * (c1 - c0)), (short)(w1 | (o0 ? kFillLeft : 0) | (o1 ? kFillRight : 0))};
+    }
+    if (tid < nrows) {
+        int i0, i1, w1;
+        bool o0, o1;
+        lin_coef(band0 + tid, ch, out_h, i0, i1, w1);
+        yc[tid][0] = src_index(wy0, i0, H, o0);
+        yc[tid][1] = src_index(wy0, i1, H, o1);
+        yc[tid][2] = w1;
+        yc[tid][3] = (o0 ? 1 : 0) | (o1 ? 2 : 0);
+    }
+    unit[tid] = (float)tid / 255.0f;            // kThreads == 256
+    __syncthreads();
+    const bool staged = pitch64 <= kMaxPitch && ((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W;
+    const int pitch = (int)pitch64;
+    const uint8_t* src = pool + off;
+    const int rowbytes = 3 * out_w, groups = out_w / VEC;   // (VEC = 4 is launched for out_w % 4 == 0 only)
+    const uint32_t fill4 = 0x01010101u * (uint32_t)fill;
+    uint8_t* obase = out + ((size_t)img * out_h + band0) * rowbytes;
+    for (int g0 = 0; g0 < nrows; g0 += kRows) {
+        const int gr = min(kRows, nrows - g0);
+        if (staged) {
+            const int chunks = pitch >> 4;
+            for (int i = tid; i < 2 * gr * chunks; i += kThreads) {
+                const int slot = i / chunks, c = i - slot * chunks;
+                const int* y = yc[g0 + (slot >> 1)];
+                u32x4 v = {fill4, fill4, fill4, fill4};
+                if (!((y[3] >> (slot & 1)) & 1)) v = *(const u32x4*)(src + (size_t)y[slot & 1] * pitch64 + 16 * c);
+                *(u32x4*)(rows + slot * pitch + 16 * c) = v;
+            }
+            __syncthreads();
+        }
+        if (staged)
+            produce_rows<VEC, true>(rows, pitch, xt, yc + g0, unit, gr, groups, colour, hue6, sat, exp, fill,
+                                    obase + (size_t)g0 * rowbytes, rowbytes);
+        else
+            produce_rows<VEC, false>(src, pitch64, xt, yc + g0, unit, gr, groups, colour, hue6, sat, exp, fill,
+                                     obase + (size_t)g0 * rowbytes, rowbytes);
+        if (staged) __syncthreads();
+    }
+}
+
+// data.hip's label kernel with the boxes following the window: x = (bx - 1 - x0) * (image_size / cw), an object whose
+// unclamped centre leaves [0, image_size) is dropped, and the mirror is the entry's flip XOR the row's.
+__global__ __launch_bounds__(kThreads) void encode_labels_window_kernel(const double* __restrict__ boxes,
+                                                                        const int32_t* __restrict__ counts,
+                                                                        const int64_t* __restrict__ table,
+                                                                        const int32_t* __restrict__ index,
+                                                                        const double* __restrict__ params, int max_obj,
+                                                                        int image_size, int S, int num_class,
+                                                                        float* __restrict__ labels) {
+    const int img = blockIdx.x, D = 5 + num_class;
+    const size_t e = index ? (size_t)index[img] : (size_t)img;
+    float* g = labels + (size_t)img * S * S * D;
+    for (int i = threadIdx.x; i < S * S * D; i += kThreads) g[i] = 0.0f;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int64_t* t = table + kTable * e;
+    const double* prm = params + (size_t)kParams * img;
+    // the window as the image kernel reads it: integers (a fraction is cut off in both)
+    const double wx0 = win_int(prm[0], -(1 << 30), 1 << 30), wy0 = win_int(prm[1], -(1 << 30), 1 << 30);
+    const double cw = win_int(prm[2], 0, 1 << 30), ch = win_int(prm[3], 0, 1 << 30);
+    if (!(cw >= 1.0 && ch >= 1.0)) return;
+    const bool flip = (t[4] != 0) != (prm[4] != 0.0);
+    const double w_ratio = (double)image_size / cw, h_ratio = (double)image_size / ch;
+    const double hi = (double)(image_size - 1), size = (double)image_size;
+    const int cnt = min(max(counts[e], 0), max_obj);
+    const double* bx = boxes + e * (size_t)max_obj * 5;
+    for (int o = 0; o < cnt; ++o, bx += 5) {
+        double x1 = (bx[0] - 1 - wx0) * w_ratio, y1 = (bx[1] - 1 - wy0) * h_ratio;
+        double x2 = (bx[2] - 1 - wx0) * w_ratio, y2 = (bx[3] - 1 - wy0) * h_ratio;
+        const double ux = (x2 + x1) / 2.0, uy = (y2 + y1) / 2.0;
+        if (!(ux >= 0.0 && ux < size && uy >= 0.0 && uy < size)) continue;   // the centre left the window
+        x1 = hi < x1 ? hi : x1; x1 = 0.0 > x1 ? 0.0 : x1;
+        y1 = hi < y1 ? hi : y1; y1 = 0.0 > y1 ? 0.0 : y1;
+        x2 = hi < x2 ? hi : x2; x2 = 0.0 > x2 ? 0.0 : x2;
+        y2 = hi < y2 ? hi : y2; y2 = 0.0 > y2 ? 0.0 : y2;
+        const double cx = (x2 + x1) / 2.0, cy = (y2 + y1) / 2.0;
+        int x_ind = (int)(cx * S / image_size), y_ind = (int)(cy * S / image_size);
+        if (!(x_ind >= 0 && x_ind < S && y_ind >= 0 && y_ind < S)) continue;
+        if (flip) x_ind = S - 1 - x_ind;
+        float* cell = g + ((size_t)y_ind * S + x_ind) * D;
+        if (cell[0] == 1.0f) continue;
+        cell[0] = 1.0f;
+        cell[1] = (float)(flip ? hi - cx : cx);
+        cell[2] = (float)cy;
+        cell[3] = (float)(x2 - x1);
+        cell[4] = (float)(y2 - y1);
+        const int cls = (int)bx[4];
+        if (cls >= 0 && cls < num_class) cell[5 + cls] = 1.0f;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int y2_augment_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, const double* params, int n,
+                        int out_h, int out_w, int fill, uint8_t* out, void* stream) {
+    if (!pool || !table || !params || !out) return fail(Y2_ERR_ARG, "y2_augment_u8_batch: null pointer");
+    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "y2_augment_u8_batch: n = %d outside 1..65535", n);
+    if (out_h < 1 || out_w < 1) return fail(Y2_ERR_ARG, "y2_augment_u8_batch: output %d x %d", out_h, out_w);
+    if (out_w > kMaxOutW)
+        return fail(Y2_ERR_ARG, "y2_augment_u8_batch: out_w = %d beyond Y2_RESIZE_MAX_OUT_W = %d", out_w, kMaxOutW);
+    if (fill < 0 || fill > 255) return fail(Y2_ERR_ARG, "y2_augment_u8_batch: fill = %d outside 0..255", fill);
+    const dim3 grid((out_h + kBand - 1) / kBand, n);
+    if (out_w % 4 == 0 && ((uintptr_t)out & 3) == 0)
+        hipLaunchKernelGGL(augment_u8_kernel<4>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, params,
+                           out_h, out_w, fill, out);
+    else
+        hipLaunchKernelGGL(augment_u8_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, params,
+                           out_h, out_w, fill, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_augment_u8_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_encode_labels_window(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
+                            const double* params, int n, int max_obj, int image_size, int S, int num_class,
+                            float* labels, void* stream) {
+    if (!boxes || !counts || !table || !params || !labels)
+        return fail(Y2_ERR_ARG, "y2_encode_labels_window: null pointer");
+    if (n < 1) return fail(Y2_ERR_ARG, "y2_encode_labels_window: n = %d", n);
+    if (max_obj < 1 || image_size < 1 || S < 1 || num_class < 0 || S > 1024)
+        return fail(Y2_ERR_ARG, "y2_encode_labels_window: max_obj = %d, image_size = %d, S = %d, num_class = %d", max_obj,
+                    image_size, S, num_class);
+    hipLaunchKernelGGL(encode_labels_window_kernel, dim3(n), dim3(kThreads), 0, (hipStream_t)stream, boxes, counts,
+                       table, index, params, max_obj, image_size, S, num_class, labels);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_encode_labels_window: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+}  // extern "C"

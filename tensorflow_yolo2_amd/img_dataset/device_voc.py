@@ -8,6 +8,11 @@ call: both walk pascal_voc.ShardedOrder (one shuffle at start, stride sharding, 
 are bit-equal to the host resize and label encoder.  Not in the reference (one image size, cv2 on the host every step);
 what it serves is multi-scale training from real images (pascal_train_darknet.py --devkit ... --multi-scale).
 
+With `augment` (an img_dataset.augment.Augment) every sample of every batch gets a parameter row drawn on the host from
+the augmentation generator -- crop / pad window, mirror, hue / saturation / exposure -- and the two kernels are
+y2_augment_u8_batch and y2_encode_labels_window (csrc/augment.hip), bit-equal to augment.py; the batch order does not
+change, and the k-th get(size) still equals the k-th get_u8() of a host batcher built with the same arguments.
+
 Pool layout: image k starts at byte offset off[k] (a multiple of 16), rows pitch[k] = 3 * width rounded up to 16 bytes
 apart, BGR uint8; the bytes between 3 * width and the pitch are zero.  Entry table: int64 [entries][5] = {off, height,
 width, pitch, flip}; with `flipped` the entries are the images followed by their mirrored copies (same offset, flip = 1),
@@ -72,7 +77,7 @@ def _ptr(t):
 
 class DeviceVOC(ShardedOrder):
     def __init__(self, image_set, batch_size=None, devkit_path=None, flipped=None, seed=0, rank=0, world=1,
-                 device="cuda", max_pool_bytes=DEFAULT_MAX_POOL_BYTES):
+                 device="cuda", max_pool_bytes=DEFAULT_MAX_POOL_BYTES, augment=None):
         from .. import config as cfg
         self.name = 'voc_2007'
         self.devkit_path = devkit_path or os.path.join('data', 'VOCdevkit')
@@ -85,6 +90,10 @@ class DeviceVOC(ShardedOrder):
         self.image_set = image_set
         self.device = device
         self._init_order(seed, rank, world)
+        self.augment = augment
+        if augment is not None:
+            from .augment import generator
+            self.aug_rng = generator(seed, rank)            # its own stream: the batch order is that of augment=None
         self.image_index, self.entries = read_image_set(self.data_path, image_set)
         assert self.entries, "no image with objects in %s" % image_set
         self.offsets, self.pitches, self.pool_bytes = pool_layout([e['shape'] for e in self.entries])
@@ -104,6 +113,7 @@ class DeviceVOC(ShardedOrder):
         self.gt_labels = self._start_order(gt)
         self._check_ranks_agree()
         self._buffers = {}
+        self._params = {}
 
     # ---- the only places that touch device memory at start-up (torch supplies allocations and copies)
     def _alloc_pool(self, nbytes):
@@ -156,6 +166,8 @@ class DeviceVOC(ShardedOrder):
         from .. import _lib
         if torch.device(self.device).type != "cuda":
             raise RuntimeError("DeviceVOC.get needs the pool on the GPU (device=%r)" % (self.device,))
+        if self.augment is not None:
+            return self._get_augmented(size)
         images, labels, index = self.buffers(size)
         host = torch.from_numpy(np.array([self._next()['entry'] for _ in range(self.batch_size)], np.int32))
         index.copy_(host.pin_memory(), non_blocking=True)
@@ -166,4 +178,30 @@ class DeviceVOC(ShardedOrder):
         _lib.check(lib.y2_encode_labels(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
                                         self.batch_size, self.max_obj, size, size // 32, self.num_class, _ptr(labels),
                                         stream))
+        return images, labels
+
+    def _get_augmented(self, size):
+        """get(size) with one parameter row per sample, drawn in batch order and uploaded as the index is"""
+        import torch
+        from .. import _lib
+        from .augment import ROW
+        images, labels, index = self.buffers(size)
+        if size not in self._params:
+            self._params[size] = torch.empty((self.batch_size, ROW), dtype=torch.float64, device=self.device)
+        params = self._params[size]
+        entries = np.empty(self.batch_size, np.int32)
+        rows = np.empty((self.batch_size, ROW), np.float64)
+        n = len(self.entries)
+        for k in range(self.batch_size):
+            entries[k] = self._next()['entry']
+            rows[k] = self.augment.draw(self.aug_rng, *self.entries[entries[k] % n]['shape'])
+        index.copy_(torch.from_numpy(entries).pin_memory(), non_blocking=True)
+        params.copy_(torch.from_numpy(rows).pin_memory(), non_blocking=True)
+        lib = _lib.load()
+        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+        _lib.check(lib.y2_augment_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index), _ptr(params),
+                                           self.batch_size, size, size, self.augment.fill, _ptr(images), stream))
+        _lib.check(lib.y2_encode_labels_window(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
+                                               _ptr(params), self.batch_size, self.max_obj, size, size // 32,
+                                               self.num_class, _ptr(labels), stream))
         return images, labels

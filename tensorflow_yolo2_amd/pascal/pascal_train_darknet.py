@@ -23,7 +23,12 @@ the decoded images once in device memory, resize + flip + label grid by two kern
 the feeder: the same batches, bit for bit.  --multi-scale redraws the input size every --ms-period steps from --ms-sizes
 (trainer.multi_scale_size: identical on every rank): one graph per size over the SAME variables (reuse=True), one Adam
 state and loss scale; with --devkit it takes its batches from DeviceVOC at the step's size, without it from the synthetic
-generator."""
+generator.
+
+Augmentation (not in the reference; Darknet's yolov2-voc.cfg recipe, img_dataset/augment.py): --augment with --devkit
+draws a crop / pad window (--jitter), a mirror and a hue / saturation / exposure distortion for every sample of every
+batch, in the host batcher or -- with --device-data / --multi-scale -- in the device kernels: the same batches, bit for
+bit.  Every rank draws for its own shard from its own generator; nothing is exchanged."""
 import argparse
 import os
 
@@ -57,6 +62,12 @@ def parse_args(argv=None):
                     help="input size redrawn every --ms-period steps from --ms-sizes; with --devkit implies --device-data")
     ap.add_argument("--ms-sizes", default=",".join(str(v) for v in MULTI_SCALE_SIZES), help="comma-separated sizes")
     ap.add_argument("--ms-period", type=int, default=10)
+    ap.add_argument("--augment", action="store_true",
+                    help="with --devkit: random crop / pad window, mirror and HSV distortion of every sample")
+    ap.add_argument("--jitter", type=float, default=0.3, help="window edges move by up to this share of the image")
+    ap.add_argument("--hue", type=float, default=0.1, help="hue shift drawn from [-hue, hue] turns")
+    ap.add_argument("--saturation", type=float, default=1.5, help="saturation factor drawn from [1 / s, s]")
+    ap.add_argument("--exposure", type=float, default=1.5, help="exposure factor drawn from [1 / e, e]")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI, default) | gloo")
     ap.add_argument("--all-ranks-on-gpu0", action="store_true", help="functional test of the N > 1 path on one GPU")
     args = ap.parse_args(argv)
@@ -76,6 +87,15 @@ def parse_args(argv=None):
             args.device_data = True
     if args.device_data and not args.devkit:
         ap.error("--device-data needs --devkit")
+    args.augmentation = None
+    if args.augment:
+        if not args.devkit:
+            ap.error("--augment needs --devkit (the synthetic batches are not images)")
+        from ..img_dataset.augment import Augment
+        try:
+            args.augmentation = Augment(args.jitter, args.hue, args.saturation, args.exposure)
+        except ValueError as e:
+            ap.error("--augment: %s" % e)
     return args
 
 
@@ -100,12 +120,13 @@ def main(argv=None):
     if args.device_data:
         from ..img_dataset.device_voc import DeviceVOC
         imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
-                         rank=rank, world=world)
+                         rank=rank, world=world, augment=args.augmentation)
     elif args.devkit:
         from ..img_dataset.pascal_voc import pascal_voc
         from ..utils.feeder import DeviceFeeder
         imdb = pascal_voc(args.image_set, batch_size=args.batch, devkit_path=args.devkit, image_size=args.size,
-                          cell_size=args.size // 32, flipped=args.flipped, rank=rank, world=world)
+                          cell_size=args.size // 32, flipped=args.flipped, rank=rank, world=world,
+                          augment=args.augmentation)
         feeder = DeviceFeeder(lambda im, lab: imdb.get_u8(im, lab), args.batch, args.size, args.size // 32)
     graphs = {}
 
