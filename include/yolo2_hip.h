@@ -439,6 +439,37 @@ int y2_encode_labels_window(const double* boxes, const int32_t* counts, const in
                             const double* params, int n, int max_obj, int image_size, int S, int num_class,
                             float* labels, void* stream);
 
+/* ---- evaluation of the grid detector from the same pool (pascal/pascal_eval_darknet.py; utils/detect_batch.py is the
+ *      specification and both calls are bit-equal to it): per image, the head's output -> boxes in the pixels of the
+ *      ORIGINAL image after a score-ordered class-aware NMS, then the VOC devkit's matching against the image's ground
+ *      truth.  Not in the reference (it has no evaluation code).  Only the precision / recall curve, one sort across all
+ *      images, stays on the host (detect_batch.map_from_flags).  `table`, `index`, `boxes`, `counts` as above; each image
+ *      takes its height and width from its table row, and the flip column is not read (evaluation uses unmirrored
+ *      entries).  All pointers are device memory. */
+#define Y2_DETECT_MAX_CANDIDATES 1024 /* S * S * B of one image (608 x 608 with B = 2: 722); more is an argument error */
+#define Y2_MATCH_MAX_OBJECTS 1024     /* max_obj of the box table; more is an argument error */
+/* predict [n][S][S][num_class + 5 B] fp32.  Candidate i = cell * B + b (cell = row * S + column): the float64 products
+ * x, y, w, h of y2_decode_detections, upper left corner x - floor(w / 2), y - floor(h / 2), the inclusive box
+ * (ulx, uly, ulx + w - 1, uly + h - 1) cut to [0, width - 1] x [0, height - 1], then + 1 (the annotation's pixels are
+ * 1-based); class = first maximum of the class values; score = the confidence.  Valid: confidence > object_thresh (not
+ * NaN), the four products finite and below 2^30 in magnitude (checked before any conversion to int), and the cut box not
+ * empty.  The valid candidates are walked in descending score (ties: ascending i); a kept box suppresses every later box
+ * of the SAME class whose IoU with it (float64, + 1 extents) is > iou_thresh; at most max_out are kept.
+ * det int32 [n][max_out][6] = xmin, ymin, xmax, ymax, class, i (unused rows all -1); score [n][max_out] (unused 0);
+ * count int32 [n].  One workgroup per image. */
+int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32_t* index, int n, int S, int B,
+                         int num_class, float object_thresh, float iou_thresh, int max_out, int* det, float* score,
+                         int* count, void* stream);
+/* flags int32 [n][max_out]: 1 true positive, 0 false positive, 2 ignored, -1 beyond count.  The rows of an image are
+ * walked in order (descending score): among the image's objects of the row's class, the first maximum of the float64
+ * IoU, taken objects included; none, or IoU < iou_thresh: false positive; else a difficult object: ignored; an object
+ * not yet taken: true positive, and it is taken; else false positive (utils/voc_eval.eval_class for one image).
+ * `difficult`: uint8 [entries][max_obj].  `det` rows may come from any detector (columns 0..4 are read); `score` is not
+ * read and may be NULL.  One 64-lane wave per image. */
+int y2_voc_match_batch(const int* det, const float* score, const int* count, const double* boxes,
+                       const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
+                       int max_out, float iou_thresh, int* flags, void* stream);
+
 /* ---- host utility: CRC-32C (Castagnoli) of a host buffer, continuing from `crc` (0 to start).  The checksum of
  *      TensorFlow's V2 checkpoint files (tensor bundle + table blocks), which the reference reads and writes through
  *      tf.train.Saver (src/yolo2_nets/net_utils.py:64-110); used by utils/tf_bundle.py on 100-MB tensors. */

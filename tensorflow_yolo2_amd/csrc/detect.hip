@@ -1,0 +1,262 @@
+// Evaluation of the grid detector on the device (pascal/pascal_eval_darknet.py): per image, the head's output decoded
+// into boxes in the pixels of the ORIGINAL image, a score-ordered class-aware greedy NMS, and the VOC devkit's matching
+// of the surviving rows against the image's ground truth.  The specification is this repository's host code
+// (utils/detect_batch.py: grid_detect, match_image) and both kernels are bit-equal to it: the decoded products and every
+// IoU are float64 in the specification's operation order, and the file is compiled with -ffp-contract=off.  What stays
+// on the host is the per-class precision / recall curve, which needs one sort across all images (map_from_flags).
+#include "data_common.h"
+#include "kernels.h"
+using namespace y2;
+
+namespace {
+
+constexpr int kMaxCand = kDetectMaxCand;   // candidates (S * S * B) of one image; LDS below is sized for it: 29 KB
+
+// IoU of two inclusive pixel boxes with the devkit's +1 extents (utils/voc_eval.box_iou_voc): `a` is its `box`
+Y2_DEV double iou_voc(double a0, double a1, double a2, double a3, double b0, double b1, double b2, double b3) {
+    const double ixmin = fmax(b0, a0), iymin = fmax(b1, a1);
+    const double ixmax = fmin(b2, a2), iymax = fmin(b3, a3);
+    const double iw = fmax(ixmax - ixmin + 1.0, 0.0), ih = fmax(iymax - iymin + 1.0, 0.0);
+    const double inter = iw * ih;
+    const double uni = ((a2 - a0 + 1.0) * (a3 - a1 + 1.0) + (b2 - b0 + 1.0) * (b3 - b1 + 1.0)) - inter;
+    return inter / uni;
+}
+
+// grid (n), one workgroup per image, KP = the next power of two of K = S * S * B (at least 64) lanes.
+//   1. lane i decodes candidate i (cell i / B: row cell / S, column cell % S) into LDS: the clipped 1-based box, the
+//      class, and the sort key = confidence, or -inf for a candidate that is not valid (and for i >= K);
+//   2. bitonic sort of (key, index), descending key, ties by ascending index: the valid candidates come first;
+//   3. the order is walked: a row that is not suppressed is kept (lane 0 writes it) and suppresses, in parallel, every
+//      later row of its class with IoU > iou_thresh.  `kept` and sup[i] are uniform over the workgroup, so the barrier
+//      inside the branch is met by every lane.
+__global__ __launch_bounds__(kMaxCand) void detect_grid_kernel(const float* __restrict__ predict,
+                                                               const int64_t* __restrict__ table,
+                                                               const int32_t* __restrict__ index, int S, int B, int C,
+                                                               float object_thresh, float iou_thresh, int max_out,
+                                                               int KP, int* __restrict__ det, float* __restrict__ score,
+                                                               int* __restrict__ count) {
+    __shared__ float skey[kMaxCand];
+    __shared__ int sidx[kMaxCand];
+    __shared__ int bx0[kMaxCand], by0[kMaxCand], bx1[kMaxCand], by1[kMaxCand];
+    __shared__ int bcls[kMaxCand];
+    __shared__ unsigned char sup[kMaxCand];
+    __shared__ int s_valid;
+    const int img = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const int K = S * S * B, D = C + 5 * B;
+    const int64_t* t = table + (size_t)kTable * (index ? index[img] : img);
+    const int64_t h64 = t[1], w64 = t[2];
+    const bool sized = h64 >= 1 && w64 >= 1 && h64 <= 0x7fffffff && w64 <= 0x7fffffff;
+    const int im_h = sized ? (int)h64 : 1, im_w = sized ? (int)w64 : 1;
+    const float* pred = predict + (size_t)img * S * S * D;
+    if (tid == 0) s_valid = 0;
+    __syncthreads();
+    for (int i = tid; i < KP; i += nt) {
+        bool valid = false;
+        float conf = -INFINITY;
+        if (i < K && sized) {
+            const int cell = i / B, b = i - cell * B;
+            const int c = cell / S, r = cell - c * S;
+            const float* p = pred + (size_t)cell * D;
+            conf = p[C + b];
+            const float* pb = p + C + B + 4 * b;
+            const double xs = ((double)pb[0] + (double)r) / (double)S;   // decode_kernel's products (loss.hip)
+            const double ys = ((double)pb[1] + (double)c) / (double)S;
+            const float ws = pb[2] * pb[2], hs = pb[3] * pb[3];          // np.square on float32
+            const double dx = xs * (double)im_w, dy = ys * (double)im_h;
+            const double dw = (double)ws * (double)im_w, dh = (double)hs * (double)im_h;
+            const double lim = 1073741824.0;                             // 2^30: checked BEFORE any conversion to int
+            valid = conf > object_thresh && fabs(dx) < lim && fabs(dy) < lim && fabs(dw) < lim && fabs(dh) < lim;
+            if (valid) {
+                const int x = (int)dx, y = (int)dy, w = (int)dw, h = (int)dh;   // w, h >= 0: floor(w / 2) = w >> 1
+                const int ulx = x - (w >> 1), uly = y - (h >> 1);
+                const int xmin = max(ulx, 0), ymin = max(uly, 0);
+                const int xmax = min(ulx + w - 1, im_w - 1), ymax = min(uly + h - 1, im_h - 1);
+                valid = xmax >= xmin && ymax >= ymin;
+                int cls = 0;
+                float best = p[0];
+                for (int k = 1; k < C; ++k)
+                    if (p[k] > best) {
+                        best = p[k];
+                        cls = k;
+                    }
+                bx0[i] = xmin + 1; by0[i] = ymin + 1; bx1[i] = xmax + 1; by1[i] = ymax + 1;
+                bcls[i] = cls;
+            }
+        }
+        skey[i] = valid ? conf : -INFINITY;
+        sidx[i] = i;
+        sup[i] = 0;
+        if (valid) atomicAdd(&s_valid, 1);
+    }
+    __syncthreads();
+    for (int k = 2; k <= KP; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < KP; i += nt) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const float a = skey[i], b = skey[l];
+                    const int ia = sidx[i], ib = sidx[l];
+                    const bool a_first = (a > b) || (a == b && ia < ib);   // a precedes b in the final order
+                    const bool desc = (i & k) == 0;
+                    if (desc ? !a_first : a_first) {
+                        skey[i] = b; skey[l] = a;
+                        sidx[i] = ib; sidx[l] = ia;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    // a valid key is > object_thresh >= -inf, so the valid candidates are exactly the first s_valid of the order
+    const int nvalid = s_valid;
+    const double thr = (double)iou_thresh;
+    int* drow = det + (size_t)img * max_out * 6;
+    float* srow = score + (size_t)img * max_out;
+    int kept = 0;
+    for (int i = 0; i < nvalid && kept < max_out; ++i) {
+        if (sup[i]) continue;
+        const int o = sidx[i];
+        const int ac = bcls[o];
+        const double a0 = bx0[o], a1 = by0[o], a2 = bx1[o], a3 = by1[o];
+        if (tid == 0) {
+            int* d = drow + (size_t)kept * 6;
+            d[0] = bx0[o]; d[1] = by0[o]; d[2] = bx1[o]; d[3] = by1[o]; d[4] = ac; d[5] = o;
+            srow[kept] = skey[i];
+        }
+        for (int j = i + 1 + tid; j < nvalid; j += nt) {
+            if (sup[j]) continue;
+            const int q = sidx[j];
+            if (bcls[q] != ac) continue;
+            if (iou_voc(a0, a1, a2, a3, bx0[q], by0[q], bx1[q], by1[q]) > thr) sup[j] = 1;
+        }
+        ++kept;
+        __syncthreads();
+    }
+    if (tid == 0) count[img] = kept;
+    for (int i = kept * 6 + tid; i < max_out * 6; i += nt) drow[i] = -1;
+    for (int i = kept + tid; i < max_out; i += nt) srow[i] = 0.0f;
+}
+
+// first maximum over the wave of (iou, object index): the larger iou, ties to the lower index
+Y2_DEV void wave_first_max(double& best, int& arg) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const double ob = __shfl_xor(best, off, kWave);
+        const int oa = __shfl_xor(arg, off, kWave);
+        if (ob > best || (ob == best && oa < arg)) {
+            best = ob;
+            arg = oa;
+        }
+    }
+}
+
+// grid (n), ONE 64-lane wave per image.  Lane l holds objects l, l + 64, ... of the image (the first one in registers,
+// the others re-read through the cache: VOC images have at most 42 objects) with their `difficult` and `taken` bits in
+// two 16-bit masks (max_obj <= 1024).  The detections are walked in row order; each step is a wave-wide first maximum
+// of the float64 IoU over the objects of the detection's class, and the lane that owns the winner settles the flag.
+__global__ __launch_bounds__(kWave) void voc_match_kernel(const int* __restrict__ det, const int* __restrict__ count,
+                                                          const double* __restrict__ boxes,
+                                                          const int32_t* __restrict__ counts,
+                                                          const uint8_t* __restrict__ difficult,
+                                                          const int32_t* __restrict__ index, int max_obj, int max_out,
+                                                          float iou_thresh, int* __restrict__ flags) {
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const size_t e = index ? (size_t)index[img] : (size_t)img;
+    const int cnt = min(max(counts[e], 0), max_obj);
+    const int ndet = min(max(count[img], 0), max_out);
+    const double* bx = boxes + e * (size_t)max_obj * 5;
+    const uint8_t* df = difficult + e * (size_t)max_obj;
+    const int strides = (cnt + kWave - 1) / kWave;
+    unsigned hard = 0, taken = 0;
+    for (int k = 0; k < strides; ++k) {
+        const int j = lane + kWave * k;
+        if (j < cnt && df[j]) hard |= 1u << k;
+    }
+    double g0 = 0, g1 = 0, g2 = 0, g3 = 0, gc = -1.0;
+    if (lane < cnt) {
+        g0 = bx[lane * 5 + 0]; g1 = bx[lane * 5 + 1]; g2 = bx[lane * 5 + 2]; g3 = bx[lane * 5 + 3]; gc = bx[lane * 5 + 4];
+    }
+    const double thr = (double)iou_thresh;
+    const int* drow = det + (size_t)img * max_out * 6;
+    int* frow = flags + (size_t)img * max_out;
+    for (int d = 0; d < ndet; ++d) {
+        const double d0 = drow[d * 6 + 0], d1 = drow[d * 6 + 1], d2 = drow[d * 6 + 2], d3 = drow[d * 6 + 3];
+        const double dc = drow[d * 6 + 4];
+        double best = -1.0;
+        int arg = 0x7fffffff;
+        if (lane < cnt && gc == dc) {
+            best = iou_voc(d0, d1, d2, d3, g0, g1, g2, g3);
+            arg = lane;
+        }
+        for (int k = 1; k < strides; ++k) {
+            const int j = lane + kWave * k;
+            if (j < cnt && bx[j * 5 + 4] == dc) {
+                const double v = iou_voc(d0, d1, d2, d3, bx[j * 5 + 0], bx[j * 5 + 1], bx[j * 5 + 2], bx[j * 5 + 3]);
+                if (v > best || arg == 0x7fffffff) {           // (ascending j: the strict > keeps the lane's first maximum)
+                    best = v;
+                    arg = j;
+                }
+            }
+        }
+        wave_first_max(best, arg);
+        int flag = 0;
+        if (arg != 0x7fffffff && best >= thr) {                // uniform: every lane holds the winner
+            const int owner = arg & (kWave - 1);
+            const unsigned bit = 1u << (arg / kWave);
+            int mine = 0;
+            if (lane == owner) {
+                if (hard & bit) mine = 2;
+                else if (!(taken & bit)) {
+                    mine = 1;
+                    taken |= bit;
+                }
+            }
+            flag = __shfl(mine, owner, kWave);
+        }
+        if (lane == 0) frow[d] = flag;
+    }
+    for (int d = ndet + lane; d < max_out; d += kWave) frow[d] = -1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32_t* index, int n, int S, int B,
+                         int num_class, float object_thresh, float iou_thresh, int max_out, int* det, float* score,
+                         int* count, void* stream) {
+    if (!predict || !table || !det || !score || !count) return fail(Y2_ERR_ARG, "y2_detect_grid_batch: null pointer");
+    if (n < 1) return fail(Y2_ERR_ARG, "y2_detect_grid_batch: n = %d", n);
+    if (max_out < 1) return fail(Y2_ERR_ARG, "y2_detect_grid_batch: max_out = %d", max_out);
+    if (S < 1 || B < 1 || num_class < 1 || S > kMaxCand || B > kMaxCand)
+        return fail(Y2_ERR_ARG, "y2_detect_grid_batch: S = %d, B = %d, num_class = %d", S, B, num_class);
+    if (S * S * B > kMaxCand)
+        return fail(Y2_ERR_ARG, "y2_detect_grid_batch: S * S * B = %d candidates beyond Y2_DETECT_MAX_CANDIDATES = %d",
+                    S * S * B, kMaxCand);
+    int KP = kWave;
+    while (KP < S * S * B) KP <<= 1;
+    hipLaunchKernelGGL(detect_grid_kernel, dim3(n), dim3(KP), 0, (hipStream_t)stream, predict, table, index, S, B,
+                       num_class, object_thresh, iou_thresh, max_out, KP, det, score, count);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_grid_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_voc_match_batch(const int* det, const float* score, const int* count, const double* boxes,
+                       const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
+                       int max_out, float iou_thresh, int* flags, void* stream) {
+    (void)score;   // the rows arrive in descending score (y2_detect_grid_batch, y2_nms): the order is all that is used
+    if (!det || !count || !boxes || !counts || !difficult || !flags)
+        return fail(Y2_ERR_ARG, "y2_voc_match_batch: null pointer");
+    if (n < 1) return fail(Y2_ERR_ARG, "y2_voc_match_batch: n = %d", n);
+    if (max_out < 1) return fail(Y2_ERR_ARG, "y2_voc_match_batch: max_out = %d", max_out);
+    if (max_obj < 1 || max_obj > kMatchMaxObj)
+        return fail(Y2_ERR_ARG, "y2_voc_match_batch: max_obj = %d outside 1..Y2_MATCH_MAX_OBJECTS = %d", max_obj,
+                    kMatchMaxObj);
+    hipLaunchKernelGGL(voc_match_kernel, dim3(n), dim3(kWave), 0, (hipStream_t)stream, det, count, boxes, counts,
+                       difficult, index, max_obj, max_out, iou_thresh, flags);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_voc_match_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "../../include/yolo2_hip.h"
 
 namespace y2 {
 
@@ -670,6 +671,10 @@ hipError_t launch_momentum_guarded(float* p, float* acc, const float* g, size_t 
 hipError_t launch_init_trunc_normal(float* p, size_t n, float stddev, uint64_t seed, uint64_t stream_id,
                                     hipStream_t s);
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
+
+// ---- evaluation of the grid detector (detect.hip): the limits its LDS arrays and bit masks are sized for
+constexpr int kDetectMaxCand = Y2_DETECT_MAX_CANDIDATES;   // candidates of one image in y2_detect_grid_batch
+constexpr int kMatchMaxObj = Y2_MATCH_MAX_OBJECTS;         // objects of one image in y2_voc_match_batch (16 per lane)
 
 // per-(device, stream) scratch of the graph-level operators (split partial sums); grows on demand, never shrinks
 void* op_scratch(hipStream_t s, size_t bytes);

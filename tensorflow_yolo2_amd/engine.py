@@ -847,6 +847,59 @@ def nms(boxes, scores, classes=None, iou_thresh=0.5, score_thresh=0.0, max_out=1
     return keep, count
 
 
+def detect_grid_batch(predict, table, index=None, num_class=20, B=2, object_thresh=0.005, iou_thresh=0.45, max_out=100,
+                      out=None):
+    """predict [n,S,S,num_class+5B] fp32, table int64 [entries][5] (DeviceVOC.table), index int32 [n] or None ->
+    (det int32 [n,max_out,6] = xmin, ymin, xmax, ymax, class, candidate (-1 rows beyond count), score [n,max_out],
+    count int32 [n]), device tensors: boxes in the 1-based pixels of each ORIGINAL image after the class-aware NMS
+    (utils/detect_batch.grid_detect, bit for bit).  `out` = (det, score, count) writes into caller tensors."""
+    lib = _lib.load()
+    assert predict.is_cuda and predict.dtype == torch.float32 and predict.is_contiguous() and predict.dim() == 4
+    n, S = predict.shape[0], predict.shape[1]
+    assert tuple(predict.shape) == (n, S, S, num_class + 5 * B), predict.shape
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert table.shape[0] >= n
+    if out is None:
+        out = (torch.empty((n, max_out, 6), dtype=torch.int32, device=predict.device),
+               torch.empty((n, max_out), dtype=torch.float32, device=predict.device),
+               torch.empty((n,), dtype=torch.int32, device=predict.device))
+    det, score, count = out
+    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * max_out * 6
+    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * max_out
+    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n
+    check(lib.y2_detect_grid_batch(_ptr(predict), _ptr(table), _ptr(index), n, S, B, num_class, float(object_thresh),
+                                   float(iou_thresh), int(max_out), _ptr(det), _ptr(score), _ptr(count), _stream()))
+    return det, score, count
+
+
+def voc_match_batch(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):
+    """det int32 [n,max_out,6], score [n,max_out], count [n] (detect_grid_batch); boxes float64 [entries,max_obj,5],
+    counts int32 [entries], difficult uint8 [entries,max_obj] (DeviceVOC) -> flags int32 [n,max_out]: 1 true positive,
+    0 false positive, 2 ignored, -1 beyond count (utils/detect_batch.match_image, bit for bit)"""
+    lib = _lib.load()
+    assert det.is_cuda and det.dtype == torch.int32 and det.is_contiguous() and det.dim() == 3 and det.shape[2] == 6
+    n, max_out = det.shape[0], det.shape[1]
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == n
+    assert score is None or (score.dtype == torch.float32 and score.is_contiguous() and score.numel() == n * max_out)
+    assert boxes.is_cuda and boxes.dtype == torch.float64 and boxes.is_contiguous() and boxes.dim() == 3
+    max_obj = boxes.shape[1]
+    assert boxes.shape[2] == 5 and counts.dtype == torch.int32 and counts.numel() == boxes.shape[0]
+    assert difficult.is_cuda and difficult.dtype == torch.uint8 and difficult.is_contiguous()
+    assert tuple(difficult.shape) == (boxes.shape[0], max_obj), difficult.shape
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert boxes.shape[0] >= n
+    flags = torch.empty((n, max_out), dtype=torch.int32, device=det.device) if out is None else out
+    assert flags.is_contiguous() and flags.dtype == torch.int32 and flags.numel() == n * max_out
+    check(lib.y2_voc_match_batch(_ptr(det), _ptr(score), _ptr(count), _ptr(boxes), _ptr(counts), _ptr(difficult),
+                                 _ptr(index), n, max_obj, max_out, float(iou_thresh), _ptr(flags), _stream()))
+    return flags
+
+
 def softmax_cross_entropy(logits, labels, need_grad=True):
     """sparse_softmax_cross_entropy_with_logits + reduce_mean (imagenet_train_darknet.py:51-53)."""
     lib = _lib.load()

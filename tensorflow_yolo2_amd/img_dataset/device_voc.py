@@ -17,7 +17,12 @@ Pool layout: image k starts at byte offset off[k] (a multiple of 16), rows pitch
 apart, BGR uint8; the bytes between 3 * width and the pitch are zero.  Entry table: int64 [entries][5] = {off, height,
 width, pitch, flip}; with `flipped` the entries are the images followed by their mirrored copies (same offset, flip = 1),
 the order of pascal_voc.prepare.  Box table: float64 [entries][max_obj][5] = xmin, ymin, xmax, ymax, class index in
-annotation order, and int32 counts [entries]."""
+annotation order, and int32 counts [entries].
+
+Evaluation (pascal/pascal_eval_darknet.py) reads the same pool: eval_batch(size, start) resizes the entries start,
+start + 1, ... in LIST order with y2_resize_bilinear_u8_batch alone and leaves the shuffled cursor of get() where it is;
+`difficult`, uint8 [entries][max_obj] parallel to the box table, goes to the device at its first use (training never
+reads it).  Evaluation wants the plain list: a data set with `flipped` or `augment` refuses."""
 import ctypes as C
 import os
 import zlib
@@ -63,6 +68,18 @@ def build_tables(entries, offsets, pitches, flipped):
     return table, boxes, counts
 
 
+def build_difficult(entries, max_obj, flipped):
+    """uint8 [E][max_obj]: the `difficult` flag of every object of the box table (0 beyond an entry's count)"""
+    n = len(entries)
+    out = np.zeros((n * (2 if flipped else 1), max_obj), np.uint8)
+    for k, e in enumerate(entries):
+        d = e.get('difficult', ())
+        out[k, :len(d)] = np.asarray(d, np.uint8)
+    if flipped:
+        out[n:] = out[:n]
+    return out
+
+
 def padded_rows(img, pitch):
     """[H, W, 3] uint8 -> [H, pitch] uint8, zero bytes after 3 * W"""
     h, w = img.shape[:2]
@@ -102,6 +119,8 @@ class DeviceVOC(ShardedOrder):
                               % (self.pool_bytes, len(self.entries), max_pool_bytes))
         table, boxes, counts = build_tables(self.entries, self.offsets, self.pitches, self.flipped)
         self.max_obj = boxes.shape[1]
+        self.difficult_host = build_difficult(self.entries, self.max_obj, self.flipped)
+        self._difficult = None
         self.pool = self._alloc_pool(self.pool_bytes)
         for e, off, pitch in zip(self.entries, self.offsets, self.pitches):
             img = imread_bgr(e['imname'])                  # decoded ONCE; no host copy is kept
@@ -114,6 +133,7 @@ class DeviceVOC(ShardedOrder):
         self._check_ranks_agree()
         self._buffers = {}
         self._params = {}
+        self._eval_buffers = {}
 
     # ---- the only places that touch device memory at start-up (torch supplies allocations and copies)
     def _alloc_pool(self, nbytes):
@@ -179,6 +199,43 @@ class DeviceVOC(ShardedOrder):
                                         self.batch_size, self.max_obj, size, size // 32, self.num_class, _ptr(labels),
                                         stream))
         return images, labels
+
+    @property
+    def difficult(self):
+        """uint8 [entries][max_obj] on the device, uploaded at the first use"""
+        if self._difficult is None:
+            self._difficult = self._upload(self.difficult_host)
+        return self._difficult
+
+    def eval_batch(self, size, start):
+        """(images [B, size, size, 3] uint8 BGR, valid): entries start .. start + B - 1 of the image list IN LIST ORDER,
+        resized on the current stream; the last batch repeats its final entry to fill the fixed batch and `valid` is the
+        number of slots that are entries of their own.  `eval_index` is the int32 [B] device tensor of the slots' entries
+        (the `index` of the detect and match calls).  The cursor of get() is neither read nor moved."""
+        import torch
+        from .. import _lib
+        if self.flipped or self.augment is not None:
+            raise ValueError("evaluation reads the plain image list: build the DeviceVOC with flipped=False, augment=None")
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("DeviceVOC.eval_batch needs the pool on the GPU (device=%r)" % (self.device,))
+        if size < 32 or size % 32:
+            raise ValueError("size %r is not a positive multiple of 32" % (size,))
+        n = len(self.entries)
+        if not 0 <= start < n:
+            raise IndexError("start = %r outside the %d entries" % (start, n))
+        if size not in self._eval_buffers:
+            self._eval_buffers[size] = (
+                torch.empty((self.batch_size, size, size, 3), dtype=torch.uint8, device=self.device),
+                torch.empty(self.batch_size, dtype=torch.int32, device=self.device))
+        images, index = self._eval_buffers[size]
+        valid = min(self.batch_size, n - start)
+        host = torch.from_numpy(np.minimum(np.arange(start, start + self.batch_size), n - 1).astype(np.int32))
+        index.copy_(host.pin_memory(), non_blocking=True)
+        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+        _lib.check(_lib.load().y2_resize_bilinear_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index),
+                                                           self.batch_size, size, size, _ptr(images), stream))
+        self.eval_index = index
+        return images, valid
 
     def _get_augmented(self, size):
         """get(size) with one parameter row per sample, drawn in batch order and uploaded as the index is"""

@@ -56,6 +56,20 @@ def parse_annotation(xml_path_or_text, im_shape=None):
     return objs, (int(im_shape[0]), int(im_shape[1]))
 
 
+def parse_difficult(xml_path_or_text):
+    """the <difficult> flag (0 / 1) of every object in annotation order, parallel to parse_annotation's list; an object
+    without the element counts as 0.  The reference never reads it (no evaluation); the devkit's protocol needs it."""
+    text = xml_path_or_text
+    if "<annotation" not in text:
+        with open(xml_path_or_text) as f:
+            text = f.read()
+    out = []
+    for obj in ET.fromstring(text).findall('object'):
+        d = obj.find('difficult')
+        out.append(1 if d is not None and d.text is not None and int(d.text.strip() or 0) else 0)
+    return out
+
+
 def load_pascal_annotation(xml_path_or_text, image_size, cell_size, im_shape=None):
     """(label [S,S,25], number of objects)"""
     objs, im_shape = parse_annotation(xml_path_or_text, im_shape)
@@ -64,8 +78,9 @@ def load_pascal_annotation(xml_path_or_text, image_size, cell_size, im_shape=Non
 
 def read_image_set(data_path, image_set):
     """The image list of pascal_voc.load_labels (:87-124) without the encoding: (image_index, entries), one entry
-    {'imname', 'objs', 'shape': (height, width)} per image of ImageSets/Main/<image_set>.txt that has objects
-    (images without any are dropped, :116-118), in list order."""
+    {'imname', 'objs', 'shape': (height, width), 'difficult'} per image of ImageSets/Main/<image_set>.txt that has
+    objects (images without any are dropped, :116-118), in list order.  'difficult' is a list of 0 / 1 parallel to
+    'objs' (parse_difficult): training ignores it as the reference does, the evaluation needs it."""
     import os
     txtname = os.path.join(data_path, 'ImageSets', 'Main', image_set + '.txt')
     assert os.path.exists(txtname), 'Path does not exist: {}'.format(txtname)
@@ -82,7 +97,9 @@ def read_image_set(data_path, image_set):
         objs, shape = parse_annotation(xml, im_shape=(h, w))
         if len(objs) == 0:
             continue
-        entries.append({'imname': imname, 'objs': objs, 'shape': shape})
+        difficult = parse_difficult(xml)
+        assert len(difficult) == len(objs), xml
+        entries.append({'imname': imname, 'objs': objs, 'shape': shape, 'difficult': difficult})
     return image_index, entries
 
 

@@ -1,0 +1,146 @@
+"""Batched evaluation of the grid detector: the host specification of csrc/detect.hip (numpy only).
+
+NOT in the reference (it has no evaluation code; SURVEY 8 a-x2).  Three functions, the per-image two of which the
+kernels y2_detect_grid_batch and y2_voc_match_batch reproduce bit for bit, as img_dataset/augment.py is the
+specification of csrc/augment.hip:
+
+  grid_detect     one image's head output -> boxes in the 1-based pixels of the ORIGINAL image, after a score-ordered,
+                  class-aware greedy NMS.  The decode is show_yolo_detection's (oracle/loss_ref.decode_detections,
+                  csrc/loss.hip: decode_kernel) and the box is utils/voc_eval.detections_from_decode's.
+  match_image     the body of utils/voc_eval.eval_class for one image: a TP / FP / ignored flag per detection.
+  map_from_flags  the global part: per class a stable sort by score, cumulative sums, utils/voc_eval.average_precision.
+
+The split works because the devkit's matching is independent per image: a ground-truth box and its `taken` bit belong
+to one image, so the flag of a detection depends only on the detections of its own image and class that rank before
+it.  grid_detect returns an image's rows in descending score, which is the order eval_class meets them in; then
+map_from_flags(rows of all images in image order) equals voc_eval.voc_map of the same detections, as floats.
+
+Preconditions shared with the kernels (outside them the two sides may differ): the class values of a cell are not NaN
+(the kernel's strict `>` walk skips a NaN, np.argmax returns it) and the box table holds finite boxes."""
+import numpy as np
+
+from . import voc_eval
+
+LIMIT = float(1 << 30)     # a decoded product at or beyond it (or not finite) drops the candidate before any int()
+
+
+def grid_candidates(predict, im_w, im_h, num_class, B, object_thresh):
+    """every candidate of one image, before the ordering and the NMS:
+    (valid bool [K], box int64 [K][4] = 1-based xmin, ymin, xmax, ymax (zero where not valid), cls int64 [K],
+    score float32 [K]), K = S * S * B, candidate i = cell * B + b, cell = row * S + column"""
+    predict = np.asarray(predict, np.float32)
+    S = predict.shape[0]
+    assert predict.shape == (S, S, num_class + 5 * B), predict.shape
+    im_w, im_h = int(im_w), int(im_h)
+    cells = predict.reshape(S * S, num_class + 5 * B)
+    K = S * S * B
+    cell = np.arange(K) // B
+    b = np.arange(K) % B
+    row, col = cell // S, cell % S
+    score = cells[cell, num_class + b]                                    # float32
+    pb = cells[:, num_class + B:].reshape(S * S, B, 4)[cell, b]           # float32 [K][4]
+    with np.errstate(all="ignore"):
+        dx = (pb[:, 0].astype(np.float64) + col) / float(S) * im_w
+        dy = (pb[:, 1].astype(np.float64) + row) / float(S) * im_h
+        dw = np.square(pb[:, 2]).astype(np.float64) * im_w                # np.square on float32, the product in float64
+        dh = np.square(pb[:, 3]).astype(np.float64) * im_h
+        prod = np.stack([dx, dy, dw, dh], axis=1)
+        valid = score > np.float32(object_thresh)                         # (a NaN confidence compares false)
+        valid &= (np.isfinite(prod) & (np.abs(prod) < LIMIT)).all(axis=1)
+    prod = np.where(valid[:, None], prod, 0.0)
+    x, y, w, h = (np.trunc(prod[:, k]).astype(np.int64) for k in range(4))   # int(): toward zero
+    ulx, uly = x - w // 2, y - h // 2
+    xmin, ymin = np.maximum(ulx, 0), np.maximum(uly, 0)                   # the box cut to the image: 0 .. im_w - 1
+    xmax, ymax = np.minimum(ulx + w - 1, im_w - 1), np.minimum(uly + h - 1, im_h - 1)
+    valid &= (xmax >= xmin) & (ymax >= ymin)
+    box = np.stack([xmin, ymin, xmax, ymax], axis=1) + 1                  # the annotation's pixels are 1-based
+    box = np.where(valid[:, None], box, 0)
+    first = cells[:, :num_class]
+    with np.errstate(all="ignore"):
+        cls = np.where(np.isnan(first[:, 0]), 0, np.argmax(np.where(np.isnan(first), -np.inf, first), axis=1))[cell]
+    return valid, box, cls.astype(np.int64), score
+
+
+def grid_detect(predict, im_w, im_h, num_class, B, object_thresh, iou_thresh, max_out):
+    """predict float32 [S][S][num_class + 5 B] of ONE image -> (det int32 [count][6] = xmin, ymin, xmax, ymax, class,
+    candidate index; score float32 [count]), count <= max_out, rows in descending score (ties: ascending index)"""
+    valid, box, cls, score = grid_candidates(predict, im_w, im_h, num_class, B, object_thresh)
+    idx = np.nonzero(valid)[0]
+    order = idx[np.lexsort((idx, -score[idx].astype(np.float64)))]        # score descending, then index ascending
+    thresh = float(np.float32(iou_thresh))                                # the C ABI passes float
+    suppressed = np.zeros(order.size, bool)
+    keep = []
+    for k in range(order.size):
+        if len(keep) >= max_out:
+            break
+        if suppressed[k]:
+            continue
+        i = order[k]
+        keep.append(i)
+        later = order[k + 1:]
+        if later.size:
+            with np.errstate(all="ignore"):
+                iou = voc_eval.box_iou_voc(box[i], box[later])
+            suppressed[k + 1:] |= (cls[later] == cls[i]) & (iou > thresh)
+    keep = np.asarray(keep, np.int64)
+    det = np.concatenate([box[keep], cls[keep, None], keep[:, None]], axis=1).astype(np.int32).reshape(-1, 6)
+    return det, score[keep].astype(np.float32)
+
+
+def match_image(det, gt_boxes, gt_difficult, iou_thresh=0.5):
+    """det int [k][>= 5] = xmin, ymin, xmax, ymax, class in descending score; gt_boxes float64 [m][5] = xmin, ymin,
+    xmax, ymax, class (a row of DeviceVOC's box table); gt_difficult [m] -> int32 [k]: 1 true positive, 0 false
+    positive, 2 ignored (the object is difficult)"""
+    det = np.asarray(det)
+    det = det.reshape(-1, det.shape[-1]) if det.size else det.reshape(0, 6)
+    gt = np.asarray(gt_boxes, np.float64).reshape(-1, 5)
+    difficult = np.asarray(gt_difficult).reshape(-1).astype(bool)
+    taken = np.zeros(len(gt), bool)
+    thresh = float(np.float32(iou_thresh))
+    flags = np.zeros(len(det), np.int32)
+    for k, d in enumerate(det):
+        objs = np.nonzero(gt[:, 4] == float(d[4]))[0]
+        if not objs.size:
+            continue
+        with np.errstate(all="ignore"):
+            ious = voc_eval.box_iou_voc((int(d[0]), int(d[1]), int(d[2]), int(d[3])), gt[objs, :4])
+        j = int(ious.argmax())                                            # first maximum, taken objects included
+        if not float(ious[j]) >= thresh:
+            continue
+        j = objs[j]
+        if difficult[j]:
+            flags[k] = 2
+        elif not taken[j]:
+            flags[k] = 1
+            taken[j] = True
+    return flags
+
+
+def npos_from_objects(classes, difficult):
+    """{class: number of non-difficult objects} over the classes that have ground truth at all (a class whose objects
+    are all difficult is evaluated, with 0), from parallel sequences over every object of the image set"""
+    npos = {}
+    for c, d in zip(classes, difficult):
+        npos[int(c)] = npos.get(int(c), 0) + (0 if d else 1)
+    return npos
+
+
+def map_from_flags(rows, npos, use_07_metric=True):
+    """rows = (class [N], score [N], flag [N]) of the detections of all images IN IMAGE ORDER, each image's in
+    match_image's order; npos: {class: non-difficult objects} with one key per class that has ground truth (or a
+    sequence indexed by class: the classes with npos > 0) -> (mAP over those classes, {class: AP}), as
+    voc_eval.voc_map"""
+    cls, score, flag = (np.asarray(a).reshape(-1) for a in rows)
+    if not isinstance(npos, dict):
+        npos = {c: int(n) for c, n in enumerate(npos) if n > 0}
+    eps = np.finfo(np.float64).eps
+    aps = {}
+    for c in sorted(npos):
+        sel = (cls == c) & (flag != 2)
+        order = np.argsort(-score[sel].astype(np.float64), kind="stable")
+        f = flag[sel][order]
+        ctp, cfp = np.cumsum((f == 1).astype(np.float64)), np.cumsum((f == 0).astype(np.float64))
+        recall = ctp / max(npos[c], 1)
+        precision = ctp / np.maximum(ctp + cfp, eps)
+        aps[c] = voc_eval.average_precision(recall, precision, use_07_metric)
+    return (float(np.mean(list(aps.values()))) if aps else 0.0), aps
