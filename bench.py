@@ -4,17 +4,23 @@
 batch 64 per GPU, synthetic inputs resident in HBM (BASELINE.json configs[3]; the
 metric is quoted on fwd+bwd at 416x416, which fits one GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W            # the headline figure and nothing else
+    python bench.py --gpus N --steps K --warmup W --full     # ... and every other leg described below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of one of the --steps timed steps.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: `value`, `ms_per_step` and the
+`roofline` of the timed region (its event brackets are part of the timed steps).  Everything that takes steps of its own
+runs under `--full` only, after the timed region, and is then switched leg by leg with the --no-* / --*-steps options:
+the serialised per-class pass (`kernels`), `sustained`, `fed_input`, the other BASELINE.json configurations
+(`c1_detect`, `c2_forward`, `c3_classifier`, `c5_resnet50`), `f32_mode`, `parity_fast_mode*` and `cpu_baseline`.
 `--dump-outputs DIR` writes what the last timed step returned (loss[5], ious, object mask; the forward output with
 --forward-only) and a fixed, seeded sample of the parameters it updated as DIR/<name>.npy (float32): the inputs are
 seeded, so two builds run with the same arguments can be compared output for output.
 `roofline` is for the dominant kernel (the MFMA
 implicit-GEMM convolution: forward, dgrad and wgrad launches): algorithmic FLOPs of those
 launches / the union of their HIP-event intervals, measured on the launch streams inside the timed region.
-`cpu_baseline` is the oracle's PyTorch-CPU restatement of the same train step on a
+`cpu_baseline` (--full) is the oracle's PyTorch-CPU restatement of the same train step on a
 bounded sample (rank 0, N=1 only) -- "port", NOT the TF1 reference, which cannot run here.
 """
 import argparse
@@ -590,7 +596,13 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="images per GPU")
     ap.add_argument("--image-size", type=int, default=416)
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "f32", "f16x2", "f16x2f"])
-    ap.add_argument("--kernel-events", default="timed", choices=["timed", "separate", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg that takes steps of its own: per-class kernel pass, "
+                         "sustained, fed input, the other configurations, f32 / parity modes, CPU baseline (the --no-* and "
+                         "--*-steps options below choose among them); off: the headline figure only")
+    ap.add_argument("--kernel-events", default="timed", choices=["timed", "separate", "off"],
+                    help="timed: bracket the MFMA launches of every --event-stride-th timed step; separate (--full only): "
+                         "no brackets in the timed steps, the serialised pass alone; off: none")
     ap.add_argument("--event-stride", type=int, default=10, help="bracket the MFMA launches of every n-th timed step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8)     # bs 8
@@ -617,6 +629,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.model != "detector":
         ap.error("--dump-outputs: --model detector only")
+    if args.kernel_events == "separate" and not args.full:
+        ap.error("--kernel-events separate measures in a pass of its own: add --full")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -700,7 +714,7 @@ def main():
     # convolutions: forward, dgrad and weight gradient, 63 of ~150 launches per step) so that the
     # measurement does not cost the step ~6 %.  The weight gradients run on a side stream beside the
     # dgrads, so the kernel time is the UNION of the launch intervals (y2_profile_busy), not their sum.
-    # A second, untimed and serialised pass brackets every launch for the per-class table.
+    # A second, untimed and serialised pass brackets every launch for the per-class table (--full).
     # Events cost ~3 us per bracketed launch (they break back-to-back dispatch), so only every
     # `--event-stride`-th step of the timed region is bracketed; the roofline uses those steps.
     stride = max(1, args.event_stride)
@@ -734,7 +748,7 @@ def main():
     prof = net.profile_collect() if args.kernel_events == "timed" else None
     net.profile_enable(0)
     prof_all = None
-    if args.kernel_events in ("timed", "separate"):
+    if args.full and args.kernel_events in ("timed", "separate"):
         net.profile_enable(1)
         for _ in range(args.steps):
             run()
@@ -744,7 +758,7 @@ def main():
         if prof is None:
             prof = prof_all
 
-    sus = sustained(run, sync_all, args.sustain_steps, bs, world) if args.sustain_steps > 0 else None
+    sus = sustained(run, sync_all, args.sustain_steps, bs, world) if args.full and args.sustain_steps > 0 else None
     if dist is not None:
         t = torch.tensor([elapsed] + ([sus["ms_per_step"]] if sus else []), dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -779,10 +793,11 @@ def main():
                 roof["avg_launch_ms"] = t_igemm * 1e3 * psteps / max(n_launch, 1)
                 roof["launches_per_step"] = n_launch / psteps
                 roof["bracketed_steps"] = psteps
+        if prof_all is not None:    # the serialised pass ran args.steps steps with every launch bracketed
             kernels = {k: {"ms_per_step": v[0] / args.steps, "launches_per_step": v[1] / args.steps}
-                       for k, v in (prof_all or prof).items()}
-            if not args.forward_only and (prof_all or prof)["wgrad"][0] > 0:
-                kernels["wgrad"]["tflops"] = fwd_igemm / ((prof_all or prof)["wgrad"][0] / args.steps * 1e-3) / 1e12
+                       for k, v in prof_all.items()}
+            if not args.forward_only and prof_all["wgrad"][0] > 0:
+                kernels["wgrad"]["tflops"] = fwd_igemm / (prof_all["wgrad"][0] / args.steps * 1e-3) / 1e12
         # HBM traffic of the same kernels from the committed rocprofv3 PMC passes (separate
         # FETCH_SIZE / WRITE_SIZE runs, FETCH doubled per the gfx950 correction), bytes per launch
         try:
@@ -827,12 +842,12 @@ def main():
             out["timed_steps_skipped_by_overflow_guard"] = st1[2] - st0[2]
         if sus is not None:
             out["sustained"] = sus
-        if world == 1 and not args.forward_only and args.fed_steps > 0:
+        if args.full and world == 1 and not args.forward_only and args.fed_steps > 0:
             try:
                 out["fed_input"] = fed_input(args, tr, device, ms_per_step)
             except Exception as e:
                 out["fed_input"] = {"error": repr(e)}
-        if world == 1 and not args.forward_only and not args.no_extra_legs:
+        if args.full and world == 1 and not args.forward_only and not args.no_extra_legs:
             del tr, net, run
             torch.cuda.empty_cache()
             tr = net = run = None
@@ -843,7 +858,7 @@ def main():
                 except Exception as e:
                     out[key] = {"error": repr(e)}
                 torch.cuda.empty_cache()
-        if world == 1 and not args.forward_only and not args.no_f32_mode and args.dtype != "f32":
+        if args.full and world == 1 and not args.forward_only and not args.no_f32_mode and args.dtype != "f32":
             try:
                 tr = net = run = None
                 torch.cuda.empty_cache()
@@ -853,14 +868,14 @@ def main():
         # the reference-tolerance legs on the f16 pipe: `parity_fast_mode` = the fastest mode that holds the exact-f32 mode's
         # whole-step gates (round 6: f16x2f); `parity_fast_mode_f16x2` = round 5's all-split mode, for continuity
         for key, dt in (("parity_fast_mode", "f16x2f"), ("parity_fast_mode_f16x2", "f16x2")):
-            if world == 1 and not args.forward_only and not args.no_fast_parity_mode and args.dtype != dt:
+            if args.full and world == 1 and not args.forward_only and not args.no_fast_parity_mode and args.dtype != dt:
                 try:
                     tr = net = run = None
                     torch.cuda.empty_cache()
                     out[key] = f32_mode(args, images, labels, device, total_flops, igemm_flops, dtype=dt)
                 except Exception as e:
                     out[key] = {"dtype": dt, "ms_per_step": None, "error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and not args.forward_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.forward_only:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, spec_core, spec_head)
             except Exception as e:  # the baseline must never take the GPU number down with it
