@@ -460,6 +460,19 @@ int y2_encode_labels_window(const double* boxes, const int32_t* counts, const in
 int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32_t* index, int n, int S, int B,
                          int num_class, float object_thresh, float iou_thresh, int max_out, int* det, float* score,
                          int* count, void* stream);
+/* The same for the YOLOv2 anchor head, from its RAW output (pascal/pascal_eval_yolov2.py; specification:
+ * utils/detect_batch.anchor_detect on the outputs of y2_decode_anchors + y2_class_argmax, bit for bit).
+ * net [n][S][S][B][5 + num_class] fp32 (tx, ty, tw, th, to, class logits), anchors [B][2] in cell units (device memory).
+ * Candidate i = cell * B + b: cx, cy, w, h relative to the image and score[c] = sigmoid(to) * softmax(logits)[c] exactly
+ * as y2_decode_anchors forms them in float32; class = first maximum of score[c], score = that maximum.  The float64
+ * products cx * width, cy * height, w * width, h * height (the resize is a plain stretch) then go the way of
+ * y2_detect_grid_batch: validity (score > score_thresh), truncation, corner, cut, + 1, ordering, class-aware walk, and the
+ * same det / score / count conventions.  S * S * B up to Y2_DETECT_ANCHOR_MAX_CANDIDATES, B up to 16.  One workgroup per
+ * image, one launch. */
+#define Y2_DETECT_ANCHOR_MAX_CANDIDATES 2048 /* 608 x 608 with B = 5: 1805; more is an argument error */
+int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
+                           int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out, int* det,
+                           float* score, int* count, void* stream);
 /* flags int32 [n][max_out]: 1 true positive, 0 false positive, 2 ignored, -1 beyond count.  The rows of an image are
  * walked in order (descending score): among the image's objects of the row's class, the first maximum of the float64
  * IoU, taken objects included; none, or IoU < iou_thresh: false positive; else a difficult object: ignored; an object

@@ -1,4 +1,5 @@
-// Evaluation of the grid detector on the device (pascal/pascal_eval_darknet.py): per image, the head's output decoded
+// Evaluation of the detectors on the device (pascal/pascal_eval_darknet.py, pascal/pascal_eval_yolov2.py): per image, the
+// head's output (the grid head's, or the raw anchor head's: detect_anchor_kernel, specified by anchor_detect) decoded
 // into boxes in the pixels of the ORIGINAL image, a score-ordered class-aware greedy NMS, and the VOC devkit's matching
 // of the surviving rows against the image's ground truth.  The specification is this repository's host code
 // (utils/detect_batch.py: grid_detect, match_image) and both kernels are bit-equal to it: the decoded products and every
@@ -6,6 +7,7 @@
 // on the host is the per-class precision / recall curve, which needs one sort across all images (map_from_flags).
 #include "data_common.h"
 #include "kernels.h"
+#include "anchor_decode.h"
 using namespace y2;
 
 namespace {
@@ -136,6 +138,139 @@ __global__ __launch_bounds__(kMaxCand) void detect_grid_kernel(const float* __re
     for (int i = kept + tid; i < max_out; i += nt) srow[i] = 0.0f;
 }
 
+// ---- the anchor (YOLOv2) head: y2_detect_anchor_batch --------------------------------------------------------------
+constexpr int kAnchorMaxCand = kDetectAnchorMaxCand;   // S * S * B of one image: 19 * 19 * 5 = 1805 at 608 x 608
+constexpr int kAnchorLanes = 1024;                     // the workgroup; above it a lane owns two decode and sort slots
+constexpr int kAnchorSlotBytes = 8 + 5 * 4 + 1;        // sort word, four corners, class, suppressed flag
+
+// (score, candidate) as one 64-bit word whose unsigned order is "score descending, then index ascending" read from the
+// top: the float's bits made monotonic in the high half, ~index in the low half.  The words of a workgroup are distinct
+// (the indices are), so the sort needs one compare.  A valid score is sigmoid * softmax >= +0 or it is not kept at all,
+// so -0.0 and +0.0, equal as floats but not as bits, never meet.
+Y2_DEV uint64_t sort_word(float key, int idx) {
+    const uint32_t u = __float_as_uint(key);
+    const uint32_t m = u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+    return ((uint64_t)m << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
+}
+Y2_DEV int word_index(uint64_t w) { return (int)(0xffffffffu - (uint32_t)w); }
+Y2_DEV float word_key(uint64_t w) {
+    const uint32_t m = (uint32_t)(w >> 32);
+    return __uint_as_float(m ^ ((m >> 31) ? 0x80000000u : 0xffffffffu));
+}
+
+// grid (n), one workgroup per image of min(KP, 1024) lanes, KP = the next power of two of K = S * S * B (64 .. 2048).
+//   1. slot i = lane + 1024 r is decoded from the raw head (anchor_decode.h: the values of y2_decode_anchors +
+//      y2_class_argmax), taken to the pixels of the original image in float64 and cut, as detect_grid_kernel does;
+//   2. bitonic sort of the 64-bit words, one compare-exchange PAIR per lane and pass (KP / 2 pairs: at 2048 slots every
+//      lane of the 1024 works in every pass).  LDS is one array per field, and a lane's slots are 1024 apart, so the lanes
+//      of a wave touch consecutive words: a pass reads and writes whole 256-byte bank rows for j >= 32 and meets at most
+//      2 lanes per bank below that (pair p -> slot 2 (p - p % j) + p % j), against 2 everywhere for adjacent slots per lane;
+//   3. detect_grid_kernel's walk: `kept` and sup[] are uniform, one barrier per kept row, none per suppressed row.
+__global__ __launch_bounds__(kAnchorLanes) void detect_anchor_kernel(const float* __restrict__ net,
+                                                                     const float* __restrict__ anchors,
+                                                                     const int64_t* __restrict__ table,
+                                                                     const int32_t* __restrict__ index, int S, int B, int C,
+                                                                     float score_thresh, float iou_thresh, int max_out,
+                                                                     int KP, int* __restrict__ det,
+                                                                     float* __restrict__ score, int* __restrict__ count) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // kAnchorSlotBytes per slot: 58 KB at 2048
+    uint64_t* sword = (uint64_t*)smem;
+    int* bx0 = (int*)(sword + KP);
+    int *by0 = bx0 + KP, *bx1 = by0 + KP, *by1 = bx1 + KP, *bcls = by1 + KP;
+    unsigned char* sup = (unsigned char*)(bcls + KP);
+    __shared__ int s_valid;
+    const int img = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const int K = S * S * B, D = 5 + C;
+    const int64_t* t = table + (size_t)kTable * (index ? index[img] : img);
+    const int64_t h64 = t[1], w64 = t[2];
+    const bool sized = h64 >= 1 && w64 >= 1 && h64 <= 0x7fffffff && w64 <= 0x7fffffff;
+    const int im_h = sized ? (int)h64 : 1, im_w = sized ? (int)w64 : 1;
+    const float* rows = net + (size_t)img * K * D;
+    if (tid == 0) s_valid = 0;
+    __syncthreads();
+    for (int i = tid; i < KP; i += nt) {
+        bool valid = false;
+        float best = -INFINITY;
+        if (i < K && sized) {
+            const int cell = i / B, b = i - cell * B;
+            const int row = cell / S, col = cell - row * S;
+            const float* p = rows + (size_t)i * D;
+            const AnchorBox bx = anchor_decode_box(p, anchors, b, row, col, S);
+            float mx, sum;
+            anchor_softmax_norm(p, C, mx, sum);
+            int cls = 0;
+            best = anchor_class_score(p, 0, bx.so, mx, sum);              // class_argmax_kernel: the first maximum
+            for (int c = 1; c < C; ++c) {
+                const float v = anchor_class_score(p, c, bx.so, mx, sum);
+                if (v > best) {
+                    best = v;
+                    cls = c;
+                }
+            }
+            const double dx = (double)bx.cx * (double)im_w, dy = (double)bx.cy * (double)im_h;
+            const double dw = (double)bx.w * (double)im_w, dh = (double)bx.h * (double)im_h;
+            const double lim = 1073741824.0;                              // 2^30: checked BEFORE any conversion to int
+            valid = best > score_thresh && fabs(dx) < lim && fabs(dy) < lim && fabs(dw) < lim && fabs(dh) < lim;
+            if (valid) {
+                const int x = (int)dx, y = (int)dy, w = (int)dw, h = (int)dh;   // >> 1 on an int is floor(. / 2)
+                const int ulx = x - (w >> 1), uly = y - (h >> 1);
+                const int xmin = max(ulx, 0), ymin = max(uly, 0);
+                const int xmax = min(ulx + w - 1, im_w - 1), ymax = min(uly + h - 1, im_h - 1);
+                valid = xmax >= xmin && ymax >= ymin;
+                bx0[i] = xmin + 1; by0[i] = ymin + 1; bx1[i] = xmax + 1; by1[i] = ymax + 1;
+                bcls[i] = cls;
+            }
+        }
+        sword[i] = sort_word(valid ? best : -INFINITY, i);
+        sup[i] = 0;
+        if (valid) atomicAdd(&s_valid, 1);
+    }
+    __syncthreads();
+    for (int k = 2; k <= KP; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int pr = tid; pr < (KP >> 1); pr += nt) {
+                const int lo = pr & (j - 1);
+                const int i = ((pr - lo) << 1) | lo, l = i | j;
+                const uint64_t a = sword[i], b = sword[l];
+                const bool desc = (i & k) == 0;
+                if (desc ? a < b : a > b) {
+                    sword[i] = b;
+                    sword[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    // a valid score is > score_thresh >= -inf, so the valid candidates are exactly the first s_valid of the order
+    const int nvalid = s_valid;
+    const double thr = (double)iou_thresh;
+    int* drow = det + (size_t)img * max_out * 6;
+    float* srow = score + (size_t)img * max_out;
+    int kept = 0;
+    for (int i = 0; i < nvalid && kept < max_out; ++i) {
+        if (sup[i]) continue;
+        const uint64_t wd = sword[i];
+        const int o = word_index(wd);
+        const int ac = bcls[o];
+        const double a0 = bx0[o], a1 = by0[o], a2 = bx1[o], a3 = by1[o];
+        if (tid == 0) {
+            int* d = drow + (size_t)kept * 6;
+            d[0] = bx0[o]; d[1] = by0[o]; d[2] = bx1[o]; d[3] = by1[o]; d[4] = ac; d[5] = o;
+            srow[kept] = word_key(wd);
+        }
+        for (int j = i + 1 + tid; j < nvalid; j += nt) {
+            if (sup[j]) continue;
+            const int q = word_index(sword[j]);
+            if (bcls[q] != ac) continue;
+            if (iou_voc(a0, a1, a2, a3, bx0[q], by0[q], bx1[q], by1[q]) > thr) sup[j] = 1;
+        }
+        ++kept;
+        __syncthreads();
+    }
+    if (tid == 0) count[img] = kept;
+    for (int i = kept * 6 + tid; i < max_out * 6; i += nt) drow[i] = -1;
+    for (int i = kept + tid; i < max_out; i += nt) srow[i] = 0.0f;
+}
+
 // first maximum over the wave of (iou, object index): the larger iou, ties to the lower index
 Y2_DEV void wave_first_max(double& best, int& arg) {
 #pragma unroll
@@ -238,6 +373,30 @@ int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32
                        num_class, object_thresh, iou_thresh, max_out, KP, det, score, count);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_grid_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
+                           int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out, int* det,
+                           float* score, int* count, void* stream) {
+    if (!net || !anchors || !table || !det || !score || !count)
+        return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: null pointer");
+    if (n < 1) return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: n = %d", n);
+    if (max_out < 1) return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: max_out = %d", max_out);
+    if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
+        return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: S = %d, B = %d (at most 16), num_class = %d", S, B, num_class);
+    if (S * S * B > kAnchorMaxCand)
+        return fail(Y2_ERR_ARG,
+                    "y2_detect_anchor_batch: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d",
+                    S * S * B, kAnchorMaxCand);
+    int KP = kWave;
+    while (KP < S * S * B) KP <<= 1;
+    const int lanes = KP < kAnchorLanes ? KP : kAnchorLanes;
+    hipLaunchKernelGGL(detect_anchor_kernel, dim3(n), dim3(lanes), (size_t)KP * kAnchorSlotBytes, (hipStream_t)stream,
+                       net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh, max_out, KP, det, score,
+                       count);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_anchor_batch: %s", hipGetErrorString(e));
     return Y2_OK;
 }
 

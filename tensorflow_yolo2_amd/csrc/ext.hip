@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include "common.h"
 #include "kernels.h"
+#include "anchor_decode.h"
 #include "../../include/yolo2_hip.h"
 
 #include <stdarg.h>
@@ -117,18 +118,14 @@ __global__ void decode_anchors_kernel(const float* __restrict__ net, const float
     const int cell = (i / B) % (S * S);
     const int row = cell / S, col = cell % S;
     const float* p = net + (size_t)i * (5 + C);
-    const float sx = 1.f / (1.f + expf(-p[0])), sy = 1.f / (1.f + expf(-p[1]));
-    const float so = 1.f / (1.f + expf(-p[4]));
-    const float fs = (float)S;
-    boxes[(size_t)i * 4 + 0] = (sx + (float)col) / fs;
-    boxes[(size_t)i * 4 + 1] = (sy + (float)row) / fs;
-    boxes[(size_t)i * 4 + 2] = anchors[2 * b] * expf(p[2]) / fs;
-    boxes[(size_t)i * 4 + 3] = anchors[2 * b + 1] * expf(p[3]) / fs;
-    float mx = p[5];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[5 + c]);
-    float sum = 0.f;
-    for (int c = 0; c < C; ++c) sum += expf(p[5 + c] - mx);
-    for (int c = 0; c < C; ++c) scores[(size_t)i * C + c] = so * (expf(p[5 + c] - mx) / sum);
+    const AnchorBox bx = anchor_decode_box(p, anchors, b, row, col, S);    // anchor_decode.h: shared with detect.hip
+    boxes[(size_t)i * 4 + 0] = bx.cx;
+    boxes[(size_t)i * 4 + 1] = bx.cy;
+    boxes[(size_t)i * 4 + 2] = bx.w;
+    boxes[(size_t)i * 4 + 3] = bx.h;
+    float mx, sum;
+    anchor_softmax_norm(p, C, mx, sum);
+    for (int c = 0; c < C; ++c) scores[(size_t)i * C + c] = anchor_class_score(p, c, bx.so, mx, sum);
 }
 
 // ---------------------------------------------------------------------------

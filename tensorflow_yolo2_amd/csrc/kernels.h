@@ -674,6 +674,7 @@ hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);
 
 // ---- evaluation of the grid detector (detect.hip): the limits its LDS arrays and bit masks are sized for
 constexpr int kDetectMaxCand = Y2_DETECT_MAX_CANDIDATES;   // candidates of one image in y2_detect_grid_batch
+constexpr int kDetectAnchorMaxCand = Y2_DETECT_ANCHOR_MAX_CANDIDATES;   // ... in y2_detect_anchor_batch
 constexpr int kMatchMaxObj = Y2_MATCH_MAX_OBJECTS;         // objects of one image in y2_voc_match_batch (16 per lane)
 
 // per-(device, stream) scratch of the graph-level operators (split partial sums); grows on demand, never shrinks

@@ -875,6 +875,39 @@ def detect_grid_batch(predict, table, index=None, num_class=20, B=2, object_thre
     return det, score, count
 
 
+def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None):
+    """net [n,S,S,B,5+C] fp32 (the RAW YOLOv2 head), anchors [B,2] in cell units (a float32 device tensor, or anything
+    numpy reads: uploaded here), table / index as detect_grid_batch -> the same (det, score, count): decode, class choice,
+    boxes in the 1-based pixels of each ORIGINAL image and the class-aware NMS in one launch
+    (utils/detect_batch.anchor_detect on decode_anchors + class_argmax of the same net, bit for bit)"""
+    lib = _lib.load()
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, S, _, B, d = net.shape
+    assert net.shape[2] == S and d > 5, net.shape
+    if torch.is_tensor(anchors):
+        an = anchors
+        assert an.is_cuda and an.dtype == torch.float32 and an.is_contiguous()
+    else:
+        an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
+    assert an.numel() == 2 * B, (tuple(an.shape), B)
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert table.shape[0] >= n
+    if out is None:
+        out = (torch.empty((n, max_out, 6), dtype=torch.int32, device=net.device),
+               torch.empty((n, max_out), dtype=torch.float32, device=net.device),
+               torch.empty((n,), dtype=torch.int32, device=net.device))
+    det, score, count = out
+    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * max_out * 6
+    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * max_out
+    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n
+    check(lib.y2_detect_anchor_batch(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, d - 5, float(score_thresh),
+                                     float(iou_thresh), int(max_out), _ptr(det), _ptr(score), _ptr(count), _stream()))
+    return det, score, count
+
+
 def voc_match_batch(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):
     """det int32 [n,max_out,6], score [n,max_out], count [n] (detect_grid_batch); boxes float64 [entries,max_obj,5],
     counts int32 [entries], difficult uint8 [entries,max_obj] (DeviceVOC) -> flags int32 [n,max_out]: 1 true positive,

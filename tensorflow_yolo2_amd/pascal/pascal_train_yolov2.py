@@ -1,0 +1,155 @@
+"""Train the YOLOv2 anchor detector (yolo2_nets/yolov2.py; not in the reference, whose trainer is the grid model) on VOC:
+    python -m tensorflow_yolo2_amd.pascal.pascal_train_yolov2 --devkit data/VOCdevkit --iters 20 \
+        [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR]
+The flags are pascal_train_darknet.py's where they apply.  The batches always come from the device-resident pool
+(img_dataset.device_voc.DeviceVOC.get(size)): the uint8 batch goes straight into YOLOv2Trainer.step, whose first layer
+converts it, and the label grid [N,S,S,5+C] (one box per cell) is the anchor loss's input as it stands.  --multi-scale
+redraws the size of iteration i from --ms-sizes every --ms-period iterations (trainer.multi_scale_size); --augment is
+Darknet's crop / mirror / HSV recipe in the device kernels.
+
+Snapshots are `train_iter_<i>.npz` (net_utils.save_yolov2_variables: the three stacks, the anchors, the three Adam
+states with their one loss scaler); a run with --ckpt-dir resumes from the latest, moves the data order and the
+augmentation stream to where the saved run stood, and so continues it.  Without a snapshot, --imagenet-ckpt-dir takes
+the Darknet-19 backbone from the latest classifier snapshot there.  --anchors kmeans clusters the image set's boxes
+(utils/anchors.py) instead of using the published VOC anchors; a resumed run keeps its snapshot's anchors.
+
+One process, one GPU."""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from .. import config as cfg
+from ..utils.timer import Timer
+from ..yolo2_nets import net_utils, yolov2
+
+
+def parse_args(argv=None):
+    from ..trainer import MULTI_SCALE_SIZES
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--batch", type=int, default=24)
+    ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--dtype", default="f16")
+    ap.add_argument("--devkit", required=True, help="VOCdevkit directory (cfg.PASCAL_PATH)")
+    ap.add_argument("--image-set", default="trainval")
+    ap.add_argument("--flipped", action="store_true", help="cfg.FLIPPED: append horizontally flipped copies")
+    ap.add_argument("--multi-scale", action="store_true", help="input size redrawn every --ms-period iterations")
+    ap.add_argument("--ms-sizes", default=",".join(str(v) for v in MULTI_SCALE_SIZES), help="comma-separated sizes")
+    ap.add_argument("--ms-period", type=int, default=10)
+    ap.add_argument("--augment", action="store_true", help="random crop / pad window, mirror and HSV distortion")
+    ap.add_argument("--jitter", type=float, default=0.3, help="window edges move by up to this share of the image")
+    ap.add_argument("--hue", type=float, default=0.1, help="hue shift drawn from [-hue, hue] turns")
+    ap.add_argument("--saturation", type=float, default=1.5, help="saturation factor drawn from [1 / s, s]")
+    ap.add_argument("--exposure", type=float, default=1.5, help="exposure factor drawn from [1 / e, e]")
+    ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_<i>.npz snapshots: resume from the latest")
+    ap.add_argument("--save-every", type=int, default=40000)
+    ap.add_argument("--imagenet-ckpt-dir", default=None, help="classifier snapshots to take the backbone from")
+    ap.add_argument("--anchors", default="voc", choices=("voc", "kmeans"),
+                    help="voc: the published VOC anchors; kmeans: cluster the image set's boxes at --size")
+    ap.add_argument("--width-div", type=int, default=1, help="divide every inner width (tests)")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    if args.size < 32 or args.size % 32:
+        ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
+    if args.batch < 1 or args.iters < 0 or args.save_every < 1 or args.width_div < 1:
+        ap.error("--batch, --save-every and --width-div must be at least 1, --iters at least 0")
+    try:
+        args.ms_sizes = tuple(int(v) for v in str(args.ms_sizes).split(",") if v.strip())
+    except ValueError:
+        ap.error("--ms-sizes %r is not a comma-separated list of integers" % (args.ms_sizes,))
+    if args.multi_scale:
+        bad = [v for v in args.ms_sizes if v < 32 or v % 32]
+        if not args.ms_sizes or bad:
+            ap.error("--ms-sizes: the detector head cannot take %s (positive multiples of 32 only)" % (bad or "an empty list"))
+        if args.ms_period < 1:
+            ap.error("--ms-period must be at least 1")
+    args.augmentation = None
+    if args.augment:
+        from ..img_dataset.augment import Augment
+        try:
+            args.augmentation = Augment(args.jitter, args.hue, args.saturation, args.exposure)
+        except ValueError as e:
+            ap.error("--augment: %s" % e)
+    return args
+
+
+def step_size(args, i):
+    """input size of training iteration i (1-based, counted over resumed runs): a function of the flags alone"""
+    if not args.multi_scale:
+        return args.size
+    from ..trainer import multi_scale_size
+    return multi_scale_size(i, args.ms_sizes, args.ms_period)
+
+
+def skip_batches(imdb, batches):
+    """move a fresh DeviceVOC to where it stands after `batches` calls of get(): the order's cursor and reshuffles, and
+    one augmentation row per sample (a row's draws do not depend on the output size)"""
+    n = len(imdb.entries)
+    for _ in range(batches * imdb.batch_size):
+        e = imdb._next()['entry']
+        if imdb.augment is not None:
+            imdb.augment.draw(imdb.aug_rng, *imdb.entries[e % n]['shape'])
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from ..img_dataset.device_voc import DeviceVOC
+    imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
+                     seed=args.seed, augment=args.augmentation)
+    latest = None
+    if args.ckpt_dir:
+        os.makedirs(args.ckpt_dir, exist_ok=True)
+        sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
+        latest = sfiles[-1] if sfiles else None
+    if latest:
+        anchors = net_utils.read_yolov2_meta(latest)[0]
+    elif args.anchors == "kmeans":
+        from ..utils import anchors as A
+        wh = A.box_table_wh(imdb.boxes, imdb.counts, imdb.table, args.size, entries=len(imdb.entries))
+        anchors = A.kmeans_anchors(wh, k=len(yolov2.ANCHORS_VOC), seed=args.seed)
+        # cell units at --size; the loss and the decode read anchors in cells of whatever size a step runs at
+        print("k-means anchors at {:d} (mean shape IoU {:.4f}): {}".format(
+            args.size, A.mean_shape_iou(wh, anchors), np.round(anchors, 4).tolist()))
+    else:
+        anchors = yolov2.ANCHORS_VOC
+    first = step_size(args, 1) if args.multi_scale else args.size
+    trainer = yolov2.YOLOv2Trainer(args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
+                                   seed=args.seed, width_div=args.width_div)
+    last_iter_num = 0
+    if latest:
+        print('Restorining model snapshots from {:s}'.format(latest))
+        last_iter_num = net_utils.restore_yolov2_variables(trainer, latest)
+        skip_batches(imdb, last_iter_num)
+    elif args.imagenet_ckpt_dir:
+        prior = net_utils.get_ordered_ckpts(args.imagenet_ckpt_dir, 'darknet19', True)
+        if prior:
+            net_utils.load_darknet19_backbone(trainer, net_utils.read_darknet19_core(prior[-1]))
+            print('Backbone restored from {:s}'.format(prior[-1]))
+    TOTAL_ITER = args.iters + last_iter_num
+    T = Timer()
+    T.tic()
+    losses, sizes = [], []
+    for i in range(last_iter_num + 1, TOTAL_ITER + 1):
+        size = step_size(args, i)
+        image, gt_labels = imdb.get(size)                     # two kernels on this stream, no host pixel work
+        loss = trainer.step(image, gt_labels)
+        losses.append(loss.cpu().numpy().copy())              # coord, object, noobject, class, total
+        sizes.append(size)
+        if i % 10 == 0:
+            _time = T.toc(average=False)
+            print('iter {:d}/{:d}, size {:d}, total loss: {:.3}, take {:.2}s'.format(i, TOTAL_ITER, size,
+                                                                                    float(losses[-1][4]), _time))
+            T.tic()
+        if args.ckpt_dir and (i % args.save_every == 0 or i == TOTAL_ITER):
+            save_path = os.path.join(args.ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) + '.npz')
+            net_utils.save_yolov2_variables(trainer, save_path, iteration=i)
+            print("Model saved in file: %s" % save_path)
+    torch.cuda.synchronize()
+    return {"losses": losses, "last_iter": TOTAL_ITER, "first_iter": last_iter_num + 1, "trainer": trainer,
+            "sizes": sizes, "anchors": np.asarray(anchors, np.float32), "imdb": imdb}
+
+
+if __name__ == "__main__":
+    main()

@@ -1,4 +1,4 @@
-"""Batched evaluation of the grid detector: the host specification of csrc/detect.hip (numpy only).
+"""Batched evaluation of the detectors: the host specification of csrc/detect.hip (numpy only).
 
 NOT in the reference (it has no evaluation code; SURVEY 8 a-x2).  Three functions, the per-image two of which the
 kernels y2_detect_grid_batch and y2_voc_match_batch reproduce bit for bit, as img_dataset/augment.py is the
@@ -7,6 +7,8 @@ specification of csrc/augment.hip:
   grid_detect     one image's head output -> boxes in the 1-based pixels of the ORIGINAL image, after a score-ordered,
                   class-aware greedy NMS.  The decode is show_yolo_detection's (oracle/loss_ref.decode_detections,
                   csrc/loss.hip: decode_kernel) and the box is utils/voc_eval.detections_from_decode's.
+  anchor_detect   the same rows for the YOLOv2 anchor head, from the outputs of y2_decode_anchors + y2_class_argmax
+                  (kernel: y2_detect_anchor_batch, which decodes the raw head itself); shares grid_detect's walk.
   match_image     the body of utils/voc_eval.eval_class for one image: a TP / FP / ignored flag per detection.
   map_from_flags  the global part: per class a stable sort by score, cumulative sums, utils/voc_eval.average_precision.
 
@@ -65,6 +67,13 @@ def grid_detect(predict, im_w, im_h, num_class, B, object_thresh, iou_thresh, ma
     """predict float32 [S][S][num_class + 5 B] of ONE image -> (det int32 [count][6] = xmin, ymin, xmax, ymax, class,
     candidate index; score float32 [count]), count <= max_out, rows in descending score (ties: ascending index)"""
     valid, box, cls, score = grid_candidates(predict, im_w, im_h, num_class, B, object_thresh)
+    return _greedy_walk(valid, box, cls, score, iou_thresh, max_out)
+
+
+def _greedy_walk(valid, box, cls, score, iou_thresh, max_out):
+    """the ordering and the class-aware greedy NMS both detectors share: the valid candidates in descending score (ties:
+    ascending index); a kept box suppresses every later box of its class with IoU (float64, + 1 extents) > iou_thresh;
+    the walk stops at max_out kept rows -> (det int32 [count][6], score float32 [count])"""
     idx = np.nonzero(valid)[0]
     order = idx[np.lexsort((idx, -score[idx].astype(np.float64)))]        # score descending, then index ascending
     thresh = float(np.float32(iou_thresh))                                # the C ABI passes float
@@ -85,6 +94,39 @@ def grid_detect(predict, im_w, im_h, num_class, B, object_thresh, iou_thresh, ma
     keep = np.asarray(keep, np.int64)
     det = np.concatenate([box[keep], cls[keep, None], keep[:, None]], axis=1).astype(np.int32).reshape(-1, 6)
     return det, score[keep].astype(np.float32)
+
+
+def anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh):
+    """every candidate of one image of the YOLOv2 anchor head, from its decode: boxes float32 [K][4] = cx, cy, w, h
+    relative to the image (what y2_decode_anchors writes), best float32 [K] and cls int [K] (what y2_class_argmax writes),
+    candidate i = cell * B + b -> (valid, box, cls, score) as grid_candidates.  The resize is a plain stretch, so the
+    relative coordinates map straight to the original image: the float64 products cx * im_w, cy * im_h, w * im_w,
+    h * im_h; from there on every rule is grid_candidates'"""
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    score = np.asarray(best, np.float32).reshape(-1)
+    cls = np.asarray(cls).reshape(-1).astype(np.int64)
+    assert len(boxes) == len(score) == len(cls), (boxes.shape, score.shape, cls.shape)
+    im_w, im_h = int(im_w), int(im_h)
+    with np.errstate(all="ignore"):
+        prod = boxes.astype(np.float64) * np.array([im_w, im_h, im_w, im_h], np.float64)
+        valid = score > np.float32(score_thresh)                          # (a NaN score compares false)
+        valid &= (np.isfinite(prod) & (np.abs(prod) < LIMIT)).all(axis=1)
+    prod = np.where(valid[:, None], prod, 0.0)
+    x, y, w, h = (np.trunc(prod[:, k]).astype(np.int64) for k in range(4))   # int(): toward zero
+    ulx, uly = x - w // 2, y - h // 2
+    xmin, ymin = np.maximum(ulx, 0), np.maximum(uly, 0)
+    xmax, ymax = np.minimum(ulx + w - 1, im_w - 1), np.minimum(uly + h - 1, im_h - 1)
+    valid &= (xmax >= xmin) & (ymax >= ymin)
+    box = np.stack([xmin, ymin, xmax, ymax], axis=1) + 1
+    box = np.where(valid[:, None], box, 0)
+    return valid, box, cls, score
+
+
+def anchor_detect(boxes, best, cls, im_w, im_h, score_thresh, iou_thresh, max_out):
+    """the decode of ONE image (anchor_candidates' arguments) -> grid_detect's rows: (det int32 [count][6] = xmin, ymin,
+    xmax, ymax, class, candidate index; score float32 [count]); the specification of y2_detect_anchor_batch"""
+    valid, box, cls, score = anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh)
+    return _greedy_walk(valid, box, cls, score, iou_thresh, max_out)
 
 
 def match_image(det, gt_boxes, gt_difficult, iou_thresh=0.5):

@@ -485,3 +485,127 @@ def restore_resnet_tf_variables(model, ckpt_dir, net_name='resnet50', retrain=Fa
     print('Restored.')
     m = re.search(r"_(\d+)\.(npz|ckpt)$", sfiles[-1])
     return int(m.group(1)) if m else 0
+
+
+# ---------------------------------------------------------------------------
+# YOLOv2 (yolo2_nets/yolov2.py: YOLOv2Detector, YOLOv2Trainer; not in the reference): one `.npz` for the three stacks and
+# the optimizer of the composed graph.  The names are utils/yolov2_snapshot.py's.
+# ---------------------------------------------------------------------------
+from ..utils import yolov2_snapshot as _v2snap
+
+
+def _layer_slots(network, layers):
+    """flat float32 array laid out like `network`'s parameters from per-layer dicts of PARAM_KEYS"""
+    flat = np.zeros(network.n_params, np.float32)
+    for l, d in enumerate(layers):
+        o = network._offsets[l]
+        for i, k in enumerate(engine.PARAM_KEYS):
+            a = np.asarray(d[k], np.float32).reshape(-1)
+            flat[o[i]:o[i] + a.size] = a
+    return flat
+
+
+def save_yolov2_variables(model, path, iteration=None):
+    """model: a YOLOv2Detector or a YOLOv2Trainer -> one .npz: the parameters and batch-norm state of the three stacks,
+    the anchors, the class count and the iteration (default: model.iteration); for a trainer also the three Adam states
+    and the one loss scaler and step counter they share, so that a resumed run continues the uninterrupted one"""
+    nets = model.networks()
+    stacks = {s: net.export_params() for s, net in zip(_v2snap.STACKS, nets)}
+    adam = scaler = None
+    if hasattr(model, "opts"):
+        adam = {}
+        for s, net, opt in zip(_v2snap.STACKS, nets, model.opts):
+            st = opt.export_state()
+            adam[s] = {"m": _slot_views(net, torch.as_tensor(st["m"])), "v": _slot_views(net, torch.as_tensor(st["v"])),
+                       "t": st["t"]}
+        sc = model.opts[0].scaler
+        if sc is not None:
+            scaler = {"ctrl": sc.ctrl.cpu().numpy(), "scale": sc.scale, "clean": sc._clean}
+    blob = _v2snap.to_blob(stacks, model.anchors, model.num_class,
+                           model.iteration if iteration is None else iteration, adam, scaler)
+    np.savez(path, **blob)
+    return sorted(blob)
+
+
+def restore_yolov2_variables(model, path):
+    """the inverse of save_yolov2_variables -> the snapshot's iteration (also left in model.iteration).  A
+    YOLOv2Detector takes the parameters and batch-norm state only; a YOLOv2Trainer also the optimizer when the file
+    holds it.  Other anchors, another class count or a tensor of another shape raise, naming both values."""
+    with np.load(path) as snap:
+        stacks, anchors, num_class, iteration, adam, scaler = _v2snap.from_blob(snap)
+    _v2snap.check_matches("num_class", path, num_class, model.num_class)
+    _v2snap.check_matches("anchors", path, anchors, np.asarray(model.anchors, np.float32).reshape(-1, 2))
+    nets = model.networks()
+    for s, net in zip(_v2snap.STACKS, nets):
+        if len(stacks[s]) != net.num_layers:
+            raise ValueError("snapshot %s: the %s stack has %d layers, the model has %d" %
+                             (path, s, len(stacks[s]), net.num_layers))
+        for l, layer in enumerate(stacks[s]):
+            for k, shape in net._shapes(l).items():
+                if tuple(layer[k].shape) != tuple(shape):
+                    raise ValueError("snapshot %s: yolov2/%s/%d/%s has shape %s, the model expects %s" %
+                                     (path, s, l, k, tuple(layer[k].shape), tuple(shape)))
+        net.load_params(stacks[s])
+    if hasattr(model, "opts") and adam is not None:
+        for s, net, opt in zip(_v2snap.STACKS, nets, model.opts):
+            opt.load_state({"m": _layer_slots(net, adam[s]["m"]), "v": _layer_slots(net, adam[s]["v"]),
+                            "t": adam[s]["t"]})
+        sc = model.opts[0].scaler
+        if sc is not None and scaler is not None:
+            sc.ctrl.copy_(torch.as_tensor(scaler["ctrl"]))
+            sc._apply(scaler["scale"])
+            sc._clean = scaler["clean"]
+            # the saved run read the control words one step late: the copy made after its last step is still to be looked
+            # at by the next one
+            sc._host.copy_(sc.ctrl)
+            sc._event = torch.cuda.Event()
+            sc._event.record()
+    model.iteration = iteration
+    return iteration
+
+
+def read_yolov2_meta(path):
+    """(anchors float32 [B][2], num_class, iteration) of a YOLOv2 snapshot, to build the model it restores into"""
+    with np.load(path) as snap:
+        return _v2snap.meta_from_blob(snap)
+
+
+def get_ordered_yolov2_ckpts(ckpt_dir):
+    """`train_iter_<i>.npz` files of ckpt_dir by iteration number, oldest first"""
+    files = glob.glob(os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + "_iter_*.npz"))
+    numbered = [(int(m.group(1)), f) for f in files for m in [re.search(r"_iter_(\d+)\.npz$", f)] if m]
+    return [f for _i, f in sorted(numbered)]
+
+
+def read_darknet19_core(path):
+    """the 18 core layers (dicts of the six arrays) of a Darknet-19 classifier or detector snapshot of this package
+    (.npz or TF V2 checkpoint): what load_darknet19_backbone takes"""
+    snap = _open_snapshot(path)
+    names = _darknet.variable_names("classifier", 1000)[:len(engine.CORE_SPEC)]
+    missing = [n for nm in names for n in nm.values() if n not in snap.files]
+    if missing:
+        raise ValueError("snapshot %s holds no Darknet-19 core: %s ... missing" % (path, missing[0]))
+    return [{k: np.asarray(snap[n], np.float32) for k, n in nm.items()} for nm in names]
+
+
+def load_darknet19_backbone(model, core_layers):
+    """core_layers: the 18 conv-BN-leaky layers of Darknet-19 (a list of dicts W, b, gamma, beta, moving_mean,
+    moving_var; longer lists -- a classifier's 19, a detector's 22 -- are cut) -> layers 0-12 into the stem and 13-17
+    into the first five layers of the 13x13 stack of a YOLOv2Detector / YOLOv2Trainer; the two added 3x3 layers and the
+    head keep their values.  Returns the number of layers loaded."""
+    n_core = len(engine.CORE_SPEC)
+    if len(core_layers) < n_core:
+        raise ValueError("load_darknet19_backbone: %d layers given, the Darknet-19 core has %d" % (len(core_layers), n_core))
+    stem, deep = model.networks()[:2]
+    split = stem.num_layers
+    for net, lo, hi in ((stem, 0, split), (deep, split, n_core)):
+        layers = net.export_params()
+        for l in range(lo, hi):
+            for k, shape in net._shapes(l - lo).items():
+                a = np.asarray(core_layers[l][k], np.float32)
+                if tuple(a.shape) != tuple(shape):
+                    raise ValueError("load_darknet19_backbone: core layer %d %s has shape %s, the model expects %s" %
+                                     (l, k, tuple(a.shape), tuple(shape)))
+                layers[l - lo][k] = a
+        net.load_params(layers)
+    return n_core

@@ -17,23 +17,30 @@ from .. import engine as E
 ANCHORS_VOC = ((1.3221, 1.73145), (3.19275, 4.00944), (5.05587, 8.09892), (9.47112, 4.84053), (11.2364, 10.0071))
 
 
-def yolov2_specs(num_class=20, num_anchors=5):
+def yolov2_specs(num_class=20, num_anchors=5, width_div=1):
     core = [tuple(s) for s in E.CORE_SPEC]
     a = core[:13]
     a[12] = (a[12][0], a[12][1], a[12][2], 0)            # keep the 26x26x512 activation un-pooled
     b = core[13:18] + [(3, 1024, 1024, 0), (3, 1024, 1024, 0)]
     c = [(3, 4 * 512 + 1024, 1024, 0), (1, 1024, num_anchors * (5 + num_class), 0)]
+    if width_div > 1:      # narrow variant for tests: every inner width divided, the output width kept
+        div = lambda ch: max(32, ch // width_div // 32 * 32)
+        a = [(k, ci if i == 0 else div(ci), div(co), p) for i, (k, ci, co, p) in enumerate(a)]
+        b = [(k, div(ci), div(co), p) for (k, ci, co, p) in b]
+        c = [(3, 4 * a[-1][2] + b[-1][2], div(1024), 0), (1, div(1024), c[1][2], 0)]
     return a, b, c
 
 
 class YOLOv2Detector:
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0"):
+                 device="cuda:0", width_div=1):
         assert image_size % 32 == 0
         self.batch, self.size, self.S = batch, image_size, image_size // 32
-        self.num_class, self.anchors = num_class, np.asarray(anchors, np.float32)
+        self.num_class, self.anchors = num_class, np.asarray(anchors, np.float32).reshape(-1, 2)
         self.B = len(self.anchors)
-        sa, sb, sc = yolov2_specs(num_class, self.B)
+        self.iteration = 0                                   # of the snapshot last restored (net_utils)
+        sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
+        self.anchors_dev = torch.as_tensor(self.anchors).to(device).contiguous()
         S = self.S
         self.stem = E.Network(sa, batch, image_size, image_size, dtype=dtype, training=False, device=device)
         self.deep = E.Network(sb, batch, S, S, dtype=dtype, training=False, device=device)
@@ -41,12 +48,17 @@ class YOLOv2Detector:
         for i, net in enumerate((self.stem, self.deep, self.head)):
             net.init_params(seed + i)
 
-    def forward(self, images):
-        """images [N,size,size,3] fp32 on the device -> raw grid [N,S,S,B,5+C]"""
+    def networks(self):
+        """the three stack contexts (stem, 13x13 stack, head)"""
+        return self.stem, self.deep, self.head
+
+    def forward(self, images, out=None):
+        """images [N,size,size,3] fp32 (or uint8 BGR pixels) on the device -> raw grid [N,S,S,B,5+C] (in `out`, a
+        contiguous fp32 tensor of that many elements, if given)"""
         fine = self.stem.forward(images, False, False)                      # [N,2S,2S,512]
         coarse = self.deep.forward(E.max_pool_2x2(fine), False, False)      # [N,S,S,1024]
         cat = E.passthrough_concat(fine, coarse)                            # [N,S,S,3072]
-        out = self.head.forward(cat, False, False)                          # [N,S,S,B*(5+C)]
+        out = self.head.forward(cat, False, False, out=out)                 # [N,S,S,B*(5+C)]
         return out.view(self.batch, self.S, self.S, self.B, 5 + self.num_class)
 
     def detect(self, images, score_thresh=0.3, iou_thresh=0.45, max_out=100, class_aware=True):
@@ -56,6 +68,15 @@ class YOLOv2Detector:
         best, cls = E.class_argmax(scores)
         keep, count = E.nms(boxes, best, cls, iou_thresh, score_thresh, max_out, class_aware)
         return boxes, best, cls, keep, count
+
+    def detect_batch(self, images_u8, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None,
+                     grid_out=None):
+        """evaluation: images_u8 [N,size,size,3] uint8 BGR (DeviceVOC.eval_batch), table / index the pool's entry table
+        and the slots' entries -> (det int32 [N,max_out,6], score [N,max_out], count [N]) in the 1-based pixels of each
+        ORIGINAL image: the forward pass on the moving statistics, then ONE launch from the raw head
+        (engine.detect_anchor_batch) -- rows that engine.voc_match_batch reads.  grid_out: keeps the raw head there."""
+        grid = self.forward(images_u8, out=grid_out)
+        return E.detect_anchor_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh, max_out, out=out)
 
 
 class YOLOv2Trainer:
@@ -72,12 +93,8 @@ class YOLOv2Trainer:
         self.anchors = np.asarray(anchors, np.float32)
         self.B = len(self.anchors)
         self.scales = scales
-        sa, sb, sc = yolov2_specs(num_class, self.B)
-        if width_div > 1:      # narrow variant for tests: every inner width divided, the output width kept
-            div = lambda c: max(32, c // width_div // 32 * 32)
-            sa = [(k, ci if i == 0 else div(ci), div(co), p) for i, (k, ci, co, p) in enumerate(sa)]
-            sb = [(k, div(ci), div(co), p) for (k, ci, co, p) in sb]
-            sc = [(3, 4 * sa[-1][2] + sb[-1][2], div(1024), 0), (1, div(1024), sc[1][2], 0)]
+        self.iteration = 0                                   # train steps taken, over resumed runs (net_utils snapshots)
+        sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
         self.specs = (sa, sb, sc)
         self.cf = sa[-1][2]
         self.ctx = {}
@@ -131,6 +148,7 @@ class YOLOv2Trainer:
         for net in (stem, deep, head):
             if len(self.ctx) > 1:
                 net.params_changed()              # shared parameters moved under another size's contexts
+        self.iteration += 1
         grid, fine = self.forward(images, True, update_moving=True)
         loss, dnet = E.yolov2_loss(grid.contiguous(), labels, self.anchors, size, True, self.scales)
         dist = _dist()
