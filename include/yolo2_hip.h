@@ -270,6 +270,22 @@ int y2_nms(const float* boxes, const float* scores, const int* classes, int N, i
 size_t y2_yolov2_loss_workspace_bytes(int batch);
 int y2_yolov2_loss(const float* net, const float* labels, const float* anchors, int batch, int S, int B, int num_class,
                    float image_size, const float* scales, float* loss, float* dnet, void* workspace, void* stream);
+/* The same loss on BOX LISTS, every object of an image kept (specification: utils/region_loss.py yolov2_loss_boxes):
+ * truth [N][max_boxes][5] = cx, cy, w, h in pixels of the input and the class index, ntruth int32 [N] (y2_encode_box_list
+ * writes both; device memory).  The loss derives a truth's cell and its best-fitting anchor; the slot (cell, anchor) is
+ * owned by the LOWEST truth index that claims it, a truth that loses its slot has no coord / object / class term but
+ * still counts in the best IoU of the noobject rule.  `scales`: 7 floats in HOST memory = {coord, object, noobject,
+ * class, iou_thresh, area_weight (0 / 1: coord terms times 2 - w h, w and h relative to the image), prior_scale (> 0:
+ * every un-owned slot adds prior_scale ((sig(tx) - 1/2)^2 + (sig(ty) - 1/2)^2 + tw^2 + th^2) to the coord part)}; NULL:
+ * 1, 5, 1, 1, 0.6, 0, 0.  One launch + the finalize; the result does not vary from run to run.  The ownership table is
+ * held in LDS in slices of 256 slots, one per workgroup, so S * S * B is bounded by the index arithmetic alone
+ * (Y2_LOSS_BOXES_MAX_SLOTS).  A class index outside [0, num_class) is the caller's error: the lists are device memory,
+ * no host-side check is made, and such a row takes no class term (its other terms stand). */
+#define Y2_LOSS_BOXES_MAX_SLOTS (1 << 20) /* S * S * B of one image; more is an argument error */
+size_t y2_yolov2_loss_boxes_workspace_bytes(int batch, int S, int B);
+int y2_yolov2_loss_boxes(const float* net, const float* truth, const int* ntruth, const float* anchors, int batch, int S,
+                         int B, int num_class, int max_boxes, float image_size, const float* scales, float* loss,
+                         float* dnet, void* workspace, void* stream);
 
 /* ---- ResNet-50 backbone swap (src/yolo2_nets/tf_resnet.py:12-32, src/pascal/pascal_train_resnet.py:37-50):
  *      graph-level operators on fp32 NHWC tensors that the conv-BN-leaky stacks do not have.  The 1x1 / 3x3
@@ -438,6 +454,15 @@ int y2_augment_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t
 int y2_encode_labels_window(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
                             const double* params, int n, int max_obj, int image_size, int S, int num_class,
                             float* labels, void* stream);
+/* The label of the anchor model that keeps EVERY object (augment.encode_box_list, bit-equal): truth float32
+ * [n][max_boxes][5] = cx, cy, w, h in pixels of the resized input and the class index, ntruth int32 [n].  Per object the
+ * arithmetic of y2_encode_labels_window without the "cell already taken" rule; objects in annotation order, those beyond
+ * max_boxes dropped in that order, rows at and beyond ntruth zero.  `params` NULL: the identity row of every entry (the
+ * plain path of y2_encode_labels).  A row without a window gives an empty list.  One 64-lane wave per image. */
+#define Y2_MAX_BOXES 1024 /* rows of a box list; more is an argument error */
+int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
+                       const double* params, int n, int max_obj, int image_size, int max_boxes, float* truth,
+                       int32_t* ntruth, void* stream);
 
 /* ---- evaluation of the grid detector from the same pool (pascal/pascal_eval_darknet.py; utils/detect_batch.py is the
  *      specification and both calls are bit-equal to it): per image, the head's output -> boxes in the pixels of the

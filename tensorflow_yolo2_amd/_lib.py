@@ -95,6 +95,8 @@ SIGNATURES = {
     "y2_nms": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
     "y2_yolov2_loss_workspace_bytes": (_sz, [_i]),
     "y2_yolov2_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "y2_yolov2_loss_boxes_workspace_bytes": (_sz, [_i, _i, _i]),
+    "y2_yolov2_loss_boxes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "y2_batch_norm_forward": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp]),
     "y2_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "y2_subsample": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -129,6 +131,7 @@ SIGNATURES = {
     "y2_encode_labels": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "y2_augment_u8_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "y2_encode_labels_window": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "y2_encode_box_list": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "y2_detect_grid_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "y2_detect_anchor_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "y2_voc_match_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),

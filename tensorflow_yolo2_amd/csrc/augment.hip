@@ -238,9 +238,91 @@ __global__ __launch_bounds__(kThreads) void encode_labels_window_kernel(const do
     }
 }
 
+// The label of the anchor model that keeps every object (augment.encode_box_list): grid (n), ONE 64-lane wave per image.
+// Lane l owns objects l, l + 64, ...: the window arithmetic of the kernel above in double, keep or drop.  The kept
+// objects of a round of 64 are compacted in annotation order with a ballot and the count of kept lanes below (no
+// atomics: order and the max_boxes cut do not depend on timing), then the rows beyond the count are zero-filled.
+// params == nullptr: the identity row {0, 0, width, height, 0} of every entry, the plain path.
+__global__ __launch_bounds__(64) void encode_box_list_kernel(const double* __restrict__ boxes,
+                                                             const int32_t* __restrict__ counts,
+                                                             const int64_t* __restrict__ table,
+                                                             const int32_t* __restrict__ index,
+                                                             const double* __restrict__ params, int max_obj,
+                                                             int image_size, int max_boxes, float* __restrict__ truth,
+                                                             int32_t* __restrict__ ntruth) {
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const size_t e = index ? (size_t)index[img] : (size_t)img;
+    const int64_t* t = table + kTable * e;
+    double wx0 = 0.0, wy0 = 0.0, cw = (double)t[2], ch = (double)t[1];
+    bool flip = t[4] != 0;
+    if (params) {
+        const double* prm = params + (size_t)kParams * img;
+        wx0 = win_int(prm[0], -(1 << 30), 1 << 30); wy0 = win_int(prm[1], -(1 << 30), 1 << 30);
+        cw = win_int(prm[2], 0, 1 << 30); ch = win_int(prm[3], 0, 1 << 30);
+        flip = flip != (prm[4] != 0.0);
+    }
+    const bool window = cw >= 1.0 && ch >= 1.0;           // a row without a window: an empty list
+    const double w_ratio = (double)image_size / cw, h_ratio = (double)image_size / ch;
+    const double hi = (double)(image_size - 1), size = (double)image_size;
+    const int cnt = window ? min(max(counts[e], 0), max_obj) : 0;
+    const double* bx0 = boxes + e * (size_t)max_obj * 5;
+    float* out = truth + (size_t)img * max_boxes * 5;
+    int base = 0;                                         // rows written by the rounds before (wave-uniform)
+    for (int o0 = 0; o0 < cnt && base < max_boxes; o0 += 64) {
+        const int o = o0 + lane;
+        bool keep = false;
+        double cx = 0.0, cy = 0.0, bw = 0.0, bh = 0.0;
+        int cls = 0;
+        if (o < cnt) {
+            const double* bx = bx0 + (size_t)o * 5;
+            double x1 = (bx[0] - 1 - wx0) * w_ratio, y1 = (bx[1] - 1 - wy0) * h_ratio;
+            double x2 = (bx[2] - 1 - wx0) * w_ratio, y2 = (bx[3] - 1 - wy0) * h_ratio;
+            const double ux = (x2 + x1) / 2.0, uy = (y2 + y1) / 2.0;
+            keep = ux >= 0.0 && ux < size && uy >= 0.0 && uy < size;   // else the centre left the window (or not a number)
+            x1 = hi < x1 ? hi : x1; x1 = 0.0 > x1 ? 0.0 : x1;
+            y1 = hi < y1 ? hi : y1; y1 = 0.0 > y1 ? 0.0 : y1;
+            x2 = hi < x2 ? hi : x2; x2 = 0.0 > x2 ? 0.0 : x2;
+            y2 = hi < y2 ? hi : y2; y2 = 0.0 > y2 ? 0.0 : y2;
+            cx = (x2 + x1) / 2.0; cy = (y2 + y1) / 2.0;
+            bw = x2 - x1; bh = y2 - y1;
+            cls = (int)bx[4];
+        }
+        const unsigned long long kept = __ballot(keep);
+        const int pos = base + __popcll(kept & ((1ull << lane) - 1ull));
+        if (keep && pos < max_boxes) {
+            float* r = out + (size_t)pos * 5;
+            r[0] = (float)(flip ? hi - cx : cx);
+            r[1] = (float)cy;
+            r[2] = (float)bw;
+            r[3] = (float)bh;
+            r[4] = (float)cls;
+        }
+        base += __popcll(kept);
+    }
+    const int rows = min(base, max_boxes);
+    for (int i = rows * 5 + lane; i < max_boxes * 5; i += 64) out[i] = 0.0f;
+    if (lane == 0) ntruth[img] = rows;
+}
+
 }  // namespace
 
 extern "C" {
+
+int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
+                       const double* params, int n, int max_obj, int image_size, int max_boxes, float* truth,
+                       int32_t* ntruth, void* stream) {
+    if (!boxes || !counts || !table || !truth || !ntruth) return fail(Y2_ERR_ARG, "y2_encode_box_list: null pointer");
+    if (n < 1) return fail(Y2_ERR_ARG, "y2_encode_box_list: n = %d", n);
+    if (max_obj < 1 || image_size < 1)
+        return fail(Y2_ERR_ARG, "y2_encode_box_list: max_obj = %d, image_size = %d", max_obj, image_size);
+    if (max_boxes < 1 || max_boxes > Y2_MAX_BOXES)
+        return fail(Y2_ERR_ARG, "y2_encode_box_list: max_boxes = %d outside 1..%d", max_boxes, Y2_MAX_BOXES);
+    hipLaunchKernelGGL(encode_box_list_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, boxes, counts, table, index,
+                       params, max_obj, image_size, max_boxes, truth, ntruth);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_encode_box_list: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
 
 int y2_augment_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, const double* params, int n,
                         int out_h, int out_w, int fill, uint8_t* out, void* stream) {

@@ -384,6 +384,148 @@ __global__ void yolov2_loss_finalize_kernel(const float* partial, float* loss, i
     loss[4] = tot;
 }
 
+// ---------------------------------------------------------------------------
+// The same loss on BOX LISTS (specification: utils/region_loss.py yolov2_loss_boxes): every ground-truth box of an
+// image is kept, truth [N][T][5] = cx, cy, w, h in pixels and the class index, ntruth [N].  Grid (ceil(S*S*B / 256), N):
+// a workgroup owns 256 consecutive (cell, anchor) slots of one image.  It stages ALL truths of the image in LDS with
+// the slot each one claims (its cell and its best-fitting anchor), settles the ownership of its own slots with
+// atomicMin on the truth index (the lowest index wins whatever the order of arrival), then one thread per slot writes
+// the slot's terms and its whole gradient row: an owned slot the coord / object / class terms of its owner, any other
+// slot the noobject term under the best IoU over all truths and, while the prior is on, the pull toward its anchor.
+// One partial [4] per workgroup; the finalize adds them in a fixed order, so two runs give the same bits.
+// ---------------------------------------------------------------------------
+struct V2BoxLossArgs {
+    const float* net;      // [N][S][S][B][5+C]
+    const float* truth;    // [N][T][5]
+    const int* ntruth;     // [N]
+    const float* anchors;  // [B][2] cell units
+    float* dnet;           // same shape as net (nullable)
+    float* partial;        // [N][gridDim.x][4]
+    int N, S, B, C, T;
+    float image_size, coord, obj, noobj, cls, thresh, prior;
+    int area_weight;
+};
+constexpr int kV2NoOwner = 0x7fffffff;
+
+__global__ __launch_bounds__(256) void yolov2_loss_boxes_kernel(V2BoxLossArgs a) {
+    __shared__ float tr[Y2_MAX_BOXES][4];
+    __shared__ int tcls[Y2_MAX_BOXES];
+    __shared__ int own[256];
+    __shared__ float red[4][256];
+    const int n = blockIdx.y, tid = threadIdx.x;
+    const int cells = a.S * a.S, D = 5 + a.C, slots = cells * a.B;
+    const int slot0 = blockIdx.x * 256;
+    const float fs = (float)a.S;
+    const int nt = min(max(a.ntruth[n], 0), a.T);
+    own[tid] = kV2NoOwner;
+    __syncthreads();
+    for (int k = tid; k < nt; k += 256) {
+        const float* tk = a.truth + ((size_t)n * a.T + k) * 5;
+        const float gx = tk[0] / a.image_size * fs, gy = tk[1] / a.image_size * fs;
+        const float gw = tk[2] / a.image_size * fs, gh = tk[3] / a.image_size * fs;
+        tr[k][0] = gx; tr[k][1] = gy; tr[k][2] = gw; tr[k][3] = gh;
+        tcls[k] = (int)tk[4];
+        // the cell of the truth (cut into the grid: every index below is in range whatever the list holds)
+        const int q = (int)fminf(fmaxf(gx, 0.0f), fs - 1.0f), r = (int)fminf(fmaxf(gy, 0.0f), fs - 1.0f);
+        int bs = 0;
+        float bi = -1.0f;
+        for (int j = 0; j < a.B; ++j) {   // the anchor whose shape fits best, first one on ties
+            const float kw = a.anchors[2 * j], kh = a.anchors[2 * j + 1];
+            const float inter = fminf(gw, kw) * fminf(gh, kh);
+            const float si = inter / (gw * gh + kw * kh - inter);
+            if (si > bi) { bi = si; bs = j; }
+        }
+        const int slot = (r * a.S + q) * a.B + bs - slot0;
+        if (slot >= 0 && slot < 256) atomicMin(&own[slot], k);
+    }
+    __syncthreads();
+    float t_coord = 0.f, t_obj = 0.f, t_noobj = 0.f, t_cls = 0.f;
+    const float invN = 1.0f / (float)a.N;
+    const int p = slot0 + tid;
+    if (p < slots) {
+        const int cell = p / a.B, b = p - cell * a.B;
+        const int row = cell / a.S, col = cell - row * a.S;
+        const float* t = a.net + ((size_t)n * slots + p) * D;
+        float* g = a.dnet ? a.dnet + ((size_t)n * slots + p) * D : nullptr;
+        const float aw = a.anchors[2 * b], ah = a.anchors[2 * b + 1];
+        const float sx = v2_sigmoid(t[0]), sy = v2_sigmoid(t[1]), so = v2_sigmoid(t[4]);
+        const float px = sx + (float)col, py = sy + (float)row, pw = aw * expf(t[2]), ph = ah * expf(t[3]);
+        const int owner = own[tid];
+        if (owner != kV2NoOwner) {
+            const float gx = tr[owner][0], gy = tr[owner][1], gw = tr[owner][2], gh = tr[owner][3];
+            const float wgt = a.area_weight ? a.coord * (2.0f - (gw / fs) * (gh / fs)) : a.coord;
+            const float ex = sx - (gx - (float)col), ey = sy - (gy - (float)row);
+            const float ew = t[2] - logf(gw / aw), eh = t[3] - logf(gh / ah);
+            t_coord += wgt * (ex * ex + ey * ey + ew * ew + eh * eh);
+            const float iou = v2_iou(px, py, pw, ph, gx, gy, gw, gh);
+            const float eo = so - iou;
+            t_obj += a.obj * eo * eo;
+            const int k = tcls[owner];
+            const bool has_class = k >= 0 && k < a.C;   // a class index outside [0, C): no class term (caller's contract)
+            float lse = 0.f;
+            if (has_class) {
+                float m = t[5];
+                for (int c = 1; c < a.C; ++c) m = fmaxf(m, t[5 + c]);
+                float se = 0.f;
+                for (int c = 0; c < a.C; ++c) se += expf(t[5 + c] - m);
+                lse = m + logf(se);
+                t_cls += a.cls * (lse - t[5 + k]);
+            }
+            if (g) {
+                g[0] = wgt * 2.0f * ex * sx * (1.0f - sx) * invN;
+                g[1] = wgt * 2.0f * ey * sy * (1.0f - sy) * invN;
+                g[2] = wgt * 2.0f * ew * invN;
+                g[3] = wgt * 2.0f * eh * invN;
+                g[4] = a.obj * 2.0f * eo * so * (1.0f - so) * invN;
+                for (int c = 0; c < a.C; ++c)
+                    g[5 + c] = has_class ? a.cls * (expf(t[5 + c] - lse) - (c == k ? 1.0f : 0.0f)) * invN : 0.f;
+            }
+        } else {
+            float best = 0.f;
+            for (int k = 0; k < nt; ++k) best = fmaxf(best, v2_iou(px, py, pw, ph, tr[k][0], tr[k][1], tr[k][2], tr[k][3]));
+            const bool pen = best <= a.thresh;
+            if (pen) t_noobj += a.noobj * so * so;
+            const bool prior = a.prior > 0.0f;
+            const float dx = sx - 0.5f, dy = sy - 0.5f;
+            if (prior) t_coord += a.prior * (dx * dx + dy * dy + t[2] * t[2] + t[3] * t[3]);
+            if (g) {
+                g[0] = prior ? a.prior * 2.0f * dx * sx * (1.0f - sx) * invN : 0.f;
+                g[1] = prior ? a.prior * 2.0f * dy * sy * (1.0f - sy) * invN : 0.f;
+                g[2] = prior ? a.prior * 2.0f * t[2] * invN : 0.f;
+                g[3] = prior ? a.prior * 2.0f * t[3] * invN : 0.f;
+                g[4] = pen ? a.noobj * 2.0f * so * so * (1.0f - so) * invN : 0.f;
+                for (int c = 0; c < a.C; ++c) g[5 + c] = 0.f;
+            }
+        }
+    }
+    red[0][tid] = t_coord; red[1][tid] = t_obj; red[2][tid] = t_noobj; red[3][tid] = t_cls;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + s];
+        __syncthreads();
+    }
+    if (tid < 4) a.partial[((size_t)n * gridDim.x + blockIdx.x) * 4 + tid] = red[tid][0];
+}
+// one workgroup of 256: lane (j, k) adds component k of the partials j, j + 64, ... in ascending order, then a tree
+__global__ __launch_bounds__(256) void yolov2_loss_boxes_finalize_kernel(const float* partial, float* loss, int count, int N) {
+    __shared__ float red[256];
+    const int tid = threadIdx.x, k = tid & 3;
+    float p = 0.f;
+    for (int j = tid >> 2; j < count; j += 64) p += partial[(size_t)j * 4 + k];
+    red[tid] = p;
+    __syncthreads();
+    for (int s = 128; s >= 4; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        float tot = 0.f;
+        for (int c = 0; c < 4; ++c) { loss[c] = red[c] / (float)N; tot += loss[c]; }
+        loss[4] = tot;
+    }
+}
+
 extern "C" {
 
 int y2_maxpool2x2(const float* x, float* y, int N, int H, int W, int C, void* stream) {
@@ -531,6 +673,41 @@ int y2_yolov2_loss(const float* net, const float* labels, const float* anchors, 
     hipLaunchKernelGGL(yolov2_loss_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, a);
     EXTCHK(hipGetLastError());
     hipLaunchKernelGGL(yolov2_loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a.partial, loss, batch);
+    EXTCHK(hipGetLastError());
+    return Y2_OK;
+}
+
+static int v2_box_blocks(int S, int B) { return (S * S * B + 255) / 256; }
+
+size_t y2_yolov2_loss_boxes_workspace_bytes(int batch, int S, int B) {
+    if (batch < 1 || S < 1 || B < 1 || (long long)S * S * B > Y2_LOSS_BOXES_MAX_SLOTS) return 0;
+    return (size_t)batch * v2_box_blocks(S, B) * 4 * sizeof(float) + 256;
+}
+
+int y2_yolov2_loss_boxes(const float* net, const float* truth, const int* ntruth, const float* anchors, int batch, int S,
+                         int B, int num_class, int max_boxes, float image_size, const float* scales, float* loss,
+                         float* dnet, void* workspace, void* stream) {
+    if (!net || !truth || !ntruth || !anchors || !loss || !workspace)
+        return fail(Y2_ERR_ARG, "y2_yolov2_loss_boxes: null pointer");
+    if (batch < 1 || batch > 65535 || S < 1 || B < 1 || num_class < 1 || !(image_size > 0.0f))
+        return fail(Y2_ERR_ARG, "y2_yolov2_loss_boxes: batch = %d, S = %d, B = %d, num_class = %d, image_size = %g", batch,
+                    S, B, num_class, (double)image_size);
+    if ((long long)S * S * B > Y2_LOSS_BOXES_MAX_SLOTS)
+        return fail(Y2_ERR_ARG, "y2_yolov2_loss_boxes: S * S * B = %lld beyond Y2_LOSS_BOXES_MAX_SLOTS = %d",
+                    (long long)S * S * B, Y2_LOSS_BOXES_MAX_SLOTS);
+    if (max_boxes < 1 || max_boxes > Y2_MAX_BOXES)
+        return fail(Y2_ERR_ARG, "y2_yolov2_loss_boxes: max_boxes = %d outside 1..%d", max_boxes, Y2_MAX_BOXES);
+    V2BoxLossArgs a{};
+    a.net = net; a.truth = truth; a.ntruth = ntruth; a.anchors = anchors; a.dnet = dnet; a.partial = (float*)workspace;
+    a.N = batch; a.S = S; a.B = B; a.C = num_class; a.T = max_boxes; a.image_size = image_size;
+    a.coord = scales ? scales[0] : 1.0f; a.obj = scales ? scales[1] : 5.0f; a.noobj = scales ? scales[2] : 1.0f;
+    a.cls = scales ? scales[3] : 1.0f; a.thresh = scales ? scales[4] : 0.6f;
+    a.area_weight = scales ? (scales[5] != 0.0f) : 0; a.prior = scales ? scales[6] : 0.0f;
+    const int blocks = v2_box_blocks(S, B);
+    hipLaunchKernelGGL(yolov2_loss_boxes_kernel, dim3(blocks, batch), dim3(256), 0, (hipStream_t)stream, a);
+    EXTCHK(hipGetLastError());
+    hipLaunchKernelGGL(yolov2_loss_boxes_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a.partial, loss,
+                       blocks * batch, batch);
     EXTCHK(hipGetLastError());
     return Y2_OK;
 }

@@ -832,6 +832,37 @@ def yolov2_loss(net, labels, anchors, image_size, need_grad=True, scales=None):
     return loss, dnet
 
 
+BOX_LOSS_SCALES = ("coord_scale", "object_scale", "noobject_scale", "class_scale", "thresh", "area_weight", "prior_scale")
+_BOX_LOSS_DEFAULTS = (1.0, 5.0, 1.0, 1.0, 0.6, 0.0, 0.0)
+
+
+def yolov2_loss_boxes(net, truth, ntruth, anchors, image_size, need_grad=True, scales=None):
+    """anchor-box loss of the YOLOv2 head on box lists (utils/region_loss.py yolov2_loss_boxes): net [N,S,S,B,5+C], truth
+    [N,T,5] float32 = cx, cy, w, h in pixels and the class index, ntruth [N] int32 (img_dataset/augment.encode_box_list)
+    -> (loss[5] = coord, object, noobject, class, total; dnet or None).  scales: a dict with any of BOX_LOSS_SCALES
+    (missing keys take the defaults 1, 5, 1, 1, 0.6, no area weight, no prior)."""
+    lib = _lib.load()
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, s, _, b, d = net.shape
+    assert truth.is_cuda and truth.dtype == torch.float32 and truth.is_contiguous(), (truth.dtype, truth.device)
+    assert truth.dim() == 3 and truth.shape[0] == n and truth.shape[2] == 5, truth.shape
+    assert ntruth.is_cuda and ntruth.dtype == torch.int32 and ntruth.is_contiguous() and tuple(ntruth.shape) == (n,)
+    an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
+    assert tuple(an.shape) == (b, 2), an.shape
+    sc = None
+    if scales is not None:
+        unknown = set(scales) - set(BOX_LOSS_SCALES)
+        if unknown:
+            raise ValueError("unknown loss scales %s" % sorted(unknown))
+        sc = (C.c_float * 7)(*[float(scales.get(k, v)) for k, v in zip(BOX_LOSS_SCALES, _BOX_LOSS_DEFAULTS)])   # host memory
+    loss = torch.empty(5, dtype=torch.float32, device=net.device)
+    dnet = torch.empty_like(net) if need_grad else None
+    ws = torch.empty(lib.y2_yolov2_loss_boxes_workspace_bytes(n, s, b), dtype=torch.uint8, device=net.device)
+    check(lib.y2_yolov2_loss_boxes(_ptr(net), _ptr(truth), _ptr(ntruth), _ptr(an), n, s, b, d - 5, int(truth.shape[1]),
+                                   float(image_size), sc, _ptr(loss), _ptr(dnet), _ptr(ws), _stream()))
+    return loss, dnet
+
+
 def nms(boxes, scores, classes=None, iou_thresh=0.5, score_thresh=0.0, max_out=100, class_aware=False):
     """boxes [N,K,4], scores [N,K] (, classes [N,K] int32) -> keep [N,max_out] int32 (-1 padded), count [N]"""
     lib = _lib.load()

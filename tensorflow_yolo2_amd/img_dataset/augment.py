@@ -161,3 +161,38 @@ def encode_boxes_window(objs, row, image_size, cell_size, num_class=20, flip=Fal
         label[y_ind, x_ind, 1:5] = boxes
         label[y_ind, x_ind, 5 + int(cls_ind)] = 1
     return flip_label(label, image_size) if bool(flip) != bool(row[FLIP]) else label
+
+
+MAX_BOXES = 30                              # rows of a box list by default: Darknet's max_boxes of the v2 region layer
+
+
+def encode_box_list(objs, row, image_size, max_boxes=MAX_BOXES, flip=False):
+    """The label of the anchor model that keeps EVERY object: (truth [max_boxes, 5] float32 = cx, cy, w, h in pixels of
+    the resized input and the class index, number of rows used).  Per object it is encode_boxes_window's arithmetic in
+    double -- the window transform, the drop rule on the unclamped centre, the clamp -- without the "cell already taken"
+    rule; a mirrored sample stores image_size - 1 - cx as flip_label does.  Objects stay in annotation order, those beyond
+    max_boxes are dropped in that order, the rows beyond the count are zeros.  One cast to float32 per stored value, so a
+    row equals [1:5] of the grid cell the same object wins.  With identity_row(H, W) this is the plain path:
+    (x - 1 - 0) * (size / W) is encode_boxes' (x - 1) * w_ratio."""
+    if not 1 <= int(max_boxes) <= 1024:
+        raise ValueError("max_boxes %r outside 1..1024" % (max_boxes,))
+    x0, y0, cw, ch = (float(int(row[k])) for k in (X0, Y0, CW, CH))
+    w_ratio = image_size / cw
+    h_ratio = image_size / ch
+    mirror = bool(flip) != bool(row[FLIP])
+    truth = np.zeros((int(max_boxes), 5), np.float32)
+    count = 0
+    for (xmin, ymin, xmax, ymax, cls_ind) in objs:
+        if count == max_boxes:
+            break
+        x1, y1 = (float(xmin) - 1 - x0) * w_ratio, (float(ymin) - 1 - y0) * h_ratio
+        x2, y2 = (float(xmax) - 1 - x0) * w_ratio, (float(ymax) - 1 - y0) * h_ratio
+        cx, cy = (x2 + x1) / 2.0, (y2 + y1) / 2.0
+        if not (0 <= cx < image_size and 0 <= cy < image_size):
+            continue
+        x1, y1 = max(min(x1, image_size - 1), 0), max(min(y1, image_size - 1), 0)
+        x2, y2 = max(min(x2, image_size - 1), 0), max(min(y2, image_size - 1), 0)
+        cx, cy = (x2 + x1) / 2.0, (y2 + y1) / 2.0
+        truth[count] = (image_size - 1 - cx if mirror else cx, cy, x2 - x1, y2 - y1, int(cls_ind))
+        count += 1
+    return truth, count

@@ -22,7 +22,12 @@ annotation order, and int32 counts [entries].
 Evaluation (pascal/pascal_eval_darknet.py) reads the same pool: eval_batch(size, start) resizes the entries start,
 start + 1, ... in LIST order with y2_resize_bilinear_u8_batch alone and leaves the shuffled cursor of get() where it is;
 `difficult`, uint8 [entries][max_obj] parallel to the box table, goes to the device at its first use (training never
-reads it).  Evaluation wants the plain list: a data set with `flipped` or `augment` refuses."""
+reads it).  Evaluation wants the plain list: a data set with `flipped` or `augment` refuses.
+
+With `max_boxes` = T, get(size) returns (images, labels, truth, ntruth): the box list of the anchor model next to the
+label grid -- truth float32 [B][T][5] = cx, cy, w, h in pixels of the input and the class index of EVERY object of the
+window in annotation order, ntruth int32 [B] (augment.encode_box_list; y2_encode_box_list, csrc/augment.hip).  One more
+launch on the same stream and no further upload: the kernel reads the index and parameter tensors of the other two."""
 import ctypes as C
 import os
 import zlib
@@ -94,7 +99,7 @@ def _ptr(t):
 
 class DeviceVOC(ShardedOrder):
     def __init__(self, image_set, batch_size=None, devkit_path=None, flipped=None, seed=0, rank=0, world=1,
-                 device="cuda", max_pool_bytes=DEFAULT_MAX_POOL_BYTES, augment=None):
+                 device="cuda", max_pool_bytes=DEFAULT_MAX_POOL_BYTES, augment=None, max_boxes=None):
         from .. import config as cfg
         self.name = 'voc_2007'
         self.devkit_path = devkit_path or os.path.join('data', 'VOCdevkit')
@@ -107,6 +112,9 @@ class DeviceVOC(ShardedOrder):
         self.image_set = image_set
         self.device = device
         self._init_order(seed, rank, world)
+        if max_boxes is not None and not 1 <= int(max_boxes) <= 1024:
+            raise ValueError("max_boxes %r outside 1..1024" % (max_boxes,))
+        self.max_boxes = None if max_boxes is None else int(max_boxes)
         self.augment = augment
         if augment is not None:
             from .augment import generator
@@ -134,6 +142,7 @@ class DeviceVOC(ShardedOrder):
         self._buffers = {}
         self._params = {}
         self._eval_buffers = {}
+        self._lists = {}
 
     # ---- the only places that touch device memory at start-up (torch supplies allocations and copies)
     def _alloc_pool(self, nbytes):
@@ -179,9 +188,23 @@ class DeviceVOC(ShardedOrder):
                 torch.empty(self.batch_size, dtype=torch.int32, device=self.device))
         return self._buffers[size]
 
+    def _box_list(self, size, index, params, stream):
+        """(truth, ntruth) of the batch whose entries `index` holds: one launch behind the label kernel's"""
+        import torch
+        from .. import _lib
+        if size not in self._lists:
+            self._lists[size] = (
+                torch.empty((self.batch_size, self.max_boxes, 5), dtype=torch.float32, device=self.device),
+                torch.empty(self.batch_size, dtype=torch.int32, device=self.device))
+        truth, ntruth = self._lists[size]
+        _lib.check(_lib.load().y2_encode_box_list(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
+                                                  None if params is None else _ptr(params), self.batch_size,
+                                                  self.max_obj, size, self.max_boxes, _ptr(truth), _ptr(ntruth), stream))
+        return truth, ntruth
+
     def get(self, size):
         """(images [B, size, size, 3] uint8 BGR, labels [B, S, S, 25] float32), S = size // 32, device tensors written
-        on the current stream; asynchronous"""
+        on the current stream; asynchronous.  With max_boxes = T also truth [B, T, 5] float32 and ntruth [B] int32."""
         import torch
         from .. import _lib
         if torch.device(self.device).type != "cuda":
@@ -198,6 +221,8 @@ class DeviceVOC(ShardedOrder):
         _lib.check(lib.y2_encode_labels(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
                                         self.batch_size, self.max_obj, size, size // 32, self.num_class, _ptr(labels),
                                         stream))
+        if self.max_boxes is not None:
+            return (images, labels) + self._box_list(size, index, None, stream)
         return images, labels
 
     @property
@@ -261,4 +286,6 @@ class DeviceVOC(ShardedOrder):
         _lib.check(lib.y2_encode_labels_window(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
                                                _ptr(params), self.batch_size, self.max_obj, size, size // 32,
                                                self.num_class, _ptr(labels), stream))
+        if self.max_boxes is not None:
+            return (images, labels) + self._box_list(size, index, params, stream)
         return images, labels

@@ -194,7 +194,7 @@ class pascal_voc(ShardedOrder):
     reshuffle together.  world = 1 is the reference's cursor, entry for entry."""
 
     def __init__(self, image_set, batch_size=None, rebuild=False, devkit_path=None, image_size=None, cell_size=None,
-                 flipped=None, seed=0, cache_images=True, rank=0, world=1, augment=None):
+                 flipped=None, seed=0, cache_images=True, rank=0, world=1, augment=None, max_boxes=None):
         import os
         from .. import config as cfg
         self.name = 'voc_2007'
@@ -211,6 +211,11 @@ class pascal_voc(ShardedOrder):
         self._init_order(seed, rank, world)
         self.cache_images = cache_images
         self._cache = {}
+        # the anchor model's box list next to the grid (img_dataset/augment.encode_box_list; not in the reference): with
+        # max_boxes = T, get() and get_u8() return (images, labels, truth [B,T,5] float32, ntruth [B] int32)
+        if max_boxes is not None and not 1 <= int(max_boxes) <= 1024:
+            raise ValueError("max_boxes %r outside 1..1024" % (max_boxes,))
+        self.max_boxes = None if max_boxes is None else int(max_boxes)
         self.augment = augment
         if augment is not None:
             from .augment import generator
@@ -257,14 +262,24 @@ class pascal_voc(ShardedOrder):
             if self.cache_images:
                 self._decoded[g['imname']] = img
         row = self.augment.draw(self.aug_rng, g['shape'][0], g['shape'][1])
-        return (self.augment.image(img, row, self.image_size, self.image_size, flip=g['flipped']),
-                self.augment.label(g['objs'], row, self.image_size, self.cell_size, self.num_class, flip=g['flipped']))
+        out = (self.augment.image(img, row, self.image_size, self.image_size, flip=g['flipped']),
+               self.augment.label(g['objs'], row, self.image_size, self.cell_size, self.num_class, flip=g['flipped']))
+        if self.max_boxes is not None:
+            out += self._box_list(g, row)
+        return out
+
+    def _box_list(self, g, row=None):
+        """(truth [T,5] float32, count) of entry g: every object, under the row's window (default: the whole image)"""
+        from .augment import encode_box_list, identity_row
+        if row is None:
+            row = identity_row(g['shape'][0], g['shape'][1])
+        return encode_box_list(g['objs'], row, self.image_size, self.max_boxes, flip=g['flipped'])
 
     # ---- pascal_voc.py:42-58 (the cursor: ShardedOrder._next)
     def get(self):
-        if self.augment is not None:
-            images, labels = self.get_u8()
-            return (images.astype(np.float32) / 255.0) * 2.0 - 1.0, labels
+        if self.augment is not None or self.max_boxes is not None:
+            images, *labels = self.get_u8()
+            return ((images.astype(np.float32) / 255.0) * 2.0 - 1.0, *labels)
         images = np.zeros((self.batch_size, self.image_size, self.image_size, 3), np.float32)
         labels = np.zeros((self.batch_size, self.cell_size, self.cell_size, 25), np.float32)
         for count in range(self.batch_size):
@@ -279,11 +294,19 @@ class pascal_voc(ShardedOrder):
             else images_out
         labels = np.empty((self.batch_size, self.cell_size, self.cell_size, 25), np.float32) if labels_out is None \
             else labels_out
+        lists = self.max_boxes is not None
+        if lists:
+            truth = np.zeros((self.batch_size, self.max_boxes, 5), np.float32)
+            ntruth = np.zeros(self.batch_size, np.int32)
         for count in range(self.batch_size):
             g = self._next()
             if self.augment is not None:
-                images[count], labels[count] = self._augmented(g)
+                images[count], labels[count], *more = self._augmented(g)
+                if lists:
+                    truth[count], ntruth[count] = more
                 continue
             images[count] = self.image_read_u8(g['imname'], g['flipped'])
             labels[count] = g['label']
-        return images, labels
+            if lists:
+                truth[count], ntruth[count] = self._box_list(g)
+        return (images, labels, truth, ntruth) if lists else (images, labels)

@@ -1,11 +1,18 @@
 """Train the YOLOv2 anchor detector (yolo2_nets/yolov2.py; not in the reference, whose trainer is the grid model) on VOC:
     python -m tensorflow_yolo2_amd.pascal.pascal_train_yolov2 --devkit data/VOCdevkit --iters 20 \
         [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR]
+        [--box-labels [--max-boxes 30] [--area-weight] [--prior-images 12800]]
 The flags are pascal_train_darknet.py's where they apply.  The batches always come from the device-resident pool
 (img_dataset.device_voc.DeviceVOC.get(size)): the uint8 batch goes straight into YOLOv2Trainer.step, whose first layer
 converts it, and the label grid [N,S,S,5+C] (one box per cell) is the anchor loss's input as it stands.  --multi-scale
 redraws the size of iteration i from --ms-sizes every --ms-period iterations (trainer.multi_scale_size); --augment is
 Darknet's crop / mirror / HSV recipe in the device kernels.
+
+--box-labels trains on the box list instead (get(size) with max_boxes: truth [N,T,5] + ntruth [N], EVERY object of an
+image, so two objects of one cell both reach their anchors; engine.yolov2_loss_boxes).  With it, --area-weight is
+Darknet's (2 - w h) weight of the coord terms and --prior-images the number of images (12800 in Darknet) during which
+every prediction without an object is pulled toward its anchor.  The list encoder draws no random numbers, so a resumed
+run moves the data and augmentation streams exactly as without it; the prior's switch reads the snapshot's iteration.
 
 Snapshots are `train_iter_<i>.npz` (net_utils.save_yolov2_variables: the three stacks, the anchors, the three Adam
 states with their one loss scaler); a run with --ckpt-dir resumes from the latest, moves the data order and the
@@ -48,6 +55,11 @@ def parse_args(argv=None):
     ap.add_argument("--imagenet-ckpt-dir", default=None, help="classifier snapshots to take the backbone from")
     ap.add_argument("--anchors", default="voc", choices=("voc", "kmeans"),
                     help="voc: the published VOC anchors; kmeans: cluster the image set's boxes at --size")
+    ap.add_argument("--box-labels", action="store_true", help="train on the box list (every object), not the label grid")
+    ap.add_argument("--max-boxes", type=int, default=None, help="rows of the box list (default 30; needs --box-labels)")
+    ap.add_argument("--area-weight", action="store_true", help="coord terms times 2 - w h (needs --box-labels)")
+    ap.add_argument("--prior-images", type=int, default=0,
+                    help="images during which un-owned predictions are pulled toward their anchors (needs --box-labels)")
     ap.add_argument("--width-div", type=int, default=1, help="divide every inner width (tests)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
@@ -65,6 +77,12 @@ def parse_args(argv=None):
             ap.error("--ms-sizes: the detector head cannot take %s (positive multiples of 32 only)" % (bad or "an empty list"))
         if args.ms_period < 1:
             ap.error("--ms-period must be at least 1")
+    if not args.box_labels and (args.area_weight or args.prior_images or args.max_boxes is not None):
+        ap.error("--max-boxes, --area-weight and --prior-images need --box-labels")
+    if args.max_boxes is None:
+        args.max_boxes = 30
+    if not 1 <= args.max_boxes <= 1024 or args.prior_images < 0:
+        ap.error("--max-boxes must lie in 1..1024, --prior-images must not be negative")
     args.augmentation = None
     if args.augment:
         from ..img_dataset.augment import Augment
@@ -97,7 +115,7 @@ def main(argv=None):
     args = parse_args(argv)
     from ..img_dataset.device_voc import DeviceVOC
     imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
-                     seed=args.seed, augment=args.augmentation)
+                     seed=args.seed, augment=args.augmentation, max_boxes=args.max_boxes if args.box_labels else None)
     latest = None
     if args.ckpt_dir:
         os.makedirs(args.ckpt_dir, exist_ok=True)
@@ -116,7 +134,8 @@ def main(argv=None):
         anchors = yolov2.ANCHORS_VOC
     first = step_size(args, 1) if args.multi_scale else args.size
     trainer = yolov2.YOLOv2Trainer(args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
-                                   seed=args.seed, width_div=args.width_div)
+                                   seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
+                                   prior_images=args.prior_images)
     last_iter_num = 0
     if latest:
         print('Restorining model snapshots from {:s}'.format(latest))
@@ -133,8 +152,12 @@ def main(argv=None):
     losses, sizes = [], []
     for i in range(last_iter_num + 1, TOTAL_ITER + 1):
         size = step_size(args, i)
-        image, gt_labels = imdb.get(size)                     # two kernels on this stream, no host pixel work
-        loss = trainer.step(image, gt_labels)
+        if args.box_labels:
+            image, _grid, truth, ntruth = imdb.get(size)      # three kernels on this stream, no host pixel work
+            loss = trainer.step(image, truth=truth, ntruth=ntruth)
+        else:
+            image, gt_labels = imdb.get(size)                 # two kernels on this stream, no host pixel work
+            loss = trainer.step(image, gt_labels)
         losses.append(loss.cpu().numpy().copy())              # coord, object, noobject, class, total
         sizes.append(size)
         if i % 10 == 0:

@@ -86,13 +86,16 @@ class YOLOv2Trainer:
     bound to the same three parameter sets (engine.Network(share_with=...))."""
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0", scales=None, width_div=1):
+                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01):
         from ..trainer import GradReducer
         self._GradReducer = GradReducer
         self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
         self.anchors = np.asarray(anchors, np.float32)
         self.B = len(self.anchors)
         self.scales = scales
+        # box-list labels only (step(images, truth=..., ntruth=...)): Darknet's (2 - w h) coord weight, and its anchor-prior
+        # term while fewer than prior_images images have been seen ((iteration - 1) * batch, counted over resumed runs)
+        self.area_weight, self.prior_images, self.prior_scale = bool(area_weight), int(prior_images), float(prior_scale)
         self.iteration = 0                                   # train steps taken, over resumed runs (net_utils snapshots)
         sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
         self.specs = (sa, sb, sc)
@@ -140,9 +143,25 @@ class YOLOv2Trainer:
         out = head.forward(cat, training, training, update_moving=update_moving)
         return out.view(self.batch, S, S, self.B, 5 + self.num_class), fine
 
-    def step(self, images, labels):
-        """one train step; returns loss[5] = coord, object, noobject, class, total"""
+    def prior_on(self, iteration=None):
+        """whether the anchor-prior term is part of train step `iteration` (1-based; default: the next one)"""
+        i = self.iteration + 1 if iteration is None else int(iteration)
+        return (i - 1) * self.batch < self.prior_images
+
+    def box_scales(self, iteration=None):
+        """the scale set of engine.yolov2_loss_boxes at a train step: `scales` + the area weight + the prior while on"""
+        sc = dict(self.scales or {})
+        sc["area_weight"] = 1.0 if self.area_weight else 0.0
+        sc["prior_scale"] = self.prior_scale if self.prior_on(iteration) else 0.0
+        return sc
+
+    def step(self, images, labels=None, truth=None, ntruth=None):
+        """one train step on the label grid `labels` [N,S,S,5+C] (one box per cell) or on the box list `truth` [N,T,5] +
+        `ntruth` [N] (every object; DeviceVOC(..., max_boxes=T)): exactly one of the two forms.  Returns loss[5] = coord,
+        object, noobject, class, total"""
         from ..trainer import _dist
+        if (labels is None) == (truth is None) or (truth is None) != (ntruth is None):
+            raise ValueError("step() takes either labels or truth + ntruth, not both and not neither")
         size = int(images.shape[1])
         stem, deep, head = self._nets(size)
         for net in (stem, deep, head):
@@ -150,7 +169,12 @@ class YOLOv2Trainer:
                 net.params_changed()              # shared parameters moved under another size's contexts
         self.iteration += 1
         grid, fine = self.forward(images, True, update_moving=True)
-        loss, dnet = E.yolov2_loss(grid.contiguous(), labels, self.anchors, size, True, self.scales)
+        if labels is not None:
+            loss, dnet = E.yolov2_loss(grid.contiguous(), labels, self.anchors, size, True, self.scales)
+        else:
+            loss, dnet = E.yolov2_loss_boxes(grid.contiguous(), truth, ntruth, self.anchors, size, True,
+                                             self.box_scales(self.iteration))
+        self.last_dnet = dnet                                # the head's output gradient of this step (tests read it)
         dist = _dist()
         red = self.reducers[size]
         dcat = head.backward_input(dnet.view(self.batch, size // 32, size // 32, -1))
