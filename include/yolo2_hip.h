@@ -498,6 +498,18 @@ int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32
 int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
                            int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out, int* det,
                            float* score, int* count, void* stream);
+/* One row per (candidate, class) instead of one per candidate, as Darknet's `valid` writes them (specification:
+ * utils/detect_batch.anchor_detect_classes on the outputs of y2_decode_anchors, bit for bit).  Class c of an image is a
+ * segment of its own: the rows of y2_detect_anchor_batch had every candidate the class c and the score score[c], so a
+ * candidate is valid in every class whose score is > score_thresh, and the ordering and the walk run per class.
+ * det int32 [n][num_class][max_per_class][6] = xmin, ymin, xmax, ymax, c, i (unused rows all -1);
+ * score [n][num_class][max_per_class] (unused 0); count int32 [n][num_class].  The [n * num_class][max_per_class][6] view
+ * of det, with count and an index vector that names each image num_class times, is what y2_voc_match_batch reads.
+ * Limits as y2_detect_anchor_batch, and n up to 65535.  One workgroup per (class, image), one launch; nothing is
+ * allocated. */
+int y2_detect_anchor_classes_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
+                                   int n, int S, int B, int num_class, float score_thresh, float iou_thresh,
+                                   int max_per_class, int* det, float* score, int* count, void* stream);
 /* flags int32 [n][max_out]: 1 true positive, 0 false positive, 2 ignored, -1 beyond count.  The rows of an image are
  * walked in order (descending score): among the image's objects of the row's class, the first maximum of the float64
  * IoU, taken objects included; none, or IoU < iou_thresh: false positive; else a difficult object: ignored; an object

@@ -1,5 +1,6 @@
 // Evaluation of the detectors on the device (pascal/pascal_eval_darknet.py, pascal/pascal_eval_yolov2.py): per image, the
-// head's output (the grid head's, or the raw anchor head's: detect_anchor_kernel, specified by anchor_detect) decoded
+// head's output (the grid head's, or the raw anchor head's: detect_anchor_kernel, specified by anchor_detect; with one
+// row per class instead of the best class: detect_anchor_classes_kernel, specified by anchor_detect_classes) decoded
 // into boxes in the pixels of the ORIGINAL image, a score-ordered class-aware greedy NMS, and the VOC devkit's matching
 // of the surviving rows against the image's ground truth.  The specification is this repository's host code
 // (utils/detect_batch.py: grid_detect, match_image) and both kernels are bit-equal to it: the decoded products and every
@@ -271,6 +272,127 @@ __global__ __launch_bounds__(kAnchorLanes) void detect_anchor_kernel(const float
     for (int i = kept + tid; i < max_out; i += nt) srow[i] = 0.0f;
 }
 
+// ---- one row per (candidate, class), as Darknet's `valid` writes: y2_detect_anchor_classes_batch ----------------------
+constexpr int kClassLanes = 512;                       // the workgroup: n * C of them, up to three resident on a CU
+constexpr int kClassSlotBytes = 8 + 4 * 4 + 1;         // sort word, four corners, suppressed flag: 50 KB at 2048
+
+// grid (C, n), one workgroup per (class, image) of min(KP, 512) lanes, KP = the next power of two of K (64 .. 2048).
+//   1. every lane decodes candidates lane, lane + lanes, ... from the raw head as detect_anchor_kernel does (the C
+//      workgroups of an image repeat the box, and the softmax's normaliser where the objectness passes the threshold by
+//      itself) but scores ONE class.  A valid candidate
+//      writes its corners at its own index and its sort word at the next free COMPACT slot: per wave and round one
+//      ballot, one LDS atomicAdd of the wave's count by its first lane, each lane's slot from the prefix of the ballot.
+//      Which slot a word lands in cannot show: the words are distinct and the sort is total.
+//   2. nvalid is uniform after the barrier; the bitonic sort runs over NP = the next power of two of nvalid (at least
+//      64) and not over KP: the slots nvalid .. NP are filled with words below every valid one (-inf).
+//   3. detect_anchor_kernel's walk without the class test: the segment holds one class.
+__global__ __launch_bounds__(kClassLanes) void detect_anchor_classes_kernel(
+    const float* __restrict__ net, const float* __restrict__ anchors, const int64_t* __restrict__ table,
+    const int32_t* __restrict__ index, int S, int B, int C, float score_thresh, float iou_thresh, int max_out, int KP,
+    int* __restrict__ det, float* __restrict__ score, int* __restrict__ count) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // kClassSlotBytes per slot
+    uint64_t* sword = (uint64_t*)smem;
+    int* bx0 = (int*)(sword + KP);
+    int *by0 = bx0 + KP, *bx1 = by0 + KP, *by1 = bx1 + KP;
+    unsigned char* sup = (unsigned char*)(by1 + KP);
+    __shared__ int s_valid;
+    const int cls = blockIdx.x, img = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+    const int lane = tid & (kWave - 1);
+    const int K = S * S * B, D = 5 + C;
+    const int64_t* t = table + (size_t)kTable * (index ? index[img] : img);
+    const int64_t h64 = t[1], w64 = t[2];
+    const bool sized = h64 >= 1 && w64 >= 1 && h64 <= 0x7fffffff && w64 <= 0x7fffffff;
+    const int im_h = sized ? (int)h64 : 1, im_w = sized ? (int)w64 : 1;
+    const float* rows = net + (size_t)img * K * D;
+    if (tid == 0) s_valid = 0;
+    __syncthreads();
+    for (int base = 0; base < K; base += nt) {                    // uniform trips: every lane of a wave meets the ballot
+        const int i = base + tid;
+        bool valid = false;
+        float v = -INFINITY;
+        if (i < K && sized) {
+            const int cell = i / B, b = i - cell * B;
+            const int row = cell / S, col = cell - row * S;
+            const float* p = rows + (size_t)i * D;
+            const AnchorBox bx = anchor_decode_box(p, anchors, b, row, col, S);
+            // score = so * (expf(<= 0) / sum) and sum holds the term expf(0) = 1, so score <= so in float32 (or it is
+            // NaN): a candidate whose objectness alone does not pass is not valid in ANY class, and on a trained head
+            // that is nearly all of them -- the class logits are not even read
+            if (bx.so > score_thresh) {
+                float mx, sum;
+                anchor_softmax_norm(p, C, mx, sum);
+                v = anchor_class_score(p, cls, bx.so, mx, sum);
+            }
+            const double dx = (double)bx.cx * (double)im_w, dy = (double)bx.cy * (double)im_h;
+            const double dw = (double)bx.w * (double)im_w, dh = (double)bx.h * (double)im_h;
+            const double lim = 1073741824.0;                              // 2^30: checked BEFORE any conversion to int
+            valid = v > score_thresh && fabs(dx) < lim && fabs(dy) < lim && fabs(dw) < lim && fabs(dh) < lim;
+            if (valid) {
+                const int x = (int)dx, y = (int)dy, w = (int)dw, h = (int)dh;   // >> 1 on an int is floor(. / 2)
+                const int ulx = x - (w >> 1), uly = y - (h >> 1);
+                const int xmin = max(ulx, 0), ymin = max(uly, 0);
+                const int xmax = min(ulx + w - 1, im_w - 1), ymax = min(uly + h - 1, im_h - 1);
+                valid = xmax >= xmin && ymax >= ymin;
+                bx0[i] = xmin + 1; by0[i] = ymin + 1; bx1[i] = xmax + 1; by1[i] = ymax + 1;
+            }
+        }
+        const unsigned long long mask = __ballot(valid);
+        int first = 0;
+        if (lane == 0 && mask) first = atomicAdd(&s_valid, __popcll(mask));
+        first = __shfl(first, 0, kWave);
+        if (valid) sword[first + __popcll(mask & ((1ull << lane) - 1ull))] = sort_word(v, i);
+    }
+    __syncthreads();
+    const int nvalid = s_valid;                                   // <= K <= KP
+    int NP = kWave;
+    while (NP < nvalid) NP <<= 1;
+    for (int i = tid; i < NP; i += nt) {
+        if (i >= nvalid) sword[i] = sort_word(-INFINITY, i);      // a valid score is > score_thresh >= -inf
+        sup[i] = 0;
+    }
+    __syncthreads();
+    for (int k = 2; k <= NP; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int pr = tid; pr < (NP >> 1); pr += nt) {
+                const int lo = pr & (j - 1);
+                const int i = ((pr - lo) << 1) | lo, l = i | j;
+                const uint64_t a = sword[i], b = sword[l];
+                const bool desc = (i & k) == 0;
+                if (desc ? a < b : a > b) {
+                    sword[i] = b;
+                    sword[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    const double thr = (double)iou_thresh;
+    const size_t seg = (size_t)img * C + cls;
+    int* drow = det + seg * max_out * 6;
+    float* srow = score + seg * max_out;
+    int kept = 0;
+    for (int i = 0; i < nvalid && kept < max_out; ++i) {
+        if (sup[i]) continue;
+        const uint64_t wd = sword[i];
+        const int o = word_index(wd);
+        const double a0 = bx0[o], a1 = by0[o], a2 = bx1[o], a3 = by1[o];
+        if (tid == 0) {
+            int* d = drow + (size_t)kept * 6;
+            d[0] = bx0[o]; d[1] = by0[o]; d[2] = bx1[o]; d[3] = by1[o]; d[4] = cls; d[5] = o;
+            srow[kept] = word_key(wd);
+        }
+        for (int j = i + 1 + tid; j < nvalid; j += nt) {
+            if (sup[j]) continue;
+            const int q = word_index(sword[j]);
+            if (iou_voc(a0, a1, a2, a3, bx0[q], by0[q], bx1[q], by1[q]) > thr) sup[j] = 1;
+        }
+        ++kept;
+        __syncthreads();
+    }
+    if (tid == 0) count[seg] = kept;
+    for (int i = kept * 6 + tid; i < max_out * 6; i += nt) drow[i] = -1;
+    for (int i = kept + tid; i < max_out; i += nt) srow[i] = 0.0f;
+}
+
 // first maximum over the wave of (iou, object index): the larger iou, ties to the lower index
 Y2_DEV void wave_first_max(double& best, int& arg) {
 #pragma unroll
@@ -397,6 +519,33 @@ int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t
                        count);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_anchor_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_detect_anchor_classes_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
+                                   int n, int S, int B, int num_class, float score_thresh, float iou_thresh,
+                                   int max_per_class, int* det, float* score, int* count, void* stream) {
+    if (!net || !anchors || !table || !det || !score || !count)
+        return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: null pointer");
+    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: n = %d outside 1..65535", n);
+    if (max_per_class < 1)
+        return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: max_per_class = %d", max_per_class);
+    if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
+        return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: S = %d, B = %d (at most 16), num_class = %d", S, B,
+                    num_class);
+    if (S * S * B > kAnchorMaxCand)
+        return fail(Y2_ERR_ARG,
+                    "y2_detect_anchor_classes_batch: S * S * B = %d candidates beyond "
+                    "Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d",
+                    S * S * B, kAnchorMaxCand);
+    int KP = kWave;
+    while (KP < S * S * B) KP <<= 1;
+    const int lanes = KP < kClassLanes ? KP : kClassLanes;
+    hipLaunchKernelGGL(detect_anchor_classes_kernel, dim3(num_class, n), dim3(lanes), (size_t)KP * kClassSlotBytes,
+                       (hipStream_t)stream, net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh,
+                       max_per_class, KP, det, score, count);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_anchor_classes_batch: %s", hipGetErrorString(e));
     return Y2_OK;
 }
 

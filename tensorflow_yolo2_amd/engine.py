@@ -939,6 +939,43 @@ def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou
     return det, score, count
 
 
+def detect_anchor_classes_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_per_class=32,
+                                out=None):
+    """detect_anchor_batch's arguments -> (det int32 [n,C,max_per_class,6], score [n,C,max_per_class], count int32
+    [n,C]): one row per (candidate, class) whose score passes, each class ordered and walked on its own, as Darknet's
+    `valid` writes them (utils/detect_batch.anchor_detect_classes on decode_anchors of the same net, bit for bit).
+    det.view(n * C, max_per_class, 6) with count.view(-1) and every index repeated C times is what voc_match_batch
+    reads."""
+    lib = _lib.load()
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, S, _, B, d = net.shape
+    assert net.shape[2] == S and d > 5, net.shape
+    C = d - 5
+    if torch.is_tensor(anchors):
+        an = anchors
+        assert an.is_cuda and an.dtype == torch.float32 and an.is_contiguous()
+    else:
+        an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
+    assert an.numel() == 2 * B, (tuple(an.shape), B)
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert table.shape[0] >= n
+    if out is None:
+        out = (torch.empty((n, C, max_per_class, 6), dtype=torch.int32, device=net.device),
+               torch.empty((n, C, max_per_class), dtype=torch.float32, device=net.device),
+               torch.empty((n, C), dtype=torch.int32, device=net.device))
+    det, score, count = out
+    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * C * max_per_class * 6
+    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * C * max_per_class
+    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n * C
+    check(lib.y2_detect_anchor_classes_batch(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C,
+                                             float(score_thresh), float(iou_thresh), int(max_per_class), _ptr(det),
+                                             _ptr(score), _ptr(count), _stream()))
+    return det, score, count
+
+
 def voc_match_batch(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):
     """det int32 [n,max_out,6], score [n,max_out], count [n] (detect_grid_batch); boxes float64 [entries,max_obj,5],
     counts int32 [entries], difficult uint8 [entries,max_obj] (DeviceVOC) -> flags int32 [n,max_out]: 1 true positive,

@@ -1,6 +1,7 @@
 """VOC mAP of the YOLOv2 anchor detector over an image set (not in the reference, which has no evaluation code):
     python -m tensorflow_yolo2_amd.pascal.pascal_eval_yolov2 --devkit data/VOCdevkit --image-set test \
         [--weights FILE | --ckpt-dir DIR] [--size 416] [--batch 32] [--metric 07|10]
+        [--per-class [--max-per-class 32]] [--results-dir DIR]
 The shape is pascal_eval_darknet.py's.  The images come from the device-resident pool in list order; per batch, four
 calls on one stream and nothing on the host:
     DeviceVOC.eval_batch (resize) -> YOLOv2Detector.detect_batch = forward on the uint8 batch (moving statistics) ->
@@ -8,9 +9,11 @@ calls on one stream and nothing on the host:
     one launch from the raw head) -> y2_voc_match_batch (TP / FP / ignored against the image's ground truth)
 The det / score / count / flags of every batch land in ONE device buffer; after the last batch it is copied to the host
 once and utils/detect_batch.map_from_flags makes the per-class curves and the APs.  A detection is an anchor's box with
-its best class (score = objectness * class probability): one row per anchor, not one per class as Darknet's `valid`
-writes.  The anchors and the class count are the snapshot's (pascal_train_yolov2.py); with neither --weights nor
---ckpt-dir the initial values are evaluated with the published VOC anchors: a plumbing run."""
+its best class (score = objectness * class probability): one row per anchor.  With --per-class it is a row per class
+whose score passes, as Darknet's `valid` writes (y2_detect_anchor_classes_batch; the matcher then runs over the
+(image, class) segments): the protocol of the published YOLOv2 figures, up to this repository's integer-pixel IoU.
+The anchors and the class count are the snapshot's (pascal_train_yolov2.py); with neither --weights nor --ckpt-dir the
+initial values are evaluated with the published VOC anchors: a plumbing run."""
 import argparse
 import sys
 
@@ -35,6 +38,16 @@ def parse_args(argv=None):
     ap.add_argument("--thresh", type=float, default=0.005, help="score above which a box is a detection")
     ap.add_argument("--nms", type=float, default=0.45, help="IoU above which a box of the same class is suppressed")
     ap.add_argument("--max-out", type=int, default=100, help="detections kept per image")
+    ap.add_argument("--per-class", action="store_true",
+                    help="one row per (box, class) whose score passes, NMS per class: the rows Darknet's `valid` writes "
+                         "and the published mAP figures are scored on (default: one row per box, its best class)")
+    ap.add_argument("--max-per-class", type=int, default=32,
+                    help="with --per-class: rows kept per image and class (Darknet has no cap: the count of saturated "
+                         "segments is printed).  The device buffer takes 32 bytes per row, images x classes x this "
+                         "many rows: about 100 MB for VOC07 test at the default")
+    ap.add_argument("--results-dir", default=None,
+                    help="write the devkit's comp4_det_<image-set>_<class>.txt files (image_id score xmin ymin xmax "
+                         "ymax) there, from the rows of either form")
     ap.add_argument("--metric", default="07", choices=("07", "10"), help="07: 11-point AP; 10: area under the envelope")
     ap.add_argument("--width-div", type=int, default=1, help="divide every inner width (tests)")
     ap.add_argument("--keep-grids", action="store_true", help="return the raw head outputs of every image (tests)")
@@ -43,8 +56,8 @@ def parse_args(argv=None):
         ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
     if (args.size // 32) ** 2 * len(yolov2.ANCHORS_VOC) > 2048:
         ap.error("--size %d: more than 2048 candidates per image" % args.size)
-    if args.batch < 1 or args.max_out < 1 or args.width_div < 1:
-        ap.error("--batch, --max-out and --width-div must be at least 1")
+    if args.batch < 1 or args.max_out < 1 or args.width_div < 1 or args.max_per_class < 1:
+        ap.error("--batch, --max-out, --max-per-class and --width-div must be at least 1")
     return args
 
 
@@ -68,55 +81,79 @@ def main(argv=None):
         print('Restorining model from weight file {:s}'.format(snapshot))
         restored = net_utils.restore_yolov2_variables(detector, snapshot)
     result = evaluate_yolov2(detector, imdb, args.size, args.thresh, args.nms, args.max_out, args.metric == "07",
-                             args.keep_grids)
+                             args.keep_grids, args.per_class, args.max_per_class)
     for c in sorted(result["aps"]):
         print('AP for {:s} = {:.4f}'.format(pascal_voc.CLASSES[c], result["aps"][c]))
     print('Mean AP = {:.4f} ({:d} images, {:d} detections, VOC{:s} metric)'.format(
         result["mAP"], len(imdb.entries), len(result["rows"]["flag"]), "07" if args.metric == "07" else "10+"))
+    if args.per_class:
+        print('{:d} of {:d} (image, class) segments reached --max-per-class {:d}'.format(
+            result["saturated"], result["count"].size, args.max_per_class))
+    if args.results_dir:
+        from ..utils import voc_eval
+        result["results_files"] = voc_eval.write_results_files(args.results_dir, args.image_set, imdb.image_index,
+                                                               pascal_voc.CLASSES[:num_class], result["rows"])
     result.update(restored=restored, detector=detector, imdb=imdb)
     return result
 
 
-def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, use_07_metric=True, keep_grids=False):
+def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, use_07_metric=True, keep_grids=False,
+                    per_class=False, max_per_class=32):
     """one pass over imdb's image list through `detector` (a YOLOv2Detector of imdb.batch_size images of `size`):
     {"mAP", "aps", "rows", "count", "npos"[, "grids"]} as pascal_eval_darknet.evaluate; everything per image runs on the
-    device, one copy at the end"""
+    device, one copy at the end.  per_class: one row per (candidate, class) as Darknet's `valid` writes them, at most
+    max_per_class per image and class (max_out is not read); an image is then num_class segments of the same buffer,
+    "count" is [entries][num_class] and "saturated" the number of segments whose count reached max_per_class"""
     n = imdb.batch_size
     assert detector.batch == n and detector.size == size, (detector.batch, detector.size, n, size)
     S, B, D = detector.S, detector.B, 5 + detector.num_class
     entries = len(imdb.entries)
     batches = (entries + n - 1) // n
-    N = batches * n
-    # det [N][max_out][6] | score [N][max_out] (float bits) | flags [N][max_out] | count [N]: one buffer, one copy
-    words = N * max_out * 8 + N
+    # a segment is what the matcher walks as one "image": the image, or with per_class one class of it
+    segs, R = (detector.num_class, max_per_class) if per_class else (1, max_out)
+    N = batches * n * segs
+    # det [N][R][6] | score [N][R] (float bits) | flags [N][R] | count [N]: one buffer, one copy
+    words = N * R * 8 + N
     acc = torch.empty(words, dtype=torch.int32, device="cuda")
-    det = acc[:N * max_out * 6].view(N, max_out, 6)
-    score = acc[N * max_out * 6:N * max_out * 7].view(torch.float32).view(N, max_out)
-    flags = acc[N * max_out * 7:N * max_out * 8].view(N, max_out)
-    count = acc[N * max_out * 8:]
-    grids = torch.empty((N, S, S, B, D), dtype=torch.float32, device="cuda") if keep_grids else None
+    det = acc[:N * R * 6].view(N, R, 6)
+    score = acc[N * R * 6:N * R * 7].view(torch.float32).view(N, R)
+    flags = acc[N * R * 7:N * R * 8].view(N, R)
+    count = acc[N * R * 8:]
+    grids = torch.empty((batches * n, S, S, B, D), dtype=torch.float32, device="cuda") if keep_grids else None
+    seg_index = torch.empty(n * segs, dtype=torch.int32, device="cuda") if per_class else None
     difficult = imdb.difficult
     for k in range(batches):
-        lo = k * n
-        images, _valid = imdb.eval_batch(size, lo)
-        detector.detect_batch(images, imdb.table, imdb.eval_index, thresh, nms, max_out,
-                              out=(det[lo:lo + n], score[lo:lo + n], count[lo:lo + n]),
-                              grid_out=grids[lo:lo + n] if grids is not None else None)
-        engine.voc_match_batch(det[lo:lo + n], score[lo:lo + n], count[lo:lo + n], imdb.boxes, imdb.counts, difficult,
-                               imdb.eval_index, 0.5, out=flags[lo:lo + n])
+        lo, m = k * n * segs, n * segs
+        images, _valid = imdb.eval_batch(size, k * n)
+        out = (det[lo:lo + m], score[lo:lo + m], count[lo:lo + m])
+        grid_out = grids[k * n:k * n + n] if grids is not None else None
+        index = imdb.eval_index
+        if per_class:
+            detector.detect_classes_batch(images, imdb.table, index, thresh, nms, max_per_class, out=out,
+                                          grid_out=grid_out)
+            seg_index.view(n, segs).copy_(index[:n, None].expand(n, segs))   # on the device: nothing waits
+            index = seg_index
+        else:
+            detector.detect_batch(images, imdb.table, index, thresh, nms, max_out, out=out, grid_out=grid_out)
+        engine.voc_match_batch(det[lo:lo + m], score[lo:lo + m], count[lo:lo + m], imdb.boxes, imdb.counts, difficult,
+                               index, 0.5, out=flags[lo:lo + m])
     host = acc.cpu().numpy()                                  # the one device-to-host copy (it waits for the stream)
-    det_h = host[:N * max_out * 6].reshape(N, max_out, 6)[:entries]
-    score_h = host[N * max_out * 6:N * max_out * 7].view(np.float32).reshape(N, max_out)[:entries]
-    flags_h = host[N * max_out * 7:N * max_out * 8].reshape(N, max_out)[:entries]
-    count_h = host[N * max_out * 8:][:entries]
-    live = np.arange(max_out)[None, :] < count_h[:, None]      # image order, each image's rows in descending score
-    rows = {"image": np.nonzero(live)[0], "box": det_h[live][:, :4], "class": det_h[live][:, 4],
+    live_segs = entries * segs
+    det_h = host[:N * R * 6].reshape(N, R, 6)[:live_segs]
+    score_h = host[N * R * 6:N * R * 7].view(np.float32).reshape(N, R)[:live_segs]
+    flags_h = host[N * R * 7:N * R * 8].reshape(N, R)[:live_segs]
+    count_h = host[N * R * 8:][:live_segs]
+    live = np.arange(R)[None, :] < count_h[:, None]            # image order (then class), each segment in descending score
+    rows = {"image": np.nonzero(live)[0] // segs, "box": det_h[live][:, :4], "class": det_h[live][:, 4],
             "candidate": det_h[live][:, 5], "score": score_h[live], "flag": flags_h[live]}
     npos = detect_batch.npos_from_objects([o[4] for e in imdb.entries for o in e['objs']],
                                           [d for e in imdb.entries for d in e['difficult']])
     mAP, aps = detect_batch.map_from_flags((rows["class"], rows["score"], rows["flag"]), npos,
                                            use_07_metric=use_07_metric)
     result = {"mAP": mAP, "aps": aps, "rows": rows, "count": count_h.copy(), "npos": npos}
+    if per_class:
+        result["count"] = result["count"].reshape(entries, segs)
+        result["saturated"] = int((count_h >= max_per_class).sum())
     if grids is not None:
         result["grids"] = grids[:entries]
     return result

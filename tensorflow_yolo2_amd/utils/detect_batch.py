@@ -9,6 +9,8 @@ specification of csrc/augment.hip:
                   csrc/loss.hip: decode_kernel) and the box is utils/voc_eval.detections_from_decode's.
   anchor_detect   the same rows for the YOLOv2 anchor head, from the outputs of y2_decode_anchors + y2_class_argmax
                   (kernel: y2_detect_anchor_batch, which decodes the raw head itself); shares grid_detect's walk.
+  anchor_detect_classes  one row per (candidate, class) from y2_decode_anchors' scores [K][C]: anchor_detect per class
+                  (kernel: y2_detect_anchor_classes_batch); class_rows flattens a batch of them for map_from_flags.
   match_image     the body of utils/voc_eval.eval_class for one image: a TP / FP / ignored flag per detection.
   map_from_flags  the global part: per class a stable sort by score, cumulative sums, utils/voc_eval.average_precision.
 
@@ -127,6 +129,37 @@ def anchor_detect(boxes, best, cls, im_w, im_h, score_thresh, iou_thresh, max_ou
     xmax, ymax, class, candidate index; score float32 [count]); the specification of y2_detect_anchor_batch"""
     valid, box, cls, score = anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh)
     return _greedy_walk(valid, box, cls, score, iou_thresh, max_out)
+
+
+def anchor_detect_classes(boxes, scores, im_w, im_h, score_thresh, iou_thresh, max_per_class):
+    """one row per (candidate, class), as Darknet's `valid` writes them: boxes float32 [K][4] and scores float32 [K][C]
+    of ONE image (what y2_decode_anchors writes) -> (det int32 [C][max_per_class][6], unused rows -1; score float32
+    [C][max_per_class], unused 0; count int32 [C]).  Class c's rows are anchor_detect's with every candidate given the
+    class c and the score scores[:, c]: a candidate is valid in every class whose score passes, and each class is
+    ordered and walked on its own.  Column 4 is c, column 5 the candidate; the specification of
+    y2_detect_anchor_classes_batch"""
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    scores = np.asarray(scores, np.float32)
+    scores = scores.reshape(len(boxes), -1)
+    K, C = scores.shape
+    det = np.full((C, max_per_class, 6), -1, np.int32)
+    score = np.zeros((C, max_per_class), np.float32)
+    count = np.zeros(C, np.int32)
+    for c in range(C):
+        d, s = anchor_detect(boxes, scores[:, c], np.full(K, c), im_w, im_h, score_thresh, iou_thresh, max_per_class)
+        count[c] = len(d)
+        det[c, :len(d)] = d
+        score[c, :len(d)] = s
+    return det, score, count
+
+
+def class_rows(det, score, count, flags):
+    """a batch of anchor_detect_classes outputs (det [n][C][M][6], score [n][C][M], count [n][C]) with the flags of
+    match_image per (image, class) segment (flags [n][C][M]) -> the (class, score, flag) rows map_from_flags takes:
+    image-major, then class, then rank"""
+    det, score, count, flags = (np.asarray(a) for a in (det, score, count, flags))
+    live = np.arange(det.shape[2])[None, None, :] < count[:, :, None]
+    return det[live][:, 4], score[live], flags[live]
 
 
 def match_image(det, gt_boxes, gt_difficult, iou_thresh=0.5):

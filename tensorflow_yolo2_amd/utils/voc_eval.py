@@ -92,6 +92,26 @@ def voc_map(detections, ground_truth, num_class=20, iou_thresh=0.5, use_07_metri
     return (float(np.mean(list(aps.values()))) if aps else 0.0), aps
 
 
+def write_results_files(directory, image_set, image_ids, class_names, rows):
+    """the devkit's results files, as Darknet's `valid` writes and voc_eval.py tools read them: one
+    comp4_det_<image_set>_<class>.txt per class (an empty file for a class without rows), one line
+    `image_id score xmin ymin xmax ymax` per row.  rows: {"image": position in image_ids [N], "class" [N], "score" [N],
+    "box" [N][4]} in any order (the rows of either evaluator); a class's lines keep the order of its rows -> the paths"""
+    import os
+    os.makedirs(directory, exist_ok=True)
+    image, cls, score = (np.asarray(rows[k]).reshape(-1) for k in ("image", "class", "score"))
+    box = np.asarray(rows["box"]).reshape(-1, 4)
+    paths = []
+    for c, name in enumerate(class_names):
+        path = os.path.join(directory, "comp4_det_%s_%s.txt" % (image_set, name))
+        with open(path, "w") as f:
+            for k in np.nonzero(cls == c)[0]:
+                x0, y0, x1, y1 = (int(v) for v in box[k])
+                f.write("%s %.6f %d %d %d %d\n" % (image_ids[int(image[k])], float(score[k]), x0, y0, x1, y1))
+        paths.append(path)
+    return paths
+
+
 def detections_from_decode(image_id, dets):
     """decode_yolo_detection tuples (upper_left_x, upper_left_y, w, h, class, confidence, ...) -> voc_map rows"""
     return [(image_id, int(d[4]), float(d[5]), d[0], d[1], d[0] + d[2] - 1, d[1] + d[3] - 1) for d in dets]

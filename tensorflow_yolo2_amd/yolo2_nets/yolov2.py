@@ -78,6 +78,15 @@ class YOLOv2Detector:
         grid = self.forward(images_u8, out=grid_out)
         return E.detect_anchor_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh, max_out, out=out)
 
+    def detect_classes_batch(self, images_u8, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_per_class=32,
+                             out=None, grid_out=None):
+        """detect_batch with one row per (candidate, class), as Darknet's `valid` scores a detector ->
+        (det int32 [N,C,max_per_class,6], score [N,C,max_per_class], count [N,C]): engine.detect_anchor_classes_batch on
+        the raw head"""
+        grid = self.forward(images_u8, out=grid_out)
+        return E.detect_anchor_classes_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh,
+                                             max_per_class, out=out)
+
 
 class YOLOv2Trainer:
     """Train step of the YOLOv2 detector (NOT in the reference: its trainer is the YOLOv1 grid model).
