@@ -390,6 +390,37 @@ int y2_adam_step_packed(y2_ctx* ctx, float* m, float* v, void* ctrl, int step, f
 int y2_momentum_step_packed(y2_ctx* ctx, float* accum, void* ctrl, float lr, float momentum, float grad_mult,
                             void* stream);
 
+/* ---- Darknet's SGD solver (YOLOv2's recipe; the reference has no counterpart.  Specification: utils/solver.py).
+ * The record: Darknet's learning_rate, momentum, decay, policy, burn_in, power, steps / scales and max_batches.
+ *   rate(t), t >= 1 the applied step:  t < burn_in: lr (t / burn_in)^power;  else constant: lr;  steps: lr times
+ *   scales[i] of every steps[i] <= t;  poly: lr max(0, 1 - t / max_batches)^power.  Double arithmetic on the widened
+ *   floats, powers as repeated products, one cast to float: the host routine and the device schedule agree bit for bit.
+ *   update:  gd = g grad_mult (+ decay p for convolution filters only);  accum = momentum accum + gd;  p -= rate accum.
+ * The losses of this library are batch means: learning_rate times the mean gradient is Darknet's learning_rate / batch
+ * times its summed gradient, so the cfg's value is the one to give. */
+#define Y2_POLICY_CONSTANT 0
+#define Y2_POLICY_STEPS 1
+#define Y2_POLICY_POLY 2
+#define Y2_SOLVER_MAX_STEPS 8
+typedef struct y2_sgd_solver {
+    float learning_rate, momentum, decay;
+    int policy, burn_in, power, max_batches, nsteps;
+    int steps[Y2_SOLVER_MAX_STEPS];
+    float scales[Y2_SOLVER_MAX_STEPS];
+} y2_sgd_solver;
+/* host only, no GPU work: *rate = rate(t).  Y2_ERR_ARG on an invalid record or t < 1 */
+int y2_solver_rate(const y2_sgd_solver* solver, int t, float* rate);
+/* The step over a bound training context's parameters / gradients: y2_sgd_step is the flat form (the packed filter
+ * copies are marked stale, as by y2_params_changed), y2_sgd_step_packed the one fused with the filter re-pack, same
+ * bits.  accum: one slot per parameter.  ctrl / step as y2_adam_step_packed: ctrl NULL -- the host gives step >= 1
+ * and computes the rate; ctrl with step >= 0 -- run y2_grad_check first; a clean flag advances ctrl.step and sets
+ * ctrl.lr_t = rate(ctrl.step) on the device, a set flag counts ctrl.skipped and moves nothing, the schedule included;
+ * ctrl with step < 0 -- another stack of the same composed step advanced the control block: use it as it stands. */
+int y2_sgd_step(y2_ctx* ctx, float* accum, void* ctrl, int step, const y2_sgd_solver* solver, float grad_mult,
+                void* stream);
+int y2_sgd_step_packed(y2_ctx* ctx, float* accum, void* ctrl, int step, const y2_sgd_solver* solver, float grad_mult,
+                       void* stream);
+
 /* The reference's train_op as ONE call (optimizer.minimize(loss) = compute_gradients + apply_gradients,
  * src/pascal/pascal_train_darknet.py:49-51; imagenet_train_darknet.py:58): y2_backward over all layers, then, with
  * ctrl, the sentinel overflow check (y2_grad_check), then y2_adam_step_packed / y2_momentum_step_packed -- and the

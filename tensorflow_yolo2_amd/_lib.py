@@ -121,6 +121,9 @@ SIGNATURES = {
     "y2_momentum_step_guarded": (_i, [_vp, _vp, _vp, _sz, _vp, _f, _f, _f, _vp]),
     "y2_adam_step_packed": (_i, [_vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp]),
     "y2_momentum_step_packed": (_i, [_vp, _vp, _vp, _f, _f, _f, _vp]),
+    "y2_solver_rate": (_i, [_vp, _i, C.POINTER(C.c_float)]),
+    "y2_sgd_step": (_i, [_vp, _vp, _vp, _i, _vp, _f, _vp]),
+    "y2_sgd_step_packed": (_i, [_vp, _vp, _vp, _i, _vp, _f, _vp]),
     "y2_backward_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp]),
     "y2_backward_momentum": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _vp]),
     "y2_conv2d_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
@@ -138,6 +141,26 @@ SIGNATURES = {
     "y2_voc_match_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "y2_crc32c": (C.c_uint32, [_vp, _sz, C.c_uint32]),
 }
+
+
+POLICIES = {"constant": 0, "steps": 1, "poly": 2}       # Y2_POLICY_*
+SOLVER_MAX_STEPS = 8
+
+
+class SgdSolver(C.Structure):
+    """y2_sgd_solver"""
+    _fields_ = [("learning_rate", _f), ("momentum", _f), ("decay", _f), ("policy", _i), ("burn_in", _i), ("power", _i),
+                ("max_batches", _i), ("nsteps", _i), ("steps", _i * SOLVER_MAX_STEPS), ("scales", _f * SOLVER_MAX_STEPS)]
+
+
+def sgd_solver(solver):
+    """utils.solver.Solver (validated there) -> the C record"""
+    solver.validate()
+    s = SgdSolver(solver.learning_rate, solver.momentum, solver.decay, POLICIES[solver.policy], solver.burn_in,
+                  solver.power, solver.max_batches, len(solver.steps))
+    for i, (st, sc) in enumerate(zip(solver.steps, solver.scales)):
+        s.steps[i], s.scales[i] = int(st), float(sc)
+    return s
 
 
 class Y2Error(RuntimeError):

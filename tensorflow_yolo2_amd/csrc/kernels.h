@@ -512,9 +512,11 @@ void pack_layer_plan(PackLayer& L, int first_block, int elem_size);
 hipError_t launch_pack_all(int dtype, const PackLayer* tab_dev, int nlayers, int total_blocks, hipStream_t s);
 // Optimizer step + filter re-pack in ONE pass over the parameters (the update reads and writes every filter
 // anyway: the packed f16 / bf16 copies leave from the same registers instead of a second 193 MB read).
-// kind 0: Adam (slot0 = m, slot1 = v), 1: Momentum (slot0 = accum).  ctrl != null: guarded (optim.hip), lr_t from
-// ctrl; else lr_t = hyper[0].  hyper = {lr_t or lr, b1 or momentum, b2, eps, grad_mult}.
-// small: [offset, count] ranges of the parameters that are not filter tiles (b, gamma, beta; a 3-channel first filter)
+// kind 0: Adam (slot0 = m, slot1 = v), 1: Momentum (slot0 = accum), 2: Darknet's SGD (slot0 = accum, b1 = momentum,
+// b2 = decay; the tiles are filters and always decay).  ctrl != null: guarded (optim.hip), lr_t from ctrl for kinds 0
+// and 2; else lr_t = hyper[0].  hyper = {lr_t or lr, b1 or momentum, b2, eps, grad_mult}.
+// small: [offset, count, decayed] ranges of the parameters that are not filter tiles (b, gamma, beta: not decayed; a
+// 3-channel first filter: decayed -- kind 2 alone reads the flag)
 struct OptPackArgs {
     float* p; float* slot0; float* slot1; const float* g;
     const void* ctrl;
@@ -668,6 +670,13 @@ hipError_t launch_adam_guarded(float* p, float* m, float* v, const float* g, siz
                                float b2, float eps, float gscale, hipStream_t s);
 hipError_t launch_momentum_guarded(float* p, float* acc, const float* g, size_t n, const void* ctrl, float lr, float mom,
                                    float gscale, hipStream_t s);
+// Darknet's SGD on a flat buffer (optim.hip): the buffer as segments that decay (filters) or not (b / gamma / beta),
+// in buffer order; first_block: the segment's first block of launch_sgd's grid, sgd_seg_blocks() blocks each
+struct SgdSeg { unsigned off, cnt, first_block, decayed; };
+int sgd_seg_blocks(size_t off, size_t cnt);
+hipError_t launch_sgd(float* p, float* acc, const float* g, const SgdSeg* segs_dev, int nsegs, int blocks,
+                      const void* ctrl, float lr_t, float mom, float decay, float gscale, hipStream_t s);
+hipError_t launch_sgd_ctrl_advance(void* ctrl, const y2_sgd_solver& sv, hipStream_t s);
 hipError_t launch_init_trunc_normal(float* p, size_t n, float stddev, uint64_t seed, uint64_t stream_id,
                                     hipStream_t s);
 hipError_t launch_fill(float* p, size_t n, float v, hipStream_t s);

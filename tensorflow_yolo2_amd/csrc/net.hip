@@ -19,6 +19,7 @@
 #include "../../include/yolo2_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "optim_math.h"
 
 using namespace y2;
 
@@ -172,7 +173,7 @@ struct y2_ctx {
     int dA_cur = 0;
     int dA_half = 0;            // f16x2f: the dA buffer in use holds f16 values (written by a launch-dtype-5 dgrad)
     size_t o_infertab = 0;      // BnInferLayer per layer (one prepare launch for all inference-mode layers)
-    size_t o_packtab = 0, o_chkranges = 0, o_smallranges = 0, o_lin = 0, o_nfflag = 0, o_slab = 0;
+    size_t o_packtab = 0, o_chkranges = 0, o_smallranges = 0, o_sgdsegs = 0, o_lin = 0, o_nfflag = 0, o_slab = 0;
     size_t o_ks = 0, ks_floats = 0;   // K-split partial tiles of small convolution launches (ConvArgs::ks_scratch)
     size_t o_gram = 0;          // first layer: Gram matrix of the input patches [48][48] + its slices / block partials
     size_t slab_floats = 0;     // split-K partial tiles of the weight gradients (WgradArgs::slab)
@@ -181,6 +182,7 @@ struct y2_ctx {
     // (y2_backward_adam / _momentum) checks and updates that part while the first layer's gradient is still
     // being computed
     int n_chk_upper = 0, n_small_upper = 0;
+    int n_sgdsegs = 0, sgd_blocks = 0;     // y2_sgd_step: the flat buffer as decayed / undecayed segments (kernels.h SgdSeg)
     struct FusedOpt {
         bool on = false;
         int kind = 0;
@@ -191,6 +193,7 @@ struct y2_ctx {
     } fopt;
     std::vector<PackLayer> packtab;
     std::vector<BnInferLayer> infertab;
+    std::vector<SgdSeg> sgdsegs;
     int pack_blocks = 0;
     // optional per-launch HIP-event bracketing (bench.py roofline leg)
     int prof = 0;   // 0 off, 1 every launch, 2 only the dominant kernel (conv forward + dgrad)
@@ -484,7 +487,8 @@ static void plan(y2_ctx* c) {
     c->o_packtab = take(c->L.size() * sizeof(PackLayer));
     c->o_infertab = take(c->L.size() * sizeof(BnInferLayer));
     c->o_chkranges = take((c->L.size() + 1) * 2 * sizeof(unsigned));
-    c->o_smallranges = take((c->L.size() + 1) * 2 * sizeof(unsigned));
+    c->o_smallranges = take((c->L.size() + 1) * 3 * sizeof(unsigned));
+    c->o_sgdsegs = take(c->L.size() * 2 * sizeof(SgdSeg));
     c->o_nfflag = take(256);
     {   // K-split partial tiles of the small launches (conv_haloq.hip haloq_ks): forward and dgrad of every layer
         size_t ks = 0;
@@ -799,19 +803,38 @@ int y2_bind(y2_ctx* c, float* params, float* grads, float* state, void* workspac
     c->pack_blocks = nb;
     c->opt_tile_blocks = ntile;
     {   // parameters outside the filter tiles of the fused optimizer + re-pack pass
+        // [offset, count, decayed]: the last word is read by Darknet's SGD alone (weight decay on filters only)
         std::vector<unsigned> rg;
         for (size_t l = 1; l <= c->L.size(); ++l) {      // layer 0 last
             const Layer& y = c->L[l % c->L.size()];
             rg.push_back((unsigned)y.pb);
             rg.push_back((unsigned)(3 * y.cout));
+            rg.push_back(0u);
         }
         c->n_small_upper = (int)c->L.size() - 1;
         if (c->L[0].first3) {
             rg.push_back((unsigned)c->L[0].pW);
             rg.push_back((unsigned)(27 * c->L[0].cout));
+            rg.push_back(1u);
         }
-        c->n_smallranges = (int)(rg.size() / 2);
+        c->n_smallranges = (int)(rg.size() / 3);
         HIPCHK(hipMemcpyAsync(c->ws + c->o_smallranges, rg.data(), rg.size() * sizeof(unsigned), hipMemcpyHostToDevice,
+                              (hipStream_t)stream));
+    }
+    {   // y2_sgd_step: every layer's filter (decayed), then its b / gamma / beta (not), in buffer order
+        std::vector<SgdSeg>& sg = c->sgdsegs;              // a member: the asynchronous copy reads it after this returns
+        sg.clear();
+        unsigned nblk = 0;
+        for (const Layer& y : c->L) {
+            const size_t nW = (size_t)y.k * y.k * y.cin * y.cout;
+            sg.push_back(SgdSeg{(unsigned)y.pW, (unsigned)nW, nblk, 1u});
+            nblk += (unsigned)sgd_seg_blocks(y.pW, nW);
+            sg.push_back(SgdSeg{(unsigned)y.pb, (unsigned)(3 * y.cout), nblk, 0u});
+            nblk += (unsigned)sgd_seg_blocks(y.pb, (size_t)3 * y.cout);
+        }
+        c->n_sgdsegs = (int)sg.size();
+        c->sgd_blocks = (int)nblk;
+        HIPCHK(hipMemcpyAsync(c->ws + c->o_sgdsegs, sg.data(), sg.size() * sizeof(SgdSeg), hipMemcpyHostToDevice,
                               (hipStream_t)stream));
     }
     {   // sentinel ranges of y2_grad_check: b, gamma, beta of every layer (contiguous) + the first filter
@@ -1563,7 +1586,7 @@ static int opt_step_packed(y2_ctx* c, int kind, float* slot0, float* slot1, void
     a.tab = (const PackLayer*)(c->ws + c->o_packtab); a.nlayers = (int)c->packtab.size();
     a.tile_blocks = part == 2 ? 0 : c->opt_tile_blocks;
     const unsigned* small = (const unsigned*)(c->ws + c->o_smallranges);
-    a.small = part == 2 ? small + 2 * c->n_small_upper : small;
+    a.small = part == 2 ? small + 3 * c->n_small_upper : small;
     a.nsmall = part == 0 ? c->n_smallranges : (part == 1 ? c->n_small_upper : c->n_smallranges - c->n_small_upper);
     HIPCHK(launch_opt_pack(c->dtype, a, s));
     if (part != 1 && !c->L.empty() && c->L[0].first3)
@@ -1629,6 +1652,35 @@ int y2_momentum_step_packed(y2_ctx* c, float* accum, void* ctrl, float lr, float
     if (!accum) return fail(Y2_ERR_ARG, "bad arguments");
     if (ctrl) HIPCHK(launch_opt_ctrl_advance(ctrl, lr, 0.9f, 0.999f, (hipStream_t)stream));
     return opt_step_packed(c, 1, accum, nullptr, ctrl, lr, momentum, 0.f, 0.f, grad_mult, (hipStream_t)stream);
+}
+// Darknet's SGD (include/yolo2_hip.h): the rate of a step is the host's (no ctrl) or the device schedule's
+int y2_solver_rate(const y2_sgd_solver* solver, int t, float* rate) {
+    if (!solver || !rate || t < 1) return fail(Y2_ERR_ARG, "y2_solver_rate: bad arguments");
+    if (const char* why = solver_invalid(*solver)) return fail(Y2_ERR_ARG, "y2_sgd_solver: %s", why);
+    *rate = solver_rate(*solver, t);
+    return Y2_OK;
+}
+static int sgd_step_any(y2_ctx* c, bool packed, float* accum, void* ctrl, int step, const y2_sgd_solver* sv,
+                        float grad_mult, hipStream_t s) {
+    if (!accum || !sv || (!ctrl && step < 1)) return fail(Y2_ERR_ARG, "bad arguments");
+    if (const char* why = solver_invalid(*sv)) return fail(Y2_ERR_ARG, "y2_sgd_solver: %s", why);
+    if (!c->ws || !c->grads || !c->bound_training) return fail(Y2_ERR_STATE, "bind with training=1 first");
+    float lr_t = 0.f;
+    if (ctrl && step >= 0) HIPCHK(launch_sgd_ctrl_advance(ctrl, *sv, s));
+    else if (!ctrl) lr_t = solver_rate(*sv, step);
+    if (packed) return opt_step_packed(c, 2, accum, nullptr, ctrl, lr_t, sv->momentum, sv->decay, 0.f, grad_mult, s);
+    HIPCHK(launch_sgd(c->params, accum, c->grads, (const SgdSeg*)(c->ws + c->o_sgdsegs), c->n_sgdsegs, c->sgd_blocks,
+                      ctrl, lr_t, sv->momentum, sv->decay, grad_mult, s));
+    c->weights_dirty = true;
+    return Y2_OK;
+}
+int y2_sgd_step(y2_ctx* c, float* accum, void* ctrl, int step, const y2_sgd_solver* solver, float grad_mult,
+                void* stream) {
+    return sgd_step_any(c, false, accum, ctrl, step, solver, grad_mult, (hipStream_t)stream);
+}
+int y2_sgd_step_packed(y2_ctx* c, float* accum, void* ctrl, int step, const y2_sgd_solver* solver, float grad_mult,
+                       void* stream) {
+    return sgd_step_any(c, true, accum, ctrl, step, solver, grad_mult, (hipStream_t)stream);
 }
 int y2_momentum_step(float* params, float* accum, const float* grads, size_t n, float lr, float momentum,
                      float grad_mult, void* stream) {

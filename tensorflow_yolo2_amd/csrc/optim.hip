@@ -213,6 +213,83 @@ hipError_t launch_momentum_guarded(float* p, float* acc, const float* g, size_t 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Darknet's SGD (optim_math.h sgd_update; specification utils/solver.py).  The flat buffer is a sequence of
+// segments -- per layer the filter (decayed) and b / gamma / beta (not decayed) -- and the decay branch is per
+// segment, so a block works inside ONE segment: it looks its segment up in the bind-time table (kernels.h SgdSeg,
+// a walk over 2 x layers entries, once per block) and takes 1024 16-byte groups of that segment's aligned body;
+// the segment's first block also takes the at most 3 + 3 elements in front of and behind the body (a segment
+// starts wherever the layer before it ended: Cout = 125 leaves every later offset odd).
+// ctrl (nullable): found_inf set -> return at once; else lr_t from the control block.
+// ---------------------------------------------------------------------------
+constexpr int kSgdGroupsPerBlock = 1024;      // 16-byte groups of one block: 4 per thread
+int sgd_seg_blocks(size_t off, size_t cnt) {
+    const size_t a0 = (off + 3) / 4 * 4, e4 = (off + cnt) / 4 * 4;
+    const size_t groups = e4 > a0 ? (e4 - a0) / 4 : 0;
+    const size_t nb = (groups + kSgdGroupsPerBlock - 1) / kSgdGroupsPerBlock;
+    return nb < 1 ? 1 : (int)nb;
+}
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* __restrict__ acc, const float* __restrict__ g,
+                                                  const SgdSeg* __restrict__ segs, int nsegs, const OptCtrl* ctrl,
+                                                  float lr_t, float mom, float decay, float gscale) {
+    if (ctrl) {
+        if (ctrl->found_inf) return;
+        lr_t = ctrl->lr_t;
+    }
+    const unsigned b = blockIdx.x;
+    int si = 0;
+    while (si + 1 < nsegs && b >= segs[si + 1].first_block) ++si;
+    const SgdSeg sg = segs[si];
+    const bool decayed = sg.decayed != 0;
+    const size_t off = sg.off, end = off + sg.cnt;
+    size_t a0 = (off + 3) / 4 * 4, e4 = end / 4 * 4;
+    if (e4 < a0) a0 = e4 = end;                 // fewer than 4 elements and no aligned group: all of it is "head"
+    const unsigned local = b - sg.first_block;
+    const size_t g0 = a0 / 4 + (size_t)local * kSgdGroupsPerBlock;
+    const size_t g1 = g0 + kSgdGroupsPerBlock < e4 / 4 ? g0 + kSgdGroupsPerBlock : e4 / 4;
+    float4* p4 = (float4*)p; float4* a4 = (float4*)acc; const float4* gr4 = (const float4*)g;
+    for (size_t i = g0 + threadIdx.x; i < g1; i += 256) {
+        float4 pp = p4[i], aa = a4[i], gg = gr4[i];
+        float* P = &pp.x; float* A = &aa.x; const float* G = &gg.x;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sgd_update(P[k], A[k], G[k] * gscale, lr_t, mom, decay, decayed);
+        p4[i] = pp; a4[i] = aa;
+    }
+    if (local == 0) {
+        // [off, a0) and [e4, end): at most 3 elements each
+        const size_t nh = a0 - off, nt = end - e4;
+        if (threadIdx.x < nh + nt) {
+            const size_t i = threadIdx.x < nh ? off + threadIdx.x : e4 + (threadIdx.x - nh);
+            float pk = p[i], ak = acc[i];
+            sgd_update(pk, ak, g[i] * gscale, lr_t, mom, decay, decayed);
+            acc[i] = ak; p[i] = pk;
+        }
+    }
+}
+hipError_t launch_sgd(float* p, float* acc, const float* g, const SgdSeg* segs_dev, int nsegs, int blocks,
+                      const void* ctrl, float lr_t, float mom, float decay, float gscale, hipStream_t s) {
+    if (nsegs < 1 || blocks < 1) return hipSuccess;
+    hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, acc, g, segs_dev, nsegs,
+                       (const OptCtrl*)ctrl, lr_t, mom, decay, gscale);
+    return hipGetLastError();
+}
+
+// the schedule beside opt_ctrl_advance_kernel: a clean flag -> step += 1, lr_t = rate(step); a set flag -> skipped += 1
+// and lr_t stays (a skipped step does not move the schedule: the rule of Adam's bias correction)
+__global__ void sgd_ctrl_advance_kernel(OptCtrl* ctrl, y2_sgd_solver sv) {
+    if (ctrl->found_inf) {
+        ctrl->skipped += 1;
+    } else {
+        const int t = ctrl->step + 1;
+        ctrl->step = t;
+        ctrl->lr_t = solver_rate(sv, t);
+    }
+}
+hipError_t launch_sgd_ctrl_advance(void* ctrl, const y2_sgd_solver& sv, hipStream_t s) {
+    hipLaunchKernelGGL(sgd_ctrl_advance_kernel, dim3(1), dim3(1), 0, s, (OptCtrl*)ctrl, sv);
+    return hipGetLastError();
+}
+
 // counter-based generator (splitmix64 finaliser) -> Box-Muller -> reject |z| > 2
 Y2_DEV uint64_t mix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;

@@ -601,13 +601,17 @@ __global__ __launch_bounds__(256) void pack_all_kernel(const PackLayer* __restri
 // updated tile leaves a second and third time in the MFMA operand type: co-contiguous rows to the dgrad copy
 // (tap-flipped), and through a 64 x 64 LDS transpose to the forward copy.  Blocks past the tiles update the
 // small ranges (b, gamma, beta, a 3-channel first filter) with the plain flat form.
+// KIND 2 (Darknet's SGD, optim_math.h sgd_update: b1 = momentum, b2 = decay): a tile is a filter and always decays; a
+// small range carries its own flag (the 3-channel first filter decays, b / gamma / beta do not).
 // ---------------------------------------------------------------------------
 struct OptCtrlView { int found_inf, step, skipped, reserved; float lr_t; };
 
 template <int KIND>
-Y2_DEV void opt_update(float& p, float& s0, float& s1, float g, float lr_t, float b1, float b2, float eps) {
+Y2_DEV void opt_update(float& p, float& s0, float& s1, float g, float lr_t, float b1, float b2, float eps,
+                       bool decayed = true) {
     if (KIND == 0) adam_update(p, s0, s1, g, lr_t, b1, b2, eps);
-    else momentum_update(p, s0, g, lr_t, b1);
+    else if (KIND == 1) momentum_update(p, s0, g, lr_t, b1);
+    else sgd_update(p, s0, g, lr_t, b1, b2, decayed);
 }
 
 template <typename T, int KIND, bool SPLIT = false>
@@ -619,7 +623,7 @@ __global__ __launch_bounds__(256) void opt_pack_kernel(OptPackArgs a) {
     if (a.ctrl) {
         const OptCtrlView* c = (const OptCtrlView*)a.ctrl;
         if (c->found_inf) return;          // overflowed gradients: nothing moves, the packed copies stay valid
-        if (KIND == 0) lr_t = c->lr_t;
+        if (KIND != 1) lr_t = c->lr_t;
     }
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -627,10 +631,11 @@ __global__ __launch_bounds__(256) void opt_pack_kernel(OptPackArgs a) {
         // small ranges: grid-stride over the concatenation of the ranges
         const int nb = gridDim.x - a.tile_blocks, bi = b - a.tile_blocks;
         for (int r = 0; r < a.nsmall; ++r) {
-            const unsigned off = a.small[2 * r], cnt = a.small[2 * r + 1];
+            const unsigned off = a.small[3 * r], cnt = a.small[3 * r + 1];
+            const bool decayed = KIND == 2 && a.small[3 * r + 2] != 0;
             for (unsigned i = bi * 256 + tid; i < cnt; i += nb * 256) {
                 float p = a.p[off + i], s0 = a.slot0[off + i], s1 = KIND == 0 ? a.slot1[off + i] : 0.f;
-                opt_update<KIND>(p, s0, s1, a.g[off + i] * a.gmult, lr_t, a.b1, a.b2, a.eps);
+                opt_update<KIND>(p, s0, s1, a.g[off + i] * a.gmult, lr_t, a.b1, a.b2, a.eps, decayed);
                 a.p[off + i] = p; a.slot0[off + i] = s0;
                 if (KIND == 0) a.slot1[off + i] = s1;
             }
@@ -720,16 +725,21 @@ hipError_t launch_opt_pack(int dtype, const OptPackArgs& a, hipStream_t s) {
     const int small_blocks = a.nsmall > 0 ? 64 : 0;
     dim3 g(a.tile_blocks + small_blocks), b(256);
     if (g.x == 0) return hipSuccess;
+    if (a.kind < 0 || a.kind > 2) return hipErrorInvalidValue;
 #define Y2_OP(T, K) hipLaunchKernelGGL((opt_pack_kernel<T, K>), g, b, 0, s, a)
-    switch (dtype * 2 + a.kind) {
+    switch (dtype * 3 + a.kind) {
         case 0: Y2_OP(float, 0); break;
         case 1: Y2_OP(float, 1); break;
-        case 2: Y2_OP(half_t, 0); break;
-        case 3: Y2_OP(half_t, 1); break;
-        case 4: Y2_OP(bf16_t, 0); break;
-        case 5: Y2_OP(bf16_t, 1); break;
-        case 6: hipLaunchKernelGGL((opt_pack_kernel<half_t, 0, true>), g, b, 0, s, a); break;     // f16x2
-        case 7: hipLaunchKernelGGL((opt_pack_kernel<half_t, 1, true>), g, b, 0, s, a); break;
+        case 2: Y2_OP(float, 2); break;
+        case 3: Y2_OP(half_t, 0); break;
+        case 4: Y2_OP(half_t, 1); break;
+        case 5: Y2_OP(half_t, 2); break;
+        case 6: Y2_OP(bf16_t, 0); break;
+        case 7: Y2_OP(bf16_t, 1); break;
+        case 8: Y2_OP(bf16_t, 2); break;
+        case 9: hipLaunchKernelGGL((opt_pack_kernel<half_t, 0, true>), g, b, 0, s, a); break;     // f16x2
+        case 10: hipLaunchKernelGGL((opt_pack_kernel<half_t, 1, true>), g, b, 0, s, a); break;
+        case 11: hipLaunchKernelGGL((opt_pack_kernel<half_t, 2, true>), g, b, 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
 #undef Y2_OP

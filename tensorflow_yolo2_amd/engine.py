@@ -639,6 +639,59 @@ class MomentumOptimizer:
         self.accum.copy_(torch.as_tensor(np.asarray(st["accum"], np.float32)).to(self.accum.device))
 
 
+class DarknetSGD:
+    """Darknet's solver for the YOLOv2 anchor model (not in the reference; specification utils/solver.py): momentum
+    SGD with weight decay on the convolution filters only and a rate schedule (burn-in, then constant / steps / poly).
+    `solver`: a utils.solver.Solver.  The shape of AdamOptimizer: guarded in the loss-scaled modes, where the step
+    counter AND the schedule live on the device -- a skipped step moves neither (`t` mirrors the counter assuming no
+    skipped step; `scaler.state()` is authoritative, word 4 of `scaler.ctrl` holds the rate last applied)."""
+
+    def __init__(self, net, solver, guard=None, fused_pack=True):
+        self.net, self.solver = net, solver
+        self._record = _lib.sgd_solver(solver)
+        self.fused_pack = bool(fused_pack)
+        self.accum = torch.zeros_like(net.params)
+        self.t = 0
+        self.guard = (net.dtype in _lib.LOSS_SCALED) if guard is None else bool(guard)
+        self.scaler = LossScaler(net) if self.guard else None
+
+    def step(self, grad_mult=1.0, full_check=False, joint=None):
+        """full_check / joint: see AdamOptimizer.step"""
+        self.t += 1
+        n = self.net
+        if not n.training:
+            raise ValueError("DarknetSGD steps a context bound for training")
+        if self.guard and joint is None:
+            self.scaler.scan(n, full_check)
+        ctrl = _ptr(self.scaler.ctrl) if self.guard else C.c_void_p(0)
+        if joint is not None:
+            assert self.guard and self.fused_pack
+        fn = n.lib.y2_sgd_step_packed if self.fused_pack else n.lib.y2_sgd_step
+        check(fn(n.h, _ptr(self.accum), ctrl, -1 if joint == "next" else self.t, C.byref(self._record), grad_mult,
+                 _stream()))
+        if not self.fused_pack:
+            n.params_changed()
+        if self.guard and joint != "next":
+            self.scaler.after_step()
+
+    def backward_step(self, dout, grad_mult=1.0):
+        """net.backward(dout), then the step (no overlapped train op for this solver)"""
+        self.net.backward(dout)
+        return self.step(grad_mult)
+
+    def export_state(self):
+        t = self.scaler.state()[1] if self.guard else self.t
+        return {"accum": self.accum.detach().cpu().numpy().copy(), "t": int(t)}
+
+    def load_state(self, st):
+        self.accum.copy_(torch.as_tensor(np.asarray(st["accum"], np.float32)).to(self.accum.device))
+        self.t = int(st["t"])
+        if self.guard:
+            c = self.scaler.ctrl.cpu()
+            c[1] = self.t
+            self.scaler.ctrl.copy_(c)
+
+
 # ---------------------------------------------------------------------------
 # loss / decode ops on device tensors
 # ---------------------------------------------------------------------------

@@ -2,6 +2,8 @@
     python -m tensorflow_yolo2_amd.pascal.pascal_train_yolov2 --devkit data/VOCdevkit --iters 20 \
         [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR]
         [--box-labels [--max-boxes 30] [--area-weight] [--prior-images 12800]]
+        [--solver darknet [--lr .001] [--momentum .9] [--decay .0005] [--burn-in 1000] [--power 4]
+                          [--policy steps --steps 40000,60000 --scales .1,.1 | --policy poly --max-batches N | --policy constant]]
 The flags are pascal_train_darknet.py's where they apply.  The batches always come from the device-resident pool
 (img_dataset.device_voc.DeviceVOC.get(size)): the uint8 batch goes straight into YOLOv2Trainer.step, whose first layer
 converts it, and the label grid [N,S,S,5+C] (one box per cell) is the anchor loss's input as it stands.  --multi-scale
@@ -14,8 +16,14 @@ Darknet's (2 - w h) weight of the coord terms and --prior-images the number of i
 every prediction without an object is pulled toward its anchor.  The list encoder draws no random numbers, so a resumed
 run moves the data and augmentation streams exactly as without it; the prior's switch reads the snapshot's iteration.
 
+--solver darknet replaces Adam by Darknet's solver (utils/solver.py; engine.DarknetSGD): momentum SGD, weight decay on
+the convolution filters only, and the rate schedule -- a burn-in lr (t / burn_in)^power, then the policy.  The defaults
+are yolov2-voc.cfg's; the losses here are batch means, so --lr times the mean gradient is Darknet's learning_rate /
+batch times its summed gradient: the cfg's learning_rate is the value to give.  The schedule counts APPLIED steps on the device (a step skipped by the overflow guard does not move it); the
+rate the 10-iteration line prints is the host's current_rate of the iteration number.
+
 Snapshots are `train_iter_<i>.npz` (net_utils.save_yolov2_variables: the three stacks, the anchors, the three Adam
-states with their one loss scaler); a run with --ckpt-dir resumes from the latest, moves the data order and the
+states -- or the three Momentum slots and the solver record -- with their one loss scaler); a run with --ckpt-dir resumes from the latest, moves the data order and the
 augmentation stream to where the saved run stood, and so continues it.  Without a snapshot, --imagenet-ckpt-dir takes
 the Darknet-19 backbone from the latest classifier snapshot there.  --anchors kmeans clusters the image set's boxes
 (utils/anchors.py) instead of using the published VOC anchors; a resumed run keeps its snapshot's anchors.
@@ -60,6 +68,17 @@ def parse_args(argv=None):
     ap.add_argument("--area-weight", action="store_true", help="coord terms times 2 - w h (needs --box-labels)")
     ap.add_argument("--prior-images", type=int, default=0,
                     help="images during which un-owned predictions are pulled toward their anchors (needs --box-labels)")
+    ap.add_argument("--solver", default="adam", choices=("adam", "darknet"),
+                    help="adam: tf.train.AdamOptimizer defaults; darknet: momentum SGD + filter decay + rate schedule")
+    ap.add_argument("--lr", type=float, default=None, help="base rate (0.001; needs --solver darknet, as all below)")
+    ap.add_argument("--momentum", type=float, default=None, help="0.9")
+    ap.add_argument("--decay", type=float, default=None, help="weight decay of the convolution filters (0.0005)")
+    ap.add_argument("--burn-in", type=int, default=None, help="steps of the lr (t / burn_in)^power ramp (1000)")
+    ap.add_argument("--power", type=int, default=None, help="exponent of the ramp and of the poly policy (4)")
+    ap.add_argument("--policy", default=None, choices=("constant", "steps", "poly"), help="after the ramp (steps)")
+    ap.add_argument("--steps", default=None, help="comma-separated steps of the steps policy (40000,60000)")
+    ap.add_argument("--scales", default=None, help="comma-separated factors, one per step (.1,.1)")
+    ap.add_argument("--max-batches", type=int, default=None, help="where the poly policy reaches zero")
     ap.add_argument("--width-div", type=int, default=1, help="divide every inner width (tests)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
@@ -83,6 +102,28 @@ def parse_args(argv=None):
         args.max_boxes = 30
     if not 1 <= args.max_boxes <= 1024 or args.prior_images < 0:
         ap.error("--max-boxes must lie in 1..1024, --prior-images must not be negative")
+    given = [f for f in SOLVER_FLAGS if getattr(args, f) is not None]
+    if args.solver != "darknet" and given:
+        ap.error("%s need(s) --solver darknet" % ", ".join("--" + f.replace("_", "-") for f in given))
+    args.solver_record = None
+    if args.solver == "darknet":
+        from ..utils.solver import Solver
+        d = Solver()
+        try:
+            steps = d.steps if args.steps is None else tuple(int(v) for v in args.steps.split(",") if v.strip())
+            scales = d.scales if args.scales is None else tuple(float(v) for v in args.scales.split(",") if v.strip())
+        except ValueError:
+            ap.error("--steps takes comma-separated integers, --scales comma-separated numbers")
+        if (args.steps is None) != (args.scales is None) and len(steps) != len(scales):
+            ap.error("--steps %s and --scales %s: one scale per step" % (steps, scales))
+        pick = lambda v, dv: dv if v is None else v
+        try:
+            args.solver_record = Solver(pick(args.lr, d.learning_rate), pick(args.momentum, d.momentum),
+                                        pick(args.decay, d.decay), pick(args.policy, d.policy),
+                                        pick(args.burn_in, d.burn_in), pick(args.power, d.power), steps, scales,
+                                        pick(args.max_batches, d.max_batches))
+        except ValueError as e:
+            ap.error("--solver darknet: %s" % e)
     args.augmentation = None
     if args.augment:
         from ..img_dataset.augment import Augment
@@ -91,6 +132,9 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error("--augment: %s" % e)
     return args
+
+
+SOLVER_FLAGS = ("lr", "momentum", "decay", "burn_in", "power", "policy", "steps", "scales", "max_batches")
 
 
 def step_size(args, i):
@@ -135,7 +179,7 @@ def main(argv=None):
     first = step_size(args, 1) if args.multi_scale else args.size
     trainer = yolov2.YOLOv2Trainer(args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
                                    seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
-                                   prior_images=args.prior_images)
+                                   prior_images=args.prior_images, solver=args.solver_record)
     last_iter_num = 0
     if latest:
         print('Restorining model snapshots from {:s}'.format(latest))
@@ -162,8 +206,13 @@ def main(argv=None):
         sizes.append(size)
         if i % 10 == 0:
             _time = T.toc(average=False)
-            print('iter {:d}/{:d}, size {:d}, total loss: {:.3}, take {:.2}s'.format(i, TOTAL_ITER, size,
-                                                                                    float(losses[-1][4]), _time))
+            rate = ''
+            if args.solver_record is not None:
+                from ..utils.solver import current_rate
+                # of the host's iteration number: after a skipped step the device's counter, the one applied, is behind
+                rate = ', rate of iteration {:d}: {:.3e}'.format(i, float(current_rate(args.solver_record, i)))
+            print('iter {:d}/{:d}, size {:d}, total loss: {:.3}{:s}, take {:.2}s'.format(i, TOTAL_ITER, size,
+                                                                                        float(losses[-1][4]), rate, _time))
             T.tic()
         if args.ckpt_dir and (i % args.save_every == 0 or i == TOTAL_ITER):
             save_path = os.path.join(args.ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) + '.npz')

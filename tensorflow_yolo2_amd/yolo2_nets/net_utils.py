@@ -508,21 +508,27 @@ def _layer_slots(network, layers):
 def save_yolov2_variables(model, path, iteration=None):
     """model: a YOLOv2Detector or a YOLOv2Trainer -> one .npz: the parameters and batch-norm state of the three stacks,
     the anchors, the class count and the iteration (default: model.iteration); for a trainer also the three Adam states
-    and the one loss scaler and step counter they share, so that a resumed run continues the uninterrupted one"""
+    (or, on Darknet's solver, the three Momentum slots and the solver record) and the one loss scaler and step counter
+    they share, so that a resumed run continues the uninterrupted one"""
     nets = model.networks()
     stacks = {s: net.export_params() for s, net in zip(_v2snap.STACKS, nets)}
-    adam = scaler = None
+    adam = scaler = sgd = None
+    solver = getattr(model, "solver", None)
     if hasattr(model, "opts"):
-        adam = {}
+        adam, sgd = ({}, None) if solver is None else (None, {})
         for s, net, opt in zip(_v2snap.STACKS, nets, model.opts):
             st = opt.export_state()
-            adam[s] = {"m": _slot_views(net, torch.as_tensor(st["m"])), "v": _slot_views(net, torch.as_tensor(st["v"])),
-                       "t": st["t"]}
+            if solver is None:
+                adam[s] = {"m": _slot_views(net, torch.as_tensor(st["m"])),
+                           "v": _slot_views(net, torch.as_tensor(st["v"])), "t": st["t"]}
+            else:
+                sgd[s] = {"accum": _slot_views(net, torch.as_tensor(st["accum"])), "t": st["t"]}
         sc = model.opts[0].scaler
         if sc is not None:
             scaler = {"ctrl": sc.ctrl.cpu().numpy(), "scale": sc.scale, "clean": sc._clean}
     blob = _v2snap.to_blob(stacks, model.anchors, model.num_class,
-                           model.iteration if iteration is None else iteration, adam, scaler)
+                           model.iteration if iteration is None else iteration, adam, scaler, sgd,
+                           solver if sgd is not None else None)
     np.savez(path, **blob)
     return sorted(blob)
 
@@ -530,9 +536,13 @@ def save_yolov2_variables(model, path, iteration=None):
 def restore_yolov2_variables(model, path):
     """the inverse of save_yolov2_variables -> the snapshot's iteration (also left in model.iteration).  A
     YOLOv2Detector takes the parameters and batch-norm state only; a YOLOv2Trainer also the optimizer when the file
-    holds it.  Other anchors, another class count or a tensor of another shape raise, naming both values."""
+    holds it.  Other anchors, another class count or a tensor of another shape raise, naming both values; so does a
+    trainer on one optimizer given the slots of the other, or another solver record than its own."""
     with np.load(path) as snap:
         stacks, anchors, num_class, iteration, adam, scaler = _v2snap.from_blob(snap)
+        sgd, snap_solver = _v2snap.sgd_from_blob(snap)
+    if hasattr(model, "opts"):      # before anything is loaded: a refused snapshot leaves the trainer as it was
+        _v2snap.check_optimizer(path, adam is not None, snap_solver, getattr(model, "solver", None))
     _v2snap.check_matches("num_class", path, num_class, model.num_class)
     _v2snap.check_matches("anchors", path, anchors, np.asarray(model.anchors, np.float32).reshape(-1, 2))
     nets = model.networks()
@@ -546,10 +556,13 @@ def restore_yolov2_variables(model, path):
                     raise ValueError("snapshot %s: yolov2/%s/%d/%s has shape %s, the model expects %s" %
                                      (path, s, l, k, tuple(layer[k].shape), tuple(shape)))
         net.load_params(stacks[s])
-    if hasattr(model, "opts") and adam is not None:
+    if hasattr(model, "opts") and (adam is not None or sgd is not None):
         for s, net, opt in zip(_v2snap.STACKS, nets, model.opts):
-            opt.load_state({"m": _layer_slots(net, adam[s]["m"]), "v": _layer_slots(net, adam[s]["v"]),
-                            "t": adam[s]["t"]})
+            if adam is not None:
+                opt.load_state({"m": _layer_slots(net, adam[s]["m"]), "v": _layer_slots(net, adam[s]["v"]),
+                                "t": adam[s]["t"]})
+            else:
+                opt.load_state({"accum": _layer_slots(net, sgd[s]["accum"]), "t": sgd[s]["t"]})
         sc = model.opts[0].scaler
         if sc is not None and scaler is not None:
             sc.ctrl.copy_(torch.as_tensor(scaler["ctrl"]))

@@ -6,7 +6,8 @@ anchor-box decode and per-image NMS.  Every layer is the reference's conv-BN-lea
 so the three stacks are `engine.Network` contexts; the glue ops are csrc/ext.hip.
 `YOLOv2Detector` is the inference graph, `YOLOv2Trainer` the train step: anchor-box loss (csrc/ext.hip
 yolov2_loss_kernel, specification oracle/ext_ref.py), backward through the head, the passthrough concat, the
-13x13 stack, the 2x2 pool and the stem, Adam on the three flat parameter buffers, optional multi-scale.
+13x13 stack, the 2x2 pool and the stem, Adam (or, with `solver`, Darknet's SGD: utils/solver.py) on the three flat
+parameter buffers, optional multi-scale.
 """
 import numpy as np
 import torch
@@ -92,10 +93,13 @@ class YOLOv2Trainer:
     """Train step of the YOLOv2 detector (NOT in the reference: its trainer is the YOLOv1 grid model).
     Three conv-BN-leaky stacks, each with its own flat parameter / gradient buffer and Adam state.  With `sizes`
     the input size may change from step to step (multi-scale {320..608}): one context + workspace per size, all
-    bound to the same three parameter sets (engine.Network(share_with=...))."""
+    bound to the same three parameter sets (engine.Network(share_with=...)).
+    solver: None -- three engine.AdamOptimizer; a utils.solver.Solver -- three engine.DarknetSGD (momentum, weight decay
+    on the filters, the burn-in / steps / poly rate schedule), again with ONE loss scaler, step counter and rate."""
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01):
+                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
+                 solver=None):
         from ..trainer import GradReducer
         self._GradReducer = GradReducer
         self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
@@ -106,6 +110,7 @@ class YOLOv2Trainer:
         # term while fewer than prior_images images have been seen ((iteration - 1) * batch, counted over resumed runs)
         self.area_weight, self.prior_images, self.prior_scale = bool(area_weight), int(prior_images), float(prior_scale)
         self.iteration = 0                                   # train steps taken, over resumed runs (net_utils snapshots)
+        self.solver = solver.validate() if solver is not None else None
         sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
         self.specs = (sa, sb, sc)
         self.cf = sa[-1][2]
@@ -127,7 +132,10 @@ class YOLOv2Trainer:
             if first is None:
                 for i, net in enumerate(nets):
                     net.init_params(self.seed + i)
-                self.opts = [E.AdamOptimizer(net) for net in nets]
+                if self.solver is None:
+                    self.opts = [E.AdamOptimizer(net) for net in nets]
+                else:
+                    self.opts = [E.DarknetSGD(net, self.solver) for net in nets]
                 # ONE loss scale, overflow flag and step counter for the composed graph: an inf confined to
                 # one stack must skip the step of all three, and a skipped step must not advance any Adam bias correction
                 for opt in self.opts[1:]:
