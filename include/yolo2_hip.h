@@ -461,6 +461,21 @@ int y2_mx_quantize(const float* x, size_t rows, int C, uint8_t* q, uint8_t* scal
  * the entry's flip is set. */
 int y2_resize_bilinear_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, int n, int out_h,
                                 int out_w, uint8_t* out, void* stream);
+/* The letterboxed input of the anchor detector (img_dataset/pascal_voc.letterbox_u8 and letterbox_geometry are the
+ * specification, bit for bit).  Geometry, integers only, as Darknet's letterbox_image: for an image of im_w x im_h and a
+ * square of `size`, if im_h <= im_w then new_w = size, new_h = max(1, im_h * size / im_w), else new_h = size,
+ * new_w = max(1, im_w * size / im_h) (C division, 64-bit products); ox = (size - new_w) / 2, oy = (size - new_h) / 2 are
+ * the left / top bars, and the right / bottom bar gets the odd pixel.  Host only, no GPU work:
+ * geometry[4] = new_w, new_h, ox, oy.  Y2_ERR_ARG on a null pointer or a value below 1. */
+int y2_letterbox_geometry(int im_h, int im_w, int size, int* geometry);
+/* out [n][size][size][3] uint8, pool / table / index as y2_resize_bilinear_u8_batch: a canvas of `fill` (0..255) whose
+ * rows oy .. oy + new_h - 1 and columns ox .. ox + new_w - 1 hold the image resized to new_w x new_h exactly as
+ * y2_resize_bilinear_u8_batch resizes it to that size.  A letterbox in DESTINATION space: the picture's edge is not
+ * blended with the fill.  The flip column of the table is not read; an empty table row gives a canvas of fill alone.
+ * `size` a multiple of 4 up to Y2_RESIZE_MAX_OUT_W and `out` 4-byte aligned (the bars are written with vector stores),
+ * else an argument error.  One launch. */
+int y2_letterbox_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, int n, int size, int fill,
+                          uint8_t* out, void* stream);
 /* labels [n][S][S][5 + num_class] float32 (zero-filled here): `boxes` double [entries][max_obj][5] = xmin, ymin, xmax,
  * ymax, class index in 1-based pixels of the original image, in annotation order; `counts` int32 [entries].  Ratios
  * image_size / width, clamp to [0, image_size - 1], centre / size, cell int(c * S / image_size), the first object of a
@@ -529,6 +544,16 @@ int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32
 int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
                            int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out, int* det,
                            float* score, int* count, void* stream);
+/* y2_detect_anchor_batch for a batch made by y2_letterbox_u8_batch at net_size = 32 S (else an argument error): the
+ * four float64 products are replaced by the exact inverse of that embedding, with new_w, new_h, ox, oy of
+ * y2_letterbox_geometry(height, width, net_size) and in this operation order:
+ *   sx = width / new_w, sy = height / new_h;  x = (cx * net_size - ox) * sx;  y = (cy * net_size - oy) * sy;
+ *   w = (w * net_size) * sx;  h = (h * net_size) * sy
+ * and everything after them is unchanged: a box in a bar maps outside the image and is cut, or empty and dropped, by the
+ * existing rule (specification: utils/detect_batch.anchor_detect with net_size, bit for bit). */
+int y2_detect_anchor_batch_lb(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
+                              int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out,
+                              int net_size, int* det, float* score, int* count, void* stream);
 /* One row per (candidate, class) instead of one per candidate, as Darknet's `valid` writes them (specification:
  * utils/detect_batch.anchor_detect_classes on the outputs of y2_decode_anchors, bit for bit).  Class c of an image is a
  * segment of its own: the rows of y2_detect_anchor_batch had every candidate the class c and the score score[c], so a
@@ -541,6 +566,12 @@ int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t
 int y2_detect_anchor_classes_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
                                    int n, int S, int B, int num_class, float score_thresh, float iou_thresh,
                                    int max_per_class, int* det, float* score, int* count, void* stream);
+/* y2_detect_anchor_classes_batch with the letterbox map of y2_detect_anchor_batch_lb (specification:
+ * utils/detect_batch.anchor_detect_classes with net_size, bit for bit). */
+int y2_detect_anchor_classes_batch_lb(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
+                                      int n, int S, int B, int num_class, float score_thresh, float iou_thresh,
+                                      int max_per_class, int net_size, int* det, float* score, int* count,
+                                      void* stream);
 /* flags int32 [n][max_out]: 1 true positive, 0 false positive, 2 ignored, -1 beyond count.  The rows of an image are
  * walked in order (descending score): among the image's objects of the row's class, the first maximum of the float64
  * IoU, taken objects included; none, or IoU < iou_thresh: false positive; else a difficult object: ignored; an object

@@ -131,13 +131,17 @@ SIGNATURES = {
     "y2_conv2d_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "y2_mx_quantize": (_i, [_vp, _sz, _i, _vp, _vp, _vp]),
     "y2_resize_bilinear_u8_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "y2_letterbox_geometry": (_i, [_i, _i, _i, _pi]),
+    "y2_letterbox_u8_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "y2_encode_labels": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "y2_augment_u8_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "y2_encode_labels_window": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "y2_encode_box_list": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "y2_detect_grid_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "y2_detect_anchor_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "y2_detect_anchor_batch_lb": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "y2_detect_anchor_classes_batch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "y2_detect_anchor_classes_batch_lb": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "y2_voc_match_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "y2_crc32c": (C.c_uint32, [_vp, _sz, C.c_uint32]),
 }

@@ -5,6 +5,7 @@
 // specification's operation order, and the file is compiled with -ffp-contract=off (a fused multiply-add in
 // (i + 0.5) * scale - 0.5 or in frac * 2048 can move a rounding tie).
 #include "data_common.h"
+#include "letterbox.h"
 using namespace y2;
 
 namespace {
@@ -86,6 +87,100 @@ __global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t* __re
     }
 }
 
+// n4 dwords of `v` from the 4-byte aligned p by the whole workgroup: 16-byte stores between the unaligned ends
+Y2_DEV void fill_dwords(uint8_t* p, int n4, uint32_t v, int tid) {
+    const int head = min(n4, (int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2));
+    const int body = (n4 - head) >> 2;
+    uint32_t* q = (uint32_t*)p;
+    if (tid < head) q[tid] = v;
+    u32x4* b = (u32x4*)(q + head);
+    const u32x4 v4 = {v, v, v, v};
+    for (int i = tid; i < body; i += kThreads) b[i] = v4;
+    const int done = head + 4 * body;
+    if (tid < n4 - done) q[done + tid] = v;     // fewer than 4 left
+}
+
+// the aligned dword at byte cb of a canvas row whose picture bytes are [lo, hi): r0 / r1 are the two source rows
+Y2_DEV uint32_t canvas_dword(const uint8_t* r0, const uint8_t* r1, const XCoef* xt, int cb, int lo, int hi, int wy1,
+                             uint32_t fill4) {
+    if (cb >= lo && cb + 4 <= hi) return resize_bytes<4>(r0, r1, xt, cb - lo, wy1);
+    uint32_t v = fill4;
+    if (cb + 4 > lo && cb < hi) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int b = cb + e - lo;
+            if (b >= 0 && b < hi - lo) v = (v & ~(255u << (8 * e))) | (resize_bytes<1>(r0, r1, xt, b, wy1) << (8 * e));
+        }
+    }
+    return v;
+}
+
+// The letterboxed batch (img_dataset/pascal_voc.letterbox_u8): grid (ceil(size / kBand), n), resize_u8_kernel's band of
+// kBand canvas rows per workgroup.  The geometry comes from letterbox.h; a band that lies wholly in the top or bottom
+// bar (or whose table row is empty) is `fill` and nothing else: no coefficient, no source row.  Otherwise the band's bar
+// rows are filled, and its picture rows go the way of the plain resize with new_w x new_h for the output size: the x
+// table is built for new_w columns, the two source rows of an output row are staged, and a lane produces one aligned
+// dword of the CANVAS row -- resize_bytes<4> where the dword lies in the picture, the fill where it lies in a side bar,
+// byte by byte (resize_bytes<1>) for the at most two dwords of a row that straddle the picture's edge.  The flip column
+// of the table is not read: evaluation uses unmirrored entries.
+__global__ __launch_bounds__(kThreads) void letterbox_u8_kernel(const uint8_t* __restrict__ pool,
+                                                                const int64_t* __restrict__ table,
+                                                                const int32_t* __restrict__ index, int size, int fill,
+                                                                uint8_t* __restrict__ out) {
+    __shared__ XCoef xt[kMaxOutW];
+    __shared__ int yc[kBand][3];
+    __shared__ __attribute__((aligned(16))) uint8_t rows[2 * kRows * kMaxPitch];
+    const int tid = threadIdx.x, img = blockIdx.y;
+    const int64_t* t = table + (size_t)kTable * (index ? index[img] : img);
+    const int64_t off = t[0], h64 = t[1], w64 = t[2], pitch64 = t[3];
+    const int band0 = blockIdx.x * kBand, nrows = min(kBand, size - band0);
+    const int rowbytes = 3 * size;
+    const uint32_t fill4 = 0x01010101u * (uint32_t)fill;
+    uint8_t* obase = out + ((size_t)img * size + band0) * rowbytes;
+    const bool sized = h64 >= 1 && w64 >= 1 && h64 <= 0x7fffffff && w64 <= 0x7fffffff;
+    const int H = sized ? (int)h64 : 1, W = sized ? (int)w64 : 1;
+    const LetterboxGeom g = letterbox_geometry(W, H, size);
+    // the picture's rows of this band, relative to band0: [p0, p1)
+    const int p0 = sized ? min(max(g.oy - band0, 0), nrows) : nrows;
+    const int p1 = sized ? min(max(g.oy + g.new_h - band0, p0), nrows) : nrows;
+    fill_dwords(obase, p0 * (rowbytes >> 2), fill4, tid);
+    fill_dwords(obase + (size_t)p1 * rowbytes, (nrows - p1) * (rowbytes >> 2), fill4, tid);
+    if (p0 >= p1) return;                       // uniform: a pure fill
+    for (int x = tid; x < g.new_w; x += kThreads) {
+        int x0, x1, w1;
+        lin_coef(x, W, g.new_w, x0, x1, w1);
+        xt[x] = XCoef{3 * x0, (short)(3 * (x1 - x0)), (short)w1};
+    }
+    if (tid >= p0 && tid < p1) lin_coef(band0 + tid - g.oy, H, g.new_h, yc[tid][0], yc[tid][1], yc[tid][2]);
+    __syncthreads();
+    const bool staged = pitch64 <= kMaxPitch && ((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W;
+    const int pitch = (int)pitch64;
+    const uint8_t* src = pool + off;
+    const int lo = 3 * g.ox, hi = lo + 3 * g.new_w;         // the picture's bytes of a canvas row: [lo, hi)
+    for (int g0 = p0; g0 < p1; g0 += kRows) {
+        const int gr = min(kRows, p1 - g0);
+        if (staged) {
+            const int chunks = pitch >> 4;
+            for (int i = tid; i < 2 * gr * chunks; i += kThreads) {
+                const int slot = i / chunks, c = i - slot * chunks;
+                const int y = yc[g0 + (slot >> 1)][slot & 1];
+                *(u32x4*)(rows + slot * pitch + 16 * c) = *(const u32x4*)(src + (size_t)y * pitch64 + 16 * c);
+            }
+            __syncthreads();
+        }
+        const int total = gr * rowbytes;
+        for (int k = tid * 4; k < total; k += kThreads * 4) {
+            const int j = k / rowbytes, cb = k - j * rowbytes;
+            const int* y = yc[g0 + j];
+            uint32_t v;                            // two calls, so that the staged one reads LDS with LDS instructions
+            if (staged) v = canvas_dword(rows + (2 * j) * pitch, rows + (2 * j + 1) * pitch, xt, cb, lo, hi, y[2], fill4);
+            else v = canvas_dword(src + (size_t)y[0] * pitch64, src + (size_t)y[1] * pitch64, xt, cb, lo, hi, y[2], fill4);
+            *(uint32_t*)(obase + (size_t)g0 * rowbytes + k) = v;
+        }
+        if (staged) __syncthreads();
+    }
+}
+
 // grid (n).  The workgroup zero-fills the image's grid; then ONE lane walks the image's objects in annotation order
 // (the first object of a cell wins, which is sequential).  double arithmetic in the specification's order, one cast
 // to float at each store.  A flipped image writes the mirrored column and image_size - 1 - x directly: the mirror is
@@ -151,6 +246,31 @@ int y2_resize_bilinear_u8_batch(const uint8_t* pool, const int64_t* table, const
                            out_w, out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_resize_bilinear_u8_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_letterbox_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, int n, int size, int fill,
+                          uint8_t* out, void* stream) {
+    if (!pool || !table || !out) return fail(Y2_ERR_ARG, "y2_letterbox_u8_batch: null pointer");
+    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "y2_letterbox_u8_batch: n = %d outside 1..65535", n);
+    if (size < 4 || size % 4 || size > kMaxOutW)
+        return fail(Y2_ERR_ARG, "y2_letterbox_u8_batch: size = %d is not a multiple of 4 in 4..Y2_RESIZE_MAX_OUT_W = %d",
+                    size, kMaxOutW);
+    if (fill < 0 || fill > 255) return fail(Y2_ERR_ARG, "y2_letterbox_u8_batch: fill = %d outside 0..255", fill);
+    if ((uintptr_t)out & 3) return fail(Y2_ERR_ARG, "y2_letterbox_u8_batch: out is not 4-byte aligned");
+    hipLaunchKernelGGL(letterbox_u8_kernel, dim3((size + kBand - 1) / kBand, n), dim3(kThreads), 0, (hipStream_t)stream,
+                       pool, table, index, size, fill, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_letterbox_u8_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_letterbox_geometry(int im_h, int im_w, int size, int* geometry) {
+    if (!geometry) return fail(Y2_ERR_ARG, "y2_letterbox_geometry: null pointer");
+    if (im_h < 1 || im_w < 1 || size < 1)
+        return fail(Y2_ERR_ARG, "y2_letterbox_geometry: image %d x %d, size = %d", im_w, im_h, size);
+    const LetterboxGeom g = letterbox_geometry(im_w, im_h, size);
+    geometry[0] = g.new_w; geometry[1] = g.new_h; geometry[2] = g.ox; geometry[3] = g.oy;
     return Y2_OK;
 }
 

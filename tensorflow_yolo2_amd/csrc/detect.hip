@@ -9,6 +9,7 @@
 #include "data_common.h"
 #include "kernels.h"
 #include "anchor_decode.h"
+#include "letterbox.h"
 using namespace y2;
 
 namespace {
@@ -159,6 +160,16 @@ Y2_DEV float word_key(uint64_t w) {
     return __uint_as_float(m ^ ((m >> 31) ? 0x80000000u : 0xffffffffu));
 }
 
+// Where the input was letterboxed (letterbox.h; net_size = 32 S): the map from a box relative to the net_size canvas to
+// the pixels of the original image, the exact inverse of the embedding, in the specification's operation order
+// (utils/detect_batch.anchor_candidates with net_size).  Uniform over the workgroup: made once from the table row.
+struct LetterboxMap { double n, ox, oy, sx, sy; };
+Y2_DEV LetterboxMap letterbox_map(int im_w, int im_h, int net_size) {
+    const LetterboxGeom g = letterbox_geometry(im_w, im_h, net_size);
+    return LetterboxMap{(double)net_size, (double)g.ox, (double)g.oy, (double)im_w / (double)g.new_w,
+                        (double)im_h / (double)g.new_h};
+}
+
 // grid (n), one workgroup per image of min(KP, 1024) lanes, KP = the next power of two of K = S * S * B (64 .. 2048).
 //   1. slot i = lane + 1024 r is decoded from the raw head (anchor_decode.h: the values of y2_decode_anchors +
 //      y2_class_argmax), taken to the pixels of the original image in float64 and cut, as detect_grid_kernel does;
@@ -167,12 +178,15 @@ Y2_DEV float word_key(uint64_t w) {
 //      of a wave touch consecutive words: a pass reads and writes whole 256-byte bank rows for j >= 32 and meets at most
 //      2 lanes per bank below that (pair p -> slot 2 (p - p % j) + p % j), against 2 everywhere for adjacent slots per lane;
 //   3. detect_grid_kernel's walk: `kept` and sup[] are uniform, one barrier per kept row, none per suppressed row.
+// LETTERBOX: the four products go through letterbox_map instead of the plain stretch; nothing else differs, and the
+// `false` instantiation does not read net_size.
+template <bool LETTERBOX>
 __global__ __launch_bounds__(kAnchorLanes) void detect_anchor_kernel(const float* __restrict__ net,
                                                                      const float* __restrict__ anchors,
                                                                      const int64_t* __restrict__ table,
                                                                      const int32_t* __restrict__ index, int S, int B, int C,
                                                                      float score_thresh, float iou_thresh, int max_out,
-                                                                     int KP, int* __restrict__ det,
+                                                                     int KP, int net_size, int* __restrict__ det,
                                                                      float* __restrict__ score, int* __restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // kAnchorSlotBytes per slot: 58 KB at 2048
     uint64_t* sword = (uint64_t*)smem;
@@ -187,6 +201,8 @@ __global__ __launch_bounds__(kAnchorLanes) void detect_anchor_kernel(const float
     const bool sized = h64 >= 1 && w64 >= 1 && h64 <= 0x7fffffff && w64 <= 0x7fffffff;
     const int im_h = sized ? (int)h64 : 1, im_w = sized ? (int)w64 : 1;
     const float* rows = net + (size_t)img * K * D;
+    LetterboxMap lb = {};
+    if (LETTERBOX) lb = letterbox_map(im_w, im_h, net_size);
     if (tid == 0) s_valid = 0;
     __syncthreads();
     for (int i = tid; i < KP; i += nt) {
@@ -208,8 +224,14 @@ __global__ __launch_bounds__(kAnchorLanes) void detect_anchor_kernel(const float
                     cls = c;
                 }
             }
-            const double dx = (double)bx.cx * (double)im_w, dy = (double)bx.cy * (double)im_h;
-            const double dw = (double)bx.w * (double)im_w, dh = (double)bx.h * (double)im_h;
+            double dx, dy, dw, dh;
+            if (LETTERBOX) {
+                dx = ((double)bx.cx * lb.n - lb.ox) * lb.sx; dy = ((double)bx.cy * lb.n - lb.oy) * lb.sy;
+                dw = ((double)bx.w * lb.n) * lb.sx; dh = ((double)bx.h * lb.n) * lb.sy;
+            } else {
+                dx = (double)bx.cx * (double)im_w; dy = (double)bx.cy * (double)im_h;
+                dw = (double)bx.w * (double)im_w; dh = (double)bx.h * (double)im_h;
+            }
             const double lim = 1073741824.0;                              // 2^30: checked BEFORE any conversion to int
             valid = best > score_thresh && fabs(dx) < lim && fabs(dy) < lim && fabs(dw) < lim && fabs(dh) < lim;
             if (valid) {
@@ -286,10 +308,12 @@ constexpr int kClassSlotBytes = 8 + 4 * 4 + 1;         // sort word, four corner
 //   2. nvalid is uniform after the barrier; the bitonic sort runs over NP = the next power of two of nvalid (at least
 //      64) and not over KP: the slots nvalid .. NP are filled with words below every valid one (-inf).
 //   3. detect_anchor_kernel's walk without the class test: the segment holds one class.
+// LETTERBOX as in detect_anchor_kernel.
+template <bool LETTERBOX>
 __global__ __launch_bounds__(kClassLanes) void detect_anchor_classes_kernel(
     const float* __restrict__ net, const float* __restrict__ anchors, const int64_t* __restrict__ table,
     const int32_t* __restrict__ index, int S, int B, int C, float score_thresh, float iou_thresh, int max_out, int KP,
-    int* __restrict__ det, float* __restrict__ score, int* __restrict__ count) {
+    int net_size, int* __restrict__ det, float* __restrict__ score, int* __restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // kClassSlotBytes per slot
     uint64_t* sword = (uint64_t*)smem;
     int* bx0 = (int*)(sword + KP);
@@ -304,6 +328,8 @@ __global__ __launch_bounds__(kClassLanes) void detect_anchor_classes_kernel(
     const bool sized = h64 >= 1 && w64 >= 1 && h64 <= 0x7fffffff && w64 <= 0x7fffffff;
     const int im_h = sized ? (int)h64 : 1, im_w = sized ? (int)w64 : 1;
     const float* rows = net + (size_t)img * K * D;
+    LetterboxMap lb = {};
+    if (LETTERBOX) lb = letterbox_map(im_w, im_h, net_size);
     if (tid == 0) s_valid = 0;
     __syncthreads();
     for (int base = 0; base < K; base += nt) {                    // uniform trips: every lane of a wave meets the ballot
@@ -323,8 +349,14 @@ __global__ __launch_bounds__(kClassLanes) void detect_anchor_classes_kernel(
                 anchor_softmax_norm(p, C, mx, sum);
                 v = anchor_class_score(p, cls, bx.so, mx, sum);
             }
-            const double dx = (double)bx.cx * (double)im_w, dy = (double)bx.cy * (double)im_h;
-            const double dw = (double)bx.w * (double)im_w, dh = (double)bx.h * (double)im_h;
+            double dx, dy, dw, dh;
+            if (LETTERBOX) {
+                dx = ((double)bx.cx * lb.n - lb.ox) * lb.sx; dy = ((double)bx.cy * lb.n - lb.oy) * lb.sy;
+                dw = ((double)bx.w * lb.n) * lb.sx; dh = ((double)bx.h * lb.n) * lb.sy;
+            } else {
+                dx = (double)bx.cx * (double)im_w; dy = (double)bx.cy * (double)im_h;
+                dw = (double)bx.w * (double)im_w; dh = (double)bx.h * (double)im_h;
+            }
             const double lim = 1073741824.0;                              // 2^30: checked BEFORE any conversion to int
             valid = v > score_thresh && fabs(dx) < lim && fabs(dy) < lim && fabs(dw) < lim && fabs(dh) < lim;
             if (valid) {
@@ -498,55 +530,97 @@ int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32
     return Y2_OK;
 }
 
-int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
-                           int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out, int* det,
-                           float* score, int* count, void* stream) {
-    if (!net || !anchors || !table || !det || !score || !count)
-        return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: null pointer");
-    if (n < 1) return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: n = %d", n);
-    if (max_out < 1) return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: max_out = %d", max_out);
+// the checks and the launch of y2_detect_anchor_batch (net_size 0: the plain stretch) and y2_detect_anchor_batch_lb
+static int detect_anchor_any(const char* name, const float* net, const float* anchors, const int64_t* table,
+                             const int32_t* index, int n, int S, int B, int num_class, float score_thresh,
+                             float iou_thresh, int max_out, int net_size, bool letterbox, int* det, float* score,
+                             int* count, void* stream) {
+    if (!net || !anchors || !table || !det || !score || !count) return fail(Y2_ERR_ARG, "%s: null pointer", name);
+    if (n < 1) return fail(Y2_ERR_ARG, "%s: n = %d", name, n);
+    if (max_out < 1) return fail(Y2_ERR_ARG, "%s: max_out = %d", name, max_out);
     if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
-        return fail(Y2_ERR_ARG, "y2_detect_anchor_batch: S = %d, B = %d (at most 16), num_class = %d", S, B, num_class);
+        return fail(Y2_ERR_ARG, "%s: S = %d, B = %d (at most 16), num_class = %d", name, S, B, num_class);
     if (S * S * B > kAnchorMaxCand)
-        return fail(Y2_ERR_ARG,
-                    "y2_detect_anchor_batch: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d",
+        return fail(Y2_ERR_ARG, "%s: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d", name,
                     S * S * B, kAnchorMaxCand);
+    if (letterbox && (net_size < 32 || net_size % 32 || net_size != 32 * S))
+        return fail(Y2_ERR_ARG, "%s: net_size = %d is not the positive multiple of 32 that S = %d makes (32 S = %d)",
+                    name, net_size, S, 32 * S);
     int KP = kWave;
     while (KP < S * S * B) KP <<= 1;
     const int lanes = KP < kAnchorLanes ? KP : kAnchorLanes;
-    hipLaunchKernelGGL(detect_anchor_kernel, dim3(n), dim3(lanes), (size_t)KP * kAnchorSlotBytes, (hipStream_t)stream,
-                       net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh, max_out, KP, det, score,
-                       count);
+    if (letterbox)
+        hipLaunchKernelGGL(detect_anchor_kernel<true>, dim3(n), dim3(lanes), (size_t)KP * kAnchorSlotBytes,
+                           (hipStream_t)stream, net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh,
+                           max_out, KP, net_size, det, score, count);
+    else
+        hipLaunchKernelGGL(detect_anchor_kernel<false>, dim3(n), dim3(lanes), (size_t)KP * kAnchorSlotBytes,
+                           (hipStream_t)stream, net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh,
+                           max_out, KP, 0, det, score, count);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_anchor_batch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
+    return Y2_OK;
+}
+
+int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
+                           int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out, int* det,
+                           float* score, int* count, void* stream) {
+    return detect_anchor_any("y2_detect_anchor_batch", net, anchors, table, index, n, S, B, num_class, score_thresh,
+                             iou_thresh, max_out, 0, false, det, score, count, stream);
+}
+
+int y2_detect_anchor_batch_lb(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
+                              int S, int B, int num_class, float score_thresh, float iou_thresh, int max_out,
+                              int net_size, int* det, float* score, int* count, void* stream) {
+    return detect_anchor_any("y2_detect_anchor_batch_lb", net, anchors, table, index, n, S, B, num_class, score_thresh,
+                             iou_thresh, max_out, net_size, true, det, score, count, stream);
+}
+
+// the same for y2_detect_anchor_classes_batch and y2_detect_anchor_classes_batch_lb
+static int detect_anchor_classes_any(const char* name, const float* net, const float* anchors, const int64_t* table,
+                                     const int32_t* index, int n, int S, int B, int num_class, float score_thresh,
+                                     float iou_thresh, int max_per_class, int net_size, bool letterbox, int* det,
+                                     float* score, int* count, void* stream) {
+    if (!net || !anchors || !table || !det || !score || !count) return fail(Y2_ERR_ARG, "%s: null pointer", name);
+    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "%s: n = %d outside 1..65535", name, n);
+    if (max_per_class < 1) return fail(Y2_ERR_ARG, "%s: max_per_class = %d", name, max_per_class);
+    if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
+        return fail(Y2_ERR_ARG, "%s: S = %d, B = %d (at most 16), num_class = %d", name, S, B, num_class);
+    if (S * S * B > kAnchorMaxCand)
+        return fail(Y2_ERR_ARG, "%s: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d", name,
+                    S * S * B, kAnchorMaxCand);
+    if (letterbox && (net_size < 32 || net_size % 32 || net_size != 32 * S))
+        return fail(Y2_ERR_ARG, "%s: net_size = %d is not the positive multiple of 32 that S = %d makes (32 S = %d)",
+                    name, net_size, S, 32 * S);
+    int KP = kWave;
+    while (KP < S * S * B) KP <<= 1;
+    const int lanes = KP < kClassLanes ? KP : kClassLanes;
+    if (letterbox)
+        hipLaunchKernelGGL(detect_anchor_classes_kernel<true>, dim3(num_class, n), dim3(lanes),
+                           (size_t)KP * kClassSlotBytes, (hipStream_t)stream, net, anchors, table, index, S, B, num_class,
+                           score_thresh, iou_thresh, max_per_class, KP, net_size, det, score, count);
+    else
+        hipLaunchKernelGGL(detect_anchor_classes_kernel<false>, dim3(num_class, n), dim3(lanes),
+                           (size_t)KP * kClassSlotBytes, (hipStream_t)stream, net, anchors, table, index, S, B, num_class,
+                           score_thresh, iou_thresh, max_per_class, KP, 0, det, score, count);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
     return Y2_OK;
 }
 
 int y2_detect_anchor_classes_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
                                    int n, int S, int B, int num_class, float score_thresh, float iou_thresh,
                                    int max_per_class, int* det, float* score, int* count, void* stream) {
-    if (!net || !anchors || !table || !det || !score || !count)
-        return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: null pointer");
-    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: n = %d outside 1..65535", n);
-    if (max_per_class < 1)
-        return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: max_per_class = %d", max_per_class);
-    if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
-        return fail(Y2_ERR_ARG, "y2_detect_anchor_classes_batch: S = %d, B = %d (at most 16), num_class = %d", S, B,
-                    num_class);
-    if (S * S * B > kAnchorMaxCand)
-        return fail(Y2_ERR_ARG,
-                    "y2_detect_anchor_classes_batch: S * S * B = %d candidates beyond "
-                    "Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d",
-                    S * S * B, kAnchorMaxCand);
-    int KP = kWave;
-    while (KP < S * S * B) KP <<= 1;
-    const int lanes = KP < kClassLanes ? KP : kClassLanes;
-    hipLaunchKernelGGL(detect_anchor_classes_kernel, dim3(num_class, n), dim3(lanes), (size_t)KP * kClassSlotBytes,
-                       (hipStream_t)stream, net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh,
-                       max_per_class, KP, det, score, count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_anchor_classes_batch: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return detect_anchor_classes_any("y2_detect_anchor_classes_batch", net, anchors, table, index, n, S, B, num_class,
+                                     score_thresh, iou_thresh, max_per_class, 0, false, det, score, count, stream);
+}
+
+int y2_detect_anchor_classes_batch_lb(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
+                                      int n, int S, int B, int num_class, float score_thresh, float iou_thresh,
+                                      int max_per_class, int net_size, int* det, float* score, int* count,
+                                      void* stream) {
+    return detect_anchor_classes_any("y2_detect_anchor_classes_batch_lb", net, anchors, table, index, n, S, B, num_class,
+                                     score_thresh, iou_thresh, max_per_class, net_size, true, det, score, count, stream);
 }
 
 int y2_voc_match_batch(const int* det, const float* score, const int* count, const double* boxes,

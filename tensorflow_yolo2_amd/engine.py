@@ -959,11 +959,40 @@ def detect_grid_batch(predict, table, index=None, num_class=20, B=2, object_thre
     return det, score, count
 
 
-def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None):
+def _net_size(net_size, S):
+    """the net_size argument of the letterboxed detect calls: the input size the head's S belongs to"""
+    if int(net_size) != net_size or net_size < 32 or net_size % 32 or net_size != 32 * S:
+        raise ValueError("net_size %r is not the positive multiple of 32 that S = %d makes (%d)" % (net_size, S, 32 * S))
+    return int(net_size)
+
+
+def letterbox_batch(pool, table, index, n, size, fill=127, out=None):
+    """pool uint8 [bytes], table int64 [entries][5], index int32 [n] or None (DeviceVOC's) -> out uint8 [n,size,size,3]:
+    every entry letterboxed into a canvas of `fill` (img_dataset/pascal_voc.letterbox_u8, bit for bit); one launch on the
+    current stream.  The batch detect_anchor_batch(..., net_size=size) un-maps."""
+    lib = _lib.load()
+    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert table.shape[0] >= n
+    if out is None:
+        out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=pool.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * size * size * 3
+    check(lib.y2_letterbox_u8_batch(_ptr(pool), _ptr(table), _ptr(index), int(n), int(size), int(fill), _ptr(out),
+                                    _stream()))
+    return out
+
+
+def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None,
+                        net_size=None):
     """net [n,S,S,B,5+C] fp32 (the RAW YOLOv2 head), anchors [B,2] in cell units (a float32 device tensor, or anything
     numpy reads: uploaded here), table / index as detect_grid_batch -> the same (det, score, count): decode, class choice,
     boxes in the 1-based pixels of each ORIGINAL image and the class-aware NMS in one launch
-    (utils/detect_batch.anchor_detect on decode_anchors + class_argmax of the same net, bit for bit)"""
+    (utils/detect_batch.anchor_detect on decode_anchors + class_argmax of the same net, bit for bit).  net_size: the
+    input was letterboxed at that size (letterbox_batch; it must be 32 S) and the boxes are un-mapped from the picture's
+    rectangle (anchor_detect with net_size, y2_detect_anchor_batch_lb); None: a plain stretch"""
     lib = _lib.load()
     assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
     n, S, _, B, d = net.shape
@@ -987,18 +1016,23 @@ def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou
     assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * max_out * 6
     assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * max_out
     assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n
+    if net_size is not None:
+        check(lib.y2_detect_anchor_batch_lb(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, d - 5,
+                                            float(score_thresh), float(iou_thresh), int(max_out), _net_size(net_size, S),
+                                            _ptr(det), _ptr(score), _ptr(count), _stream()))
+        return det, score, count
     check(lib.y2_detect_anchor_batch(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, d - 5, float(score_thresh),
                                      float(iou_thresh), int(max_out), _ptr(det), _ptr(score), _ptr(count), _stream()))
     return det, score, count
 
 
 def detect_anchor_classes_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_per_class=32,
-                                out=None):
+                                out=None, net_size=None):
     """detect_anchor_batch's arguments -> (det int32 [n,C,max_per_class,6], score [n,C,max_per_class], count int32
     [n,C]): one row per (candidate, class) whose score passes, each class ordered and walked on its own, as Darknet's
     `valid` writes them (utils/detect_batch.anchor_detect_classes on decode_anchors of the same net, bit for bit).
     det.view(n * C, max_per_class, 6) with count.view(-1) and every index repeated C times is what voc_match_batch
-    reads."""
+    reads.  net_size as in detect_anchor_batch (y2_detect_anchor_classes_batch_lb)."""
     lib = _lib.load()
     assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
     n, S, _, B, d = net.shape
@@ -1023,6 +1057,12 @@ def detect_anchor_classes_batch(net, anchors, table, index=None, score_thresh=0.
     assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * C * max_per_class * 6
     assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * C * max_per_class
     assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n * C
+    if net_size is not None:
+        check(lib.y2_detect_anchor_classes_batch_lb(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C,
+                                                    float(score_thresh), float(iou_thresh), int(max_per_class),
+                                                    _net_size(net_size, S), _ptr(det), _ptr(score), _ptr(count),
+                                                    _stream()))
+        return det, score, count
     check(lib.y2_detect_anchor_classes_batch(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C,
                                              float(score_thresh), float(iou_thresh), int(max_per_class), _ptr(det),
                                              _ptr(score), _ptr(count), _stream()))

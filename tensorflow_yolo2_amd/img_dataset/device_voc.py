@@ -22,7 +22,9 @@ annotation order, and int32 counts [entries].
 Evaluation (pascal/pascal_eval_darknet.py) reads the same pool: eval_batch(size, start) resizes the entries start,
 start + 1, ... in LIST order with y2_resize_bilinear_u8_batch alone and leaves the shuffled cursor of get() where it is;
 `difficult`, uint8 [entries][max_obj] parallel to the box table, goes to the device at its first use (training never
-reads it).  Evaluation wants the plain list: a data set with `flipped` or `augment` refuses.
+reads it).  Evaluation wants the plain list: a data set with `flipped` or `augment` refuses.  eval_batch(size, start,
+letterbox=True) keeps every image's aspect ratio instead (y2_letterbox_u8_batch: csrc/data.hip); img_dataset/
+device_images.py is the same pool and entry table built from plain image files, without annotations.
 
 With `max_boxes` = T, get(size) returns (images, labels, truth, ntruth): the box list of the anchor model next to the
 label grid -- truth float32 [B][T][5] = cx, cy, w, h in pixels of the input and the class index of EVERY object of the
@@ -95,6 +97,39 @@ def padded_rows(img, pitch):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def list_batch(ds, who, size, start, letterbox, fill):
+    """the body of DeviceVOC.eval_batch and DeviceImages.batch: `ds` holds pool, table, entries, batch_size, device and
+    the per-size buffers; sets ds.eval_index"""
+    import torch
+    from .. import _lib
+    if torch.device(ds.device).type != "cuda":
+        raise RuntimeError("%s needs the pool on the GPU (device=%r)" % (who, ds.device))
+    if size < 32 or size % 32:
+        raise ValueError("size %r is not a positive multiple of 32" % (size,))
+    if letterbox and not 0 <= int(fill) <= 255:
+        raise ValueError("fill %r outside 0..255" % (fill,))
+    n = len(ds.entries)
+    if not 0 <= start < n:
+        raise IndexError("start = %r outside the %d entries" % (start, n))
+    if size not in ds._eval_buffers:
+        ds._eval_buffers[size] = (
+            torch.empty((ds.batch_size, size, size, 3), dtype=torch.uint8, device=ds.device),
+            torch.empty(ds.batch_size, dtype=torch.int32, device=ds.device))
+    images, index = ds._eval_buffers[size]
+    valid = min(ds.batch_size, n - start)
+    host = torch.from_numpy(np.minimum(np.arange(start, start + ds.batch_size), n - 1).astype(np.int32))
+    index.copy_(host.pin_memory(), non_blocking=True)
+    stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+    if letterbox:
+        _lib.check(_lib.load().y2_letterbox_u8_batch(_ptr(ds.pool), _ptr(ds.table), _ptr(index), ds.batch_size, size,
+                                                     int(fill), _ptr(images), stream))
+    else:
+        _lib.check(_lib.load().y2_resize_bilinear_u8_batch(_ptr(ds.pool), _ptr(ds.table), _ptr(index), ds.batch_size,
+                                                           size, size, _ptr(images), stream))
+    ds.eval_index = index
+    return images, valid
 
 
 class DeviceVOC(ShardedOrder):
@@ -232,35 +267,16 @@ class DeviceVOC(ShardedOrder):
             self._difficult = self._upload(self.difficult_host)
         return self._difficult
 
-    def eval_batch(self, size, start):
+    def eval_batch(self, size, start, letterbox=False, fill=127):
         """(images [B, size, size, 3] uint8 BGR, valid): entries start .. start + B - 1 of the image list IN LIST ORDER,
         resized on the current stream; the last batch repeats its final entry to fill the fixed batch and `valid` is the
         number of slots that are entries of their own.  `eval_index` is the int32 [B] device tensor of the slots' entries
-        (the `index` of the detect and match calls).  The cursor of get() is neither read nor moved."""
-        import torch
-        from .. import _lib
+        (the `index` of the detect and match calls).  The cursor of get() is neither read nor moved.  letterbox: the
+        aspect ratio is kept and the rest of the square is `fill` (pascal_voc.letterbox_u8; y2_letterbox_u8_batch) --
+        the detect calls then take net_size=size; the same buffers, index and refusals."""
         if self.flipped or self.augment is not None:
             raise ValueError("evaluation reads the plain image list: build the DeviceVOC with flipped=False, augment=None")
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("DeviceVOC.eval_batch needs the pool on the GPU (device=%r)" % (self.device,))
-        if size < 32 or size % 32:
-            raise ValueError("size %r is not a positive multiple of 32" % (size,))
-        n = len(self.entries)
-        if not 0 <= start < n:
-            raise IndexError("start = %r outside the %d entries" % (start, n))
-        if size not in self._eval_buffers:
-            self._eval_buffers[size] = (
-                torch.empty((self.batch_size, size, size, 3), dtype=torch.uint8, device=self.device),
-                torch.empty(self.batch_size, dtype=torch.int32, device=self.device))
-        images, index = self._eval_buffers[size]
-        valid = min(self.batch_size, n - start)
-        host = torch.from_numpy(np.minimum(np.arange(start, start + self.batch_size), n - 1).astype(np.int32))
-        index.copy_(host.pin_memory(), non_blocking=True)
-        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
-        _lib.check(_lib.load().y2_resize_bilinear_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index),
-                                                           self.batch_size, size, size, _ptr(images), stream))
-        self.eval_index = index
-        return images, valid
+        return list_batch(self, "DeviceVOC.eval_batch", size, start, letterbox, fill)
 
     def _get_augmented(self, size):
         """get(size) with one parameter row per sample, drawn in batch order and uploaded as the index is"""

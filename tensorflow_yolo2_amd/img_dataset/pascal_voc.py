@@ -152,6 +152,35 @@ def resize_bilinear_u8(img, out_h, out_w):
     return ((top * wy0[:, None, None] + bot * wy1[:, None, None] + (1 << 21)) >> 22).astype(np.uint8)
 
 
+def letterbox_geometry(im_h, im_w, size):
+    """(new_w, new_h, ox, oy) of an im_w x im_h image letterboxed into a size x size input, in integers only, as
+    Darknet's letterbox_image: the longer side becomes `size`, the other keeps the aspect ratio (floor division, at
+    least 1); ox / oy are the left / top bars and the right / bottom bar gets the odd pixel.  The restatement of
+    csrc/letterbox.h (y2_letterbox_geometry)."""
+    im_h, im_w, size = int(im_h), int(im_w), int(size)
+    if im_h < 1 or im_w < 1 or size < 1:
+        raise ValueError("letterbox_geometry: image %d x %d, size = %d: every value must be at least 1" % (im_w, im_h, size))
+    if size * im_h <= size * im_w:
+        new_w, new_h = size, max(1, (im_h * size) // im_w)
+    else:
+        new_h, new_w = size, max(1, (im_w * size) // im_h)
+    return new_w, new_h, (size - new_w) // 2, (size - new_h) // 2
+
+
+def letterbox_u8(img, size, fill=127):
+    """[H, W, 3] uint8 -> the [size, size, 3] letterboxed input: a canvas of `fill` whose rows oy .. oy + new_h - 1 and
+    columns ox .. ox + new_w - 1 (letterbox_geometry) hold resize_bilinear_u8(img, new_h, new_w).  A letterbox in
+    DESTINATION space: the picture's edge is not blended with the fill.  `fill` defaults to 127 as Augment's does;
+    Darknet's 0.5 lies between 127 and 128.  The specification of y2_letterbox_u8_batch (csrc/data.hip)."""
+    img = np.asarray(img)
+    if not 0 <= int(fill) <= 255:
+        raise ValueError("letterbox_u8: fill = %r outside 0..255" % (fill,))
+    new_w, new_h, ox, oy = letterbox_geometry(img.shape[0], img.shape[1], size)
+    out = np.full((int(size), int(size), 3), int(fill), np.uint8)
+    out[oy:oy + new_h, ox:ox + new_w] = resize_bilinear_u8(img, new_h, new_w)
+    return out
+
+
 def image_read(image_bgr_u8, image_size, flipped=False):
     """pascal_voc.image_read (:60-67) on an already decoded BGR uint8 array."""
     image = resize_bilinear_u8(image_bgr_u8, image_size, image_size).astype(np.float32)

@@ -1,7 +1,7 @@
 """VOC mAP of the YOLOv2 anchor detector over an image set (not in the reference, which has no evaluation code):
     python -m tensorflow_yolo2_amd.pascal.pascal_eval_yolov2 --devkit data/VOCdevkit --image-set test \
         [--weights FILE | --ckpt-dir DIR] [--size 416] [--batch 32] [--metric 07|10]
-        [--per-class [--max-per-class 32]] [--results-dir DIR]
+        [--per-class [--max-per-class 32]] [--letterbox [--fill 127]] [--results-dir DIR]
 The shape is pascal_eval_darknet.py's.  The images come from the device-resident pool in list order; per batch, four
 calls on one stream and nothing on the host:
     DeviceVOC.eval_batch (resize) -> YOLOv2Detector.detect_batch = forward on the uint8 batch (moving statistics) ->
@@ -12,6 +12,9 @@ once and utils/detect_batch.map_from_flags makes the per-class curves and the AP
 its best class (score = objectness * class probability): one row per anchor.  With --per-class it is a row per class
 whose score passes, as Darknet's `valid` writes (y2_detect_anchor_classes_batch; the matcher then runs over the
 (image, class) segments): the protocol of the published YOLOv2 figures, up to this repository's integer-pixel IoU.
+With --letterbox every image keeps its aspect ratio, as at Darknet's test time: eval_batch embeds it in a square of
+--fill (y2_letterbox_u8_batch) and the detect launch un-maps the boxes from that rectangle (y2_detect_anchor_batch_lb,
+y2_detect_anchor_classes_batch_lb); the default is the plain stretch, bit for bit as before.
 The anchors and the class count are the snapshot's (pascal_train_yolov2.py); with neither --weights nor --ckpt-dir the
 initial values are evaluated with the published VOC anchors: a plumbing run."""
 import argparse
@@ -45,6 +48,10 @@ def parse_args(argv=None):
                     help="with --per-class: rows kept per image and class (Darknet has no cap: the count of saturated "
                          "segments is printed).  The device buffer takes 32 bytes per row, images x classes x this "
                          "many rows: about 100 MB for VOC07 test at the default")
+    ap.add_argument("--letterbox", action="store_true",
+                    help="keep every image's aspect ratio: embed it in the square input between bars of --fill and "
+                         "un-map the boxes from that rectangle, as Darknet's test-time input (default: a plain stretch)")
+    ap.add_argument("--fill", type=int, default=127, help="with --letterbox: the value of the bars, 0..255")
     ap.add_argument("--results-dir", default=None,
                     help="write the devkit's comp4_det_<image-set>_<class>.txt files (image_id score xmin ymin xmax "
                          "ymax) there, from the rows of either form")
@@ -58,6 +65,8 @@ def parse_args(argv=None):
         ap.error("--size %d: more than 2048 candidates per image" % args.size)
     if args.batch < 1 or args.max_out < 1 or args.width_div < 1 or args.max_per_class < 1:
         ap.error("--batch, --max-out, --max-per-class and --width-div must be at least 1")
+    if not 0 <= args.fill <= 255:
+        ap.error("--fill %d outside 0..255" % args.fill)
     return args
 
 
@@ -81,7 +90,7 @@ def main(argv=None):
         print('Restorining model from weight file {:s}'.format(snapshot))
         restored = net_utils.restore_yolov2_variables(detector, snapshot)
     result = evaluate_yolov2(detector, imdb, args.size, args.thresh, args.nms, args.max_out, args.metric == "07",
-                             args.keep_grids, args.per_class, args.max_per_class)
+                             args.keep_grids, args.per_class, args.max_per_class, args.letterbox, args.fill)
     for c in sorted(result["aps"]):
         print('AP for {:s} = {:.4f}'.format(pascal_voc.CLASSES[c], result["aps"][c]))
     print('Mean AP = {:.4f} ({:d} images, {:d} detections, VOC{:s} metric)'.format(
@@ -98,12 +107,13 @@ def main(argv=None):
 
 
 def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, use_07_metric=True, keep_grids=False,
-                    per_class=False, max_per_class=32):
+                    per_class=False, max_per_class=32, letterbox=False, fill=127):
     """one pass over imdb's image list through `detector` (a YOLOv2Detector of imdb.batch_size images of `size`):
     {"mAP", "aps", "rows", "count", "npos"[, "grids"]} as pascal_eval_darknet.evaluate; everything per image runs on the
     device, one copy at the end.  per_class: one row per (candidate, class) as Darknet's `valid` writes them, at most
     max_per_class per image and class (max_out is not read); an image is then num_class segments of the same buffer,
-    "count" is [entries][num_class] and "saturated" the number of segments whose count reached max_per_class"""
+    "count" is [entries][num_class] and "saturated" the number of segments whose count reached max_per_class.
+    letterbox: the batches are letterboxed between bars of `fill` and the boxes un-mapped from each picture's rectangle"""
     n = imdb.batch_size
     assert detector.batch == n and detector.size == size, (detector.batch, detector.size, n, size)
     S, B, D = detector.S, detector.B, 5 + detector.num_class
@@ -124,17 +134,18 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     difficult = imdb.difficult
     for k in range(batches):
         lo, m = k * n * segs, n * segs
-        images, _valid = imdb.eval_batch(size, k * n)
+        images, _valid = imdb.eval_batch(size, k * n, letterbox=letterbox, fill=fill)
         out = (det[lo:lo + m], score[lo:lo + m], count[lo:lo + m])
         grid_out = grids[k * n:k * n + n] if grids is not None else None
         index = imdb.eval_index
         if per_class:
             detector.detect_classes_batch(images, imdb.table, index, thresh, nms, max_per_class, out=out,
-                                          grid_out=grid_out)
+                                          grid_out=grid_out, letterbox=letterbox)
             seg_index.view(n, segs).copy_(index[:n, None].expand(n, segs))   # on the device: nothing waits
             index = seg_index
         else:
-            detector.detect_batch(images, imdb.table, index, thresh, nms, max_out, out=out, grid_out=grid_out)
+            detector.detect_batch(images, imdb.table, index, thresh, nms, max_out, out=out, grid_out=grid_out,
+                                  letterbox=letterbox)
         engine.voc_match_batch(det[lo:lo + m], score[lo:lo + m], count[lo:lo + m], imdb.boxes, imdb.counts, difficult,
                                index, 0.5, out=flags[lo:lo + m])
     host = acc.cpu().numpy()                                  # the one device-to-host copy (it waits for the stream)

@@ -11,6 +11,8 @@ specification of csrc/augment.hip:
                   (kernel: y2_detect_anchor_batch, which decodes the raw head itself); shares grid_detect's walk.
   anchor_detect_classes  one row per (candidate, class) from y2_decode_anchors' scores [K][C]: anchor_detect per class
                   (kernel: y2_detect_anchor_classes_batch); class_rows flattens a batch of them for map_from_flags.
+                  Both take net_size=N for a letterboxed input (img_dataset/pascal_voc.letterbox_u8): the boxes are
+                  un-mapped from the picture's rectangle (kernels: y2_detect_anchor_batch_lb, ..._classes_batch_lb).
   match_image     the body of utils/voc_eval.eval_class for one image: a TP / FP / ignored flag per detection.
   map_from_flags  the global part: per class a stable sort by score, cumulative sums, utils/voc_eval.average_precision.
 
@@ -98,19 +100,26 @@ def _greedy_walk(valid, box, cls, score, iou_thresh, max_out):
     return det, score[keep].astype(np.float32)
 
 
-def anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh):
+def anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh, net_size=None):
     """every candidate of one image of the YOLOv2 anchor head, from its decode: boxes float32 [K][4] = cx, cy, w, h
     relative to the image (what y2_decode_anchors writes), best float32 [K] and cls int [K] (what y2_class_argmax writes),
-    candidate i = cell * B + b -> (valid, box, cls, score) as grid_candidates.  The resize is a plain stretch, so the
-    relative coordinates map straight to the original image: the float64 products cx * im_w, cy * im_h, w * im_w,
-    h * im_h; from there on every rule is grid_candidates'"""
+    candidate i = cell * B + b -> (valid, box, cls, score) as grid_candidates.  net_size None: the resize was a plain
+    stretch, so the relative coordinates map straight to the original image: the float64 products cx * im_w, cy * im_h,
+    w * im_w, h * im_h.  net_size N: the input was letterboxed (img_dataset/pascal_voc.letterbox_u8 at N) and the
+    products are the exact inverse of that embedding, with (new_w, new_h, ox, oy) = letterbox_geometry(im_h, im_w, N):
+    sx = im_w / new_w, sy = im_h / new_h, (cx * N - ox) * sx, (cy * N - oy) * sy, (w * N) * sx, (h * N) * sy in float64
+    and in this order of operations.  From there on every rule is grid_candidates': a box that lies in a bar maps
+    outside the image and comes out cut, or empty and dropped"""
     boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
     score = np.asarray(best, np.float32).reshape(-1)
     cls = np.asarray(cls).reshape(-1).astype(np.int64)
     assert len(boxes) == len(score) == len(cls), (boxes.shape, score.shape, cls.shape)
     im_w, im_h = int(im_w), int(im_h)
     with np.errstate(all="ignore"):
-        prod = boxes.astype(np.float64) * np.array([im_w, im_h, im_w, im_h], np.float64)
+        if net_size is None:
+            prod = boxes.astype(np.float64) * np.array([im_w, im_h, im_w, im_h], np.float64)
+        else:
+            prod = _letterbox_products(boxes, im_w, im_h, net_size)
         valid = score > np.float32(score_thresh)                          # (a NaN score compares false)
         valid &= (np.isfinite(prod) & (np.abs(prod) < LIMIT)).all(axis=1)
     prod = np.where(valid[:, None], prod, 0.0)
@@ -124,20 +133,34 @@ def anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh):
     return valid, box, cls, score
 
 
-def anchor_detect(boxes, best, cls, im_w, im_h, score_thresh, iou_thresh, max_out):
+def _letterbox_products(boxes, im_w, im_h, net_size):
+    """float64 [K][4]: relative boxes of a letterboxed input of net_size -> x, y, w, h in pixels of the original image"""
+    from ..img_dataset.pascal_voc import letterbox_geometry
+    if int(net_size) != net_size or net_size < 32 or net_size % 32:
+        raise ValueError("net_size %r is not a positive multiple of 32" % (net_size,))
+    new_w, new_h, ox, oy = letterbox_geometry(im_h, im_w, net_size)
+    n = np.float64(net_size)
+    sx, sy = np.float64(im_w) / np.float64(new_w), np.float64(im_h) / np.float64(new_h)
+    b = boxes.astype(np.float64)
+    return np.stack([(b[:, 0] * n - np.float64(ox)) * sx, (b[:, 1] * n - np.float64(oy)) * sy,
+                     (b[:, 2] * n) * sx, (b[:, 3] * n) * sy], axis=1)
+
+
+def anchor_detect(boxes, best, cls, im_w, im_h, score_thresh, iou_thresh, max_out, net_size=None):
     """the decode of ONE image (anchor_candidates' arguments) -> grid_detect's rows: (det int32 [count][6] = xmin, ymin,
-    xmax, ymax, class, candidate index; score float32 [count]); the specification of y2_detect_anchor_batch"""
-    valid, box, cls, score = anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh)
+    xmax, ymax, class, candidate index; score float32 [count]); the specification of y2_detect_anchor_batch and, with
+    net_size, of y2_detect_anchor_batch_lb"""
+    valid, box, cls, score = anchor_candidates(boxes, best, cls, im_w, im_h, score_thresh, net_size=net_size)
     return _greedy_walk(valid, box, cls, score, iou_thresh, max_out)
 
 
-def anchor_detect_classes(boxes, scores, im_w, im_h, score_thresh, iou_thresh, max_per_class):
+def anchor_detect_classes(boxes, scores, im_w, im_h, score_thresh, iou_thresh, max_per_class, net_size=None):
     """one row per (candidate, class), as Darknet's `valid` writes them: boxes float32 [K][4] and scores float32 [K][C]
     of ONE image (what y2_decode_anchors writes) -> (det int32 [C][max_per_class][6], unused rows -1; score float32
     [C][max_per_class], unused 0; count int32 [C]).  Class c's rows are anchor_detect's with every candidate given the
     class c and the score scores[:, c]: a candidate is valid in every class whose score passes, and each class is
     ordered and walked on its own.  Column 4 is c, column 5 the candidate; the specification of
-    y2_detect_anchor_classes_batch"""
+    y2_detect_anchor_classes_batch and, with net_size (anchor_candidates), of y2_detect_anchor_classes_batch_lb"""
     boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
     scores = np.asarray(scores, np.float32)
     scores = scores.reshape(len(boxes), -1)
@@ -146,7 +169,8 @@ def anchor_detect_classes(boxes, scores, im_w, im_h, score_thresh, iou_thresh, m
     score = np.zeros((C, max_per_class), np.float32)
     count = np.zeros(C, np.int32)
     for c in range(C):
-        d, s = anchor_detect(boxes, scores[:, c], np.full(K, c), im_w, im_h, score_thresh, iou_thresh, max_per_class)
+        d, s = anchor_detect(boxes, scores[:, c], np.full(K, c), im_w, im_h, score_thresh, iou_thresh, max_per_class,
+                             net_size=net_size)
         count[c] = len(d)
         det[c, :len(d)] = d
         score[c, :len(d)] = s

@@ -71,22 +71,25 @@ class YOLOv2Detector:
         return boxes, best, cls, keep, count
 
     def detect_batch(self, images_u8, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None,
-                     grid_out=None):
+                     grid_out=None, letterbox=False):
         """evaluation: images_u8 [N,size,size,3] uint8 BGR (DeviceVOC.eval_batch), table / index the pool's entry table
         and the slots' entries -> (det int32 [N,max_out,6], score [N,max_out], count [N]) in the 1-based pixels of each
         ORIGINAL image: the forward pass on the moving statistics, then ONE launch from the raw head
-        (engine.detect_anchor_batch) -- rows that engine.voc_match_batch reads.  grid_out: keeps the raw head there."""
+        (engine.detect_anchor_batch) -- rows that engine.voc_match_batch reads.  grid_out: keeps the raw head there.
+        letterbox: images_u8 is a letterboxed batch (DeviceVOC.eval_batch(..., letterbox=True)) and the boxes are
+        un-mapped from each picture's rectangle."""
         grid = self.forward(images_u8, out=grid_out)
-        return E.detect_anchor_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh, max_out, out=out)
+        return E.detect_anchor_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh, max_out, out=out,
+                                     net_size=self.size if letterbox else None)
 
     def detect_classes_batch(self, images_u8, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_per_class=32,
-                             out=None, grid_out=None):
+                             out=None, grid_out=None, letterbox=False):
         """detect_batch with one row per (candidate, class), as Darknet's `valid` scores a detector ->
         (det int32 [N,C,max_per_class,6], score [N,C,max_per_class], count [N,C]): engine.detect_anchor_classes_batch on
         the raw head"""
         grid = self.forward(images_u8, out=grid_out)
         return E.detect_anchor_classes_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh,
-                                             max_per_class, out=out)
+                                             max_per_class, out=out, net_size=self.size if letterbox else None)
 
 
 class YOLOv2Trainer:
