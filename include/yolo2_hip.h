@@ -510,6 +510,22 @@ int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t
                        const double* params, int n, int max_obj, int image_size, int max_boxes, float* truth,
                        int32_t* ntruth, void* stream);
 
+/* ---- the classifier's augmentation on the same pool (img_dataset/augment_cls.py is the specification, bit for bit):
+ *      mirror, rotation, scale and crop as ONE affine map.  `params` double [n][9] in device memory, one row per batch
+ *      slot = {m00, m01, m02, m10, m11, m12, hue, sat, exp}: output pixel (u, v) reads the source coordinate
+ *      sx = (m00 * u + m01 * v) + m02, sy = (m10 * u + m11 * v) + m12 (float64, every operation rounded on its own).  A
+ *      coordinate that is not finite or of magnitude >= 2^30 gives `fill`; else x0 = floor(sx), weight
+ *      (int)((sx - x0) * 2048 + 0.5), four taps that read `fill` (0..255) outside the image, the int32 blend of the
+ *      calls above, then the colour stage of y2_augment_u8_batch ((0, 1, 1) = none; fill pixels pass through it too).
+ *      `params` NULL: every slot takes the plain stretch of its entry (augment_cls.identity_row of the table row, formed
+ *      in the kernel) and no colour stage.  `labels` int32 [entries] with `labels_out` int32 [n]: labels_out[b] =
+ *      labels[index[b]] in the same launch; both NULL: no labels.  The flip column of the table is not read; an empty
+ *      table row writes no pixel.  Y2_ERR_ARG: n outside 1..65535, out_h < 1, out_w not a positive multiple of 4, fill
+ *      outside 0..255, `out` not 4-byte aligned, exactly one of labels / labels_out NULL.  One launch. */
+int y2_warp_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, const double* params,
+                     const int32_t* labels, int n, int out_h, int out_w, int fill, uint8_t* out, int32_t* labels_out,
+                     void* stream);
+
 /* ---- evaluation of the grid detector from the same pool (pascal/pascal_eval_darknet.py; utils/detect_batch.py is the
  *      specification and both calls are bit-equal to it): per image, the head's output -> boxes in the pixels of the
  *      ORIGINAL image after a score-ordered class-aware NMS, then the VOC devkit's matching against the image's ground

@@ -304,9 +304,218 @@ __global__ __launch_bounds__(64) void encode_box_list_kernel(const double* __res
     if (lane == 0) ntruth[img] = rows;
 }
 
+// ---- The classifier's augmentation (img_dataset/augment_cls.py): mirror, rotation, scale and crop are ONE affine map from
+// an output pixel index to a source coordinate, so the kernel is a gather of four taps per pixel through that map -- not
+// the row-staged resize above, whose window is axis-aligned.  Bit-equal to augment_cls.warp_affine_u8 + distort_hsv_u8:
+// the coordinates in double with every product and sum rounded on its own (-ffp-contract=off), the validity test before
+// any conversion to integer, the blend in int32, the colour stage through distort_pixel.
+constexpr int kWarpParams = 9;                  // double per batch slot: m00 m01 m02 m10 m11 m12, hue, sat, exp
+constexpr int kWarpTile = 32;                   // a workgroup owns kWarpTile x kWarpTile output pixels: 4 per lane
+constexpr int kWarpLds = 32768;                 // bytes of source staged per tile (augment_cls.LDS_BUDGET)
+constexpr double kWarpLimit = 1073741824.0;     // a coordinate of this magnitude, or not finite, reads as fill
+
+struct WarpMap { double m00, m01, m02, m10, m11, m12; };
+
+// source coordinate of output pixel (u, v); false: not a coordinate (not finite, or |c| >= 2^30) -> the pixel is fill
+Y2_DEV bool warp_coord(const WarpMap& m, int u, int v, double& sx, double& sy) {
+    const double du = (double)u, dv = (double)v;
+    sx = (m.m00 * du + m.m01 * dv) + m.m02;
+    sy = (m.m10 * du + m.m11 * dv) + m.m12;
+    return fabs(sx) < kWarpLimit && fabs(sy) < kWarpLimit;
+}
+
+// one output pixel, b | g << 8 | r << 16.  STAGED: `base` is the LDS copy of source rows ly0 .. ly1, `pitch` bytes each,
+// whose byte 0 is byte `a0` of the source row; else `base` is the image in the pool (a0 = 0, ly0 = 0).  A tap inside the
+// image lies inside [lx0, lx1] x [ly0, ly1] (the tile's box, or the image); one outside reads `fill` and its address
+// is clamped into that rectangle, so that every address formed is readable.
+template <bool STAGED>
+Y2_DEV uint32_t warp_pixel(const uint8_t* base, int64_t pitch, int64_t a0, int lx0, int lx1, int ly0, int ly1, int H,
+                           int W, const WarpMap& m, int u, int v, int fill) {
+    double sx, sy;
+    if (!warp_coord(m, u, v, sx, sy)) return 0x010101u * (uint32_t)fill;
+    const double fx = floor(sx), fy = floor(sy);
+    const int x0 = (int)fx, y0 = (int)fy;       // |c| < 2^30
+    const int wx1 = (int)((sx - fx) * 2048.0 + 0.5), wy1 = (int)((sy - fy) * 2048.0 + 0.5);
+    const int wx0 = 2048 - wx1, wy0 = 2048 - wy1;
+    const bool ol = x0 < 0 || x0 >= W, orr = x0 + 1 < 0 || x0 + 1 >= W;
+    const bool ot = y0 < 0 || y0 >= H, ob = y0 + 1 < 0 || y0 + 1 >= H;
+    const int xa = min(max(x0, lx0), lx1), xb = min(max(x0 + 1, lx0), lx1);
+    const int ya = min(max(y0, ly0), ly1), yb = min(max(y0 + 1, ly0), ly1);
+    const uint8_t *r0, *r1;
+    int ca, cb;
+    if (STAGED) {
+        r0 = base + (ya - ly0) * (int)pitch;
+        r1 = base + (yb - ly0) * (int)pitch;
+        ca = 3 * xa - (int)a0;
+        cb = 3 * xb - (int)a0;
+        uint32_t packed = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int v00 = (ol || ot) ? fill : (int)r0[ca + c], v01 = (orr || ot) ? fill : (int)r0[cb + c];
+            const int v10 = (ol || ob) ? fill : (int)r1[ca + c], v11 = (orr || ob) ? fill : (int)r1[cb + c];
+            const int top = v00 * wx0 + v01 * wx1;
+            const int bot = v10 * wx0 + v11 * wx1;
+            const int val = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;   // <= 255 * 2^22 + 2^21 < 2^31
+            packed |= (uint32_t)(val & 255) << (8 * c);
+        }
+        return packed;
+    }
+    r0 = base + (size_t)ya * pitch;
+    r1 = base + (size_t)yb * pitch;
+    const size_t ga = 3 * (size_t)xa, gb = 3 * (size_t)xb;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int v00 = (ol || ot) ? fill : (int)r0[ga + c], v01 = (orr || ot) ? fill : (int)r0[gb + c];
+        const int v10 = (ol || ob) ? fill : (int)r1[ga + c], v11 = (orr || ob) ? fill : (int)r1[gb + c];
+        const int top = v00 * wx0 + v01 * wx1;
+        const int bot = v10 * wx0 + v11 * wx1;
+        const int val = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;
+        packed |= (uint32_t)(val & 255) << (8 * c);
+    }
+    return packed;
+}
+
+// the lane's 4 pixels (u .. u + 3, v) of one tile: gather, colour, three dwords
+template <bool STAGED>
+Y2_DEV void warp_produce(const uint8_t* base, int64_t pitch, int64_t a0, int lx0, int lx1, int ly0, int ly1, int H, int W,
+                         const WarpMap& m, int u, int v, int fill, bool colour, const float* unit, float hue6, float sat,
+                         float exp, uint32_t* o32) {
+    uint32_t pix[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pix[e] = warp_pixel<STAGED>(base, pitch, a0, lx0, lx1, ly0, ly1, H, W, m, u + e, v, fill);
+    if (colour) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pix[e] = distort_pixel(pix[e], unit, hue6, sat, exp);
+    }
+    o32[0] = pix[0] | pix[1] << 24;
+    o32[1] = pix[1] >> 8 | pix[2] << 16;
+    o32[2] = pix[2] >> 16 | pix[3] << 8;
+}
+
+// grid (tiles of kWarpTile x kWarpTile output pixels, n), 256 lanes; lane l produces the 4 pixels 4 (l % 8) .. + 3 of tile
+// row l / 8 and stores them as three dwords (out_w % 4 == 0, `out` 4-byte aligned).  The source box of the tile is
+// spanned by its four corners through the map -- the map is monotone in u and in v, rounding included -- plus one pixel
+// for the second tap, cut to the image:
+//   a corner that is no coordinate   every pixel decides for itself, the taps read the pool in place
+//   the box is empty                 the tile is fill (through the colour stage), nothing is read
+//   the 16-byte aligned row segments of the box fit kWarpLds bytes: staged with 16-byte loads (pool rows start on 16-byte
+//                                    boundaries and the pitch is a multiple of 16: an aligned superset of a segment lies
+//                                    inside the row), and the taps read LDS
+//   else (strong down-scaling)       the taps read the pool in place
+// The choice depends on the table row, the parameter row and the tile alone (augment_cls.tile_path restates it).
+// PARAMS = false: no parameter rows; the map is augment_cls.identity_row of the table row, formed here in the same
+// float64 operations, and there is no colour stage.  One lane per batch slot copies the slot's class label.
+template <bool PARAMS>
+__global__ __launch_bounds__(kThreads) void warp_u8_kernel(const uint8_t* __restrict__ pool,
+                                                           const int64_t* __restrict__ table,
+                                                           const int32_t* __restrict__ index,
+                                                           const double* __restrict__ params,
+                                                           const int32_t* __restrict__ labels, int out_h, int out_w,
+                                                           int fill, uint8_t* __restrict__ out,
+                                                           int32_t* __restrict__ labels_out) {
+    __shared__ float unit[256];
+    __shared__ __attribute__((aligned(16))) uint8_t rows[kWarpLds];
+    const int tid = threadIdx.x, img = blockIdx.y;
+    const size_t e = index ? (size_t)index[img] : (size_t)img;
+    if (labels_out && blockIdx.x == 0 && tid == 0) labels_out[img] = labels[e];
+    const int64_t* t = table + (size_t)kTable * e;
+    const int64_t off = t[0], pitch64 = t[3];
+    const int H = (int)t[1], W = (int)t[2];
+    if (H < 1 || W < 1) return;                 // (an empty table row: nothing to read, as data.hip)
+    WarpMap m;
+    float hue = 0.0f, sat = 1.0f, exp = 1.0f;
+    if (PARAMS) {
+        const double* prm = params + (size_t)kWarpParams * img;
+        m = WarpMap{prm[0], prm[1], prm[2], prm[3], prm[4], prm[5]};
+        hue = (float)prm[6]; sat = (float)prm[7]; exp = (float)prm[8];
+    } else {                                    // compose(H, W, out_w, out_h, 0, 0, angle 0, no mirror): alpha 1, beta 0
+        const double ax = (double)W / (double)out_w, ay = (double)H / (double)out_h;
+        const double bx = 0.5 * ax - 0.5, by = 0.5 * ay - 0.5;
+        const double cx = (double)(W / 2), cy = (double)(H / 2);
+        m = WarpMap{ax, 0.0, (bx - cx) + cx, 0.0, ay, (by - cy) + cy};
+    }
+    const bool colour = PARAMS && !(hue == 0.0f && sat == 1.0f && exp == 1.0f);
+    const float hue6 = 6.0f * hue;
+    if (colour) {                               // (uniform in the workgroup)
+        unit[tid] = (float)tid / 255.0f;        // kThreads == 256
+        __syncthreads();
+    }
+    const int tiles_x = (out_w + kWarpTile - 1) / kWarpTile;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int u0 = tx * kWarpTile, v0 = ty * kWarpTile;
+    const int u1 = min(u0 + kWarpTile - 1, out_w - 1), v1 = min(v0 + kWarpTile - 1, out_h - 1);
+    const int u = u0 + 4 * (tid & 7), v = v0 + (tid >> 3);
+    const bool active = u < out_w && v < out_h;             // out_w % 4 == 0: the 4 pixels are inside together
+    uint32_t* o32 = (uint32_t*)(out + (((size_t)img * out_h + (active ? v : 0)) * out_w + (active ? u : 0)) * 3);
+    const uint8_t* src = pool + off;
+    double x00, y00, x10, y10, x01, y01, x11, y11;
+    bool box = warp_coord(m, u0, v0, x00, y00);
+    box = warp_coord(m, u1, v0, x10, y10) && box;
+    box = warp_coord(m, u0, v1, x01, y01) && box;
+    box = warp_coord(m, u1, v1, x11, y11) && box;
+    if (box) {
+        const int bx0 = max((int)floor(fmin(fmin(x00, x10), fmin(x01, x11))), 0);
+        const int bx1 = min((int)floor(fmax(fmax(x00, x10), fmax(x01, x11))) + 1, W - 1);
+        const int by0 = max((int)floor(fmin(fmin(y00, y10), fmin(y01, y11))), 0);
+        const int by1 = min((int)floor(fmax(fmax(y00, y10), fmax(y01, y11))) + 1, H - 1);
+        if (bx0 > bx1 || by0 > by1) {           // every tap of every pixel lies outside the image
+            if (!active) return;
+            uint32_t p = 0x010101u * (uint32_t)fill;
+            if (colour) p = distort_pixel(p, unit, hue6, sat, exp);
+            o32[0] = p | p << 24;
+            o32[1] = p >> 8 | p << 16;
+            o32[2] = p >> 16 | p << 8;
+            return;
+        }
+        const int64_t a0 = (3 * (int64_t)bx0) & ~(int64_t)15, a1 = (3 * (int64_t)bx1 + 3 + 15) & ~(int64_t)15;
+        const int64_t seg = a1 - a0, nrow = (int64_t)by1 - by0 + 1;
+        if (((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W && seg * nrow <= kWarpLds) {
+            const int chunks = (int)(seg >> 4), total = chunks * (int)nrow;
+            for (int i = tid; i < total; i += kThreads) {
+                const int r = i / chunks, c = i - r * chunks;
+                *(u32x4*)(rows + r * (int)seg + 16 * c) =
+                    *(const u32x4*)(src + (size_t)(by0 + r) * pitch64 + a0 + 16 * c);
+            }
+            __syncthreads();
+            if (active)
+                warp_produce<true>(rows, seg, a0, bx0, bx1, by0, by1, H, W, m, u, v, fill, colour, unit, hue6, sat, exp,
+                                   o32);
+            return;
+        }
+    }
+    if (active)
+        warp_produce<false>(src, pitch64, 0, 0, W - 1, 0, H - 1, H, W, m, u, v, fill, colour, unit, hue6, sat, exp, o32);
+}
+
 }  // namespace
 
 extern "C" {
+
+int y2_warp_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, const double* params,
+                     const int32_t* labels, int n, int out_h, int out_w, int fill, uint8_t* out, int32_t* labels_out,
+                     void* stream) {
+    if (!pool || !table || !out) return fail(Y2_ERR_ARG, "y2_warp_u8_batch: null pointer");
+    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "y2_warp_u8_batch: n = %d outside 1..65535", n);
+    if (out_h < 1 || out_w < 4 || out_w % 4)
+        return fail(Y2_ERR_ARG, "y2_warp_u8_batch: output %d x %d (out_w must be a positive multiple of 4)", out_h, out_w);
+    if (fill < 0 || fill > 255) return fail(Y2_ERR_ARG, "y2_warp_u8_batch: fill = %d outside 0..255", fill);
+    if ((uintptr_t)out & 3) return fail(Y2_ERR_ARG, "y2_warp_u8_batch: out is not 4-byte aligned");
+    if ((labels == nullptr) != (labels_out == nullptr))
+        return fail(Y2_ERR_ARG, "y2_warp_u8_batch: labels and labels_out come together or not at all");
+    const int64_t tiles = (int64_t)((out_w + kWarpTile - 1) / kWarpTile) * ((out_h + kWarpTile - 1) / kWarpTile);
+    if (tiles > 0x7fffffff) return fail(Y2_ERR_ARG, "y2_warp_u8_batch: output %d x %d has too many tiles", out_h, out_w);
+    const dim3 grid((unsigned)tiles, n);
+    if (params)
+        hipLaunchKernelGGL(warp_u8_kernel<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, params,
+                           labels, out_h, out_w, fill, out, labels_out);
+    else
+        hipLaunchKernelGGL(warp_u8_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, params,
+                           labels, out_h, out_w, fill, out, labels_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_warp_u8_batch: %s", hipGetErrorString(e));
+    return Y2_OK;
+}
 
 int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
                        const double* params, int n, int max_obj, int image_size, int max_boxes, float* truth,

@@ -985,6 +985,36 @@ def letterbox_batch(pool, table, index, n, size, fill=127, out=None):
     return out
 
 
+def warp_batch(pool, table, index, n, size, params=None, fill=127, labels=None, out=None, labels_out=None):
+    """pool / table / index as letterbox_batch, params float64 [n, 9] on the device or None -> out uint8 [n,size,size,3]:
+    every slot through its affine map and colour triple (img_dataset/augment_cls.ClsAugment.image, bit for bit; None: the
+    plain stretch, augment_cls.plain_image).  labels int32 [entries]: also labels_out int32 [n] = labels[index], from the
+    same launch, and the return value is (out, labels_out).  One launch on the current stream."""
+    lib = _lib.load()
+    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert table.shape[0] >= n
+    if params is not None:
+        assert params.is_cuda and params.dtype == torch.float64 and params.is_contiguous() and params.numel() >= 9 * n
+    if out is None:
+        out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=pool.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * size * size * 3
+    if labels is not None:
+        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()
+        if labels_out is None:
+            labels_out = torch.empty((n,), dtype=torch.int32, device=pool.device)
+        assert labels_out.is_cuda and labels_out.dtype == torch.int32 and labels_out.is_contiguous()
+        assert labels_out.numel() >= n
+    else:
+        assert labels_out is None, "labels_out without labels"
+    check(lib.y2_warp_u8_batch(_ptr(pool), _ptr(table), _ptr(index), _ptr(params), _ptr(labels), int(n), int(size),
+                               int(size), int(fill), _ptr(out), _ptr(labels_out), _stream()))
+    return out if labels is None else (out, labels_out)
+
+
 def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None,
                         net_size=None):
     """net [n,S,S,B,5+C] fp32 (the RAW YOLOv2 head), anchors [B,2] in cell units (a float32 device tensor, or anything

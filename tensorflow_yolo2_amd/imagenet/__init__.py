@@ -1,6 +1,8 @@
 """Counterparts of src/imagenet/imagenet_{train,test,predict}_darknet.py (the callers of the classifier path,
-SURVEY.md section 2 row 14).  The reference's ILSVRC loader (img_dataset/ilsvrc2017_cls_multithread.py: ten prefetch
-processes, cv2 augmentation) is out of scope: batches come from synthetic data or from a plain image list."""
+SURVEY.md section 2 row 14).  Batches come from synthetic data, from a plain image list read on the host (load_batch), or
+-- with --device-data -- from a device-resident pool of that list (img_dataset/device_cls.DeviceCls), whose training
+batches carry the augmentation of the reference's ILSVRC loader (img_dataset/ilsvrc2017_cls_multithread.py:320-415) as
+img_dataset/augment_cls.py specifies it.  The loader's ten prefetch processes stay out of scope."""
 import numpy as np
 
 

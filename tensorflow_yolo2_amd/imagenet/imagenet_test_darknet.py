@@ -1,7 +1,8 @@
 """Counterpart of src/imagenet/imagenet_test_darknet.py: validation accuracy with per-batch timing.
-    python -m tensorflow_yolo2_amd.imagenet.imagenet_test_darknet --image-list val.txt --ckpt-dir DIR [--batch 50]
+    python -m tensorflow_yolo2_amd.imagenet.imagenet_test_darknet --image-list val.txt --ckpt-dir DIR [--batch 50] [--device-data]
 darknet19(is_training = 0) -> accuracy per batch (:30-34), the latest snapshot restored (:47-51), the loop and the two
-summary lines of :53-68 (the image count must be a multiple of the batch size, :21)."""
+summary lines of :53-68 (the image count must be a multiple of the batch size, :21).  --device-data: the list is decoded
+once into a device pool (img_dataset/device_cls.DeviceCls) and every batch is its eval_batch, uint8 into the network."""
 import argparse
 
 import torch
@@ -19,7 +20,10 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=50)           # ilsvrc_cls('val', batch_size=50) (:20)
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--ckpt-dir", default=None)
+    ap.add_argument("--device-data", action="store_true", help="batches from a device-resident pool (needs --image-list)")
     args = ap.parse_args(argv)
+    if args.device_data and not args.image_list:
+        ap.error("--device-data needs --image-list")
     size = 224
     items = read_image_list(args.image_list) if args.image_list else None
     if items is not None:
@@ -35,10 +39,16 @@ def main(argv=None):
             print('Restorining model snapshots from {:s}'.format(ckpts[-1]))
             net_utils.restore_variables(net, ckpts[-1], kind="classifier")
             print('Restored.')
+    pool = None
+    if args.device_data:
+        from ..img_dataset.device_cls import DeviceCls
+        pool = DeviceCls(items, args.batch)
     T = Timer()
     accumulated_acc = accumulated_time = 0.0
     for i in range(total_batch):
-        if items is not None:
+        if pool:
+            (images, _valid), labels = pool.eval_batch(size, i * args.batch), pool.labels_of(i * args.batch)
+        elif items is not None:
             images, labels = load_batch(items[i * args.batch:(i + 1) * args.batch], size)
         else:
             images, labels = synthetic.images(args.batch, size, i), synthetic.cls_labels(args.batch, i)

@@ -1,10 +1,18 @@
 """Counterpart of src/imagenet/imagenet_train_darknet.py:
     python -m tensorflow_yolo2_amd.imagenet.imagenet_train_darknet --iters 20 [--image-list train.txt --val-list val.txt]
+        [--device-data [--augment [--angle 7 --crop-chance .75 --hue .1 --saturation 1.5 --exposure 1.5 --fill 127]]
+         [--pool-short-side 292]] [--size 224]
 Graph as the reference (:46-61): darknet19(input, is_training) -> sparse_softmax_cross_entropy_with_logits ->
 reduce_mean -> MomentumOptimizer(0.001, 0.9); accuracy = mean(argmax == label).  Loop as the reference (:87-135): restore
 the latest `train_epoch_<e>` snapshot (variables and Momentum slots; the reference requires one -- here a fresh tree
 starts from the initial values), print loss / accuracy / time every step, a validation batch with is_training = 0 every
-25 steps, a snapshot at the end of every --save-every steps."""
+25 steps, a snapshot at the end of every --save-every steps.
+
+--device-data (needs --image-list): the decoded list lives in device memory (img_dataset/device_cls.DeviceCls) and every
+train batch is one launch -- with --augment the mirror / rotation / scale / crop / colour of img_dataset/augment_cls.py,
+else the plain stretch; the uint8 batch goes to ClassifierTrainer.step as it is (Network.forward converts on the device).
+The validation batch walks --val-list in list order through a second pool's eval_batch.  --pool-short-side L0 stores
+larger images with a short side of L0.  Without --device-data nothing changes."""
 import argparse
 import os
 import re
@@ -29,8 +37,25 @@ def main(argv=None):
     ap.add_argument("--save-every", type=int, default=0, help="steps between snapshots (the reference: every 2 epochs)")
     ap.add_argument("--image-list", default=None, help="training images: lines `path label`")
     ap.add_argument("--val-list", default=None)
+    ap.add_argument("--size", type=int, default=224, help="input size, a multiple of 32 (448: the high-resolution fine-tune)")
+    ap.add_argument("--device-data", action="store_true", help="batches from a device-resident pool (needs --image-list)")
+    ap.add_argument("--augment", action="store_true", help="with --device-data: img_dataset/augment_cls.ClsAugment")
+    ap.add_argument("--angle", type=float, default=7.0)
+    ap.add_argument("--crop-chance", type=float, default=0.75)
+    ap.add_argument("--hue", type=float, default=0.1)
+    ap.add_argument("--saturation", type=float, default=1.5)
+    ap.add_argument("--exposure", type=float, default=1.5)
+    ap.add_argument("--fill", type=int, default=127)
+    ap.add_argument("--pool-short-side", type=int, default=None)
+    ap.add_argument("--seed", type=int, default=0, help="with --device-data: the batch order and the augmentation stream")
     args = ap.parse_args(argv)
-    size = 224
+    if args.device_data and not args.image_list:
+        ap.error("--device-data needs --image-list")
+    if (args.augment or args.pool_short_side is not None) and not args.device_data:
+        ap.error("--augment and --pool-short-side need --device-data")
+    size = args.size
+    if size < 32 or size % 32:
+        ap.error("--size %d is not a positive multiple of 32" % size)
     tr = ClassifierTrainer(args.batch, size, dtype=args.dtype)
     old_epoch = 0
     if args.ckpt_dir:
@@ -43,13 +68,25 @@ def main(argv=None):
             old_epoch = int(re.search(r"_(\d+)\.(npz|ckpt)$", ckpts[-1]).group(1))
     train = read_image_list(args.image_list) if args.image_list else None
     val = read_image_list(args.val_list) if args.val_list else None
+    pool = vpool = None
+    if args.device_data:
+        from ..img_dataset.augment_cls import ClsAugment
+        from ..img_dataset.device_cls import DeviceCls
+        aug = ClsAugment(angle=args.angle, crop_chance=args.crop_chance, hue=args.hue, saturation=args.saturation,
+                         exposure=args.exposure, fill=args.fill) if args.augment else None
+        pool = DeviceCls(train, args.batch, seed=args.seed, augment=aug, pool_short_side=args.pool_short_side)
+        if val:
+            vpool = DeviceCls(val, args.batch, seed=args.seed, pool_short_side=args.pool_short_side)
+        vstart = 0
     epoch = old_epoch + 1
     rng = np.random.default_rng(epoch)
     T = Timer()
     log = []
     for i in range(args.iters):
         T.tic()
-        if train:
+        if pool:
+            images, labels = pool.get(size)
+        elif train:
             pick = [train[j] for j in rng.integers(0, len(train), args.batch)]
             images, labels = load_batch(pick, size)
         else:
@@ -63,8 +100,12 @@ def main(argv=None):
         log.append((loss_value, acc_value))
         if (i + 1) % 25 == 0 and val:
             T.tic()
-            vi, vl = load_batch([val[j] for j in rng.integers(0, len(val), args.batch)], size)
-            vi, vl = torch.as_tensor(vi).cuda(), torch.as_tensor(vl).cuda()
+            if vpool:
+                (vi, _valid), vl = vpool.eval_batch(size, vstart), vpool.labels_of(vstart)
+                vstart = (vstart + args.batch) % len(val)
+            else:
+                vi, vl = load_batch([val[j] for j in rng.integers(0, len(val), args.batch)], size)
+                vi, vl = torch.as_tensor(vi).cuda(), torch.as_tensor(vl).cuda()
             vlogits = tr.net.forward(vi, False, False)                  # is_training: 0
             vloss, _ = E.softmax_cross_entropy(vlogits, vl, need_grad=False)
             print('###validation loss: {:.3}, validation acc: {:.3}, take {:.2}s'

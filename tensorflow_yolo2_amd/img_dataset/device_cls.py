@@ -1,0 +1,132 @@
+"""Device-resident classifier batches: the decoded images of an image list [(path, label)] live ONCE in the uint8 pool of
+device_voc.py (same layout, same entry table), the labels in an int32 [entries] device tensor, and every training batch
+-- at any size -- is ONE launch of y2_warp_u8_batch (csrc/augment.hip): mirror, rotation, scale, crop, colour and the
+labels of the slots.  After start-up the host touches no pixel; per batch it draws the parameter rows
+(augment_cls.ClsAugment.draw_batch: one block of uniforms, vector arithmetic) and uploads them with the index.
+
+For equal arguments the k-th get(size) equals the k-th get_u8(size) of the host batcher cls_images (cls_images.py) on both
+arrays: both walk pascal_voc.ShardedOrder and the kernel is bit-equal to augment_cls.py.  With augment=None the kernel
+forms the plain stretch of every entry itself (params = NULL: augment_cls.identity_row).
+
+eval_batch(size, start) is the plain stretch of the reference's non-augmented image_read in LIST order
+(y2_resize_bilinear_u8_batch through device_voc.list_batch, as DeviceImages.batch(..., letterbox=False)); labels_of(start)
+returns the labels of the same slots."""
+import ctypes as C
+import os
+import zlib
+
+import numpy as np
+
+from .cls_images import check_items, stored_image
+from .device_voc import DEFAULT_MAX_POOL_BYTES, DeviceVOC, list_batch, padded_rows, pool_layout, _ptr
+from .pascal_voc import ShardedOrder, imread_bgr
+
+
+class DeviceCls(ShardedOrder):
+    def __init__(self, items, batch_size, seed=0, rank=0, world=1, device="cuda",
+                 max_pool_bytes=DEFAULT_MAX_POOL_BYTES, augment=None, pool_short_side=None):
+        self.items = check_items(items, batch_size, pool_short_side)
+        self.batch_size, self.device = int(batch_size), device
+        self.pool_short_side = pool_short_side
+        self._init_order(seed, rank, world)
+        self.augment = augment
+        if augment is not None:
+            from .augment_cls import generator
+            self.aug_rng = generator(seed, rank)            # its own stream: the batch order is that of augment=None
+        from PIL import Image
+        from .cls_images import stored_shape
+        shapes = []
+        for p, _ in self.items:                             # the header is enough for the layout
+            with Image.open(p) as im:
+                w, h = im.size
+            shapes.append(stored_shape(h, w, pool_short_side))
+        self.entries = [{'imname': p, 'shape': s} for (p, _), s in zip(self.items, shapes)]
+        self.shapes = np.array(shapes, np.int64)
+        self.offsets, self.pitches, self.pool_bytes = pool_layout(shapes)
+        if self.pool_bytes > max_pool_bytes:
+            raise MemoryError("the decoded image pool needs %d bytes (%d images), max_pool_bytes is %d"
+                              % (self.pool_bytes, len(self.entries), max_pool_bytes))
+        table = np.array([(off, s[0], s[1], pitch, 0) for s, off, pitch in zip(shapes, self.offsets, self.pitches)],
+                         np.int64)
+        self.pool = self._alloc_pool(self.pool_bytes)
+        for e, off, pitch in zip(self.entries, self.offsets, self.pitches):
+            img = stored_image(imread_bgr(e['imname']), pool_short_side)   # decoded ONCE; no host copy is kept
+            assert img.shape == (e['shape'][0], e['shape'][1], 3), (e['imname'], img.shape, e['shape'])
+            self._put(self.pool, off, padded_rows(img, pitch).reshape(-1))
+        self.table = self._upload(table)
+        self.labels_host = np.array([l for _, l in self.items], np.int32)
+        self.labels = self._upload(self.labels_host)
+        self.gt_labels = self._start_order([{'imname': p, 'entry': k} for k, (p, _) in enumerate(self.items)])
+        self._check_ranks_agree()
+        self._buffers = {}
+        self._eval_buffers = {}
+
+    # ---- the only places that touch device memory at start-up, as in DeviceVOC
+    _alloc_pool = DeviceVOC._alloc_pool
+    _put = DeviceVOC._put
+    _upload = DeviceVOC._upload
+    _check_ranks_agree = DeviceVOC._check_ranks_agree
+
+    def order_digest(self):
+        """(number of entries, CRC-32 of the current order and its labels): equal on ranks that hold the same list"""
+        text = "\n".join("%s %d" % (os.path.basename(g['imname']), self.labels_host[g['entry']]) for g in self.gt_labels)
+        return len(self.gt_labels), zlib.crc32(text.encode())
+
+    def buffers(self, size):
+        """the (images, labels, index, params) tensors get(size) writes: kept per size, overwritten by the next call"""
+        import torch
+        from .augment_cls import ROW
+        if size < 32 or size % 32:
+            raise ValueError("size %r is not a positive multiple of 32" % (size,))
+        if size not in self._buffers:
+            self._buffers[size] = (
+                torch.empty((self.batch_size, size, size, 3), dtype=torch.uint8, device=self.device),
+                torch.empty(self.batch_size, dtype=torch.int32, device=self.device),
+                torch.empty(self.batch_size, dtype=torch.int32, device=self.device),
+                torch.empty((self.batch_size, ROW), dtype=torch.float64, device=self.device))
+        return self._buffers[size]
+
+    def get(self, size):
+        """(images [B, size, size, 3] uint8 BGR, labels [B] int32), device tensors written on the current stream by one
+        launch; asynchronous: one index upload and, with `augment`, one parameter upload from pinned memory"""
+        import torch
+        from .. import _lib
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("DeviceCls.get needs the pool on the GPU (device=%r)" % (self.device,))
+        images, labels, index, params = self.buffers(size)
+        entries = np.array([self._next()['entry'] for _ in range(self.batch_size)], np.int32)
+        index.copy_(torch.from_numpy(entries).pin_memory(), non_blocking=True)
+        fill = 127
+        if self.augment is not None:
+            rows = self.augment.draw_batch(self.aug_rng, self.shapes[entries], size)
+            params.copy_(torch.from_numpy(rows).pin_memory(), non_blocking=True)
+            fill = self.augment.fill
+        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+        _lib.check(_lib.load().y2_warp_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index),
+                                                _ptr(params) if self.augment is not None else None, _ptr(self.labels),
+                                                self.batch_size, size, size, fill, _ptr(images), _ptr(labels), stream))
+        return images, labels
+
+    def skip_batches(self, k):
+        """advance the order and the augmentation stream by k batches, without a launch"""
+        for _ in range(int(k) * self.batch_size):
+            self._next()
+        if self.augment is not None:
+            self.augment.skip(self.aug_rng, self.batch_size, k)
+
+    def eval_batch(self, size, start):
+        """(images [B, size, size, 3] uint8 BGR, valid): entries start .. start + B - 1 IN LIST ORDER, stretched to size x
+        size on the current stream (DeviceVOC.eval_batch's contract: the last batch repeats its final entry, `eval_index`
+        holds the slots' entries, the cursor of get() is neither read nor moved)"""
+        if self.augment is not None:
+            raise ValueError("evaluation reads the plain image list: build the DeviceCls with augment=None")
+        return list_batch(self, "DeviceCls.eval_batch", size, start, False, 127)
+
+    def labels_of(self, start):
+        """int32 [B] device tensor: the labels of the slots of eval_batch(size, start)"""
+        import torch
+        n = len(self.entries)
+        if not 0 <= start < n:
+            raise IndexError("start = %r outside the %d entries" % (start, n))
+        idx = np.minimum(np.arange(start, start + self.batch_size), n - 1)
+        return torch.from_numpy(self.labels_host[idx]).to(self.device)
