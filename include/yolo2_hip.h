@@ -598,6 +598,24 @@ int y2_voc_match_batch(const int* det, const float* score, const int* count, con
                        const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
                        int max_out, float iou_thresh, int* flags, void* stream);
 
+/* ---- classifier scoring over several views of an image (csrc/score.hip; specification: utils/score_views.py, float64).
+ * logits [n * views][classes] fp32, row b * views + v is view v of image b.  Per view p_v[c] = exp(x_v[c] - max_v) /
+ * sum_c exp(x_v[c] - max_v), then p[c] = (1 / views) * sum_v p_v[c] (Darknet's validate_classifier_10 averages the
+ * predictions of the views).  The classes are ordered larger score first, equal scores by the lower class index; the
+ * score is the LOGIT for views == 1 (the order of tf.nn.top_k / tf.argmax: two logits that round to one probability still
+ * rank as the logits do) and the float32 p[c] for views > 1.
+ *   prob    [n][classes] or NULL: p
+ *   top_idx, top_val [n][k]: the j-th class in that order and its p; for j >= classes index -1, value 0
+ *   rank    [n] or NULL: the number of classes ordered before labels[b], 0-based
+ *   hits    [4] or NULL, ACCUMULATED (zero it before the first batch): images, top-1 (rank == 0), top-k (rank < k), labels
+ *           outside 0 .. classes - 1.  Only slots b < n_valid count (the repeated last entry of a short final batch);
+ *           every slot gets its other outputs.
+ * A label outside 0 .. classes - 1 forms no address: rank = classes, a miss, one more in hits[3].  views 1..16, k 1..8,
+ * n_valid 0..n; rank and hits need labels.  One workgroup per image, one launch; reductions in a fixed order (two calls on
+ * the same logits return the same bits), integer atomics on hits only. */
+int y2_score_views(const float* logits, const int32_t* labels, int n, int views, int classes, int k, int n_valid,
+                   float* prob, int32_t* top_idx, float* top_val, int32_t* rank, int32_t* hits, void* stream);
+
 /* ---- host utility: CRC-32C (Castagnoli) of a host buffer, continuing from `crc` (0 to start).  The checksum of
  *      TensorFlow's V2 checkpoint files (tensor bundle + table blocks), which the reference reads and writes through
  *      tf.train.Saver (src/yolo2_nets/net_utils.py:64-110); used by utils/tf_bundle.py on 100-MB tensors. */

@@ -1147,6 +1147,45 @@ def accuracy(logits, labels):
     return acc[0]
 
 
+def score_views(logits, labels=None, views=1, k=5, n_valid=None, hits=None, want_prob=False, top_idx=None, top_val=None,
+                rank=None, prob=None):
+    """logits fp32 [n * views, classes] (row b * views + v: view v of image b), labels int32 [n] or None ->
+    (top_idx int32 [n, k], top_val [n, k], rank int32 [n], hits int32 [4], prob [n, classes]) as device tensors, None for
+    what was not asked for (rank and hits come with labels, prob with want_prob or a `prob` tensor): softmax per view,
+    mean over the views, the k best classes, the label's rank and the counters of y2_score_views in one launch on the
+    current stream (utils/score_views.score_views_ref is the specification).  `hits` is ACCUMULATED: pass the tensor of
+    the previous batch (None: a zeroed one); only the first n_valid images count (None: all).  top_idx, top_val, rank and
+    prob may be the caller's own tensors."""
+    lib = _lib.load()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+    views, k = int(views), int(k)
+    rows, classes = logits.shape
+    if views < 1 or rows % views or rows == 0:
+        raise ValueError("%d rows of logits are not a positive multiple of views = %d" % (rows, views))
+    n = rows // views
+    n_valid = n if n_valid is None else int(n_valid)
+    dev = logits.device
+
+    def own(t, shape, dtype, name):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), (name, t.shape)
+        return t
+    top_idx = own(top_idx, (n, k), torch.int32, "top_idx")
+    top_val = own(top_val, (n, k), torch.float32, "top_val")
+    if labels is not None:
+        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == n
+        rank = own(rank, (n,), torch.int32, "rank")
+        hits = torch.zeros(4, dtype=torch.int32, device=dev) if hits is None else own(hits, (4,), torch.int32, "hits")
+    else:
+        assert rank is None and hits is None, "rank and hits need labels"
+    if want_prob or prob is not None:
+        prob = own(prob, (n, classes), torch.float32, "prob")
+    check(lib.y2_score_views(_ptr(logits), _ptr(labels), n, views, classes, k, n_valid, _ptr(prob), _ptr(top_idx),
+                             _ptr(top_val), _ptr(rank), _ptr(hits), _stream()))
+    return top_idx, top_val, rank, hits, prob
+
+
 def conv2d(x, w, bias=None, dtype="f32"):
     """tf.nn.conv2d(x, W, [1,1,1,1], 'SAME') (+ bias) on fp32 NHWC / HWIO device tensors."""
     lib = _lib.load()

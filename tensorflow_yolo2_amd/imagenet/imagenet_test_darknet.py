@@ -1,10 +1,19 @@
 """Counterpart of src/imagenet/imagenet_test_darknet.py: validation accuracy with per-batch timing.
-    python -m tensorflow_yolo2_amd.imagenet.imagenet_test_darknet --image-list val.txt --ckpt-dir DIR [--batch 50] [--device-data]
+    python -m tensorflow_yolo2_amd.imagenet.imagenet_test_darknet --image-list val.txt --ckpt-dir DIR [--batch 50] [--device-data
+        [--views stretch|centre|ten] [--topk 5] [--crop-margin 32]]
 darknet19(is_training = 0) -> accuracy per batch (:30-34), the latest snapshot restored (:47-51), the loop and the two
 summary lines of :53-68 (the image count must be a multiple of the batch size, :21).  --device-data: the list is decoded
-once into a device pool (img_dataset/device_cls.DeviceCls) and every batch is its eval_batch, uint8 into the network."""
+once into a device pool (img_dataset/device_cls.DeviceCls) and every batch is its eval_batch, uint8 into the network.
+
+--views / --topk (with --device-data): Darknet's classifier validation.  Every image gives V views (img_dataset/
+eval_views.py: the stretch, the aspect-preserving centre crop of validate_classifier_single, or the ten crops of
+validate_classifier_10 with --crop-margin), --batch keeps counting IMAGES and the network is built at batch x V; per batch
+DeviceCls.eval_views -> forward -> engine.score_views (softmax per view, mean over the views, top-k, the label's rank) into
+one counter tensor on the device.  The image count need not be a multiple of the batch (the short last batch repeats its
+final entry, which the counters skip), and the summary is top-1 / top-k over the images, not a mean of batch means."""
 import argparse
 
+import numpy as np
 import torch
 
 from .. import engine as E, synthetic
@@ -21,15 +30,33 @@ def main(argv=None):
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--ckpt-dir", default=None)
     ap.add_argument("--device-data", action="store_true", help="batches from a device-resident pool (needs --image-list)")
+    ap.add_argument("--views", default=None, choices=("stretch", "centre", "ten"),
+                    help="with --device-data: the evaluation views of every image (img_dataset/eval_views.py)")
+    ap.add_argument("--topk", type=int, default=None, help="with --device-data: also the top-k accuracy (5)")
+    ap.add_argument("--crop-margin", type=int, default=32, help="--views ten: the short side is scaled to 224 + margin")
     args = ap.parse_args(argv)
     if args.device_data and not args.image_list:
         ap.error("--device-data needs --image-list")
+    scored = args.views is not None or args.topk is not None
+    if scored and not args.device_data:
+        ap.error("--views and --topk need --device-data")
     size = 224
     items = read_image_list(args.image_list) if args.image_list else None
-    if items is not None:
-        assert 0 == (len(items) % args.batch)
-    total_batch = len(items) // args.batch if items is not None else args.batches
-    net = E.Network(list(E.CORE_SPEC) + list(E.CLS_HEAD_SPEC), args.batch, size, size, dtype=args.dtype,
+    V = 1
+    if scored:
+        from ..img_dataset.eval_views import VIEWS
+        views, topk = args.views or "stretch", 5 if args.topk is None else args.topk
+        if not 1 <= topk <= 8:
+            ap.error("--topk %d outside 1..8" % topk)
+        if args.crop_margin < 0:
+            ap.error("--crop-margin %d below 0" % args.crop_margin)
+        V = VIEWS[views]
+        total_batch = (len(items) + args.batch - 1) // args.batch
+    else:
+        if items is not None:
+            assert 0 == (len(items) % args.batch)
+        total_batch = len(items) // args.batch if items is not None else args.batches
+    net = E.Network(list(E.CORE_SPEC) + list(E.CLS_HEAD_SPEC), args.batch * V, size, size, dtype=args.dtype,
                     core_layers=len(E.CORE_SPEC) + len(E.CLS_HEAD_SPEC), tail=E._lib.Y2_TAIL_AVGPOOL, tail_k=size // 32,
                     training=False)
     net.init_params(0)
@@ -45,6 +72,35 @@ def main(argv=None):
         pool = DeviceCls(items, args.batch)
     T = Timer()
     accumulated_acc = accumulated_time = 0.0
+    if scored:
+        hits = torch.zeros(4, dtype=torch.int32, device="cuda")
+        ranks = torch.empty(total_batch * args.batch, dtype=torch.int32, device="cuda")
+        seen = np.zeros(4, np.int64)
+        for i in range(total_batch):
+            start = i * args.batch
+            images, valid = pool.eval_views(size, start, views, margin=args.crop_margin)
+            labels = pool.labels_of(start)
+            T.tic()
+            logits_value = net.forward(images, False, False).contiguous().float()
+            E.score_views(logits_value, labels, views=V, k=topk, n_valid=valid, hits=hits,
+                          rank=ranks[start:start + args.batch])
+            now = hits.cpu().numpy().astype(np.int64)                   # the host read closes the timed region: 16 bytes
+            _time = T.toc(average=False)
+            d = now - seen
+            seen = now
+            print("batch {:d}/{:d}, acc: {:3f}, time: {:2f}sec, top-{:d}: {:3f}"
+                  .format(i + 1, total_batch, d[1] / float(d[0]), _time, topk, d[2] / float(d[0])))
+            accumulated_time += _time
+        images_seen = int(seen[0])
+        assert images_seen == len(items), (images_seen, len(items))
+        top1, topk_acc = seen[1] / float(images_seen), seen[2] / float(images_seen)
+        print("###########validation accuracy:", top1)
+        print("###########validation top-{:d} accuracy:".format(topk), topk_acc)
+        if seen[3]:
+            print("###########labels outside the %d classes: %d" % (logits_value.shape[1], seen[3]))
+        print("###########average time per batch:", (accumulated_time / float(total_batch)))
+        return {"accuracy": top1, "time_per_batch": accumulated_time / float(total_batch), "network": net, "top1": top1,
+                "topk": topk_acc, "images": images_seen, "ranks": ranks[:images_seen].cpu().numpy()}
     for i in range(total_batch):
         if pool:
             (images, _valid), labels = pool.eval_batch(size, i * args.batch), pool.labels_of(i * args.batch)

@@ -1,7 +1,7 @@
 """Counterpart of src/imagenet/imagenet_train_darknet.py:
     python -m tensorflow_yolo2_amd.imagenet.imagenet_train_darknet --iters 20 [--image-list train.txt --val-list val.txt]
         [--device-data [--augment [--angle 7 --crop-chance .75 --hue .1 --saturation 1.5 --exposure 1.5 --fill 127]]
-         [--pool-short-side 292]] [--size 224]
+         [--pool-short-side 292] [--val-views stretch|centre|ten]] [--size 224]
 Graph as the reference (:46-61): darknet19(input, is_training) -> sparse_softmax_cross_entropy_with_logits ->
 reduce_mean -> MomentumOptimizer(0.001, 0.9); accuracy = mean(argmax == label).  Loop as the reference (:87-135): restore
 the latest `train_epoch_<e>` snapshot (variables and Momentum slots; the reference requires one -- here a fresh tree
@@ -12,7 +12,8 @@ starts from the initial values), print loss / accuracy / time every step, a vali
 train batch is one launch -- with --augment the mirror / rotation / scale / crop / colour of img_dataset/augment_cls.py,
 else the plain stretch; the uint8 batch goes to ClassifierTrainer.step as it is (Network.forward converts on the device).
 The validation batch walks --val-list in list order through a second pool's eval_batch.  --pool-short-side L0 stores
-larger images with a short side of L0.  Without --device-data nothing changes."""
+larger images with a short side of L0; --val-views centre | ten scores the validation batch on evaluation views
+(img_dataset/eval_views.py, averaged by engine.score_views) in place of the stretch.  Without --device-data nothing changes."""
 import argparse
 import os
 import re
@@ -47,12 +48,16 @@ def main(argv=None):
     ap.add_argument("--exposure", type=float, default=1.5)
     ap.add_argument("--fill", type=int, default=127)
     ap.add_argument("--pool-short-side", type=int, default=None)
+    ap.add_argument("--val-views", default="stretch", choices=("stretch", "centre", "ten"),
+                    help="with --device-data and --val-list: the views of a validation image (stretch: eval_batch)")
     ap.add_argument("--seed", type=int, default=0, help="with --device-data: the batch order and the augmentation stream")
     args = ap.parse_args(argv)
     if args.device_data and not args.image_list:
         ap.error("--device-data needs --image-list")
     if (args.augment or args.pool_short_side is not None) and not args.device_data:
         ap.error("--augment and --pool-short-side need --device-data")
+    if args.val_views != "stretch" and not (args.device_data and args.val_list):
+        ap.error("--val-views needs --device-data and --val-list")
     size = args.size
     if size < 32 or size % 32:
         ap.error("--size %d is not a positive multiple of 32" % size)
@@ -78,6 +83,14 @@ def main(argv=None):
         if val:
             vpool = DeviceCls(val, args.batch, seed=args.seed, pool_short_side=args.pool_short_side)
         vstart = 0
+        if vpool and args.val_views != "stretch":
+            from ..img_dataset.eval_views import VIEWS
+            vviews = VIEWS[args.val_views]
+            # the trainer's network is built at the train batch: the views of a validation batch need one of their own,
+            # on the trainer's variables and batch-norm state
+            vnet = E.Network(tr.net.spec, args.batch * vviews, size, size, dtype=args.dtype,
+                             core_layers=tr.net.core_layers, tail=E._lib.Y2_TAIL_AVGPOOL, tail_k=size // 32,
+                             training=False, buffers=(tr.net.params, None, tr.net.state))
     epoch = old_epoch + 1
     rng = np.random.default_rng(epoch)
     T = Timer()
@@ -100,16 +113,30 @@ def main(argv=None):
         log.append((loss_value, acc_value))
         if (i + 1) % 25 == 0 and val:
             T.tic()
-            if vpool:
+            if vpool and args.val_views != "stretch":
+                (vi, _valid), vl = vpool.eval_views(size, vstart, args.val_views), vpool.labels_of(vstart)
+                vstart = (vstart + args.batch) % len(val)
+                vnet.params_changed()                                       # the optimizer has moved the variables
+                vlogits = vnet.forward(vi, False, False).contiguous().float()
+                _, _, _, vhits, vprob = E.score_views(vlogits, vl, views=vviews, k=5, want_prob=True)
+                vh, vp, lab = vhits.cpu().numpy(), vprob.cpu().numpy(), vl.cpu().numpy()
+                # the loss of the averaged prediction, -log p[label], the mean over the batch (host-side reporting)
+                with np.errstate(divide="ignore"):                          # (p = 0 in float32: an infinite loss)
+                    vloss_value = float(-np.log(vp[np.arange(len(lab)), np.clip(lab, 0, vp.shape[1] - 1)]
+                                                .astype(np.float64)).mean())
+                print('###validation loss: {:.3}, validation acc: {:.3}, take {:.2}s'
+                      .format(vloss_value, vh[1] / float(vh[0]), T.toc(average=False)))
+            elif vpool:
                 (vi, _valid), vl = vpool.eval_batch(size, vstart), vpool.labels_of(vstart)
                 vstart = (vstart + args.batch) % len(val)
             else:
                 vi, vl = load_batch([val[j] for j in rng.integers(0, len(val), args.batch)], size)
                 vi, vl = torch.as_tensor(vi).cuda(), torch.as_tensor(vl).cuda()
-            vlogits = tr.net.forward(vi, False, False)                  # is_training: 0
-            vloss, _ = E.softmax_cross_entropy(vlogits, vl, need_grad=False)
-            print('###validation loss: {:.3}, validation acc: {:.3}, take {:.2}s'
-                  .format(float(vloss), float(E.accuracy(vlogits, vl)), T.toc(average=False)))
+            if not (vpool and args.val_views != "stretch"):
+                vlogits = tr.net.forward(vi, False, False)                  # is_training: 0
+                vloss, _ = E.softmax_cross_entropy(vlogits, vl, need_grad=False)
+                print('###validation loss: {:.3}, validation acc: {:.3}, take {:.2}s'
+                      .format(float(vloss), float(E.accuracy(vlogits, vl)), T.toc(average=False)))
         if args.ckpt_dir and ((args.save_every and (i + 1) % args.save_every == 0) or i + 1 == args.iters):
             save_path = os.path.join(args.ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_epoch_' + str(epoch) + '.' + args.ckpt_format)
             net_utils.save_variables(tr.net, save_path, kind="classifier", optimizer=tr.opt)

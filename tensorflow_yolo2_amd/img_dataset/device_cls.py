@@ -10,7 +10,8 @@ forms the plain stretch of every entry itself (params = NULL: augment_cls.identi
 
 eval_batch(size, start) is the plain stretch of the reference's non-augmented image_read in LIST order
 (y2_resize_bilinear_u8_batch through device_voc.list_batch, as DeviceImages.batch(..., letterbox=False)); labels_of(start)
-returns the labels of the same slots."""
+returns the labels of the same slots.  eval_views(size, start, views) is the same walk with V evaluation views per entry
+(img_dataset/eval_views.py: stretch, centre crop, ten crops) from one launch of y2_warp_u8_batch."""
 import ctypes as C
 import os
 import zlib
@@ -60,6 +61,7 @@ class DeviceCls(ShardedOrder):
         self._check_ranks_agree()
         self._buffers = {}
         self._eval_buffers = {}
+        self._view_buffers = {}
 
     # ---- the only places that touch device memory at start-up, as in DeviceVOC
     _alloc_pool = DeviceVOC._alloc_pool
@@ -121,6 +123,42 @@ class DeviceCls(ShardedOrder):
         if self.augment is not None:
             raise ValueError("evaluation reads the plain image list: build the DeviceCls with augment=None")
         return list_batch(self, "DeviceCls.eval_batch", size, start, False, 127)
+
+    def eval_views(self, size, start, views="centre", margin=32, fill=127):
+        """(images [B * V, size, size, 3] uint8 BGR, valid): slot b * V + v is view v (eval_views.view_rows) of entry
+        min(start + b, E - 1) IN LIST ORDER -- the last batch repeats its final entry, `valid` counts the entries that
+        are no repeat, the cursor of get() is neither read nor moved.  One launch of y2_warp_u8_batch on the current
+        stream with the repeated index and one pinned upload of the B * V parameter rows; the buffers are kept per
+        (size, views) and overwritten by the next call; bit-equal to eval_views.view_images."""
+        import torch
+        from .. import _lib
+        from .augment_cls import ROW
+        from .eval_views import VIEWS, view_rows
+        if self.augment is not None:
+            raise ValueError("evaluation reads the plain image list: build the DeviceCls with augment=None")
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("DeviceCls.eval_views needs the pool on the GPU (device=%r)" % (self.device,))
+        if not (0 <= fill <= 255 and int(fill) == fill):
+            raise ValueError("fill %r is not an integer of 0..255" % (fill,))
+        n = len(self.entries)
+        if not 0 <= start < n:
+            raise IndexError("start = %r outside the %d entries" % (start, n))
+        entries = np.minimum(np.arange(start, start + self.batch_size), n - 1)
+        rows = view_rows(self.shapes[entries], size, views, margin)         # (raises for the other arguments)
+        V = VIEWS[views]
+        slots = self.batch_size * V
+        if (size, views) not in self._view_buffers:
+            self._view_buffers[(size, views)] = (
+                torch.empty((slots, size, size, 3), dtype=torch.uint8, device=self.device),
+                torch.empty(slots, dtype=torch.int32, device=self.device),
+                torch.empty((slots, ROW), dtype=torch.float64, device=self.device))
+        images, index, params = self._view_buffers[(size, views)]
+        index.copy_(torch.from_numpy(np.repeat(entries, V).astype(np.int32)).pin_memory(), non_blocking=True)
+        params.copy_(torch.from_numpy(rows.reshape(slots, ROW)).pin_memory(), non_blocking=True)
+        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+        _lib.check(_lib.load().y2_warp_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index), _ptr(params), None, slots,
+                                                size, size, int(fill), _ptr(images), None, stream))
+        return images, min(self.batch_size, n - start)
 
     def labels_of(self, start):
         """int32 [B] device tensor: the labels of the slots of eval_batch(size, start)"""
