@@ -5,18 +5,18 @@
 // resize coefficients in double in the specification's operation order (as data.hip), the colour stage in float32
 // with one correctly rounded operation per specification operation.  The file is compiled with -ffp-contract=off: a
 // fused multiply-add in x * 255 + 0.5 or 1 - s * f rounds once where the specification rounds twice.
+// Here: what the window, the colour stage and the warp need of their own (the x table with fill flags, tap_pixel,
+// distort_pixel, the band loop with its staging of rows outside the image, the box-list compaction, the warp's tiles).
+// Coefficients, blend, three-dword store, the window arithmetic of the boxes and the body of the label-grid kernel are
+// data_common.h's: one definition with data.hip.
 #include "data_common.h"
 using namespace y2;
 
 namespace {
 
-constexpr int kParams = 8;                      // double per batch slot: x0, y0, cw, ch, flip, hue, sat, exp
 // XCoef here: offsets CLAMPED into the source row (every address is readable whatever the window is), and above the
 // 11-bit weight (0 .. 2048) of w1 a flag where that pixel of the window lies outside the image and reads as the fill
 constexpr int kFillLeft = 1 << 12, kFillRight = 1 << 13;
-
-// a window coordinate of the parameter row as an integer of [lo, hi] (not a number -> lo)
-Y2_DEV int win_int(double v, int lo, int hi) { return (int)fmin(fmax(v, (double)lo), (double)hi); }
 
 // window index i -> source index x0 + i clamped into [0, n), and whether it was outside
 Y2_DEV int src_index(int x0, int i, int n, bool& outside) {
@@ -25,24 +25,25 @@ Y2_DEV int src_index(int x0, int i, int n, bool& outside) {
     return (int)min(max(s, 0LL), (long long)n - 1);
 }
 
-// one output pixel, b | g << 8 | r << 16: r0 / r1 are the two source rows (LDS or global), f0 / f1 say that the whole
-// row lies outside the image
-Y2_DEV uint32_t resize_pixel(const uint8_t* r0, const uint8_t* r1, const XCoef q, int wy1, bool f0, bool f1, int fill) {
-    const int wy0 = 2048 - wy1;
-    const int a0 = q.x0, a1 = a0 + q.dx;
-    const int wx1 = q.w1 & 4095, wx0 = 2048 - wx1;
-    const bool fl = q.w1 & kFillLeft, fr = q.w1 & kFillRight;
+// one output pixel, b | g << 8 | r << 16, from the taps at bytes ca (left) and cb (right) of the source rows r0 / r1 (LDS
+// or global): fl / fr / f0 / f1 say that the left / right column, the upper / lower row lies outside the image -- such a
+// tap reads `fill`, whatever its (readable) address holds
+template <typename Off>
+Y2_DEV uint32_t tap_pixel(const uint8_t* r0, const uint8_t* r1, Off ca, Off cb, bool fl, bool fr, bool f0, bool f1,
+                          int wx1, int wy1, int fill) {
     uint32_t packed = 0;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const int v00 = (fl || f0) ? fill : (int)r0[a0 + c], v01 = (fr || f0) ? fill : (int)r0[a1 + c];
-        const int v10 = (fl || f1) ? fill : (int)r1[a0 + c], v11 = (fr || f1) ? fill : (int)r1[a1 + c];
-        const int top = v00 * wx0 + v01 * wx1;
-        const int bot = v10 * wx0 + v11 * wx1;
-        const int v = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;   // <= 255 * 2^22 + 2^21 < 2^31
-        packed |= (uint32_t)(v & 255) << (8 * c);
+        const int v00 = (fl || f0) ? fill : (int)r0[ca + c], v01 = (fr || f0) ? fill : (int)r0[cb + c];
+        const int v10 = (fl || f1) ? fill : (int)r1[ca + c], v11 = (fr || f1) ? fill : (int)r1[cb + c];
+        packed |= (uint32_t)(blend4(v00, v01, v10, v11, wx1, wy1) & 255) << (8 * c);
     }
     return packed;
+}
+
+// one pixel of the row-staged resize: f0 / f1 say that the whole source row lies outside the image
+Y2_DEV uint32_t resize_pixel(const uint8_t* r0, const uint8_t* r1, const XCoef q, int wy1, bool f0, bool f1, int fill) {
+    return tap_pixel(r0, r1, q.x0, q.x0 + q.dx, q.w1 & kFillLeft, q.w1 & kFillRight, f0, f1, q.w1 & 4095, wy1, fill);
 }
 
 Y2_DEV uint32_t to_u8(float x) { return (uint32_t)min(max((int)(x * 255.0f + 0.5f), 0), 255); }
@@ -94,11 +95,8 @@ Y2_DEV void produce_rows(const uint8_t* base, int64_t pitch, const XCoef* xt, co
             for (int e = 0; e < VEC; ++e) pix[e] = distort_pixel(pix[e], unit, hue6, sat, exp);
         }
         uint8_t* o = obase + (size_t)j * rowbytes + 3 * px;
-        if (VEC == 4) {                         // 12 bytes at a multiple of 12 of a 4-byte aligned batch
-            uint32_t* o32 = (uint32_t*)o;
-            o32[0] = pix[0] | pix[1] << 24;
-            o32[1] = pix[1] >> 8 | pix[2] << 16;
-            o32[2] = pix[2] >> 16 | pix[3] << 8;
+        if (VEC == 4) {
+            store_px4((uint32_t*)o, pix);
         } else {
             o[0] = (uint8_t)pix[0];
             o[1] = (uint8_t)(pix[0] >> 8);
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(kThreads) void augment_u8_kernel(const uint8_t* __r
     }
     unit[tid] = (float)tid / 255.0f;            // kThreads == 256
     __syncthreads();
-    const bool staged = pitch64 <= kMaxPitch && ((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W;
+    const bool staged = pitch64 <= kMaxPitch && stageable(off, pitch64, W);
     const int pitch = (int)pitch64;
     const uint8_t* src = pool + off;
     const int rowbytes = 3 * out_w, groups = out_w / VEC;   // (VEC = 4 is launched for out_w % 4 == 0 only)
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void augment_u8_kernel(const uint8_t* __r
     for (int g0 = 0; g0 < nrows; g0 += kRows) {
         const int gr = min(kRows, nrows - g0);
         if (staged) {
-            const int chunks = pitch >> 4;
+            const int chunks = pitch >> 4;          // data_common.h's stage_rows with the fill: see there
             for (int i = tid; i < 2 * gr * chunks; i += kThreads) {
                 const int slot = i / chunks, c = i - slot * chunks;
                 const int* y = yc[g0 + (slot >> 1)];
@@ -187,8 +185,8 @@ __global__ __launch_bounds__(kThreads) void augment_u8_kernel(const uint8_t* __r
     }
 }
 
-// data.hip's label kernel with the boxes following the window: x = (bx - 1 - x0) * (image_size / cw), an object whose
-// unclamped centre leaves [0, image_size) is dropped, and the mirror is the entry's flip XOR the row's.
+// the label grid with the boxes following the window (data_common.h: encode_labels): x = (bx - 1 - x0) * (image_size /
+// cw), an object whose unclamped centre leaves [0, image_size) is dropped, and the mirror is the entry's flip XOR the row's
 __global__ __launch_bounds__(kThreads) void encode_labels_window_kernel(const double* __restrict__ boxes,
                                                                         const int32_t* __restrict__ counts,
                                                                         const int64_t* __restrict__ table,
@@ -196,46 +194,7 @@ __global__ __launch_bounds__(kThreads) void encode_labels_window_kernel(const do
                                                                         const double* __restrict__ params, int max_obj,
                                                                         int image_size, int S, int num_class,
                                                                         float* __restrict__ labels) {
-    const int img = blockIdx.x, D = 5 + num_class;
-    const size_t e = index ? (size_t)index[img] : (size_t)img;
-    float* g = labels + (size_t)img * S * S * D;
-    for (int i = threadIdx.x; i < S * S * D; i += kThreads) g[i] = 0.0f;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const int64_t* t = table + kTable * e;
-    const double* prm = params + (size_t)kParams * img;
-    // the window as the image kernel reads it: integers (a fraction is cut off in both)
-    const double wx0 = win_int(prm[0], -(1 << 30), 1 << 30), wy0 = win_int(prm[1], -(1 << 30), 1 << 30);
-    const double cw = win_int(prm[2], 0, 1 << 30), ch = win_int(prm[3], 0, 1 << 30);
-    if (!(cw >= 1.0 && ch >= 1.0)) return;
-    const bool flip = (t[4] != 0) != (prm[4] != 0.0);
-    const double w_ratio = (double)image_size / cw, h_ratio = (double)image_size / ch;
-    const double hi = (double)(image_size - 1), size = (double)image_size;
-    const int cnt = min(max(counts[e], 0), max_obj);
-    const double* bx = boxes + e * (size_t)max_obj * 5;
-    for (int o = 0; o < cnt; ++o, bx += 5) {
-        double x1 = (bx[0] - 1 - wx0) * w_ratio, y1 = (bx[1] - 1 - wy0) * h_ratio;
-        double x2 = (bx[2] - 1 - wx0) * w_ratio, y2 = (bx[3] - 1 - wy0) * h_ratio;
-        const double ux = (x2 + x1) / 2.0, uy = (y2 + y1) / 2.0;
-        if (!(ux >= 0.0 && ux < size && uy >= 0.0 && uy < size)) continue;   // the centre left the window
-        x1 = hi < x1 ? hi : x1; x1 = 0.0 > x1 ? 0.0 : x1;
-        y1 = hi < y1 ? hi : y1; y1 = 0.0 > y1 ? 0.0 : y1;
-        x2 = hi < x2 ? hi : x2; x2 = 0.0 > x2 ? 0.0 : x2;
-        y2 = hi < y2 ? hi : y2; y2 = 0.0 > y2 ? 0.0 : y2;
-        const double cx = (x2 + x1) / 2.0, cy = (y2 + y1) / 2.0;
-        int x_ind = (int)(cx * S / image_size), y_ind = (int)(cy * S / image_size);
-        if (!(x_ind >= 0 && x_ind < S && y_ind >= 0 && y_ind < S)) continue;
-        if (flip) x_ind = S - 1 - x_ind;
-        float* cell = g + ((size_t)y_ind * S + x_ind) * D;
-        if (cell[0] == 1.0f) continue;
-        cell[0] = 1.0f;
-        cell[1] = (float)(flip ? hi - cx : cx);
-        cell[2] = (float)cy;
-        cell[3] = (float)(x2 - x1);
-        cell[4] = (float)(y2 - y1);
-        const int cls = (int)bx[4];
-        if (cls >= 0 && cls < num_class) cell[5 + cls] = 1.0f;
-    }
+    encode_labels<true>(boxes, counts, table, index, params, max_obj, image_size, S, num_class, labels);
 }
 
 // The label of the anchor model that keeps every object (augment.encode_box_list): grid (n), ONE 64-lane wave per image.
@@ -255,12 +214,7 @@ __global__ __launch_bounds__(64) void encode_box_list_kernel(const double* __res
     const int64_t* t = table + kTable * e;
     double wx0 = 0.0, wy0 = 0.0, cw = (double)t[2], ch = (double)t[1];
     bool flip = t[4] != 0;
-    if (params) {
-        const double* prm = params + (size_t)kParams * img;
-        wx0 = win_int(prm[0], -(1 << 30), 1 << 30); wy0 = win_int(prm[1], -(1 << 30), 1 << 30);
-        cw = win_int(prm[2], 0, 1 << 30); ch = win_int(prm[3], 0, 1 << 30);
-        flip = flip != (prm[4] != 0.0);
-    }
+    if (params) flip = read_window(params + (size_t)kParams * img, flip, wx0, wy0, cw, ch);
     const bool window = cw >= 1.0 && ch >= 1.0;           // a row without a window: an empty list
     const double w_ratio = (double)image_size / cw, h_ratio = (double)image_size / ch;
     const double hi = (double)(image_size - 1), size = (double)image_size;
@@ -275,16 +229,10 @@ __global__ __launch_bounds__(64) void encode_box_list_kernel(const double* __res
         int cls = 0;
         if (o < cnt) {
             const double* bx = bx0 + (size_t)o * 5;
-            double x1 = (bx[0] - 1 - wx0) * w_ratio, y1 = (bx[1] - 1 - wy0) * h_ratio;
-            double x2 = (bx[2] - 1 - wx0) * w_ratio, y2 = (bx[3] - 1 - wy0) * h_ratio;
-            const double ux = (x2 + x1) / 2.0, uy = (y2 + y1) / 2.0;
-            keep = ux >= 0.0 && ux < size && uy >= 0.0 && uy < size;   // else the centre left the window (or not a number)
-            x1 = hi < x1 ? hi : x1; x1 = 0.0 > x1 ? 0.0 : x1;
-            y1 = hi < y1 ? hi : y1; y1 = 0.0 > y1 ? 0.0 : y1;
-            x2 = hi < x2 ? hi : x2; x2 = 0.0 > x2 ? 0.0 : x2;
-            y2 = hi < y2 ? hi : y2; y2 = 0.0 > y2 ? 0.0 : y2;
-            cx = (x2 + x1) / 2.0; cy = (y2 + y1) / 2.0;
-            bw = x2 - x1; bh = y2 - y1;
+            const WindowBox b = window_box(bx, wx0, wy0, w_ratio, h_ratio, hi, size);
+            keep = b.keep;                                // else the centre left the window (or not a number)
+            cx = b.cx(); cy = b.cy();
+            bw = b.w(); bh = b.h();
             cls = (int)bx[4];
         }
         const unsigned long long kept = __ballot(keep);
@@ -336,44 +284,15 @@ Y2_DEV uint32_t warp_pixel(const uint8_t* base, int64_t pitch, int64_t a0, int l
     const double fx = floor(sx), fy = floor(sy);
     const int x0 = (int)fx, y0 = (int)fy;       // |c| < 2^30
     const int wx1 = (int)((sx - fx) * 2048.0 + 0.5), wy1 = (int)((sy - fy) * 2048.0 + 0.5);
-    const int wx0 = 2048 - wx1, wy0 = 2048 - wy1;
     const bool ol = x0 < 0 || x0 >= W, orr = x0 + 1 < 0 || x0 + 1 >= W;
     const bool ot = y0 < 0 || y0 >= H, ob = y0 + 1 < 0 || y0 + 1 >= H;
     const int xa = min(max(x0, lx0), lx1), xb = min(max(x0 + 1, lx0), lx1);
     const int ya = min(max(y0, ly0), ly1), yb = min(max(y0 + 1, ly0), ly1);
-    const uint8_t *r0, *r1;
-    int ca, cb;
-    if (STAGED) {
-        r0 = base + (ya - ly0) * (int)pitch;
-        r1 = base + (yb - ly0) * (int)pitch;
-        ca = 3 * xa - (int)a0;
-        cb = 3 * xb - (int)a0;
-        uint32_t packed = 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int v00 = (ol || ot) ? fill : (int)r0[ca + c], v01 = (orr || ot) ? fill : (int)r0[cb + c];
-            const int v10 = (ol || ob) ? fill : (int)r1[ca + c], v11 = (orr || ob) ? fill : (int)r1[cb + c];
-            const int top = v00 * wx0 + v01 * wx1;
-            const int bot = v10 * wx0 + v11 * wx1;
-            const int val = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;   // <= 255 * 2^22 + 2^21 < 2^31
-            packed |= (uint32_t)(val & 255) << (8 * c);
-        }
-        return packed;
-    }
-    r0 = base + (size_t)ya * pitch;
-    r1 = base + (size_t)yb * pitch;
-    const size_t ga = 3 * (size_t)xa, gb = 3 * (size_t)xb;
-    uint32_t packed = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int v00 = (ol || ot) ? fill : (int)r0[ga + c], v01 = (orr || ot) ? fill : (int)r0[gb + c];
-        const int v10 = (ol || ob) ? fill : (int)r1[ga + c], v11 = (orr || ob) ? fill : (int)r1[gb + c];
-        const int top = v00 * wx0 + v01 * wx1;
-        const int bot = v10 * wx0 + v11 * wx1;
-        const int val = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;
-        packed |= (uint32_t)(val & 255) << (8 * c);
-    }
-    return packed;
+    if (STAGED)                                 // its own row pointers and 32-bit offsets: LDS read with LDS instructions
+        return tap_pixel(base + (ya - ly0) * (int)pitch, base + (yb - ly0) * (int)pitch, 3 * xa - (int)a0,
+                         3 * xb - (int)a0, ol, orr, ot, ob, wx1, wy1, fill);
+    return tap_pixel(base + (size_t)ya * pitch, base + (size_t)yb * pitch, 3 * (size_t)xa, 3 * (size_t)xb, ol, orr, ot,
+                     ob, wx1, wy1, fill);
 }
 
 // the lane's 4 pixels (u .. u + 3, v) of one tile: gather, colour, three dwords
@@ -388,9 +307,7 @@ Y2_DEV void warp_produce(const uint8_t* base, int64_t pitch, int64_t a0, int lx0
 #pragma unroll
         for (int e = 0; e < 4; ++e) pix[e] = distort_pixel(pix[e], unit, hue6, sat, exp);
     }
-    o32[0] = pix[0] | pix[1] << 24;
-    o32[1] = pix[1] >> 8 | pix[2] << 16;
-    o32[2] = pix[2] >> 16 | pix[3] << 8;
+    store_px4(o32, pix);
 }
 
 // grid (tiles of kWarpTile x kWarpTile output pixels, n), 256 lanes; lane l produces the 4 pixels 4 (l % 8) .. + 3 of tile
@@ -463,14 +380,13 @@ __global__ __launch_bounds__(kThreads) void warp_u8_kernel(const uint8_t* __rest
             if (!active) return;
             uint32_t p = 0x010101u * (uint32_t)fill;
             if (colour) p = distort_pixel(p, unit, hue6, sat, exp);
-            o32[0] = p | p << 24;
-            o32[1] = p >> 8 | p << 16;
-            o32[2] = p >> 16 | p << 8;
+            const uint32_t pix[4] = {p, p, p, p};
+            store_px4(o32, pix);
             return;
         }
         const int64_t a0 = (3 * (int64_t)bx0) & ~(int64_t)15, a1 = (3 * (int64_t)bx1 + 3 + 15) & ~(int64_t)15;
         const int64_t seg = a1 - a0, nrow = (int64_t)by1 - by0 + 1;
-        if (((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W && seg * nrow <= kWarpLds) {
+        if (stageable(off, pitch64, W) && seg * nrow <= kWarpLds) {
             const int chunks = (int)(seg >> 4), total = chunks * (int)nrow;
             for (int i = tid; i < total; i += kThreads) {
                 const int r = i / chunks, c = i - r * chunks;
@@ -512,9 +428,7 @@ int y2_warp_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* i
     else
         hipLaunchKernelGGL(warp_u8_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, params,
                            labels, out_h, out_w, fill, out, labels_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_warp_u8_batch: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_warp_u8_batch");
 }
 
 int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
@@ -528,9 +442,7 @@ int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t
         return fail(Y2_ERR_ARG, "y2_encode_box_list: max_boxes = %d outside 1..%d", max_boxes, Y2_MAX_BOXES);
     hipLaunchKernelGGL(encode_box_list_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, boxes, counts, table, index,
                        params, max_obj, image_size, max_boxes, truth, ntruth);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_encode_box_list: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_encode_box_list");
 }
 
 int y2_augment_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, const double* params, int n,
@@ -548,9 +460,7 @@ int y2_augment_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t
     else
         hipLaunchKernelGGL(augment_u8_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, params,
                            out_h, out_w, fill, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_augment_u8_batch: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_augment_u8_batch");
 }
 
 int y2_encode_labels_window(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
@@ -564,9 +474,7 @@ int y2_encode_labels_window(const double* boxes, const int32_t* counts, const in
                     image_size, S, num_class);
     hipLaunchKernelGGL(encode_labels_window_kernel, dim3(n), dim3(kThreads), 0, (hipStream_t)stream, boxes, counts,
                        table, index, params, max_obj, image_size, S, num_class, labels);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_encode_labels_window: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_encode_labels_window");
 }
 
 }  // extern "C"

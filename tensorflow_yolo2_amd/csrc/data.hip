@@ -4,6 +4,9 @@
 // oracle/data_ref.py), and both kernels are bit-equal to it: the coefficients are computed in double in the
 // specification's operation order, and the file is compiled with -ffp-contract=off (a fused multiply-add in
 // (i + 0.5) * scale - 0.5 or in frac * 2048 can move a rounding tie).
+// Here: the band loops of the plain resize and of the letterbox and what only they need (resize_bytes, fill_dwords,
+// canvas_dword).  The coefficient and x-table arithmetic, the blend, the staging of source rows and the body of the label
+// kernel are data_common.h's, shared with augment.hip.
 #include "data_common.h"
 #include "letterbox.h"
 using namespace y2;
@@ -13,17 +16,14 @@ namespace {
 // VEC consecutive output bytes starting at byte b of an output row: r0 / r1 are the two source rows (LDS or global)
 template <int VEC>
 Y2_DEV uint32_t resize_bytes(const uint8_t* r0, const uint8_t* r1, const XCoef* xt, int b, int wy1) {
-    const int wy0 = 2048 - wy1;
     int x = b / 3, c = b - 3 * x;
     uint32_t packed = 0;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
         const XCoef q = xt[x];
         const int a0 = q.x0 + c, a1 = a0 + q.dx;
-        const int wx1 = q.w1, wx0 = 2048 - wx1;
-        const int top = (int)r0[a0] * wx0 + (int)r0[a1] * wx1;
-        const int bot = (int)r1[a0] * wx0 + (int)r1[a1] * wx1;
-        const int v = (top * wy0 + bot * wy1 + (1 << 21)) >> 22;   // <= 255 * 2^22 + 2^21 < 2^31
+        const int wx1 = q.w1;                   // read before the taps, not after them as an argument would be: measured,
+        const int v = blend4(r0[a0], r0[a1], r1[a0], r1[a1], wx1, wy1);   // 1 % of the kernel at 320 and 416
         packed |= (uint32_t)(v & 255) << (8 * e);
         if (++c == 3) { c = 0; ++x; }
     }
@@ -47,14 +47,10 @@ __global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t* __re
     const int H = (int)t[1], W = (int)t[2], flip = (int)t[4];
     const int band0 = blockIdx.x * kBand, nrows = min(kBand, out_h - band0);
     if (H < 1 || W < 1) return;                 // (an empty table row: nothing to read)
-    for (int x = tid; x < out_w; x += kThreads) {
-        int x0, x1, w1;
-        lin_coef(flip ? out_w - 1 - x : x, W, out_w, x0, x1, w1);
-        xt[x] = XCoef{3 * x0, (short)(3 * (x1 - x0)), (short)w1};
-    }
+    build_xtable(xt, W, out_w, flip, tid);
     if (tid < nrows) lin_coef(band0 + tid, H, out_h, yc[tid][0], yc[tid][1], yc[tid][2]);
     __syncthreads();
-    const bool staged = pitch64 <= kMaxPitch && ((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W;
+    const bool staged = pitch64 <= kMaxPitch && stageable(off, pitch64, W);
     const int pitch = (int)pitch64;
     const uint8_t* src = pool + off;
     const int rowbytes = 3 * out_w;
@@ -62,12 +58,7 @@ __global__ __launch_bounds__(kThreads) void resize_u8_kernel(const uint8_t* __re
     for (int g0 = 0; g0 < nrows; g0 += kRows) {
         const int gr = min(kRows, nrows - g0);
         if (staged) {
-            const int chunks = pitch >> 4;
-            for (int i = tid; i < 2 * gr * chunks; i += kThreads) {
-                const int slot = i / chunks, c = i - slot * chunks;
-                const int y = yc[g0 + (slot >> 1)][slot & 1];
-                *(u32x4*)(rows + slot * pitch + 16 * c) = *(const u32x4*)(src + (size_t)y * pitch64 + 16 * c);
-            }
+            stage_rows(rows, src, pitch64, yc + g0, gr, tid);
             __syncthreads();
         }
         const int total = gr * rowbytes;
@@ -146,26 +137,17 @@ __global__ __launch_bounds__(kThreads) void letterbox_u8_kernel(const uint8_t* _
     fill_dwords(obase, p0 * (rowbytes >> 2), fill4, tid);
     fill_dwords(obase + (size_t)p1 * rowbytes, (nrows - p1) * (rowbytes >> 2), fill4, tid);
     if (p0 >= p1) return;                       // uniform: a pure fill
-    for (int x = tid; x < g.new_w; x += kThreads) {
-        int x0, x1, w1;
-        lin_coef(x, W, g.new_w, x0, x1, w1);
-        xt[x] = XCoef{3 * x0, (short)(3 * (x1 - x0)), (short)w1};
-    }
+    build_xtable(xt, W, g.new_w, 0, tid);
     if (tid >= p0 && tid < p1) lin_coef(band0 + tid - g.oy, H, g.new_h, yc[tid][0], yc[tid][1], yc[tid][2]);
     __syncthreads();
-    const bool staged = pitch64 <= kMaxPitch && ((off | pitch64) & 15) == 0 && pitch64 >= 3 * (int64_t)W;
+    const bool staged = pitch64 <= kMaxPitch && stageable(off, pitch64, W);
     const int pitch = (int)pitch64;
     const uint8_t* src = pool + off;
     const int lo = 3 * g.ox, hi = lo + 3 * g.new_w;         // the picture's bytes of a canvas row: [lo, hi)
     for (int g0 = p0; g0 < p1; g0 += kRows) {
         const int gr = min(kRows, p1 - g0);
         if (staged) {
-            const int chunks = pitch >> 4;
-            for (int i = tid; i < 2 * gr * chunks; i += kThreads) {
-                const int slot = i / chunks, c = i - slot * chunks;
-                const int y = yc[g0 + (slot >> 1)][slot & 1];
-                *(u32x4*)(rows + slot * pitch + 16 * c) = *(const u32x4*)(src + (size_t)y * pitch64 + 16 * c);
-            }
+            stage_rows(rows, src, pitch64, yc + g0, gr, tid);
             __syncthreads();
         }
         const int total = gr * rowbytes;
@@ -181,49 +163,14 @@ __global__ __launch_bounds__(kThreads) void letterbox_u8_kernel(const uint8_t* _
     }
 }
 
-// grid (n).  The workgroup zero-fills the image's grid; then ONE lane walks the image's objects in annotation order
-// (the first object of a cell wins, which is sequential).  double arithmetic in the specification's order, one cast
-// to float at each store.  A flipped image writes the mirrored column and image_size - 1 - x directly: the mirror is
-// a bijection of the cells, so "first wins" picks the same objects as flipping the finished grid.
+// pascal_voc.encode_boxes: the label grid of the plain path (data_common.h: encode_labels without a window)
 __global__ __launch_bounds__(kThreads) void encode_labels_kernel(const double* __restrict__ boxes,
                                                                  const int32_t* __restrict__ counts,
                                                                  const int64_t* __restrict__ table,
                                                                  const int32_t* __restrict__ index, int max_obj,
                                                                  int image_size, int S, int num_class,
                                                                  float* __restrict__ labels) {
-    const int img = blockIdx.x, D = 5 + num_class;
-    const size_t e = index ? (size_t)index[img] : (size_t)img;
-    float* g = labels + (size_t)img * S * S * D;
-    for (int i = threadIdx.x; i < S * S * D; i += kThreads) g[i] = 0.0f;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const int64_t* t = table + kTable * e;
-    const int im_h = (int)t[1], im_w = (int)t[2], flip = (int)t[4];
-    const double h_ratio = 1.0 * image_size / im_h, w_ratio = 1.0 * image_size / im_w;
-    const double hi = (double)(image_size - 1);
-    const int cnt = min(max(counts[e], 0), max_obj);
-    const double* bx = boxes + e * (size_t)max_obj * 5;
-    for (int o = 0; o < cnt; ++o, bx += 5) {
-        double x1 = (bx[0] - 1) * w_ratio, y1 = (bx[1] - 1) * h_ratio;
-        double x2 = (bx[2] - 1) * w_ratio, y2 = (bx[3] - 1) * h_ratio;
-        x1 = hi < x1 ? hi : x1; x1 = 0.0 > x1 ? 0.0 : x1;
-        y1 = hi < y1 ? hi : y1; y1 = 0.0 > y1 ? 0.0 : y1;
-        x2 = hi < x2 ? hi : x2; x2 = 0.0 > x2 ? 0.0 : x2;
-        y2 = hi < y2 ? hi : y2; y2 = 0.0 > y2 ? 0.0 : y2;
-        const double cx = (x2 + x1) / 2.0, cy = (y2 + y1) / 2.0;
-        int x_ind = (int)(cx * S / image_size), y_ind = (int)(cy * S / image_size);
-        if (!(x_ind >= 0 && x_ind < S && y_ind >= 0 && y_ind < S)) continue;   // (not a number in the box table)
-        if (flip) x_ind = S - 1 - x_ind;
-        float* cell = g + ((size_t)y_ind * S + x_ind) * D;
-        if (cell[0] == 1.0f) continue;
-        cell[0] = 1.0f;
-        cell[1] = (float)(flip ? hi - cx : cx);
-        cell[2] = (float)cy;
-        cell[3] = (float)(x2 - x1);
-        cell[4] = (float)(y2 - y1);
-        const int cls = (int)bx[4];
-        if (cls >= 0 && cls < num_class) cell[5 + cls] = 1.0f;
-    }
+    encode_labels<false>(boxes, counts, table, index, nullptr, max_obj, image_size, S, num_class, labels);
 }
 
 }  // namespace
@@ -244,9 +191,7 @@ int y2_resize_bilinear_u8_batch(const uint8_t* pool, const int64_t* table, const
     else
         hipLaunchKernelGGL(resize_u8_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, pool, table, index, out_h,
                            out_w, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_resize_bilinear_u8_batch: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_resize_bilinear_u8_batch");
 }
 
 int y2_letterbox_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, int n, int size, int fill,
@@ -260,9 +205,7 @@ int y2_letterbox_u8_batch(const uint8_t* pool, const int64_t* table, const int32
     if ((uintptr_t)out & 3) return fail(Y2_ERR_ARG, "y2_letterbox_u8_batch: out is not 4-byte aligned");
     hipLaunchKernelGGL(letterbox_u8_kernel, dim3((size + kBand - 1) / kBand, n), dim3(kThreads), 0, (hipStream_t)stream,
                        pool, table, index, size, fill, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_letterbox_u8_batch: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_letterbox_u8_batch");
 }
 
 int y2_letterbox_geometry(int im_h, int im_w, int size, int* geometry) {
@@ -283,9 +226,7 @@ int y2_encode_labels(const double* boxes, const int32_t* counts, const int64_t* 
                     image_size, S, num_class);
     hipLaunchKernelGGL(encode_labels_kernel, dim3(n), dim3(kThreads), 0, (hipStream_t)stream, boxes, counts, table,
                        index, max_obj, image_size, S, num_class, labels);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_encode_labels: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_encode_labels");
 }
 
 }  // extern "C"

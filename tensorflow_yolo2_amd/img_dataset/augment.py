@@ -136,14 +136,13 @@ def distort_hsv_u8(bgr_u8, hue, sat, exp):
     return np.clip((out * _f32(255) + _f32(0.5)).astype(np.int32), 0, 255).astype(np.uint8)
 
 
-def encode_boxes_window(objs, row, image_size, cell_size, num_class=20, flip=False):
-    """pascal_voc.encode_boxes with the boxes following the row's window: x = (bx - 1 - x0) * (image_size / cw), y
-    likewise, in double.  An object whose unclamped centre lies outside [0, image_size) in x or y is dropped; the others
-    are clamped, placed and mirrored as encode_boxes / flip_label do."""
+def _window_boxes(objs, row, image_size):
+    """the window arithmetic of both label formats, in double: per object of `objs` whose unclamped centre lies inside
+    [0, image_size) in x and y -- the others are dropped -- the clamped box as (cx, cy, w, h, class index), in annotation
+    order.  x = (bx - 1 - x0) * (image_size / cw), y likewise."""
     x0, y0, cw, ch = (float(int(row[k])) for k in (X0, Y0, CW, CH))     # integers, as cut_window reads them
     w_ratio = image_size / cw
     h_ratio = image_size / ch
-    label = np.zeros((cell_size, cell_size, 5 + num_class))
     for (xmin, ymin, xmax, ymax, cls_ind) in objs:
         x1, y1 = (float(xmin) - 1 - x0) * w_ratio, (float(ymin) - 1 - y0) * h_ratio
         x2, y2 = (float(xmax) - 1 - x0) * w_ratio, (float(ymax) - 1 - y0) * h_ratio
@@ -152,14 +151,22 @@ def encode_boxes_window(objs, row, image_size, cell_size, num_class=20, flip=Fal
             continue
         x1, y1 = max(min(x1, image_size - 1), 0), max(min(y1, image_size - 1), 0)
         x2, y2 = max(min(x2, image_size - 1), 0), max(min(y2, image_size - 1), 0)
-        boxes = [(x2 + x1) / 2.0, (y2 + y1) / 2.0, x2 - x1, y2 - y1]
-        x_ind = int(boxes[0] * cell_size / image_size)
-        y_ind = int(boxes[1] * cell_size / image_size)
+        yield (x2 + x1) / 2.0, (y2 + y1) / 2.0, x2 - x1, y2 - y1, int(cls_ind)
+
+
+def encode_boxes_window(objs, row, image_size, cell_size, num_class=20, flip=False):
+    """pascal_voc.encode_boxes with the boxes following the row's window: x = (bx - 1 - x0) * (image_size / cw), y
+    likewise, in double.  An object whose unclamped centre lies outside [0, image_size) in x or y is dropped; the others
+    are clamped, placed and mirrored as encode_boxes / flip_label do."""
+    label = np.zeros((cell_size, cell_size, 5 + num_class))
+    for (cx, cy, w, h, cls_ind) in _window_boxes(objs, row, image_size):
+        x_ind = int(cx * cell_size / image_size)
+        y_ind = int(cy * cell_size / image_size)
         if label[y_ind, x_ind, 0] == 1:
             continue
         label[y_ind, x_ind, 0] = 1
-        label[y_ind, x_ind, 1:5] = boxes
-        label[y_ind, x_ind, 5 + int(cls_ind)] = 1
+        label[y_ind, x_ind, 1:5] = (cx, cy, w, h)
+        label[y_ind, x_ind, 5 + cls_ind] = 1
     return flip_label(label, image_size) if bool(flip) != bool(row[FLIP]) else label
 
 
@@ -176,23 +183,12 @@ def encode_box_list(objs, row, image_size, max_boxes=MAX_BOXES, flip=False):
     (x - 1 - 0) * (size / W) is encode_boxes' (x - 1) * w_ratio."""
     if not 1 <= int(max_boxes) <= 1024:
         raise ValueError("max_boxes %r outside 1..1024" % (max_boxes,))
-    x0, y0, cw, ch = (float(int(row[k])) for k in (X0, Y0, CW, CH))
-    w_ratio = image_size / cw
-    h_ratio = image_size / ch
     mirror = bool(flip) != bool(row[FLIP])
     truth = np.zeros((int(max_boxes), 5), np.float32)
     count = 0
-    for (xmin, ymin, xmax, ymax, cls_ind) in objs:
+    for (cx, cy, w, h, cls_ind) in _window_boxes(objs, row, image_size):
         if count == max_boxes:
             break
-        x1, y1 = (float(xmin) - 1 - x0) * w_ratio, (float(ymin) - 1 - y0) * h_ratio
-        x2, y2 = (float(xmax) - 1 - x0) * w_ratio, (float(ymax) - 1 - y0) * h_ratio
-        cx, cy = (x2 + x1) / 2.0, (y2 + y1) / 2.0
-        if not (0 <= cx < image_size and 0 <= cy < image_size):
-            continue
-        x1, y1 = max(min(x1, image_size - 1), 0), max(min(y1, image_size - 1), 0)
-        x2, y2 = max(min(x2, image_size - 1), 0), max(min(y2, image_size - 1), 0)
-        cx, cy = (x2 + x1) / 2.0, (y2 + y1) / 2.0
-        truth[count] = (image_size - 1 - cx if mirror else cx, cy, x2 - x1, y2 - y1, int(cls_ind))
+        truth[count] = (image_size - 1 - cx if mirror else cx, cy, w, h, cls_ind)
         count += 1
     return truth, count

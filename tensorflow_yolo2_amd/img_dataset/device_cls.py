@@ -1,6 +1,6 @@
 """Device-resident classifier batches: the decoded images of an image list [(path, label)] live ONCE in the uint8 pool of
-device_voc.py (same layout, same entry table), the labels in an int32 [entries] device tensor, and every training batch
--- at any size -- is ONE launch of y2_warp_u8_batch (csrc/augment.hip): mirror, rotation, scale, crop, colour and the
+DevicePool (device_pool.py: layout, plain entry table, construction, per-call plumbing), the labels in an int32 [entries]
+device tensor, and every training batch -- at any size -- is ONE launch of y2_warp_u8_batch (csrc/augment.hip): mirror, rotation, scale, crop, colour and the
 labels of the slots.  After start-up the host touches no pixel; per batch it draws the parameter rows
 (augment_cls.ClsAugment.draw_batch: one block of uniforms, vector arithmetic) and uploads them with the index.
 
@@ -9,21 +9,21 @@ arrays: both walk pascal_voc.ShardedOrder and the kernel is bit-equal to augment
 forms the plain stretch of every entry itself (params = NULL: augment_cls.identity_row).
 
 eval_batch(size, start) is the plain stretch of the reference's non-augmented image_read in LIST order
-(y2_resize_bilinear_u8_batch through device_voc.list_batch, as DeviceImages.batch(..., letterbox=False)); labels_of(start)
+(y2_resize_bilinear_u8_batch through DevicePool.list_batch, as DeviceImages.batch(..., letterbox=False)); labels_of(start)
 returns the labels of the same slots.  eval_views(size, start, views) is the same walk with V evaluation views per entry
 (img_dataset/eval_views.py: stretch, centre crop, ten crops) from one launch of y2_warp_u8_batch."""
-import ctypes as C
 import os
 import zlib
 
 import numpy as np
 
 from .cls_images import check_items, stored_image
-from .device_voc import DEFAULT_MAX_POOL_BYTES, DeviceVOC, list_batch, padded_rows, pool_layout, _ptr
+from .device_pool import (DEFAULT_MAX_POOL_BYTES, DevicePool, _ptr, check_size, list_index, need_gpu, stream_of,
+                          upload_async)
 from .pascal_voc import ShardedOrder, imread_bgr
 
 
-class DeviceCls(ShardedOrder):
+class DeviceCls(DevicePool, ShardedOrder):
     def __init__(self, items, batch_size, seed=0, rank=0, world=1, device="cuda",
                  max_pool_bytes=DEFAULT_MAX_POOL_BYTES, augment=None, pool_short_side=None):
         self.items = check_items(items, batch_size, pool_short_side)
@@ -43,31 +43,14 @@ class DeviceCls(ShardedOrder):
             shapes.append(stored_shape(h, w, pool_short_side))
         self.entries = [{'imname': p, 'shape': s} for (p, _), s in zip(self.items, shapes)]
         self.shapes = np.array(shapes, np.int64)
-        self.offsets, self.pitches, self.pool_bytes = pool_layout(shapes)
-        if self.pool_bytes > max_pool_bytes:
-            raise MemoryError("the decoded image pool needs %d bytes (%d images), max_pool_bytes is %d"
-                              % (self.pool_bytes, len(self.entries), max_pool_bytes))
-        table = np.array([(off, s[0], s[1], pitch, 0) for s, off, pitch in zip(shapes, self.offsets, self.pitches)],
-                         np.int64)
-        self.pool = self._alloc_pool(self.pool_bytes)
-        for e, off, pitch in zip(self.entries, self.offsets, self.pitches):
-            img = stored_image(imread_bgr(e['imname']), pool_short_side)   # decoded ONCE; no host copy is kept
-            assert img.shape == (e['shape'][0], e['shape'][1], 3), (e['imname'], img.shape, e['shape'])
-            self._put(self.pool, off, padded_rows(img, pitch).reshape(-1))
-        self.table = self._upload(table)
+        # decoded ONCE; no host copy is kept
+        self._build_pool(lambda k: stored_image(imread_bgr(self.entries[k]['imname']), pool_short_side), max_pool_bytes)
         self.labels_host = np.array([l for _, l in self.items], np.int32)
         self.labels = self._upload(self.labels_host)
         self.gt_labels = self._start_order([{'imname': p, 'entry': k} for k, (p, _) in enumerate(self.items)])
         self._check_ranks_agree()
         self._buffers = {}
-        self._eval_buffers = {}
         self._view_buffers = {}
-
-    # ---- the only places that touch device memory at start-up, as in DeviceVOC
-    _alloc_pool = DeviceVOC._alloc_pool
-    _put = DeviceVOC._put
-    _upload = DeviceVOC._upload
-    _check_ranks_agree = DeviceVOC._check_ranks_agree
 
     def order_digest(self):
         """(number of entries, CRC-32 of the current order and its labels): equal on ranks that hold the same list"""
@@ -78,8 +61,7 @@ class DeviceCls(ShardedOrder):
         """the (images, labels, index, params) tensors get(size) writes: kept per size, overwritten by the next call"""
         import torch
         from .augment_cls import ROW
-        if size < 32 or size % 32:
-            raise ValueError("size %r is not a positive multiple of 32" % (size,))
+        check_size(size)
         if size not in self._buffers:
             self._buffers[size] = (
                 torch.empty((self.batch_size, size, size, 3), dtype=torch.uint8, device=self.device),
@@ -91,22 +73,19 @@ class DeviceCls(ShardedOrder):
     def get(self, size):
         """(images [B, size, size, 3] uint8 BGR, labels [B] int32), device tensors written on the current stream by one
         launch; asynchronous: one index upload and, with `augment`, one parameter upload from pinned memory"""
-        import torch
         from .. import _lib
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("DeviceCls.get needs the pool on the GPU (device=%r)" % (self.device,))
+        need_gpu(self.device, "DeviceCls.get")
         images, labels, index, params = self.buffers(size)
         entries = np.array([self._next()['entry'] for _ in range(self.batch_size)], np.int32)
-        index.copy_(torch.from_numpy(entries).pin_memory(), non_blocking=True)
+        upload_async(index, entries)
         fill = 127
         if self.augment is not None:
-            rows = self.augment.draw_batch(self.aug_rng, self.shapes[entries], size)
-            params.copy_(torch.from_numpy(rows).pin_memory(), non_blocking=True)
+            upload_async(params, self.augment.draw_batch(self.aug_rng, self.shapes[entries], size))
             fill = self.augment.fill
-        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
         _lib.check(_lib.load().y2_warp_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index),
                                                 _ptr(params) if self.augment is not None else None, _ptr(self.labels),
-                                                self.batch_size, size, size, fill, _ptr(images), _ptr(labels), stream))
+                                                self.batch_size, size, size, fill, _ptr(images), _ptr(labels),
+                                                stream_of(images)))
         return images, labels
 
     def skip_batches(self, k):
@@ -122,7 +101,7 @@ class DeviceCls(ShardedOrder):
         holds the slots' entries, the cursor of get() is neither read nor moved)"""
         if self.augment is not None:
             raise ValueError("evaluation reads the plain image list: build the DeviceCls with augment=None")
-        return list_batch(self, "DeviceCls.eval_batch", size, start, False, 127)
+        return self.list_batch("DeviceCls.eval_batch", size, start, False, 127)
 
     def eval_views(self, size, start, views="centre", margin=32, fill=127):
         """(images [B * V, size, size, 3] uint8 BGR, valid): slot b * V + v is view v (eval_views.view_rows) of entry
@@ -136,14 +115,11 @@ class DeviceCls(ShardedOrder):
         from .eval_views import VIEWS, view_rows
         if self.augment is not None:
             raise ValueError("evaluation reads the plain image list: build the DeviceCls with augment=None")
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("DeviceCls.eval_views needs the pool on the GPU (device=%r)" % (self.device,))
+        need_gpu(self.device, "DeviceCls.eval_views")
         if not (0 <= fill <= 255 and int(fill) == fill):
             raise ValueError("fill %r is not an integer of 0..255" % (fill,))
         n = len(self.entries)
-        if not 0 <= start < n:
-            raise IndexError("start = %r outside the %d entries" % (start, n))
-        entries = np.minimum(np.arange(start, start + self.batch_size), n - 1)
+        entries = list_index(start, self.batch_size, n)
         rows = view_rows(self.shapes[entries], size, views, margin)         # (raises for the other arguments)
         V = VIEWS[views]
         slots = self.batch_size * V
@@ -153,18 +129,14 @@ class DeviceCls(ShardedOrder):
                 torch.empty(slots, dtype=torch.int32, device=self.device),
                 torch.empty((slots, ROW), dtype=torch.float64, device=self.device))
         images, index, params = self._view_buffers[(size, views)]
-        index.copy_(torch.from_numpy(np.repeat(entries, V).astype(np.int32)).pin_memory(), non_blocking=True)
-        params.copy_(torch.from_numpy(rows.reshape(slots, ROW)).pin_memory(), non_blocking=True)
-        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
+        upload_async(index, np.repeat(entries, V).astype(np.int32))
+        upload_async(params, rows.reshape(slots, ROW))
         _lib.check(_lib.load().y2_warp_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index), _ptr(params), None, slots,
-                                                size, size, int(fill), _ptr(images), None, stream))
+                                                size, size, int(fill), _ptr(images), None, stream_of(images)))
         return images, min(self.batch_size, n - start)
 
     def labels_of(self, start):
         """int32 [B] device tensor: the labels of the slots of eval_batch(size, start)"""
         import torch
-        n = len(self.entries)
-        if not 0 <= start < n:
-            raise IndexError("start = %r outside the %d entries" % (start, n))
-        idx = np.minimum(np.arange(start, start + self.batch_size), n - 1)
+        idx = list_index(start, self.batch_size, len(self.entries))
         return torch.from_numpy(self.labels_host[idx]).to(self.device)

@@ -13,48 +13,31 @@ the augmentation generator -- crop / pad window, mirror, hue / saturation / expo
 y2_augment_u8_batch and y2_encode_labels_window (csrc/augment.hip), bit-equal to augment.py; the batch order does not
 change, and the k-th get(size) still equals the k-th get_u8() of a host batcher built with the same arguments.
 
-Pool layout: image k starts at byte offset off[k] (a multiple of 16), rows pitch[k] = 3 * width rounded up to 16 bytes
-apart, BGR uint8; the bytes between 3 * width and the pitch are zero.  Entry table: int64 [entries][5] = {off, height,
-width, pitch, flip}; with `flipped` the entries are the images followed by their mirrored copies (same offset, flip = 1),
-the order of pascal_voc.prepare.  Box table: float64 [entries][max_obj][5] = xmin, ymin, xmax, ymax, class index in
-annotation order, and int32 counts [entries].
+The pool, its construction, the list-order batch and the per-call plumbing are DevicePool's (device_pool.py: layout and
+entry table there; pool_layout, padded_rows, ALIGN and DEFAULT_MAX_POOL_BYTES are re-exported here).  What is DeviceVOC's
+own: with `flipped` the entries of the table are the images followed by their mirrored copies (same offset, flip = 1),
+the order of pascal_voc.prepare (build_tables, through _entry_table).  Box table: float64 [entries][max_obj][5] = xmin,
+ymin, xmax, ymax, class index in annotation order, and int32 counts [entries].
 
 Evaluation (pascal/pascal_eval_darknet.py) reads the same pool: eval_batch(size, start) resizes the entries start,
 start + 1, ... in LIST order with y2_resize_bilinear_u8_batch alone and leaves the shuffled cursor of get() where it is;
 `difficult`, uint8 [entries][max_obj] parallel to the box table, goes to the device at its first use (training never
 reads it).  Evaluation wants the plain list: a data set with `flipped` or `augment` refuses.  eval_batch(size, start,
-letterbox=True) keeps every image's aspect ratio instead (y2_letterbox_u8_batch: csrc/data.hip); img_dataset/
-device_images.py is the same pool and entry table built from plain image files, without annotations.
+letterbox=True) keeps every image's aspect ratio instead (y2_letterbox_u8_batch: csrc/data.hip).  Both are
+DevicePool.list_batch; img_dataset/device_images.py is the same pool built from plain image files, without annotations.
 
 With `max_boxes` = T, get(size) returns (images, labels, truth, ntruth): the box list of the anchor model next to the
 label grid -- truth float32 [B][T][5] = cx, cy, w, h in pixels of the input and the class index of EVERY object of the
 window in annotation order, ntruth int32 [B] (augment.encode_box_list; y2_encode_box_list, csrc/augment.hip).  One more
 launch on the same stream and no further upload: the kernel reads the index and parameter tensors of the other two."""
-import ctypes as C
 import os
 import zlib
 
 import numpy as np
 
+from .device_pool import (ALIGN, DEFAULT_MAX_POOL_BYTES, DevicePool, _ptr, check_size, need_gpu, padded_rows,  # noqa: F401
+                          pool_layout, stream_of, upload_async)
 from .pascal_voc import CLASSES, ShardedOrder, imread_bgr, read_image_set
-
-ALIGN = 16
-DEFAULT_MAX_POOL_BYTES = 16 << 30
-
-
-def _round_up(v, a):
-    return (int(v) + a - 1) // a * a
-
-
-def pool_layout(shapes):
-    """(offsets, pitches, total bytes) of images of the given (height, width) shapes, 16-byte aligned"""
-    offsets, pitches, total = [], [], 0
-    for (h, w) in shapes:
-        pitch = _round_up(3 * w, ALIGN)
-        offsets.append(total)
-        pitches.append(pitch)
-        total += _round_up(h * pitch, ALIGN)
-    return offsets, pitches, total
 
 
 def build_tables(entries, offsets, pitches, flipped):
@@ -87,52 +70,10 @@ def build_difficult(entries, max_obj, flipped):
     return out
 
 
-def padded_rows(img, pitch):
-    """[H, W, 3] uint8 -> [H, pitch] uint8, zero bytes after 3 * W"""
-    h, w = img.shape[:2]
-    out = np.zeros((h, pitch), np.uint8)
-    out[:, :3 * w] = img.reshape(h, 3 * w)
-    return out
+list_batch = DevicePool.list_batch          # callable as list_batch(ds, who, size, start, letterbox, fill)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def list_batch(ds, who, size, start, letterbox, fill):
-    """the body of DeviceVOC.eval_batch and DeviceImages.batch: `ds` holds pool, table, entries, batch_size, device and
-    the per-size buffers; sets ds.eval_index"""
-    import torch
-    from .. import _lib
-    if torch.device(ds.device).type != "cuda":
-        raise RuntimeError("%s needs the pool on the GPU (device=%r)" % (who, ds.device))
-    if size < 32 or size % 32:
-        raise ValueError("size %r is not a positive multiple of 32" % (size,))
-    if letterbox and not 0 <= int(fill) <= 255:
-        raise ValueError("fill %r outside 0..255" % (fill,))
-    n = len(ds.entries)
-    if not 0 <= start < n:
-        raise IndexError("start = %r outside the %d entries" % (start, n))
-    if size not in ds._eval_buffers:
-        ds._eval_buffers[size] = (
-            torch.empty((ds.batch_size, size, size, 3), dtype=torch.uint8, device=ds.device),
-            torch.empty(ds.batch_size, dtype=torch.int32, device=ds.device))
-    images, index = ds._eval_buffers[size]
-    valid = min(ds.batch_size, n - start)
-    host = torch.from_numpy(np.minimum(np.arange(start, start + ds.batch_size), n - 1).astype(np.int32))
-    index.copy_(host.pin_memory(), non_blocking=True)
-    stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
-    if letterbox:
-        _lib.check(_lib.load().y2_letterbox_u8_batch(_ptr(ds.pool), _ptr(ds.table), _ptr(index), ds.batch_size, size,
-                                                     int(fill), _ptr(images), stream))
-    else:
-        _lib.check(_lib.load().y2_resize_bilinear_u8_batch(_ptr(ds.pool), _ptr(ds.table), _ptr(index), ds.batch_size,
-                                                           size, size, _ptr(images), stream))
-    ds.eval_index = index
-    return images, valid
-
-
-class DeviceVOC(ShardedOrder):
+class DeviceVOC(DevicePool, ShardedOrder):
     def __init__(self, image_set, batch_size=None, devkit_path=None, flipped=None, seed=0, rank=0, world=1,
                  device="cuda", max_pool_bytes=DEFAULT_MAX_POOL_BYTES, augment=None, max_boxes=None):
         from .. import config as cfg
@@ -156,65 +97,33 @@ class DeviceVOC(ShardedOrder):
             self.aug_rng = generator(seed, rank)            # its own stream: the batch order is that of augment=None
         self.image_index, self.entries = read_image_set(self.data_path, image_set)
         assert self.entries, "no image with objects in %s" % image_set
-        self.offsets, self.pitches, self.pool_bytes = pool_layout([e['shape'] for e in self.entries])
-        if self.pool_bytes > max_pool_bytes:
-            raise MemoryError("the decoded image pool needs %d bytes (%d images), max_pool_bytes is %d"
-                              % (self.pool_bytes, len(self.entries), max_pool_bytes))
-        table, boxes, counts = build_tables(self.entries, self.offsets, self.pitches, self.flipped)
-        self.max_obj = boxes.shape[1]
-        self.difficult_host = build_difficult(self.entries, self.max_obj, self.flipped)
-        self._difficult = None
-        self.pool = self._alloc_pool(self.pool_bytes)
-        for e, off, pitch in zip(self.entries, self.offsets, self.pitches):
-            img = imread_bgr(e['imname'])                  # decoded ONCE; no host copy is kept
-            assert img.shape == (e['shape'][0], e['shape'][1], 3), (e['imname'], img.shape, e['shape'])
-            self._put(self.pool, off, padded_rows(img, pitch).reshape(-1))
-        self.table, self.boxes, self.counts = self._upload(table), self._upload(boxes), self._upload(counts)
+        self._build_pool(lambda k: imread_bgr(self.entries[k]['imname']), max_pool_bytes)
+        self.boxes, self.counts = self._upload(self.boxes), self._upload(self.counts)
         n = len(self.entries)
-        gt = [{'imname': self.entries[k % n]['imname'], 'flipped': k >= n, 'entry': k} for k in range(len(table))]
+        gt = [{'imname': self.entries[k % n]['imname'], 'flipped': k >= n, 'entry': k} for k in range(len(self.counts))]
         self.gt_labels = self._start_order(gt)
         self._check_ranks_agree()
         self._buffers = {}
         self._params = {}
-        self._eval_buffers = {}
         self._lists = {}
 
-    # ---- the only places that touch device memory at start-up (torch supplies allocations and copies)
-    def _alloc_pool(self, nbytes):
-        import torch
-        return torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-
-    def _put(self, pool, offset, flat_u8):
-        import torch
-        pool[offset:offset + flat_u8.size].copy_(torch.from_numpy(flat_u8))
-
-    def _upload(self, array):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(array)).to(self.device)
+    def _entry_table(self):
+        """the table with the mirrored copies; the box table and the counts ride along (host arrays until uploaded)"""
+        table, self.boxes, self.counts = build_tables(self.entries, self.offsets, self.pitches, self.flipped)
+        self.max_obj = self.boxes.shape[1]
+        self.difficult_host = build_difficult(self.entries, self.max_obj, self.flipped)
+        self._difficult = None
+        return table
 
     def order_digest(self):
         """(number of entries, CRC-32 of the current order): equal on ranks that hold the same list and seed"""
         text = "\n".join("%s %d" % (os.path.basename(g['imname']), g['flipped']) for g in self.gt_labels)
         return len(self.gt_labels), zlib.crc32(text.encode())
 
-    def _check_ranks_agree(self):
-        """stride sharding assumes ONE list on every rank: compare its length and first shuffled order"""
-        if self.world <= 1:
-            return
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() == self.world):
-            return                                          # plain constructor arguments, no process group
-        mine = self.order_digest()
-        every = [None] * self.world
-        dist.all_gather_object(every, mine)
-        if any(tuple(d) != tuple(mine) for d in every):
-            raise RuntimeError("ranks hold different image lists or orders (entries, crc32 per rank): %r" % (every,))
-
     def buffers(self, size):
         """the (images, labels) tensors get(size) writes: kept per size, overwritten by the next get(size)"""
         import torch
-        if size < 32 or size % 32:
-            raise ValueError("size %r is not a positive multiple of 32" % (size,))
+        check_size(size)
         if size not in self._buffers:
             S = size // 32
             self._buffers[size] = (
@@ -239,25 +148,38 @@ class DeviceVOC(ShardedOrder):
 
     def get(self, size):
         """(images [B, size, size, 3] uint8 BGR, labels [B, S, S, 25] float32), S = size // 32, device tensors written
-        on the current stream; asynchronous.  With max_boxes = T also truth [B, T, 5] float32 and ntruth [B] int32."""
+        on the current stream; asynchronous.  With max_boxes = T also truth [B, T, 5] float32 and ntruth [B] int32.
+        With an Augment every sample has one parameter row, drawn in batch order and uploaded as the index is."""
         import torch
         from .. import _lib
-        if torch.device(self.device).type != "cuda":
-            raise RuntimeError("DeviceVOC.get needs the pool on the GPU (device=%r)" % (self.device,))
-        if self.augment is not None:
-            return self._get_augmented(size)
+        from .augment import ROW
+        need_gpu(self.device, "DeviceVOC.get")
         images, labels, index = self.buffers(size)
-        host = torch.from_numpy(np.array([self._next()['entry'] for _ in range(self.batch_size)], np.int32))
-        index.copy_(host.pin_memory(), non_blocking=True)
-        lib = _lib.load()
-        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
-        _lib.check(lib.y2_resize_bilinear_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index), self.batch_size,
-                                                   size, size, _ptr(images), stream))
-        _lib.check(lib.y2_encode_labels(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
-                                        self.batch_size, self.max_obj, size, size // 32, self.num_class, _ptr(labels),
-                                        stream))
+        aug, params, n = self.augment, None, len(self.entries)
+        entries = np.empty(self.batch_size, np.int32)
+        rows = np.empty((self.batch_size, ROW), np.float64)
+        for k in range(self.batch_size):
+            entries[k] = self._next()['entry']
+            if aug is not None:
+                rows[k] = aug.draw(self.aug_rng, *self.entries[entries[k] % n]['shape'])
+        upload_async(index, entries)
+        if aug is not None:
+            if size not in self._params:
+                self._params[size] = torch.empty((self.batch_size, ROW), dtype=torch.float64, device=self.device)
+            params = self._params[size]
+            upload_async(params, rows)
+        lib, stream = _lib.load(), stream_of(images)
+        if aug is None:
+            image_kernel, label_kernel, window, fill = lib.y2_resize_bilinear_u8_batch, lib.y2_encode_labels, (), ()
+        else:                                               # the window kernels: parameter rows after the index, and a fill
+            image_kernel, label_kernel = lib.y2_augment_u8_batch, lib.y2_encode_labels_window
+            window, fill = (_ptr(params),), (aug.fill,)
+        entry = (_ptr(self.table), _ptr(index)) + window
+        _lib.check(image_kernel(_ptr(self.pool), *entry, self.batch_size, size, size, *fill, _ptr(images), stream))
+        _lib.check(label_kernel(_ptr(self.boxes), _ptr(self.counts), *entry, self.batch_size, self.max_obj, size,
+                                size // 32, self.num_class, _ptr(labels), stream))
         if self.max_boxes is not None:
-            return (images, labels) + self._box_list(size, index, None, stream)
+            return (images, labels) + self._box_list(size, index, params, stream)
         return images, labels
 
     @property
@@ -276,32 +198,4 @@ class DeviceVOC(ShardedOrder):
         the detect calls then take net_size=size; the same buffers, index and refusals."""
         if self.flipped or self.augment is not None:
             raise ValueError("evaluation reads the plain image list: build the DeviceVOC with flipped=False, augment=None")
-        return list_batch(self, "DeviceVOC.eval_batch", size, start, letterbox, fill)
-
-    def _get_augmented(self, size):
-        """get(size) with one parameter row per sample, drawn in batch order and uploaded as the index is"""
-        import torch
-        from .. import _lib
-        from .augment import ROW
-        images, labels, index = self.buffers(size)
-        if size not in self._params:
-            self._params[size] = torch.empty((self.batch_size, ROW), dtype=torch.float64, device=self.device)
-        params = self._params[size]
-        entries = np.empty(self.batch_size, np.int32)
-        rows = np.empty((self.batch_size, ROW), np.float64)
-        n = len(self.entries)
-        for k in range(self.batch_size):
-            entries[k] = self._next()['entry']
-            rows[k] = self.augment.draw(self.aug_rng, *self.entries[entries[k] % n]['shape'])
-        index.copy_(torch.from_numpy(entries).pin_memory(), non_blocking=True)
-        params.copy_(torch.from_numpy(rows).pin_memory(), non_blocking=True)
-        lib = _lib.load()
-        stream = C.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)
-        _lib.check(lib.y2_augment_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index), _ptr(params),
-                                           self.batch_size, size, size, self.augment.fill, _ptr(images), stream))
-        _lib.check(lib.y2_encode_labels_window(_ptr(self.boxes), _ptr(self.counts), _ptr(self.table), _ptr(index),
-                                               _ptr(params), self.batch_size, self.max_obj, size, size // 32,
-                                               self.num_class, _ptr(labels), stream))
-        if self.max_boxes is not None:
-            return (images, labels) + self._box_list(size, index, params, stream)
-        return images, labels
+        return self.list_batch("DeviceVOC.eval_batch", size, start, letterbox, fill)
