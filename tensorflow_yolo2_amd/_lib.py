@@ -77,6 +77,8 @@ SIGNATURES = {
     "y2_reorg": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "y2_passthrough_concat": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "y2_passthrough_concat_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "y2_passthrough_concat_darknet": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "y2_u8_bgr_to_f32_rgb": (_i, [_vp, _vp, _sz, _vp]),
     "y2_accumulate": (_i, [_vp, _vp, _sz, _vp]),
     "y2_add_relu": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "y2_add_relu_backward": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),

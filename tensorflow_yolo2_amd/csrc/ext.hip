@@ -713,3 +713,142 @@ int y2_yolov2_loss_boxes(const float* net, const float* truth, const int* ntruth
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Darknet's passthrough (specification: utils/darknet_reorg.py): out [N,Ho,Wo,4*C+Cc] = concat(Darknet's reorg of
+// fine [N,H,W,C], coarse [N,Ho,Wo,Cc]), H = 2 Ho, W = 2 Wo -- the order of `route layers=-1,-4`.  Darknet's reorg is a
+// scramble of each image's C*H*W values over channels and positions, not a space-to-depth, so the reorganised part is
+// an element gather; ONE launch writes both parts.  The OUTPUT side is the coalesced one: a lane owns VEC consecutive
+// output channels of one output pixel (VEC = 4: one 16-byte store; the coarse part is a 16-byte load too).  The four
+// values of a reorganised slot are four 4-byte loads: output channels 4k .. 4k+3 come from four different input
+// pixels, while the neighbouring lane (k + 1) reads 16 bytes further in the same four pixel rows -- a wave's load
+// covers whole 256-byte rows of `fine` in 16-byte steps, and the steps in between belong to lanes of the same
+// workgroup, so the rows are fetched once and re-read from the vector cache.  `fine` is a seventh of the bytes moved
+// (N*H*W*C against the 4*C + Cc written and Cc read per output pixel), which is why no LDS tile is staged for it.
+// ---------------------------------------------------------------------------
+// the input element (offset into one image of fine [H][W][C]) of output channel co < 4 C at output pixel s = jo * Wo + io
+Y2_DEV int darknet_reorg_source(int s, int co, int H, int W, int C) {
+    const int HW = H * W;
+    const int k = co >> 2;
+    const int rem = s + (HW >> 2) * (co & 3);        // q = s + Ho Wo co, unravelled over [C][H][W]: (k, rem)
+    const int j = rem / W, i = rem - j * W;
+    const int out_c = C >> 2;
+    const int off = k / out_c, c2 = k - off * out_c;
+    const int m = (2 * i + (off & 1)) + 2 * W * (2 * j + (off >> 1));      // p = m + 4 H W c2, m < 4 H W
+    const int t = m / HW, mm = m - t * HW;
+    const int js = mm / W, is = mm - js * W;
+    return (js * W + is) * C + 4 * c2 + t;
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void passthrough_concat_darknet_kernel(const float* __restrict__ fine,
+                                                                         const float* __restrict__ coarse,
+                                                                         float* __restrict__ out, int N, int Ho, int Wo,
+                                                                         int C, int Cc) {
+    const int H = 2 * Ho, W = 2 * Wo, ld = 4 * C + Cc;
+    const int ldv = ld / VEC;
+    const size_t image = (size_t)H * W * C;
+    const size_t total = (size_t)N * Ho * Wo * ldv;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int co = (int)(e % ldv) * VEC;
+        const size_t pix = e / ldv;                  // n * Ho * Wo + s
+        const int s = (int)(pix % ((size_t)Ho * Wo));
+        const size_t n = pix / ((size_t)Ho * Wo);
+        float* dst = out + pix * ld + co;
+        if (co >= 4 * C) {
+            const float* src = coarse + pix * Cc + (co - 4 * C);
+            if (VEC == 4) *(f32x4*)dst = *(const f32x4*)src;
+            else *dst = *src;
+        } else {
+            const float* img = fine + n * image;
+            if (VEC == 4) {
+                f32x4 v;
+                v[0] = img[darknet_reorg_source(s, co + 0, H, W, C)];
+                v[1] = img[darknet_reorg_source(s, co + 1, H, W, C)];
+                v[2] = img[darknet_reorg_source(s, co + 2, H, W, C)];
+                v[3] = img[darknet_reorg_source(s, co + 3, H, W, C)];
+                *(f32x4*)dst = v;
+            } else {
+                *dst = img[darknet_reorg_source(s, co, H, W, C)];
+            }
+        }
+    }
+}
+
+// Darknet's network input from this repository's uint8 BGR batches: dst[p][c] = float(src[p][2 - c]) / 255.0f, a true
+// division (bit-equal to numpy's float32 quotient).  VEC4: a lane converts four pixels, three dwords in, three 16-byte
+// stores out; the entry point sends the pixels behind the last whole group of four to the scalar form.
+template <bool VEC4>
+__global__ __launch_bounds__(256) void u8_bgr_to_f32_rgb_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
+                                                                 size_t first, size_t count) {
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < count; g += (size_t)gridDim.x * blockDim.x) {
+        if (VEC4) {
+            const uint32_t* s = (const uint32_t*)src + g * 3;
+            const uint32_t w0 = s[0], w1 = s[1], w2 = s[2];      // b0 g0 r0 b1 | g1 r1 b2 g2 | r2 b3 g3 r3
+            float* d = dst + g * 12;
+            f32x4 a, b, c;
+            a[0] = (float)((w0 >> 16) & 255u) / 255.0f; a[1] = (float)((w0 >> 8) & 255u) / 255.0f;
+            a[2] = (float)(w0 & 255u) / 255.0f;         a[3] = (float)((w1 >> 8) & 255u) / 255.0f;
+            b[0] = (float)(w1 & 255u) / 255.0f;         b[1] = (float)(w0 >> 24) / 255.0f;
+            b[2] = (float)(w2 & 255u) / 255.0f;         b[3] = (float)(w1 >> 24) / 255.0f;
+            c[0] = (float)((w1 >> 16) & 255u) / 255.0f; c[1] = (float)(w2 >> 24) / 255.0f;
+            c[2] = (float)((w2 >> 16) & 255u) / 255.0f; c[3] = (float)((w2 >> 8) & 255u) / 255.0f;
+            *(f32x4*)(d + 0) = a; *(f32x4*)(d + 4) = b; *(f32x4*)(d + 8) = c;
+        } else {
+            const size_t p = first + g;
+            dst[p * 3 + 0] = (float)src[p * 3 + 2] / 255.0f;
+            dst[p * 3 + 1] = (float)src[p * 3 + 1] / 255.0f;
+            dst[p * 3 + 2] = (float)src[p * 3 + 0] / 255.0f;
+        }
+    }
+}
+
+extern "C" {
+
+int y2_passthrough_concat_darknet(const float* fine, const float* coarse, float* out, int N, int H, int W, int Cf, int Cc,
+                                  void* stream) {
+    if (!fine || !coarse || !out) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: null tensor");
+    if (N < 1 || H < 1 || W < 1 || Cf < 1 || Cc < 1)
+        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: N = %d, H = %d, W = %d, Cf = %d, Cc = %d must be positive",
+                    N, H, W, Cf, Cc);
+    if (Cf % 4) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: Cf = %d is no multiple of 4 (Darknet's reorg "
+                            "reads the fine map as [Cf / 4][4 H][4 W])", Cf);
+    // the index arithmetic of one image is 32-bit: 16 H W Cf values of `fine`, (4 Cf + Cc) channels
+    if ((long long)16 * H * W * Cf > 0x7fffffffLL || (long long)4 * Cf + Cc > 0x7fffffffLL)
+        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: an image of %d x %d x %d is beyond 32-bit indices", 2 * H,
+                    2 * W, Cf);
+    const bool vec = (Cc % 4) == 0 && ((uintptr_t)coarse % 16) == 0 && ((uintptr_t)out % 16) == 0;
+    const size_t total = (size_t)N * H * W * ((size_t)(4 * Cf + Cc) / (vec ? 4 : 1));
+    size_t nb = (total + 255) / 256;
+    if (nb > 65536) nb = 65536;
+    if (vec) hipLaunchKernelGGL(passthrough_concat_darknet_kernel<4>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                                fine, coarse, out, N, H, W, Cf, Cc);
+    else hipLaunchKernelGGL(passthrough_concat_darknet_kernel<1>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                            fine, coarse, out, N, H, W, Cf, Cc);
+    EXTCHK(hipGetLastError());
+    return Y2_OK;
+}
+
+int y2_u8_bgr_to_f32_rgb(const uint8_t* src, float* dst, size_t n_pixels, void* stream) {
+    if (!src || !dst) return fail(Y2_ERR_ARG, "y2_u8_bgr_to_f32_rgb: null tensor");
+    if (n_pixels < 1) return fail(Y2_ERR_ARG, "y2_u8_bgr_to_f32_rgb: no pixels");
+    const bool vec = ((uintptr_t)src % 4) == 0 && ((uintptr_t)dst % 16) == 0;
+    const size_t groups = vec ? n_pixels / 4 : 0, rest = n_pixels - groups * 4;
+    if (groups) {
+        size_t nb = (groups + 255) / 256;
+        if (nb > 65536) nb = 65536;
+        hipLaunchKernelGGL(u8_bgr_to_f32_rgb_kernel<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, dst,
+                           (size_t)0, groups);
+        EXTCHK(hipGetLastError());
+    }
+    if (rest) {
+        size_t nb = (rest + 255) / 256;
+        if (nb > 65536) nb = 65536;
+        hipLaunchKernelGGL(u8_bgr_to_f32_rgb_kernel<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, dst,
+                           groups * 4, rest);
+        EXTCHK(hipGetLastError());
+    }
+    return Y2_OK;
+}
+
+}  // extern "C"

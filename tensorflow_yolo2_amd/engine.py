@@ -142,6 +142,7 @@ class Network:
             grad_scale = 1024.0 if self.dtype in _lib.LOSS_SCALED else 1.0
         self.grad_scale = float(grad_scale)
         self.bn_eps, self.bn_momentum, self.zero_bias_grad = 1e-3, 0.99, False     # y2_ctx defaults (darknet.py:39-44)
+        self.slopes = None         # the per-layer slopes last given to set_layer_options (None: 0.1 everywhere)
         self._bessel = bool(bessel)
         check(self.lib.y2_set_options(h, self.grad_scale, int(bessel)))
         self._offsets = []
@@ -178,6 +179,7 @@ class Network:
         if slopes is not None:
             assert len(slopes) == self.num_layers
             arr = (C.c_float * self.num_layers)(*[float(v) for v in slopes])
+            self.slopes = [float(v) for v in slopes]
         if bn_eps is not None:
             self.bn_eps = float(bn_eps)
         if bn_momentum is not None:
@@ -797,6 +799,33 @@ def passthrough_concat(fine, coarse):
     assert tuple(fine.shape[:3]) == (n, 2 * h, 2 * w) and fine.is_contiguous() and coarse.is_contiguous()
     out = torch.empty((n, h, w, 4 * cf + cc), dtype=torch.float32, device=coarse.device)
     check(lib.y2_passthrough_concat(_ptr(fine), _ptr(coarse), _ptr(out), n, h, w, cf, cc, _stream()))
+    return out
+
+
+def passthrough_concat_darknet(fine, coarse, out=None):
+    """Darknet's passthrough (utils/darknet_reorg.passthrough_concat_darknet): concat(Darknet's reorg of fine
+    [N,2H,2W,Cf], coarse [N,H,W,Cc]) -> [N,H,W,4*Cf+Cc], one launch, forward only"""
+    lib = _lib.load()
+    n, h, w, cc = coarse.shape
+    cf = fine.shape[3]
+    assert fine.is_cuda and coarse.is_cuda and fine.dtype == coarse.dtype == torch.float32
+    assert tuple(fine.shape[:3]) == (n, 2 * h, 2 * w) and fine.is_contiguous() and coarse.is_contiguous()
+    if out is None:
+        out = torch.empty((n, h, w, 4 * cf + cc), dtype=torch.float32, device=coarse.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * h * w * (4 * cf + cc)
+    check(lib.y2_passthrough_concat_darknet(_ptr(fine), _ptr(coarse), _ptr(out), n, h, w, cf, cc, _stream()))
+    return out
+
+
+def u8_to_darknet_input(images_u8, out=None):
+    """uint8 BGR pixels [..., 3] (DeviceVOC.eval_batch, DeviceImages.batch) -> float32 RGB in [0, 1] of the same shape,
+    Darknet's network input: out[..., c] = float32(images_u8[..., 2 - c]) / 255"""
+    lib = _lib.load()
+    assert images_u8.is_cuda and images_u8.dtype == torch.uint8 and images_u8.is_contiguous() and images_u8.shape[-1] == 3
+    if out is None:
+        out = torch.empty(images_u8.shape, dtype=torch.float32, device=images_u8.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == images_u8.numel()
+    check(lib.y2_u8_bgr_to_f32_rgb(_ptr(images_u8), _ptr(out), images_u8.numel() // 3, _stream()))
     return out
 
 

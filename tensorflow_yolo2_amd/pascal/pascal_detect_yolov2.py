@@ -1,5 +1,6 @@
 """The YOLOv2 anchor detector on plain image files (not in the reference, whose detect script is the grid model's):
-    python -m tensorflow_yolo2_amd.pascal.pascal_detect_yolov2 [--weights FILE | --ckpt-dir DIR] --images A.jpg B.jpg ...
+    python -m tensorflow_yolo2_amd.pascal.pascal_detect_yolov2 [--weights FILE | --ckpt-dir DIR | --darknet-weights FILE]
+        --images A.jpg B.jpg ...
         [--size 416] [--thresh 0.24] [--nms 0.45] [--stretch] [--out FILE]
 The files are decoded once into ONE device pool (img_dataset/device_images.py); per batch, DeviceImages.batch makes the
 letterboxed input -- every image keeps its aspect ratio between bars of --fill, as at Darknet's test time -- and
@@ -8,7 +9,8 @@ picture's rectangle and does the class-aware NMS (y2_detect_anchor_batch_lb).  -
 instead: a plain resize.  One line per detection, `image class score xmin ymin xmax ymax`, in the 1-based pixels of each
 ORIGINAL image, images in the order given and each image's rows in descending score.  Drawing boxes is not part of it.
 The anchors and the class count are the snapshot's; with neither --weights nor --ckpt-dir the initial values run: a
-plumbing run."""
+plumbing run.  --darknet-weights FILE runs a file Darknet wrote for yolov2-voc.cfg instead: the "darknet" topology of
+yolo2_nets/yolov2.py with the published VOC anchors (net_utils.load_darknet_weights); every other flag works as before."""
 import argparse
 import sys
 
@@ -26,6 +28,9 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--weights", default=None, help="snapshot file (train_iter_<i>.npz of pascal_train_yolov2.py)")
     ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_*.npz snapshots: the latest is used")
+    ap.add_argument("--darknet-weights", default=None,
+                    help="a Darknet .weights file of yolov2-voc.cfg (yolov2-voc.weights): builds the \"darknet\" topology "
+                         "with the published VOC anchors and 20 classes; not with --weights or --ckpt-dir")
     ap.add_argument("--thresh", type=float, default=0.24, help="score above which a box is a detection")
     ap.add_argument("--nms", type=float, default=0.45, help="IoU above which a box of the same class is suppressed")
     ap.add_argument("--max-out", type=int, default=100, help="detections kept per image")
@@ -45,6 +50,8 @@ def parse_args(argv=None):
         ap.error("--batch, --max-out and --width-div must be at least 1")
     if not 0 <= args.fill <= 255:
         ap.error("--fill %d outside 0..255" % args.fill)
+    if args.darknet_weights and (args.weights or args.ckpt_dir):
+        ap.error("--darknet-weights goes with neither --weights nor --ckpt-dir")
     return args
 
 
@@ -57,11 +64,18 @@ def main(argv=None):
         sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
         snapshot = sfiles[-1] if sfiles else None
     anchors, num_class = yolov2.ANCHORS_VOC, len(pascal_voc.CLASSES)
+    bn_eps = None
     if snapshot:
         anchors, num_class, _it = net_utils.read_yolov2_meta(snapshot)
+        bn_eps = net_utils.read_yolov2_bn_eps(snapshot)
     detector = yolov2.YOLOv2Detector(args.batch, args.size, num_class=num_class, anchors=anchors, dtype=args.dtype,
-                                     width_div=args.width_div)
+                                     width_div=args.width_div, bn_eps=bn_eps,
+                                     topology="darknet" if args.darknet_weights else "paper")
     restored = 0
+    if args.darknet_weights:
+        print('Restorining model from Darknet weight file {:s}'.format(args.darknet_weights))
+        seen = net_utils.load_darknet_weights(detector, args.darknet_weights)
+        print('{:d} images seen'.format(seen))
     if snapshot:
         print('Restorining model from weight file {:s}'.format(snapshot))
         restored = net_utils.restore_yolov2_variables(detector, snapshot)

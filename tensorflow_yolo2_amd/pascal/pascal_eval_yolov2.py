@@ -16,7 +16,9 @@ With --letterbox every image keeps its aspect ratio, as at Darknet's test time: 
 --fill (y2_letterbox_u8_batch) and the detect launch un-maps the boxes from that rectangle (y2_detect_anchor_batch_lb,
 y2_detect_anchor_classes_batch_lb); the default is the plain stretch, bit for bit as before.
 The anchors and the class count are the snapshot's (pascal_train_yolov2.py); with neither --weights nor --ckpt-dir the
-initial values are evaluated with the published VOC anchors: a plumbing run."""
+initial values are evaluated with the published VOC anchors: a plumbing run.  --darknet-weights FILE evaluates a file
+Darknet wrote for yolov2-voc.cfg instead (the "darknet" topology of yolo2_nets/yolov2.py, net_utils.load_darknet_weights):
+    pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --per-class --letterbox"""
 import argparse
 import sys
 
@@ -38,6 +40,9 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--weights", default=None, help="snapshot file (train_iter_<i>.npz of pascal_train_yolov2.py)")
     ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_*.npz snapshots: the latest is evaluated")
+    ap.add_argument("--darknet-weights", default=None,
+                    help="a Darknet .weights file of yolov2-voc.cfg (yolov2-voc.weights): builds the \"darknet\" topology "
+                         "with the published VOC anchors and the image set's class count; not with --weights or --ckpt-dir")
     ap.add_argument("--thresh", type=float, default=0.005, help="score above which a box is a detection")
     ap.add_argument("--nms", type=float, default=0.45, help="IoU above which a box of the same class is suppressed")
     ap.add_argument("--max-out", type=int, default=100, help="detections kept per image")
@@ -67,6 +72,8 @@ def parse_args(argv=None):
         ap.error("--batch, --max-out, --max-per-class and --width-div must be at least 1")
     if not 0 <= args.fill <= 255:
         ap.error("--fill %d outside 0..255" % args.fill)
+    if args.darknet_weights and (args.weights or args.ckpt_dir):
+        ap.error("--darknet-weights goes with neither --weights nor --ckpt-dir")
     return args
 
 
@@ -79,13 +86,20 @@ def main(argv=None):
         sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
         snapshot = sfiles[-1] if sfiles else None
     anchors, num_class = yolov2.ANCHORS_VOC, imdb.num_class
+    bn_eps = None
     if snapshot:
         anchors, num_class, _it = net_utils.read_yolov2_meta(snapshot)
+        bn_eps = net_utils.read_yolov2_bn_eps(snapshot)
         if num_class != imdb.num_class:
             raise ValueError("snapshot %s: num_class is %d, the image set has %d" % (snapshot, num_class, imdb.num_class))
     detector = yolov2.YOLOv2Detector(args.batch, args.size, num_class=num_class, anchors=anchors, dtype=args.dtype,
-                                     width_div=args.width_div)
+                                     width_div=args.width_div, bn_eps=bn_eps,
+                                     topology="darknet" if args.darknet_weights else "paper")
     restored = 0
+    if args.darknet_weights:
+        print('Restorining model from Darknet weight file {:s}'.format(args.darknet_weights))
+        seen = net_utils.load_darknet_weights(detector, args.darknet_weights)
+        print('{:d} images seen'.format(seen))
     if snapshot:
         print('Restorining model from weight file {:s}'.format(snapshot))
         restored = net_utils.restore_yolov2_variables(detector, snapshot)

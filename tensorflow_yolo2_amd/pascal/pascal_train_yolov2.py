@@ -1,6 +1,6 @@
 """Train the YOLOv2 anchor detector (yolo2_nets/yolov2.py; not in the reference, whose trainer is the grid model) on VOC:
     python -m tensorflow_yolo2_amd.pascal.pascal_train_yolov2 --devkit data/VOCdevkit --iters 20 \
-        [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR]
+        [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR | --darknet-backbone FILE]
         [--box-labels [--max-boxes 30] [--area-weight] [--prior-images 12800]]
         [--solver darknet [--lr .001] [--momentum .9] [--decay .0005] [--burn-in 1000] [--power 4]
                           [--policy steps --steps 40000,60000 --scales .1,.1 | --policy poly --max-batches N | --policy constant]]
@@ -25,7 +25,9 @@ rate the 10-iteration line prints is the host's current_rate of the iteration nu
 Snapshots are `train_iter_<i>.npz` (net_utils.save_yolov2_variables: the three stacks, the anchors, the three Adam
 states -- or the three Momentum slots and the solver record -- with their one loss scaler); a run with --ckpt-dir resumes from the latest, moves the data order and the
 augmentation stream to where the saved run stood, and so continues it.  Without a snapshot, --imagenet-ckpt-dir takes
-the Darknet-19 backbone from the latest classifier snapshot there.  --anchors kmeans clusters the image set's boxes
+the Darknet-19 backbone from the latest classifier snapshot there, and --darknet-backbone FILE from a file Darknet wrote
+(darknet19_448.conv.23; net_utils.read_darknet_backbone): the trainer then runs batch-norm epsilon 1e-6, which its
+snapshots record (yolov2/bn_eps) and a resumed run takes from them.  --anchors kmeans clusters the image set's boxes
 (utils/anchors.py) instead of using the published VOC anchors; a resumed run keeps its snapshot's anchors.
 
 One process, one GPU."""
@@ -61,6 +63,9 @@ def parse_args(argv=None):
     ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_<i>.npz snapshots: resume from the latest")
     ap.add_argument("--save-every", type=int, default=40000)
     ap.add_argument("--imagenet-ckpt-dir", default=None, help="classifier snapshots to take the backbone from")
+    ap.add_argument("--darknet-backbone", default=None,
+                    help="a Darknet .weights file to take the Darknet-19 backbone from (darknet19_448.conv.23); the trainer "
+                         "then runs Darknet's batch-norm epsilon 1e-6; not with --imagenet-ckpt-dir")
     ap.add_argument("--anchors", default="voc", choices=("voc", "kmeans"),
                     help="voc: the published VOC anchors; kmeans: cluster the image set's boxes at --size")
     ap.add_argument("--box-labels", action="store_true", help="train on the box list (every object), not the label grid")
@@ -86,6 +91,8 @@ def parse_args(argv=None):
         ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
     if args.batch < 1 or args.iters < 0 or args.save_every < 1 or args.width_div < 1:
         ap.error("--batch, --save-every and --width-div must be at least 1, --iters at least 0")
+    if args.darknet_backbone and args.imagenet_ckpt_dir:
+        ap.error("--darknet-backbone and --imagenet-ckpt-dir name two backbones: give one")
     try:
         args.ms_sizes = tuple(int(v) for v in str(args.ms_sizes).split(",") if v.strip())
     except ValueError:
@@ -177,9 +184,13 @@ def main(argv=None):
     else:
         anchors = yolov2.ANCHORS_VOC
     first = step_size(args, 1) if args.multi_scale else args.size
+    # Darknet's layers were trained with its batch-norm epsilon; a resumed run keeps its snapshot's (yolov2/bn_eps)
+    bn_eps = yolov2.DARKNET_BN_EPS if args.darknet_backbone else None
+    if latest and bn_eps is None:
+        bn_eps = net_utils.read_yolov2_bn_eps(latest)
     trainer = yolov2.YOLOv2Trainer(args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
                                    seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
-                                   prior_images=args.prior_images, solver=args.solver_record)
+                                   prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps)
     last_iter_num = 0
     if latest:
         print('Restorining model snapshots from {:s}'.format(latest))
@@ -190,6 +201,10 @@ def main(argv=None):
         if prior:
             net_utils.load_darknet19_backbone(trainer, net_utils.read_darknet19_core(prior[-1]))
             print('Backbone restored from {:s}'.format(prior[-1]))
+    elif args.darknet_backbone:
+        net_utils.load_darknet19_backbone(trainer, net_utils.read_darknet_backbone(args.darknet_backbone, trainer.bn_eps,
+                                                                                   width_div=args.width_div))
+        print('Backbone restored from Darknet weight file {:s}'.format(args.darknet_backbone))
     TOTAL_ITER = args.iters + last_iter_num
     T = Timer()
     T.tic()

@@ -18,7 +18,11 @@ stack, the one momentum slot of every parameter and its step count, and once the
     yolov2/solver/learning_rate, momentum, decay  float32      yolov2/solver/policy  str
     yolov2/solver/burn_in, power, max_batches  int64   yolov2/solver/steps  int64 [n]   yolov2/solver/scales  float32 [n]
 
-A snapshot holds the slots of one optimizer; the Adam names and an Adam snapshot's bytes are what they were."""
+A snapshot holds the slots of one optimizer; the Adam names and an Adam snapshot's bytes are what they were.
+
+A model built with another batch-norm epsilon than the contexts' default (YOLOv2Trainer(bn_eps=1e-6), the one a backbone
+from a Darknet file needs) adds ONE key, `yolov2/bn_eps` float64; a default model writes no such key, so its snapshots
+keep their bytes."""
 import numpy as np
 
 STACKS = ("stem", "deep", "head")
@@ -30,7 +34,10 @@ PREFIX = "yolov2/"
 SOLVER_PREFIX = PREFIX + "solver/"
 
 
-def to_blob(stacks, anchors, num_class, iteration, adam=None, scaler=None, sgd=None, solver=None):
+DEFAULT_BN_EPS = 1e-3            # engine.Network's (tf.layers.batch_normalization's)
+
+
+def to_blob(stacks, anchors, num_class, iteration, adam=None, scaler=None, sgd=None, solver=None, bn_eps=None):
     """stacks: {stack: [layer dict of the six arrays]}; adam: {stack: {"m": [layer dict of PARAM_KEYS], "v": [...],
     "t": int}} or None; scaler: {"ctrl": int32 [8], "scale": float, "clean": int} or None; sgd: {stack: {"accum": [layer
     dict of PARAM_KEYS], "t": int}} with solver, a utils.solver.Solver, or both None -> flat {name: array}"""
@@ -62,7 +69,14 @@ def to_blob(stacks, anchors, num_class, iteration, adam=None, scaler=None, sgd=N
         blob[PREFIX + "scaler/ctrl"] = np.asarray(scaler["ctrl"], np.int32).reshape(8)
         blob[PREFIX + "scaler/scale"] = np.float64(scaler["scale"])
         blob[PREFIX + "scaler/clean"] = np.int64(scaler["clean"])
+    if bn_eps is not None and float(bn_eps) != DEFAULT_BN_EPS:
+        blob[PREFIX + "bn_eps"] = np.float64(bn_eps)
     return blob
+
+
+def bn_eps_from_blob(snap):
+    """the batch-norm epsilon a snapshot was written with: its `yolov2/bn_eps`, or the default where it has none"""
+    return float(snap[PREFIX + "bn_eps"]) if _has(snap, PREFIX + "bn_eps") else DEFAULT_BN_EPS
 
 
 def _has(snap, name):

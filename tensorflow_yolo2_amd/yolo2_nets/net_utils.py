@@ -509,7 +509,9 @@ def save_yolov2_variables(model, path, iteration=None):
     """model: a YOLOv2Detector or a YOLOv2Trainer -> one .npz: the parameters and batch-norm state of the three stacks,
     the anchors, the class count and the iteration (default: model.iteration); for a trainer also the three Adam states
     (or, on Darknet's solver, the three Momentum slots and the solver record) and the one loss scaler and step counter
-    they share, so that a resumed run continues the uninterrupted one"""
+    they share, so that a resumed run continues the uninterrupted one.  A batch-norm epsilon other than the default adds
+    the key yolov2/bn_eps.  The "darknet" topology has no .npz form: its snapshot is the .weights file"""
+    _refuse_darknet_topology(model, "save_yolov2_variables", "save_darknet_weights")
     nets = model.networks()
     stacks = {s: net.export_params() for s, net in zip(_v2snap.STACKS, nets)}
     adam = scaler = sgd = None
@@ -528,7 +530,7 @@ def save_yolov2_variables(model, path, iteration=None):
             scaler = {"ctrl": sc.ctrl.cpu().numpy(), "scale": sc.scale, "clean": sc._clean}
     blob = _v2snap.to_blob(stacks, model.anchors, model.num_class,
                            model.iteration if iteration is None else iteration, adam, scaler, sgd,
-                           solver if sgd is not None else None)
+                           solver if sgd is not None else None, bn_eps=getattr(model, "bn_eps", None))
     np.savez(path, **blob)
     return sorted(blob)
 
@@ -537,11 +539,19 @@ def restore_yolov2_variables(model, path):
     """the inverse of save_yolov2_variables -> the snapshot's iteration (also left in model.iteration).  A
     YOLOv2Detector takes the parameters and batch-norm state only; a YOLOv2Trainer also the optimizer when the file
     holds it.  Other anchors, another class count or a tensor of another shape raise, naming both values; so does a
-    trainer on one optimizer given the slots of the other, or another solver record than its own."""
+    trainer on one optimizer given the slots of the other, or another solver record than its own, or a model whose
+    batch-norm epsilon is not the snapshot's (yolov2/bn_eps; the default where the file has no such key)."""
+    _refuse_darknet_topology(model, "restore_yolov2_variables", "load_darknet_weights")
     with np.load(path) as snap:
         stacks, anchors, num_class, iteration, adam, scaler = _v2snap.from_blob(snap)
         sgd, snap_solver = _v2snap.sgd_from_blob(snap)
-    if hasattr(model, "opts"):      # before anything is loaded: a refused snapshot leaves the trainer as it was
+        snap_eps = _v2snap.bn_eps_from_blob(snap)
+    model_eps = getattr(model, "bn_eps", None)
+    model_eps = _v2snap.DEFAULT_BN_EPS if model_eps is None else float(model_eps)
+    if snap_eps != model_eps:       # before anything is loaded: a refused snapshot leaves the model as it was
+        raise ValueError("snapshot %s was written with batch-norm epsilon %g, the model runs %g (build it with bn_eps=%g)" %
+                         (path, snap_eps, model_eps, snap_eps))
+    if hasattr(model, "opts"):
         _v2snap.check_optimizer(path, adam is not None, snap_solver, getattr(model, "solver", None))
     _v2snap.check_matches("num_class", path, num_class, model.num_class)
     _v2snap.check_matches("anchors", path, anchors, np.asarray(model.anchors, np.float32).reshape(-1, 2))
@@ -583,6 +593,19 @@ def read_yolov2_meta(path):
         return _v2snap.meta_from_blob(snap)
 
 
+def read_yolov2_bn_eps(path):
+    """the `bn_eps` argument of the model a YOLOv2 snapshot restores into: its yolov2/bn_eps, or None (the default)"""
+    with np.load(path) as snap:
+        eps = _v2snap.bn_eps_from_blob(snap)
+    return None if eps == _v2snap.DEFAULT_BN_EPS else eps
+
+
+def _refuse_darknet_topology(model, what, instead):
+    if getattr(model, "topology", "paper") == "darknet":
+        raise ValueError("%s: .npz snapshots of the \"darknet\" topology are out of scope -- the .weights file is this "
+                         "topology's snapshot (%s)" % (what, instead))
+
+
 def get_ordered_yolov2_ckpts(ckpt_dir):
     """`train_iter_<i>.npz` files of ckpt_dir by iteration number, oldest first"""
     files = glob.glob(os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + "_iter_*.npz"))
@@ -622,3 +645,115 @@ def load_darknet19_backbone(model, core_layers):
                 layers[l - lo][k] = a
         net.load_params(layers)
     return n_core
+
+
+# ---------------------------------------------------------------------------
+# Darknet's `.weights` files (utils/darknet_weights.py holds the format and the per-layer arithmetic, numpy only).
+# load_darknet_weights / save_darknet_weights: a YOLOv2Detector(topology="darknet"), whose four stacks in networks()
+# order are the file's convolutions in cfg order.  read_darknet_backbone: the 18 Darknet-19 layers of any such file
+# (darknet19_448.conv.23) for the paper-topology trainer, through load_darknet19_backbone.
+# ---------------------------------------------------------------------------
+from ..utils import darknet_weights as _dkw
+
+
+def _darknet_model(model, what):
+    if getattr(model, "topology", "paper") != "darknet":
+        raise ValueError("%s takes a YOLOv2Detector(topology=\"darknet\"): the paper topology's graph is not the one a "
+                         "Darknet file holds" % what)
+    return model.networks()
+
+
+def darknet_file_layers(model):
+    """[(k, c, n, batch_norm)] of the file a "darknet" detector reads and writes: its layers in networks() order, every
+    one with batch norm but the last, and Darknet's filter size in the 18 core positions (its fourth layer is 1x1)"""
+    nets = _darknet_model(model, "darknet_file_layers")
+    out = []
+    for net in nets:
+        for l, (k, ci, co, _pool) in enumerate(net.spec):
+            kf = _dkw.DARKNET19_CORE[len(out)][0] if len(out) < len(_dkw.DARKNET19_CORE) else k
+            out.append((kf, ci, co, not (net is nets[-1] and l == net.num_layers - 1)))
+    return out
+
+
+def _describe(model):
+    return "%d classes, %d anchors, widths %s" % (model.num_class, model.B,
+                                                  "/".join(str(net.spec[-1][2]) for net in model.networks()))
+
+
+def load_darknet_weights(model, path):
+    """fill a YOLOv2Detector(topology="darknet") from a Darknet `.weights` file (yolov2-voc.weights) -> its `seen`.
+    Per layer with batch norm: W = weights.transpose(2, 3, 1, 0) -- the first layer keeps Darknet's RGB order, the model
+    feeds RGB --, b = 0, the four batch-norm arrays copied.  Last layer: b = biases and an inference batch norm that is
+    the identity to one ulp (utils/darknet_weights.to_layer_params).  A file whose float count is not the one of the
+    model's class count, anchors and width raises, naming both."""
+    nets = _darknet_model(model, "load_darknet_weights")
+    file_layers = darknet_file_layers(model)
+    _major, _minor, _revision, seen, values = _dkw.read(path)
+    want = sum(_dkw.layer_floats(l) for l in file_layers)
+    try:
+        layers, _used = _dkw.split(values, file_layers)
+    except ValueError as e:
+        raise ValueError("%s holds %d floats, the model (%s: %d convolutions) needs %d: %s" %
+                         (path, values.size, _describe(model), len(file_layers), want, e))
+    if len(layers) != len(file_layers):
+        raise ValueError("%s holds %d convolutions (%d floats), the model (%s) has %d (%d floats)" %
+                         (path, len(layers), values.size, _describe(model), len(file_layers), want))
+    pos = 0
+    for net in nets:
+        params = [_dkw.to_layer_params(layers[pos + l], net.spec[l][0], model.bn_eps) for l in range(net.num_layers)]
+        for l, p in enumerate(params):
+            for k, shape in net._shapes(l).items():
+                if tuple(p[k].shape) != tuple(shape):
+                    raise ValueError("%s: convolution %d %s has shape %s, the model (%s) expects %s" %
+                                     (path, pos + l, k, tuple(p[k].shape), _describe(model), tuple(shape)))
+        net.load_params(params)
+        pos += net.num_layers
+    return seen
+
+
+def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):
+    """the inverse, for a YOLOv2Detector(topology="darknet"): batch-norm layers with the conv bias folded into the mean,
+    the last layer (it must run without activation: slope 1) with its inference affine folded into filters and biases
+    (utils/darknet_weights.from_layer_params).  A model that load_darknet_weights filled and nothing changed gives the
+    bytes that were read (write the header's version too: a file of version 0.2 has a 64-bit `seen`)."""
+    nets = _darknet_model(model, "save_darknet_weights")
+    slopes = nets[-1].slopes                     # None: a context that was never given slopes runs 0.1 everywhere
+    if slopes is None or float(slopes[-1]) != 1.0:
+        raise ValueError("save_darknet_weights: the last layer runs with slope %s, Darknet's is linear (slope 1): its "
+                         "batch norm cannot be folded through an activation" % (0.1 if slopes is None else slopes[-1]))
+    file_layers = darknet_file_layers(model)
+    out, pos = [], 0
+    for net in nets:
+        for l, p in enumerate(net.export_params()):
+            kf, _c, _n, bn = file_layers[pos + l]
+            out.append(_dkw.from_layer_params(p, kf, bn, model.bn_eps))
+        pos += net.num_layers
+    return _dkw.write(path, out, seen, major, minor, revision)
+
+
+def read_darknet_backbone(path, bn_eps_model, width_div=1):
+    """the 18 Darknet-19 core layers of a Darknet file (darknet19_448.conv.23, or the front of a longer one) as the dicts
+    load_darknet19_backbone takes, for THIS repository's input convention -- uint8 BGR pixels mapped to [-1, 1), the
+    paper-topology YOLOv2Trainer.  Per layer b = 0 and the batch-norm arrays are copied; Darknet's 1x1 fourth layer sits
+    on the centre tap of this graph's 3x3 one.  The first layer's filter channels are reversed and halved and the
+    constant sum(W) / 2 goes into moving_mean (utils/darknet_weights.fold_first_layer): exact in the interior, NOT on
+    the one-pixel border ring of the first layer's output, where Darknet pads with black and this stack with mid-grey.
+    Darknet's epsilon is 1e-6 and the variances are not bent to another one: a model on any other epsilon is refused.
+    width_div: the narrow variant's widths (tests); a Darknet file carries no shapes."""
+    from . import yolov2 as _yolov2
+    if bn_eps_model is None or float(bn_eps_model) != _yolov2.DARKNET_BN_EPS:
+        raise ValueError("read_darknet_backbone: the model's batch-norm epsilon is %s, Darknet's layers were trained with "
+                         "%g -- build the trainer with YOLOv2Trainer(bn_eps=1e-6)" %
+                         ("the default" if bn_eps_model is None else "%g" % float(bn_eps_model), _yolov2.DARKNET_BN_EPS))
+    sa, sb, _sc = _yolov2.yolov2_specs(width_div=width_div)
+    spec = (sa + sb)[:len(_dkw.DARKNET19_CORE)]
+    file_layers = [(_dkw.DARKNET19_CORE[l][0], ci, co, True) for l, (_k, ci, co, _p) in enumerate(spec)]
+    want = sum(_dkw.layer_floats(l) for l in file_layers)
+    values = _dkw.read(path)[4]
+    if values.size < want:
+        raise ValueError("%s holds %d floats, the Darknet-19 core at width_div %d needs %d" %
+                         (path, values.size, width_div, want))
+    layers, _used = _dkw.split(values[:want], file_layers)
+    out = [_dkw.to_layer_params(d, spec[l][0], bn_eps_model) for l, d in enumerate(layers)]
+    out[0] = _dkw.fold_first_layer(out[0])
+    return out

@@ -32,30 +32,91 @@ def yolov2_specs(num_class=20, num_anchors=5, width_div=1):
     return a, b, c
 
 
+DARKNET_BN_EPS = 1e-6            # Darknet's batch norm: (x - mean) / sqrt(var + .000001f)
+DARKNET_ROUTE_WIDTH = 64         # the 1x1 convolution on the route of yolov2-voc.cfg: 512 -> 64, reorganised to 256
+
+
+def yolov2_darknet_specs(num_class=20, num_anchors=5, width_div=1):
+    """the four stacks of yolov2-voc.cfg: the stem and the 13x13 stack of yolov2_specs, the one-layer route stack on the
+    fine map (its width stays 64 under width_div, its input is the divided one) and the head behind Darknet's
+    passthrough: 3x3 over 4 * 64 + C13 channels, then the 1x1 output layer (linear, no batch norm in Darknet)"""
+    a, b, c = yolov2_specs(num_class, num_anchors, width_div)
+    r = [(1, a[-1][2], DARKNET_ROUTE_WIDTH, 0)]
+    c = [(3, 4 * DARKNET_ROUTE_WIDTH + b[-1][2], c[0][2], 0), c[1]]
+    return a, b, r, c
+
+
+TOPOLOGIES = ("paper", "darknet")
+
+
 class YOLOv2Detector:
+    """topology "paper" (default): the graph of the module docstring.  "darknet": the graph of yolov2-voc.cfg, the one a
+    Darknet `.weights` file holds (net_utils.load_darknet_weights / save_darknet_weights) -- a fourth stack, the 1x1
+    route convolution 512 -> 64 on the fine map; Darknet's reorg (engine.passthrough_concat_darknet) with the
+    reorganised map in FRONT of the 13x13 path; a last layer without activation; batch-norm epsilon 1e-6; and the input
+    RGB in [0, 1]: uint8 BGR batches are converted by engine.u8_to_darknet_input, float input is taken as that already.
+    bn_eps: the batch-norm epsilon of every stack (None: the context's default 1e-3, or 1e-6 on "darknet")."""
+
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0", width_div=1):
+                 device="cuda:0", width_div=1, topology="paper", bn_eps=None):
         assert image_size % 32 == 0
+        if topology not in TOPOLOGIES:
+            raise ValueError("topology %r: one of %s" % (topology, ", ".join(TOPOLOGIES)))
+        self.topology = topology
+        self.bn_eps = None if bn_eps is None else float(bn_eps)
         self.batch, self.size, self.S = batch, image_size, image_size // 32
         self.num_class, self.anchors = num_class, np.asarray(anchors, np.float32).reshape(-1, 2)
         self.B = len(self.anchors)
         self.iteration = 0                                   # of the snapshot last restored (net_utils)
-        sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
         self.anchors_dev = torch.as_tensor(self.anchors).to(device).contiguous()
         S = self.S
+        if topology == "darknet":
+            self._init_darknet(batch, image_size, num_class, dtype, seed, device, width_div)
+            return
+        sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
         self.stem = E.Network(sa, batch, image_size, image_size, dtype=dtype, training=False, device=device)
         self.deep = E.Network(sb, batch, S, S, dtype=dtype, training=False, device=device)
         self.head = E.Network(sc, batch, S, S, dtype=dtype, training=False, device=device)
         for i, net in enumerate((self.stem, self.deep, self.head)):
             net.init_params(seed + i)
+            if self.bn_eps is not None:
+                net.set_layer_options(bn_eps=self.bn_eps)
+
+    def _init_darknet(self, batch, image_size, num_class, dtype, seed, device, width_div):
+        S = self.S
+        if self.bn_eps is None:
+            self.bn_eps = DARKNET_BN_EPS
+        sa, sb, sr, sc = yolov2_darknet_specs(num_class, self.B, width_div)
+        mk = lambda spec, h: E.Network(spec, batch, h, h, dtype=dtype, training=False, device=device)
+        self.stem, self.deep, self.route, self.head = mk(sa, image_size), mk(sb, S), mk(sr, 2 * S), mk(sc, S)
+        for i, net in enumerate(self.networks()):
+            net.init_params(seed + i)
+            net.set_layer_options(slopes=[0.1, 1.0] if net is self.head else None, bn_eps=self.bn_eps)
+        self._input = torch.empty((batch, image_size, image_size, 3), dtype=torch.float32, device=device)
+        self._cat = torch.empty((batch, S, S, sc[0][1]), dtype=torch.float32, device=device)
 
     def networks(self):
-        """the three stack contexts (stem, 13x13 stack, head)"""
+        """the stack contexts: (stem, 13x13 stack, head), or on the "darknet" topology (stem, 13x13 stack, route, head)
+        -- the order of the convolutions in a `.weights` file"""
+        if self.topology == "darknet":
+            return self.stem, self.deep, self.route, self.head
         return self.stem, self.deep, self.head
+
+    def _forward_darknet(self, images, out=None):
+        if images.dtype == torch.uint8:
+            images = E.u8_to_darknet_input(images, out=self._input)        # BGR pixels -> RGB in [0, 1]
+        fine = self.stem.forward(images, False, False)                      # [N,2S,2S,512]
+        coarse = self.deep.forward(E.max_pool_2x2(fine), False, False)      # [N,S,S,1024]
+        route = self.route.forward(fine, False, False)                      # [N,2S,2S,64]
+        cat = E.passthrough_concat_darknet(route, coarse, out=self._cat)    # [N,S,S,256+1024], reorganised map first
+        out = self.head.forward(cat, False, False, out=out)                 # [N,S,S,B*(5+C)], last layer linear
+        return out.view(self.batch, self.S, self.S, self.B, 5 + self.num_class)
 
     def forward(self, images, out=None):
         """images [N,size,size,3] fp32 (or uint8 BGR pixels) on the device -> raw grid [N,S,S,B,5+C] (in `out`, a
-        contiguous fp32 tensor of that many elements, if given)"""
+        contiguous fp32 tensor of that many elements, if given).  On the "darknet" topology fp32 input is RGB in [0, 1]"""
+        if self.topology == "darknet":
+            return self._forward_darknet(images, out)
         fine = self.stem.forward(images, False, False)                      # [N,2S,2S,512]
         coarse = self.deep.forward(E.max_pool_2x2(fine), False, False)      # [N,S,S,1024]
         cat = E.passthrough_concat(fine, coarse)                            # [N,S,S,3072]
@@ -102,7 +163,16 @@ class YOLOv2Trainer:
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
-                 solver=None):
+                 solver=None, bn_eps=None, topology="paper"):
+        if topology != "paper":
+            if topology not in TOPOLOGIES:
+                raise ValueError("topology %r: one of %s" % (topology, ", ".join(TOPOLOGIES)))
+            raise NotImplementedError("YOLOv2Trainer trains the paper topology only: the %r graph needs the gradient of "
+                                      "Darknet's reorg, a fourth optimizer and a last layer without batch statistics" %
+                                      topology)
+        # the batch-norm epsilon of every context and size (None: the contexts' default, 1e-3); 1e-6 is Darknet's, the one
+        # a backbone read from a Darknet file was trained with (net_utils.read_darknet_backbone)
+        self.topology, self.bn_eps = topology, None if bn_eps is None else float(bn_eps)
         from ..trainer import GradReducer
         self._GradReducer = GradReducer
         self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
@@ -132,6 +202,9 @@ class YOLOv2Trainer:
                                                   device=self.device, share_with=share)
             nets = (mk(sa, size, first[0] if first else None), mk(sb, S, first[1] if first else None),
                     mk(sc, S, first[2] if first else None))
+            if self.bn_eps is not None:
+                for net in nets:
+                    net.set_layer_options(bn_eps=self.bn_eps)
             if first is None:
                 for i, net in enumerate(nets):
                     net.init_params(self.seed + i)
