@@ -212,12 +212,19 @@ int y2_passthrough_concat(const float* fine, const float* coarse, float* out, in
                           void* stream);
 int y2_passthrough_concat_backward(const float* dout, float* dfine, float* dcoarse, int N, int H, int W, int Cf,
                                    int Cc, void* stream);
-/* Darknet's passthrough, forward only (specification: utils/darknet_reorg.py): out [N,H,W,4*Cf+Cc] = Darknet's `reorg`
+/* Darknet's passthrough, forward (specification: utils/darknet_reorg.py): out [N,H,W,4*Cf+Cc] = Darknet's `reorg`
  * (stride 2, as yolov2-voc.cfg runs it: a scramble of each image over channels and positions, not a space-to-depth) of
  * fine [N,2H,2W,Cf] in channels 0 .. 4*Cf-1, coarse [N,H,W,Cc] behind it -- `route layers=-1,-4`.  A pure gather, bit
  * exact, one launch.  Y2_ERR_ARG: a null tensor, a size below 1, Cf % 4 != 0, an image beyond 32-bit indices. */
 int y2_passthrough_concat_darknet(const float* fine, const float* coarse, float* out, int N, int H, int W, int Cf, int Cc,
                                   void* stream);
+/* Its gradient (specification: utils/darknet_reorg.passthrough_concat_darknet_backward): dout [N,H,W,4*Cf+Cc] ->
+ * dfine [N,2H,2W,Cf] (the inverse of Darknet's reorg, a permutation of each image) and dcoarse [N,H,W,Cc].  One launch
+ * writes every element of both outputs exactly once: no zero fill, no atomics, bit exact.  Y2_ERR_ARG as above. */
+int y2_passthrough_concat_darknet_backward(const float* dout, float* dfine, float* dcoarse, int N, int H, int W, int Cf,
+                                           int Cc, void* stream);
+/* x[0 .. n) = 0 on an fp32 buffer (a trainer's gradient masks: parameters that must not move) */
+int y2_zero(float* x, size_t n, void* stream);
 /* Darknet's network input from uint8 BGR pixels: dst[p][c] = float(src[p][2 - c]) / 255.0f (RGB in [0, 1]; a true
  * division, bit-equal to numpy's float32 quotient).  Y2_ERR_ARG: a null tensor, n_pixels = 0. */
 int y2_u8_bgr_to_f32_rgb(const uint8_t* src, float* dst, size_t n_pixels, void* stream);

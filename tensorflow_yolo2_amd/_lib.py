@@ -78,6 +78,8 @@ SIGNATURES = {
     "y2_passthrough_concat": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "y2_passthrough_concat_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "y2_passthrough_concat_darknet": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "y2_passthrough_concat_darknet_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "y2_zero": (_i, [_vp, _sz, _vp]),
     "y2_u8_bgr_to_f32_rgb": (_i, [_vp, _vp, _sz, _vp]),
     "y2_accumulate": (_i, [_vp, _vp, _sz, _vp]),
     "y2_add_relu": (_i, [_vp, _vp, _vp, _sz, _vp]),

@@ -775,6 +775,50 @@ __global__ __launch_bounds__(256) void passthrough_concat_darknet_kernel(const f
     }
 }
 
+// The gradient of Darknet's passthrough (specification: utils/darknet_reorg.passthrough_concat_darknet_backward).  The
+// reorg is a permutation of each image, so its gradient is the inverse permutation: dfine[darknet_reorg_source(s, co)] =
+// dout[s][co], every element of dfine named exactly once.  ONE launch writes both outputs, every element exactly once,
+// with no zero fill and no atomics.  This is the SCATTER form, the forward kernel with loads and stores exchanged: a lane
+// owns VEC consecutive channels of one dout pixel (VEC = 4: one 16-byte load), then makes one 16-byte store into dcoarse
+// or four 4-byte stores into dfine -- the lane beside it (k + 1) writes 16 bytes further in the same four pixel rows, so a
+// wave's stores fill whole 256-byte rows of dfine between them.  The gather form (a lane owns four channels of a dfine
+// pixel, one 16-byte store, four 4-byte loads through the closed-form inverse of darknet_reorg_source) is the same
+// function and measured 7 % slower at S = 13 and 19 (scripts/probes/darknet_route_backward_ab.hip holds both forms and
+// the inverse with its derivation), so it is not in the library.  VEC = 1: Cc % 4 != 0 or a pointer off 16 bytes.
+template <int VEC>
+__global__ __launch_bounds__(256) void darknet_route_backward_kernel(const float* __restrict__ dout,
+                                                                     float* __restrict__ dfine,
+                                                                     float* __restrict__ dcoarse, int N, int Ho, int Wo,
+                                                                     int C, int Cc) {
+    const int H = 2 * Ho, W = 2 * Wo, ld = 4 * C + Cc;
+    const int ldv = ld / VEC;
+    const size_t image = (size_t)H * W * C;
+    const size_t total = (size_t)N * Ho * Wo * ldv;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int co = (int)(e % ldv) * VEC;
+        const size_t pix = e / ldv;                  // n * Ho * Wo + s
+        const int s = (int)(pix % ((size_t)Ho * Wo));
+        const size_t n = pix / ((size_t)Ho * Wo);
+        const float* src = dout + pix * ld + co;
+        if (co >= 4 * C) {
+            float* dst = dcoarse + pix * Cc + (co - 4 * C);
+            if (VEC == 4) *(f32x4*)dst = *(const f32x4*)src;
+            else *dst = *src;
+        } else {
+            float* img = dfine + n * image;
+            if (VEC == 4) {
+                const f32x4 v = *(const f32x4*)src;
+                img[darknet_reorg_source(s, co + 0, H, W, C)] = v[0];
+                img[darknet_reorg_source(s, co + 1, H, W, C)] = v[1];
+                img[darknet_reorg_source(s, co + 2, H, W, C)] = v[2];
+                img[darknet_reorg_source(s, co + 3, H, W, C)] = v[3];
+            } else {
+                img[darknet_reorg_source(s, co, H, W, C)] = *src;
+            }
+        }
+    }
+}
+
 // Darknet's network input from this repository's uint8 BGR batches: dst[p][c] = float(src[p][2 - c]) / 255.0f, a true
 // division (bit-equal to numpy's float32 quotient).  VEC4: a lane converts four pixels, three dwords in, three 16-byte
 // stores out; the entry point sends the pixels behind the last whole group of four to the scalar form.
@@ -826,6 +870,37 @@ int y2_passthrough_concat_darknet(const float* fine, const float* coarse, float*
     else hipLaunchKernelGGL(passthrough_concat_darknet_kernel<1>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
                             fine, coarse, out, N, H, W, Cf, Cc);
     EXTCHK(hipGetLastError());
+    return Y2_OK;
+}
+
+int y2_passthrough_concat_darknet_backward(const float* dout, float* dfine, float* dcoarse, int N, int H, int W, int Cf,
+                                           int Cc, void* stream) {
+    if (!dout || !dfine || !dcoarse) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: null tensor");
+    if (N < 1 || H < 1 || W < 1 || Cf < 1 || Cc < 1)
+        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: N = %d, H = %d, W = %d, Cf = %d, Cc = %d must be "
+                    "positive", N, H, W, Cf, Cc);
+    if (Cf % 4) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: Cf = %d is no multiple of 4 (Darknet's "
+                            "reorg reads the fine map as [Cf / 4][4 H][4 W])", Cf);
+    // the forward entry point's bounds: the index arithmetic of one image of dfine is 32-bit
+    if ((long long)16 * H * W * Cf > 0x7fffffffLL || (long long)4 * Cf + Cc > 0x7fffffffLL)
+        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: an image of %d x %d x %d is beyond 32-bit indices",
+                    2 * H, 2 * W, Cf);
+    const bool vec = (Cc % 4) == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)dcoarse % 16) == 0;
+    const size_t total = (size_t)N * H * W * ((size_t)(4 * Cf + Cc) / (vec ? 4 : 1));
+    size_t nb = (total + 255) / 256;
+    if (nb > 65536) nb = 65536;
+    if (vec) hipLaunchKernelGGL(darknet_route_backward_kernel<4>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                                dout, dfine, dcoarse, N, H, W, Cf, Cc);
+    else hipLaunchKernelGGL(darknet_route_backward_kernel<1>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                            dout, dfine, dcoarse, N, H, W, Cf, Cc);
+    EXTCHK(hipGetLastError());
+    return Y2_OK;
+}
+
+int y2_zero(float* x, size_t n, void* stream) {
+    if (!x) return fail(Y2_ERR_ARG, "y2_zero: null tensor");
+    if (n == 0) return Y2_OK;
+    EXTCHK(hipMemsetAsync(x, 0, n * sizeof(float), (hipStream_t)stream));
     return Y2_OK;
 }
 

@@ -804,7 +804,7 @@ def passthrough_concat(fine, coarse):
 
 def passthrough_concat_darknet(fine, coarse, out=None):
     """Darknet's passthrough (utils/darknet_reorg.passthrough_concat_darknet): concat(Darknet's reorg of fine
-    [N,2H,2W,Cf], coarse [N,H,W,Cc]) -> [N,H,W,4*Cf+Cc], one launch, forward only"""
+    [N,2H,2W,Cf], coarse [N,H,W,Cc]) -> [N,H,W,4*Cf+Cc], one launch (gradient: passthrough_concat_darknet_backward)"""
     lib = _lib.load()
     n, h, w, cc = coarse.shape
     cf = fine.shape[3]
@@ -838,6 +838,32 @@ def passthrough_concat_backward(dout, cf):
     dcoarse = torch.empty((n, h, w, cc), dtype=torch.float32, device=dout.device)
     check(lib.y2_passthrough_concat_backward(_ptr(dout), _ptr(dfine), _ptr(dcoarse), n, h, w, cf, cc, _stream()))
     return dfine, dcoarse
+
+
+def passthrough_concat_darknet_backward(dout, cf, dfine_out=None, dcoarse_out=None):
+    """the gradient of passthrough_concat_darknet (utils/darknet_reorg.passthrough_concat_darknet_backward): dout
+    [N,H,W,4*cf+Cc] -> (dfine [N,2H,2W,cf], dcoarse [N,H,W,Cc]), one launch that writes every element of both once"""
+    lib = _lib.load()
+    assert dout.is_cuda and dout.dtype == torch.float32 and dout.is_contiguous() and dout.dim() == 4
+    n, h, w, ct = dout.shape
+    cf = int(cf)
+    cc = ct - 4 * cf
+    if dfine_out is None:
+        dfine_out = torch.empty((n, 2 * h, 2 * w, cf), dtype=torch.float32, device=dout.device)
+    if dcoarse_out is None:
+        dcoarse_out = torch.empty((n, h, w, max(cc, 0)), dtype=torch.float32, device=dout.device)
+    for t, count in ((dfine_out, n * 4 * h * w * cf), (dcoarse_out, n * h * w * cc)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == max(count, 0)
+    check(lib.y2_passthrough_concat_darknet_backward(_ptr(dout), _ptr(dfine_out), _ptr(dcoarse_out), n, h, w, cf, cc,
+                                                     _stream()))
+    return dfine_out, dcoarse_out
+
+
+def zero_(x):
+    """x[:] = 0 on a contiguous fp32 device tensor or view (gradient masks of a trainer)"""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    check(_lib.load().y2_zero(_ptr(x), x.numel(), _stream()))
+    return x
 
 
 def add_relu(a, b):

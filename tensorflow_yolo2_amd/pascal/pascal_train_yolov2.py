@@ -1,6 +1,7 @@
 """Train the YOLOv2 anchor detector (yolo2_nets/yolov2.py; not in the reference, whose trainer is the grid model) on VOC:
     python -m tensorflow_yolo2_amd.pascal.pascal_train_yolov2 --devkit data/VOCdevkit --iters 20 \
         [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR | --darknet-backbone FILE]
+        [--topology paper|darknet] [--darknet-weights FILE]
         [--box-labels [--max-boxes 30] [--area-weight] [--prior-images 12800]]
         [--solver darknet [--lr .001] [--momentum .9] [--decay .0005] [--burn-in 1000] [--power 4]
                           [--policy steps --steps 40000,60000 --scales .1,.1 | --policy poly --max-batches N | --policy constant]]
@@ -29,6 +30,14 @@ the Darknet-19 backbone from the latest classifier snapshot there, and --darknet
 (darknet19_448.conv.23; net_utils.read_darknet_backbone): the trainer then runs batch-norm epsilon 1e-6, which its
 snapshots record (yolov2/bn_eps) and a resumed run takes from them.  --anchors kmeans clusters the image set's boxes
 (utils/anchors.py) instead of using the published VOC anchors; a resumed run keeps its snapshot's anchors.
+
+--topology darknet trains the graph of yolov2-voc.cfg instead (yolov2.YOLOv2DarknetTrainer): --darknet-weights FILE starts
+from a whole Darknet file (it implies the topology), --darknet-backbone FILE from the leading layers of a shorter one
+(net_utils.load_darknet_prefix: no first-layer fold, this graph takes Darknet's input).  Its snapshots are
+`train_iter_<i>.weights`, written by net_utils.save_darknet_weights with seen = i * batch, which Darknet and
+pascal_eval_yolov2 --darknet-weights read; a run with --ckpt-dir resumes from the latest at iteration seen // batch and
+moves the data as above.  A .weights file carries no optimizer state and no anchors: the moments and the loss scale start
+afresh, as in Darknet, and the anchors are the flags'.  A --ckpt-dir that holds the other topology's snapshots is an error.
 
 One process, one GPU."""
 import argparse
@@ -66,6 +75,14 @@ def parse_args(argv=None):
     ap.add_argument("--darknet-backbone", default=None,
                     help="a Darknet .weights file to take the Darknet-19 backbone from (darknet19_448.conv.23); the trainer "
                          "then runs Darknet's batch-norm epsilon 1e-6; not with --imagenet-ckpt-dir")
+    ap.add_argument("--topology", default=None, choices=yolov2.TOPOLOGIES,
+                    help="paper (default): the graph of yolo2_nets/yolov2.py, .npz snapshots; darknet: the graph of "
+                         "yolov2-voc.cfg (YOLOv2DarknetTrainer), whose snapshots are train_iter_<i>.weights files Darknet "
+                         "reads -- such a file carries no optimizer state, so a resumed run starts the moments and the loss "
+                         "scale afresh, as Darknet does, and takes the iteration from the file's `seen` / --batch")
+    ap.add_argument("--darknet-weights", default=None,
+                    help="start from a whole Darknet .weights file (yolov2-voc.weights); implies --topology darknet; not "
+                         "with --darknet-backbone or --imagenet-ckpt-dir")
     ap.add_argument("--anchors", default="voc", choices=("voc", "kmeans"),
                     help="voc: the published VOC anchors; kmeans: cluster the image set's boxes at --size")
     ap.add_argument("--box-labels", action="store_true", help="train on the box list (every object), not the label grid")
@@ -93,6 +110,16 @@ def parse_args(argv=None):
         ap.error("--batch, --save-every and --width-div must be at least 1, --iters at least 0")
     if args.darknet_backbone and args.imagenet_ckpt_dir:
         ap.error("--darknet-backbone and --imagenet-ckpt-dir name two backbones: give one")
+    if args.darknet_weights:
+        if args.darknet_backbone or args.imagenet_ckpt_dir:
+            ap.error("--darknet-weights holds the whole model: not with --darknet-backbone or --imagenet-ckpt-dir")
+        if args.topology == "paper":
+            ap.error("--darknet-weights is a file of the darknet topology: not with --topology paper")
+        args.topology = "darknet"
+    if args.topology is None:
+        args.topology = "paper"
+    if args.topology == "darknet" and args.imagenet_ckpt_dir:
+        ap.error("--imagenet-ckpt-dir feeds the paper topology; with --topology darknet give --darknet-backbone FILE")
     try:
         args.ms_sizes = tuple(int(v) for v in str(args.ms_sizes).split(",") if v.strip())
     except ValueError:
@@ -168,11 +195,19 @@ def main(argv=None):
     imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
                      seed=args.seed, augment=args.augmentation, max_boxes=args.max_boxes if args.box_labels else None)
     latest = None
+    darknet = args.topology == "darknet"
     if args.ckpt_dir:
         os.makedirs(args.ckpt_dir, exist_ok=True)
-        sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
+        npz, dkw = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir), net_utils.get_ordered_darknet_ckpts(args.ckpt_dir)
+        if (dkw if not darknet else npz):
+            raise ValueError("--ckpt-dir %s holds snapshots of the %s topology (%s); this run trains the %s topology, whose "
+                             "snapshots are %s files" % ((args.ckpt_dir, "paper", os.path.basename(npz[-1]), "darknet",
+                                                          ".weights") if darknet else
+                                                         (args.ckpt_dir, "darknet", os.path.basename(dkw[-1]), "paper",
+                                                          ".npz")))
+        sfiles = dkw if darknet else npz
         latest = sfiles[-1] if sfiles else None
-    if latest:
+    if latest and not darknet:
         anchors = net_utils.read_yolov2_meta(latest)[0]
     elif args.anchors == "kmeans":
         from ..utils import anchors as A
@@ -186,13 +221,27 @@ def main(argv=None):
     first = step_size(args, 1) if args.multi_scale else args.size
     # Darknet's layers were trained with its batch-norm epsilon; a resumed run keeps its snapshot's (yolov2/bn_eps)
     bn_eps = yolov2.DARKNET_BN_EPS if args.darknet_backbone else None
-    if latest and bn_eps is None:
+    if latest and bn_eps is None and not darknet:
         bn_eps = net_utils.read_yolov2_bn_eps(latest)
-    trainer = yolov2.YOLOv2Trainer(args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
-                                   seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
-                                   prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps)
+    make = yolov2.YOLOv2DarknetTrainer if darknet else yolov2.YOLOv2Trainer
+    trainer = make(args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
+                   seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
+                   prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps)
     last_iter_num = 0
-    if latest:
+    if darknet:
+        # a .weights file is the whole snapshot: parameters, moving statistics and `seen`, no optimizer state
+        if latest:
+            print('Restorining model snapshots from {:s}'.format(latest))
+            last_iter_num = net_utils.load_darknet_weights(trainer, latest) // args.batch
+            trainer.resume_at(last_iter_num)
+            skip_batches(imdb, last_iter_num)
+        elif args.darknet_weights:
+            seen = net_utils.load_darknet_weights(trainer, args.darknet_weights)
+            print('Model restored from Darknet weight file {:s} ({:d} images seen)'.format(args.darknet_weights, seen))
+        elif args.darknet_backbone:
+            n = net_utils.load_darknet_prefix(trainer, args.darknet_backbone)
+            print('{:d} layers restored from Darknet weight file {:s}'.format(n, args.darknet_backbone))
+    elif latest:
         print('Restorining model snapshots from {:s}'.format(latest))
         last_iter_num = net_utils.restore_yolov2_variables(trainer, latest)
         skip_batches(imdb, last_iter_num)
@@ -230,8 +279,12 @@ def main(argv=None):
                                                                                         float(losses[-1][4]), rate, _time))
             T.tic()
         if args.ckpt_dir and (i % args.save_every == 0 or i == TOTAL_ITER):
-            save_path = os.path.join(args.ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) + '.npz')
-            net_utils.save_yolov2_variables(trainer, save_path, iteration=i)
+            save_path = os.path.join(args.ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) +
+                                     ('.weights' if darknet else '.npz'))
+            if darknet:
+                net_utils.save_darknet_weights(trainer, save_path, seen=i * args.batch)
+            else:
+                net_utils.save_yolov2_variables(trainer, save_path, iteration=i)
             print("Model saved in file: %s" % save_path)
     torch.cuda.synchronize()
     return {"losses": losses, "last_iter": TOTAL_ITER, "first_iter": last_iter_num + 1, "trainer": trainer,

@@ -8,7 +8,11 @@ to apply it.
 
 `reorg_darknet_chw` is the loop form, as Darknet writes it; `reorg_darknet` is the same map per image in this
 repository's NHWC through ONE vectorised index table (`reorg_darknet_table`).  tests/test_darknet_weights_host.py holds
-the two equal element for element."""
+the two equal element for element.
+
+The map is a permutation of each image's values, so its gradient is the inverse permutation: `reorg_darknet_backward`
+and `passthrough_concat_darknet_backward`, written from the same table, are the specification of
+y2_passthrough_concat_darknet_backward (tests/test_darknet_train_host.py)."""
 import numpy as np
 
 
@@ -57,3 +61,32 @@ def reorg_darknet(fine):
 def passthrough_concat_darknet(fine, coarse):
     """route layers=-1,-4 of yolov2-voc.cfg: the reorganised fine map in channels 0 .. 4 Cf - 1, coarse behind it"""
     return np.concatenate([reorg_darknet(fine), np.asarray(coarse)], axis=-1)
+
+
+def reorg_darknet_backward(dout):
+    """dout [N][H/2][W/2][4C] -> the gradient [N][H][W][C] of reorg_darknet's input.  The reorg is a permutation of each
+    image's values (the table is a bijection), so its gradient is the inverse permutation: every row of the index table
+    names the ONE input element an output element was read from, and that element receives the output's gradient.
+    Written from the table as a scatter through unique indices -- the specification of the reorganised part of
+    y2_passthrough_concat_darknet_backward."""
+    dout = np.asarray(dout)
+    n, Ho, Wo, C4 = dout.shape
+    if C4 % 16:
+        raise ValueError("reorg_darknet_backward: %d channels are not 4 C with C %% 4 == 0" % C4)
+    H, W, C = 2 * Ho, 2 * Wo, C4 // 4
+    js, is_, cs = reorg_darknet_table(H, W, C)
+    flat = ((js * W + is_) * C + cs).reshape(-1)         # the input element of every output element, per image
+    if np.unique(flat).size != H * W * C:
+        raise AssertionError("reorg_darknet_table is no permutation at H %d, W %d, C %d" % (H, W, C))
+    din = np.empty((n, H * W * C), dout.dtype)
+    din[:, flat] = dout.reshape(n, -1)
+    return din.reshape(n, H, W, C)
+
+
+def passthrough_concat_darknet_backward(dout, cf):
+    """dout [N][H][W][4 cf + Cc] -> (dfine [N][2H][2W][cf], dcoarse [N][H][W][Cc]): the split at channel 4 cf, the front
+    part through reorg_darknet_backward"""
+    dout = np.asarray(dout)
+    if dout.ndim != 4 or cf < 4 or cf % 4 or dout.shape[3] <= 4 * cf:
+        raise ValueError("passthrough_concat_darknet_backward: dout %s does not split at 4 * %d" % (dout.shape, cf))
+    return reorg_darknet_backward(dout[..., :4 * cf]), np.ascontiguousarray(dout[..., 4 * cf:])

@@ -613,6 +613,13 @@ def get_ordered_yolov2_ckpts(ckpt_dir):
     return [f for _i, f in sorted(numbered)]
 
 
+def get_ordered_darknet_ckpts(ckpt_dir):
+    """`train_iter_<i>.weights` files of ckpt_dir (the "darknet" topology's snapshots) by iteration number, oldest first"""
+    files = glob.glob(os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + "_iter_*.weights"))
+    numbered = [(int(m.group(1)), f) for f in files for m in [re.search(r"_iter_(\d+)\.weights$", f)] if m]
+    return [f for _i, f in sorted(numbered)]
+
+
 def read_darknet19_core(path):
     """the 18 core layers (dicts of the six arrays) of a Darknet-19 classifier or detector snapshot of this package
     (.npz or TF V2 checkpoint): what load_darknet19_backbone takes"""
@@ -651,15 +658,17 @@ def load_darknet19_backbone(model, core_layers):
 # Darknet's `.weights` files (utils/darknet_weights.py holds the format and the per-layer arithmetic, numpy only).
 # load_darknet_weights / save_darknet_weights: a YOLOv2Detector(topology="darknet"), whose four stacks in networks()
 # order are the file's convolutions in cfg order.  read_darknet_backbone: the 18 Darknet-19 layers of any such file
-# (darknet19_448.conv.23) for the paper-topology trainer, through load_darknet19_backbone.
+# (darknet19_448.conv.23) for the paper-topology trainer, through load_darknet19_backbone.  A YOLOv2DarknetTrainer has
+# the same four stacks in networks() order and is taken wherever the detector is; load_darknet_prefix fills the leading
+# layers of either from a shorter file, without a fold.
 # ---------------------------------------------------------------------------
 from ..utils import darknet_weights as _dkw
 
 
 def _darknet_model(model, what):
     if getattr(model, "topology", "paper") != "darknet":
-        raise ValueError("%s takes a YOLOv2Detector(topology=\"darknet\"): the paper topology's graph is not the one a "
-                         "Darknet file holds" % what)
+        raise ValueError("%s takes a YOLOv2Detector(topology=\"darknet\") or a YOLOv2DarknetTrainer: the paper topology's "
+                         "graph is not the one a Darknet file holds" % what)
     return model.networks()
 
 
@@ -708,7 +717,49 @@ def load_darknet_weights(model, path):
                                      (path, pos + l, k, tuple(p[k].shape), _describe(model), tuple(shape)))
         net.load_params(params)
         pos += net.num_layers
+    _all_sizes_changed(model)
     return seen
+
+
+def _all_sizes_changed(model):
+    """a trainer's multi-scale contexts share the parameters just written: every size re-packs its filters"""
+    if hasattr(model, "params_changed"):
+        model.params_changed()
+
+
+def load_darknet_prefix(model, path):
+    """the leading convolutions of a SHORTER Darknet file (darknet19_448.conv.23: the 18 core layers) into a
+    "darknet"-topology model, detector or trainer -> the number of layers read.  The arithmetic of load_darknet_weights
+    per layer and NO first-layer fold: this graph takes Darknet's input, so the import is exact on the border ring too
+    (read_darknet_backbone, for the paper topology, is not).  The layers behind the prefix keep their values.  A file
+    that ends inside a layer, holds more than the model or holds no layer at all raises."""
+    nets = _darknet_model(model, "load_darknet_prefix")
+    file_layers = darknet_file_layers(model)
+    values = _dkw.read(path)[4]
+    try:
+        layers, _used = _dkw.split(values, file_layers)
+    except ValueError as e:
+        raise ValueError("%s holds %d floats, no whole-layer prefix of the model (%s: %d convolutions): %s" %
+                         (path, values.size, _describe(model), len(file_layers), e))
+    if not layers:
+        raise ValueError("%s holds no convolution" % path)
+    pos = 0
+    for net in nets:
+        take = min(net.num_layers, len(layers) - pos)
+        if take <= 0:
+            break
+        params = net.export_params()
+        for l in range(take):
+            p = _dkw.to_layer_params(layers[pos + l], net.spec[l][0], model.bn_eps)
+            for k, shape in net._shapes(l).items():
+                if tuple(p[k].shape) != tuple(shape):
+                    raise ValueError("%s: convolution %d %s has shape %s, the model (%s) expects %s" %
+                                     (path, pos + l, k, tuple(p[k].shape), _describe(model), tuple(shape)))
+            params[l] = p
+        net.load_params(params)
+        pos += take
+    _all_sizes_changed(model)
+    return len(layers)
 
 
 def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):

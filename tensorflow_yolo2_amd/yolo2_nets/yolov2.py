@@ -7,7 +7,8 @@ so the three stacks are `engine.Network` contexts; the glue ops are csrc/ext.hip
 `YOLOv2Detector` is the inference graph, `YOLOv2Trainer` the train step: anchor-box loss (csrc/ext.hip
 yolov2_loss_kernel, specification oracle/ext_ref.py), backward through the head, the passthrough concat, the
 13x13 stack, the 2x2 pool and the stem, Adam (or, with `solver`, Darknet's SGD: utils/solver.py) on the three flat
-parameter buffers, optional multi-scale.
+parameter buffers, optional multi-scale.  `YOLOv2DarknetTrainer` is the train step of the "darknet" topology, the graph
+of yolov2-voc.cfg: four stacks, Darknet's reorg and its gradient, a last layer without batch statistics.
 """
 import numpy as np
 import torch
@@ -168,8 +169,8 @@ class YOLOv2Trainer:
             if topology not in TOPOLOGIES:
                 raise ValueError("topology %r: one of %s" % (topology, ", ".join(TOPOLOGIES)))
             raise NotImplementedError("YOLOv2Trainer trains the paper topology only: the %r graph needs the gradient of "
-                                      "Darknet's reorg, a fourth optimizer and a last layer without batch statistics" %
-                                      topology)
+                                      "Darknet's reorg, a fourth optimizer and a last layer without batch statistics -- "
+                                      "YOLOv2DarknetTrainer has them" % topology)
         # the batch-norm epsilon of every context and size (None: the contexts' default, 1e-3); 1e-6 is Darknet's, the one
         # a backbone read from a Darknet file was trained with (net_utils.read_darknet_backbone)
         self.topology, self.bn_eps = topology, None if bn_eps is None else float(bn_eps)
@@ -307,6 +308,233 @@ class YOLOv2Trainer:
         size = size or self.default_size
         tot = 0.0
         for spec, h0 in zip(self.specs, (size, size // 32, size // 32)):
+            h = h0
+            for (k, ci, co, pool) in spec:
+                if not (mfma_launches_only and ci == 3):
+                    tot += 2.0 * self.batch * h * h * k * k * ci * co
+                if pool:
+                    h = (h + 1) // 2
+        return 3.0 * tot
+
+
+DARKNET_1X1_CORE_LAYER = 3       # Darknet-19's fourth convolution: 1x1 in the file, 3x3 with a centre tap in this graph
+
+
+class YOLOv2DarknetTrainer:
+    """Train step of the yolov2-voc.cfg graph (YOLOv2Detector(topology="darknet")): what a Darknet `.weights` file holds
+    can be fine-tuned here and written back (net_utils.load_darknet_weights / load_darknet_prefix / save_darknet_weights
+    take this object).  YOLOv2Trainer's constructor arguments and step() contract; FOUR stacks in file order -- stem,
+    13x13 stack, the 1x1 route convolution, head -- each with its flat buffers, optimizer and gradient reducer, ONE loss
+    scaler, step counter and rate; the multi-scale contexts share the four parameter sets.
+
+    Differences from YOLOv2Trainer: Darknet's input (uint8 BGR batches through engine.u8_to_darknet_input; float input
+    is RGB in [0, 1]); the route stack and Darknet's reorg (engine.passthrough_concat_darknet and its gradient, the
+    reorganised map in FRONT); batch-norm epsilon 1e-6; moving variances on the n - 1 estimate (bessel; the
+    normalisation itself stays on the biased variance: a known difference from Darknet); and a last layer that is
+    linear and runs WITHOUT batch statistics -- the head context has core_layers = 1, its 1x1 layer normalises with the
+    identity moving statistics the importer writes and its gamma / beta gradients are zeroed every step, so those four
+    arrays never move and the export folds exactly 1.  The eight off-centre taps of core layer 3 (Darknet's 1x1) get a
+    zero gradient every step too: they stay exactly zero and the model stays writable."""
+
+    topology = "darknet"
+
+    def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
+                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
+                 solver=None, bn_eps=None, topology="darknet"):
+        if topology != "darknet":
+            raise ValueError("YOLOv2DarknetTrainer trains the \"darknet\" topology; topology %r is YOLOv2Trainer's" %
+                             (topology,))
+        self.bn_eps = DARKNET_BN_EPS if bn_eps is None else float(bn_eps)
+        from ..trainer import GradReducer
+        self._GradReducer = GradReducer
+        self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
+        self.anchors = np.asarray(anchors, np.float32)
+        self.B = len(self.anchors)
+        self.scales = scales
+        self.area_weight, self.prior_images, self.prior_scale = bool(area_weight), int(prior_images), float(prior_scale)
+        self.iteration = 0
+        self.solver = solver.validate() if solver is not None else None
+        self.specs = yolov2_darknet_specs(num_class, self.B, width_div)
+        self.cf = self.specs[2][-1][2]                       # the route's width: what the reorg scrambles
+        self.ctx, self.reducers, self._buffers = {}, {}, {}
+        self.opts = None
+        self.default_size = image_size
+        self._nets(image_size)
+
+    def _nets(self, size):
+        if size not in self.ctx:
+            assert size % 32 == 0
+            S = size // 32
+            first = next(iter(self.ctx.values())) if self.ctx else None
+            sa, sb, sr, sc = self.specs
+            # the head trains its 3x3 layer on batch statistics and runs the last layer on its moving ones (core_layers 1)
+            mk = lambda i, spec, h, core: E.Network(spec, self.batch, h, h, dtype=self.dtype, core_layers=core,
+                                                    training=True, device=self.device, bessel=True,
+                                                    share_with=first[i] if first else None)
+            nets = (mk(0, sa, size, None), mk(1, sb, S, None), mk(2, sr, 2 * S, None), mk(3, sc, S, 1))
+            for net in nets:
+                net.set_layer_options(slopes=[0.1, 1.0] if net is nets[3] else None, bn_eps=self.bn_eps)
+            if first is None:
+                for i, net in enumerate(nets):
+                    net.init_params(self.seed + i)
+                self._init_darknet_form(nets)
+                if self.solver is None:
+                    self.opts = [E.AdamOptimizer(net) for net in nets]
+                else:
+                    self.opts = [E.DarknetSGD(net, self.solver) for net in nets]
+                for opt in self.opts[1:]:
+                    opt.scaler = self.opts[0].scaler          # one scale, overflow flag and step counter for the graph
+            self.ctx[size] = nets
+            self.reducers[size] = [self._GradReducer(net) for net in nets]
+            dev = nets[0].device
+            self._buffers[size] = (torch.empty((self.batch, size, size, 3), dtype=torch.float32, device=dev),
+                                   torch.empty((self.batch, S, S, sc[0][1]), dtype=torch.float32, device=dev))
+        return self.ctx[size]
+
+    def _init_darknet_form(self, nets):
+        """a fresh model in the form a `.weights` file can hold: the 1x1 layer's off-centre taps zero, the last layer's
+        batch norm the importer's identity (utils/darknet_weights.to_layer_params)"""
+        stem, head = nets[0], nets[3]
+        params = stem.export_params()
+        W = params[DARKNET_1X1_CORE_LAYER]["W"]
+        centre = W[1, 1].copy()
+        W[...] = 0
+        W[1, 1] = centre
+        stem.load_params(params)
+        params = head.export_params()
+        n = params[-1]["b"].size
+        params[-1].update(gamma=np.full(n, np.sqrt(1.0 + np.float64(self.bn_eps)), np.float32),
+                          beta=np.zeros(n, np.float32), moving_mean=np.zeros(n, np.float32),
+                          moving_var=np.ones(n, np.float32))
+        head.load_params(params)
+
+    @property
+    def nets(self):
+        return self.ctx[self.default_size]
+
+    def networks(self, size=None):
+        """the four stack contexts (stem, 13x13 stack, route, head) of an input size: the order of a `.weights` file"""
+        return self._nets(size or self.default_size)
+
+    def params_changed(self):
+        """the shared parameters were written from outside (a file was loaded): every size's contexts re-pack"""
+        for nets in self.ctx.values():
+            for net in nets:
+                net.params_changed()
+
+    def resume_at(self, iteration):
+        """continue a run whose `.weights` snapshot stood at `iteration` (seen // batch): the step count the prior term
+        reads and, under Darknet's solver, the position in the rate schedule -- Darknet derives both from `seen`.  A
+        `.weights` file carries no optimizer state: moments and the loss scale start afresh, as in Darknet"""
+        self.iteration = int(iteration)
+        if self.solver is not None:
+            for opt in self.opts:
+                opt.t = self.iteration
+            scaler = self.opts[0].scaler
+            if scaler is not None:
+                c = scaler.ctrl.cpu()
+                c[1] = self.iteration
+                scaler.ctrl.copy_(c)
+
+    prior_on = YOLOv2Trainer.prior_on
+    box_scales = YOLOv2Trainer.box_scales
+
+    def forward(self, images, training=True, update_moving=False):
+        """images [N,size,size,3] uint8 BGR pixels or fp32 RGB in [0, 1] -> (raw grid [N,S,S,B,5+C], fine [N,2S,2S,Cf]);
+        the last layer runs on its moving statistics in either mode"""
+        size = int(images.shape[1])
+        stem, deep, route, head = self._nets(size)
+        S = size // 32
+        x_buf, cat_buf = self._buffers[size]
+        if images.dtype == torch.uint8:
+            images = E.u8_to_darknet_input(images, out=x_buf)
+        fine = stem.forward(images, training, training, update_moving=update_moving)              # [N,2S,2S,Cf]
+        coarse = deep.forward(E.max_pool_2x2(fine), training, training, update_moving=update_moving)
+        r = route.forward(fine, training, training, update_moving=update_moving)                  # [N,2S,2S,64]
+        cat = E.passthrough_concat_darknet(r, coarse, out=cat_buf)                                # [N,S,S,256+Cc]
+        out = head.forward(cat, training, False, update_moving=update_moving)
+        return out.view(self.batch, S, S, self.B, 5 + self.num_class), fine
+
+    def backward(self, dnet, fine, size):
+        """the whole backward pass of the forward(training) just run at `size`, from the head's output gradient `dnet`:
+        gradients into the four flat buffers, reduced over the replicas and masked.  Returns the world size.
+        last_dcat / last_dfine keep the gradients at the concat and at the fine map (tests read them)."""
+        from ..trainer import _dist
+        stem, deep, route, head = self._nets(size)
+        S = size // 32
+        dist = _dist()
+        red = self.reducers[size]
+        dcat = head.backward_input(dnet.view(self.batch, S, S, -1))
+        if dist is not None:
+            red[3].reduce_all_async()
+        droute, dcoarse = E.passthrough_concat_darknet_backward(dcat, self.cf)
+        dpooled = deep.backward_input(dcoarse)
+        if dist is not None:
+            red[1].reduce_all_async()
+        dfine = route.backward_input(droute)
+        if dist is not None:
+            red[2].reduce_all_async()
+        E.accumulate(dfine, E.max_pool_2x2_backward(fine, dpooled))
+        self.last_dcat, self.last_dfine = dcat, dfine
+        world = red[0].backward_and_reduce(dfine)
+        if dist is not None:
+            red[1].join(); red[2].join(); red[3].join()
+        return world
+
+    def _mask_gradients(self, stem, head):
+        """after the all-reduce, before the optimizers: no gradient for the eight off-centre taps of Darknet's 1x1 layer
+        nor for the last layer's gamma / beta"""
+        gW = stem.layer_views(DARKNET_1X1_CORE_LAYER, grads=True)["W"]
+        taps = gW.view(9, -1)
+        E.zero_(taps[:4])
+        E.zero_(taps[5:])
+        g = head.layer_views(head.num_layers - 1, grads=True)
+        E.zero_(g["gamma"])
+        E.zero_(g["beta"])
+
+    def step(self, images, labels=None, truth=None, ntruth=None):
+        """YOLOv2Trainer.step's contract: one train step on the label grid or on the box list -> loss[5]"""
+        if (labels is None) == (truth is None) or (truth is None) != (ntruth is None):
+            raise ValueError("step() takes either labels or truth + ntruth, not both and not neither")
+        size = int(images.shape[1])
+        nets = self._nets(size)
+        if len(self.ctx) > 1:
+            for net in nets:
+                net.params_changed()              # shared parameters moved under another size's contexts
+        self.iteration += 1
+        grid, fine = self.forward(images, True, update_moving=True)
+        if labels is not None:
+            loss, dnet = E.yolov2_loss(grid.contiguous(), labels, self.anchors, size, True, self.scales)
+        else:
+            loss, dnet = E.yolov2_loss_boxes(grid.contiguous(), truth, ntruth, self.anchors, size, True,
+                                             self.box_scales(self.iteration))
+        self.last_dnet = dnet
+        world = self.backward(dnet, fine, size)
+        scaler = self.opts[0].scaler
+        for opt, net in zip(self.opts, nets):
+            opt.net = net
+            if scaler is not None:
+                scaler.attach(net)
+        if scaler is None:
+            self._mask_gradients(nets[0], nets[3])
+            for opt in self.opts:
+                opt.step(grad_mult=1.0 / world)
+            return loss
+        # every stack's sentinels into the one flag (on the gradients as the backward pass left them), the masks, then
+        # the four guarded updates: all of them or none
+        for i, net in enumerate(nets):
+            scaler.scan(net, more=(i > 0))
+        self._mask_gradients(nets[0], nets[3])
+        for i, opt in enumerate(self.opts):
+            opt.step(grad_mult=1.0 / world, joint="first" if i == 0 else "next")
+        return loss
+
+    def flops_per_step(self, size=None, mfma_launches_only=False):
+        """YOLOv2Trainer.flops_per_step over the four stacks"""
+        size = size or self.default_size
+        S = size // 32
+        tot = 0.0
+        for spec, h0 in zip(self.specs, (size, S, 2 * S, S)):
             h = h0
             for (k, ci, co, pool) in spec:
                 if not (mfma_launches_only and ci == 3):
