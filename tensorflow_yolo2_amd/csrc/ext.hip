@@ -740,83 +740,78 @@ Y2_DEV int darknet_reorg_source(int s, int co, int H, int W, int C) {
     return (js * W + is) * C + 4 * c2 + t;
 }
 
-template <int VEC>
-__global__ __launch_bounds__(256) void passthrough_concat_darknet_kernel(const float* __restrict__ fine,
-                                                                         const float* __restrict__ coarse,
-                                                                         float* __restrict__ out, int N, int Ho, int Wo,
-                                                                         int C, int Cc) {
-    const int H = 2 * Ho, W = 2 * Wo, ld = 4 * C + Cc;
-    const int ldv = ld / VEC;
-    const size_t image = (size_t)H * W * C;
-    const size_t total = (size_t)N * Ho * Wo * ldv;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int co = (int)(e % ldv) * VEC;
-        const size_t pix = e / ldv;                  // n * Ho * Wo + s
-        const int s = (int)(pix % ((size_t)Ho * Wo));
-        const size_t n = pix / ((size_t)Ho * Wo);
-        float* dst = out + pix * ld + co;
-        if (co >= 4 * C) {
-            const float* src = coarse + pix * Cc + (co - 4 * C);
-            if (VEC == 4) *(f32x4*)dst = *(const f32x4*)src;
-            else *dst = *src;
-        } else {
-            const float* img = fine + n * image;
-            if (VEC == 4) {
-                f32x4 v;
-                v[0] = img[darknet_reorg_source(s, co + 0, H, W, C)];
-                v[1] = img[darknet_reorg_source(s, co + 1, H, W, C)];
-                v[2] = img[darknet_reorg_source(s, co + 2, H, W, C)];
-                v[3] = img[darknet_reorg_source(s, co + 3, H, W, C)];
-                *(f32x4*)dst = v;
-            } else {
-                *dst = img[darknet_reorg_source(s, co, H, W, C)];
-            }
-        }
-    }
-}
-
 // The gradient of Darknet's passthrough (specification: utils/darknet_reorg.passthrough_concat_darknet_backward).  The
 // reorg is a permutation of each image, so its gradient is the inverse permutation: dfine[darknet_reorg_source(s, co)] =
 // dout[s][co], every element of dfine named exactly once.  ONE launch writes both outputs, every element exactly once,
-// with no zero fill and no atomics.  This is the SCATTER form, the forward kernel with loads and stores exchanged: a lane
+// with no zero fill and no atomics.  This is the SCATTER form, the forward walk with loads and stores exchanged: a lane
 // owns VEC consecutive channels of one dout pixel (VEC = 4: one 16-byte load), then makes one 16-byte store into dcoarse
 // or four 4-byte stores into dfine -- the lane beside it (k + 1) writes 16 bytes further in the same four pixel rows, so a
 // wave's stores fill whole 256-byte rows of dfine between them.  The gather form (a lane owns four channels of a dfine
 // pixel, one 16-byte store, four 4-byte loads through the closed-form inverse of darknet_reorg_source) is the same
 // function and measured 7 % slower at S = 13 and 19 (scripts/probes/darknet_route_backward_ab.hip holds both forms and
 // the inverse with its derivation), so it is not in the library.  VEC = 1: Cc % 4 != 0 or a pointer off 16 bytes.
+//
+// Both directions are ONE walk over the concatenated tensor `cat` [N,Ho,Wo,4*C+Cc]: BACKWARD = false reads fine and
+// coarse and writes cat (cat = out), BACKWARD = true reads cat (= dout) and writes fine (= dfine) and coarse (= dcoarse).
+// The direction is a template argument, so each of the two kernels below holds its own loads and stores only.  first /
+// stride: the grid-stride loop's start and step, (size_t)blockIdx.x * blockDim.x + threadIdx.x and (size_t)gridDim.x *
+// blockDim.x -- read in the kernels, where the compiler knows the workgroup size to be uniform (read here, every
+// instantiation gains 8 to 11 instructions that pick the size of a partial last workgroup).
+template <int VEC, bool BACKWARD>
+Y2_DEV void darknet_passthrough_walk(float* __restrict__ fine, float* __restrict__ coarse, float* __restrict__ cat, int N,
+                                     int Ho, int Wo, int C, int Cc, size_t first, size_t stride) {
+    const int H = 2 * Ho, W = 2 * Wo, ld = 4 * C + Cc;
+    const int ldv = ld / VEC;
+    const size_t image = (size_t)H * W * C;
+    const size_t total = (size_t)N * Ho * Wo * ldv;
+    for (size_t e = first; e < total; e += stride) {
+        const int co = (int)(e % ldv) * VEC;
+        const size_t pix = e / ldv;                  // n * Ho * Wo + s
+        const int s = (int)(pix % ((size_t)Ho * Wo));
+        const size_t n = pix / ((size_t)Ho * Wo);
+        float* slot = cat + pix * ld + co;
+        if (co >= 4 * C) {
+            float* part = coarse + pix * Cc + (co - 4 * C);
+            float* dst = BACKWARD ? part : slot;
+            const float* src = BACKWARD ? slot : part;
+            if (VEC == 4) *(f32x4*)dst = *(const f32x4*)src;
+            else *dst = *src;
+        } else {
+            float* img = fine + n * image;
+            if (VEC == 4) {
+                f32x4 v;
+                if (BACKWARD) v = *(const f32x4*)slot;
+                for (int q = 0; q < 4; ++q) {
+                    float* p = img + darknet_reorg_source(s, co + q, H, W, C);
+                    if (BACKWARD) *p = v[q];
+                    else v[q] = *p;
+                }
+                if (!BACKWARD) *(f32x4*)slot = v;
+            } else {
+                float* p = img + darknet_reorg_source(s, co, H, W, C);
+                if (BACKWARD) *p = *slot;
+                else *slot = *p;
+            }
+        }
+    }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void passthrough_concat_darknet_kernel(const float* __restrict__ fine,
+                                                                         const float* __restrict__ coarse,
+                                                                         float* __restrict__ out, int N, int Ho, int Wo,
+                                                                         int C, int Cc) {
+    darknet_passthrough_walk<VEC, false>(const_cast<float*>(fine), const_cast<float*>(coarse), out, N, Ho, Wo, C, Cc,
+                                         (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+}
+
 template <int VEC>
 __global__ __launch_bounds__(256) void darknet_route_backward_kernel(const float* __restrict__ dout,
                                                                      float* __restrict__ dfine,
                                                                      float* __restrict__ dcoarse, int N, int Ho, int Wo,
                                                                      int C, int Cc) {
-    const int H = 2 * Ho, W = 2 * Wo, ld = 4 * C + Cc;
-    const int ldv = ld / VEC;
-    const size_t image = (size_t)H * W * C;
-    const size_t total = (size_t)N * Ho * Wo * ldv;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int co = (int)(e % ldv) * VEC;
-        const size_t pix = e / ldv;                  // n * Ho * Wo + s
-        const int s = (int)(pix % ((size_t)Ho * Wo));
-        const size_t n = pix / ((size_t)Ho * Wo);
-        const float* src = dout + pix * ld + co;
-        if (co >= 4 * C) {
-            float* dst = dcoarse + pix * Cc + (co - 4 * C);
-            if (VEC == 4) *(f32x4*)dst = *(const f32x4*)src;
-            else *dst = *src;
-        } else {
-            float* img = dfine + n * image;
-            if (VEC == 4) {
-                const f32x4 v = *(const f32x4*)src;
-                img[darknet_reorg_source(s, co + 0, H, W, C)] = v[0];
-                img[darknet_reorg_source(s, co + 1, H, W, C)] = v[1];
-                img[darknet_reorg_source(s, co + 2, H, W, C)] = v[2];
-                img[darknet_reorg_source(s, co + 3, H, W, C)] = v[3];
-            } else {
-                img[darknet_reorg_source(s, co, H, W, C)] = *src;
-            }
-        }
-    }
+    darknet_passthrough_walk<VEC, true>(dfine, dcoarse, const_cast<float*>(dout), N, Ho, Wo, C, Cc,
+                                        (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 // Darknet's network input from this repository's uint8 BGR batches: dst[p][c] = float(src[p][2 - c]) / 255.0f, a true
@@ -847,54 +842,45 @@ __global__ __launch_bounds__(256) void u8_bgr_to_f32_rgb_kernel(const uint8_t* _
     }
 }
 
-extern "C" {
-
-int y2_passthrough_concat_darknet(const float* fine, const float* coarse, float* out, int N, int H, int W, int Cf, int Cc,
-                                  void* stream) {
-    if (!fine || !coarse || !out) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: null tensor");
+// The one launcher of the two Darknet passthrough entry points (`what`: the entry point's name, for its messages).  a, b, c
+// are the kernel's three tensors in its own order; wide_a and wide_b the two that move 16 bytes at a time: the coarse part
+// and the concatenated tensor.  The bounds: the index arithmetic of one image of the fine map is 32-bit -- 16 H W Cf
+// values, (4 Cf + Cc) channels.
+template <typename A, typename B, typename C>
+static int darknet_passthrough_launch(const char* what, void (*vec4)(A*, B*, C*, int, int, int, int, int),
+                                      void (*vec1)(A*, B*, C*, int, int, int, int, int), A* a, B* b, C* c,
+                                      const float* wide_a, const float* wide_b, int N, int H, int W, int Cf, int Cc,
+                                      void* stream) {
+    if (!a || !b || !c) return fail(Y2_ERR_ARG, "%s: null tensor", what);
     if (N < 1 || H < 1 || W < 1 || Cf < 1 || Cc < 1)
-        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: N = %d, H = %d, W = %d, Cf = %d, Cc = %d must be positive",
-                    N, H, W, Cf, Cc);
-    if (Cf % 4) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: Cf = %d is no multiple of 4 (Darknet's reorg "
-                            "reads the fine map as [Cf / 4][4 H][4 W])", Cf);
-    // the index arithmetic of one image is 32-bit: 16 H W Cf values of `fine`, (4 Cf + Cc) channels
+        return fail(Y2_ERR_ARG, "%s: N = %d, H = %d, W = %d, Cf = %d, Cc = %d must be positive", what, N, H, W, Cf, Cc);
+    if (Cf % 4) return fail(Y2_ERR_ARG, "%s: Cf = %d is no multiple of 4 (Darknet's reorg reads the fine map as "
+                            "[Cf / 4][4 H][4 W])", what, Cf);
     if ((long long)16 * H * W * Cf > 0x7fffffffLL || (long long)4 * Cf + Cc > 0x7fffffffLL)
-        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet: an image of %d x %d x %d is beyond 32-bit indices", 2 * H,
-                    2 * W, Cf);
-    const bool vec = (Cc % 4) == 0 && ((uintptr_t)coarse % 16) == 0 && ((uintptr_t)out % 16) == 0;
+        return fail(Y2_ERR_ARG, "%s: an image of %d x %d x %d is beyond 32-bit indices", what, 2 * H, 2 * W, Cf);
+    const bool vec = (Cc % 4) == 0 && ((uintptr_t)wide_a % 16) == 0 && ((uintptr_t)wide_b % 16) == 0;
     const size_t total = (size_t)N * H * W * ((size_t)(4 * Cf + Cc) / (vec ? 4 : 1));
     size_t nb = (total + 255) / 256;
     if (nb > 65536) nb = 65536;
-    if (vec) hipLaunchKernelGGL(passthrough_concat_darknet_kernel<4>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
-                                fine, coarse, out, N, H, W, Cf, Cc);
-    else hipLaunchKernelGGL(passthrough_concat_darknet_kernel<1>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
-                            fine, coarse, out, N, H, W, Cf, Cc);
+    hipLaunchKernelGGL(vec ? vec4 : vec1, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a, b, c, N, H, W, Cf, Cc);
     EXTCHK(hipGetLastError());
     return Y2_OK;
 }
 
+extern "C" {
+
+int y2_passthrough_concat_darknet(const float* fine, const float* coarse, float* out, int N, int H, int W, int Cf, int Cc,
+                                  void* stream) {
+    return darknet_passthrough_launch("y2_passthrough_concat_darknet", passthrough_concat_darknet_kernel<4>,
+                                      passthrough_concat_darknet_kernel<1>, fine, coarse, out, coarse, out, N, H, W, Cf, Cc,
+                                      stream);
+}
+
 int y2_passthrough_concat_darknet_backward(const float* dout, float* dfine, float* dcoarse, int N, int H, int W, int Cf,
                                            int Cc, void* stream) {
-    if (!dout || !dfine || !dcoarse) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: null tensor");
-    if (N < 1 || H < 1 || W < 1 || Cf < 1 || Cc < 1)
-        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: N = %d, H = %d, W = %d, Cf = %d, Cc = %d must be "
-                    "positive", N, H, W, Cf, Cc);
-    if (Cf % 4) return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: Cf = %d is no multiple of 4 (Darknet's "
-                            "reorg reads the fine map as [Cf / 4][4 H][4 W])", Cf);
-    // the forward entry point's bounds: the index arithmetic of one image of dfine is 32-bit
-    if ((long long)16 * H * W * Cf > 0x7fffffffLL || (long long)4 * Cf + Cc > 0x7fffffffLL)
-        return fail(Y2_ERR_ARG, "y2_passthrough_concat_darknet_backward: an image of %d x %d x %d is beyond 32-bit indices",
-                    2 * H, 2 * W, Cf);
-    const bool vec = (Cc % 4) == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)dcoarse % 16) == 0;
-    const size_t total = (size_t)N * H * W * ((size_t)(4 * Cf + Cc) / (vec ? 4 : 1));
-    size_t nb = (total + 255) / 256;
-    if (nb > 65536) nb = 65536;
-    if (vec) hipLaunchKernelGGL(darknet_route_backward_kernel<4>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
-                                dout, dfine, dcoarse, N, H, W, Cf, Cc);
-    else hipLaunchKernelGGL(darknet_route_backward_kernel<1>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
-                            dout, dfine, dcoarse, N, H, W, Cf, Cc);
-    EXTCHK(hipGetLastError());
-    return Y2_OK;
+    return darknet_passthrough_launch("y2_passthrough_concat_darknet_backward", darknet_route_backward_kernel<4>,
+                                      darknet_route_backward_kernel<1>, dout, dfine, dcoarse, dout, dcoarse, N, H, W, Cf, Cc,
+                                      stream);
 }
 
 int y2_zero(float* x, size_t n, void* stream) {

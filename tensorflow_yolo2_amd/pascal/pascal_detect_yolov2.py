@@ -17,41 +17,30 @@ import sys
 import torch
 
 from ..img_dataset import pascal_voc
-from ..yolo2_nets import net_utils, yolov2
+from . import yolov2_model_flags as model_flags
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", nargs="+", required=True, help="image files")
-    ap.add_argument("--size", type=int, default=416)
-    ap.add_argument("--batch", type=int, default=None, help="images per forward pass (default: all of them, at most 32)")
-    ap.add_argument("--dtype", default="f16")
-    ap.add_argument("--weights", default=None, help="snapshot file (train_iter_<i>.npz of pascal_train_yolov2.py)")
-    ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_*.npz snapshots: the latest is used")
-    ap.add_argument("--darknet-weights", default=None,
-                    help="a Darknet .weights file of yolov2-voc.cfg (yolov2-voc.weights): builds the \"darknet\" topology "
-                         "with the published VOC anchors and 20 classes; not with --weights or --ckpt-dir")
+    model_flags.add_model_flags(ap, None, "images per forward pass (default: all of them, at most 32)", "used",
+                                "20 classes")
     ap.add_argument("--thresh", type=float, default=0.24, help="score above which a box is a detection")
     ap.add_argument("--nms", type=float, default=0.45, help="IoU above which a box of the same class is suppressed")
     ap.add_argument("--max-out", type=int, default=100, help="detections kept per image")
     ap.add_argument("--stretch", action="store_true", help="resize without keeping the aspect ratio (no letterbox)")
     ap.add_argument("--fill", type=int, default=127, help="the value of the letterbox bars, 0..255")
     ap.add_argument("--out", default=None, help="write the lines to this file as well")
-    ap.add_argument("--width-div", type=int, default=1, help="divide every inner width (tests)")
-    ap.add_argument("--keep-grids", action="store_true", help="return the raw head outputs of every image (tests)")
+    model_flags.add_test_flags(ap)
     args = ap.parse_args(argv)
-    if args.size < 32 or args.size % 32:
-        ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
-    if (args.size // 32) ** 2 * len(yolov2.ANCHORS_VOC) > 2048:
-        ap.error("--size %d: more than 2048 candidates per image" % args.size)
+    model_flags.check_size(ap, args)
     if args.batch is None:
         args.batch = min(len(args.images), 32)
     if args.batch < 1 or args.max_out < 1 or args.width_div < 1:
         ap.error("--batch, --max-out and --width-div must be at least 1")
     if not 0 <= args.fill <= 255:
         ap.error("--fill %d outside 0..255" % args.fill)
-    if args.darknet_weights and (args.weights or args.ckpt_dir):
-        ap.error("--darknet-weights goes with neither --weights nor --ckpt-dir")
+    model_flags.check_weights(ap, args)
     return args
 
 
@@ -59,26 +48,8 @@ def main(argv=None):
     args = parse_args(argv)
     from ..img_dataset.device_images import DeviceImages
     pool = DeviceImages(args.images, args.batch)
-    snapshot = args.weights
-    if not snapshot and args.ckpt_dir:
-        sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
-        snapshot = sfiles[-1] if sfiles else None
-    anchors, num_class = yolov2.ANCHORS_VOC, len(pascal_voc.CLASSES)
-    bn_eps = None
-    if snapshot:
-        anchors, num_class, _it = net_utils.read_yolov2_meta(snapshot)
-        bn_eps = net_utils.read_yolov2_bn_eps(snapshot)
-    detector = yolov2.YOLOv2Detector(args.batch, args.size, num_class=num_class, anchors=anchors, dtype=args.dtype,
-                                     width_div=args.width_div, bn_eps=bn_eps,
-                                     topology="darknet" if args.darknet_weights else "paper")
-    restored = 0
-    if args.darknet_weights:
-        print('Restorining model from Darknet weight file {:s}'.format(args.darknet_weights))
-        seen = net_utils.load_darknet_weights(detector, args.darknet_weights)
-        print('{:d} images seen'.format(seen))
-    if snapshot:
-        print('Restorining model from weight file {:s}'.format(snapshot))
-        restored = net_utils.restore_yolov2_variables(detector, snapshot)
+    snapshot, anchors, num_class, bn_eps = model_flags.find_snapshot(args, len(pascal_voc.CLASSES))
+    detector, restored = model_flags.build_detector(args, snapshot, anchors, num_class, bn_eps)
     names = pascal_voc.CLASSES if num_class == len(pascal_voc.CLASSES) else [str(c) for c in range(num_class)]
     n, entries = args.batch, len(pool.entries)
     grids = []

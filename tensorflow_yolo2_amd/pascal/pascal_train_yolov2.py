@@ -46,7 +46,6 @@ import os
 import numpy as np
 import torch
 
-from .. import config as cfg
 from ..utils.timer import Timer
 from ..yolo2_nets import net_utils, yolov2
 
@@ -171,6 +170,9 @@ def parse_args(argv=None):
 SOLVER_FLAGS = ("lr", "momentum", "decay", "burn_in", "power", "policy", "steps", "scales", "max_batches")
 
 
+TRAINERS = {"paper": yolov2.YOLOv2Trainer, "darknet": yolov2.YOLOv2DarknetTrainer}
+
+
 def step_size(args, i):
     """input size of training iteration i (1-based, counted over resumed runs): a function of the flags alone"""
     if not args.multi_scale:
@@ -198,16 +200,8 @@ def main(argv=None):
     darknet = args.topology == "darknet"
     if args.ckpt_dir:
         os.makedirs(args.ckpt_dir, exist_ok=True)
-        npz, dkw = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir), net_utils.get_ordered_darknet_ckpts(args.ckpt_dir)
-        if (dkw if not darknet else npz):
-            raise ValueError("--ckpt-dir %s holds snapshots of the %s topology (%s); this run trains the %s topology, whose "
-                             "snapshots are %s files" % ((args.ckpt_dir, "paper", os.path.basename(npz[-1]), "darknet",
-                                                          ".weights") if darknet else
-                                                         (args.ckpt_dir, "darknet", os.path.basename(dkw[-1]), "paper",
-                                                          ".npz")))
-        sfiles = dkw if darknet else npz
-        latest = sfiles[-1] if sfiles else None
-    if latest and not darknet:
+        latest = net_utils.latest_yolov2_snapshot(args.ckpt_dir, args.topology)
+    if latest and not darknet:                # a .weights file carries no anchors: the flags'
         anchors = net_utils.read_yolov2_meta(latest)[0]
     elif args.anchors == "kmeans":
         from ..utils import anchors as A
@@ -223,33 +217,25 @@ def main(argv=None):
     bn_eps = yolov2.DARKNET_BN_EPS if args.darknet_backbone else None
     if latest and bn_eps is None and not darknet:
         bn_eps = net_utils.read_yolov2_bn_eps(latest)
-    make = yolov2.YOLOv2DarknetTrainer if darknet else yolov2.YOLOv2Trainer
-    trainer = make(args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
-                   seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
-                   prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps)
+    trainer = TRAINERS[args.topology](args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
+                                      seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
+                                      prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps)
     last_iter_num = 0
-    if darknet:
-        # a .weights file is the whole snapshot: parameters, moving statistics and `seen`, no optimizer state
-        if latest:
-            print('Restorining model snapshots from {:s}'.format(latest))
-            last_iter_num = net_utils.load_darknet_weights(trainer, latest) // args.batch
-            trainer.resume_at(last_iter_num)
-            skip_batches(imdb, last_iter_num)
-        elif args.darknet_weights:
-            seen = net_utils.load_darknet_weights(trainer, args.darknet_weights)
-            print('Model restored from Darknet weight file {:s} ({:d} images seen)'.format(args.darknet_weights, seen))
-        elif args.darknet_backbone:
-            n = net_utils.load_darknet_prefix(trainer, args.darknet_backbone)
-            print('{:d} layers restored from Darknet weight file {:s}'.format(n, args.darknet_backbone))
-    elif latest:
+    if latest:
         print('Restorining model snapshots from {:s}'.format(latest))
-        last_iter_num = net_utils.restore_yolov2_variables(trainer, latest)
+        last_iter_num = net_utils.restore_yolov2_snapshot(trainer, latest)
         skip_batches(imdb, last_iter_num)
+    elif args.darknet_weights:
+        seen = net_utils.load_darknet_weights(trainer, args.darknet_weights)
+        print('Model restored from Darknet weight file {:s} ({:d} images seen)'.format(args.darknet_weights, seen))
     elif args.imagenet_ckpt_dir:
         prior = net_utils.get_ordered_ckpts(args.imagenet_ckpt_dir, 'darknet19', True)
         if prior:
             net_utils.load_darknet19_backbone(trainer, net_utils.read_darknet19_core(prior[-1]))
             print('Backbone restored from {:s}'.format(prior[-1]))
+    elif args.darknet_backbone and darknet:
+        n = net_utils.load_darknet_prefix(trainer, args.darknet_backbone)
+        print('{:d} layers restored from Darknet weight file {:s}'.format(n, args.darknet_backbone))
     elif args.darknet_backbone:
         net_utils.load_darknet19_backbone(trainer, net_utils.read_darknet_backbone(args.darknet_backbone, trainer.bn_eps,
                                                                                    width_div=args.width_div))
@@ -279,13 +265,7 @@ def main(argv=None):
                                                                                         float(losses[-1][4]), rate, _time))
             T.tic()
         if args.ckpt_dir and (i % args.save_every == 0 or i == TOTAL_ITER):
-            save_path = os.path.join(args.ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) +
-                                     ('.weights' if darknet else '.npz'))
-            if darknet:
-                net_utils.save_darknet_weights(trainer, save_path, seen=i * args.batch)
-            else:
-                net_utils.save_yolov2_variables(trainer, save_path, iteration=i)
-            print("Model saved in file: %s" % save_path)
+            print("Model saved in file: %s" % net_utils.save_yolov2_snapshot(trainer, args.ckpt_dir, i))
     torch.cuda.synchronize()
     return {"losses": losses, "last_iter": TOTAL_ITER, "first_iter": last_iter_num + 1, "trainer": trainer,
             "sizes": sizes, "anchors": np.asarray(anchors, np.float32), "imdb": imdb}

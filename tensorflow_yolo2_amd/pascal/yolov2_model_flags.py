@@ -1,0 +1,65 @@
+"""What pascal_eval_yolov2.py and pascal_detect_yolov2.py share: the flags that name the model, their checks, and the
+sequence snapshot -> its anchors, class count and batch-norm epsilon -> YOLOv2Detector -> restore.  The flags are added in
+two groups so that each script's usage line keeps its order."""
+from ..yolo2_nets import net_utils, yolov2
+
+
+def add_model_flags(ap, batch, batch_help, latest_is, darknet_classes):
+    """--size, --batch, --dtype and the three ways to name the weights.  batch / batch_help: the script's own default and
+    help of --batch; latest_is: what happens to the latest snapshot of --ckpt-dir ("evaluated", "used"); darknet_classes:
+    where a Darknet file's class count comes from"""
+    ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--batch", type=int, default=batch, help=batch_help)
+    ap.add_argument("--dtype", default="f16")
+    ap.add_argument("--weights", default=None, help="snapshot file (train_iter_<i>.npz of pascal_train_yolov2.py)")
+    ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_*.npz snapshots: the latest is " + latest_is)
+    ap.add_argument("--darknet-weights", default=None,
+                    help="a Darknet .weights file of yolov2-voc.cfg (yolov2-voc.weights): builds the \"darknet\" topology "
+                         "with the published VOC anchors and %s; not with --weights or --ckpt-dir" % darknet_classes)
+
+
+def add_test_flags(ap):
+    ap.add_argument("--width-div", type=int, default=1, help="divide every inner width (tests)")
+    ap.add_argument("--keep-grids", action="store_true", help="return the raw head outputs of every image (tests)")
+
+
+def check_size(ap, args):
+    if args.size < 32 or args.size % 32:
+        ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
+    if (args.size // 32) ** 2 * len(yolov2.ANCHORS_VOC) > 2048:
+        ap.error("--size %d: more than 2048 candidates per image" % args.size)
+
+
+def check_weights(ap, args):
+    if args.darknet_weights and (args.weights or args.ckpt_dir):
+        ap.error("--darknet-weights goes with neither --weights nor --ckpt-dir")
+
+
+def find_snapshot(args, num_class):
+    """-> (snapshot path or None, anchors, class count, bn_eps) of the model to build: the snapshot's own where --weights
+    or --ckpt-dir names one, else the published VOC anchors, `num_class` and the default epsilon"""
+    snapshot = args.weights
+    if not snapshot and args.ckpt_dir:
+        sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
+        snapshot = sfiles[-1] if sfiles else None
+    if not snapshot:
+        return None, yolov2.ANCHORS_VOC, num_class, None
+    anchors, num_class, _it = net_utils.read_yolov2_meta(snapshot)
+    return snapshot, anchors, num_class, net_utils.read_yolov2_bn_eps(snapshot)
+
+
+def build_detector(args, snapshot, anchors, num_class, bn_eps):
+    """the detector of find_snapshot's answer, filled from --darknet-weights or from the snapshot -> (detector, the
+    snapshot's iteration or 0)"""
+    detector = yolov2.YOLOv2Detector(args.batch, args.size, num_class=num_class, anchors=anchors, dtype=args.dtype,
+                                     width_div=args.width_div, bn_eps=bn_eps,
+                                     topology="darknet" if args.darknet_weights else "paper")
+    restored = 0
+    if args.darknet_weights:
+        print('Restorining model from Darknet weight file {:s}'.format(args.darknet_weights))
+        seen = net_utils.load_darknet_weights(detector, args.darknet_weights)
+        print('{:d} images seen'.format(seen))
+    if snapshot:
+        print('Restorining model from weight file {:s}'.format(snapshot))
+        restored = net_utils.restore_yolov2_variables(detector, snapshot)
+    return detector, restored

@@ -600,24 +600,31 @@ def read_yolov2_bn_eps(path):
     return None if eps == _v2snap.DEFAULT_BN_EPS else eps
 
 
+def _is_darknet(model):
+    return getattr(model, "topology", "paper") == "darknet"
+
+
 def _refuse_darknet_topology(model, what, instead):
-    if getattr(model, "topology", "paper") == "darknet":
+    if _is_darknet(model):
         raise ValueError("%s: .npz snapshots of the \"darknet\" topology are out of scope -- the .weights file is this "
                          "topology's snapshot (%s)" % (what, instead))
 
 
+def _ordered_snapshots(ckpt_dir, ext):
+    """`train_iter_<i><ext>` files of ckpt_dir by iteration number, oldest first"""
+    files = glob.glob(os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + "_iter_*" + ext))
+    numbered = [(int(m.group(1)), f) for f in files for m in [re.search(r"_iter_(\d+)%s$" % re.escape(ext), f)] if m]
+    return [f for _i, f in sorted(numbered)]
+
+
 def get_ordered_yolov2_ckpts(ckpt_dir):
     """`train_iter_<i>.npz` files of ckpt_dir by iteration number, oldest first"""
-    files = glob.glob(os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + "_iter_*.npz"))
-    numbered = [(int(m.group(1)), f) for f in files for m in [re.search(r"_iter_(\d+)\.npz$", f)] if m]
-    return [f for _i, f in sorted(numbered)]
+    return _ordered_snapshots(ckpt_dir, ".npz")
 
 
 def get_ordered_darknet_ckpts(ckpt_dir):
     """`train_iter_<i>.weights` files of ckpt_dir (the "darknet" topology's snapshots) by iteration number, oldest first"""
-    files = glob.glob(os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + "_iter_*.weights"))
-    numbered = [(int(m.group(1)), f) for f in files for m in [re.search(r"_iter_(\d+)\.weights$", f)] if m]
-    return [f for _i, f in sorted(numbered)]
+    return _ordered_snapshots(ckpt_dir, ".weights")
 
 
 def read_darknet19_core(path):
@@ -666,7 +673,7 @@ from ..utils import darknet_weights as _dkw
 
 
 def _darknet_model(model, what):
-    if getattr(model, "topology", "paper") != "darknet":
+    if not _is_darknet(model):
         raise ValueError("%s takes a YOLOv2Detector(topology=\"darknet\") or a YOLOv2DarknetTrainer: the paper topology's "
                          "graph is not the one a Darknet file holds" % what)
     return model.networks()
@@ -689,58 +696,24 @@ def _describe(model):
                                                   "/".join(str(net.spec[-1][2]) for net in model.networks()))
 
 
-def load_darknet_weights(model, path):
-    """fill a YOLOv2Detector(topology="darknet") from a Darknet `.weights` file (yolov2-voc.weights) -> its `seen`.
-    Per layer with batch norm: W = weights.transpose(2, 3, 1, 0) -- the first layer keeps Darknet's RGB order, the model
-    feeds RGB --, b = 0, the four batch-norm arrays copied.  Last layer: b = biases and an inference batch norm that is
-    the identity to one ulp (utils/darknet_weights.to_layer_params).  A file whose float count is not the one of the
-    model's class count, anchors and width raises, naming both."""
-    nets = _darknet_model(model, "load_darknet_weights")
+def _load_darknet_layers(model, path, what, whole):
+    """the one per-layer loop of load_darknet_weights (whole: the file must hold every convolution of the model) and
+    load_darknet_prefix (its leading ones; the layers behind keep their values) -> (seen, layers read)"""
+    nets = _darknet_model(model, what)
     file_layers = darknet_file_layers(model)
     _major, _minor, _revision, seen, values = _dkw.read(path)
     want = sum(_dkw.layer_floats(l) for l in file_layers)
     try:
         layers, _used = _dkw.split(values, file_layers)
     except ValueError as e:
-        raise ValueError("%s holds %d floats, the model (%s: %d convolutions) needs %d: %s" %
-                         (path, values.size, _describe(model), len(file_layers), want, e))
-    if len(layers) != len(file_layers):
-        raise ValueError("%s holds %d convolutions (%d floats), the model (%s) has %d (%d floats)" %
-                         (path, len(layers), values.size, _describe(model), len(file_layers), want))
-    pos = 0
-    for net in nets:
-        params = [_dkw.to_layer_params(layers[pos + l], net.spec[l][0], model.bn_eps) for l in range(net.num_layers)]
-        for l, p in enumerate(params):
-            for k, shape in net._shapes(l).items():
-                if tuple(p[k].shape) != tuple(shape):
-                    raise ValueError("%s: convolution %d %s has shape %s, the model (%s) expects %s" %
-                                     (path, pos + l, k, tuple(p[k].shape), _describe(model), tuple(shape)))
-        net.load_params(params)
-        pos += net.num_layers
-    _all_sizes_changed(model)
-    return seen
-
-
-def _all_sizes_changed(model):
-    """a trainer's multi-scale contexts share the parameters just written: every size re-packs its filters"""
-    if hasattr(model, "params_changed"):
-        model.params_changed()
-
-
-def load_darknet_prefix(model, path):
-    """the leading convolutions of a SHORTER Darknet file (darknet19_448.conv.23: the 18 core layers) into a
-    "darknet"-topology model, detector or trainer -> the number of layers read.  The arithmetic of load_darknet_weights
-    per layer and NO first-layer fold: this graph takes Darknet's input, so the import is exact on the border ring too
-    (read_darknet_backbone, for the paper topology, is not).  The layers behind the prefix keep their values.  A file
-    that ends inside a layer, holds more than the model or holds no layer at all raises."""
-    nets = _darknet_model(model, "load_darknet_prefix")
-    file_layers = darknet_file_layers(model)
-    values = _dkw.read(path)[4]
-    try:
-        layers, _used = _dkw.split(values, file_layers)
-    except ValueError as e:
+        if whole:
+            raise ValueError("%s holds %d floats, the model (%s: %d convolutions) needs %d: %s" %
+                             (path, values.size, _describe(model), len(file_layers), want, e))
         raise ValueError("%s holds %d floats, no whole-layer prefix of the model (%s: %d convolutions): %s" %
                          (path, values.size, _describe(model), len(file_layers), e))
+    if whole and len(layers) != len(file_layers):
+        raise ValueError("%s holds %d convolutions (%d floats), the model (%s) has %d (%d floats)" %
+                         (path, len(layers), values.size, _describe(model), len(file_layers), want))
     if not layers:
         raise ValueError("%s holds no convolution" % path)
     pos = 0
@@ -758,8 +731,27 @@ def load_darknet_prefix(model, path):
             params[l] = p
         net.load_params(params)
         pos += take
-    _all_sizes_changed(model)
-    return len(layers)
+    if hasattr(model, "params_changed"):
+        model.params_changed()      # a trainer's multi-scale contexts share the parameters just written: all re-pack
+    return seen, len(layers)
+
+
+def load_darknet_weights(model, path):
+    """fill a YOLOv2Detector(topology="darknet") from a Darknet `.weights` file (yolov2-voc.weights) -> its `seen`.
+    Per layer with batch norm: W = weights.transpose(2, 3, 1, 0) -- the first layer keeps Darknet's RGB order, the model
+    feeds RGB --, b = 0, the four batch-norm arrays copied.  Last layer: b = biases and an inference batch norm that is
+    the identity to one ulp (utils/darknet_weights.to_layer_params).  A file whose float count is not the one of the
+    model's class count, anchors and width raises, naming both."""
+    return _load_darknet_layers(model, path, "load_darknet_weights", True)[0]
+
+
+def load_darknet_prefix(model, path):
+    """the leading convolutions of a SHORTER Darknet file (darknet19_448.conv.23: the 18 core layers) into a
+    "darknet"-topology model, detector or trainer -> the number of layers read.  The arithmetic of load_darknet_weights
+    per layer and NO first-layer fold: this graph takes Darknet's input, so the import is exact on the border ring too
+    (read_darknet_backbone, for the paper topology, is not).  The layers behind the prefix keep their values.  A file
+    that ends inside a layer, holds more than the model or holds no layer at all raises."""
+    return _load_darknet_layers(model, path, "load_darknet_prefix", False)[1]
 
 
 def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):
@@ -780,6 +772,48 @@ def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):
             out.append(_dkw.from_layer_params(p, kf, bn, model.bn_eps))
         pos += net.num_layers
     return _dkw.write(path, out, seen, major, minor, revision)
+
+
+# ---------------------------------------------------------------------------
+# One snapshot front for both topologies, keyed on model.topology / a topology name: the callers (pascal/) do not branch.
+# "paper": train_iter_<i>.npz, the whole train state.  "darknet": train_iter_<i>.weights, parameters and `seen`.
+# ---------------------------------------------------------------------------
+_SNAPSHOT_EXT = {"paper": ".npz", "darknet": ".weights"}
+
+
+def latest_yolov2_snapshot(ckpt_dir, topology):
+    """the newest snapshot of `topology` in ckpt_dir, or None; a directory that holds the OTHER topology's raises"""
+    (other,) = [t for t in _SNAPSHOT_EXT if t != topology]
+    foreign = _ordered_snapshots(ckpt_dir, _SNAPSHOT_EXT[other])
+    if foreign:
+        raise ValueError("--ckpt-dir %s holds snapshots of the %s topology (%s); this run trains the %s topology, whose "
+                         "snapshots are %s files" % (ckpt_dir, other, os.path.basename(foreign[-1]), topology,
+                                                     _SNAPSHOT_EXT[topology]))
+    sfiles = _ordered_snapshots(ckpt_dir, _SNAPSHOT_EXT[topology])
+    return sfiles[-1] if sfiles else None
+
+
+def save_yolov2_snapshot(model, ckpt_dir, i):
+    """snapshot `i` of a model into ckpt_dir, in its topology's format (`seen` = i * batch in a .weights file) -> the path"""
+    topology = "darknet" if _is_darknet(model) else "paper"
+    path = os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) + _SNAPSHOT_EXT[topology])
+    if _is_darknet(model):
+        save_darknet_weights(model, path, seen=i * model.batch)
+    else:
+        save_yolov2_variables(model, path, iteration=i)
+    return path
+
+
+def restore_yolov2_snapshot(model, path):
+    """a model from a snapshot of its topology -> the iteration it stood at.  A .weights file is the whole snapshot of the
+    "darknet" topology: parameters, moving statistics and `seen`, no optimizer state -- the iteration is seen // batch,
+    and a trainer continues there (resume_at)"""
+    if not _is_darknet(model):
+        return restore_yolov2_variables(model, path)
+    iteration = load_darknet_weights(model, path) // model.batch
+    if hasattr(model, "resume_at"):
+        model.resume_at(iteration)
+    return iteration
 
 
 def read_darknet_backbone(path, bn_eps_model, width_div=1):

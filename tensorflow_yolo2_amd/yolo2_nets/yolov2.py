@@ -10,6 +10,8 @@ yolov2_loss_kernel, specification oracle/ext_ref.py), backward through the head,
 parameter buffers, optional multi-scale.  `YOLOv2DarknetTrainer` is the train step of the "darknet" topology, the graph
 of yolov2-voc.cfg: four stacks, Darknet's reorg and its gradient, a last layer without batch statistics.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -48,6 +50,85 @@ def yolov2_darknet_specs(num_class=20, num_anchors=5, width_div=1):
 
 
 TOPOLOGIES = ("paper", "darknet")
+DARKNET_1X1_CORE_LAYER = 3       # Darknet-19's fourth convolution: 1x1 in the file, 3x3 with a centre tap in this graph
+
+
+def _paper_concat(fine, coarse, out=None):
+    return E.passthrough_concat(fine, coarse)            # torch allocates the result: this path keeps no buffers
+
+
+# What one YOLOv2 graph is, as data: everything below reads this record and never asks for the name.  Per stack, in
+# networks() order: `heights` the input height in units of S = size / 32, `slopes` the activation slopes (None: 0.1
+# everywhere), `train_options` the engine.Network options of a training context.  bn_eps: the default batch-norm epsilon
+# (None: the contexts' own 1e-3).  head_statistics: whether the head trains on batch statistics.  darknet_input: uint8
+# batches go through engine.u8_to_darknet_input into a buffer kept per size, and so does the concat; otherwise the first
+# layer converts and torch allocates.  concat / concat_backward: the passthrough pair; cf_stack: the stack whose output
+# width that pair reads as `cf`.
+_Topology = collections.namedtuple("_Topology", "name specs heights bn_eps slopes train_options head_statistics "
+                                                "darknet_input concat concat_backward cf_stack")
+
+_BESSEL = {"bessel": True}       # moving variances on the n - 1 estimate, as Darknet keeps them
+_TOPOLOGY = {
+    # (stem, 13x13 stack, head): the graph of the module docstring
+    "paper": _Topology(name="paper", specs=yolov2_specs, heights=(32, 1, 1), bn_eps=None, slopes=(None, None, None),
+                       train_options=({}, {}, {}), head_statistics=True, darknet_input=False, concat=_paper_concat,
+                       concat_backward=E.passthrough_concat_backward, cf_stack=0),
+    # (stem, 13x13 stack, route, head): the order of the convolutions in a `.weights` file.  The head trains its 3x3 layer
+    # on batch statistics and runs the last, linear layer on its moving ones (core_layers 1)
+    "darknet": _Topology(name="darknet", specs=yolov2_darknet_specs, heights=(32, 1, 2, 1), bn_eps=DARKNET_BN_EPS,
+                         slopes=(None, None, None, [0.1, 1.0]),
+                         train_options=(_BESSEL, _BESSEL, _BESSEL, dict(_BESSEL, core_layers=1)), head_statistics=False,
+                         darknet_input=True, concat=E.passthrough_concat_darknet,
+                         concat_backward=E.passthrough_concat_darknet_backward, cf_stack=2),
+}
+
+
+def _topology(name):
+    if name not in TOPOLOGIES:
+        raise ValueError("topology %r: one of %s" % (name, ", ".join(TOPOLOGIES)))
+    return _TOPOLOGY[name]
+
+
+def _build_stacks(topo, specs, batch, size, dtype, device, bn_eps, training, seed, share_with=None):
+    """the stack contexts of one input size, in networks() order.  share_with: the contexts of another size, whose
+    parameters these are bound to; without it every stack draws its initial values from seed + its position"""
+    assert size % 32 == 0
+    nets = []
+    for i, (spec, units) in enumerate(zip(specs, topo.heights)):
+        h = units * (size // 32)
+        options = dict(topo.train_options[i], share_with=share_with[i] if share_with else None) if training else {}
+        net = E.Network(spec, batch, h, h, dtype=dtype, training=training, device=device, **options)
+        if topo.slopes[i] is not None or bn_eps is not None:
+            net.set_layer_options(slopes=topo.slopes[i], bn_eps=bn_eps)
+        if share_with is None:
+            net.init_params(seed + i)
+        nets.append(net)
+    return tuple(nets)
+
+
+def _make_buffers(topo, nets, batch, size):
+    """(network input, concat) of one size on a topology that keeps them, else (None, None)"""
+    if not topo.darknet_input:
+        return None, None
+    S, dev = size // 32, nets[0].device
+    return (torch.empty((batch, size, size, 3), dtype=torch.float32, device=dev),
+            torch.empty((batch, S, S, nets[-1].spec[0][1]), dtype=torch.float32, device=dev))
+
+
+def _forward(topo, nets, buffers, images, training, update_moving, out=None):
+    """the forward pass of either graph -> (flat head output, fine map).  nets = (stem, 13x13 stack, [route,] head)"""
+    x_buf, cat_buf = buffers
+    if topo.darknet_input and images.dtype == torch.uint8:
+        images = E.u8_to_darknet_input(images, out=x_buf)                   # BGR pixels -> RGB in [0, 1]
+    stem, deep, head = nets[0], nets[1], nets[-1]
+    fine = stem.forward(images, training, training, update_moving=update_moving)                  # [N,2S,2S,512]
+    coarse = deep.forward(E.max_pool_2x2(fine), training, training, update_moving=update_moving)  # [N,S,S,1024]
+    passed = fine
+    for route in nets[2:-1]:                                                # "darknet": the 1x1 route, [N,2S,2S,64]
+        passed = route.forward(passed, training, training, update_moving=update_moving)
+    cat = topo.concat(passed, coarse, out=cat_buf)                          # [N,S,S,4*cf+1024], reorganised map first
+    out = head.forward(cat, training, training and topo.head_statistics, out=out, update_moving=update_moving)
+    return out, fine                                                        # [N,S,S,B*(5+C)]
 
 
 class YOLOv2Detector:
@@ -61,67 +142,30 @@ class YOLOv2Detector:
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", width_div=1, topology="paper", bn_eps=None):
         assert image_size % 32 == 0
-        if topology not in TOPOLOGIES:
-            raise ValueError("topology %r: one of %s" % (topology, ", ".join(TOPOLOGIES)))
+        self._topo = _topology(topology)
         self.topology = topology
-        self.bn_eps = None if bn_eps is None else float(bn_eps)
+        self.bn_eps = self._topo.bn_eps if bn_eps is None else float(bn_eps)
         self.batch, self.size, self.S = batch, image_size, image_size // 32
         self.num_class, self.anchors = num_class, np.asarray(anchors, np.float32).reshape(-1, 2)
         self.B = len(self.anchors)
         self.iteration = 0                                   # of the snapshot last restored (net_utils)
         self.anchors_dev = torch.as_tensor(self.anchors).to(device).contiguous()
-        S = self.S
-        if topology == "darknet":
-            self._init_darknet(batch, image_size, num_class, dtype, seed, device, width_div)
-            return
-        sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
-        self.stem = E.Network(sa, batch, image_size, image_size, dtype=dtype, training=False, device=device)
-        self.deep = E.Network(sb, batch, S, S, dtype=dtype, training=False, device=device)
-        self.head = E.Network(sc, batch, S, S, dtype=dtype, training=False, device=device)
-        for i, net in enumerate((self.stem, self.deep, self.head)):
-            net.init_params(seed + i)
-            if self.bn_eps is not None:
-                net.set_layer_options(bn_eps=self.bn_eps)
-
-    def _init_darknet(self, batch, image_size, num_class, dtype, seed, device, width_div):
-        S = self.S
-        if self.bn_eps is None:
-            self.bn_eps = DARKNET_BN_EPS
-        sa, sb, sr, sc = yolov2_darknet_specs(num_class, self.B, width_div)
-        mk = lambda spec, h: E.Network(spec, batch, h, h, dtype=dtype, training=False, device=device)
-        self.stem, self.deep, self.route, self.head = mk(sa, image_size), mk(sb, S), mk(sr, 2 * S), mk(sc, S)
-        for i, net in enumerate(self.networks()):
-            net.init_params(seed + i)
-            net.set_layer_options(slopes=[0.1, 1.0] if net is self.head else None, bn_eps=self.bn_eps)
-        self._input = torch.empty((batch, image_size, image_size, 3), dtype=torch.float32, device=device)
-        self._cat = torch.empty((batch, S, S, sc[0][1]), dtype=torch.float32, device=device)
+        specs = self._topo.specs(num_class, self.B, width_div)
+        self._stacks = _build_stacks(self._topo, specs, batch, image_size, dtype, device, self.bn_eps, False, seed)
+        self.stem, self.deep, self.head = self._stacks[0], self._stacks[1], self._stacks[-1]
+        if len(self._stacks) == 4:
+            self.route = self._stacks[2]
+        self._buffers = _make_buffers(self._topo, self._stacks, batch, image_size)
 
     def networks(self):
         """the stack contexts: (stem, 13x13 stack, head), or on the "darknet" topology (stem, 13x13 stack, route, head)
         -- the order of the convolutions in a `.weights` file"""
-        if self.topology == "darknet":
-            return self.stem, self.deep, self.route, self.head
-        return self.stem, self.deep, self.head
-
-    def _forward_darknet(self, images, out=None):
-        if images.dtype == torch.uint8:
-            images = E.u8_to_darknet_input(images, out=self._input)        # BGR pixels -> RGB in [0, 1]
-        fine = self.stem.forward(images, False, False)                      # [N,2S,2S,512]
-        coarse = self.deep.forward(E.max_pool_2x2(fine), False, False)      # [N,S,S,1024]
-        route = self.route.forward(fine, False, False)                      # [N,2S,2S,64]
-        cat = E.passthrough_concat_darknet(route, coarse, out=self._cat)    # [N,S,S,256+1024], reorganised map first
-        out = self.head.forward(cat, False, False, out=out)                 # [N,S,S,B*(5+C)], last layer linear
-        return out.view(self.batch, self.S, self.S, self.B, 5 + self.num_class)
+        return self._stacks
 
     def forward(self, images, out=None):
         """images [N,size,size,3] fp32 (or uint8 BGR pixels) on the device -> raw grid [N,S,S,B,5+C] (in `out`, a
         contiguous fp32 tensor of that many elements, if given).  On the "darknet" topology fp32 input is RGB in [0, 1]"""
-        if self.topology == "darknet":
-            return self._forward_darknet(images, out)
-        fine = self.stem.forward(images, False, False)                      # [N,2S,2S,512]
-        coarse = self.deep.forward(E.max_pool_2x2(fine), False, False)      # [N,S,S,1024]
-        cat = E.passthrough_concat(fine, coarse)                            # [N,S,S,3072]
-        out = self.head.forward(cat, False, False, out=out)                 # [N,S,S,B*(5+C)]
+        out, _fine = _forward(self._topo, self._stacks, self._buffers, images, False, False, out=out)
         return out.view(self.batch, self.S, self.S, self.B, 5 + self.num_class)
 
     def detect(self, images, score_thresh=0.3, iou_thresh=0.45, max_out=100, class_aware=True):
@@ -154,26 +198,18 @@ class YOLOv2Detector:
                                              max_per_class, out=out, net_size=self.size if letterbox else None)
 
 
-class YOLOv2Trainer:
-    """Train step of the YOLOv2 detector (NOT in the reference: its trainer is the YOLOv1 grid model).
-    Three conv-BN-leaky stacks, each with its own flat parameter / gradient buffer and Adam state.  With `sizes`
-    the input size may change from step to step (multi-scale {320..608}): one context + workspace per size, all
-    bound to the same three parameter sets (engine.Network(share_with=...)).
-    solver: None -- three engine.AdamOptimizer; a utils.solver.Solver -- three engine.DarknetSGD (momentum, weight decay
-    on the filters, the burn-in / steps / poly rate schedule), again with ONE loss scaler, step counter and rate."""
+class _Trainer:
+    """what the two train steps share: the contexts per input size on ONE set of parameters, the optimizers on one loss
+    scaler, the gradient reducers, the step.  A subclass names its topology and adds what only it has."""
 
-    def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
-                 solver=None, bn_eps=None, topology="paper"):
-        if topology != "paper":
-            if topology not in TOPOLOGIES:
-                raise ValueError("topology %r: one of %s" % (topology, ", ".join(TOPOLOGIES)))
-            raise NotImplementedError("YOLOv2Trainer trains the paper topology only: the %r graph needs the gradient of "
-                                      "Darknet's reorg, a fourth optimizer and a last layer without batch statistics -- "
-                                      "YOLOv2DarknetTrainer has them" % topology)
+    keeps_backward = False           # whether backward() leaves last_dcat / last_dfine behind (a subclass's tests read them)
+
+    def __init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
+                 area_weight, prior_images, prior_scale, solver, bn_eps):
+        self._topo = _topology(topology)
         # the batch-norm epsilon of every context and size (None: the contexts' default, 1e-3); 1e-6 is Darknet's, the one
         # a backbone read from a Darknet file was trained with (net_utils.read_darknet_backbone)
-        self.topology, self.bn_eps = topology, None if bn_eps is None else float(bn_eps)
+        self.topology, self.bn_eps = topology, self._topo.bn_eps if bn_eps is None else float(bn_eps)
         from ..trainer import GradReducer
         self._GradReducer = GradReducer
         self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
@@ -185,57 +221,60 @@ class YOLOv2Trainer:
         self.area_weight, self.prior_images, self.prior_scale = bool(area_weight), int(prior_images), float(prior_scale)
         self.iteration = 0                                   # train steps taken, over resumed runs (net_utils snapshots)
         self.solver = solver.validate() if solver is not None else None
-        sa, sb, sc = yolov2_specs(num_class, self.B, width_div)
-        self.specs = (sa, sb, sc)
-        self.cf = sa[-1][2]
-        self.ctx = {}
+        self.specs = tuple(self._topo.specs(num_class, self.B, width_div))
+        self.cf = self.specs[self._topo.cf_stack][-1][2]     # the width the passthrough reorganises
+        self.ctx, self.reducers, self._buffers = {}, {}, {}
         self.opts = None
         self.default_size = image_size
         self._nets(image_size)
 
     def _nets(self, size):
         if size not in self.ctx:
-            assert size % 32 == 0
-            S = size // 32
             first = next(iter(self.ctx.values())) if self.ctx else None
-            sa, sb, sc = self.specs
-            mk = lambda spec, h, share: E.Network(spec, self.batch, h, h, dtype=self.dtype, training=True,
-                                                  device=self.device, share_with=share)
-            nets = (mk(sa, size, first[0] if first else None), mk(sb, S, first[1] if first else None),
-                    mk(sc, S, first[2] if first else None))
-            if self.bn_eps is not None:
-                for net in nets:
-                    net.set_layer_options(bn_eps=self.bn_eps)
+            nets = _build_stacks(self._topo, self.specs, self.batch, size, self.dtype, self.device, self.bn_eps, True,
+                                 self.seed, share_with=first)
             if first is None:
-                for i, net in enumerate(nets):
-                    net.init_params(self.seed + i)
+                self._init_form(nets)
                 if self.solver is None:
                     self.opts = [E.AdamOptimizer(net) for net in nets]
                 else:
                     self.opts = [E.DarknetSGD(net, self.solver) for net in nets]
                 # ONE loss scale, overflow flag and step counter for the composed graph: an inf confined to
-                # one stack must skip the step of all three, and a skipped step must not advance any Adam bias correction
+                # one stack must skip the step of all, and a skipped step must not advance any Adam bias correction
                 for opt in self.opts[1:]:
                     opt.scaler = self.opts[0].scaler
             self.ctx[size] = nets
-            self.reducers = getattr(self, "reducers", {})
             self.reducers[size] = [self._GradReducer(net) for net in nets]
+            self._buffers[size] = _make_buffers(self._topo, nets, self.batch, size)
         return self.ctx[size]
+
+    def _init_form(self, nets):
+        """bring a fresh model into the form its snapshots can hold (nothing to do here)"""
+
+    def _mask_gradients(self, nets):
+        """after the all-reduce, before the optimizers: zero the gradients that must not move (none here)"""
 
     @property
     def nets(self):
         return self.ctx[self.default_size]
 
+    def networks(self, size=None):
+        """the stack contexts of an input size: (stem, 13x13 stack, head), or on "darknet" (stem, 13x13 stack, route,
+        head), the order of a `.weights` file"""
+        return self._nets(size or self.default_size)
+
+    def params_changed(self):
+        """the shared parameters were written from outside (a file was loaded): every size's contexts re-pack"""
+        for nets in self.ctx.values():
+            for net in nets:
+                net.params_changed()
+
     def forward(self, images, training=True, update_moving=False):
+        """images [N,size,size,3] -> (raw grid [N,S,S,B,5+C], fine [N,2S,2S,Cf]).  "darknet": uint8 BGR pixels or fp32 RGB
+        in [0, 1], and the last layer runs on its moving statistics in either mode"""
         size = int(images.shape[1])
-        stem, deep, head = self._nets(size)
-        S = size // 32
-        fine = stem.forward(images, training, training, update_moving=update_moving)          # [N,2S,2S,Cf]
-        pooled = E.max_pool_2x2(fine)
-        coarse = deep.forward(pooled, training, training, update_moving=update_moving)         # [N,S,S,Cc]
-        cat = E.passthrough_concat(fine, coarse)
-        out = head.forward(cat, training, training, update_moving=update_moving)
-        return out.view(self.batch, S, S, self.B, 5 + self.num_class), fine
+        out, fine = _forward(self._topo, self._nets(size), self._buffers[size], images, training, update_moving)
+        return out.view(self.batch, size // 32, size // 32, self.B, 5 + self.num_class), fine
 
     def prior_on(self, iteration=None):
         """whether the anchor-prior term is part of train step `iteration` (1-based; default: the next one)"""
@@ -249,251 +288,39 @@ class YOLOv2Trainer:
         sc["prior_scale"] = self.prior_scale if self.prior_on(iteration) else 0.0
         return sc
 
+    def backward(self, dnet, fine, size):
+        """the whole backward pass of the forward(training) just run at `size`, from the head's output gradient `dnet`:
+        gradients into the flat buffers, reduced over the replicas.  Returns the world size.  Each stack's all-reduce
+        starts as soon as its gradients are complete and is joined after the stem's."""
+        from ..trainer import _dist
+        nets = self._nets(size)
+        S = size // 32
+        dist = _dist()
+        red = self.reducers[size]
+        dcat = nets[-1].backward_input(dnet.view(self.batch, S, S, -1))
+        if dist is not None:
+            red[-1].reduce_all_async()
+        dfine, dcoarse = self._topo.concat_backward(dcat, self.cf)
+        dpooled = nets[1].backward_input(dcoarse)
+        if dist is not None:
+            red[1].reduce_all_async()
+        for i in range(2, len(nets) - 1):                    # "darknet": back through the route, to the fine map
+            dfine = nets[i].backward_input(dfine)
+            if dist is not None:
+                red[i].reduce_all_async()
+        E.accumulate(dfine, E.max_pool_2x2_backward(fine, dpooled))
+        if self.keeps_backward:
+            self.last_dcat, self.last_dfine = dcat, dfine
+        world = red[0].backward_and_reduce(dfine)
+        if dist is not None:
+            for r in red[1:]:
+                r.join()
+        return world
+
     def step(self, images, labels=None, truth=None, ntruth=None):
         """one train step on the label grid `labels` [N,S,S,5+C] (one box per cell) or on the box list `truth` [N,T,5] +
         `ntruth` [N] (every object; DeviceVOC(..., max_boxes=T)): exactly one of the two forms.  Returns loss[5] = coord,
         object, noobject, class, total"""
-        from ..trainer import _dist
-        if (labels is None) == (truth is None) or (truth is None) != (ntruth is None):
-            raise ValueError("step() takes either labels or truth + ntruth, not both and not neither")
-        size = int(images.shape[1])
-        stem, deep, head = self._nets(size)
-        for net in (stem, deep, head):
-            if len(self.ctx) > 1:
-                net.params_changed()              # shared parameters moved under another size's contexts
-        self.iteration += 1
-        grid, fine = self.forward(images, True, update_moving=True)
-        if labels is not None:
-            loss, dnet = E.yolov2_loss(grid.contiguous(), labels, self.anchors, size, True, self.scales)
-        else:
-            loss, dnet = E.yolov2_loss_boxes(grid.contiguous(), truth, ntruth, self.anchors, size, True,
-                                             self.box_scales(self.iteration))
-        self.last_dnet = dnet                                # the head's output gradient of this step (tests read it)
-        dist = _dist()
-        red = self.reducers[size]
-        dcat = head.backward_input(dnet.view(self.batch, size // 32, size // 32, -1))
-        if dist is not None:
-            red[2].reduce_all_async()
-        dfine, dcoarse = E.passthrough_concat_backward(dcat, self.cf)
-        dpooled = deep.backward_input(dcoarse)
-        if dist is not None:
-            red[1].reduce_all_async()
-        E.accumulate(dfine, E.max_pool_2x2_backward(fine, dpooled))
-        world = red[0].backward_and_reduce(dfine)
-        if dist is not None:
-            red[1].join(); red[2].join()
-        scaler = self.opts[0].scaler
-        for opt, net in zip(self.opts, (stem, deep, head)):
-            opt.net = net
-            if scaler is not None:
-                scaler.attach(net)
-        if scaler is None:
-            for opt in self.opts:
-                opt.step(grad_mult=1.0 / world)
-            return loss
-        # every stack's sentinels into the one flag, then the three guarded updates: all of them or none
-        for i, net in enumerate((stem, deep, head)):
-            scaler.scan(net, more=(i > 0))
-        for i, opt in enumerate(self.opts):
-            opt.step(grad_mult=1.0 / world, joint="first" if i == 0 else "next")
-        return loss
-
-    def networks(self, size=None):
-        """the three stack contexts (stem, 13x13 stack, head) of an input size"""
-        return self._nets(size or self.default_size)
-
-    def flops_per_step(self, size=None, mfma_launches_only=False):
-        """algorithmic FLOPs of one train step (3 x forward conv FLOPs, SURVEY 8(d) convention);
-        mfma_launches_only: without the 3-channel first layer, which has its own (non-GEMM) kernels"""
-        size = size or self.default_size
-        tot = 0.0
-        for spec, h0 in zip(self.specs, (size, size // 32, size // 32)):
-            h = h0
-            for (k, ci, co, pool) in spec:
-                if not (mfma_launches_only and ci == 3):
-                    tot += 2.0 * self.batch * h * h * k * k * ci * co
-                if pool:
-                    h = (h + 1) // 2
-        return 3.0 * tot
-
-
-DARKNET_1X1_CORE_LAYER = 3       # Darknet-19's fourth convolution: 1x1 in the file, 3x3 with a centre tap in this graph
-
-
-class YOLOv2DarknetTrainer:
-    """Train step of the yolov2-voc.cfg graph (YOLOv2Detector(topology="darknet")): what a Darknet `.weights` file holds
-    can be fine-tuned here and written back (net_utils.load_darknet_weights / load_darknet_prefix / save_darknet_weights
-    take this object).  YOLOv2Trainer's constructor arguments and step() contract; FOUR stacks in file order -- stem,
-    13x13 stack, the 1x1 route convolution, head -- each with its flat buffers, optimizer and gradient reducer, ONE loss
-    scaler, step counter and rate; the multi-scale contexts share the four parameter sets.
-
-    Differences from YOLOv2Trainer: Darknet's input (uint8 BGR batches through engine.u8_to_darknet_input; float input
-    is RGB in [0, 1]); the route stack and Darknet's reorg (engine.passthrough_concat_darknet and its gradient, the
-    reorganised map in FRONT); batch-norm epsilon 1e-6; moving variances on the n - 1 estimate (bessel; the
-    normalisation itself stays on the biased variance: a known difference from Darknet); and a last layer that is
-    linear and runs WITHOUT batch statistics -- the head context has core_layers = 1, its 1x1 layer normalises with the
-    identity moving statistics the importer writes and its gamma / beta gradients are zeroed every step, so those four
-    arrays never move and the export folds exactly 1.  The eight off-centre taps of core layer 3 (Darknet's 1x1) get a
-    zero gradient every step too: they stay exactly zero and the model stays writable."""
-
-    topology = "darknet"
-
-    def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
-                 solver=None, bn_eps=None, topology="darknet"):
-        if topology != "darknet":
-            raise ValueError("YOLOv2DarknetTrainer trains the \"darknet\" topology; topology %r is YOLOv2Trainer's" %
-                             (topology,))
-        self.bn_eps = DARKNET_BN_EPS if bn_eps is None else float(bn_eps)
-        from ..trainer import GradReducer
-        self._GradReducer = GradReducer
-        self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
-        self.anchors = np.asarray(anchors, np.float32)
-        self.B = len(self.anchors)
-        self.scales = scales
-        self.area_weight, self.prior_images, self.prior_scale = bool(area_weight), int(prior_images), float(prior_scale)
-        self.iteration = 0
-        self.solver = solver.validate() if solver is not None else None
-        self.specs = yolov2_darknet_specs(num_class, self.B, width_div)
-        self.cf = self.specs[2][-1][2]                       # the route's width: what the reorg scrambles
-        self.ctx, self.reducers, self._buffers = {}, {}, {}
-        self.opts = None
-        self.default_size = image_size
-        self._nets(image_size)
-
-    def _nets(self, size):
-        if size not in self.ctx:
-            assert size % 32 == 0
-            S = size // 32
-            first = next(iter(self.ctx.values())) if self.ctx else None
-            sa, sb, sr, sc = self.specs
-            # the head trains its 3x3 layer on batch statistics and runs the last layer on its moving ones (core_layers 1)
-            mk = lambda i, spec, h, core: E.Network(spec, self.batch, h, h, dtype=self.dtype, core_layers=core,
-                                                    training=True, device=self.device, bessel=True,
-                                                    share_with=first[i] if first else None)
-            nets = (mk(0, sa, size, None), mk(1, sb, S, None), mk(2, sr, 2 * S, None), mk(3, sc, S, 1))
-            for net in nets:
-                net.set_layer_options(slopes=[0.1, 1.0] if net is nets[3] else None, bn_eps=self.bn_eps)
-            if first is None:
-                for i, net in enumerate(nets):
-                    net.init_params(self.seed + i)
-                self._init_darknet_form(nets)
-                if self.solver is None:
-                    self.opts = [E.AdamOptimizer(net) for net in nets]
-                else:
-                    self.opts = [E.DarknetSGD(net, self.solver) for net in nets]
-                for opt in self.opts[1:]:
-                    opt.scaler = self.opts[0].scaler          # one scale, overflow flag and step counter for the graph
-            self.ctx[size] = nets
-            self.reducers[size] = [self._GradReducer(net) for net in nets]
-            dev = nets[0].device
-            self._buffers[size] = (torch.empty((self.batch, size, size, 3), dtype=torch.float32, device=dev),
-                                   torch.empty((self.batch, S, S, sc[0][1]), dtype=torch.float32, device=dev))
-        return self.ctx[size]
-
-    def _init_darknet_form(self, nets):
-        """a fresh model in the form a `.weights` file can hold: the 1x1 layer's off-centre taps zero, the last layer's
-        batch norm the importer's identity (utils/darknet_weights.to_layer_params)"""
-        stem, head = nets[0], nets[3]
-        params = stem.export_params()
-        W = params[DARKNET_1X1_CORE_LAYER]["W"]
-        centre = W[1, 1].copy()
-        W[...] = 0
-        W[1, 1] = centre
-        stem.load_params(params)
-        params = head.export_params()
-        n = params[-1]["b"].size
-        params[-1].update(gamma=np.full(n, np.sqrt(1.0 + np.float64(self.bn_eps)), np.float32),
-                          beta=np.zeros(n, np.float32), moving_mean=np.zeros(n, np.float32),
-                          moving_var=np.ones(n, np.float32))
-        head.load_params(params)
-
-    @property
-    def nets(self):
-        return self.ctx[self.default_size]
-
-    def networks(self, size=None):
-        """the four stack contexts (stem, 13x13 stack, route, head) of an input size: the order of a `.weights` file"""
-        return self._nets(size or self.default_size)
-
-    def params_changed(self):
-        """the shared parameters were written from outside (a file was loaded): every size's contexts re-pack"""
-        for nets in self.ctx.values():
-            for net in nets:
-                net.params_changed()
-
-    def resume_at(self, iteration):
-        """continue a run whose `.weights` snapshot stood at `iteration` (seen // batch): the step count the prior term
-        reads and, under Darknet's solver, the position in the rate schedule -- Darknet derives both from `seen`.  A
-        `.weights` file carries no optimizer state: moments and the loss scale start afresh, as in Darknet"""
-        self.iteration = int(iteration)
-        if self.solver is not None:
-            for opt in self.opts:
-                opt.t = self.iteration
-            scaler = self.opts[0].scaler
-            if scaler is not None:
-                c = scaler.ctrl.cpu()
-                c[1] = self.iteration
-                scaler.ctrl.copy_(c)
-
-    prior_on = YOLOv2Trainer.prior_on
-    box_scales = YOLOv2Trainer.box_scales
-
-    def forward(self, images, training=True, update_moving=False):
-        """images [N,size,size,3] uint8 BGR pixels or fp32 RGB in [0, 1] -> (raw grid [N,S,S,B,5+C], fine [N,2S,2S,Cf]);
-        the last layer runs on its moving statistics in either mode"""
-        size = int(images.shape[1])
-        stem, deep, route, head = self._nets(size)
-        S = size // 32
-        x_buf, cat_buf = self._buffers[size]
-        if images.dtype == torch.uint8:
-            images = E.u8_to_darknet_input(images, out=x_buf)
-        fine = stem.forward(images, training, training, update_moving=update_moving)              # [N,2S,2S,Cf]
-        coarse = deep.forward(E.max_pool_2x2(fine), training, training, update_moving=update_moving)
-        r = route.forward(fine, training, training, update_moving=update_moving)                  # [N,2S,2S,64]
-        cat = E.passthrough_concat_darknet(r, coarse, out=cat_buf)                                # [N,S,S,256+Cc]
-        out = head.forward(cat, training, False, update_moving=update_moving)
-        return out.view(self.batch, S, S, self.B, 5 + self.num_class), fine
-
-    def backward(self, dnet, fine, size):
-        """the whole backward pass of the forward(training) just run at `size`, from the head's output gradient `dnet`:
-        gradients into the four flat buffers, reduced over the replicas and masked.  Returns the world size.
-        last_dcat / last_dfine keep the gradients at the concat and at the fine map (tests read them)."""
-        from ..trainer import _dist
-        stem, deep, route, head = self._nets(size)
-        S = size // 32
-        dist = _dist()
-        red = self.reducers[size]
-        dcat = head.backward_input(dnet.view(self.batch, S, S, -1))
-        if dist is not None:
-            red[3].reduce_all_async()
-        droute, dcoarse = E.passthrough_concat_darknet_backward(dcat, self.cf)
-        dpooled = deep.backward_input(dcoarse)
-        if dist is not None:
-            red[1].reduce_all_async()
-        dfine = route.backward_input(droute)
-        if dist is not None:
-            red[2].reduce_all_async()
-        E.accumulate(dfine, E.max_pool_2x2_backward(fine, dpooled))
-        self.last_dcat, self.last_dfine = dcat, dfine
-        world = red[0].backward_and_reduce(dfine)
-        if dist is not None:
-            red[1].join(); red[2].join(); red[3].join()
-        return world
-
-    def _mask_gradients(self, stem, head):
-        """after the all-reduce, before the optimizers: no gradient for the eight off-centre taps of Darknet's 1x1 layer
-        nor for the last layer's gamma / beta"""
-        gW = stem.layer_views(DARKNET_1X1_CORE_LAYER, grads=True)["W"]
-        taps = gW.view(9, -1)
-        E.zero_(taps[:4])
-        E.zero_(taps[5:])
-        g = head.layer_views(head.num_layers - 1, grads=True)
-        E.zero_(g["gamma"])
-        E.zero_(g["beta"])
-
-    def step(self, images, labels=None, truth=None, ntruth=None):
-        """YOLOv2Trainer.step's contract: one train step on the label grid or on the box list -> loss[5]"""
         if (labels is None) == (truth is None) or (truth is None) != (ntruth is None):
             raise ValueError("step() takes either labels or truth + ntruth, not both and not neither")
         size = int(images.shape[1])
@@ -508,7 +335,7 @@ class YOLOv2DarknetTrainer:
         else:
             loss, dnet = E.yolov2_loss_boxes(grid.contiguous(), truth, ntruth, self.anchors, size, True,
                                              self.box_scales(self.iteration))
-        self.last_dnet = dnet
+        self.last_dnet = dnet                                # the head's output gradient of this step (tests read it)
         world = self.backward(dnet, fine, size)
         scaler = self.opts[0].scaler
         for opt, net in zip(self.opts, nets):
@@ -516,29 +343,122 @@ class YOLOv2DarknetTrainer:
             if scaler is not None:
                 scaler.attach(net)
         if scaler is None:
-            self._mask_gradients(nets[0], nets[3])
+            self._mask_gradients(nets)
             for opt in self.opts:
                 opt.step(grad_mult=1.0 / world)
             return loss
         # every stack's sentinels into the one flag (on the gradients as the backward pass left them), the masks, then
-        # the four guarded updates: all of them or none
+        # the guarded updates: all of them or none
         for i, net in enumerate(nets):
             scaler.scan(net, more=(i > 0))
-        self._mask_gradients(nets[0], nets[3])
+        self._mask_gradients(nets)
         for i, opt in enumerate(self.opts):
             opt.step(grad_mult=1.0 / world, joint="first" if i == 0 else "next")
         return loss
 
     def flops_per_step(self, size=None, mfma_launches_only=False):
-        """YOLOv2Trainer.flops_per_step over the four stacks"""
+        """algorithmic FLOPs of one train step (3 x forward conv FLOPs, SURVEY 8(d) convention);
+        mfma_launches_only: without the 3-channel first layer, which has its own (non-GEMM) kernels"""
         size = size or self.default_size
-        S = size // 32
         tot = 0.0
-        for spec, h0 in zip(self.specs, (size, S, 2 * S, S)):
-            h = h0
+        for spec, units in zip(self.specs, self._topo.heights):
+            h = units * (size // 32)
             for (k, ci, co, pool) in spec:
                 if not (mfma_launches_only and ci == 3):
                     tot += 2.0 * self.batch * h * h * k * k * ci * co
                 if pool:
                     h = (h + 1) // 2
         return 3.0 * tot
+
+
+class YOLOv2Trainer(_Trainer):
+    """Train step of the YOLOv2 detector (NOT in the reference: its trainer is the YOLOv1 grid model).
+    Three conv-BN-leaky stacks, each with its own flat parameter / gradient buffer and Adam state.  With `sizes`
+    the input size may change from step to step (multi-scale {320..608}): one context + workspace per size, all
+    bound to the same three parameter sets (engine.Network(share_with=...)).
+    solver: None -- three engine.AdamOptimizer; a utils.solver.Solver -- three engine.DarknetSGD (momentum, weight decay
+    on the filters, the burn-in / steps / poly rate schedule), again with ONE loss scaler, step counter and rate."""
+
+    def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
+                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
+                 solver=None, bn_eps=None, topology="paper"):
+        if topology != "paper":
+            _topology(topology)
+            raise NotImplementedError("YOLOv2Trainer trains the paper topology only: the %r graph needs the gradient of "
+                                      "Darknet's reorg, a fourth optimizer and a last layer without batch statistics -- "
+                                      "YOLOv2DarknetTrainer has them" % topology)
+        _Trainer.__init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
+                          area_weight, prior_images, prior_scale, solver, bn_eps)
+
+
+class YOLOv2DarknetTrainer(_Trainer):
+    """Train step of the yolov2-voc.cfg graph (YOLOv2Detector(topology="darknet")): what a Darknet `.weights` file holds
+    can be fine-tuned here and written back (net_utils.load_darknet_weights / load_darknet_prefix / save_darknet_weights
+    take this object).  YOLOv2Trainer's constructor arguments and step() contract; FOUR stacks in file order -- stem,
+    13x13 stack, the 1x1 route convolution, head -- each with its flat buffers, optimizer and gradient reducer, ONE loss
+    scaler, step counter and rate; the multi-scale contexts share the four parameter sets.
+
+    Differences from YOLOv2Trainer: Darknet's input (uint8 BGR batches through engine.u8_to_darknet_input; float input
+    is RGB in [0, 1]); the route stack and Darknet's reorg (engine.passthrough_concat_darknet and its gradient, the
+    reorganised map in FRONT); batch-norm epsilon 1e-6; moving variances on the n - 1 estimate (bessel; the
+    normalisation itself stays on the biased variance: a known difference from Darknet); and a last layer that is
+    linear and runs WITHOUT batch statistics -- the head context has core_layers = 1, its 1x1 layer normalises with the
+    identity moving statistics the importer writes and its gamma / beta gradients are zeroed every step, so those four
+    arrays never move and the export folds exactly 1.  The eight off-centre taps of core layer 3 (Darknet's 1x1) get a
+    zero gradient every step too: they stay exactly zero and the model stays writable.
+    backward() leaves the gradients at the concat and at the fine map in last_dcat / last_dfine (tests read them)."""
+
+    topology = "darknet"
+    keeps_backward = True
+
+    def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
+                 device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
+                 solver=None, bn_eps=None, topology="darknet"):
+        if topology != "darknet":
+            raise ValueError("YOLOv2DarknetTrainer trains the \"darknet\" topology; topology %r is YOLOv2Trainer's" %
+                             (topology,))
+        _Trainer.__init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
+                          area_weight, prior_images, prior_scale, solver, bn_eps)
+
+    def _init_form(self, nets):
+        """a fresh model in the form a `.weights` file can hold: the 1x1 layer's off-centre taps zero, the last layer's
+        batch norm the importer's identity (utils/darknet_weights.to_layer_params)"""
+        stem, head = nets[0], nets[-1]
+        params = stem.export_params()
+        W = params[DARKNET_1X1_CORE_LAYER]["W"]
+        centre = W[1, 1].copy()
+        W[...] = 0
+        W[1, 1] = centre
+        stem.load_params(params)
+        params = head.export_params()
+        n = params[-1]["b"].size
+        params[-1].update(gamma=np.full(n, np.sqrt(1.0 + np.float64(self.bn_eps)), np.float32),
+                          beta=np.zeros(n, np.float32), moving_mean=np.zeros(n, np.float32),
+                          moving_var=np.ones(n, np.float32))
+        head.load_params(params)
+
+    def _mask_gradients(self, nets):
+        """after the all-reduce, before the optimizers: no gradient for the eight off-centre taps of Darknet's 1x1 layer
+        nor for the last layer's gamma / beta"""
+        stem, head = nets[0], nets[-1]
+        gW = stem.layer_views(DARKNET_1X1_CORE_LAYER, grads=True)["W"]
+        taps = gW.view(9, -1)
+        E.zero_(taps[:4])
+        E.zero_(taps[5:])
+        g = head.layer_views(head.num_layers - 1, grads=True)
+        E.zero_(g["gamma"])
+        E.zero_(g["beta"])
+
+    def resume_at(self, iteration):
+        """continue a run whose `.weights` snapshot stood at `iteration` (seen // batch): the step count the prior term
+        reads and, under Darknet's solver, the position in the rate schedule -- Darknet derives both from `seen`.  A
+        `.weights` file carries no optimizer state: moments and the loss scale start afresh, as in Darknet"""
+        self.iteration = int(iteration)
+        if self.solver is not None:
+            for opt in self.opts:
+                opt.t = self.iteration
+            scaler = self.opts[0].scaler
+            if scaler is not None:
+                c = scaler.ctrl.cpu()
+                c[1] = self.iteration
+                scaler.ctrl.copy_(c)
