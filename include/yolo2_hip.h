@@ -614,6 +614,47 @@ int y2_voc_match_batch(const int* det, const float* score, const int* count, con
                        const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
                        int max_out, float iou_thresh, int* flags, void* stream);
 
+/* ---- Darknet's test-time protocol (csrc/darknet_io.hip): the input its `letterbox_image` makes and the rows
+ *      its `valid` writes.  Everything is float32 in the stated operation order, double where it says so, no fused
+ *      multiply-add; the specifications are img_dataset/pascal_voc.letterbox_darknet and utils/detect_batch
+ *      (darknet_unmap, box_iou_darknet, anchor_detect_classes_darknet, match_image_f), bit for bit. */
+/* out [n][size][size][3] float32, RGB in [0, 1], pool / table / index as y2_letterbox_u8_batch: a canvas of 0.5 whose
+ * rectangle new_w x new_h at (ox, oy) of y2_letterbox_geometry holds Darknet's resize_image of the picture, with
+ * src(x, y, k) = float(byte of channel 2 - k) / 255:
+ *   horizontal, per source row: w_scale = float(w - 1) / float(new_w - 1); column c: sx = float(c) * w_scale, ix = (int)sx,
+ *     dx = sx - float(ix), part = (1 - dx) * src(ix) + dx * src(ix + 1); the last column (and a source one pixel wide) is
+ *     src(w - 1), copied;
+ *   vertical: h_scale = float(h - 1) / float(new_h - 1); row r: sy = float(r) * h_scale, iy = (int)sy, dy = sy - float(iy),
+ *     v = (1 - dy) * part(iy), then v = v + dy * part(iy + 1) unless r is the last row or h is 1.
+ * The last row never receives the second term, as in Darknet: where float(new_h - 1) * h_scale rounds below h - 1 it is
+ * nearly black.  An output extent of 1 takes the scale 0; ix, iy and their + 1 neighbours are clamped to the last column /
+ * row (never with a non-zero weight), so no read leaves an image.  A letterbox in DESTINATION space; the flip column is not
+ * read; an empty table row gives a canvas of 0.5.  Y2_ERR_ARG: a null pointer, n outside 1..65535, `size` not a multiple
+ * of 32 in 32..Y2_RESIZE_MAX_OUT_W, `out` not 16-byte aligned.  One launch, from the uint8 pool to the network's input. */
+int y2_letterbox_darknet_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, int n, int size,
+                               float* out, void* stream);
+/* y2_detect_anchor_classes_batch_lb's arguments, grid, ordering (descending score, ties by ascending candidate) and cap, for
+ * a batch made by y2_letterbox_darknet_batch at net_size = 32 S (else an argument error), with Darknet's boxes.  From
+ * cx, cy, w, h of y2_decode_anchors, N = net_size and new_w, new_h of y2_letterbox_geometry:
+ *   bx = float((double(cx) - double(N - new_w) / 2. / double(N)) / double(float(new_w) / float(N)));
+ *   bw = w * (float(N) / float(new_w));  then bx = bx * float(width), bw = bw * float(width);  by, bh likewise.
+ * Valid in class c: score[c] > score_thresh (not NaN) and the four values finite; nothing else.  A kept box suppresses every
+ * later box of the class whose float32 IoU on (bx, by, bw, bh) is > iou_thresh: overlap = min(x1 + w1 / 2, x2 + w2 / 2) -
+ * max(x1 - w1 / 2, x2 - w2 / 2) per axis, inter = 0 if either is negative else their product, union = (aw * ah + bw * bh) -
+ * inter; a NaN suppresses nothing.  Row: xmin = float(double(bx) - double(bw) / 2. + 1.) raised to 1, xmax =
+ * float(double(bx) + double(bw) / 2. + 1.) lowered to float(width), ymin / ymax likewise; a box empty after that is kept.
+ * det int32 [n][num_class][max_per_class][6]: words 0..3 are the BIT PATTERNS of the float32 xmin, ymin, xmax, ymax, word 4
+ * the class, word 5 the candidate (unused rows all -1); score and count as y2_detect_anchor_classes_batch. */
+int y2_detect_anchor_classes_batch_dk(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
+                                      int n, int S, int B, int num_class, float score_thresh, float iou_thresh,
+                                      int max_per_class, int net_size, int* det, float* score, int* count,
+                                      void* stream);
+/* y2_voc_match_batch with words 0..3 of a det row read as float32 (the rows of y2_detect_anchor_classes_batch_dk): the
+ * float64 IoU with + 1 extents works on those four values promoted to double.  The same flags, limits and launch. */
+int y2_voc_match_batch_f(const int* det, const float* score, const int* count, const double* boxes,
+                         const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
+                         int max_out, float iou_thresh, int* flags, void* stream);
+
 /* ---- classifier scoring over several views of an image (csrc/score.hip; specification: utils/score_views.py, float64).
  * logits [n * views][classes] fp32, row b * views + v is view v of image b.  Per view p_v[c] = exp(x_v[c] - max_v) /
  * sum_c exp(x_v[c] - max_v), then p[c] = (1 / views) * sum_v p_v[c] (Darknet's validate_classifier_10 averages the

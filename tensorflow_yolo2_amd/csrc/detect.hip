@@ -10,21 +10,13 @@
 #include "kernels.h"
 #include "anchor_decode.h"
 #include "letterbox.h"
+#include "detect_common.h"
 using namespace y2;
 
 namespace {
 
 constexpr int kMaxCand = kDetectMaxCand;   // candidates (S * S * B) of one image; LDS below is sized for it: 29 KB
-
-// IoU of two inclusive pixel boxes with the devkit's +1 extents (utils/voc_eval.box_iou_voc): `a` is its `box`
-Y2_DEV double iou_voc(double a0, double a1, double a2, double a3, double b0, double b1, double b2, double b3) {
-    const double ixmin = fmax(b0, a0), iymin = fmax(b1, a1);
-    const double ixmax = fmin(b2, a2), iymax = fmin(b3, a3);
-    const double iw = fmax(ixmax - ixmin + 1.0, 0.0), ih = fmax(iymax - iymin + 1.0, 0.0);
-    const double inter = iw * ih;
-    const double uni = ((a2 - a0 + 1.0) * (a3 - a1 + 1.0) + (b2 - b0 + 1.0) * (b3 - b1 + 1.0)) - inter;
-    return inter / uni;
-}
+// (the sort word, the devkit's IoU and the matching kernel are detect_common.h's, shared with darknet_io.hip)
 
 // grid (n), one workgroup per image, KP = the next power of two of K = S * S * B (at least 64) lanes.
 //   1. lane i decodes candidate i (cell i / B: row cell / S, column cell % S) into LDS: the clipped 1-based box, the
@@ -144,21 +136,6 @@ __global__ __launch_bounds__(kMaxCand) void detect_grid_kernel(const float* __re
 constexpr int kAnchorMaxCand = kDetectAnchorMaxCand;   // S * S * B of one image: 19 * 19 * 5 = 1805 at 608 x 608
 constexpr int kAnchorLanes = 1024;                     // the workgroup; above it a lane owns two decode and sort slots
 constexpr int kAnchorSlotBytes = 8 + 5 * 4 + 1;        // sort word, four corners, class, suppressed flag
-
-// (score, candidate) as one 64-bit word whose unsigned order is "score descending, then index ascending" read from the
-// top: the float's bits made monotonic in the high half, ~index in the low half.  The words of a workgroup are distinct
-// (the indices are), so the sort needs one compare.  A valid score is sigmoid * softmax >= +0 or it is not kept at all,
-// so -0.0 and +0.0, equal as floats but not as bits, never meet.
-Y2_DEV uint64_t sort_word(float key, int idx) {
-    const uint32_t u = __float_as_uint(key);
-    const uint32_t m = u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-    return ((uint64_t)m << 32) | (uint32_t)(0xffffffffu - (uint32_t)idx);
-}
-Y2_DEV int word_index(uint64_t w) { return (int)(0xffffffffu - (uint32_t)w); }
-Y2_DEV float word_key(uint64_t w) {
-    const uint32_t m = (uint32_t)(w >> 32);
-    return __uint_as_float(m ^ ((m >> 31) ? 0x80000000u : 0xffffffffu));
-}
 
 // Where the input was letterboxed (letterbox.h; net_size = 32 S): the map from a box relative to the net_size canvas to
 // the pixels of the original image, the exact inverse of the embedding, in the specification's operation order
@@ -425,87 +402,6 @@ __global__ __launch_bounds__(kClassLanes) void detect_anchor_classes_kernel(
     for (int i = kept + tid; i < max_out; i += nt) srow[i] = 0.0f;
 }
 
-// first maximum over the wave of (iou, object index): the larger iou, ties to the lower index
-Y2_DEV void wave_first_max(double& best, int& arg) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        const double ob = __shfl_xor(best, off, kWave);
-        const int oa = __shfl_xor(arg, off, kWave);
-        if (ob > best || (ob == best && oa < arg)) {
-            best = ob;
-            arg = oa;
-        }
-    }
-}
-
-// grid (n), ONE 64-lane wave per image.  Lane l holds objects l, l + 64, ... of the image (the first one in registers,
-// the others re-read through the cache: VOC images have at most 42 objects) with their `difficult` and `taken` bits in
-// two 16-bit masks (max_obj <= 1024).  The detections are walked in row order; each step is a wave-wide first maximum
-// of the float64 IoU over the objects of the detection's class, and the lane that owns the winner settles the flag.
-__global__ __launch_bounds__(kWave) void voc_match_kernel(const int* __restrict__ det, const int* __restrict__ count,
-                                                          const double* __restrict__ boxes,
-                                                          const int32_t* __restrict__ counts,
-                                                          const uint8_t* __restrict__ difficult,
-                                                          const int32_t* __restrict__ index, int max_obj, int max_out,
-                                                          float iou_thresh, int* __restrict__ flags) {
-    const int img = blockIdx.x, lane = threadIdx.x;
-    const size_t e = index ? (size_t)index[img] : (size_t)img;
-    const int cnt = min(max(counts[e], 0), max_obj);
-    const int ndet = min(max(count[img], 0), max_out);
-    const double* bx = boxes + e * (size_t)max_obj * 5;
-    const uint8_t* df = difficult + e * (size_t)max_obj;
-    const int strides = (cnt + kWave - 1) / kWave;
-    unsigned hard = 0, taken = 0;
-    for (int k = 0; k < strides; ++k) {
-        const int j = lane + kWave * k;
-        if (j < cnt && df[j]) hard |= 1u << k;
-    }
-    double g0 = 0, g1 = 0, g2 = 0, g3 = 0, gc = -1.0;
-    if (lane < cnt) {
-        g0 = bx[lane * 5 + 0]; g1 = bx[lane * 5 + 1]; g2 = bx[lane * 5 + 2]; g3 = bx[lane * 5 + 3]; gc = bx[lane * 5 + 4];
-    }
-    const double thr = (double)iou_thresh;
-    const int* drow = det + (size_t)img * max_out * 6;
-    int* frow = flags + (size_t)img * max_out;
-    for (int d = 0; d < ndet; ++d) {
-        const double d0 = drow[d * 6 + 0], d1 = drow[d * 6 + 1], d2 = drow[d * 6 + 2], d3 = drow[d * 6 + 3];
-        const double dc = drow[d * 6 + 4];
-        double best = -1.0;
-        int arg = 0x7fffffff;
-        if (lane < cnt && gc == dc) {
-            best = iou_voc(d0, d1, d2, d3, g0, g1, g2, g3);
-            arg = lane;
-        }
-        for (int k = 1; k < strides; ++k) {
-            const int j = lane + kWave * k;
-            if (j < cnt && bx[j * 5 + 4] == dc) {
-                const double v = iou_voc(d0, d1, d2, d3, bx[j * 5 + 0], bx[j * 5 + 1], bx[j * 5 + 2], bx[j * 5 + 3]);
-                if (v > best || arg == 0x7fffffff) {           // (ascending j: the strict > keeps the lane's first maximum)
-                    best = v;
-                    arg = j;
-                }
-            }
-        }
-        wave_first_max(best, arg);
-        int flag = 0;
-        if (arg != 0x7fffffff && best >= thr) {                // uniform: every lane holds the winner
-            const int owner = arg & (kWave - 1);
-            const unsigned bit = 1u << (arg / kWave);
-            int mine = 0;
-            if (lane == owner) {
-                if (hard & bit) mine = 2;
-                else if (!(taken & bit)) {
-                    mine = 1;
-                    taken |= bit;
-                }
-            }
-            flag = __shfl(mine, owner, kWave);
-        }
-        if (lane == 0) frow[d] = flag;
-    }
-    for (int d = ndet + lane; d < max_out; d += kWave) frow[d] = -1;
-}
-
 }  // namespace
 
 extern "C" {
@@ -634,7 +530,7 @@ int y2_voc_match_batch(const int* det, const float* score, const int* count, con
     if (max_obj < 1 || max_obj > kMatchMaxObj)
         return fail(Y2_ERR_ARG, "y2_voc_match_batch: max_obj = %d outside 1..Y2_MATCH_MAX_OBJECTS = %d", max_obj,
                     kMatchMaxObj);
-    hipLaunchKernelGGL(voc_match_kernel, dim3(n), dim3(kWave), 0, (hipStream_t)stream, det, count, boxes, counts,
+    hipLaunchKernelGGL(voc_match_kernel<false>, dim3(n), dim3(kWave), 0, (hipStream_t)stream, det, count, boxes, counts,
                        difficult, index, max_obj, max_out, iou_thresh, flags);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_voc_match_batch: %s", hipGetErrorString(e));

@@ -1179,6 +1179,90 @@ def voc_match_batch(det, score, count, boxes, counts, difficult, index=None, iou
     return flags
 
 
+# ---- Darknet's test-time protocol (csrc/darknet_io.hip)
+def letterbox_darknet_batch(pool, table, index, n, size, out=None):
+    """letterbox_batch's pool / table / index -> out float32 [n,size,size,3], RGB in [0, 1]: every entry through Darknet's
+    float letterbox_image (corner-aligned two-pass bilinear in float32, bars of 0.5;
+    img_dataset/pascal_voc.letterbox_darknet, bit for bit), one launch from the uint8 pool to the network's input on the
+    current stream.  The batch detect_anchor_classes_batch_darknet(..., net_size=size) un-maps."""
+    lib = _lib.load()
+    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert table.shape[0] >= n
+    if out is None:
+        out = torch.empty((n, size, size, 3), dtype=torch.float32, device=pool.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * size * size * 3
+    check(lib.y2_letterbox_darknet_batch(_ptr(pool), _ptr(table), _ptr(index), int(n), int(size), _ptr(out), _stream()))
+    return out
+
+
+def detect_anchor_classes_batch_darknet(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45,
+                                        max_per_class=32, out=None, net_size=None):
+    """detect_anchor_classes_batch's arguments and outputs under Darknet's protocol, for a batch made by
+    letterbox_darknet_batch at net_size (required: 32 S): the float un-map of correct_region_boxes, validity by score and
+    finiteness alone, a float centre-box IoU in the walk, and rows whose words 0..3 are the BIT PATTERNS of the float32
+    corners -- det[..., :4].view(torch.float32) -- so det keeps its int32 layout
+    (utils/detect_batch.anchor_detect_classes_darknet on decode_anchors of the same net, bit for bit).
+    voc_match_batch_f reads the [n * C] view."""
+    lib = _lib.load()
+    if net_size is None:
+        raise ValueError("detect_anchor_classes_batch_darknet needs net_size: Darknet's protocol is letterboxed")
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, S, _, B, d = net.shape
+    assert net.shape[2] == S and d > 5, net.shape
+    C = d - 5
+    if torch.is_tensor(anchors):
+        an = anchors
+        assert an.is_cuda and an.dtype == torch.float32 and an.is_contiguous()
+    else:
+        an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
+    assert an.numel() == 2 * B, (tuple(an.shape), B)
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert table.shape[0] >= n
+    if out is None:
+        out = (torch.empty((n, C, max_per_class, 6), dtype=torch.int32, device=net.device),
+               torch.empty((n, C, max_per_class), dtype=torch.float32, device=net.device),
+               torch.empty((n, C), dtype=torch.int32, device=net.device))
+    det, score, count = out
+    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * C * max_per_class * 6
+    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * C * max_per_class
+    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n * C
+    check(lib.y2_detect_anchor_classes_batch_dk(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C,
+                                                float(score_thresh), float(iou_thresh), int(max_per_class),
+                                                _net_size(net_size, S), _ptr(det), _ptr(score), _ptr(count), _stream()))
+    return det, score, count
+
+
+def voc_match_batch_f(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):
+    """voc_match_batch for rows whose words 0..3 hold float32 corners (detect_anchor_classes_batch_darknet):
+    utils/detect_batch.match_image_f, bit for bit"""
+    lib = _lib.load()
+    assert det.is_cuda and det.dtype == torch.int32 and det.is_contiguous() and det.dim() == 3 and det.shape[2] == 6
+    n, max_out = det.shape[0], det.shape[1]
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == n
+    assert score is None or (score.dtype == torch.float32 and score.is_contiguous() and score.numel() == n * max_out)
+    assert boxes.is_cuda and boxes.dtype == torch.float64 and boxes.is_contiguous() and boxes.dim() == 3
+    max_obj = boxes.shape[1]
+    assert boxes.shape[2] == 5 and counts.dtype == torch.int32 and counts.numel() == boxes.shape[0]
+    assert difficult.is_cuda and difficult.dtype == torch.uint8 and difficult.is_contiguous()
+    assert tuple(difficult.shape) == (boxes.shape[0], max_obj), difficult.shape
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
+    else:
+        assert boxes.shape[0] >= n
+    flags = torch.empty((n, max_out), dtype=torch.int32, device=det.device) if out is None else out
+    assert flags.is_contiguous() and flags.dtype == torch.int32 and flags.numel() == n * max_out
+    check(lib.y2_voc_match_batch_f(_ptr(det), _ptr(score), _ptr(count), _ptr(boxes), _ptr(counts), _ptr(difficult),
+                                   _ptr(index), n, max_obj, max_out, float(iou_thresh), _ptr(flags), _stream()))
+    return flags
+
+
 def softmax_cross_entropy(logits, labels, need_grad=True):
     """sparse_softmax_cross_entropy_with_logits + reduce_mean (imagenet_train_darknet.py:51-53)."""
     lib = _lib.load()

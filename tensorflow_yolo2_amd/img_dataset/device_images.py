@@ -23,6 +23,6 @@ class DeviceImages(DevicePool):
         self.entries = [{'imname': p, 'shape': img.shape[:2]} for p, img in zip(self.paths, images)]
         self._build_pool(images.__getitem__, max_pool_bytes)
 
-    def batch(self, size, start, letterbox=True, fill=127):
+    def batch(self, size, start, letterbox=True, fill=127, protocol="repo"):
         """(images [B, size, size, 3] uint8 BGR, valid) of the entries start .. start + B - 1: DeviceVOC.eval_batch"""
-        return self.list_batch("DeviceImages.batch", size, start, letterbox, fill)
+        return self.list_batch("DeviceImages.batch", size, start, letterbox, fill, protocol)

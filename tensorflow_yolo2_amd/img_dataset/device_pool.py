@@ -126,15 +126,23 @@ class DevicePool(object):
         if any(tuple(d) != tuple(mine) for d in every):
             raise RuntimeError("ranks hold different image lists or orders (entries, crc32 per rank): %r" % (every,))
 
-    def list_batch(self, who, size, start, letterbox, fill):
+    def list_batch(self, who, size, start, letterbox, fill, protocol="repo"):
         """(images [B, size, size, 3] uint8 BGR, valid): entries start .. start + B - 1 IN LIST ORDER, stretched (or
         letterboxed: the aspect ratio kept, the rest of the square `fill`) on the current stream; the last batch repeats
         its final entry and `valid` is the number of slots that are entries of their own.  Sets `eval_index`, the int32
-        [B] device tensor of the slots' entries; the buffers are kept per size.  `who` names the caller in a refusal."""
+        [B] device tensor of the slots' entries; the buffers are kept per size.  `who` names the caller in a refusal.
+        protocol="darknet": the images are float32 RGB in [0, 1] instead, Darknet's letterbox_image
+        (pascal_voc.letterbox_darknet; y2_letterbox_darknet_batch: one launch from the pool to the network's input), in a
+        buffer of their own per size.  That protocol is letterboxed by definition and its bars are 0.5: `letterbox` and
+        `fill` are not read, and a `fill` other than the default is refused."""
         import torch
         from .. import _lib
         need_gpu(self.device, who)
         check_size(size)
+        if protocol == "darknet":
+            return self._list_batch_darknet(size, start, fill)
+        if protocol != "repo":
+            raise ValueError("protocol %r is neither 'repo' nor 'darknet'" % (protocol,))
         if letterbox and not 0 <= int(fill) <= 255:
             raise ValueError("fill %r outside 0..255" % (fill,))
         n = len(self.entries)
@@ -152,5 +160,25 @@ class DevicePool(object):
             _lib.check(_lib.load().y2_resize_bilinear_u8_batch(_ptr(self.pool), _ptr(self.table), _ptr(index),
                                                                self.batch_size, size, size, _ptr(images),
                                                                stream_of(images)))
+        self.eval_index = index
+        return images, min(self.batch_size, n - start)
+
+    def _list_batch_darknet(self, size, start, fill):
+        """list_batch under Darknet's protocol: the same index and last-batch rule, a float32 batch kept per size"""
+        import torch
+        from .. import _lib
+        if fill != 127:
+            raise ValueError("fill = %r with protocol='darknet': its bars are 0.5 and `fill` is not read" % (fill,))
+        n = len(self.entries)
+        host = list_index(start, self.batch_size, n).astype(np.int32)
+        key = ("darknet", size)
+        if key not in self._eval_buffers:
+            self._eval_buffers[key] = (
+                torch.empty((self.batch_size, size, size, 3), dtype=torch.float32, device=self.device),
+                torch.empty(self.batch_size, dtype=torch.int32, device=self.device))
+        images, index = self._eval_buffers[key]
+        upload_async(index, host)
+        _lib.check(_lib.load().y2_letterbox_darknet_batch(_ptr(self.pool), _ptr(self.table), _ptr(index), self.batch_size,
+                                                          size, _ptr(images), stream_of(images)))
         self.eval_index = index
         return images, min(self.batch_size, n - start)

@@ -189,13 +189,14 @@ class DeviceVOC(DevicePool, ShardedOrder):
             self._difficult = self._upload(self.difficult_host)
         return self._difficult
 
-    def eval_batch(self, size, start, letterbox=False, fill=127):
+    def eval_batch(self, size, start, letterbox=False, fill=127, protocol="repo"):
         """(images [B, size, size, 3] uint8 BGR, valid): entries start .. start + B - 1 of the image list IN LIST ORDER,
         resized on the current stream; the last batch repeats its final entry to fill the fixed batch and `valid` is the
         number of slots that are entries of their own.  `eval_index` is the int32 [B] device tensor of the slots' entries
         (the `index` of the detect and match calls).  The cursor of get() is neither read nor moved.  letterbox: the
         aspect ratio is kept and the rest of the square is `fill` (pascal_voc.letterbox_u8; y2_letterbox_u8_batch) --
-        the detect calls then take net_size=size; the same buffers, index and refusals."""
+        the detect calls then take net_size=size; the same buffers, index and refusals.  protocol="darknet": float32
+        RGB in [0, 1] through Darknet's letterbox_image instead (DevicePool.list_batch)."""
         if self.flipped or self.augment is not None:
             raise ValueError("evaluation reads the plain image list: build the DeviceVOC with flipped=False, augment=None")
-        return self.list_batch("DeviceVOC.eval_batch", size, start, letterbox, fill)
+        return self.list_batch("DeviceVOC.eval_batch", size, start, letterbox, fill, protocol)

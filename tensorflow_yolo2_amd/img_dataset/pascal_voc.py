@@ -181,6 +181,50 @@ def letterbox_u8(img, size, fill=127):
     return out
 
 
+def letterbox_darknet(img, size):
+    """[H, W, 3] uint8 BGR -> the [size, size, 3] float32 RGB input in [0, 1] that Darknet's `letterbox_image` makes: a
+    canvas of 0.5 whose rectangle letterbox_geometry names holds Darknet's `resize_image` of the picture.  All float32,
+    no fused multiply-add:
+      src(x, y, k) = float32(byte of channel 2 - k) / 255
+      horizontal, per source row: w_scale = float(W - 1) / float(new_w - 1); column c: sx = float(c) * w_scale,
+        ix = int(sx), dx = sx - float(ix), part = (1 - dx) * src(ix) + dx * src(ix + 1); the LAST column (and every
+        column of a source one pixel wide) is src(W - 1), copied
+      vertical: h_scale = float(H - 1) / float(new_h - 1); row r: sy = float(r) * h_scale, iy = int(sy),
+        dy = sy - float(iy), v = (1 - dy) * part(iy), and v = v + dy * part(iy + 1) UNLESS r is the last row (or H is 1).
+    The quirk stays: the last row never receives the second term, so where float(new_h - 1) * h_scale rounds to just
+    below H - 1 it is (1 - dy) * part(iy) with dy ~ 1, nearly black ((H, new_h) = (8, 24) is the smallest pair).
+    Published weights were scored on such inputs.  Where Darknet is undefined: an output extent of 1 takes the scale 0
+    (it would divide by zero), and ix, iy and their + 1 neighbours are clamped to the last column / row (unreachable
+    with a non-zero weight).  The specification of y2_letterbox_darknet_batch (csrc/darknet_io.hip), bit for bit."""
+    img = np.asarray(img)
+    assert img.ndim == 3 and img.shape[2] == 3 and img.dtype == np.uint8, (img.shape, img.dtype)
+    f = np.float32
+    H, W = img.shape[:2]
+    new_w, new_h, ox, oy = letterbox_geometry(H, W, size)
+    src = img[:, :, ::-1].astype(f) / f(255.0)                            # [H][W][3] RGB
+    w_scale = f(W - 1) / f(new_w - 1) if new_w > 1 else f(0.0)
+    h_scale = f(H - 1) / f(new_h - 1) if new_h > 1 else f(0.0)
+    sx = np.arange(new_w).astype(f) * w_scale
+    ix = sx.astype(np.int64)
+    dx = (sx - ix.astype(f))[None, :, None]
+    ix0, ix1 = np.minimum(ix, W - 1), np.minimum(ix + 1, W - 1)
+    part = (f(1.0) - dx) * src[:, ix0] + dx * src[:, ix1]                 # [H][new_w][3]
+    part[:, new_w - 1] = src[:, W - 1]
+    if W == 1:
+        part[:] = src[:, :1]
+    sy = np.arange(new_h).astype(f) * h_scale
+    iy = sy.astype(np.int64)
+    dy = (sy - iy.astype(f))[:, None, None]
+    iy0, iy1 = np.minimum(iy, H - 1), np.minimum(iy + 1, H - 1)
+    pic = (f(1.0) - dy) * part[iy0]
+    if H != 1:
+        pic[:new_h - 1] = pic[:new_h - 1] + dy[:new_h - 1] * part[iy1[:new_h - 1]]
+    assert pic.dtype == np.float32
+    out = np.full((int(size), int(size), 3), 0.5, np.float32)
+    out[oy:oy + new_h, ox:ox + new_w] = pic
+    return out
+
+
 def image_read(image_bgr_u8, image_size, flipped=False):
     """pascal_voc.image_read (:60-67) on an already decoded BGR uint8 array."""
     image = resize_bilinear_u8(image_bgr_u8, image_size, image_size).astype(np.float32)

@@ -1,7 +1,7 @@
 """VOC mAP of the YOLOv2 anchor detector over an image set (not in the reference, which has no evaluation code):
     python -m tensorflow_yolo2_amd.pascal.pascal_eval_yolov2 --devkit data/VOCdevkit --image-set test \
         [--weights FILE | --ckpt-dir DIR] [--size 416] [--batch 32] [--metric 07|10]
-        [--per-class [--max-per-class 32]] [--letterbox [--fill 127]] [--results-dir DIR]
+        [--per-class [--max-per-class 32]] [--letterbox [--fill 127]] [--protocol repo|darknet] [--results-dir DIR]
 The shape is pascal_eval_darknet.py's.  The images come from the device-resident pool in list order; per batch, four
 calls on one stream and nothing on the host:
     DeviceVOC.eval_batch (resize) -> YOLOv2Detector.detect_batch = forward on the uint8 batch (moving statistics) ->
@@ -18,7 +18,11 @@ y2_detect_anchor_classes_batch_lb); the default is the plain stretch, bit for bi
 The anchors and the class count are the snapshot's (pascal_train_yolov2.py); with neither --weights nor --ckpt-dir the
 initial values are evaluated with the published VOC anchors: a plumbing run.  --darknet-weights FILE evaluates a file
 Darknet wrote for yolov2-voc.cfg instead (the "darknet" topology of yolo2_nets/yolov2.py, net_utils.load_darknet_weights):
-    pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --per-class --letterbox"""
+    pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --per-class --letterbox
+and --protocol darknet scores it as Darknet's `valid` would (it implies the two switches): the float letterbox with bars
+of 0.5 in one launch from the pool (y2_letterbox_darknet_batch), Darknet's float un-map, float NMS and float corners
+(y2_detect_anchor_classes_batch_dk), the matcher on those (y2_voc_match_batch_f), and "%f" results files:
+    pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --protocol darknet"""
 import argparse
 import sys
 
@@ -49,7 +53,11 @@ def parse_args(argv=None):
     ap.add_argument("--letterbox", action="store_true",
                     help="keep every image's aspect ratio: embed it in the square input between bars of --fill and "
                          "un-map the boxes from that rectangle, as Darknet's test-time input (default: a plain stretch)")
-    ap.add_argument("--fill", type=int, default=127, help="with --letterbox: the value of the bars, 0..255")
+    ap.add_argument("--fill", type=int, default=None, help="with --letterbox: the value of the bars, 0..255 (127)")
+    ap.add_argument("--protocol", default="repo", choices=("repo", "darknet"),
+                    help="darknet: Darknet's test-time protocol -- its float letterbox with bars of 0.5, its float un-map "
+                         "and NMS, float corners in the rows and the results files.  Implies --per-class --letterbox; needs "
+                         "--darknet-weights; not with --fill (default: this repository's integer-pixel protocol)")
     ap.add_argument("--results-dir", default=None,
                     help="write the devkit's comp4_det_<image-set>_<class>.txt files (image_id score xmin ymin xmax "
                          "ymax) there, from the rows of either form")
@@ -59,6 +67,15 @@ def parse_args(argv=None):
     model_flags.check_size(ap, args)
     if args.batch < 1 or args.max_out < 1 or args.width_div < 1 or args.max_per_class < 1:
         ap.error("--batch, --max-out, --max-per-class and --width-div must be at least 1")
+    if args.protocol == "darknet":
+        if args.fill is not None:
+            ap.error("--fill is not read with --protocol darknet: Darknet's bars are 0.5")
+        if not args.darknet_weights:
+            ap.error("--protocol darknet needs the darknet topology (--darknet-weights FILE): the paper topology's input "
+                     "is BGR in [-1, 1)")
+        args.per_class = args.letterbox = True
+    if args.fill is None:
+        args.fill = 127
     if not 0 <= args.fill <= 255:
         ap.error("--fill %d outside 0..255" % args.fill)
     model_flags.check_weights(ap, args)
@@ -74,7 +91,8 @@ def main(argv=None):
         raise ValueError("snapshot %s: num_class is %d, the image set has %d" % (snapshot, num_class, imdb.num_class))
     detector, restored = model_flags.build_detector(args, snapshot, anchors, num_class, bn_eps)
     result = evaluate_yolov2(detector, imdb, args.size, args.thresh, args.nms, args.max_out, args.metric == "07",
-                             args.keep_grids, args.per_class, args.max_per_class, args.letterbox, args.fill)
+                             args.keep_grids, args.per_class, args.max_per_class, args.letterbox, args.fill,
+                             protocol=args.protocol)
     for c in sorted(result["aps"]):
         print('AP for {:s} = {:.4f}'.format(pascal_voc.CLASSES[c], result["aps"][c]))
     print('Mean AP = {:.4f} ({:d} images, {:d} detections, VOC{:s} metric)'.format(
@@ -91,13 +109,27 @@ def main(argv=None):
 
 
 def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, use_07_metric=True, keep_grids=False,
-                    per_class=False, max_per_class=32, letterbox=False, fill=127):
+                    per_class=False, max_per_class=32, letterbox=False, fill=127, protocol="repo"):
     """one pass over imdb's image list through `detector` (a YOLOv2Detector of imdb.batch_size images of `size`):
     {"mAP", "aps", "rows", "count", "npos"[, "grids"]} as pascal_eval_darknet.evaluate; everything per image runs on the
     device, one copy at the end.  per_class: one row per (candidate, class) as Darknet's `valid` writes them, at most
     max_per_class per image and class (max_out is not read); an image is then num_class segments of the same buffer,
     "count" is [entries][num_class] and "saturated" the number of segments whose count reached max_per_class.
-    letterbox: the batches are letterboxed between bars of `fill` and the boxes un-mapped from each picture's rectangle"""
+    letterbox: the batches are letterboxed between bars of `fill` and the boxes un-mapped from each picture's rectangle.
+    protocol="darknet": Darknet's test-time protocol -- its float letterbox from the pool to the network's input in one
+    launch, its float un-map and NMS, the matcher on float corners (csrc/darknet_io.hip).  It is per_class and
+    letterboxed by definition (both must be set), needs a detector of the "darknet" topology and the default `fill`;
+    rows["box"] is then float32"""
+    if protocol not in ("repo", "darknet"):
+        raise ValueError("protocol %r is neither 'repo' nor 'darknet'" % (protocol,))
+    darknet = protocol == "darknet"
+    if darknet and not (per_class and letterbox):
+        raise ValueError("protocol='darknet' scores one row per (box, class) on a letterboxed input: per_class=True, "
+                         "letterbox=True")
+    if darknet and getattr(detector, "topology", "paper") != "darknet":
+        raise ValueError("protocol='darknet' needs a detector of the \"darknet\" topology, not %r"
+                         % (getattr(detector, "topology", "paper"),))
+    match = engine.voc_match_batch_f if darknet else engine.voc_match_batch
     n = imdb.batch_size
     assert detector.batch == n and detector.size == size, (detector.batch, detector.size, n, size)
     S, B, D = detector.S, detector.B, 5 + detector.num_class
@@ -118,20 +150,27 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     difficult = imdb.difficult
     for k in range(batches):
         lo, m = k * n * segs, n * segs
-        images, _valid = imdb.eval_batch(size, k * n, letterbox=letterbox, fill=fill)
+        if darknet:
+            images, _valid = imdb.eval_batch(size, k * n, letterbox=True, fill=fill, protocol="darknet")
+        else:
+            images, _valid = imdb.eval_batch(size, k * n, letterbox=letterbox, fill=fill)
         out = (det[lo:lo + m], score[lo:lo + m], count[lo:lo + m])
         grid_out = grids[k * n:k * n + n] if grids is not None else None
         index = imdb.eval_index
-        if per_class:
+        if darknet:
+            detector.detect_classes_batch(images, imdb.table, index, thresh, nms, max_per_class, out=out,
+                                          grid_out=grid_out, letterbox=True, protocol="darknet")
+        elif per_class:
             detector.detect_classes_batch(images, imdb.table, index, thresh, nms, max_per_class, out=out,
                                           grid_out=grid_out, letterbox=letterbox)
+        if per_class:
             seg_index.view(n, segs).copy_(index[:n, None].expand(n, segs))   # on the device: nothing waits
             index = seg_index
         else:
             detector.detect_batch(images, imdb.table, index, thresh, nms, max_out, out=out, grid_out=grid_out,
                                   letterbox=letterbox)
-        engine.voc_match_batch(det[lo:lo + m], score[lo:lo + m], count[lo:lo + m], imdb.boxes, imdb.counts, difficult,
-                               index, 0.5, out=flags[lo:lo + m])
+        match(det[lo:lo + m], score[lo:lo + m], count[lo:lo + m], imdb.boxes, imdb.counts, difficult, index, 0.5,
+              out=flags[lo:lo + m])
     host = acc.cpu().numpy()                                  # the one device-to-host copy (it waits for the stream)
     live_segs = entries * segs
     det_h = host[:N * R * 6].reshape(N, R, 6)[:live_segs]
@@ -139,7 +178,10 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     flags_h = host[N * R * 7:N * R * 8].reshape(N, R)[:live_segs]
     count_h = host[N * R * 8:][:live_segs]
     live = np.arange(R)[None, :] < count_h[:, None]            # image order (then class), each segment in descending score
-    rows = {"image": np.nonzero(live)[0] // segs, "box": det_h[live][:, :4], "class": det_h[live][:, 4],
+    box = det_h[live][:, :4]
+    if darknet:
+        box = np.ascontiguousarray(box).view(np.float32)       # words 0..3 hold the bit patterns of the float corners
+    rows = {"image": np.nonzero(live)[0] // segs, "box": box, "class": det_h[live][:, 4],
             "candidate": det_h[live][:, 5], "score": score_h[live], "flag": flags_h[live]}
     npos = detect_batch.npos_from_objects([o[4] for e in imdb.entries for o in e['objs']],
                                           [d for e in imdb.entries for d in e['difficult']])

@@ -177,6 +177,147 @@ def anchor_detect_classes(boxes, scores, im_w, im_h, score_thresh, iou_thresh, m
     return det, score, count
 
 
+# ---- Darknet's test-time protocol: float un-map, float centre-box NMS, float corners.  The specification
+#      of csrc/darknet_io.hip; float32 in this operation order, double where it says so.
+def darknet_unmap(boxes, im_w, im_h, net_size):
+    """Darknet's correct_region_boxes for a letterboxed input: boxes float32 [K][4] = cx, cy, w, h relative to the
+    net_size canvas -> float32 [K][4] = bx, by, bw, bh in pixels of the original image.  With new_w, new_h of
+    letterbox_geometry: bx = float((double(cx) - double(N - new_w) / 2. / double(N)) / double(float(new_w) / float(N))),
+    bw = w * (float(N) / float(new_w)), then bx * float(im_w), bw * float(im_w); y likewise.  The half offset is NOT
+    rounded to the pixel the picture was embedded at: that is Darknet's"""
+    from ..img_dataset.pascal_voc import letterbox_geometry
+    if int(net_size) != net_size or net_size < 32 or net_size % 32:
+        raise ValueError("net_size %r is not a positive multiple of 32" % (net_size,))
+    f, d = np.float32, np.float64
+    boxes = np.asarray(boxes, f).reshape(-1, 4)
+    im_w, im_h, n = int(im_w), int(im_h), int(net_size)
+    new_w, new_h, _, _ = letterbox_geometry(im_h, im_w, n)
+    out = np.empty_like(boxes)
+    with np.errstate(all="ignore"):
+        for k, (new, im) in enumerate(((new_w, im_w), (new_h, im_h))):
+            off = d(n - new) / d(2.0) / d(n)
+            sc = d(f(new) / f(n))
+            centre = ((boxes[:, k].astype(d) - off) / sc).astype(f)
+            extent = boxes[:, 2 + k] * (f(n) / f(new))
+            out[:, k] = centre * f(im)
+            out[:, 2 + k] = extent * f(im)
+    return out
+
+
+def box_iou_darknet(a, b):
+    """Darknet's box_iou on centre boxes (x, y, w, h), all float32: a [4], b [..., 4] -> float32 [...].
+    overlap = min(x1 + w1 / 2, x2 + w2 / 2) - max(x1 - w1 / 2, x2 - w2 / 2) per axis; a negative overlap on either axis
+    is no intersection; union = (aw * ah + bw * bh) - inter.  A zero union gives NaN, which compares false"""
+    f = np.float32
+    a = np.asarray(a, f)
+    b = np.asarray(b, f)
+    two = f(2.0)
+    with np.errstate(all="ignore"):
+        def overlap(x1, w1, x2, w2):
+            return np.minimum(x1 + w1 / two, x2 + w2 / two) - np.maximum(x1 - w1 / two, x2 - w2 / two)
+        ow = overlap(a[0], a[2], b[..., 0], b[..., 2])
+        oh = overlap(a[1], a[3], b[..., 1], b[..., 3])
+        inter = np.where((ow < 0) | (oh < 0), f(0.0), ow * oh).astype(f)
+        union = (a[2] * a[3] + b[..., 2] * b[..., 3]) - inter
+        return (inter / union).astype(f)
+
+
+def darknet_corners(box, im_w, im_h):
+    """centre boxes float32 [k][4] in pixels -> the row's float32 [k][4] = xmin, ymin, xmax, ymax as Darknet's `valid`
+    prints them: float(double(bx) -/+ double(bw) / 2. + 1.), a minimum below 1 raised to 1, a maximum above the image
+    size lowered to it"""
+    f, d = np.float32, np.float64
+    b = np.asarray(box, f).reshape(-1, 4).astype(d)
+    with np.errstate(all="ignore"):
+        xmin = (b[:, 0] - b[:, 2] / 2.0 + 1.0).astype(f)
+        ymin = (b[:, 1] - b[:, 3] / 2.0 + 1.0).astype(f)
+        xmax = (b[:, 0] + b[:, 2] / 2.0 + 1.0).astype(f)
+        ymax = (b[:, 1] + b[:, 3] / 2.0 + 1.0).astype(f)
+    xmin = np.where(xmin < f(1.0), f(1.0), xmin)
+    ymin = np.where(ymin < f(1.0), f(1.0), ymin)
+    xmax = np.where(xmax > f(im_w), f(im_w), xmax)
+    ymax = np.where(ymax > f(im_h), f(im_h), ymax)
+    return np.stack([xmin, ymin, xmax, ymax], axis=1).astype(f)
+
+
+def anchor_detect_classes_darknet(boxes, scores, im_w, im_h, score_thresh, iou_thresh, max_per_class, net_size):
+    """anchor_detect_classes under Darknet's protocol: boxes float32 [K][4] and scores float32 [K][C] of ONE image (what
+    y2_decode_anchors writes) -> (det int32 [C][max_per_class][6], score float32 [C][max_per_class], count int32 [C]).
+    Words 0..3 of a det row are the BIT PATTERNS of the float32 corners (det[..., :4].view(np.float32)), word 4 the
+    class, word 5 the candidate; unused rows -1, unused scores 0.  A candidate is valid in class c if scores[:, c] >
+    score_thresh (NaN compares false) and its four darknet_unmap values are finite -- no other rule: a box that is empty
+    after the cut is kept.  Per class: descending score, ties by ascending candidate (our rule: qsort leaves ties open);
+    a kept box suppresses every later one with box_iou_darknet > iou_thresh on the centre boxes; the walk stops at
+    max_per_class rows (our cap).  The specification of y2_detect_anchor_classes_batch_dk"""
+    f = np.float32
+    boxes = np.asarray(boxes, f).reshape(-1, 4)
+    scores = np.asarray(scores, f).reshape(len(boxes), -1)
+    K, C = scores.shape
+    px = darknet_unmap(boxes, im_w, im_h, net_size)
+    finite = np.isfinite(px).all(axis=1)
+    thresh = f(iou_thresh)
+    det = np.full((C, max_per_class, 6), -1, np.int32)
+    score = np.zeros((C, max_per_class), f)
+    count = np.zeros(C, np.int32)
+    for c in range(C):
+        with np.errstate(all="ignore"):
+            idx = np.nonzero((scores[:, c] > f(score_thresh)) & finite)[0]
+        order = idx[np.lexsort((idx, -scores[idx, c].astype(np.float64)))]
+        suppressed = np.zeros(order.size, bool)
+        keep = []
+        for k in range(order.size):
+            if len(keep) >= max_per_class:
+                break
+            if suppressed[k]:
+                continue
+            keep.append(order[k])
+            later = order[k + 1:]
+            if later.size:
+                suppressed[k + 1:] |= box_iou_darknet(px[order[k]], px[later]) > thresh
+        keep = np.asarray(keep, np.int64)
+        count[c] = len(keep)
+        det[c, :len(keep), :4] = darknet_corners(px[keep], im_w, im_h).view(np.int32)
+        det[c, :len(keep), 4] = c
+        det[c, :len(keep), 5] = keep
+        score[c, :len(keep)] = scores[keep, c]
+    return det, score, count
+
+
+def match_image_f(det, gt_boxes, gt_difficult, iou_thresh=0.5):
+    """match_image for rows whose corners are float32: det [k][>= 5] = xmin, ymin, xmax, ymax (float32 values, or the
+    int32 bit patterns of anchor_detect_classes_darknet's rows) and the class.  The rules are match_image's; the devkit's
+    IoU (float64, + 1 extents) works on the four float32 values promoted to double, not on the six decimals a results
+    file would keep.  The specification of y2_voc_match_batch_f"""
+    det = np.asarray(det)
+    det = det.reshape(-1, det.shape[-1]) if det.size else det.reshape(0, 6)
+    if det.dtype == np.int32:
+        corners = np.ascontiguousarray(det[:, :4]).view(np.float32)
+    else:
+        corners = det[:, :4].astype(np.float32)
+    cls = det[:, 4]
+    gt = np.asarray(gt_boxes, np.float64).reshape(-1, 5)
+    difficult = np.asarray(gt_difficult).reshape(-1).astype(bool)
+    taken = np.zeros(len(gt), bool)
+    thresh = float(np.float32(iou_thresh))
+    flags = np.zeros(len(det), np.int32)
+    for k in range(len(det)):
+        objs = np.nonzero(gt[:, 4] == float(cls[k]))[0]
+        if not objs.size:
+            continue
+        with np.errstate(all="ignore"):
+            ious = voc_eval.box_iou_voc(tuple(float(v) for v in corners[k]), gt[objs, :4])
+        j = int(ious.argmax())                                            # first maximum, taken objects included
+        if not float(ious[j]) >= thresh:
+            continue
+        j = objs[j]
+        if difficult[j]:
+            flags[k] = 2
+        elif not taken[j]:
+            flags[k] = 1
+            taken[j] = True
+    return flags
+
+
 def class_rows(det, score, count, flags):
     """a batch of anchor_detect_classes outputs (det [n][C][M][6], score [n][C][M], count [n][C]) with the flags of
     match_image per (image, class) segment (flags [n][C][M]) -> the (class, score, flag) rows map_from_flags takes:

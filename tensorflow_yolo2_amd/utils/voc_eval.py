@@ -96,16 +96,22 @@ def write_results_files(directory, image_set, image_ids, class_names, rows):
     """the devkit's results files, as Darknet's `valid` writes and voc_eval.py tools read them: one
     comp4_det_<image_set>_<class>.txt per class (an empty file for a class without rows), one line
     `image_id score xmin ymin xmax ymax` per row.  rows: {"image": position in image_ids [N], "class" [N], "score" [N],
-    "box" [N][4]} in any order (the rows of either evaluator); a class's lines keep the order of its rows -> the paths"""
+    "box" [N][4]} in any order (the rows of either evaluator); a class's lines keep the order of its rows -> the paths.
+    Integer boxes print as integers; boxes of a floating dtype print all five numbers with "%f", as Darknet does"""
     import os
     os.makedirs(directory, exist_ok=True)
     image, cls, score = (np.asarray(rows[k]).reshape(-1) for k in ("image", "class", "score"))
     box = np.asarray(rows["box"]).reshape(-1, 4)
+    floating = box.dtype.kind == "f"            # the float corners of Darknet's protocol (evaluate_yolov2, protocol="darknet")
     paths = []
     for c, name in enumerate(class_names):
         path = os.path.join(directory, "comp4_det_%s_%s.txt" % (image_set, name))
         with open(path, "w") as f:
             for k in np.nonzero(cls == c)[0]:
+                if floating:                    # Darknet's print_detector_detections: "%s %f %f %f %f %f"
+                    f.write("%s %f %f %f %f %f\n" % ((image_ids[int(image[k])], float(score[k]))
+                                                     + tuple(float(v) for v in box[k])))
+                    continue
                 x0, y0, x1, y1 = (int(v) for v in box[k])
                 f.write("%s %.6f %d %d %d %d\n" % (image_ids[int(image[k])], float(score[k]), x0, y0, x1, y1))
         paths.append(path)

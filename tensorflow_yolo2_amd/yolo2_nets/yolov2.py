@@ -189,10 +189,25 @@ class YOLOv2Detector:
                                      net_size=self.size if letterbox else None)
 
     def detect_classes_batch(self, images_u8, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_per_class=32,
-                             out=None, grid_out=None, letterbox=False):
+                             out=None, grid_out=None, letterbox=False, protocol="repo"):
         """detect_batch with one row per (candidate, class), as Darknet's `valid` scores a detector ->
         (det int32 [N,C,max_per_class,6], score [N,C,max_per_class], count [N,C]): engine.detect_anchor_classes_batch on
-        the raw head"""
+        the raw head.  protocol="darknet": the batch is the float32 RGB one of DeviceVOC.eval_batch(...,
+        protocol="darknet") and the rows are Darknet's -- float un-map, float IoU, float corners as bit patterns in words
+        0..3 (engine.detect_anchor_classes_batch_darknet).  It needs the "darknet" topology, whose float input is RGB in
+        [0, 1], and letterbox=True"""
+        if protocol == "darknet":
+            if self.topology != "darknet":
+                raise ValueError("protocol='darknet' needs the \"darknet\" topology: the input of the %r topology is BGR "
+                                 "in [-1, 1), not Darknet's RGB in [0, 1]" % (self.topology,))
+            if not letterbox:
+                raise ValueError("protocol='darknet' is letterboxed: pass letterbox=True")
+            assert images_u8.dtype == torch.float32, images_u8.dtype
+            grid = self.forward(images_u8, out=grid_out)
+            return E.detect_anchor_classes_batch_darknet(grid, self.anchors_dev, table, index, score_thresh, iou_thresh,
+                                                         max_per_class, out=out, net_size=self.size)
+        if protocol != "repo":
+            raise ValueError("protocol %r is neither 'repo' nor 'darknet'" % (protocol,))
         grid = self.forward(images_u8, out=grid_out)
         return E.detect_anchor_classes_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh,
                                              max_per_class, out=out, net_size=self.size if letterbox else None)
