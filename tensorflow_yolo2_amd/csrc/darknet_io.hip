@@ -118,7 +118,6 @@ __global__ __launch_bounds__(256) void letterbox_darknet_kernel(const uint8_t* _
 }
 
 // ---- the boxes: y2_detect_anchor_classes_batch_dk -------------------------------------------------------------------
-constexpr int kAnchorMaxCand = kDetectAnchorMaxCand;   // S * S * B of one image
 constexpr int kClassLanes = 512;                       // the workgroup, as detect_anchor_classes_kernel's
 constexpr int kClassSlotBytes = 8 + 4 * 4 + 1;         // sort word, the float centre box, suppressed flag: 50 KB at 2048
 
@@ -294,19 +293,10 @@ int y2_detect_anchor_classes_batch_dk(const float* net, const float* anchors, co
                                       int max_per_class, int net_size, int* det, float* score, int* count,
                                       void* stream) {
     const char* name = "y2_detect_anchor_classes_batch_dk";
-    if (!net || !anchors || !table || !det || !score || !count) return fail(Y2_ERR_ARG, "%s: null pointer", name);
-    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "%s: n = %d outside 1..65535", name, n);
-    if (max_per_class < 1) return fail(Y2_ERR_ARG, "%s: max_per_class = %d", name, max_per_class);
-    if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
-        return fail(Y2_ERR_ARG, "%s: S = %d, B = %d (at most 16), num_class = %d", name, S, B, num_class);
-    if (S * S * B > kAnchorMaxCand)
-        return fail(Y2_ERR_ARG, "%s: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d", name,
-                    S * S * B, kAnchorMaxCand);
-    if (net_size < 32 || net_size % 32 || net_size != 32 * S)
-        return fail(Y2_ERR_ARG, "%s: net_size = %d is not the positive multiple of 32 that S = %d makes (32 S = %d)",
-                    name, net_size, S, 32 * S);
-    int KP = kWave;
-    while (KP < S * S * B) KP <<= 1;
+    int KP;
+    if (const int rc = detect_anchor_args(name, net && anchors && table && det && score && count, n, 65535,
+                                          "max_per_class", max_per_class, S, B, num_class, true, net_size, &KP))
+        return rc;
     const int lanes = KP < kClassLanes ? KP : kClassLanes;
     hipLaunchKernelGGL(detect_anchor_classes_dk_kernel, dim3(num_class, n), dim3(lanes), (size_t)KP * kClassSlotBytes,
                        (hipStream_t)stream, net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh,
@@ -317,17 +307,9 @@ int y2_detect_anchor_classes_batch_dk(const float* net, const float* anchors, co
 int y2_voc_match_batch_f(const int* det, const float* score, const int* count, const double* boxes,
                          const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
                          int max_out, float iou_thresh, int* flags, void* stream) {
-    (void)score;   // as y2_voc_match_batch: the order of the rows is all that is used
-    if (!det || !count || !boxes || !counts || !difficult || !flags)
-        return fail(Y2_ERR_ARG, "y2_voc_match_batch_f: null pointer");
-    if (n < 1) return fail(Y2_ERR_ARG, "y2_voc_match_batch_f: n = %d", n);
-    if (max_out < 1) return fail(Y2_ERR_ARG, "y2_voc_match_batch_f: max_out = %d", max_out);
-    if (max_obj < 1 || max_obj > kMatchMaxObj)
-        return fail(Y2_ERR_ARG, "y2_voc_match_batch_f: max_obj = %d outside 1..Y2_MATCH_MAX_OBJECTS = %d", max_obj,
-                    kMatchMaxObj);
-    hipLaunchKernelGGL(voc_match_kernel<true>, dim3(n), dim3(kWave), 0, (hipStream_t)stream, det, count, boxes, counts,
-                       difficult, index, max_obj, max_out, iou_thresh, flags);
-    return launched("y2_voc_match_batch_f");
+    (void)score;
+    return voc_match_any<true>("y2_voc_match_batch_f", det, count, boxes, counts, difficult, index, n, max_obj, max_out,
+                               iou_thresh, flags, stream);
 }
 
 }  // extern "C"

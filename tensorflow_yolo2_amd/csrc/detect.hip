@@ -133,7 +133,6 @@ __global__ __launch_bounds__(kMaxCand) void detect_grid_kernel(const float* __re
 }
 
 // ---- the anchor (YOLOv2) head: y2_detect_anchor_batch --------------------------------------------------------------
-constexpr int kAnchorMaxCand = kDetectAnchorMaxCand;   // S * S * B of one image: 19 * 19 * 5 = 1805 at 608 x 608
 constexpr int kAnchorLanes = 1024;                     // the workgroup; above it a lane owns two decode and sort slots
 constexpr int kAnchorSlotBytes = 8 + 5 * 4 + 1;        // sort word, four corners, class, suppressed flag
 
@@ -421,29 +420,19 @@ int y2_detect_grid_batch(const float* predict, const int64_t* table, const int32
     while (KP < S * S * B) KP <<= 1;
     hipLaunchKernelGGL(detect_grid_kernel, dim3(n), dim3(KP), 0, (hipStream_t)stream, predict, table, index, S, B,
                        num_class, object_thresh, iou_thresh, max_out, KP, det, score, count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_detect_grid_batch: %s", hipGetErrorString(e));
-    return Y2_OK;
+    return launched("y2_detect_grid_batch");
 }
 
-// the checks and the launch of y2_detect_anchor_batch (net_size 0: the plain stretch) and y2_detect_anchor_batch_lb
+// y2_detect_anchor_batch (net_size 0: the plain stretch) and y2_detect_anchor_batch_lb: detect_anchor_args' checks
+// (detect_common.h) with this family's bounds, and the launch
 static int detect_anchor_any(const char* name, const float* net, const float* anchors, const int64_t* table,
                              const int32_t* index, int n, int S, int B, int num_class, float score_thresh,
                              float iou_thresh, int max_out, int net_size, bool letterbox, int* det, float* score,
                              int* count, void* stream) {
-    if (!net || !anchors || !table || !det || !score || !count) return fail(Y2_ERR_ARG, "%s: null pointer", name);
-    if (n < 1) return fail(Y2_ERR_ARG, "%s: n = %d", name, n);
-    if (max_out < 1) return fail(Y2_ERR_ARG, "%s: max_out = %d", name, max_out);
-    if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
-        return fail(Y2_ERR_ARG, "%s: S = %d, B = %d (at most 16), num_class = %d", name, S, B, num_class);
-    if (S * S * B > kAnchorMaxCand)
-        return fail(Y2_ERR_ARG, "%s: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d", name,
-                    S * S * B, kAnchorMaxCand);
-    if (letterbox && (net_size < 32 || net_size % 32 || net_size != 32 * S))
-        return fail(Y2_ERR_ARG, "%s: net_size = %d is not the positive multiple of 32 that S = %d makes (32 S = %d)",
-                    name, net_size, S, 32 * S);
-    int KP = kWave;
-    while (KP < S * S * B) KP <<= 1;
+    int KP;
+    if (const int rc = detect_anchor_args(name, net && anchors && table && det && score && count, n, 0, "max_out",
+                                          max_out, S, B, num_class, letterbox, net_size, &KP))
+        return rc;
     const int lanes = KP < kAnchorLanes ? KP : kAnchorLanes;
     if (letterbox)
         hipLaunchKernelGGL(detect_anchor_kernel<true>, dim3(n), dim3(lanes), (size_t)KP * kAnchorSlotBytes,
@@ -453,9 +442,7 @@ static int detect_anchor_any(const char* name, const float* net, const float* an
         hipLaunchKernelGGL(detect_anchor_kernel<false>, dim3(n), dim3(lanes), (size_t)KP * kAnchorSlotBytes,
                            (hipStream_t)stream, net, anchors, table, index, S, B, num_class, score_thresh, iou_thresh,
                            max_out, KP, 0, det, score, count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
-    return Y2_OK;
+    return launched(name);
 }
 
 int y2_detect_anchor_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index, int n,
@@ -477,19 +464,10 @@ static int detect_anchor_classes_any(const char* name, const float* net, const f
                                      const int32_t* index, int n, int S, int B, int num_class, float score_thresh,
                                      float iou_thresh, int max_per_class, int net_size, bool letterbox, int* det,
                                      float* score, int* count, void* stream) {
-    if (!net || !anchors || !table || !det || !score || !count) return fail(Y2_ERR_ARG, "%s: null pointer", name);
-    if (n < 1 || n > 65535) return fail(Y2_ERR_ARG, "%s: n = %d outside 1..65535", name, n);
-    if (max_per_class < 1) return fail(Y2_ERR_ARG, "%s: max_per_class = %d", name, max_per_class);
-    if (S < 1 || B < 1 || num_class < 1 || S > kAnchorMaxCand || B > 16)
-        return fail(Y2_ERR_ARG, "%s: S = %d, B = %d (at most 16), num_class = %d", name, S, B, num_class);
-    if (S * S * B > kAnchorMaxCand)
-        return fail(Y2_ERR_ARG, "%s: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d", name,
-                    S * S * B, kAnchorMaxCand);
-    if (letterbox && (net_size < 32 || net_size % 32 || net_size != 32 * S))
-        return fail(Y2_ERR_ARG, "%s: net_size = %d is not the positive multiple of 32 that S = %d makes (32 S = %d)",
-                    name, net_size, S, 32 * S);
-    int KP = kWave;
-    while (KP < S * S * B) KP <<= 1;
+    int KP;
+    if (const int rc = detect_anchor_args(name, net && anchors && table && det && score && count, n, 65535,
+                                          "max_per_class", max_per_class, S, B, num_class, letterbox, net_size, &KP))
+        return rc;
     const int lanes = KP < kClassLanes ? KP : kClassLanes;
     if (letterbox)
         hipLaunchKernelGGL(detect_anchor_classes_kernel<true>, dim3(num_class, n), dim3(lanes),
@@ -499,9 +477,7 @@ static int detect_anchor_classes_any(const char* name, const float* net, const f
         hipLaunchKernelGGL(detect_anchor_classes_kernel<false>, dim3(num_class, n), dim3(lanes),
                            (size_t)KP * kClassSlotBytes, (hipStream_t)stream, net, anchors, table, index, S, B, num_class,
                            score_thresh, iou_thresh, max_per_class, KP, 0, det, score, count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
-    return Y2_OK;
+    return launched(name);
 }
 
 int y2_detect_anchor_classes_batch(const float* net, const float* anchors, const int64_t* table, const int32_t* index,
@@ -522,19 +498,9 @@ int y2_detect_anchor_classes_batch_lb(const float* net, const float* anchors, co
 int y2_voc_match_batch(const int* det, const float* score, const int* count, const double* boxes,
                        const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
                        int max_out, float iou_thresh, int* flags, void* stream) {
-    (void)score;   // the rows arrive in descending score (y2_detect_grid_batch, y2_nms): the order is all that is used
-    if (!det || !count || !boxes || !counts || !difficult || !flags)
-        return fail(Y2_ERR_ARG, "y2_voc_match_batch: null pointer");
-    if (n < 1) return fail(Y2_ERR_ARG, "y2_voc_match_batch: n = %d", n);
-    if (max_out < 1) return fail(Y2_ERR_ARG, "y2_voc_match_batch: max_out = %d", max_out);
-    if (max_obj < 1 || max_obj > kMatchMaxObj)
-        return fail(Y2_ERR_ARG, "y2_voc_match_batch: max_obj = %d outside 1..Y2_MATCH_MAX_OBJECTS = %d", max_obj,
-                    kMatchMaxObj);
-    hipLaunchKernelGGL(voc_match_kernel<false>, dim3(n), dim3(kWave), 0, (hipStream_t)stream, det, count, boxes, counts,
-                       difficult, index, max_obj, max_out, iou_thresh, flags);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(Y2_ERR_HIP, "y2_voc_match_batch: %s", hipGetErrorString(e));
-    return Y2_OK;
+    (void)score;
+    return voc_match_any<false>("y2_voc_match_batch", det, count, boxes, counts, difficult, index, n, max_obj, max_out,
+                                iou_thresh, flags, stream);
 }
 
 }  // extern "C"

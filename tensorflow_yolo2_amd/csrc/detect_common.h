@@ -1,8 +1,11 @@
 // What the detect kernels of detect.hip (integer pixel rows) and darknet_io.hip (Darknet's float rows) share: the 64-bit
 // sort word, the devkit's IoU, the wave-wide first maximum and the matching kernel, whose only difference between the two
-// is how words 0..3 of a row are read.  One definition of each; both files are compiled with -ffp-contract=off.
+// is how words 0..3 of a row are read, and (host code) the argument checks of the per-anchor detect entries and the
+// matchers' entry.  One definition of each; both files are compiled with -ffp-contract=off.
 #pragma once
 #include "common.h"
+#include "data_common.h"
+#include "kernels.h"
 
 namespace y2 {
 
@@ -120,6 +123,47 @@ __global__ __launch_bounds__(kWave) void voc_match_kernel(const int* __restrict_
         if (lane == 0) frow[d] = flag;
     }
     for (int d = ndet + lane; d < max_out; d += kWave) frow[d] = -1;
+}
+
+// ---- host code: the entry points' argument checks ----------------------------------------------------------------
+// The checks of a per-anchor detect entry `name`, in the order every one of them reports: null pointers, n (the
+// per-class entries launch n as the grid's y and cap it with n_cap; 0: no cap), the rows per image or per class
+// (`rows_name` is max_out or max_per_class), the head's shape, the candidate limit and, for a letterboxed batch,
+// net_size = 32 S.  Leaves KP, the next power of two of S * S * B (at least one wave), for the launch.
+static int detect_anchor_args(const char* name, bool pointers, int n, int n_cap, const char* rows_name, int rows, int S,
+                              int B, int num_class, bool letterbox, int net_size, int* KP) {
+    if (!pointers) return fail(Y2_ERR_ARG, "%s: null pointer", name);
+    if (n < 1 || (n_cap && n > n_cap))
+        return n_cap ? fail(Y2_ERR_ARG, "%s: n = %d outside 1..%d", name, n, n_cap)
+                     : fail(Y2_ERR_ARG, "%s: n = %d", name, n);
+    if (rows < 1) return fail(Y2_ERR_ARG, "%s: %s = %d", name, rows_name, rows);
+    if (S < 1 || B < 1 || num_class < 1 || S > kDetectAnchorMaxCand || B > 16)
+        return fail(Y2_ERR_ARG, "%s: S = %d, B = %d (at most 16), num_class = %d", name, S, B, num_class);
+    if (S * S * B > kDetectAnchorMaxCand)
+        return fail(Y2_ERR_ARG, "%s: S * S * B = %d candidates beyond Y2_DETECT_ANCHOR_MAX_CANDIDATES = %d", name,
+                    S * S * B, kDetectAnchorMaxCand);
+    if (letterbox && (net_size < 32 || net_size % 32 || net_size != 32 * S))
+        return fail(Y2_ERR_ARG, "%s: net_size = %d is not the positive multiple of 32 that S = %d makes (32 S = %d)",
+                    name, net_size, S, 32 * S);
+    *KP = kWave;
+    while (*KP < S * S * B) *KP <<= 1;
+    return Y2_OK;
+}
+
+// y2_voc_match_batch (integer rows) and y2_voc_match_batch_f (float rows).  `score` is not read: the rows arrive in
+// descending score (y2_detect_grid_batch, y2_nms), and the order is all that is used.
+template <bool FLOAT_ROWS>
+static int voc_match_any(const char* name, const int* det, const int* count, const double* boxes, const int32_t* counts,
+                         const uint8_t* difficult, const int32_t* index, int n, int max_obj, int max_out,
+                         float iou_thresh, int* flags, void* stream) {
+    if (!det || !count || !boxes || !counts || !difficult || !flags) return fail(Y2_ERR_ARG, "%s: null pointer", name);
+    if (n < 1) return fail(Y2_ERR_ARG, "%s: n = %d", name, n);
+    if (max_out < 1) return fail(Y2_ERR_ARG, "%s: max_out = %d", name, max_out);
+    if (max_obj < 1 || max_obj > kMatchMaxObj)
+        return fail(Y2_ERR_ARG, "%s: max_obj = %d outside 1..Y2_MATCH_MAX_OBJECTS = %d", name, max_obj, kMatchMaxObj);
+    hipLaunchKernelGGL(voc_match_kernel<FLOAT_ROWS>, dim3(n), dim3(kWave), 0, (hipStream_t)stream, det, count, boxes,
+                       counts, difficult, index, max_obj, max_out, iou_thresh, flags);
+    return launched(name);
 }
 
 }  // namespace y2

@@ -48,6 +48,77 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ---- the tensor contracts of the entry points below, each stated once.  Plain functions with positional arguments:
+# several of them front kernels of about 10 us, where a Python frame shows (docs/HISTORY.md), so nothing here builds a
+# closure, a dict or a format string on the success path, and the callers pass the counts they already hold.
+def _dev(t, dtype, name):
+    """t is a contiguous device tensor of dtype"""
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), name
+    return t
+
+
+def _chk(*ts):
+    """contiguous fp32 device tensors, or None"""
+    for t in ts:
+        if t is not None:
+            _dev(t, torch.float32, "operand")
+
+
+def _entries(table, index, n, rows):
+    """the entries of a batch of n: table int64 [entries][5] (DeviceVOC.table; None where a call has no table), and
+    index int32 [at least n] on the device, or None for the first n of `rows` entries"""
+    if table is not None:
+        assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5, "table"
+    if index is not None:
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n, "index"
+    else:
+        assert rows >= n, (rows, n)
+
+
+def _upload_anchors(anchors, device):
+    """anything numpy reads -> a contiguous float32 tensor on the device"""
+    return torch.as_tensor(np.asarray(anchors, np.float32)).to(device).contiguous()
+
+
+def _anchors(anchors, B, device):
+    """anchors [B,2]: a float32 device tensor as it is, or anything numpy reads, uploaded"""
+    if torch.is_tensor(anchors):
+        an = anchors
+        assert an.is_cuda and an.dtype == torch.float32 and an.is_contiguous(), "anchors"
+    else:
+        an = _upload_anchors(anchors, device)
+    assert an.numel() == 2 * B, (tuple(an.shape), B)
+    return an
+
+
+def _own(t, shape, dtype, device, numel=None):
+    """an output tensor of `shape`: allocated when t is None, else the caller's own device tensor, contiguous and of
+    dtype, of exactly that shape -- or, with numel, of that element count (callers pass views of another shape)"""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), "out"
+    if numel is None:
+        assert tuple(t.shape) == tuple(shape), t.shape
+    else:
+        assert t.numel() == numel, t.shape
+    return t
+
+
+def _det_out(out, lead, segments, m, device):
+    """the (det int32 lead + [m,6], score float32 lead + [m], count int32 lead) of a detect call over `segments` =
+    prod(lead) images or (image, class) pairs: allocated, or the caller's `out` checked by element count (callers pass
+    views such as det.view(n * C, m, 6)); where the caller's tensors live is not checked"""
+    if out is None:
+        return (torch.empty(lead + (m, 6), dtype=torch.int32, device=device),
+                torch.empty(lead + (m,), dtype=torch.float32, device=device),
+                torch.empty(lead, dtype=torch.int32, device=device))
+    det, score, count = out
+    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == segments * m * 6
+    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == segments * m
+    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == segments
+    return det, score, count
+
+
 class ForwardGraph:
     """Network.forward captured into a HIP graph (Network.forward_graph)."""
 
@@ -515,19 +586,84 @@ class LossScaler:
         return int(c[0]), int(c[1]), int(c[2])
 
 
-class AdamOptimizer:
+class _FlatOptimizer:
+    """What the optimizers over a Network's flat buffers share: the guard (default: the loss-scaled modes) with its
+    LossScaler, the bracket of a step (scan before, after_step after), backward_step's fallback and the tf.train.Saver
+    slots.  A subclass names its slot tensors in SLOTS (created zeroed, exported and loaded by name), says with COUNTS
+    whether it keeps a step counter `t`, and keeps its own step() and library calls."""
+    SLOTS = ()
+    COUNTS = True
+
+    def __init__(self, net, guard, fused_pack):
+        self.net = net
+        self.fused_pack = bool(fused_pack)
+        for k in self.SLOTS:
+            setattr(self, k, torch.zeros_like(net.params))
+        if self.COUNTS:
+            self.t = 0
+        self.guard = (net.dtype in _lib.LOSS_SCALED) if guard is None else bool(guard)
+        self.scaler = LossScaler(net) if self.guard else None
+
+    def _ctrl(self):
+        return _ptr(self.scaler.ctrl) if self.guard else C.c_void_p(0)
+
+    def _scan(self, full_check, joint=None):
+        """before the launch of a step: the gradient scan (in a joint group the caller has scanned every stack into
+        the shared flag) -> the ctrl pointer"""
+        if self.guard and joint is None:
+            self.scaler.scan(self.net, full_check)
+        return self._ctrl()
+
+    def _after(self, owner=True):
+        """after the launch: once per step and shared scaler, by the call that owns the step"""
+        if self.guard and owner:
+            self.scaler.after_step()
+
+    _train_op = None     # (dout, ctrl, grad_mult): backward + step + re-pack in one library call, where the solver has one
+
+    def backward_step(self, dout, grad_mult=1.0):
+        """train_op in one library call: net.backward(dout) + the (guarded) step + filter re-pack, with the update
+        of the layers above the first one overlapped with the first layer's gradient kernel (single-process
+        training; the data-parallel trainers reduce between backward() and step()).  Without the packed step, or
+        for a solver that has no overlapped train op (DarknetSGD): net.backward(dout), then the step."""
+        n = self.net
+        if self._train_op is None or not (self.fused_pack and n.training) or os.environ.get("Y2_NO_FUSED_TRAIN_OP"):
+            n.backward(dout)
+            return self.step(grad_mult)
+        if self.COUNTS:
+            self.t += 1
+        self._train_op(dout.contiguous(), self._ctrl(), grad_mult)
+        self._after()
+
+    # ---- tf.train.Saver slots (ADVICE r1: a resumed run must not restart Adam at t = 0)
+    def export_state(self):
+        st = {k: getattr(self, k).detach().cpu().numpy().copy() for k in self.SLOTS}
+        if self.COUNTS:
+            # the device counter is authoritative under a guard; `t` is its host mirror
+            st["t"] = int(self.scaler.state()[1] if self.guard else self.t)
+        return st
+
+    def load_state(self, st):
+        for k in self.SLOTS:
+            slot = getattr(self, k)
+            slot.copy_(torch.as_tensor(np.asarray(st[k], np.float32)).to(slot.device))
+        if self.COUNTS:
+            self.t = int(st["t"])
+            if self.guard:
+                c = self.scaler.ctrl.cpu()
+                c[1] = self.t
+                self.scaler.ctrl.copy_(c)
+
+
+class AdamOptimizer(_FlatOptimizer):
     """tf.train.AdamOptimizer defaults (src/pascal/pascal_train_darknet.py:51).
     guard=True (default for the f16 mode): the overflow-safe kernels + LossScaler; the step counter then lives
     on the device (`t` mirrors it assuming no skipped step; `scaler.state()` is authoritative)."""
+    SLOTS = ("m", "v")
 
     def __init__(self, net, learning_rate=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8, guard=None, fused_pack=True):
-        self.net, self.lr, self.b1, self.b2, self.eps = net, learning_rate, beta1, beta2, epsilon
-        self.fused_pack = bool(fused_pack)
-        self.m = torch.zeros_like(net.params)
-        self.v = torch.zeros_like(net.params)
-        self.t = 0
-        self.guard = (net.dtype in _lib.LOSS_SCALED) if guard is None else bool(guard)
-        self.scaler = LossScaler(net) if self.guard else None
+        _FlatOptimizer.__init__(self, net, guard, fused_pack)
+        self.lr, self.b1, self.b2, self.eps = learning_rate, beta1, beta2, epsilon
 
     def step(self, grad_mult=1.0, full_check=False, joint=None):
         """full_check: scan every gradient element instead of the sentinel ranges (a gradient buffer that was
@@ -537,20 +673,14 @@ class AdamOptimizer:
         "next": use the counter / lr_t the first stack's call advanced)."""
         self.t += 1
         n = self.net
-        if self.guard and joint is None:
-            self.scaler.scan(n, full_check)
-        ctrl = _ptr(self.scaler.ctrl) if self.guard else C.c_void_p(0)
+        ctrl = self._scan(full_check, joint)
+        owner = joint is None or joint == "first"
         if joint is not None:
             assert self.guard and self.fused_pack and n.training
-            check(n.lib.y2_adam_step_packed(n.h, _ptr(self.m), _ptr(self.v), ctrl, self.t if joint == "first" else -1,
-                                            self.lr, self.b1, self.b2, self.eps, grad_mult, _stream()))
-            if joint == "first":
-                self.scaler.after_step()
-            return
         if self.fused_pack and n.training:
             # update + filter re-pack in one pass over the parameters (the context's packed copies stay current)
-            check(n.lib.y2_adam_step_packed(n.h, _ptr(self.m), _ptr(self.v), ctrl, self.t, self.lr, self.b1, self.b2,
-                                            self.eps, grad_mult, _stream()))
+            check(n.lib.y2_adam_step_packed(n.h, _ptr(self.m), _ptr(self.v), ctrl, self.t if owner else -1, self.lr,
+                                            self.b1, self.b2, self.eps, grad_mult, _stream()))
         elif self.guard:
             check(n.lib.y2_adam_step_guarded(_ptr(n.params), _ptr(self.m), _ptr(self.v), _ptr(n.grads), n.n_params,
                                              ctrl, self.lr, self.b1, self.b2, self.eps, grad_mult, _stream()))
@@ -559,55 +689,26 @@ class AdamOptimizer:
             check(n.lib.y2_adam_step(_ptr(n.params), _ptr(self.m), _ptr(self.v), _ptr(n.grads), n.n_params, self.t,
                                      self.lr, self.b1, self.b2, self.eps, grad_mult, _stream()))
             n.params_changed()
-        if self.guard:
-            self.scaler.after_step()
+        self._after(owner)
 
-    def backward_step(self, dout, grad_mult=1.0):
-        """train_op in one library call: net.backward(dout) + the (guarded) step + filter re-pack, with the update
-        of the layers above the first one overlapped with the first layer's gradient kernel (single-process
-        training; the data-parallel trainers reduce between backward() and step())."""
+    def _train_op(self, dout, ctrl, grad_mult):
         n = self.net
-        if not (self.fused_pack and n.training) or os.environ.get("Y2_NO_FUSED_TRAIN_OP"):
-            n.backward(dout)
-            return self.step(grad_mult)
-        self.t += 1
-        ctrl = _ptr(self.scaler.ctrl) if self.guard else C.c_void_p(0)
-        dout = dout.contiguous()
         check(n.lib.y2_backward_adam(n.h, _ptr(dout), _ptr(self.m), _ptr(self.v), ctrl, self.t, self.lr, self.b1,
                                      self.b2, self.eps, grad_mult, _stream()))
-        if self.guard:
-            self.scaler.after_step()
-
-    # ---- tf.train.Saver slots (ADVICE r1: a resumed run must not restart Adam at t = 0)
-    def export_state(self):
-        t = self.scaler.state()[1] if self.guard else self.t
-        return {"m": self.m.detach().cpu().numpy().copy(), "v": self.v.detach().cpu().numpy().copy(), "t": int(t)}
-
-    def load_state(self, st):
-        self.m.copy_(torch.as_tensor(np.asarray(st["m"], np.float32)).to(self.m.device))
-        self.v.copy_(torch.as_tensor(np.asarray(st["v"], np.float32)).to(self.v.device))
-        self.t = int(st["t"])
-        if self.guard:
-            c = self.scaler.ctrl.cpu()
-            c[1] = self.t
-            self.scaler.ctrl.copy_(c)
 
 
-class MomentumOptimizer:
+class MomentumOptimizer(_FlatOptimizer):
     """tf.train.MomentumOptimizer(0.001, 0.9) (src/imagenet/imagenet_train_darknet.py:58)."""
+    SLOTS = ("accum",)
+    COUNTS = False
 
     def __init__(self, net, learning_rate=1e-3, momentum=0.9, guard=None, fused_pack=True):
-        self.net, self.lr, self.mom = net, learning_rate, momentum
-        self.fused_pack = bool(fused_pack)
-        self.accum = torch.zeros_like(net.params)
-        self.guard = (net.dtype in _lib.LOSS_SCALED) if guard is None else bool(guard)
-        self.scaler = LossScaler(net) if self.guard else None
+        _FlatOptimizer.__init__(self, net, guard, fused_pack)
+        self.lr, self.mom = learning_rate, momentum
 
     def step(self, grad_mult=1.0, full_check=False):
         n = self.net
-        if self.guard:
-            self.scaler.scan(n, full_check)
-        ctrl = _ptr(self.scaler.ctrl) if self.guard else C.c_void_p(0)
+        ctrl = self._scan(full_check)
         if self.fused_pack and n.training:
             check(n.lib.y2_momentum_step_packed(n.h, _ptr(self.accum), ctrl, self.lr, self.mom, grad_mult, _stream()))
         elif self.guard:
@@ -618,44 +719,26 @@ class MomentumOptimizer:
             check(n.lib.y2_momentum_step(_ptr(n.params), _ptr(self.accum), _ptr(n.grads), n.n_params, self.lr,
                                          self.mom, grad_mult, _stream()))
             n.params_changed()
-        if self.guard:
-            self.scaler.after_step()
+        self._after()
 
-    def backward_step(self, dout, grad_mult=1.0):
-        """see AdamOptimizer.backward_step"""
+    def _train_op(self, dout, ctrl, grad_mult):
         n = self.net
-        if not (self.fused_pack and n.training) or os.environ.get("Y2_NO_FUSED_TRAIN_OP"):
-            n.backward(dout)
-            return self.step(grad_mult)
-        ctrl = _ptr(self.scaler.ctrl) if self.guard else C.c_void_p(0)
-        dout = dout.contiguous()
         check(n.lib.y2_backward_momentum(n.h, _ptr(dout), _ptr(self.accum), ctrl, self.lr, self.mom, grad_mult,
                                          _stream()))
-        if self.guard:
-            self.scaler.after_step()
-
-    def export_state(self):
-        return {"accum": self.accum.detach().cpu().numpy().copy()}
-
-    def load_state(self, st):
-        self.accum.copy_(torch.as_tensor(np.asarray(st["accum"], np.float32)).to(self.accum.device))
 
 
-class DarknetSGD:
+class DarknetSGD(_FlatOptimizer):
     """Darknet's solver for the YOLOv2 anchor model (not in the reference; specification utils/solver.py): momentum
     SGD with weight decay on the convolution filters only and a rate schedule (burn-in, then constant / steps / poly).
     `solver`: a utils.solver.Solver.  The shape of AdamOptimizer: guarded in the loss-scaled modes, where the step
     counter AND the schedule live on the device -- a skipped step moves neither (`t` mirrors the counter assuming no
     skipped step; `scaler.state()` is authoritative, word 4 of `scaler.ctrl` holds the rate last applied)."""
+    SLOTS = ("accum",)
 
     def __init__(self, net, solver, guard=None, fused_pack=True):
-        self.net, self.solver = net, solver
+        _FlatOptimizer.__init__(self, net, guard, fused_pack)
+        self.solver = solver
         self._record = _lib.sgd_solver(solver)
-        self.fused_pack = bool(fused_pack)
-        self.accum = torch.zeros_like(net.params)
-        self.t = 0
-        self.guard = (net.dtype in _lib.LOSS_SCALED) if guard is None else bool(guard)
-        self.scaler = LossScaler(net) if self.guard else None
 
     def step(self, grad_mult=1.0, full_check=False, joint=None):
         """full_check / joint: see AdamOptimizer.step"""
@@ -663,9 +746,7 @@ class DarknetSGD:
         n = self.net
         if not n.training:
             raise ValueError("DarknetSGD steps a context bound for training")
-        if self.guard and joint is None:
-            self.scaler.scan(n, full_check)
-        ctrl = _ptr(self.scaler.ctrl) if self.guard else C.c_void_p(0)
+        ctrl = self._scan(full_check, joint)
         if joint is not None:
             assert self.guard and self.fused_pack
         fn = n.lib.y2_sgd_step_packed if self.fused_pack else n.lib.y2_sgd_step
@@ -673,25 +754,7 @@ class DarknetSGD:
                  _stream()))
         if not self.fused_pack:
             n.params_changed()
-        if self.guard and joint != "next":
-            self.scaler.after_step()
-
-    def backward_step(self, dout, grad_mult=1.0):
-        """net.backward(dout), then the step (no overlapped train op for this solver)"""
-        self.net.backward(dout)
-        return self.step(grad_mult)
-
-    def export_state(self):
-        t = self.scaler.state()[1] if self.guard else self.t
-        return {"accum": self.accum.detach().cpu().numpy().copy(), "t": int(t)}
-
-    def load_state(self, st):
-        self.accum.copy_(torch.as_tensor(np.asarray(st["accum"], np.float32)).to(self.accum.device))
-        self.t = int(st["t"])
-        if self.guard:
-            c = self.scaler.ctrl.cpu()
-            c[1] = self.t
-            self.scaler.ctrl.copy_(c)
+        self._after(joint != "next")
 
 
 # ---------------------------------------------------------------------------
@@ -912,7 +975,7 @@ def decode_anchors(net, anchors):
     n, s, _, b, d = net.shape
     c = d - 5
     assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous()
-    an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
+    an = _upload_anchors(anchors, net.device)
     boxes = torch.empty((n, s * s * b, 4), dtype=torch.float32, device=net.device)
     scores = torch.empty((n, s * s * b, c), dtype=torch.float32, device=net.device)
     check(lib.y2_decode_anchors(_ptr(net), _ptr(an), _ptr(boxes), _ptr(scores), n, s, b, c, _stream()))
@@ -927,7 +990,7 @@ def yolov2_loss(net, labels, anchors, image_size, need_grad=True, scales=None):
     n, s, _, b, d = net.shape
     labels = labels.contiguous().float()
     assert tuple(labels.shape) == (n, s, s, d), labels.shape
-    an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
+    an = _upload_anchors(anchors, net.device)
     sc = None
     if scales is not None:
         sc = torch.as_tensor(np.asarray([scales[k] for k in ("coord_scale", "object_scale", "noobject_scale",
@@ -955,7 +1018,7 @@ def yolov2_loss_boxes(net, truth, ntruth, anchors, image_size, need_grad=True, s
     assert truth.is_cuda and truth.dtype == torch.float32 and truth.is_contiguous(), (truth.dtype, truth.device)
     assert truth.dim() == 3 and truth.shape[0] == n and truth.shape[2] == 5, truth.shape
     assert ntruth.is_cuda and ntruth.dtype == torch.int32 and ntruth.is_contiguous() and tuple(ntruth.shape) == (n,)
-    an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
+    an = _upload_anchors(anchors, net.device)
     assert tuple(an.shape) == (b, 2), an.shape
     sc = None
     if scales is not None:
@@ -996,19 +1059,8 @@ def detect_grid_batch(predict, table, index=None, num_class=20, B=2, object_thre
     assert predict.is_cuda and predict.dtype == torch.float32 and predict.is_contiguous() and predict.dim() == 4
     n, S = predict.shape[0], predict.shape[1]
     assert tuple(predict.shape) == (n, S, S, num_class + 5 * B), predict.shape
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert table.shape[0] >= n
-    if out is None:
-        out = (torch.empty((n, max_out, 6), dtype=torch.int32, device=predict.device),
-               torch.empty((n, max_out), dtype=torch.float32, device=predict.device),
-               torch.empty((n,), dtype=torch.int32, device=predict.device))
-    det, score, count = out
-    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * max_out * 6
-    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * max_out
-    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n
+    _entries(table, index, n, table.shape[0])
+    det, score, count = _det_out(out, (n,), n, max_out, predict.device)
     check(lib.y2_detect_grid_batch(_ptr(predict), _ptr(table), _ptr(index), n, S, B, num_class, float(object_thresh),
                                    float(iou_thresh), int(max_out), _ptr(det), _ptr(score), _ptr(count), _stream()))
     return det, score, count
@@ -1021,22 +1073,20 @@ def _net_size(net_size, S):
     return int(net_size)
 
 
+def _canvas(pool, table, index, n, size, dtype, out):
+    """the pool / table / index contract of the letterbox and warp calls -> their output [n,size,size,3] of dtype"""
+    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()
+    _entries(table, index, n, table.shape[0])
+    return _own(out, (n, size, size, 3), dtype, pool.device, n * size * size * 3)
+
+
 def letterbox_batch(pool, table, index, n, size, fill=127, out=None):
     """pool uint8 [bytes], table int64 [entries][5], index int32 [n] or None (DeviceVOC's) -> out uint8 [n,size,size,3]:
     every entry letterboxed into a canvas of `fill` (img_dataset/pascal_voc.letterbox_u8, bit for bit); one launch on the
     current stream.  The batch detect_anchor_batch(..., net_size=size) un-maps."""
-    lib = _lib.load()
-    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert table.shape[0] >= n
-    if out is None:
-        out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=pool.device)
-    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * size * size * 3
-    check(lib.y2_letterbox_u8_batch(_ptr(pool), _ptr(table), _ptr(index), int(n), int(size), int(fill), _ptr(out),
-                                    _stream()))
+    out = _canvas(pool, table, index, n, size, torch.uint8, out)
+    check(_lib.load().y2_letterbox_u8_batch(_ptr(pool), _ptr(table), _ptr(index), int(n), int(size), int(fill),
+                                            _ptr(out), _stream()))
     return out
 
 
@@ -1045,29 +1095,43 @@ def warp_batch(pool, table, index, n, size, params=None, fill=127, labels=None, 
     every slot through its affine map and colour triple (img_dataset/augment_cls.ClsAugment.image, bit for bit; None: the
     plain stretch, augment_cls.plain_image).  labels int32 [entries]: also labels_out int32 [n] = labels[index], from the
     same launch, and the return value is (out, labels_out).  One launch on the current stream."""
-    lib = _lib.load()
-    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert table.shape[0] >= n
+    out = _canvas(pool, table, index, n, size, torch.uint8, out)
     if params is not None:
-        assert params.is_cuda and params.dtype == torch.float64 and params.is_contiguous() and params.numel() >= 9 * n
-    if out is None:
-        out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=pool.device)
-    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * size * size * 3
+        assert _dev(params, torch.float64, "params").numel() >= 9 * n
     if labels is not None:
-        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()
+        _dev(labels, torch.int32, "labels")
         if labels_out is None:
             labels_out = torch.empty((n,), dtype=torch.int32, device=pool.device)
-        assert labels_out.is_cuda and labels_out.dtype == torch.int32 and labels_out.is_contiguous()
-        assert labels_out.numel() >= n
+        assert _dev(labels_out, torch.int32, "labels_out").numel() >= n
     else:
         assert labels_out is None, "labels_out without labels"
-    check(lib.y2_warp_u8_batch(_ptr(pool), _ptr(table), _ptr(index), _ptr(params), _ptr(labels), int(n), int(size),
-                               int(size), int(fill), _ptr(out), _ptr(labels_out), _stream()))
+    check(_lib.load().y2_warp_u8_batch(_ptr(pool), _ptr(table), _ptr(index), _ptr(params), _ptr(labels), int(n),
+                                       int(size), int(size), int(fill), _ptr(out), _ptr(labels_out), _stream()))
     return out if labels is None else (out, labels_out)
+
+
+def _detect_anchor(plain, letterboxed, per_class, net, anchors, table, index, score_thresh, iou_thresh, m, out, net_size):
+    """the body of the three per-anchor detect calls: `plain` / `letterboxed` name the library's entry without and with
+    net_size; rows per image (m = max_out) or per (image, class) (m = max_per_class)"""
+    lib = _lib.load()
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, S, _, B, d = net.shape
+    assert net.shape[2] == S and d > 5, net.shape
+    C = d - 5
+    an = _anchors(anchors, B, net.device)
+    _entries(table, index, n, table.shape[0])
+    if per_class:
+        det, score, count = _det_out(out, (n, C), n * C, m, net.device)
+    else:
+        det, score, count = _det_out(out, (n,), n, m, net.device)
+    if net_size is not None:
+        check(getattr(lib, letterboxed)(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C, float(score_thresh),
+                                        float(iou_thresh), int(m), _net_size(net_size, S), _ptr(det), _ptr(score),
+                                        _ptr(count), _stream()))
+    else:
+        check(getattr(lib, plain)(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C, float(score_thresh),
+                                  float(iou_thresh), int(m), _ptr(det), _ptr(score), _ptr(count), _stream()))
+    return det, score, count
 
 
 def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None,
@@ -1078,37 +1142,8 @@ def detect_anchor_batch(net, anchors, table, index=None, score_thresh=0.005, iou
     (utils/detect_batch.anchor_detect on decode_anchors + class_argmax of the same net, bit for bit).  net_size: the
     input was letterboxed at that size (letterbox_batch; it must be 32 S) and the boxes are un-mapped from the picture's
     rectangle (anchor_detect with net_size, y2_detect_anchor_batch_lb); None: a plain stretch"""
-    lib = _lib.load()
-    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
-    n, S, _, B, d = net.shape
-    assert net.shape[2] == S and d > 5, net.shape
-    if torch.is_tensor(anchors):
-        an = anchors
-        assert an.is_cuda and an.dtype == torch.float32 and an.is_contiguous()
-    else:
-        an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
-    assert an.numel() == 2 * B, (tuple(an.shape), B)
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert table.shape[0] >= n
-    if out is None:
-        out = (torch.empty((n, max_out, 6), dtype=torch.int32, device=net.device),
-               torch.empty((n, max_out), dtype=torch.float32, device=net.device),
-               torch.empty((n,), dtype=torch.int32, device=net.device))
-    det, score, count = out
-    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * max_out * 6
-    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * max_out
-    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n
-    if net_size is not None:
-        check(lib.y2_detect_anchor_batch_lb(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, d - 5,
-                                            float(score_thresh), float(iou_thresh), int(max_out), _net_size(net_size, S),
-                                            _ptr(det), _ptr(score), _ptr(count), _stream()))
-        return det, score, count
-    check(lib.y2_detect_anchor_batch(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, d - 5, float(score_thresh),
-                                     float(iou_thresh), int(max_out), _ptr(det), _ptr(score), _ptr(count), _stream()))
-    return det, score, count
+    return _detect_anchor("y2_detect_anchor_batch", "y2_detect_anchor_batch_lb", False, net, anchors, table, index,
+                          score_thresh, iou_thresh, max_out, out, net_size)
 
 
 def detect_anchor_classes_batch(net, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_per_class=32,
@@ -1118,47 +1153,12 @@ def detect_anchor_classes_batch(net, anchors, table, index=None, score_thresh=0.
     `valid` writes them (utils/detect_batch.anchor_detect_classes on decode_anchors of the same net, bit for bit).
     det.view(n * C, max_per_class, 6) with count.view(-1) and every index repeated C times is what voc_match_batch
     reads.  net_size as in detect_anchor_batch (y2_detect_anchor_classes_batch_lb)."""
-    lib = _lib.load()
-    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
-    n, S, _, B, d = net.shape
-    assert net.shape[2] == S and d > 5, net.shape
-    C = d - 5
-    if torch.is_tensor(anchors):
-        an = anchors
-        assert an.is_cuda and an.dtype == torch.float32 and an.is_contiguous()
-    else:
-        an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
-    assert an.numel() == 2 * B, (tuple(an.shape), B)
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert table.shape[0] >= n
-    if out is None:
-        out = (torch.empty((n, C, max_per_class, 6), dtype=torch.int32, device=net.device),
-               torch.empty((n, C, max_per_class), dtype=torch.float32, device=net.device),
-               torch.empty((n, C), dtype=torch.int32, device=net.device))
-    det, score, count = out
-    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * C * max_per_class * 6
-    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * C * max_per_class
-    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n * C
-    if net_size is not None:
-        check(lib.y2_detect_anchor_classes_batch_lb(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C,
-                                                    float(score_thresh), float(iou_thresh), int(max_per_class),
-                                                    _net_size(net_size, S), _ptr(det), _ptr(score), _ptr(count),
-                                                    _stream()))
-        return det, score, count
-    check(lib.y2_detect_anchor_classes_batch(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C,
-                                             float(score_thresh), float(iou_thresh), int(max_per_class), _ptr(det),
-                                             _ptr(score), _ptr(count), _stream()))
-    return det, score, count
+    return _detect_anchor("y2_detect_anchor_classes_batch", "y2_detect_anchor_classes_batch_lb", True, net, anchors, table,
+                          index, score_thresh, iou_thresh, max_per_class, out, net_size)
 
 
-def voc_match_batch(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):
-    """det int32 [n,max_out,6], score [n,max_out], count [n] (detect_grid_batch); boxes float64 [entries,max_obj,5],
-    counts int32 [entries], difficult uint8 [entries,max_obj] (DeviceVOC) -> flags int32 [n,max_out]: 1 true positive,
-    0 false positive, 2 ignored, -1 beyond count (utils/detect_batch.match_image, bit for bit)"""
-    lib = _lib.load()
+def _voc_match(symbol, det, score, count, boxes, counts, difficult, index, iou_thresh, out):
+    """the body of voc_match_batch (integer rows) and voc_match_batch_f (float rows): one library symbol apart"""
     assert det.is_cuda and det.dtype == torch.int32 and det.is_contiguous() and det.dim() == 3 and det.shape[2] == 6
     n, max_out = det.shape[0], det.shape[1]
     assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == n
@@ -1168,15 +1168,19 @@ def voc_match_batch(det, score, count, boxes, counts, difficult, index=None, iou
     assert boxes.shape[2] == 5 and counts.dtype == torch.int32 and counts.numel() == boxes.shape[0]
     assert difficult.is_cuda and difficult.dtype == torch.uint8 and difficult.is_contiguous()
     assert tuple(difficult.shape) == (boxes.shape[0], max_obj), difficult.shape
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert boxes.shape[0] >= n
+    _entries(None, index, n, boxes.shape[0])       # no table here: without an index, the first n rows of `boxes`
     flags = torch.empty((n, max_out), dtype=torch.int32, device=det.device) if out is None else out
     assert flags.is_contiguous() and flags.dtype == torch.int32 and flags.numel() == n * max_out
-    check(lib.y2_voc_match_batch(_ptr(det), _ptr(score), _ptr(count), _ptr(boxes), _ptr(counts), _ptr(difficult),
-                                 _ptr(index), n, max_obj, max_out, float(iou_thresh), _ptr(flags), _stream()))
+    check(getattr(_lib.load(), symbol)(_ptr(det), _ptr(score), _ptr(count), _ptr(boxes), _ptr(counts), _ptr(difficult),
+                                       _ptr(index), n, max_obj, max_out, float(iou_thresh), _ptr(flags), _stream()))
     return flags
+
+
+def voc_match_batch(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):
+    """det int32 [n,max_out,6], score [n,max_out], count [n] (detect_grid_batch); boxes float64 [entries,max_obj,5],
+    counts int32 [entries], difficult uint8 [entries,max_obj] (DeviceVOC) -> flags int32 [n,max_out]: 1 true positive,
+    0 false positive, 2 ignored, -1 beyond count (utils/detect_batch.match_image, bit for bit)"""
+    return _voc_match("y2_voc_match_batch", det, score, count, boxes, counts, difficult, index, iou_thresh, out)
 
 
 # ---- Darknet's test-time protocol (csrc/darknet_io.hip; DESIGN.md 9)
@@ -1185,17 +1189,9 @@ def letterbox_darknet_batch(pool, table, index, n, size, out=None):
     float letterbox_image (corner-aligned two-pass bilinear in float32, bars of 0.5;
     img_dataset/pascal_voc.letterbox_darknet, bit for bit), one launch from the uint8 pool to the network's input on the
     current stream.  The batch detect_anchor_classes_batch_darknet(..., net_size=size) un-maps."""
-    lib = _lib.load()
-    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert table.shape[0] >= n
-    if out is None:
-        out = torch.empty((n, size, size, 3), dtype=torch.float32, device=pool.device)
-    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * size * size * 3
-    check(lib.y2_letterbox_darknet_batch(_ptr(pool), _ptr(table), _ptr(index), int(n), int(size), _ptr(out), _stream()))
+    out = _canvas(pool, table, index, n, size, torch.float32, out)
+    check(_lib.load().y2_letterbox_darknet_batch(_ptr(pool), _ptr(table), _ptr(index), int(n), int(size), _ptr(out),
+                                                 _stream()))
     return out
 
 
@@ -1207,60 +1203,16 @@ def detect_anchor_classes_batch_darknet(net, anchors, table, index=None, score_t
     corners -- det[..., :4].view(torch.float32) -- so det keeps its int32 layout
     (utils/detect_batch.anchor_detect_classes_darknet on decode_anchors of the same net, bit for bit).
     voc_match_batch_f reads the [n * C] view."""
-    lib = _lib.load()
     if net_size is None:
         raise ValueError("detect_anchor_classes_batch_darknet needs net_size: Darknet's protocol is letterboxed")
-    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
-    n, S, _, B, d = net.shape
-    assert net.shape[2] == S and d > 5, net.shape
-    C = d - 5
-    if torch.is_tensor(anchors):
-        an = anchors
-        assert an.is_cuda and an.dtype == torch.float32 and an.is_contiguous()
-    else:
-        an = torch.as_tensor(np.asarray(anchors, np.float32)).to(net.device).contiguous()
-    assert an.numel() == 2 * B, (tuple(an.shape), B)
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape[-1] == 5
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert table.shape[0] >= n
-    if out is None:
-        out = (torch.empty((n, C, max_per_class, 6), dtype=torch.int32, device=net.device),
-               torch.empty((n, C, max_per_class), dtype=torch.float32, device=net.device),
-               torch.empty((n, C), dtype=torch.int32, device=net.device))
-    det, score, count = out
-    assert det.is_contiguous() and det.dtype == torch.int32 and det.numel() == n * C * max_per_class * 6
-    assert score.is_contiguous() and score.dtype == torch.float32 and score.numel() == n * C * max_per_class
-    assert count.is_contiguous() and count.dtype == torch.int32 and count.numel() == n * C
-    check(lib.y2_detect_anchor_classes_batch_dk(_ptr(net), _ptr(an), _ptr(table), _ptr(index), n, S, B, C,
-                                                float(score_thresh), float(iou_thresh), int(max_per_class),
-                                                _net_size(net_size, S), _ptr(det), _ptr(score), _ptr(count), _stream()))
-    return det, score, count
+    return _detect_anchor(None, "y2_detect_anchor_classes_batch_dk", True, net, anchors, table, index, score_thresh,
+                          iou_thresh, max_per_class, out, net_size)
 
 
 def voc_match_batch_f(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):
     """voc_match_batch for rows whose words 0..3 hold float32 corners (detect_anchor_classes_batch_darknet):
     utils/detect_batch.match_image_f, bit for bit"""
-    lib = _lib.load()
-    assert det.is_cuda and det.dtype == torch.int32 and det.is_contiguous() and det.dim() == 3 and det.shape[2] == 6
-    n, max_out = det.shape[0], det.shape[1]
-    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == n
-    assert score is None or (score.dtype == torch.float32 and score.is_contiguous() and score.numel() == n * max_out)
-    assert boxes.is_cuda and boxes.dtype == torch.float64 and boxes.is_contiguous() and boxes.dim() == 3
-    max_obj = boxes.shape[1]
-    assert boxes.shape[2] == 5 and counts.dtype == torch.int32 and counts.numel() == boxes.shape[0]
-    assert difficult.is_cuda and difficult.dtype == torch.uint8 and difficult.is_contiguous()
-    assert tuple(difficult.shape) == (boxes.shape[0], max_obj), difficult.shape
-    if index is not None:
-        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and index.numel() >= n
-    else:
-        assert boxes.shape[0] >= n
-    flags = torch.empty((n, max_out), dtype=torch.int32, device=det.device) if out is None else out
-    assert flags.is_contiguous() and flags.dtype == torch.int32 and flags.numel() == n * max_out
-    check(lib.y2_voc_match_batch_f(_ptr(det), _ptr(score), _ptr(count), _ptr(boxes), _ptr(counts), _ptr(difficult),
-                                   _ptr(index), n, max_obj, max_out, float(iou_thresh), _ptr(flags), _stream()))
-    return flags
+    return _voc_match("y2_voc_match_batch_f", det, score, count, boxes, counts, difficult, index, iou_thresh, out)
 
 
 def softmax_cross_entropy(logits, labels, need_grad=True):
@@ -1304,22 +1256,16 @@ def score_views(logits, labels=None, views=1, k=5, n_valid=None, hits=None, want
     n = rows // views
     n_valid = n if n_valid is None else int(n_valid)
     dev = logits.device
-
-    def own(t, shape, dtype, name):
-        if t is None:
-            return torch.empty(shape, dtype=dtype, device=dev)
-        assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), (name, t.shape)
-        return t
-    top_idx = own(top_idx, (n, k), torch.int32, "top_idx")
-    top_val = own(top_val, (n, k), torch.float32, "top_val")
+    top_idx = _own(top_idx, (n, k), torch.int32, dev)
+    top_val = _own(top_val, (n, k), torch.float32, dev)
     if labels is not None:
-        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == n
-        rank = own(rank, (n,), torch.int32, "rank")
-        hits = torch.zeros(4, dtype=torch.int32, device=dev) if hits is None else own(hits, (4,), torch.int32, "hits")
+        assert _dev(labels, torch.int32, "labels").numel() == n
+        rank = _own(rank, (n,), torch.int32, dev)
+        hits = torch.zeros(4, dtype=torch.int32, device=dev) if hits is None else _own(hits, (4,), torch.int32, dev)
     else:
         assert rank is None and hits is None, "rank and hits need labels"
     if want_prob or prob is not None:
-        prob = own(prob, (n, classes), torch.float32, "prob")
+        prob = _own(prob, (n, classes), torch.float32, dev)
     check(lib.y2_score_views(_ptr(logits), _ptr(labels), n, views, classes, k, n_valid, _ptr(prob), _ptr(top_idx),
                              _ptr(top_val), _ptr(rank), _ptr(hits), _stream()))
     return top_idx, top_val, rank, hits, prob
@@ -1360,11 +1306,6 @@ def conv2d_backward(x, w, dy, dtype="f32", dw_out=None):
 
 # ---- operators of the ResNet-50 backbone swap (csrc/resnet_ops.hip; reference: slim_dir/nets/resnet_v1.py,
 # resnet_utils.py, pascal/pascal_train_resnet.py:37-50) on fp32 NHWC device tensors -----------------------------
-def _chk(*ts):
-    for t in ts:
-        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
-
-
 def batch_norm_forward(x, gamma, beta, moving_mean, moving_var, residual=None, is_training=True, update_moving=False,
                        relu=True, eps=1e-5, decay=0.997):
     """slim.batch_norm (+ residual add, + ReLU) on [..., C] -> (y, save_mean, save_var)"""
