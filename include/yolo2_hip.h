@@ -223,6 +223,16 @@ int y2_passthrough_concat_darknet(const float* fine, const float* coarse, float*
  * writes every element of both outputs exactly once: no zero fill, no atomics, bit exact.  Y2_ERR_ARG as above. */
 int y2_passthrough_concat_darknet_backward(const float* dout, float* dfine, float* dcoarse, int N, int H, int W, int Cf,
                                            int Cc, void* stream);
+/* Darknet's `[maxpool] size=2 stride=1` on fp32 NHWC (specification: utils/darknet_maxpool.py): y [N,H,W,C], y(i, j) =
+ * the maximum of x(i + dy, j + dx), dy, dx in {0, 1}, over the taps inside the map -- a window anchored top-left and
+ * clipped at the bottom and right edges; the maximum starts at -FLT_MAX and moves on a strict >, so the first maximum
+ * wins a tie and a NaN is never chosen.  Bit exact, one launch; 16-byte accesses when C % 4 == 0 and the pointers are
+ * 16-byte aligned, one float per lane otherwise.  Y2_ERR_ARG: a null tensor, a size below 1, more than 2^31 - 1 elements. */
+int y2_maxpool2x2s1(const float* x, float* y, int N, int H, int W, int C, void* stream);
+/* Its gradient: dx(p) = the float32 sum, from +0, of the dy of the up to four windows whose arg-max p is, in ascending
+ * row-major order of their anchors.  A gather: every dx element is written exactly once, no zero fill, no atomics, the
+ * same bits every run; a window of NaNs alone routes no gradient.  Y2_ERR_ARG as above. */
+int y2_maxpool2x2s1_backward(const float* x, const float* dy, float* dx, int N, int H, int W, int C, void* stream);
 /* x[0 .. n) = 0 on an fp32 buffer (a trainer's gradient masks: parameters that must not move) */
 int y2_zero(float* x, size_t n, void* stream);
 /* Darknet's network input from uint8 BGR pixels: dst[p][c] = float(src[p][2 - c]) / 255.0f (RGB in [0, 1]; a true

@@ -74,6 +74,8 @@ SIGNATURES = {
     "y2_accuracy": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "y2_maxpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "y2_maxpool2x2_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "y2_maxpool2x2s1": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "y2_maxpool2x2s1_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "y2_reorg": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "y2_passthrough_concat": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "y2_passthrough_concat_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

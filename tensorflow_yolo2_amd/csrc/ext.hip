@@ -10,6 +10,7 @@
 #include "../../include/yolo2_hip.h"
 
 #include <stdarg.h>
+#include <float.h>
 namespace y2 {
 int set_error(int code, const char* msg);   // net.hip (y2_last_error)
 }
@@ -867,7 +868,143 @@ static int darknet_passthrough_launch(const char* what, void (*vec4)(A*, B*, C*,
     return Y2_OK;
 }
 
+// Darknet's `[maxpool] size=2 stride=1` (maxpool_layer.c with padding = size - 1 = 1, offset -padding / 2 = 0) on fp32
+// NHWC; specification: utils/darknet_maxpool.py.  Output (i, j) is the maximum over input (i + dy, j + dx), dy, dx in
+// {0, 1}, of the taps inside the map: the window is anchored top-left and clipped at the bottom and right edges.  The
+// running maximum starts at -FLT_MAX and is replaced on a strict >, taps in the order (0,0), (0,1), (1,0), (1,1): the
+// first maximum wins a tie (-0.0 does not displace +0.0 nor the reverse) and a NaN is never chosen.  A window of NaNs
+// alone keeps -FLT_MAX and has no arg-max, so it routes no gradient -- where Darknet would index out of bounds.
+//
+// Both kernels walk the tensor's channel groups with one grid-stride loop: a lane owns VEC consecutive channels of one
+// pixel and consecutive lanes hold consecutive channel groups, so a wave reads and writes whole stretches of a row of C
+// floats.  VEC = 4: 16-byte loads and stores; VEC = 1: C % 4 != 0 or a pointer off 16 bytes.  Every index fits 31 bits
+// (the entry points check), so the index arithmetic is 32-bit.  No LDS, no scratch.
+template <int VEC>
+Y2_DEV void s1_load(float (&v)[VEC], const float* __restrict__ p) {
+    if (VEC == 4) { const f32x4 w = *(const f32x4*)p; for (int q = 0; q < 4; ++q) v[q] = w[q]; }
+    else v[0] = *p;
+}
+
+template <int VEC>
+Y2_DEV void s1_store(float* __restrict__ p, const float (&v)[VEC]) {
+    if (VEC == 4) { f32x4 w; for (int q = 0; q < 4; ++q) w[q] = v[q]; *(f32x4*)p = w; }
+    else *p = v[0];
+}
+
+// forward: a lane owns VEC consecutive channels of one OUTPUT pixel: up to four loads, one store
+template <int VEC>
+__global__ __launch_bounds__(256) void maxpool2x2s1_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H,
+                                                           int W, int C) {
+    const uint32_t cv = C / VEC, total = (uint32_t)N * H * W * cv;
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const uint32_t pix = e / cv;                 // (n * H + i) * W + j; e * VEC = pix * C + c
+        const int j = (int)(pix % W), i = (int)((pix / W) % H);
+        const bool right = j + 1 < W, below = i + 1 < H;
+        const float* p = x + (size_t)e * VEC;        // tap (0,0)
+        float best[VEC], v[VEC];
+        for (int q = 0; q < VEC; ++q) best[q] = -FLT_MAX;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (((t & 1) && !right) || ((t >> 1) && !below)) continue;
+            s1_load<VEC>(v, p + ((t >> 1) * W + (t & 1)) * C);
+            for (int q = 0; q < VEC; ++q)
+                if (v[q] > best[q]) best[q] = v[q];
+        }
+        s1_store<VEC>(y + (size_t)e * VEC, best);
+    }
+}
+
+// backward, the GATHER form: a lane owns VEC channels of one INPUT pixel (i, j), decides which of the up to four windows
+// that hold it -- anchors (i-1,j-1), (i-1,j), (i,j-1), (i,j), in which it is tap 3, 2, 1, 0 -- it won, and adds the dy
+// of those in that (ascending row-major) order, starting from +0.0f; then ONE store of dx.  No atomics, no zero fill,
+// every dx element written exactly once, the same bits every run.
+//
+// The four windows lie in the 3 x 3 neighbourhood of the pixel, which the lane loads once (nine loads where the
+// forward rule, window by window, asks sixteen times); a position outside the map holds NaN, which loses every
+// comparison below just as a clipped tap takes no part.  The pixel's value m wins a window under the running-maximum
+// rule exactly when
+//     m > -FLT_MAX,   no EARLIER tap u has u >= m   and   no LATER tap u has u > m:
+// an earlier tap with u >= m leaves a running maximum that m does not exceed, and otherwise the running maximum in front
+// of m is below it (or still -FLT_MAX); m then stays unless a later tap exceeds it.  A NaN m fails the first test, a NaN
+// u fails both of its tests, as in the running rule.
+template <int VEC>
+__global__ __launch_bounds__(256) void maxpool2x2s1_backward_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                    float* __restrict__ dx, int N, int H, int W, int C) {
+    const uint32_t cv = C / VEC, total = (uint32_t)N * H * W * cv;
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const uint32_t pix = e / cv;
+        const int j = (int)(pix % W), i = (int)((pix / W) % H);
+        const bool rows_in[3] = {i > 0, true, i + 1 < H}, cols_in[3] = {j > 0, true, j + 1 < W};
+        const size_t at = (size_t)e * VEC;           // this pixel's channels
+        float v[3][3][VEC];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                if (rows_in[r] && cols_in[s]) s1_load<VEC>(v[r][s], x + at + ((r - 1) * W + (s - 1)) * C);
+                else for (int q = 0; q < VEC; ++q) v[r][s][q] = __builtin_nanf("");
+            }
+        float acc[VEC], g[VEC];
+        for (int q = 0; q < VEC; ++q) acc[q] = 0.0f;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {                // the anchor (i - 1 + ar, j - 1 + as); this pixel is its tap 3 - a
+            const int ar = a >> 1, as = a & 1;
+            if (!rows_in[ar] || !cols_in[as]) continue;
+            s1_load<VEC>(g, dy + at + ((ar - 1) * W + (as - 1)) * C);
+            for (int q = 0; q < VEC; ++q) {
+                const float m = v[1][1][q];
+                bool wins = m > -FLT_MAX;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    if (t == 3 - a) continue;
+                    const float u = v[ar + (t >> 1)][as + (t & 1)][q];
+                    wins = wins && (t < 3 - a ? !(u >= m) : !(u > m));
+                }
+                if (wins) acc[q] += g[q];
+            }
+        }
+        s1_store<VEC>(dx + at, acc);
+    }
+}
+
+// the checks and the grid the two stride-1 pool entry points share (`what`: the entry point's name, for its messages)
+static int maxpool2x2s1_check(const char* what, bool null, int N, int H, int W, int C) {
+    if (null) return fail(Y2_ERR_ARG, "%s: null tensor", what);
+    if (N < 1 || H < 1 || W < 1 || C < 1)
+        return fail(Y2_ERR_ARG, "%s: N = %d, H = %d, W = %d, C = %d must be positive", what, N, H, W, C);
+    const long long rows = (long long)N * H;         // below 2^62; the next factors go in only while the count fits 31 bits
+    if (rows > 0x7fffffffLL || rows * W > 0x7fffffffLL || rows * W * C > 0x7fffffffLL)
+        return fail(Y2_ERR_ARG, "%s: %d x %d x %d x %d elements are beyond 32-bit indices", what, N, H, W, C);
+    return Y2_OK;
+}
+
+static unsigned maxpool2x2s1_blocks(int N, int H, int W, int C, bool vec) {
+    const size_t total = (size_t)N * H * W * (size_t)(C / (vec ? 4 : 1));
+    const size_t nb = (total + 255) / 256;
+    return (unsigned)(nb > 65536 ? 65536 : nb);
+}
+
 extern "C" {
+
+int y2_maxpool2x2s1(const float* x, float* y, int N, int H, int W, int C, void* stream) {
+    const int rc = maxpool2x2s1_check("y2_maxpool2x2s1", !x || !y, N, H, W, C);
+    if (rc) return rc;
+    const bool vec = (C % 4) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0;
+    hipLaunchKernelGGL(vec ? maxpool2x2s1_kernel<4> : maxpool2x2s1_kernel<1>, dim3(maxpool2x2s1_blocks(N, H, W, C, vec)),
+                       dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C);
+    EXTCHK(hipGetLastError());
+    return Y2_OK;
+}
+
+int y2_maxpool2x2s1_backward(const float* x, const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
+    const int rc = maxpool2x2s1_check("y2_maxpool2x2s1_backward", !x || !dy || !dx, N, H, W, C);
+    if (rc) return rc;
+    const bool vec = (C % 4) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dx % 16) == 0;
+    hipLaunchKernelGGL(vec ? maxpool2x2s1_backward_kernel<4> : maxpool2x2s1_backward_kernel<1>,
+                       dim3(maxpool2x2s1_blocks(N, H, W, C, vec)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, N, H, W, C);
+    EXTCHK(hipGetLastError());
+    return Y2_OK;
+}
 
 int y2_passthrough_concat_darknet(const float* fine, const float* coarse, float* out, int N, int H, int W, int Cf, int Cc,
                                   void* stream) {

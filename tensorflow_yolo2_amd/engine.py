@@ -837,6 +837,32 @@ def max_pool_2x2_backward(x, dy):
     return dx
 
 
+def max_pool_2x2_s1(x):
+    """Darknet's `[maxpool] size=2 stride=1` on [N,H,W,C] fp32 -> [N,H,W,C]: the window anchored top-left, clipped at the
+    bottom and right edges (utils/darknet_maxpool.maxpool_s1, bit-equal)"""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError("max_pool_2x2_s1: x %s is no non-empty [N,H,W,C]" % (tuple(x.shape),))
+    n, h, w, c = x.shape
+    y = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    check(lib.y2_maxpool2x2s1(_ptr(x), _ptr(y), n, h, w, c, _stream()))
+    return y
+
+
+def max_pool_2x2_s1_backward(x, dy):
+    """the gradient of max_pool_2x2_s1 (utils/darknet_maxpool.maxpool_s1_backward, bit-equal): every dx element written once"""
+    lib = _lib.load()
+    assert x.is_cuda and dy.is_cuda and x.dtype == dy.dtype == torch.float32 and x.is_contiguous() and dy.is_contiguous()
+    if x.dim() != 4 or x.numel() == 0 or dy.shape != x.shape:
+        raise ValueError("max_pool_2x2_s1_backward: x %s must be a non-empty [N,H,W,C] and dy %s of its shape" %
+                         (tuple(x.shape), tuple(dy.shape)))
+    n, h, w, c = x.shape
+    dx = torch.empty_like(x)
+    check(lib.y2_maxpool2x2s1_backward(_ptr(x), _ptr(dy), _ptr(dx), n, h, w, c, _stream()))
+    return dx
+
+
 def reorg(x, stride=2, inverse=False):
     """space-to-depth [N,H,W,C] -> [N,H/s,W/s,s*s*C]; inverse=True: the gradient (depth-to-space)"""
     lib = _lib.load()

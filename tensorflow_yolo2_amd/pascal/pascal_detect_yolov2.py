@@ -14,7 +14,9 @@ plumbing run.  --protocol darknet prints what Darknet's own detector would: the 
 (y2_detect_anchor_classes_batch_dk; at most --max-out rows per class), float corners, every number with "%f"; each image's
 rows class by class, each class in descending score.  It needs --darknet-weights and goes with neither --stretch nor
 --fill.  --darknet-weights FILE runs a file Darknet wrote for yolov2-voc.cfg instead: the "darknet" topology of
-yolo2_nets/yolov2.py with the published VOC anchors (net_utils.load_darknet_weights); every other flag works as before."""
+yolo2_nets/yolov2.py with the published VOC anchors (net_utils.load_darknet_weights); every other flag works as before.
+A file of tiny-yolo-voc.cfg is taken the same way: its float count says so (net_utils.darknet_file_topology), and the
+"tiny" topology is built with that graph's published anchors."""
 import argparse
 import sys
 
@@ -103,7 +105,7 @@ def main(argv=None):
     if args.out:
         with open(args.out, "w") as f:
             f.write("".join(line + "\n" for line in lines))
-    result = {"rows": rows, "restored": restored, "detector": detector, "pool": pool}
+    result = {"rows": rows, "restored": restored, "detector": detector, "pool": pool, "topology": detector.topology}
     if args.keep_grids:
         result["grids"] = torch.cat(grids)[:entries]
     return result

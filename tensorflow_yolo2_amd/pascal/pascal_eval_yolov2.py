@@ -19,6 +19,9 @@ The anchors and the class count are the snapshot's (pascal_train_yolov2.py); wit
 initial values are evaluated with the published VOC anchors: a plumbing run.  --darknet-weights FILE evaluates a file
 Darknet wrote for yolov2-voc.cfg instead (the "darknet" topology of yolo2_nets/yolov2.py, net_utils.load_darknet_weights):
     pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --per-class --letterbox
+or one it wrote for tiny-yolo-voc.cfg (the "tiny" topology, with its own published anchors): the file's float count says
+which of the two graphs is built (net_utils.darknet_file_topology):
+    pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights tiny-yolo-voc.weights --protocol darknet
 and --protocol darknet scores it as Darknet's `valid` would (it implies the two switches): the float letterbox with bars
 of 0.5 in one launch from the pool (y2_letterbox_darknet_batch), Darknet's float un-map, float NMS and float corners
 (y2_detect_anchor_classes_batch_dk), the matcher on those (y2_voc_match_batch_f), and "%f" results files:
@@ -104,7 +107,7 @@ def main(argv=None):
         from ..utils import voc_eval
         result["results_files"] = voc_eval.write_results_files(args.results_dir, args.image_set, imdb.image_index,
                                                                pascal_voc.CLASSES[:num_class], result["rows"])
-    result.update(restored=restored, detector=detector, imdb=imdb)
+    result.update(restored=restored, detector=detector, imdb=imdb, topology=detector.topology)
     return result
 
 
@@ -126,7 +129,7 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     if darknet and not (per_class and letterbox):
         raise ValueError("protocol='darknet' scores one row per (box, class) on a letterboxed input: per_class=True, "
                          "letterbox=True")
-    if darknet and getattr(detector, "topology", "paper") != "darknet":
+    if darknet and getattr(detector, "topology", "paper") not in ("darknet", "tiny"):
         raise ValueError("protocol='darknet' needs a detector of the \"darknet\" topology, not %r"
                          % (getattr(detector, "topology", "paper"),))
     match = engine.voc_match_batch_f if darknet else engine.voc_match_batch

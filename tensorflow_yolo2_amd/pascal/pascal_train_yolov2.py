@@ -39,6 +39,11 @@ pascal_eval_yolov2 --darknet-weights read; a run with --ckpt-dir resumes from th
 moves the data as above.  A .weights file carries no optimizer state and no anchors: the moments and the loss scale start
 afresh, as in Darknet, and the anchors are the flags'.  A --ckpt-dir that holds the other topology's snapshots is an error.
 
+--topology tiny trains the graph of tiny-yolo-voc.cfg with the same trainer, files, snapshots and resume, and that graph's
+published anchors.  --darknet-weights FILE chooses between the two Darknet graphs by the file's float count
+(net_utils.darknet_file_topology); a stated --topology that contradicts the file is an argument error, and a --ckpt-dir
+whose .weights files belong to the other Darknet graph fails in the loader, by the float count.
+
 One process, one GPU."""
 import argparse
 import os
@@ -78,10 +83,12 @@ def parse_args(argv=None):
                     help="paper (default): the graph of yolo2_nets/yolov2.py, .npz snapshots; darknet: the graph of "
                          "yolov2-voc.cfg (YOLOv2DarknetTrainer), whose snapshots are train_iter_<i>.weights files Darknet "
                          "reads -- such a file carries no optimizer state, so a resumed run starts the moments and the loss "
-                         "scale afresh, as Darknet does, and takes the iteration from the file's `seen` / --batch")
+                         "scale afresh, as Darknet does, and takes the iteration from the file's `seen` / --batch; tiny: "
+                         "the graph of tiny-yolo-voc.cfg, the same trainer, snapshots and resume, its own published anchors")
     ap.add_argument("--darknet-weights", default=None,
-                    help="start from a whole Darknet .weights file (yolov2-voc.weights); implies --topology darknet; not "
-                         "with --darknet-backbone or --imagenet-ckpt-dir")
+                    help="start from a whole Darknet .weights file (yolov2-voc.weights or tiny-yolo-voc.weights); its float "
+                         "count chooses --topology darknet or tiny, and a stated --topology that contradicts the file is "
+                         "an error; not with --darknet-backbone or --imagenet-ckpt-dir")
     ap.add_argument("--anchors", default="voc", choices=("voc", "kmeans"),
                     help="voc: the published VOC anchors; kmeans: cluster the image set's boxes at --size")
     ap.add_argument("--box-labels", action="store_true", help="train on the box list (every object), not the label grid")
@@ -103,6 +110,7 @@ def parse_args(argv=None):
     ap.add_argument("--width-div", type=int, default=1, help="divide every inner width (tests)")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
+    args.error, args.topology_stated = ap.error, args.topology
     if args.size < 32 or args.size % 32:
         ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
     if args.batch < 1 or args.iters < 0 or args.save_every < 1 or args.width_div < 1:
@@ -114,11 +122,13 @@ def parse_args(argv=None):
             ap.error("--darknet-weights holds the whole model: not with --darknet-backbone or --imagenet-ckpt-dir")
         if args.topology == "paper":
             ap.error("--darknet-weights is a file of the darknet topology: not with --topology paper")
-        args.topology = "darknet"
+        if args.topology is None:
+            args.topology = "darknet"             # until main() has read the file's float count (file_topology)
     if args.topology is None:
         args.topology = "paper"
-    if args.topology == "darknet" and args.imagenet_ckpt_dir:
-        ap.error("--imagenet-ckpt-dir feeds the paper topology; with --topology darknet give --darknet-backbone FILE")
+    if args.topology in yolov2.DARKNET_FILE_TOPOLOGIES and args.imagenet_ckpt_dir:
+        ap.error("--imagenet-ckpt-dir feeds the paper topology; with --topology %s give --darknet-backbone FILE" %
+                 args.topology)
     try:
         args.ms_sizes = tuple(int(v) for v in str(args.ms_sizes).split(",") if v.strip())
     except ValueError:
@@ -170,7 +180,17 @@ def parse_args(argv=None):
 SOLVER_FLAGS = ("lr", "momentum", "decay", "burn_in", "power", "policy", "steps", "scales", "max_batches")
 
 
-TRAINERS = {"paper": yolov2.YOLOv2Trainer, "darknet": yolov2.YOLOv2DarknetTrainer}
+TRAINERS = {"paper": yolov2.YOLOv2Trainer, "darknet": yolov2.YOLOv2DarknetTrainer, "tiny": yolov2.YOLOv2DarknetTrainer}
+
+
+def file_topology(args, num_class):
+    """the topology of a run that starts from --darknet-weights: the graph whose float count the file has (at the image
+    set's classes, five anchors and --width-div); a stated --topology that is another one is an argument error"""
+    found = net_utils.darknet_file_topology(args.darknet_weights, num_class, len(yolov2.ANCHORS_VOC), args.width_div)
+    if args.topology_stated not in (None, found):
+        args.error("--topology %s, but --darknet-weights %s holds the %s graph" %
+                   (args.topology_stated, args.darknet_weights, found))
+    return found
 
 
 def step_size(args, i):
@@ -197,7 +217,9 @@ def main(argv=None):
     imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
                      seed=args.seed, augment=args.augmentation, max_boxes=args.max_boxes if args.box_labels else None)
     latest = None
-    darknet = args.topology == "darknet"
+    if args.darknet_weights:
+        args.topology = file_topology(args, imdb.num_class)
+    darknet = args.topology in yolov2.DARKNET_FILE_TOPOLOGIES
     if args.ckpt_dir:
         os.makedirs(args.ckpt_dir, exist_ok=True)
         latest = net_utils.latest_yolov2_snapshot(args.ckpt_dir, args.topology)
@@ -211,7 +233,7 @@ def main(argv=None):
         print("k-means anchors at {:d} (mean shape IoU {:.4f}): {}".format(
             args.size, A.mean_shape_iou(wh, anchors), np.round(anchors, 4).tolist()))
     else:
-        anchors = yolov2.ANCHORS_VOC
+        anchors = yolov2._TOPOLOGY[args.topology].anchors     # the graph's published ones
     first = step_size(args, 1) if args.multi_scale else args.size
     # Darknet's layers were trained with its batch-norm epsilon; a resumed run keeps its snapshot's (yolov2/bn_eps)
     bn_eps = yolov2.DARKNET_BN_EPS if args.darknet_backbone else None
@@ -219,7 +241,8 @@ def main(argv=None):
         bn_eps = net_utils.read_yolov2_bn_eps(latest)
     trainer = TRAINERS[args.topology](args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
                                       seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
-                                      prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps)
+                                      prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps,
+                                      topology=args.topology)
     last_iter_num = 0
     if latest:
         print('Restorining model snapshots from {:s}'.format(latest))
@@ -268,7 +291,7 @@ def main(argv=None):
             print("Model saved in file: %s" % net_utils.save_yolov2_snapshot(trainer, args.ckpt_dir, i))
     torch.cuda.synchronize()
     return {"losses": losses, "last_iter": TOTAL_ITER, "first_iter": last_iter_num + 1, "trainer": trainer,
-            "sizes": sizes, "anchors": np.asarray(anchors, np.float32), "imdb": imdb}
+            "sizes": sizes, "anchors": np.asarray(anchors, np.float32), "imdb": imdb, "topology": args.topology}
 
 
 if __name__ == "__main__":

@@ -14,8 +14,10 @@ def add_model_flags(ap, batch, batch_help, latest_is, darknet_classes):
     ap.add_argument("--weights", default=None, help="snapshot file (train_iter_<i>.npz of pascal_train_yolov2.py)")
     ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_*.npz snapshots: the latest is " + latest_is)
     ap.add_argument("--darknet-weights", default=None,
-                    help="a Darknet .weights file of yolov2-voc.cfg (yolov2-voc.weights): builds the \"darknet\" topology "
-                         "with the published VOC anchors and %s; not with --weights or --ckpt-dir" % darknet_classes)
+                    help="a Darknet .weights file of yolov2-voc.cfg (yolov2-voc.weights) or of tiny-yolo-voc.cfg "
+                         "(tiny-yolo-voc.weights): builds the graph the file holds, by its float count -- the \"darknet\" or "
+                         "the \"tiny\" topology -- with that graph's published anchors and %s; not with --weights or "
+                         "--ckpt-dir" % darknet_classes)
 
 
 def add_test_flags(ap):
@@ -37,7 +39,8 @@ def check_weights(ap, args):
 
 def find_snapshot(args, num_class):
     """-> (snapshot path or None, anchors, class count, bn_eps) of the model to build: the snapshot's own where --weights
-    or --ckpt-dir names one, else the published VOC anchors, `num_class` and the default epsilon"""
+    or --ckpt-dir names one, else the published VOC anchors, `num_class` and the default epsilon (--darknet-weights:
+    build_detector takes the published anchors of the graph the file holds)"""
     snapshot = args.weights
     if not snapshot and args.ckpt_dir:
         sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
@@ -51,12 +54,15 @@ def find_snapshot(args, num_class):
 def build_detector(args, snapshot, anchors, num_class, bn_eps):
     """the detector of find_snapshot's answer, filled from --darknet-weights or from the snapshot -> (detector, the
     snapshot's iteration or 0)"""
+    topology = "paper"
+    if args.darknet_weights:
+        topology = net_utils.darknet_file_topology(args.darknet_weights, num_class, len(anchors), args.width_div)
+        anchors = yolov2._TOPOLOGY[topology].anchors
     detector = yolov2.YOLOv2Detector(args.batch, args.size, num_class=num_class, anchors=anchors, dtype=args.dtype,
-                                     width_div=args.width_div, bn_eps=bn_eps,
-                                     topology="darknet" if args.darknet_weights else "paper")
+                                     width_div=args.width_div, bn_eps=bn_eps, topology=topology)
     restored = 0
     if args.darknet_weights:
-        print('Restorining model from Darknet weight file {:s}'.format(args.darknet_weights))
+        print('Restorining model from Darknet weight file {:s} (topology {:s})'.format(args.darknet_weights, topology))
         seen = net_utils.load_darknet_weights(detector, args.darknet_weights)
         print('{:d} images seen'.format(seen))
     if snapshot:

@@ -33,6 +33,14 @@ def yolov2_voc_layers(num_class=20, num_anchors=5):
     return layers
 
 
+def yolov2_tiny_voc_layers(num_class=20, num_anchors=5):
+    """the 9 convolutions of tiny-yolo-voc.cfg (yolov2-tiny-voc.cfg) as (k, c, n, batch_norm), in file order: 15,867,885
+    floats at 20 classes and 5 anchors -- with the 16-byte header the 63,471,556 bytes of tiny-yolo-voc.weights"""
+    widths = (3, 16, 32, 64, 128, 256, 512, 1024, 1024)
+    layers = [(3, c, n, True) for c, n in zip(widths[:-1], widths[1:])]
+    return layers + [(1, 1024, num_anchors * (5 + num_class), False)]
+
+
 def seen_is_64bit(major, minor):
     return major * 10 + minor >= 2 and major < 1000 and minor < 1000
 
@@ -148,6 +156,53 @@ def from_layer_params(p, k_file, batch_norm, eps, dtype=np.float32):
     t = s * (f64("b") - f64("moving_mean"))
     biases = np.where(f64("beta") == 0, t, t + f64("beta")).astype(dtype)        # (a zero beta keeps the sign of -0.0)
     return {"biases": biases, "weights": _filters_out(f64("W") * s, k_file, np.float64).astype(dtype)}
+
+
+PAD_VALUES = {"b": 0, "gamma": 1, "beta": 0, "moving_mean": 0, "moving_var": 1}
+
+
+def pad_layer_params(p, c_model, n_model):
+    """a layer dict of the file's widths [k][k][c][n] -> the same function at the model's widths c_model >= c, n_model >=
+    n (tiny-yolo-voc.cfg's 3 -> 16 and 16 -> 32 in stacks whose widths are multiples of 32): the added filters and input
+    channels are zero, the added filters' b = 0, gamma = 1, beta = 0, moving mean 0, moving variance 1.  Under zero
+    padding and either batch-norm mode a zero filter's activation is exactly 0 (batch mean 0, variance 0: 0 / sqrt(eps) =
+    0), and a zero input channel adds exactly 0 to every sum"""
+    W = np.asarray(p["W"])
+    k, _k, c, n = W.shape
+    if c > c_model or n > n_model:
+        raise ValueError("a %d -> %d layer does not fit a %d -> %d one" % (c, n, c_model, n_model))
+    if (c, n) == (c_model, n_model):
+        return p
+    out = {"W": np.zeros((k, k, c_model, n_model), W.dtype)}
+    out["W"][:, :, :c, :n] = W
+    for key, fill in PAD_VALUES.items():
+        a = np.asarray(p[key])
+        out[key] = np.concatenate([a, np.full(n_model - n, fill, a.dtype)])
+    return out
+
+
+def strip_layer_params(p, c_file, n_file, check=True):
+    """the inverse: the leading c_file input channels and n_file filters of a layer dict.  check: refuse a layer that is
+    not the padded form of one -- a non-zero filter value, b, beta or moving mean among the entries that go (gamma and
+    the moving variance scale an exact zero: training moves the padded variances, and they may)"""
+    W = np.asarray(p["W"])
+    _k, _k2, c, n = W.shape
+    if c_file > c or n_file > n:
+        raise ValueError("a %d -> %d layer holds no %d -> %d one" % (c, n, c_file, n_file))
+    if (c, n) == (c_file, n_file):
+        return p
+    if check:
+        gone = W.copy()
+        gone[:, :, :c_file, :n_file] = 0
+        bad = ["W"] if np.any(gone != 0) else []
+        bad += [key for key in ("b", "beta", "moving_mean") if np.any(np.asarray(p[key])[n_file:] != 0)]
+        if bad:
+            raise ValueError("a %d -> %d layer written as Darknet's %d -> %d needs its padded entries to be zero: %s has "
+                             "non-zero ones" % (c, n, c_file, n_file, ", ".join(bad)))
+    out = {"W": np.ascontiguousarray(W[:, :, :c_file, :n_file])}
+    for key in PAD_VALUES:
+        out[key] = np.asarray(p[key])[:n_file].copy()
+    return out
 
 
 def fold_first_layer(p, dtype=np.float32):

@@ -601,13 +601,14 @@ def read_yolov2_bn_eps(path):
 
 
 def _is_darknet(model):
-    return getattr(model, "topology", "paper") == "darknet"
+    """whether the model's graph is one a Darknet `.weights` file holds ("darknet", "tiny"): that file is its snapshot"""
+    return getattr(model, "topology", "paper") in _yolov2.DARKNET_FILE_TOPOLOGIES
 
 
 def _refuse_darknet_topology(model, what, instead):
     if _is_darknet(model):
-        raise ValueError("%s: .npz snapshots of the \"darknet\" topology are out of scope -- the .weights file is this "
-                         "topology's snapshot (%s)" % (what, instead))
+        raise ValueError("%s: .npz snapshots of the \"%s\" topology are out of scope -- the .weights file is this "
+                         "topology's snapshot (%s)" % (what, model.topology, instead))
 
 
 def _ordered_snapshots(ckpt_dir, ext):
@@ -670,29 +671,67 @@ def load_darknet19_backbone(model, core_layers):
 # layers of either from a shorter file, without a fold.
 # ---------------------------------------------------------------------------
 from ..utils import darknet_weights as _dkw
+from . import yolov2 as _yolov2
 
 
 def _darknet_model(model, what):
     if not _is_darknet(model):
-        raise ValueError("%s takes a YOLOv2Detector(topology=\"darknet\") or a YOLOv2DarknetTrainer: the paper topology's "
-                         "graph is not the one a Darknet file holds" % what)
+        raise ValueError("%s takes a YOLOv2Detector(topology=\"darknet\" or \"tiny\") or a YOLOv2DarknetTrainer: the "
+                         "paper topology's graph is not the one a Darknet file holds" % what)
     return model.networks()
 
 
-def darknet_file_layers(model):
-    """[(k, c, n, batch_norm)] of the file a "darknet" detector reads and writes: its layers in networks() order, every
-    one with batch norm but the last, and Darknet's filter size in the 18 core positions (its fourth layer is 1x1)"""
-    nets = _darknet_model(model, "darknet_file_layers")
+def _file_layers(topology, specs):
+    """[(k, c, n, batch_norm)] of the file of a Darknet graph from its stacks' specs, in networks() order: every layer
+    with batch norm but the last; on "darknet" Darknet's filter size in the 18 core positions (its fourth layer is 1x1);
+    on "tiny" the FILE's widths of the narrow layers (16 filters, and c = 16 behind them), which the stacks run padded"""
+    topo = _yolov2._TOPOLOGY[topology]
+    narrow = dict(topo.narrow)
     out = []
-    for net in nets:
-        for l, (k, ci, co, _pool) in enumerate(net.spec):
-            kf = _dkw.DARKNET19_CORE[len(out)][0] if len(out) < len(_dkw.DARKNET19_CORE) else k
-            out.append((kf, ci, co, not (net is nets[-1] and l == net.num_layers - 1)))
+    for s, spec in enumerate(specs):
+        for l, (k, ci, co, _pool) in enumerate(spec):
+            if topology == "darknet" and len(out) < len(_dkw.DARKNET19_CORE):
+                k = _dkw.DARKNET19_CORE[len(out)][0]
+            if s == 0:
+                ci, co = narrow.get(l - 1, ci), narrow.get(l, co)
+            out.append((k, ci, co, not (s == len(specs) - 1 and l == len(spec) - 1)))
     return out
 
 
+def darknet_file_layers(model):
+    """[(k, c, n, batch_norm)] of the file a "darknet" or "tiny" detector or trainer reads and writes (_file_layers)"""
+    nets = _darknet_model(model, "darknet_file_layers")
+    return _file_layers(model.topology, [net.spec for net in nets])
+
+
+def darknet_graph_floats(topology, num_class, num_anchors, width_div=1):
+    """the float count of the `.weights` file of a Darknet graph at these classes, anchors and widths"""
+    specs = _yolov2._TOPOLOGY[topology].specs(num_class, num_anchors, width_div)
+    return sum(_dkw.layer_floats(l) for l in _file_layers(topology, specs))
+
+
+def darknet_file_topology(path, num_class, num_anchors, width_div=1):
+    """which Darknet graph a `.weights` file holds, by its float count -> "darknet" (yolov2-voc.cfg) or "tiny"
+    (tiny-yolo-voc.cfg); a count that is neither raises, naming both expected counts"""
+    values = _dkw.read(path)[4]
+    counts = {t: darknet_graph_floats(t, num_class, num_anchors, width_div) for t in _yolov2.DARKNET_FILE_TOPOLOGIES}
+    for t, n in counts.items():
+        if n == values.size:
+            return t
+    raise ValueError("%s holds %d floats: at %d classes, %d anchors and width_div %d the \"darknet\" graph "
+                     "(yolov2-voc.cfg) holds %d and the \"tiny\" graph (tiny-yolo-voc.cfg) holds %d" %
+                     (path, values.size, num_class, num_anchors, width_div, counts["darknet"], counts["tiny"]))
+
+
+def _other_graph(model):
+    """for the float-count errors: what the file of the OTHER Darknet graph holds at the model's classes, anchors and width"""
+    (other,) = [t for t in _yolov2.DARKNET_FILE_TOPOLOGIES if t != model.topology]
+    return "the \"%s\" graph at these classes, anchors and width_div %d holds %d floats" % (
+        other, model.width_div, darknet_graph_floats(other, model.num_class, model.B, model.width_div))
+
+
 def _describe(model):
-    return "%d classes, %d anchors, widths %s" % (model.num_class, model.B,
+    return "\"%s\" graph, %d classes, %d anchors, widths %s" % (model.topology, model.num_class, model.B,
                                                   "/".join(str(net.spec[-1][2]) for net in model.networks()))
 
 
@@ -707,13 +746,13 @@ def _load_darknet_layers(model, path, what, whole):
         layers, _used = _dkw.split(values, file_layers)
     except ValueError as e:
         if whole:
-            raise ValueError("%s holds %d floats, the model (%s: %d convolutions) needs %d: %s" %
-                             (path, values.size, _describe(model), len(file_layers), want, e))
+            raise ValueError("%s holds %d floats, the model (%s: %d convolutions) needs %d; %s: %s" %
+                             (path, values.size, _describe(model), len(file_layers), want, _other_graph(model), e))
         raise ValueError("%s holds %d floats, no whole-layer prefix of the model (%s: %d convolutions): %s" %
                          (path, values.size, _describe(model), len(file_layers), e))
     if whole and len(layers) != len(file_layers):
-        raise ValueError("%s holds %d convolutions (%d floats), the model (%s) has %d (%d floats)" %
-                         (path, len(layers), values.size, _describe(model), len(file_layers), want))
+        raise ValueError("%s holds %d convolutions (%d floats), the model (%s) has %d (%d floats); %s" %
+                         (path, len(layers), values.size, _describe(model), len(file_layers), want, _other_graph(model)))
     if not layers:
         raise ValueError("%s holds no convolution" % path)
     pos = 0
@@ -724,6 +763,7 @@ def _load_darknet_layers(model, path, what, whole):
         params = net.export_params()
         for l in range(take):
             p = _dkw.to_layer_params(layers[pos + l], net.spec[l][0], model.bn_eps)
+            p = _dkw.pad_layer_params(p, net.spec[l][1], net.spec[l][2])       # "tiny": the two narrow layers
             for k, shape in net._shapes(l).items():
                 if tuple(p[k].shape) != tuple(shape):
                     raise ValueError("%s: convolution %d %s has shape %s, the model (%s) expects %s" %
@@ -768,8 +808,8 @@ def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):
     out, pos = [], 0
     for net in nets:
         for l, p in enumerate(net.export_params()):
-            kf, _c, _n, bn = file_layers[pos + l]
-            out.append(_dkw.from_layer_params(p, kf, bn, model.bn_eps))
+            kf, c, n, bn = file_layers[pos + l]
+            out.append(_dkw.from_layer_params(_dkw.strip_layer_params(p, c, n), kf, bn, model.bn_eps))
         pos += net.num_layers
     return _dkw.write(path, out, seen, major, minor, revision)
 
@@ -778,12 +818,14 @@ def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):
 # One snapshot front for both topologies, keyed on model.topology / a topology name: the callers (pascal/) do not branch.
 # "paper": train_iter_<i>.npz, the whole train state.  "darknet": train_iter_<i>.weights, parameters and `seen`.
 # ---------------------------------------------------------------------------
-_SNAPSHOT_EXT = {"paper": ".npz", "darknet": ".weights"}
+_SNAPSHOT_EXT = {"paper": ".npz", "darknet": ".weights", "tiny": ".weights"}
 
 
 def latest_yolov2_snapshot(ckpt_dir, topology):
-    """the newest snapshot of `topology` in ckpt_dir, or None; a directory that holds the OTHER topology's raises"""
-    (other,) = [t for t in _SNAPSHOT_EXT if t != topology]
+    """the newest snapshot of `topology` in ckpt_dir, or None; a directory that holds snapshots of the OTHER format
+    raises.  The two Darknet graphs share the .weights format: a file of the other one fails in the loader, by its
+    float count"""
+    other = [t for t in _SNAPSHOT_EXT if _SNAPSHOT_EXT[t] != _SNAPSHOT_EXT[topology]][0]    # .weights: named "darknet"
     foreign = _ordered_snapshots(ckpt_dir, _SNAPSHOT_EXT[other])
     if foreign:
         raise ValueError("--ckpt-dir %s holds snapshots of the %s topology (%s); this run trains the %s topology, whose "
@@ -795,8 +837,8 @@ def latest_yolov2_snapshot(ckpt_dir, topology):
 
 def save_yolov2_snapshot(model, ckpt_dir, i):
     """snapshot `i` of a model into ckpt_dir, in its topology's format (`seen` = i * batch in a .weights file) -> the path"""
-    topology = "darknet" if _is_darknet(model) else "paper"
-    path = os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) + _SNAPSHOT_EXT[topology])
+    path = os.path.join(ckpt_dir, cfg.TRAIN_SNAPSHOT_PREFIX + '_iter_' + str(i) +
+                        _SNAPSHOT_EXT[getattr(model, "topology", "paper")])
     if _is_darknet(model):
         save_darknet_weights(model, path, seen=i * model.batch)
     else:
@@ -825,7 +867,6 @@ def read_darknet_backbone(path, bn_eps_model, width_div=1):
     the one-pixel border ring of the first layer's output, where Darknet pads with black and this stack with mid-grey.
     Darknet's epsilon is 1e-6 and the variances are not bent to another one: a model on any other epsilon is refused.
     width_div: the narrow variant's widths (tests); a Darknet file carries no shapes."""
-    from . import yolov2 as _yolov2
     if bn_eps_model is None or float(bn_eps_model) != _yolov2.DARKNET_BN_EPS:
         raise ValueError("read_darknet_backbone: the model's batch-norm epsilon is %s, Darknet's layers were trained with "
                          "%g -- build the trainer with YOLOv2Trainer(bn_eps=1e-6)" %

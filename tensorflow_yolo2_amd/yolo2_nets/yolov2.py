@@ -8,7 +8,9 @@ so the three stacks are `engine.Network` contexts; the glue ops are csrc/ext.hip
 yolov2_loss_kernel, specification oracle/ext_ref.py), backward through the head, the passthrough concat, the
 13x13 stack, the 2x2 pool and the stem, Adam (or, with `solver`, Darknet's SGD: utils/solver.py) on the three flat
 parameter buffers, optional multi-scale.  `YOLOv2DarknetTrainer` is the train step of the "darknet" topology, the graph
-of yolov2-voc.cfg: four stacks, Darknet's reorg and its gradient, a last layer without batch statistics.
+of yolov2-voc.cfg: four stacks, Darknet's reorg and its gradient, a last layer without batch statistics -- and, with
+topology="tiny", of the "tiny" topology, the graph of tiny-yolo-voc.cfg: two stacks, Darknet's stride-1 pool between them
+(engine.max_pool_2x2_s1), no passthrough, two narrow layers that run zero-padded.
 """
 import collections
 
@@ -49,7 +51,29 @@ def yolov2_darknet_specs(num_class=20, num_anchors=5, width_div=1):
     return a, b, r, c
 
 
-TOPOLOGIES = ("paper", "darknet")
+# tiny-yolo-voc.cfg (yolov2-tiny-voc.cfg): the anchors in 13x13 cell units, written down from memory of the cfg -- no
+# file was at hand to confirm them ("Tiny YOLOv2")
+ANCHORS_TINY_VOC = ((1.08, 1.19), (3.42, 4.41), (6.63, 11.38), (9.42, 5.11), (16.62, 10.52))
+TINY_WIDTHS = (16, 32, 64, 128, 256, 512, 1024, 1024)    # the filters of its eight conv-BN-leaky layers, in the file
+TINY_NARROW = ((0, 16),)         # (stem layer, filters in the file): the stack runs it 32 wide, the rest exactly zero
+
+
+def yolov2_tiny_specs(num_class=20, num_anchors=5, width_div=1):
+    """the two stacks of tiny-yolo-voc.cfg: six 3x3 layers with 2x2 / stride-2 pools behind the first five (Darknet's
+    stride-1 pool behind the sixth runs between the stacks: engine.max_pool_2x2_s1), then 3x3, 3x3 and the 1x1 output
+    layer.  The file's first two layers are 3 -> 16 and 16 -> 32; the stack's first layer is 3 -> 32 and inner input
+    widths are multiples of 32, so they run as 3 -> 32 and 32 -> 32 with filters 16 .. 31 of the first and input
+    channels 16 .. 31 of the second exactly zero (TINY_NARROW) -- the same function.  width_div divides the other widths
+    only, so a narrow test model still exercises the padding."""
+    div = (lambda ch: max(32, ch // width_div // 32 * 32)) if width_div > 1 else (lambda ch: ch)
+    w = [32, 32] + [div(ch) for ch in TINY_WIDTHS[2:]]
+    a = [(3, 3 if l == 0 else w[l - 1], w[l], 1 if l < 5 else 0) for l in range(6)]
+    b = [(3, w[5], w[6], 0), (3, w[6], w[7], 0), (1, w[7], num_anchors * (5 + num_class), 0)]
+    return a, b
+
+
+TOPOLOGIES = ("paper", "darknet", "tiny")
+DARKNET_FILE_TOPOLOGIES = ("darknet", "tiny")            # the graphs a Darknet `.weights` file can hold
 DARKNET_1X1_CORE_LAYER = 3       # Darknet-19's fourth convolution: 1x1 in the file, 3x3 with a centre tap in this graph
 
 
@@ -63,23 +87,38 @@ def _paper_concat(fine, coarse, out=None):
 # (None: the contexts' own 1e-3).  head_statistics: whether the head trains on batch statistics.  darknet_input: uint8
 # batches go through engine.u8_to_darknet_input into a buffer kept per size, and so does the concat; otherwise the first
 # layer converts and torch allocates.  concat / concat_backward: the passthrough pair; cf_stack: the stack whose output
-# width that pair reads as `cf`.
+# width that pair reads as `cf` -- all three None on a graph without a passthrough, whose second stack is the head.
+# pool / pool_backward: the op between the first and the second stack and its gradient.  centre_tap: the stem layers that
+# are 1x1 in a `.weights` file and run 3x3 on their centre tap; narrow: (stem layer, filters in the file) of the layers
+# that run wider than the file holds them, the padded filters and the next layer's padded input channels exactly zero.
+# anchors: the published anchors of the graph.
 _Topology = collections.namedtuple("_Topology", "name specs heights bn_eps slopes train_options head_statistics "
-                                                "darknet_input concat concat_backward cf_stack")
+                                                "darknet_input concat concat_backward cf_stack pool pool_backward "
+                                                "centre_tap narrow anchors")
 
 _BESSEL = {"bessel": True}       # moving variances on the n - 1 estimate, as Darknet keeps them
 _TOPOLOGY = {
     # (stem, 13x13 stack, head): the graph of the module docstring
     "paper": _Topology(name="paper", specs=yolov2_specs, heights=(32, 1, 1), bn_eps=None, slopes=(None, None, None),
                        train_options=({}, {}, {}), head_statistics=True, darknet_input=False, concat=_paper_concat,
-                       concat_backward=E.passthrough_concat_backward, cf_stack=0),
+                       concat_backward=E.passthrough_concat_backward, cf_stack=0, pool=E.max_pool_2x2,
+                       pool_backward=E.max_pool_2x2_backward, centre_tap=(), narrow=(), anchors=ANCHORS_VOC),
     # (stem, 13x13 stack, route, head): the order of the convolutions in a `.weights` file.  The head trains its 3x3 layer
     # on batch statistics and runs the last, linear layer on its moving ones (core_layers 1)
     "darknet": _Topology(name="darknet", specs=yolov2_darknet_specs, heights=(32, 1, 2, 1), bn_eps=DARKNET_BN_EPS,
                          slopes=(None, None, None, [0.1, 1.0]),
                          train_options=(_BESSEL, _BESSEL, _BESSEL, dict(_BESSEL, core_layers=1)), head_statistics=False,
                          darknet_input=True, concat=E.passthrough_concat_darknet,
-                         concat_backward=E.passthrough_concat_darknet_backward, cf_stack=2),
+                         concat_backward=E.passthrough_concat_darknet_backward, cf_stack=2, pool=E.max_pool_2x2,
+                         pool_backward=E.max_pool_2x2_backward, centre_tap=(DARKNET_1X1_CORE_LAYER,), narrow=(),
+                         anchors=ANCHORS_VOC),
+    # (stem, head): tiny-yolo-voc.cfg.  No passthrough; Darknet's stride-1 pool between the stacks; the "darknet" head with
+    # one more core layer
+    "tiny": _Topology(name="tiny", specs=yolov2_tiny_specs, heights=(32, 1), bn_eps=DARKNET_BN_EPS,
+                      slopes=(None, [0.1, 0.1, 1.0]), train_options=(_BESSEL, dict(_BESSEL, core_layers=2)),
+                      head_statistics=False, darknet_input=True, concat=None, concat_backward=None, cf_stack=None,
+                      pool=E.max_pool_2x2_s1, pool_backward=E.max_pool_2x2_s1_backward, centre_tap=(),
+                      narrow=TINY_NARROW, anchors=ANCHORS_TINY_VOC),
 }
 
 
@@ -112,21 +151,24 @@ def _make_buffers(topo, nets, batch, size):
         return None, None
     S, dev = size // 32, nets[0].device
     return (torch.empty((batch, size, size, 3), dtype=torch.float32, device=dev),
-            torch.empty((batch, S, S, nets[-1].spec[0][1]), dtype=torch.float32, device=dev))
+            torch.empty((batch, S, S, nets[-1].spec[0][1]), dtype=torch.float32, device=dev) if topo.concat else None)
 
 
 def _forward(topo, nets, buffers, images, training, update_moving, out=None):
-    """the forward pass of either graph -> (flat head output, fine map).  nets = (stem, 13x13 stack, [route,] head)"""
+    """the forward pass of every graph -> (flat head output, fine map).  nets = (stem, 13x13 stack, [route,] head), or
+    (stem, head) on a graph without a passthrough"""
     x_buf, cat_buf = buffers
     if topo.darknet_input and images.dtype == torch.uint8:
         images = E.u8_to_darknet_input(images, out=x_buf)                   # BGR pixels -> RGB in [0, 1]
-    stem, deep, head = nets[0], nets[1], nets[-1]
+    stem, head = nets[0], nets[-1]
     fine = stem.forward(images, training, training, update_moving=update_moving)                  # [N,2S,2S,512]
-    coarse = deep.forward(E.max_pool_2x2(fine), training, training, update_moving=update_moving)  # [N,S,S,1024]
-    passed = fine
-    for route in nets[2:-1]:                                                # "darknet": the 1x1 route, [N,2S,2S,64]
-        passed = route.forward(passed, training, training, update_moving=update_moving)
-    cat = topo.concat(passed, coarse, out=cat_buf)                          # [N,S,S,4*cf+1024], reorganised map first
+    cat = topo.pool(fine)                                                   # "tiny": [N,S,S,512], the head's input
+    if topo.concat is not None:
+        coarse = nets[1].forward(cat, training, training, update_moving=update_moving)            # [N,S,S,1024]
+        passed = fine
+        for route in nets[2:-1]:                                            # "darknet": the 1x1 route, [N,2S,2S,64]
+            passed = route.forward(passed, training, training, update_moving=update_moving)
+        cat = topo.concat(passed, coarse, out=cat_buf)                      # [N,S,S,4*cf+1024], reorganised map first
     out = head.forward(cat, training, training and topo.head_statistics, out=out, update_moving=update_moving)
     return out, fine                                                        # [N,S,S,B*(5+C)]
 
@@ -137,7 +179,9 @@ class YOLOv2Detector:
     route convolution 512 -> 64 on the fine map; Darknet's reorg (engine.passthrough_concat_darknet) with the
     reorganised map in FRONT of the 13x13 path; a last layer without activation; batch-norm epsilon 1e-6; and the input
     RGB in [0, 1]: uint8 BGR batches are converted by engine.u8_to_darknet_input, float input is taken as that already.
-    bn_eps: the batch-norm epsilon of every stack (None: the context's default 1e-3, or 1e-6 on "darknet")."""
+    "tiny": the graph of tiny-yolo-voc.cfg, Darknet's second VOC model (yolov2_tiny_specs; anchors ANCHORS_TINY_VOC) --
+    two stacks with Darknet's stride-1 pool between them, no passthrough, the input, epsilon and last layer of "darknet".
+    bn_eps: the batch-norm epsilon of every stack (None: the context's default 1e-3, or 1e-6 on "darknet" / "tiny")."""
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", width_div=1, topology="paper", bn_eps=None):
@@ -147,12 +191,14 @@ class YOLOv2Detector:
         self.bn_eps = self._topo.bn_eps if bn_eps is None else float(bn_eps)
         self.batch, self.size, self.S = batch, image_size, image_size // 32
         self.num_class, self.anchors = num_class, np.asarray(anchors, np.float32).reshape(-1, 2)
-        self.B = len(self.anchors)
+        self.B, self.width_div = len(self.anchors), width_div
         self.iteration = 0                                   # of the snapshot last restored (net_utils)
         self.anchors_dev = torch.as_tensor(self.anchors).to(device).contiguous()
         specs = self._topo.specs(num_class, self.B, width_div)
         self._stacks = _build_stacks(self._topo, specs, batch, image_size, dtype, device, self.bn_eps, False, seed)
-        self.stem, self.deep, self.head = self._stacks[0], self._stacks[1], self._stacks[-1]
+        self.stem, self.head = self._stacks[0], self._stacks[-1]
+        if len(self._stacks) > 2:
+            self.deep = self._stacks[1]
         if len(self._stacks) == 4:
             self.route = self._stacks[2]
         self._buffers = _make_buffers(self._topo, self._stacks, batch, image_size)
@@ -197,7 +243,7 @@ class YOLOv2Detector:
         0..3 (engine.detect_anchor_classes_batch_darknet).  It needs the "darknet" topology, whose float input is RGB in
         [0, 1], and letterbox=True"""
         if protocol == "darknet":
-            if self.topology != "darknet":
+            if not self._topo.darknet_input:
                 raise ValueError("protocol='darknet' needs the \"darknet\" topology: the input of the %r topology is BGR "
                                  "in [-1, 1), not Darknet's RGB in [0, 1]" % (self.topology,))
             if not letterbox:
@@ -229,7 +275,7 @@ class _Trainer:
         self._GradReducer = GradReducer
         self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
         self.anchors = np.asarray(anchors, np.float32)
-        self.B = len(self.anchors)
+        self.B, self.width_div = len(self.anchors), width_div
         self.scales = scales
         # box-list labels only (step(images, truth=..., ntruth=...)): Darknet's (2 - w h) coord weight, and its anchor-prior
         # term while fewer than prior_images images have been seen ((iteration - 1) * batch, counted over resumed runs)
@@ -237,7 +283,8 @@ class _Trainer:
         self.iteration = 0                                   # train steps taken, over resumed runs (net_utils snapshots)
         self.solver = solver.validate() if solver is not None else None
         self.specs = tuple(self._topo.specs(num_class, self.B, width_div))
-        self.cf = self.specs[self._topo.cf_stack][-1][2]     # the width the passthrough reorganises
+        # the width the passthrough reorganises (None: a graph without one)
+        self.cf = self.specs[self._topo.cf_stack][-1][2] if self._topo.cf_stack is not None else None
         self.ctx, self.reducers, self._buffers = {}, {}, {}
         self.opts = None
         self.default_size = image_size
@@ -315,15 +362,18 @@ class _Trainer:
         dcat = nets[-1].backward_input(dnet.view(self.batch, S, S, -1))
         if dist is not None:
             red[-1].reduce_all_async()
-        dfine, dcoarse = self._topo.concat_backward(dcat, self.cf)
-        dpooled = nets[1].backward_input(dcoarse)
-        if dist is not None:
-            red[1].reduce_all_async()
-        for i in range(2, len(nets) - 1):                    # "darknet": back through the route, to the fine map
-            dfine = nets[i].backward_input(dfine)
+        if self._topo.concat_backward is None:               # no passthrough: the pool's gradient is the fine map's
+            dfine = self._topo.pool_backward(fine, dcat)
+        else:
+            dfine, dcoarse = self._topo.concat_backward(dcat, self.cf)
+            dpooled = nets[1].backward_input(dcoarse)
             if dist is not None:
-                red[i].reduce_all_async()
-        E.accumulate(dfine, E.max_pool_2x2_backward(fine, dpooled))
+                red[1].reduce_all_async()
+            for i in range(2, len(nets) - 1):                # "darknet": back through the route, to the fine map
+                dfine = nets[i].backward_input(dfine)
+                if dist is not None:
+                    red[i].reduce_all_async()
+            E.accumulate(dfine, self._topo.pool_backward(fine, dpooled))
         if self.keeps_backward:
             self.last_dcat, self.last_dfine = dcat, dfine
         world = red[0].backward_and_reduce(dfine)
@@ -397,6 +447,10 @@ class YOLOv2Trainer(_Trainer):
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
                  solver=None, bn_eps=None, topology="paper"):
+        if topology == "tiny":
+            raise NotImplementedError("YOLOv2Trainer trains the paper topology only: the \"tiny\" graph needs Darknet's "
+                                      "stride-1 pool and its gradient, zero-padded narrow layers and a last layer without "
+                                      "batch statistics -- YOLOv2DarknetTrainer(topology=\"tiny\") has them")
         if topology != "paper":
             _topology(topology)
             raise NotImplementedError("YOLOv2Trainer trains the paper topology only: the %r graph needs the gradient of "
@@ -421,7 +475,14 @@ class YOLOv2DarknetTrainer(_Trainer):
     identity moving statistics the importer writes and its gamma / beta gradients are zeroed every step, so those four
     arrays never move and the export folds exactly 1.  The eight off-centre taps of core layer 3 (Darknet's 1x1) get a
     zero gradient every step too: they stay exactly zero and the model stays writable.
-    backward() leaves the gradients at the concat and at the fine map in last_dcat / last_dfine (tests read them)."""
+    backward() leaves the gradients at the concat and at the fine map in last_dcat / last_dfine (tests read them).
+
+    topology="tiny": the graph of tiny-yolo-voc.cfg (YOLOv2Detector(topology="tiny"); pass anchors=ANCHORS_TINY_VOC for
+    the published ones) under the same contract -- TWO stacks, Darknet's stride-1 pool and its gradient between them, a
+    head with core_layers = 2.  Its first layer's filters 16 .. 31 and its second layer's input channels 16 .. 31 are the
+    zero padding of yolov2_tiny_specs: a fresh model starts with them zero and their gradients (W, b, gamma, beta of the
+    padded filters, W of the padded input channels) are zeroed every step, so they stay bit-zero under both optimizers,
+    weight decay included, and the model stays writable."""
 
     topology = "darknet"
     keeps_backward = True
@@ -429,21 +490,29 @@ class YOLOv2DarknetTrainer(_Trainer):
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
                  solver=None, bn_eps=None, topology="darknet"):
-        if topology != "darknet":
-            raise ValueError("YOLOv2DarknetTrainer trains the \"darknet\" topology; topology %r is YOLOv2Trainer's" %
-                             (topology,))
+        if topology not in DARKNET_FILE_TOPOLOGIES:
+            raise ValueError("YOLOv2DarknetTrainer trains the \"darknet\" and \"tiny\" topologies; topology %r is "
+                             "YOLOv2Trainer's" % (topology,))
         _Trainer.__init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
                           area_weight, prior_images, prior_scale, solver, bn_eps)
 
     def _init_form(self, nets):
-        """a fresh model in the form a `.weights` file can hold: the 1x1 layer's off-centre taps zero, the last layer's
-        batch norm the importer's identity (utils/darknet_weights.to_layer_params)"""
+        """a fresh model in the form a `.weights` file can hold: the 1x1 layers' off-centre taps zero, the narrow layers'
+        padding zero (utils/darknet_weights.pad_layer_params), the last layer's batch norm the importer's identity
+        (utils/darknet_weights.to_layer_params)"""
+        from ..utils import darknet_weights as dkw
         stem, head = nets[0], nets[-1]
         params = stem.export_params()
-        W = params[DARKNET_1X1_CORE_LAYER]["W"]
-        centre = W[1, 1].copy()
-        W[...] = 0
-        W[1, 1] = centre
+        for l in self._topo.centre_tap:
+            W = params[l]["W"]
+            centre = W[1, 1].copy()
+            W[...] = 0
+            W[1, 1] = centre
+        for l, n_file in self._topo.narrow:
+            k, ci, co, _pool = stem.spec[l]
+            params[l] = dkw.pad_layer_params(dkw.strip_layer_params(params[l], ci, n_file, check=False), ci, co)
+            co2 = stem.spec[l + 1][2]
+            params[l + 1] = dkw.pad_layer_params(dkw.strip_layer_params(params[l + 1], n_file, co2, check=False), co, co2)
         stem.load_params(params)
         params = head.export_params()
         n = params[-1]["b"].size
@@ -453,13 +522,21 @@ class YOLOv2DarknetTrainer(_Trainer):
         head.load_params(params)
 
     def _mask_gradients(self, nets):
-        """after the all-reduce, before the optimizers: no gradient for the eight off-centre taps of Darknet's 1x1 layer
-        nor for the last layer's gamma / beta"""
+        """after the all-reduce, before the optimizers: no gradient for the eight off-centre taps of Darknet's 1x1 layers,
+        for the zero padding of the narrow layers nor for the last layer's gamma / beta"""
         stem, head = nets[0], nets[-1]
-        gW = stem.layer_views(DARKNET_1X1_CORE_LAYER, grads=True)["W"]
-        taps = gW.view(9, -1)
-        E.zero_(taps[:4])
-        E.zero_(taps[5:])
+        for l in self._topo.centre_tap:
+            taps = stem.layer_views(l, grads=True)["W"].view(9, -1)
+            E.zero_(taps[:4])
+            E.zero_(taps[5:])
+        for l, n_file in self._topo.narrow:
+            g = stem.layer_views(l, grads=True)
+            for row in g["W"].view(-1, g["W"].shape[3]):                  # [k k ci][co]: the padded filters of every row
+                E.zero_(row[n_file:])
+            for key in ("b", "gamma", "beta"):
+                E.zero_(g[key][n_file:])
+            for tap in stem.layer_views(l + 1, grads=True)["W"].flatten(0, 1):     # [k k][ci][co]: the padded inputs
+                E.zero_(tap[n_file:])
         g = head.layer_views(head.num_layers - 1, grads=True)
         E.zero_(g["gamma"])
         E.zero_(g["beta"])
