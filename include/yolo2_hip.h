@@ -312,6 +312,17 @@ size_t y2_yolov2_loss_boxes_workspace_bytes(int batch, int S, int B);
 int y2_yolov2_loss_boxes(const float* net, const float* truth, const int* ntruth, const float* anchors, int batch, int S,
                          int B, int num_class, int max_boxes, float image_size, const float* scales, float* loss,
                          float* dnet, void* workspace, void* stream);
+/* Region statistics of the same inputs (specification: utils/region_loss.py region_stats_boxes): the numbers of Darknet's
+ * region-layer log line.  Every listed truth counts, owner of its slot or not (Darknet's layer has no ownership rule);
+ * per truth the prediction at its cell and best-fitting anchor is decoded.  stats[6] in device memory = mean IoU, mean
+ * softmax probability of the true class (over the truths whose class lies in [0, num_class)), mean sig(to) at the truths,
+ * mean sig(to) over all batch * S * S * B slots, share of truths with IoU > 0.5, truth count.  A mean over nothing is 0.
+ * One launch (a workgroup per image) + the finalize; no atomics: the result does not vary from run to run.  Argument
+ * errors are the loss entry's, and B <= 8. */
+size_t y2_yolov2_region_stats_workspace_bytes(int batch);
+int y2_yolov2_region_stats(const float* net, const float* truth, const int* ntruth, const float* anchors, int batch, int S,
+                           int B, int num_class, int max_boxes, float image_size, float* stats, void* workspace,
+                           void* stream);
 
 /* ---- ResNet-50 backbone swap (src/yolo2_nets/tf_resnet.py:12-32, src/pascal/pascal_train_resnet.py:37-50):
  *      graph-level operators on fp32 NHWC tensors that the conv-BN-leaky stacks do not have.  The 1x1 / 3x3

@@ -527,6 +527,109 @@ __global__ __launch_bounds__(256) void yolov2_loss_boxes_finalize_kernel(const f
     }
 }
 
+// ---------------------------------------------------------------------------
+// Region statistics (specification: utils/region_loss.py region_stats_boxes): the numbers of Darknet's region-layer log
+// line, from the tensors the box-list loss reads.  One workgroup of 256 per image.  Pass 1: the lanes walk the image's
+// S*S*B slots and add sig(to).  Pass 2: the lanes walk the image's truths; each derives its truth's cell and
+// best-fitting anchor exactly as the loss does, decodes the prediction there and adds the IoU, the objectness, the class
+// probability (valid class only) and the counts.  EVERY listed truth counts, owner of its slot or not.  The four float
+// sums and three counts go through one LDS tree per image into partial[n][8]; the finalize adds the images in a fixed
+// order (lane (j, k): component k of images j, j + 32, ... ascending, then a tree), so two runs give the same bits.
+// ---------------------------------------------------------------------------
+struct V2RegionStatsArgs {
+    const float* net;      // [N][S][S][B][5+C]
+    const float* truth;    // [N][T][5]
+    const int* ntruth;     // [N]
+    const float* anchors;  // [B][2] cell units
+    int* partial;          // [N][8]: float bits of sum iou, sum class, sum obj, sum sig(to); int recall, count, classed; 0
+    int N, S, B, C, T;
+    float image_size;
+};
+
+// components 0..3 are float bit patterns, 4..7 integers
+__device__ __forceinline__ int v2_stats_add(int k, int a, int b) {
+    return k < 4 ? __float_as_int(__int_as_float(a) + __int_as_float(b)) : a + b;
+}
+
+__global__ __launch_bounds__(256) void yolov2_region_stats_kernel(V2RegionStatsArgs a) {
+    __shared__ int red[8][256];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int cells = a.S * a.S, D = 5 + a.C, slots = cells * a.B;
+    const float fs = (float)a.S;
+    const int nt = min(max(a.ntruth[n], 0), a.T);
+    const float* base = a.net + (size_t)n * slots * D;
+    float s_all = 0.f;
+    for (int p = tid; p < slots; p += 256) s_all += v2_sigmoid(base[(size_t)p * D + 4]);
+    float s_iou = 0.f, s_cls = 0.f, s_obj = 0.f;
+    int recall = 0, count = 0, classed = 0;
+    for (int k = tid; k < nt; k += 256) {
+        const float* tk = a.truth + ((size_t)n * a.T + k) * 5;
+        const float gx = tk[0] / a.image_size * fs, gy = tk[1] / a.image_size * fs;
+        const float gw = tk[2] / a.image_size * fs, gh = tk[3] / a.image_size * fs;
+        // the cell of the truth, cut into the grid as the loss cuts it: every index below is in range
+        const int q = (int)fminf(fmaxf(gx, 0.0f), fs - 1.0f), r = (int)fminf(fmaxf(gy, 0.0f), fs - 1.0f);
+        int bs = 0;
+        float bi = -1.0f;
+        for (int j = 0; j < a.B; ++j) {   // the anchor whose shape fits best, first one on ties
+            const float kw = a.anchors[2 * j], kh = a.anchors[2 * j + 1];
+            const float inter = fminf(gw, kw) * fminf(gh, kh);
+            const float si = inter / (gw * gh + kw * kh - inter);
+            if (si > bi) { bi = si; bs = j; }
+        }
+        const float* t = base + ((size_t)(r * a.S + q) * a.B + bs) * D;
+        const float px = v2_sigmoid(t[0]) + (float)q, py = v2_sigmoid(t[1]) + (float)r;
+        const float pw = a.anchors[2 * bs] * expf(t[2]), ph = a.anchors[2 * bs + 1] * expf(t[3]);
+        const float iou = v2_iou(px, py, pw, ph, gx, gy, gw, gh);
+        s_iou += iou;
+        s_obj += v2_sigmoid(t[4]);
+        recall += iou > 0.5f ? 1 : 0;
+        count += 1;
+        const int c = (int)tk[4];
+        if (c >= 0 && c < a.C) {
+            float m = t[5];
+            for (int j = 1; j < a.C; ++j) m = fmaxf(m, t[5 + j]);
+            float se = 0.f;
+            for (int j = 0; j < a.C; ++j) se += expf(t[5 + j] - m);
+            s_cls += expf(t[5 + c] - m) / se;
+            classed += 1;
+        }
+    }
+    red[0][tid] = __float_as_int(s_iou); red[1][tid] = __float_as_int(s_cls); red[2][tid] = __float_as_int(s_obj);
+    red[3][tid] = __float_as_int(s_all); red[4][tid] = recall; red[5][tid] = count; red[6][tid] = classed; red[7][tid] = 0;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int k = 0; k < 8; ++k) red[k][tid] = v2_stats_add(k, red[k][tid], red[k][tid + s]);
+        __syncthreads();
+    }
+    if (tid < 8) a.partial[(size_t)n * 8 + tid] = red[tid][0];
+}
+
+// stats[6] = mean IoU, mean class probability, mean objectness at the truths, mean sig(to) over every slot, recall at
+// IoU 0.5, the truth count.  A mean over nothing is 0 (Darknet prints NaN there)
+__global__ __launch_bounds__(256) void yolov2_region_stats_finalize_kernel(const int* partial, float* stats, int N,
+                                                                           float slots) {
+    __shared__ int red[256];
+    const int tid = threadIdx.x, k = tid & 7;
+    int p = 0;                                           // the bit pattern of 0.0f too
+    for (int j = tid >> 3; j < N; j += 32) p = v2_stats_add(k, p, partial[(size_t)j * 8 + k]);
+    red[tid] = p;
+    __syncthreads();
+    for (int s = 128; s >= 8; s >>= 1) {
+        if (tid < s) red[tid] = v2_stats_add(k, red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float count = (float)red[5], classed = (float)red[6];
+        stats[0] = red[5] > 0 ? __int_as_float(red[0]) / count : 0.f;
+        stats[1] = red[6] > 0 ? __int_as_float(red[1]) / classed : 0.f;
+        stats[2] = red[5] > 0 ? __int_as_float(red[2]) / count : 0.f;
+        stats[3] = __int_as_float(red[3]) / slots;
+        stats[4] = red[5] > 0 ? (float)red[4] / count : 0.f;
+        stats[5] = count;
+    }
+}
+
 extern "C" {
 
 int y2_maxpool2x2(const float* x, float* y, int N, int H, int W, int C, void* stream) {
@@ -709,6 +812,35 @@ int y2_yolov2_loss_boxes(const float* net, const float* truth, const int* ntruth
     EXTCHK(hipGetLastError());
     hipLaunchKernelGGL(yolov2_loss_boxes_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a.partial, loss,
                        blocks * batch, batch);
+    EXTCHK(hipGetLastError());
+    return Y2_OK;
+}
+
+size_t y2_yolov2_region_stats_workspace_bytes(int batch) {
+    if (batch < 1 || batch > 65535) return 0;
+    return (size_t)batch * 8 * sizeof(int) + 256;
+}
+
+int y2_yolov2_region_stats(const float* net, const float* truth, const int* ntruth, const float* anchors, int batch, int S,
+                           int B, int num_class, int max_boxes, float image_size, float* stats, void* workspace,
+                           void* stream) {
+    if (!net || !truth || !ntruth || !anchors || !stats || !workspace)
+        return fail(Y2_ERR_ARG, "y2_yolov2_region_stats: null pointer");
+    if (batch < 1 || batch > 65535 || S < 1 || B < 1 || B > 8 || num_class < 1 || !(image_size > 0.0f))
+        return fail(Y2_ERR_ARG, "y2_yolov2_region_stats: batch = %d, S = %d, B = %d (1..8), num_class = %d, image_size = %g",
+                    batch, S, B, num_class, (double)image_size);
+    if ((long long)S * S * B > Y2_LOSS_BOXES_MAX_SLOTS)
+        return fail(Y2_ERR_ARG, "y2_yolov2_region_stats: S * S * B = %lld beyond Y2_LOSS_BOXES_MAX_SLOTS = %d",
+                    (long long)S * S * B, Y2_LOSS_BOXES_MAX_SLOTS);
+    if (max_boxes < 1 || max_boxes > Y2_MAX_BOXES)
+        return fail(Y2_ERR_ARG, "y2_yolov2_region_stats: max_boxes = %d outside 1..%d", max_boxes, Y2_MAX_BOXES);
+    V2RegionStatsArgs a{};
+    a.net = net; a.truth = truth; a.ntruth = ntruth; a.anchors = anchors; a.partial = (int*)workspace;
+    a.N = batch; a.S = S; a.B = B; a.C = num_class; a.T = max_boxes; a.image_size = image_size;
+    hipLaunchKernelGGL(yolov2_region_stats_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, a);
+    EXTCHK(hipGetLastError());
+    hipLaunchKernelGGL(yolov2_region_stats_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a.partial, stats,
+                       batch, (float)batch * (float)S * (float)S * (float)B);
     EXTCHK(hipGetLastError());
     return Y2_OK;
 }

@@ -1060,6 +1060,28 @@ def yolov2_loss_boxes(net, truth, ntruth, anchors, image_size, need_grad=True, s
     return loss, dnet
 
 
+def yolov2_region_stats(net, truth, ntruth, anchors, image_size, out=None):
+    """the numbers of Darknet's region-layer log line (utils/region_loss.py region_stats_boxes) from the tensors
+    yolov2_loss_boxes reads: net [N,S,S,B,5+C], truth [N,T,5], ntruth [N], anchors [B,2] (anything numpy reads, or a
+    float32 device tensor) -> stats float32 [6] on the device (in `out` if
+    given) = mean IoU, mean class probability, mean objectness at the truths, mean objectness over every slot, recall at
+    IoU 0.5, truth count.  No host synchronisation; the result does not vary from run to run"""
+    lib = _lib.load()
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, s, _, b, d = net.shape
+    assert truth.is_cuda and truth.dtype == torch.float32 and truth.is_contiguous(), (truth.dtype, truth.device)
+    assert truth.dim() == 3 and truth.shape[0] == n and truth.shape[2] == 5, truth.shape
+    assert ntruth.is_cuda and ntruth.dtype == torch.int32 and ntruth.is_contiguous() and tuple(ntruth.shape) == (n,)
+    an = _anchors(anchors, b, net.device)                 # a device tensor is taken as it is: no copy per call
+    if out is None:
+        out = torch.empty(6, dtype=torch.float32, device=net.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 6, (out.dtype, out.shape)
+    ws = torch.empty(lib.y2_yolov2_region_stats_workspace_bytes(n), dtype=torch.uint8, device=net.device)
+    check(lib.y2_yolov2_region_stats(_ptr(net), _ptr(truth), _ptr(ntruth), _ptr(an), n, s, b, d - 5, int(truth.shape[1]),
+                                     float(image_size), _ptr(out), _ptr(ws), _stream()))
+    return out
+
+
 def nms(boxes, scores, classes=None, iou_thresh=0.5, score_thresh=0.0, max_out=100, class_aware=False):
     """boxes [N,K,4], scores [N,K] (, classes [N,K] int32) -> keep [N,max_out] int32 (-1 padded), count [N]"""
     lib = _lib.load()

@@ -1,5 +1,6 @@
 """The YOLOv2 anchor detector on plain image files (not in the reference, whose detect script is the grid model's):
     python -m tensorflow_yolo2_amd.pascal.pascal_detect_yolov2 [--weights FILE | --ckpt-dir DIR | --darknet-weights FILE]
+        [--cfg FILE] [--names FILE]
         --images A.jpg B.jpg ...
         [--size 416] [--thresh 0.24] [--nms 0.45] [--stretch] [--protocol repo|darknet] [--out FILE]
 The files are decoded once into ONE device pool (img_dataset/device_images.py); per batch, DeviceImages.batch makes the
@@ -16,7 +17,10 @@ rows class by class, each class in descending score.  It needs --darknet-weights
 --fill.  --darknet-weights FILE runs a file Darknet wrote for yolov2-voc.cfg instead: the "darknet" topology of
 yolo2_nets/yolov2.py with the published VOC anchors (net_utils.load_darknet_weights); every other flag works as before.
 A file of tiny-yolo-voc.cfg is taken the same way: its float count says so (net_utils.darknet_file_topology), and the
-"tiny" topology is built with that graph's published anchors."""
+"tiny" topology is built with that graph's published anchors.  --cfg FILE names the Darknet cfg that goes with the
+`.weights` file instead: the graph, the class count, the anchors and the widths are the file's (utils/darknet_cfg.py;
+YOLOv2Detector.from_cfg), so the COCO models load -- `--cfg yolov2.cfg --darknet-weights yolov2.weights --names coco.names`
+-- and --names FILE writes each detection under its class name (one per line; the count must be the model's)."""
 import argparse
 import sys
 
@@ -42,6 +46,8 @@ def parse_args(argv=None):
     ap.add_argument("--out", default=None, help="write the lines to this file as well")
     model_flags.add_test_flags(ap)
     args = ap.parse_args(argv)
+    args.error = ap.error
+    model_flags.resolve_cfg(ap, args)
     model_flags.check_size(ap, args)
     if args.batch is None:
         args.batch = min(len(args.images), 32)
@@ -52,7 +58,7 @@ def parse_args(argv=None):
             ap.error("--protocol darknet is letterboxed: not with --stretch")
         if args.fill is not None:
             ap.error("--fill is not read with --protocol darknet: Darknet's bars are 0.5")
-        if not args.darknet_weights:
+        if not (args.darknet_weights or args.cfg):
             ap.error("--protocol darknet needs the darknet topology (--darknet-weights FILE): the paper topology's input "
                      "is BGR in [-1, 1)")
     if args.fill is None:
@@ -70,6 +76,7 @@ def main(argv=None):
     snapshot, anchors, num_class, bn_eps = model_flags.find_snapshot(args, len(pascal_voc.CLASSES))
     detector, restored = model_flags.build_detector(args, snapshot, anchors, num_class, bn_eps)
     names = pascal_voc.CLASSES if num_class == len(pascal_voc.CLASSES) else [str(c) for c in range(num_class)]
+    names = model_flags.class_names(args.error, args, num_class, names)
     n, entries = args.batch, len(pool.entries)
     grids = []
     rows = []

@@ -25,7 +25,10 @@ which of the two graphs is built (net_utils.darknet_file_topology):
 and --protocol darknet scores it as Darknet's `valid` would (it implies the two switches): the float letterbox with bars
 of 0.5 in one launch from the pool (y2_letterbox_darknet_batch), Darknet's float un-map, float NMS and float corners
 (y2_detect_anchor_classes_batch_dk), the matcher on those (y2_voc_match_batch_f), and "%f" results files:
-    pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --protocol darknet"""
+    pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --protocol darknet
+--cfg FILE names the Darknet cfg that goes with --darknet-weights: graph, class count, anchors and widths are the file's
+(YOLOv2Detector.from_cfg); its class count must be the devkit's, since the evaluation stays VOC's.  --names FILE names
+the classes of the --results-dir files."""
 import argparse
 import sys
 
@@ -67,13 +70,15 @@ def parse_args(argv=None):
     ap.add_argument("--metric", default="07", choices=("07", "10"), help="07: 11-point AP; 10: area under the envelope")
     model_flags.add_test_flags(ap)
     args = ap.parse_args(argv)
+    args.error = ap.error
+    model_flags.resolve_cfg(ap, args)
     model_flags.check_size(ap, args)
     if args.batch < 1 or args.max_out < 1 or args.width_div < 1 or args.max_per_class < 1:
         ap.error("--batch, --max-out, --max-per-class and --width-div must be at least 1")
     if args.protocol == "darknet":
         if args.fill is not None:
             ap.error("--fill is not read with --protocol darknet: Darknet's bars are 0.5")
-        if not args.darknet_weights:
+        if not (args.darknet_weights or args.cfg):
             ap.error("--protocol darknet needs the darknet topology (--darknet-weights FILE): the paper topology's input "
                      "is BGR in [-1, 1)")
         args.per_class = args.letterbox = True
@@ -90,6 +95,10 @@ def main(argv=None):
     from ..img_dataset.device_voc import DeviceVOC
     imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=False)
     snapshot, anchors, num_class, bn_eps = model_flags.find_snapshot(args, imdb.num_class)
+    if args.cfg_record is not None and num_class != imdb.num_class:     # the evaluation is VOC's
+        args.error("--cfg %s has classes=%d, the image set %s has %d classes" %
+                   (args.cfg, num_class, args.image_set, imdb.num_class))
+    names = model_flags.class_names(args.error, args, num_class, pascal_voc.CLASSES[:num_class])
     if num_class != imdb.num_class:
         raise ValueError("snapshot %s: num_class is %d, the image set has %d" % (snapshot, num_class, imdb.num_class))
     detector, restored = model_flags.build_detector(args, snapshot, anchors, num_class, bn_eps)
@@ -106,7 +115,7 @@ def main(argv=None):
     if args.results_dir:
         from ..utils import voc_eval
         result["results_files"] = voc_eval.write_results_files(args.results_dir, args.image_set, imdb.image_index,
-                                                               pascal_voc.CLASSES[:num_class], result["rows"])
+                                                               names, result["rows"])
     result.update(restored=restored, detector=detector, imdb=imdb, topology=detector.topology)
     return result
 

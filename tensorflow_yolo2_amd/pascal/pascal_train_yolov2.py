@@ -1,7 +1,7 @@
 """Train the YOLOv2 anchor detector (yolo2_nets/yolov2.py; not in the reference, whose trainer is the grid model) on VOC:
     python -m tensorflow_yolo2_amd.pascal.pascal_train_yolov2 --devkit data/VOCdevkit --iters 20 \
         [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR | --darknet-backbone FILE]
-        [--topology paper|darknet] [--darknet-weights FILE]
+        [--topology paper|darknet] [--darknet-weights FILE] [--cfg FILE [--single-scale]] [--region-stats]
         [--box-labels [--max-boxes 30] [--area-weight] [--prior-images 12800]]
         [--solver darknet [--lr .001] [--momentum .9] [--decay .0005] [--burn-in 1000] [--power 4]
                           [--policy steps --steps 40000,60000 --scales .1,.1 | --policy poly --max-batches N | --policy constant]]
@@ -44,6 +44,19 @@ published anchors.  --darknet-weights FILE chooses between the two Darknet graph
 (net_utils.darknet_file_topology); a stated --topology that contradicts the file is an argument error, and a --ckpt-dir
 whose .weights files belong to the other Darknet graph fails in the loader, by the float count.
 
+--cfg FILE trains the graph a Darknet cfg describes (utils/darknet_cfg.py; yolov2.YOLOv2DarknetTrainer.from_cfg): the file
+decides the topology, the class count, the anchors and the widths -- the float count of --darknet-weights is checked against
+it, not guessed from -- and implies Darknet's recipe: --augment --box-labels --area-weight --prior-images 12800 --solver
+darknet, --multi-scale where the file says random=1 (--single-scale keeps one size), and the file's jitter, hue, saturation,
+exposure, solver values, width (--size) and batch (--batch).  A flag given on the command line beats the file; the resolved
+recipe is printed once.  It goes with --darknet-weights, --darknet-backbone or a fresh model, and with a --ckpt-dir of
+.weights snapshots; not with --topology paper, --imagenet-ckpt-dir, --anchors or a --ckpt-dir of .npz snapshots.  The image
+set's class count must be the file's.
+
+--region-stats (with --box-labels or --cfg) prints Darknet's region-layer line for the last step beside the 10-iteration
+line: `Region Avg IOU, Class, Obj, No Obj, Avg Recall, count`, computed on the device from the step's head output and its
+box list (engine.yolov2_region_stats; utils/region_loss.py region_stats_boxes).
+
 One process, one GPU."""
 import argparse
 import os
@@ -59,8 +72,8 @@ def parse_args(argv=None):
     from ..trainer import MULTI_SCALE_SIZES
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--batch", type=int, default=24)
-    ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--batch", type=int, default=None, help="24, or the batch of --cfg")
+    ap.add_argument("--size", type=int, default=None, help="416, or the width of --cfg")
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--devkit", required=True, help="VOCdevkit directory (cfg.PASCAL_PATH)")
     ap.add_argument("--image-set", default="trainval")
@@ -69,10 +82,10 @@ def parse_args(argv=None):
     ap.add_argument("--ms-sizes", default=",".join(str(v) for v in MULTI_SCALE_SIZES), help="comma-separated sizes")
     ap.add_argument("--ms-period", type=int, default=10)
     ap.add_argument("--augment", action="store_true", help="random crop / pad window, mirror and HSV distortion")
-    ap.add_argument("--jitter", type=float, default=0.3, help="window edges move by up to this share of the image")
-    ap.add_argument("--hue", type=float, default=0.1, help="hue shift drawn from [-hue, hue] turns")
-    ap.add_argument("--saturation", type=float, default=1.5, help="saturation factor drawn from [1 / s, s]")
-    ap.add_argument("--exposure", type=float, default=1.5, help="exposure factor drawn from [1 / e, e]")
+    ap.add_argument("--jitter", type=float, default=None, help="window edges move by up to this share of the image (0.3)")
+    ap.add_argument("--hue", type=float, default=None, help="hue shift drawn from [-hue, hue] turns (0.1)")
+    ap.add_argument("--saturation", type=float, default=None, help="saturation factor drawn from [1 / s, s] (1.5)")
+    ap.add_argument("--exposure", type=float, default=None, help="exposure factor drawn from [1 / e, e] (1.5)")
     ap.add_argument("--ckpt-dir", default=None, help="directory of train_iter_<i>.npz snapshots: resume from the latest")
     ap.add_argument("--save-every", type=int, default=40000)
     ap.add_argument("--imagenet-ckpt-dir", default=None, help="classifier snapshots to take the backbone from")
@@ -89,12 +102,22 @@ def parse_args(argv=None):
                     help="start from a whole Darknet .weights file (yolov2-voc.weights or tiny-yolo-voc.weights); its float "
                          "count chooses --topology darknet or tiny, and a stated --topology that contradicts the file is "
                          "an error; not with --darknet-backbone or --imagenet-ckpt-dir")
-    ap.add_argument("--anchors", default="voc", choices=("voc", "kmeans"),
+    ap.add_argument("--cfg", default=None,
+                    help="a Darknet .cfg file: it decides the topology, class count, anchors and widths and implies "
+                         "Darknet's recipe (--augment --box-labels --area-weight --prior-images 12800 --solver darknet, "
+                         "multi-scale on random=1, the file's jitter / hue / saturation / exposure / solver values / width "
+                         "/ batch); a flag given on the command line beats the file.  Not with --topology paper, "
+                         "--imagenet-ckpt-dir, --anchors or .npz snapshots")
+    ap.add_argument("--single-scale", action="store_true", help="with --cfg: one input size even where random=1")
+    ap.add_argument("--region-stats", action="store_true",
+                    help="print Darknet's region-layer line (Avg IOU, Class, Obj, No Obj, Avg Recall, count) of the last "
+                         "step every 10 iterations (needs --box-labels or --cfg)")
+    ap.add_argument("--anchors", default=None, choices=("voc", "kmeans"),
                     help="voc: the published VOC anchors; kmeans: cluster the image set's boxes at --size")
     ap.add_argument("--box-labels", action="store_true", help="train on the box list (every object), not the label grid")
     ap.add_argument("--max-boxes", type=int, default=None, help="rows of the box list (default 30; needs --box-labels)")
     ap.add_argument("--area-weight", action="store_true", help="coord terms times 2 - w h (needs --box-labels)")
-    ap.add_argument("--prior-images", type=int, default=0,
+    ap.add_argument("--prior-images", type=int, default=None,
                     help="images during which un-owned predictions are pulled toward their anchors (needs --box-labels)")
     ap.add_argument("--solver", default="adam", choices=("adam", "darknet"),
                     help="adam: tf.train.AdamOptimizer defaults; darknet: momentum SGD + filter decay + rate schedule")
@@ -111,6 +134,7 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     args.error, args.topology_stated = ap.error, args.topology
+    apply_cfg(ap, args)
     if args.size < 32 or args.size % 32:
         ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
     if args.batch < 1 or args.iters < 0 or args.save_every < 1 or args.width_div < 1:
@@ -141,6 +165,8 @@ def parse_args(argv=None):
             ap.error("--ms-period must be at least 1")
     if not args.box_labels and (args.area_weight or args.prior_images or args.max_boxes is not None):
         ap.error("--max-boxes, --area-weight and --prior-images need --box-labels")
+    if args.prior_images is None:
+        args.prior_images = 0
     if args.max_boxes is None:
         args.max_boxes = 30
     if not 1 <= args.max_boxes <= 1024 or args.prior_images < 0:
@@ -152,6 +178,10 @@ def parse_args(argv=None):
     if args.solver == "darknet":
         from ..utils.solver import Solver
         d = Solver()
+        if args.cfg_record is not None:         # the file's values where no flag is given
+            d = args.cfg_record.solver
+            if args.policy == "poly" and args.max_batches is None:
+                args.max_batches = args.cfg_record.max_batches
         try:
             steps = d.steps if args.steps is None else tuple(int(v) for v in args.steps.split(",") if v.strip())
             scales = d.scales if args.scales is None else tuple(float(v) for v in args.scales.split(",") if v.strip())
@@ -175,6 +205,61 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error("--augment: %s" % e)
     return args
+
+
+def apply_cfg(ap, args):
+    """--cfg: read the file (args.cfg_record; None without the flag), refuse what contradicts it, and fill every flag that
+    was not given from it -- then today's defaults, with or without a file"""
+    args.cfg_record = args.cfg_graph = None
+    pick = lambda v, dv: dv if v is None else v
+    if args.single_scale and not args.cfg:
+        ap.error("--single-scale needs --cfg")
+    if args.cfg:
+        from ..utils import darknet_cfg
+        if args.topology == "paper":
+            ap.error("--cfg describes a Darknet graph: not with --topology paper")
+        if args.imagenet_ckpt_dir:
+            ap.error("--cfg describes a Darknet graph: --imagenet-ckpt-dir feeds the paper topology; give --darknet-backbone")
+        if args.anchors is not None:
+            ap.error("--cfg holds the anchors: not with --anchors")
+        if args.width_div != 1:
+            ap.error("--cfg holds the widths: not with --width-div")
+        try:
+            rec = args.cfg_record = darknet_cfg.load(args.cfg)
+            args.cfg_graph = darknet_cfg.compile_graph(rec, 1024 if args.dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH)
+        except (OSError, ValueError) as e:
+            ap.error("--cfg: %s" % e)
+        found = {"chain": "tiny", "passthrough": "darknet"}[args.cfg_graph.shape]
+        if args.topology not in (None, found):
+            ap.error("--topology %s, but --cfg %s describes the %s graph" % (args.topology, args.cfg, found))
+        args.topology = args.topology_stated = found
+        args.augment = args.box_labels = args.area_weight = True
+        args.solver = "darknet"
+        if rec.random and not args.single_scale:
+            args.multi_scale = True
+        args.prior_images = pick(args.prior_images, yolov2.YOLOv2DarknetTrainer.CFG_PRIOR_IMAGES)
+        args.size, args.batch = pick(args.size, rec.size), pick(args.batch, rec.batch)
+        aug = rec.augmentation
+        args.jitter, args.hue = pick(args.jitter, aug.jitter), pick(args.hue, aug.hue)
+        args.saturation, args.exposure = pick(args.saturation, aug.saturation), pick(args.exposure, aug.exposure)
+    args.size, args.batch = pick(args.size, 416), pick(args.batch, 24)
+    args.jitter, args.hue = pick(args.jitter, 0.3), pick(args.hue, 0.1)
+    args.saturation, args.exposure = pick(args.saturation, 1.5), pick(args.exposure, 1.5)
+    args.anchors = pick(args.anchors, "voc")
+    if args.region_stats and not args.box_labels:
+        ap.error("--region-stats reads the box list: it needs --box-labels or --cfg")
+
+
+def print_recipe(args):
+    """the recipe a --cfg run resolved to, once at start: the file's values and what a flag put in their place"""
+    aug = args.augmentation
+    print("cfg {:s}: topology {:s}, {:d} classes, {:d} anchors, size {:d}, batch {:d}, multi-scale {:s}".format(
+        args.cfg, args.topology, args.cfg_record.classes, args.cfg_record.num, args.size, args.batch,
+        "on" if args.multi_scale else "off"))
+    print("cfg recipe: box labels, area weight, prior images {:d}, jitter {:g}, hue {:g}, saturation {:g}, exposure {:g}, "
+          "scales {}".format(args.prior_images, aug.jitter, aug.hue, aug.saturation, aug.exposure,
+                             ", ".join("%s %g" % kv for kv in args.cfg_record.scales)))
+    print("cfg solver: {!r}".format(args.solver_record))
 
 
 SOLVER_FLAGS = ("lr", "momentum", "decay", "burn_in", "power", "policy", "steps", "scales", "max_batches")
@@ -217,13 +302,26 @@ def main(argv=None):
     imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
                      seed=args.seed, augment=args.augmentation, max_boxes=args.max_boxes if args.box_labels else None)
     latest = None
-    if args.darknet_weights:
+    rec = args.cfg_record
+    if rec is not None:
+        if imdb.num_class != rec.classes:
+            args.error("--cfg %s has classes=%d, the image set %s has %d classes" %
+                       (args.cfg, rec.classes, args.image_set, imdb.num_class))
+        print_recipe(args)
+    elif args.darknet_weights:
         args.topology = file_topology(args, imdb.num_class)
     darknet = args.topology in yolov2.DARKNET_FILE_TOPOLOGIES
     if args.ckpt_dir:
         os.makedirs(args.ckpt_dir, exist_ok=True)
-        latest = net_utils.latest_yolov2_snapshot(args.ckpt_dir, args.topology)
-    if latest and not darknet:                # a .weights file carries no anchors: the flags'
+        try:
+            latest = net_utils.latest_yolov2_snapshot(args.ckpt_dir, args.topology)
+        except ValueError as e:
+            if rec is None:
+                raise
+            args.error("--cfg: %s" % e)       # a directory of .npz snapshots
+    if rec is not None:
+        anchors = rec.anchors
+    elif latest and not darknet:              # a .weights file carries no anchors: the flags'
         anchors = net_utils.read_yolov2_meta(latest)[0]
     elif args.anchors == "kmeans":
         from ..utils import anchors as A
@@ -239,10 +337,14 @@ def main(argv=None):
     bn_eps = yolov2.DARKNET_BN_EPS if args.darknet_backbone else None
     if latest and bn_eps is None and not darknet:
         bn_eps = net_utils.read_yolov2_bn_eps(latest)
-    trainer = TRAINERS[args.topology](args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
-                                      seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
-                                      prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps,
-                                      topology=args.topology)
+    if rec is not None:
+        trainer = yolov2.YOLOv2DarknetTrainer.from_cfg(rec, args.batch, first, dtype=args.dtype, seed=args.seed,
+                                                       solver=args.solver_record, prior_images=args.prior_images)
+    else:
+        trainer = TRAINERS[args.topology](args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
+                                          seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
+                                          prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps,
+                                          topology=args.topology)
     last_iter_num = 0
     if latest:
         print('Restorining model snapshots from {:s}'.format(latest))
@@ -267,16 +369,20 @@ def main(argv=None):
     T = Timer()
     T.tic()
     losses, sizes = [], []
+    stats = torch.empty(6, dtype=torch.float32, device="cuda") if args.region_stats else None
+    region_stats = [] if args.region_stats else None
     for i in range(last_iter_num + 1, TOTAL_ITER + 1):
         size = step_size(args, i)
         if args.box_labels:
             image, _grid, truth, ntruth = imdb.get(size)      # three kernels on this stream, no host pixel work
-            loss = trainer.step(image, truth=truth, ntruth=ntruth)
+            loss = trainer.step(image, truth=truth, ntruth=ntruth, stats=stats)
         else:
             image, gt_labels = imdb.get(size)                 # two kernels on this stream, no host pixel work
             loss = trainer.step(image, gt_labels)
         losses.append(loss.cpu().numpy().copy())              # coord, object, noobject, class, total
         sizes.append(size)
+        if stats is not None:
+            region_stats.append(stats.cpu().numpy().copy())    # avg IoU, class, obj, no obj, avg recall, count
         if i % 10 == 0:
             _time = T.toc(average=False)
             rate = ''
@@ -286,12 +392,17 @@ def main(argv=None):
                 rate = ', rate of iteration {:d}: {:.3e}'.format(i, float(current_rate(args.solver_record, i)))
             print('iter {:d}/{:d}, size {:d}, total loss: {:.3}{:s}, take {:.2}s'.format(i, TOTAL_ITER, size,
                                                                                         float(losses[-1][4]), rate, _time))
+            if stats is not None:
+                from ..utils.region_loss import REGION_STATS_LINE
+                r = region_stats[-1]
+                print(REGION_STATS_LINE % (r[0], r[1], r[2], r[3], r[4], int(r[5])))
             T.tic()
         if args.ckpt_dir and (i % args.save_every == 0 or i == TOTAL_ITER):
             print("Model saved in file: %s" % net_utils.save_yolov2_snapshot(trainer, args.ckpt_dir, i))
     torch.cuda.synchronize()
     return {"losses": losses, "last_iter": TOTAL_ITER, "first_iter": last_iter_num + 1, "trainer": trainer,
-            "sizes": sizes, "anchors": np.asarray(anchors, np.float32), "imdb": imdb, "topology": args.topology}
+            "sizes": sizes, "anchors": np.asarray(anchors, np.float32), "imdb": imdb, "topology": args.topology,
+            "region_stats": region_stats}
 
 
 if __name__ == "__main__":

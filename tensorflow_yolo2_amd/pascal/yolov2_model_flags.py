@@ -8,7 +8,7 @@ def add_model_flags(ap, batch, batch_help, latest_is, darknet_classes):
     """--size, --batch, --dtype and the three ways to name the weights.  batch / batch_help: the script's own default and
     help of --batch; latest_is: what happens to the latest snapshot of --ckpt-dir ("evaluated", "used"); darknet_classes:
     where a Darknet file's class count comes from"""
-    ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--size", type=int, default=None, help="416, or the width of --cfg")
     ap.add_argument("--batch", type=int, default=batch, help=batch_help)
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--weights", default=None, help="snapshot file (train_iter_<i>.npz of pascal_train_yolov2.py)")
@@ -18,6 +18,49 @@ def add_model_flags(ap, batch, batch_help, latest_is, darknet_classes):
                          "(tiny-yolo-voc.weights): builds the graph the file holds, by its float count -- the \"darknet\" or "
                          "the \"tiny\" topology -- with that graph's published anchors and %s; not with --weights or "
                          "--ckpt-dir" % darknet_classes)
+    ap.add_argument("--cfg", default=None,
+                    help="the Darknet .cfg file that goes with --darknet-weights: it decides the graph, the class count, the "
+                         "anchors and the widths, and the file's float count is checked against it instead of guessed "
+                         "from; --size defaults to its width.  Not with --weights, --ckpt-dir or --width-div")
+    ap.add_argument("--names", default=None,
+                    help="a Darknet .names file, one class name per line: the names the detections are written under.  Its "
+                         "line count must be the model's class count")
+
+
+def resolve_cfg(ap, args):
+    """right behind parse_args: --cfg read into args.cfg_record (None without the flag) and the flags nobody gave filled
+    from it, then from today's defaults; --names read into args.class_names (None without the flag)"""
+    args.cfg_record = args.class_names = None
+    if args.cfg:
+        from ..utils import darknet_cfg
+        if args.weights or args.ckpt_dir:
+            ap.error("--cfg describes a Darknet graph, whose snapshot is the .weights file: not with --weights or --ckpt-dir")
+        if args.width_div != 1:
+            ap.error("--cfg holds the widths: not with --width-div")
+        try:
+            args.cfg_record = darknet_cfg.load(args.cfg)
+            darknet_cfg.compile_graph(args.cfg_record, 1024 if args.dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH)
+        except (OSError, ValueError) as e:
+            ap.error("--cfg: %s" % e)
+        if args.size is None:
+            args.size = args.cfg_record.size
+    if args.size is None:
+        args.size = 416
+    if args.names:
+        from ..utils import darknet_cfg
+        try:
+            args.class_names = darknet_cfg.read_names(args.names)
+        except OSError as e:
+            ap.error("--names: %s" % e)
+
+
+def class_names(ap_error, args, num_class, default):
+    """the names the detections are written under: --names (its count must be num_class), else `default`"""
+    if args.class_names is None:
+        return default
+    if len(args.class_names) != num_class:
+        ap_error("--names %s holds %d names, the model has %d classes" % (args.names, len(args.class_names), num_class))
+    return args.class_names
 
 
 def add_test_flags(ap):
@@ -28,7 +71,8 @@ def add_test_flags(ap):
 def check_size(ap, args):
     if args.size < 32 or args.size % 32:
         ap.error("--size %d: the detector head needs a positive multiple of 32 (S = size / 32)" % args.size)
-    if (args.size // 32) ** 2 * len(yolov2.ANCHORS_VOC) > 2048:
+    num = args.cfg_record.num if getattr(args, "cfg_record", None) is not None else len(yolov2.ANCHORS_VOC)
+    if (args.size // 32) ** 2 * num > 2048:
         ap.error("--size %d: more than 2048 candidates per image" % args.size)
 
 
@@ -41,6 +85,8 @@ def find_snapshot(args, num_class):
     """-> (snapshot path or None, anchors, class count, bn_eps) of the model to build: the snapshot's own where --weights
     or --ckpt-dir names one, else the published VOC anchors, `num_class` and the default epsilon (--darknet-weights:
     build_detector takes the published anchors of the graph the file holds)"""
+    if args.cfg_record is not None:           # the cfg decides: nothing is guessed from the file's float count
+        return None, args.cfg_record.anchors, args.cfg_record.classes, None
     snapshot = args.weights
     if not snapshot and args.ckpt_dir:
         sfiles = net_utils.get_ordered_yolov2_ckpts(args.ckpt_dir)
@@ -54,6 +100,13 @@ def find_snapshot(args, num_class):
 def build_detector(args, snapshot, anchors, num_class, bn_eps):
     """the detector of find_snapshot's answer, filled from --darknet-weights or from the snapshot -> (detector, the
     snapshot's iteration or 0)"""
+    if args.cfg_record is not None:
+        detector = yolov2.YOLOv2Detector.from_cfg(args.cfg_record, args.batch, args.size, dtype=args.dtype)
+        if args.darknet_weights:
+            print('Restorining model from Darknet weight file {:s} (cfg {:s}, topology {:s})'.format(
+                args.darknet_weights, args.cfg, detector.topology))
+            print('{:d} images seen'.format(net_utils.load_darknet_weights(detector, args.darknet_weights)))
+        return detector, 0
     topology = "paper"
     if args.darknet_weights:
         topology = net_utils.darknet_file_topology(args.darknet_weights, num_class, len(anchors), args.width_div)

@@ -124,6 +124,61 @@ def yolov2_loss_boxes(net, truth, ntruth, anchors, image_size, coord_scale=1.0, 
     return (loss, dnet, margins) if return_margins else (loss, dnet)
 
 
+REGION_STATS = ("avg_iou", "class", "obj", "no_obj", "avg_recall", "count")
+REGION_STATS_LINE = "Region Avg IOU: %f, Class: %f, Obj: %f, No Obj: %f, Avg Recall: %f,  count: %d"
+
+
+def region_stats_boxes(net, truth, ntruth, anchors, image_size, dtype=np.float64, return_margins=False):
+    """the numbers of Darknet's region-layer log line, from the inputs of yolov2_loss_boxes and with its derivations (cell
+    units, the cell (r, q), the first-maximum shape-IoU anchor bs, the decoded prediction, the centre-form IoU).  EVERY
+    listed truth counts, owner of its slot or not: Darknet's region layer has no ownership rule.  Per truth k: iou_k of
+    the prediction at (r, q, bs) with the truth, obj_k = sig(to) there, cls_k = softmax(class logits)[class] there when
+    0 <= class < C.  -> stats[6] = mean iou_k; mean cls_k over the truths with a valid class; mean obj_k; mean sig(to)
+    over all N S S B slots; share of truths with iou_k > 0.5; the truth count.  A mean over nothing is 0 (Darknet prints
+    NaN there).  With return_margins a second value: {"iou_half": least |iou_k - 0.5|, "shape_gap", "cell_edge"}, the
+    last two as yolov2_loss_boxes defines them."""
+    net = np.asarray(net, dtype)
+    truth = np.asarray(truth, dtype)
+    ntruth = np.asarray(ntruth).astype(np.int64)
+    an = np.asarray(anchors, dtype)
+    n, s, _, b, d = net.shape
+    c = d - 5
+    assert truth.ndim == 3 and truth.shape[0] == n and truth.shape[2] == 5, truth.shape
+    assert ntruth.shape == (n,) and (ntruth >= 0).all() and (ntruth <= truth.shape[1]).all(), ntruth
+    sig = lambda v: 1.0 / (1.0 + np.exp(-v))
+    margins = {"iou_half": np.inf, "shape_gap": np.inf, "cell_edge": np.inf}
+    ious, objs, clss = [], [], []
+    for i in range(n):
+        for k in range(int(ntruth[i])):
+            tr = truth[i, k]
+            gx, gy = tr[0] / image_size * s, tr[1] / image_size * s
+            gw, gh = tr[2] / image_size * s, tr[3] / image_size * s
+            r, q = min(int(gy), s - 1), min(int(gx), s - 1)
+            for g in (gx, gy):
+                frac = float(g) - np.floor(float(g))
+                margins["cell_edge"] = min(margins["cell_edge"], frac, 1.0 - frac)
+            shape_iou = shape_ious(gw, gh, an)
+            bs = int(np.argmax(shape_iou))                       # first maximum
+            if b > 1:
+                two = np.sort(shape_iou)[-2:]
+                margins["shape_gap"] = min(margins["shape_gap"], float(two[1] - two[0]))
+            t = net[i, r, q, bs]
+            iou = float(_box_iou_cwh(sig(t[0]) + q, sig(t[1]) + r, an[bs, 0] * np.exp(t[2]), an[bs, 1] * np.exp(t[3]),
+                                     gx, gy, gw, gh))
+            margins["iou_half"] = min(margins["iou_half"], abs(iou - 0.5))
+            ious.append(iou)
+            objs.append(sig(t[4]))
+            cls = int(tr[4])
+            if 0 <= cls < c:
+                lg = t[5:]
+                m = lg.max()
+                clss.append(np.exp(lg[cls] - m) / np.exp(lg - m).sum())
+    mean = lambda v: float(np.mean(np.asarray(v, dtype))) if len(v) else 0.0
+    stats = np.array([mean(ious), mean(clss), mean(objs), float(sig(net[..., 4]).mean()),
+                      mean([float(v > 0.5) for v in ious]), float(len(ious))], dtype)
+    return (stats, margins) if return_margins else stats
+
+
 def grid_to_box_list(labels, max_boxes=None):
     """the box list of a label grid [N,S,S,5+C] (one object per cell): its occupied cells in row-major order ->
     (truth [N][T][5] float32, ntruth [N] int32), T = max_boxes or the largest count (at least 1)"""

@@ -701,6 +701,8 @@ def _file_layers(topology, specs):
 def darknet_file_layers(model):
     """[(k, c, n, batch_norm)] of the file a "darknet" or "tiny" detector or trainer reads and writes (_file_layers)"""
     nets = _darknet_model(model, "darknet_file_layers")
+    if getattr(model, "cfg", None) is not None:          # a model built from a cfg: the file's own list
+        return list(model.cfg.file_layers)
     return _file_layers(model.topology, [net.spec for net in nets])
 
 
@@ -724,7 +726,10 @@ def darknet_file_topology(path, num_class, num_anchors, width_div=1):
 
 
 def _other_graph(model):
-    """for the float-count errors: what the file of the OTHER Darknet graph holds at the model's classes, anchors and width"""
+    """for the float-count errors: what the file of the OTHER Darknet graph holds at the model's classes, anchors and width
+    -- or, for a model built from a cfg, the cfg and its own count: no other graph is guessed"""
+    if getattr(model, "cfg", None) is not None:
+        return "the cfg %s describes %d floats" % (model.cfg.path, model.cfg.floats)
     (other,) = [t for t in _yolov2.DARKNET_FILE_TOPOLOGIES if t != model.topology]
     return "the \"%s\" graph at these classes, anchors and width_div %d holds %d floats" % (
         other, model.width_div, darknet_graph_floats(other, model.num_class, model.B, model.width_div))

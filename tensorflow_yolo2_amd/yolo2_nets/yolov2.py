@@ -11,6 +11,9 @@ parameter buffers, optional multi-scale.  `YOLOv2DarknetTrainer` is the train st
 of yolov2-voc.cfg: four stacks, Darknet's reorg and its gradient, a last layer without batch statistics -- and, with
 topology="tiny", of the "tiny" topology, the graph of tiny-yolo-voc.cfg: two stacks, Darknet's stride-1 pool between them
 (engine.max_pool_2x2_s1), no passthrough, two narrow layers that run zero-padded.
+`YOLOv2Detector.from_cfg` / `YOLOv2DarknetTrainer.from_cfg` build the graph a Darknet cfg describes (utils/darknet_cfg.py):
+its layer list compiled onto the same record (_cfg_topology) -- a chain under the name "tiny", a passthrough under the name
+"darknet" -- with the file's widths, class count and anchors.
 """
 import collections
 
@@ -128,6 +131,32 @@ def _topology(name):
     return _TOPOLOGY[name]
 
 
+def _cfg_topology(record, dtype):
+    """the _Topology of a Darknet cfg (utils/darknet_cfg.py) -> (topology, record): one more way to produce the record the
+    code below reads, under the name of the shape it has -- "tiny" for a chain, "darknet" for a passthrough.  A cfg that
+    describes yolov2-voc.cfg or tiny-yolo-voc.cfg gives the named topology's stacks, options and ops"""
+    from ..utils import darknet_cfg
+    record = darknet_cfg.as_record(record)
+    graph = darknet_cfg.compile_graph(record, 1024 if dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH)
+    n, head = len(graph.specs), graph.head_layers
+    slopes = (None,) * (n - 1) + ([0.1] * (head - 1) + [1.0],)
+    options = (_BESSEL,) * (n - 1) + (dict(_BESSEL, core_layers=head - 1),)
+    common = dict(specs=lambda num_class, num_anchors, width_div, _s=graph.specs: tuple(list(s) for s in _s),
+                  bn_eps=DARKNET_BN_EPS, slopes=slopes, train_options=options, head_statistics=False, darknet_input=True,
+                  centre_tap=graph.centre_tap, narrow=graph.narrow, anchors=record.anchors)
+    if graph.shape == "chain":
+        s1 = graph.pool == "s1"
+        topo = _Topology(name="tiny", heights=(32, 1), concat=None, concat_backward=None, cf_stack=None,
+                         pool=E.max_pool_2x2_s1 if s1 else E.max_pool_2x2,
+                         pool_backward=E.max_pool_2x2_s1_backward if s1 else E.max_pool_2x2_backward, **common)
+    else:
+        topo = _Topology(name="darknet", heights=(32, 1, 2, 1) if graph.route else (32, 1, 1),
+                         concat=E.passthrough_concat_darknet, concat_backward=E.passthrough_concat_darknet_backward,
+                         cf_stack=2 if graph.route else 0, pool=E.max_pool_2x2, pool_backward=E.max_pool_2x2_backward,
+                         **common)
+    return topo, record
+
+
 def _build_stacks(topo, specs, batch, size, dtype, device, bn_eps, training, seed, share_with=None):
     """the stack contexts of one input size, in networks() order.  share_with: the contexts of another size, whose
     parameters these are bound to; without it every stack draws its initial values from seed + its position"""
@@ -184,10 +213,11 @@ class YOLOv2Detector:
     bn_eps: the batch-norm epsilon of every stack (None: the context's default 1e-3, or 1e-6 on "darknet" / "tiny")."""
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0", width_div=1, topology="paper", bn_eps=None):
+                 device="cuda:0", width_div=1, topology="paper", bn_eps=None, _cfg=None):
         assert image_size % 32 == 0
-        self._topo = _topology(topology)
-        self.topology = topology
+        # _cfg: (topology record, cfg record) of from_cfg -- the graph of a file under the name of its shape
+        self._topo, self.cfg = _cfg if _cfg is not None else (_topology(topology), None)
+        self.topology = topology = self._topo.name
         self.bn_eps = self._topo.bn_eps if bn_eps is None else float(bn_eps)
         self.batch, self.size, self.S = batch, image_size, image_size // 32
         self.num_class, self.anchors = num_class, np.asarray(anchors, np.float32).reshape(-1, 2)
@@ -202,6 +232,15 @@ class YOLOv2Detector:
         if len(self._stacks) == 4:
             self.route = self._stacks[2]
         self._buffers = _make_buffers(self._topo, self._stacks, batch, image_size)
+
+    @classmethod
+    def from_cfg(cls, record_or_path, batch, image_size=None, dtype="f16", seed=0, device="cuda:0"):
+        """the detector of a Darknet cfg (utils/darknet_cfg.py: a record or a file): its graph, widths, class count and
+        anchors; image_size defaults to the file's width.  net_utils.load_darknet_weights fills it from the `.weights`
+        file that goes with the cfg"""
+        topo, record = _cfg_topology(record_or_path, dtype)
+        return cls(batch, record.size if image_size is None else image_size, num_class=record.classes,
+                   anchors=record.anchors, dtype=dtype, seed=seed, device=device, _cfg=(topo, record))
 
     def networks(self):
         """the stack contexts: (stem, 13x13 stack, head), or on the "darknet" topology (stem, 13x13 stack, route, head)
@@ -266,8 +305,9 @@ class _Trainer:
     keeps_backward = False           # whether backward() leaves last_dcat / last_dfine behind (a subclass's tests read them)
 
     def __init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
-                 area_weight, prior_images, prior_scale, solver, bn_eps):
-        self._topo = _topology(topology)
+                 area_weight, prior_images, prior_scale, solver, bn_eps, _cfg=None):
+        self._topo, self.cfg = _cfg if _cfg is not None else (_topology(topology), None)
+        topology = self._topo.name
         # the batch-norm epsilon of every context and size (None: the contexts' default, 1e-3); 1e-6 is Darknet's, the one
         # a backbone read from a Darknet file was trained with (net_utils.read_darknet_backbone)
         self.topology, self.bn_eps = topology, self._topo.bn_eps if bn_eps is None else float(bn_eps)
@@ -276,6 +316,7 @@ class _Trainer:
         self.batch, self.num_class, self.dtype, self.device, self.seed = batch, num_class, dtype, device, seed
         self.anchors = np.asarray(anchors, np.float32)
         self.B, self.width_div = len(self.anchors), width_div
+        self._anchors_dev = None                             # the anchors on the device, for step(stats=...)
         self.scales = scales
         # box-list labels only (step(images, truth=..., ntruth=...)): Darknet's (2 - w h) coord weight, and its anchor-prior
         # term while fewer than prior_images images have been seen ((iteration - 1) * batch, counted over resumed runs)
@@ -382,12 +423,15 @@ class _Trainer:
                 r.join()
         return world
 
-    def step(self, images, labels=None, truth=None, ntruth=None):
+    def step(self, images, labels=None, truth=None, ntruth=None, stats=None):
         """one train step on the label grid `labels` [N,S,S,5+C] (one box per cell) or on the box list `truth` [N,T,5] +
         `ntruth` [N] (every object; DeviceVOC(..., max_boxes=T)): exactly one of the two forms.  Returns loss[5] = coord,
-        object, noobject, class, total"""
+        object, noobject, class, total.  stats: a six-float device tensor that engine.yolov2_region_stats fills from this
+        step's head output, before the update (box lists only); None launches nothing more"""
         if (labels is None) == (truth is None) or (truth is None) != (ntruth is None):
             raise ValueError("step() takes either labels or truth + ntruth, not both and not neither")
+        if stats is not None and truth is None:
+            raise ValueError("step(stats=...) reads the box list: give truth + ntruth, not labels")
         size = int(images.shape[1])
         nets = self._nets(size)
         if len(self.ctx) > 1:
@@ -400,6 +444,10 @@ class _Trainer:
         else:
             loss, dnet = E.yolov2_loss_boxes(grid.contiguous(), truth, ntruth, self.anchors, size, True,
                                              self.box_scales(self.iteration))
+            if stats is not None:
+                if self._anchors_dev is None:                # uploaded once: the statistics add two launches, no copy
+                    self._anchors_dev = torch.as_tensor(self.anchors).to(grid.device).contiguous()
+                E.yolov2_region_stats(grid.contiguous(), truth, ntruth, self._anchors_dev, size, out=stats)
         self.last_dnet = dnet                                # the head's output gradient of this step (tests read it)
         world = self.backward(dnet, fine, size)
         scaler = self.opts[0].scaler
@@ -489,12 +537,28 @@ class YOLOv2DarknetTrainer(_Trainer):
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
-                 solver=None, bn_eps=None, topology="darknet"):
+                 solver=None, bn_eps=None, topology="darknet", _cfg=None):
         if topology not in DARKNET_FILE_TOPOLOGIES:
             raise ValueError("YOLOv2DarknetTrainer trains the \"darknet\" and \"tiny\" topologies; topology %r is "
                              "YOLOv2Trainer's" % (topology,))
         _Trainer.__init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
-                          area_weight, prior_images, prior_scale, solver, bn_eps)
+                          area_weight, prior_images, prior_scale, solver, bn_eps, _cfg=_cfg)
+
+    CFG_PRIOR_IMAGES = 12800         # Darknet's region layer hard-codes the prior's span and the (2 - w h) weight
+
+    @classmethod
+    def from_cfg(cls, record_or_path, batch=None, image_size=None, dtype="f16", seed=0, device="cuda:0", solver=None,
+                 prior_images=None):
+        """the train step of a Darknet cfg (utils/darknet_cfg.py: a record or a file): its graph, widths, class count and
+        anchors; its [net] solver; its [region] scales (coord_scale ... thresh); area_weight and prior_images 12800, which
+        Darknet hard-codes.  batch and image_size default to the file's; solver / prior_images: a caller's own in place
+        of the file's (a flag given on the command line)"""
+        topo, record = _cfg_topology(record_or_path, dtype)
+        return cls(record.batch if batch is None else batch, record.size if image_size is None else image_size,
+                   num_class=record.classes, anchors=record.anchors, dtype=dtype, seed=seed, device=device,
+                   scales=dict(record.scales), area_weight=True,
+                   prior_images=cls.CFG_PRIOR_IMAGES if prior_images is None else prior_images,
+                   solver=record.solver if solver is None else solver, _cfg=(topo, record))
 
     def _init_form(self, nets):
         """a fresh model in the form a `.weights` file can hold: the 1x1 layers' off-centre taps zero, the narrow layers'
