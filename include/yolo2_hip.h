@@ -676,6 +676,45 @@ int y2_voc_match_batch_f(const int* det, const float* score, const int* count, c
                          const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
                          int max_out, float iou_thresh, int* flags, void* stream);
 
+/* ---- COCO's bounding-box matching (csrc/coco.hip; DESIGN.md 9, "COCO evaluation"; specification:
+ *      utils/coco_eval.match_segment, numpy float64, bit for bit -- a restatement of COCOeval.evaluateImg with
+ *      iouType = "bbox", useCats = 1 and of the mask API's bbIou).  Not in the reference.
+ * det [n][max_out][6], count [n], index [n] or NULL: as y2_voc_match_batch reads them (columns 0..4 of a row; with
+ * per-class rows a segment is one (image, class) and index names each image num_class times).  boxes float64
+ * [entries][max_obj][5] = x, y, w, h, class of every annotation in file order, in COCO's own convention (zero-based
+ * continuous corner, no + 1 extent); area float64 [entries][max_obj], the annotation's `area` field; crowd uint8
+ * [entries][max_obj]; counts int32 [entries].  thresholds float64 [T], area_ranges float64 [A][2] = lo, hi.  All pointers
+ * are device memory.
+ * A row's box: row_form 0, the integer rows of y2_detect_anchor_classes_batch[_lb] (1-based inclusive corners):
+ * x = xmin - 1, y = ymin - 1, w = xmax - xmin + 1, h = ymax - ymin + 1; row_form 1, the float rows of
+ * y2_detect_anchor_classes_batch_dk (both corners carry Darknet's + 1): x = double(xmin) - 1, y = double(ymin) - 1,
+ * w = double(xmax) - double(xmin), h likewise.
+ * IoU(d, g, crowd), every operation a separate double operation: da = dw * dh; ga = gw * gh; ow = min(dx + dw, gx + gw) -
+ * max(dx, gx), 0 if ow <= 0; oh likewise; i = ow * oh; u = crowd ? da : (da + ga) - i; i / u.
+ * For every area range a and threshold t on their own: an object is IGNORED if it is crowd or its area is < lo or > hi.
+ * The rows are walked in order (descending score).  Per row best = min(thresholds[t], 1 - 1e-10), no match; first the
+ * non-ignored objects of the row's class in annotation order: one already matched under (a, t) is skipped, one whose IoU
+ * is < best is skipped, else best = IoU and it is the match (an equal IoU moves the match to the later object); only if
+ * none was found, the ignored objects of the class by the same rules, except that a crowd object is never skipped for
+ * being matched and its IoU is the crowd form.  A match becomes matched; the row's value is 1 (true positive) if the
+ * match is not ignored, else 2 (ignored).  Without a match the value is 2 if the row's own w * h is < lo or > hi, else 0
+ * (false positive).
+ * match int32 [n][max_out][A]: bits 2t, 2t + 1 of word a hold the value under (a, t), the other bits 0; rows at or beyond
+ * count are all -1.  Non-finite rows are not specified.  Y2_ERR_ARG, nothing launched: a null pointer (index may be
+ * NULL), n outside 1..Y2_COCO_MAX_SEGMENTS, max_obj outside 1..Y2_COCO_MAX_OBJECTS, max_out outside 1..Y2_COCO_MAX_ROWS,
+ * T outside 1..Y2_COCO_MAX_THRESHOLDS, A outside 1..Y2_COCO_MAX_AREAS, T * A > 64, row_form not 0 or 1.
+ * One 64-lane wave per segment, lane = (a, t); one launch, nothing allocated, no synchronisation, no atomics. */
+#define Y2_COCO_MAX_SEGMENTS (65535 * 80) /* n: 65535 images of 80 classes */
+#define Y2_COCO_MAX_OBJECTS 256           /* max_obj: 116 bytes of LDS per object (29 KB here, and several waves per CU
+                                             at COCO's real maximum of about a hundred annotations per image) */
+#define Y2_COCO_MAX_ROWS 65536            /* max_out (COCO's maxDets is 100) */
+#define Y2_COCO_MAX_THRESHOLDS 16         /* T: two bits per threshold in one int32 word */
+#define Y2_COCO_MAX_AREAS 4               /* A */
+int y2_coco_match_batch(const int* det, const int* count, const double* boxes, const double* area,
+                        const uint8_t* crowd, const int32_t* counts, const int32_t* index, int n, int max_obj,
+                        int max_out, const double* thresholds, int T, const double* area_ranges, int A, int row_form,
+                        int* match, void* stream);
+
 /* ---- classifier scoring over several views of an image (csrc/score.hip; specification: utils/score_views.py, float64).
  * logits [n * views][classes] fp32, row b * views + v is view v of image b.  Per view p_v[c] = exp(x_v[c] - max_v) /
  * sum_c exp(x_v[c] - max_v), then p[c] = (1 / views) * sum_v p_v[c] (Darknet's validate_classifier_10 averages the

@@ -155,6 +155,7 @@ SIGNATURES = {
     "y2_letterbox_darknet_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "y2_detect_anchor_classes_batch_dk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "y2_voc_match_batch_f": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "y2_coco_match_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "y2_score_views": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "y2_crc32c": (C.c_uint32, [_vp, _sz, C.c_uint32]),
 }

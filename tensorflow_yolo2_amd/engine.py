@@ -1263,6 +1263,64 @@ def voc_match_batch_f(det, score, count, boxes, counts, difficult, index=None, i
     return _voc_match("y2_voc_match_batch_f", det, score, count, boxes, counts, difficult, index, iou_thresh, out)
 
 
+# ---- COCO's bounding-box matching (csrc/coco.hip; DESIGN.md 9, "COCO evaluation")
+COCO_MAX_OBJECTS, COCO_MAX_THRESHOLDS, COCO_MAX_AREAS = 256, 16, 4          # Y2_COCO_MAX_*
+_coco_defaults = {}
+
+
+def _coco_table(values, default, width, device):
+    """thresholds / area_ranges: a float64 device tensor as it is; None: COCO's own, uploaded once per device; anything
+    else numpy reads: uploaded here"""
+    if torch.is_tensor(values):
+        return _dev(values, torch.float64, "thresholds" if width == 1 else "area_ranges")
+    if values is None:
+        key = (default, str(device))
+        if key not in _coco_defaults:
+            from .utils import coco_eval
+            _coco_defaults[key] = torch.as_tensor(np.ascontiguousarray(getattr(coco_eval, default), np.float64)).to(device)
+        return _coco_defaults[key]
+    return torch.as_tensor(np.ascontiguousarray(values, np.float64)).to(device)
+
+
+def coco_match_batch(det, count, boxes, area, crowd, counts, index=None, thresholds=None, area_ranges=None, row_form=0,
+                     out=None):
+    """det int32 [n,max_out,6], count int32 [n] (the [n * C] view of detect_anchor_classes_batch's rows, or any detect
+    call's); boxes float64 [entries,max_obj,5] = x, y, w, h, class in COCO's convention, area float64 [entries,max_obj],
+    crowd uint8 [entries,max_obj], counts int32 [entries] (DeviceCOCO); index int32 [n] or None; thresholds float64 [T]
+    and area_ranges float64 [A,2]: device tensors, anything numpy reads, or None for COCO's ten thresholds and four
+    ranges -> match int32 [n,max_out,A] (`out` comes back by identity): bits 2t, 2t + 1 of word a hold 1 true positive,
+    0 false positive, 2 ignored under threshold t and area range a; -1 beyond count
+    (utils/coco_eval.match_segment per segment, bit for bit).  row_form 0: integer rows; 1: the float rows of
+    detect_anchor_classes_batch_darknet.  One launch on the current stream.
+    ValueError: "row_form R is neither 0 (integer rows) nor 1 (float rows)"; "T thresholds and A area ranges: at most 16
+    and 4, and at most 64 pairs"; "max_obj = M: the matcher holds at most 256 annotations of an image"."""
+    if row_form not in (0, 1):
+        raise ValueError("row_form %r is neither 0 (integer rows) nor 1 (float rows)" % (row_form,))
+    assert det.is_cuda and det.dtype == torch.int32 and det.is_contiguous() and det.dim() == 3 and det.shape[2] == 6
+    n, max_out = det.shape[0], det.shape[1]
+    assert _dev(count, torch.int32, "count").numel() == n
+    assert _dev(boxes, torch.float64, "boxes").dim() == 3 and boxes.shape[2] == 5, boxes.shape
+    entries, max_obj = boxes.shape[0], boxes.shape[1]
+    assert tuple(_dev(area, torch.float64, "area").shape) == (entries, max_obj), area.shape
+    assert tuple(_dev(crowd, torch.uint8, "crowd").shape) == (entries, max_obj), crowd.shape
+    assert _dev(counts, torch.int32, "counts").numel() == entries
+    _entries(None, index, n, entries)                  # no table here: without an index, the first n rows of `boxes`
+    thr = _coco_table(thresholds, "THRESHOLDS", 1, det.device)
+    rng = _coco_table(area_ranges, "AREA_RANGES", 2, det.device)
+    assert thr.dim() == 1 and rng.dim() == 2 and rng.shape[1] == 2, (thr.shape, rng.shape)
+    T, A = thr.shape[0], rng.shape[0]
+    if not (1 <= T <= COCO_MAX_THRESHOLDS and 1 <= A <= COCO_MAX_AREAS and T * A <= 64):
+        raise ValueError("%d thresholds and %d area ranges: at most %d and %d, and at most 64 pairs"
+                         % (T, A, COCO_MAX_THRESHOLDS, COCO_MAX_AREAS))
+    if max_obj > COCO_MAX_OBJECTS:
+        raise ValueError("max_obj = %d: the matcher holds at most %d annotations of an image" % (max_obj, COCO_MAX_OBJECTS))
+    match = _own(out, (n, max_out, A), torch.int32, det.device, n * max_out * A)
+    check(_lib.load().y2_coco_match_batch(_ptr(det), _ptr(count), _ptr(boxes), _ptr(area), _ptr(crowd), _ptr(counts),
+                                          _ptr(index), n, max_obj, max_out, _ptr(thr), T, _ptr(rng), A, int(row_form),
+                                          _ptr(match), _stream()))
+    return match
+
+
 def softmax_cross_entropy(logits, labels, need_grad=True):
     """sparse_softmax_cross_entropy_with_logits + reduce_mean (imagenet_train_darknet.py:51-53)."""
     lib = _lib.load()
