@@ -546,6 +546,16 @@ int y2_encode_labels_window(const double* boxes, const int32_t* counts, const in
 int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
                        const double* params, int n, int max_obj, int image_size, int max_boxes, float* truth,
                        int32_t* ntruth, void* stream);
+/* y2_encode_box_list with Darknet's shuffle-then-cut (augment.encode_box_list_draw, bit-equal).  `keys` uint32 [n] in
+ * device memory, one per batch slot.  An image whose window keeps at most max_boxes objects gives y2_encode_box_list's
+ * rows, whatever its key.  One that keeps more gives exactly max_boxes rows: the objects with the smallest
+ * (augment.box_rank(key, j), j), j the annotation index, written in annotation order.  `keys` NULL: y2_encode_box_list's
+ * result.  max_obj beyond Y2_DRAW_MAX_OBJ (the kernel keeps one ballot bit per object in LDS) is an argument error.  One
+ * 64-lane wave per image, no atomics. */
+#define Y2_DRAW_MAX_OBJ 1024
+int y2_encode_box_list_draw(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
+                            const double* params, const uint32_t* keys, int n, int max_obj, int image_size,
+                            int max_boxes, float* truth, int32_t* ntruth, void* stream);
 
 /* ---- the classifier's augmentation on the same pool (img_dataset/augment_cls.py is the specification, bit for bit):
  *      mirror, rotation, scale and crop as ONE affine map.  `params` double [n][9] in device memory, one row per batch

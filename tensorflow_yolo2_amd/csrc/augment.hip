@@ -252,6 +252,100 @@ __global__ __launch_bounds__(64) void encode_box_list_kernel(const double* __res
     if (lane == 0) ntruth[img] = rows;
 }
 
+// augment.box_rank: the 32-bit hash of (key, annotation index) that orders an image's objects for the draw.  32-bit
+// integer operations only -- xor, shift, multiply modulo 2^32 -- so that numpy and this function agree on every bit.
+Y2_DEV uint32_t box_rank(uint32_t key, uint32_t j) {
+    uint32_t x = key ^ (j * 0x9E3779B9u);
+    x ^= x >> 16; x *= 0x7FEB352Du;
+    x ^= x >> 15; x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+
+constexpr int kDrawMaxObj = 1024;               // Y2_DRAW_MAX_OBJ: objects per entry the draw kernel holds ballots for
+constexpr int kDrawRounds = kDrawMaxObj / 64;
+
+// The box list with Darknet's shuffle-then-cut (augment.encode_box_list_draw): grid (n), ONE 64-lane wave per image, the
+// arithmetic and the layout of the kernel above.  Where an image has more surviving objects than max_boxes, the ones
+// kept are the max_boxes with the smallest (box_rank(key, j), j), written in annotation order:
+//   round one   window_box per object, keep or drop; the ballot of every round of 64 goes to LDS (kDrawRounds words)
+//   round two   a surviving lane counts the survivors that rank before it: the ballot words are wave-uniform, so the walk
+//               over their set bits is a scalar loop, and every lane recomputes the other object's hash -- no sort, no
+//               atomics, nothing depends on timing.  It is selected when fewer than max_boxes rank before it
+//   compaction  the selected lanes of a round, with the ballot and the count of selected lanes below
+// With at most max_boxes survivors, or keys == nullptr, every survivor is selected and the pos < max_boxes guard is the
+// kernel above's cut: the same rows bit for bit.  The box is formed again in round two rather than held: the rounds of
+// an image are few, and a per-round register array would be indexed at run time (scratch).
+__global__ __launch_bounds__(64) void encode_box_list_draw_kernel(const double* __restrict__ boxes,
+                                                                  const int32_t* __restrict__ counts,
+                                                                  const int64_t* __restrict__ table,
+                                                                  const int32_t* __restrict__ index,
+                                                                  const double* __restrict__ params,
+                                                                  const uint32_t* __restrict__ keys, int max_obj,
+                                                                  int image_size, int max_boxes,
+                                                                  float* __restrict__ truth,
+                                                                  int32_t* __restrict__ ntruth) {
+    __shared__ unsigned long long kept[kDrawRounds];
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const size_t e = index ? (size_t)index[img] : (size_t)img;
+    const int64_t* t = table + kTable * e;
+    double wx0 = 0.0, wy0 = 0.0, cw = (double)t[2], ch = (double)t[1];
+    bool flip = t[4] != 0;
+    if (params) flip = read_window(params + (size_t)kParams * img, flip, wx0, wy0, cw, ch);
+    const bool window = cw >= 1.0 && ch >= 1.0;           // a row without a window: an empty list
+    const double w_ratio = (double)image_size / cw, h_ratio = (double)image_size / ch;
+    const double hi = (double)(image_size - 1), size = (double)image_size;
+    const int cnt = window ? min(max(counts[e], 0), min(max_obj, kDrawMaxObj)) : 0;
+    const int rounds = (cnt + 63) >> 6;                   // <= kDrawRounds
+    const double* bx0 = boxes + e * (size_t)max_obj * 5;
+    float* out = truth + (size_t)img * max_boxes * 5;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int survivors = 0;
+    for (int r = 0; r < rounds; ++r) {
+        const int o = r * 64 + lane;
+        const bool keep = o < cnt && window_box(bx0 + (size_t)o * 5, wx0, wy0, w_ratio, h_ratio, hi, size).keep;
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) kept[r] = b;
+        survivors += __popcll(b);
+    }
+    __syncthreads();
+    const bool draw = keys != nullptr && survivors > max_boxes;          // (wave-uniform)
+    const uint32_t key = keys ? keys[img] : 0u;
+    int base = 0;                                         // rows written by the rounds before (wave-uniform)
+    for (int r = 0; r < rounds; ++r) {
+        const int o = r * 64 + lane;
+        bool sel = (kept[r] >> lane) & 1ull;
+        if (draw) {
+            const uint32_t mine = box_rank(key, (uint32_t)o);
+            int before = 0;
+            for (int r2 = 0; r2 < rounds; ++r2) {
+                for (unsigned long long m = kept[r2]; m; m &= m - 1ull) {
+                    const int j = r2 * 64 + __builtin_ctzll(m);
+                    const uint32_t other = box_rank(key, (uint32_t)j);
+                    before += (other < mine || (other == mine && j < o)) ? 1 : 0;
+                }
+            }
+            sel = sel && before < max_boxes;
+        }
+        const unsigned long long chosen = __ballot(sel);
+        const int pos = base + __popcll(chosen & below);
+        if (sel && pos < max_boxes) {
+            const double* bx = bx0 + (size_t)o * 5;
+            const WindowBox b = window_box(bx, wx0, wy0, w_ratio, h_ratio, hi, size);
+            float* row = out + (size_t)pos * 5;
+            row[0] = (float)(flip ? hi - b.cx() : b.cx());
+            row[1] = (float)b.cy();
+            row[2] = (float)b.w();
+            row[3] = (float)b.h();
+            row[4] = (float)(int)bx[4];
+        }
+        base += __popcll(chosen);
+    }
+    const int rows = min(base, max_boxes);
+    for (int i = rows * 5 + lane; i < max_boxes * 5; i += 64) out[i] = 0.0f;
+    if (lane == 0) ntruth[img] = rows;
+}
+
 // ---- The classifier's augmentation (img_dataset/augment_cls.py): mirror, rotation, scale and crop are ONE affine map from
 // an output pixel index to a source coordinate, so the kernel is a gather of four taps per pixel through that map -- not
 // the row-staged resize above, whose window is axis-aligned.  Bit-equal to augment_cls.warp_affine_u8 + distort_hsv_u8:
@@ -443,6 +537,23 @@ int y2_encode_box_list(const double* boxes, const int32_t* counts, const int64_t
     hipLaunchKernelGGL(encode_box_list_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, boxes, counts, table, index,
                        params, max_obj, image_size, max_boxes, truth, ntruth);
     return launched("y2_encode_box_list");
+}
+
+int y2_encode_box_list_draw(const double* boxes, const int32_t* counts, const int64_t* table, const int32_t* index,
+                            const double* params, const uint32_t* keys, int n, int max_obj, int image_size,
+                            int max_boxes, float* truth, int32_t* ntruth, void* stream) {
+    if (!boxes || !counts || !table || !truth || !ntruth)
+        return fail(Y2_ERR_ARG, "y2_encode_box_list_draw: null pointer");
+    if (n < 1) return fail(Y2_ERR_ARG, "y2_encode_box_list_draw: n = %d", n);
+    if (max_obj < 1 || image_size < 1)
+        return fail(Y2_ERR_ARG, "y2_encode_box_list_draw: max_obj = %d, image_size = %d", max_obj, image_size);
+    if (max_obj > kDrawMaxObj)
+        return fail(Y2_ERR_ARG, "y2_encode_box_list_draw: max_obj = %d beyond Y2_DRAW_MAX_OBJ = %d", max_obj, kDrawMaxObj);
+    if (max_boxes < 1 || max_boxes > Y2_MAX_BOXES)
+        return fail(Y2_ERR_ARG, "y2_encode_box_list_draw: max_boxes = %d outside 1..%d", max_boxes, Y2_MAX_BOXES);
+    hipLaunchKernelGGL(encode_box_list_draw_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, boxes, counts, table,
+                       index, params, keys, max_obj, image_size, max_boxes, truth, ntruth);
+    return launched("y2_encode_box_list_draw");
 }
 
 int y2_augment_u8_batch(const uint8_t* pool, const int64_t* table, const int32_t* index, const double* params, int n,

@@ -140,10 +140,16 @@ def _window_boxes(objs, row, image_size):
     """the window arithmetic of both label formats, in double: per object of `objs` whose unclamped centre lies inside
     [0, image_size) in x and y -- the others are dropped -- the clamped box as (cx, cy, w, h, class index), in annotation
     order.  x = (bx - 1 - x0) * (image_size / cw), y likewise."""
+    for (_j, cx, cy, w, h, cls_ind) in _window_boxes_indexed(objs, row, image_size):
+        yield cx, cy, w, h, cls_ind
+
+
+def _window_boxes_indexed(objs, row, image_size):
+    """_window_boxes with the annotation index j of every survivor in front"""
     x0, y0, cw, ch = (float(int(row[k])) for k in (X0, Y0, CW, CH))     # integers, as cut_window reads them
     w_ratio = image_size / cw
     h_ratio = image_size / ch
-    for (xmin, ymin, xmax, ymax, cls_ind) in objs:
+    for j, (xmin, ymin, xmax, ymax, cls_ind) in enumerate(objs):
         x1, y1 = (float(xmin) - 1 - x0) * w_ratio, (float(ymin) - 1 - y0) * h_ratio
         x2, y2 = (float(xmax) - 1 - x0) * w_ratio, (float(ymax) - 1 - y0) * h_ratio
         cx, cy = (x2 + x1) / 2.0, (y2 + y1) / 2.0
@@ -151,7 +157,7 @@ def _window_boxes(objs, row, image_size):
             continue
         x1, y1 = max(min(x1, image_size - 1), 0), max(min(y1, image_size - 1), 0)
         x2, y2 = max(min(x2, image_size - 1), 0), max(min(y2, image_size - 1), 0)
-        yield (x2 + x1) / 2.0, (y2 + y1) / 2.0, x2 - x1, y2 - y1, int(cls_ind)
+        yield j, (x2 + x1) / 2.0, (y2 + y1) / 2.0, x2 - x1, y2 - y1, int(cls_ind)
 
 
 def encode_boxes_window(objs, row, image_size, cell_size, num_class=20, flip=False):
@@ -192,3 +198,62 @@ def encode_box_list(objs, row, image_size, max_boxes=MAX_BOXES, flip=False):
         truth[count] = (image_size - 1 - cx if mirror else cx, cy, w, h, cls_ind)
         count += 1
     return truth, count
+
+
+# ---- Darknet's shuffle-then-cut: which objects a crowded image keeps
+KEY_STREAM = 0xB0C                          # last word of the key generator's seed sequence (STREAM's neighbour)
+
+
+def key_generator(seed, rank):
+    """the stream the draw's keys come from, one uint32 per sample: a generator of its own, so that turning the draw on
+    moves neither the batch order nor the augmentation rows"""
+    return np.random.default_rng([int(seed), int(rank), KEY_STREAM])
+
+
+def draw_key(rng):
+    """the next key of the stream: one call of the Generator per sample, whatever the sample holds"""
+    return int(rng.integers(0, 1 << 32, dtype=np.uint64))
+
+
+def box_rank(key, j):
+    """the 32-bit hash of (key, annotation index j) that orders an image's objects for the draw.  32-bit integer
+    operations only -- xor, shift, multiply modulo 2^32 -- so that numpy and a kernel agree on every bit:
+        x = key ^ (j * 0x9E3779B9)
+        x = x ^ (x >> 16);  x = x * 0x7FEB352D
+        x = x ^ (x >> 15);  x = x * 0x846CA68B
+        x = x ^ (x >> 16)
+    every product modulo 2^32.  (The two multipliers and three shifts are the published `lowbias32` integer finaliser;
+    the first line spreads neighbouring indices by the 32-bit golden ratio.)  key and j may be arrays: the result is
+    uint32 of their broadcast shape."""
+    m = np.uint64(0xFFFFFFFF)
+    key, j = np.asarray(key, np.uint64) & m, np.asarray(j, np.uint64) & m
+    x = key ^ ((j * np.uint64(0x9E3779B9)) & m)
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & m
+    x = x ^ (x >> np.uint64(16))
+    return x.astype(np.uint32)
+
+
+def encode_box_list_draw(objs, row, image_size, max_boxes=MAX_BOXES, key=0, flip=False):
+    """encode_box_list with Darknet's shuffle-then-cut in place of "the first max_boxes": (truth [max_boxes, 5] float32,
+    number of rows used).  The survivors are exactly _window_boxes' survivors, each with its annotation index j and
+    box_rank(key, j); the max_boxes survivors with the smallest (hash, j) are kept and written IN ANNOTATION ORDER, in
+    encode_box_list's arithmetic.  So with at most max_boxes survivors the result is encode_box_list's bit for bit,
+    whatever the key; with more it is exactly max_boxes of the uncut list's rows, and the key decides which.  `key` is
+    one uint32 per sample (key_generator).  The specification of y2_encode_box_list_draw (csrc/augment.hip)."""
+    if not 1 <= int(max_boxes) <= 1024:
+        raise ValueError("max_boxes %r outside 1..1024" % (max_boxes,))
+    if not 0 <= int(key) < 1 << 32:
+        raise ValueError("key %r is no uint32" % (key,))
+    mirror = bool(flip) != bool(row[FLIP])
+    survivors = list(_window_boxes_indexed(objs, row, image_size))
+    if len(survivors) > max_boxes:
+        ranks = box_rank(int(key), [s[0] for s in survivors])
+        first = sorted(range(len(survivors)), key=lambda k: (int(ranks[k]), survivors[k][0]))[:int(max_boxes)]
+        survivors = [survivors[k] for k in sorted(first)]
+    truth = np.zeros((int(max_boxes), 5), np.float32)
+    for count, (_j, cx, cy, w, h, cls_ind) in enumerate(survivors):
+        truth[count] = (image_size - 1 - cx if mirror else cx, cy, w, h, cls_ind)
+    return truth, len(survivors)

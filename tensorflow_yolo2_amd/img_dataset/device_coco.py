@@ -17,12 +17,17 @@ max_obj is the largest annotation count of an image (at least 1), at most engine
 
 eval_batch(size, start, letterbox, fill, protocol) goes through DevicePool.list_batch exactly as DeviceVOC.eval_batch
 does; `eval_index`, `table`, `num_class`, `classes` (the category names) and `category_ids` (the original ids, ascending:
-with the published files the order of coco.names) are named as there.  Training batches are out of scope: a training
-path converts the box table to its own convention."""
+with the published files the order of coco.names) are named as there.
+
+Training batches are DeviceCOCOTrain's: the same images as the entries of a DeviceBoxes pool (device_boxes.py), with the
+annotations converted to that pool's convention by train_entries -- crowd annotations and boxes with w <= 0 or h <= 0
+left out, x, y, w, h -> the 1-based corners (x + 1, y + 1, x + w + 1, y + h + 1), the class the category index 0..K-1,
+`difficult` all zero.  Images without an object stay (Darknet's negatives).  DeviceCOCO itself stays as it is."""
 import os
 
 import numpy as np
 
+from .device_boxes import DeviceBoxes
 from .device_pool import DEFAULT_MAX_POOL_BYTES, DevicePool
 from .pascal_voc import imread_bgr
 
@@ -75,3 +80,31 @@ class DeviceCOCO(DevicePool):
     def eval_batch(self, size, start, letterbox=False, fill=127, protocol="repo"):
         """(images [B, size, size, 3], valid) of the entries start .. start + B - 1 in list order: DeviceVOC.eval_batch"""
         return self.list_batch("DeviceCOCO.eval_batch", size, start, letterbox, fill, protocol)
+
+
+def train_entries(images, image_dir):
+    """read_instances' images -> the entries of a DeviceBoxes pool, in the same order"""
+    entries = []
+    for im in images:
+        objs = [(x + 1, y + 1, x + w + 1, y + h + 1, int(o["category"]))
+                for o in im["anns"] if not o["iscrowd"] for (x, y, w, h) in (o["bbox"],) if w > 0 and h > 0]
+        entries.append({'imname': os.path.join(image_dir, im["file_name"]), 'shape': (im["height"], im["width"]),
+                        'id': im["id"], 'objs': objs, 'difficult': [0] * len(objs)})
+    return entries
+
+
+class DeviceCOCOTrain(DeviceBoxes):
+    """the training pool of a COCO instances file: DeviceBoxes over train_entries of coco_eval.read_instances' images
+    (ascending image id, restricted to `image_list` where one is given); `classes` are the category names,
+    `category_ids` the original ids and `image_ids` the images', as DeviceCOCO names them"""
+
+    def __init__(self, annotations, image_dir, batch_size, image_list=None, flipped=False, seed=0, rank=0, world=1,
+                 device="cuda", max_pool_bytes=DEFAULT_MAX_POOL_BYTES, augment=None, max_boxes=None, draw=False):
+        from ..utils import coco_eval
+        self._check_lists(max_boxes, draw)
+        self.dataset = coco_eval.read_instances(annotations, image_list)
+        self.category_ids = list(self.dataset["categories"])
+        self.image_ids = [im["id"] for im in self.dataset["images"]]
+        self.image_index = [os.path.splitext(im["file_name"])[0] for im in self.dataset["images"]]
+        self._init_batches(train_entries(self.dataset["images"], image_dir), self.dataset["names"], batch_size, flipped,
+                           seed, rank, world, device, max_pool_bytes, augment, max_boxes, draw)

@@ -28,7 +28,11 @@ of 0.5 in one launch from the pool (y2_letterbox_darknet_batch), Darknet's float
     pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --protocol darknet
 --cfg FILE names the Darknet cfg that goes with --darknet-weights: graph, class count, anchors and widths are the file's
 (YOLOv2Detector.from_cfg); its class count must be the devkit's, since the evaluation stays VOC's.  --names FILE names
-the classes of the --results-dir files."""
+the classes of the --results-dir files.
+
+main(argv, dataset=None) takes the data set through a seam: `dataset(args)` returns the pool -- a DeviceBoxes
+(img_dataset/device_boxes.py) with its `classes` and `image_index` -- where --devkit's DeviceVOC is not the one wanted
+(darknet/detector.py: the valid= list of a .data file); with it --devkit is not required."""
 import argparse
 import sys
 
@@ -36,14 +40,13 @@ import numpy as np
 import torch
 
 from .. import engine
-from ..img_dataset import pascal_voc
 from ..utils import detect_batch
 from . import yolov2_model_flags as model_flags
 
 
-def parse_args(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--devkit", required=True, help="VOCdevkit directory (cfg.PASCAL_PATH)")
+def parse_args(argv=None, need_devkit=True, prog=None):
+    ap = argparse.ArgumentParser(prog=prog)
+    ap.add_argument("--devkit", required=need_devkit, default=None, help="VOCdevkit directory (cfg.PASCAL_PATH)")
     ap.add_argument("--image-set", default="test")
     model_flags.add_model_flags(ap, 32, None, "evaluated", "the image set's class count")
     ap.add_argument("--thresh", type=float, default=0.005, help="score above which a box is a detection")
@@ -90,15 +93,21 @@ def parse_args(argv=None):
     return args
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def voc_dataset(args):
+    """--devkit's pool"""
     from ..img_dataset.device_voc import DeviceVOC
-    imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=False)
+    return DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=False)
+
+
+def main(argv=None, dataset=None):
+    """argv: the command line, or an args record a caller parsed (parse_args) and filled; dataset: see above"""
+    args = argv if isinstance(argv, argparse.Namespace) else parse_args(argv)
+    imdb = (dataset or voc_dataset)(args)
     snapshot, anchors, num_class, bn_eps = model_flags.find_snapshot(args, imdb.num_class)
     if args.cfg_record is not None and num_class != imdb.num_class:     # the evaluation is VOC's
         args.error("--cfg %s has classes=%d, the image set %s has %d classes" %
-                   (args.cfg, num_class, args.image_set, imdb.num_class))
-    names = model_flags.class_names(args.error, args, num_class, pascal_voc.CLASSES[:num_class])
+                   (args.cfg, num_class, getattr(args, "dataset_name", args.image_set), imdb.num_class))
+    names = model_flags.class_names(args.error, args, num_class, imdb.classes[:num_class])
     if num_class != imdb.num_class:
         raise ValueError("snapshot %s: num_class is %d, the image set has %d" % (snapshot, num_class, imdb.num_class))
     detector, restored = model_flags.build_detector(args, snapshot, anchors, num_class, bn_eps)
@@ -106,7 +115,7 @@ def main(argv=None):
                              args.keep_grids, args.per_class, args.max_per_class, args.letterbox, args.fill,
                              protocol=args.protocol)
     for c in sorted(result["aps"]):
-        print('AP for {:s} = {:.4f}'.format(pascal_voc.CLASSES[c], result["aps"][c]))
+        print('AP for {:s} = {:.4f}'.format(imdb.classes[c], result["aps"][c]))
     print('Mean AP = {:.4f} ({:d} images, {:d} detections, VOC{:s} metric)'.format(
         result["mAP"], len(imdb.entries), len(result["rows"]["flag"]), "07" if args.metric == "07" else "10+"))
     if args.per_class:

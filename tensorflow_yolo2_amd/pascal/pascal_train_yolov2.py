@@ -2,7 +2,7 @@
     python -m tensorflow_yolo2_amd.pascal.pascal_train_yolov2 --devkit data/VOCdevkit --iters 20 \
         [--multi-scale] [--augment] [--anchors voc|kmeans] [--ckpt-dir DIR] [--imagenet-ckpt-dir DIR | --darknet-backbone FILE]
         [--topology paper|darknet] [--darknet-weights FILE] [--cfg FILE [--single-scale]] [--region-stats]
-        [--box-labels [--max-boxes 30] [--area-weight] [--prior-images 12800]]
+        [--box-labels [--max-boxes 30] [--area-weight] [--prior-images 12800] [--draw-boxes]]
         [--solver darknet [--lr .001] [--momentum .9] [--decay .0005] [--burn-in 1000] [--power 4]
                           [--policy steps --steps 40000,60000 --scales .1,.1 | --policy poly --max-batches N | --policy constant]]
 The flags are pascal_train_darknet.py's where they apply.  The batches always come from the device-resident pool
@@ -16,6 +16,13 @@ image, so two objects of one cell both reach their anchors; engine.yolov2_loss_b
 Darknet's (2 - w h) weight of the coord terms and --prior-images the number of images (12800 in Darknet) during which
 every prediction without an object is pulled toward its anchor.  The list encoder draws no random numbers, so a resumed
 run moves the data and augmentation streams exactly as without it; the prior's switch reads the snapshot's iteration.
+--draw-boxes (off by default) is Darknet's shuffle-then-cut: an image whose window keeps more than --max-boxes objects
+trains a subset drawn anew every time, not the first ones (augment.encode_box_list_draw; y2_encode_box_list_draw).  Its
+keys come from a stream of their own, one per sample, which a resumed run moves with the other two.
+
+main(argv, dataset=None) takes the data set through a seam: `dataset(args)` returns the pool -- a DeviceBoxes
+(img_dataset/device_boxes.py) -- where --devkit's DeviceVOC is not the one wanted, as darknet/detector.py and
+coco/coco_train_yolov2.py do; with it --devkit is not required.
 
 --solver darknet replaces Adam by Darknet's solver (utils/solver.py; engine.DarknetSGD): momentum SGD, weight decay on
 the convolution filters only, and the rate schedule -- a burn-in lr (t / burn_in)^power, then the policy.  The defaults
@@ -68,14 +75,16 @@ from ..utils.timer import Timer
 from ..yolo2_nets import net_utils, yolov2
 
 
-def parse_args(argv=None):
+def parse_args(argv=None, need_devkit=True, prog=None, draw_boxes=None):
+    """need_devkit=False: a caller that brings its own data set (main's `dataset`); prog: its name in the usage line;
+    draw_boxes: its default of --draw-boxes where the recipe has box labels (None: off)"""
     from ..trainer import MULTI_SCALE_SIZES
-    ap = argparse.ArgumentParser()
+    ap = argparse.ArgumentParser(prog=prog)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=None, help="24, or the batch of --cfg")
     ap.add_argument("--size", type=int, default=None, help="416, or the width of --cfg")
     ap.add_argument("--dtype", default="f16")
-    ap.add_argument("--devkit", required=True, help="VOCdevkit directory (cfg.PASCAL_PATH)")
+    ap.add_argument("--devkit", required=need_devkit, default=None, help="VOCdevkit directory (cfg.PASCAL_PATH)")
     ap.add_argument("--image-set", default="trainval")
     ap.add_argument("--flipped", action="store_true", help="cfg.FLIPPED: append horizontally flipped copies")
     ap.add_argument("--multi-scale", action="store_true", help="input size redrawn every --ms-period iterations")
@@ -119,6 +128,9 @@ def parse_args(argv=None):
     ap.add_argument("--area-weight", action="store_true", help="coord terms times 2 - w h (needs --box-labels)")
     ap.add_argument("--prior-images", type=int, default=None,
                     help="images during which un-owned predictions are pulled toward their anchors (needs --box-labels)")
+    ap.add_argument("--draw-boxes", action="store_true",
+                    help="an image with more than --max-boxes objects keeps a subset drawn anew at every use, Darknet's "
+                         "shuffle-then-cut, not the first ones (needs --box-labels)")
     ap.add_argument("--solver", default="adam", choices=("adam", "darknet"),
                     help="adam: tf.train.AdamOptimizer defaults; darknet: momentum SGD + filter decay + rate schedule")
     ap.add_argument("--lr", type=float, default=None, help="base rate (0.001; needs --solver darknet, as all below)")
@@ -165,6 +177,10 @@ def parse_args(argv=None):
             ap.error("--ms-period must be at least 1")
     if not args.box_labels and (args.area_weight or args.prior_images or args.max_boxes is not None):
         ap.error("--max-boxes, --area-weight and --prior-images need --box-labels")
+    if args.draw_boxes and not args.box_labels:
+        ap.error("--draw-boxes chooses among the objects of the box list: it needs --box-labels")
+    if draw_boxes and args.box_labels:
+        args.draw_boxes = True
     if args.prior_images is None:
         args.prior_images = 0
     if args.max_boxes is None:
@@ -287,26 +303,30 @@ def step_size(args, i):
 
 
 def skip_batches(imdb, batches):
-    """move a fresh DeviceVOC to where it stands after `batches` calls of get(): the order's cursor and reshuffles, and
-    one augmentation row per sample (a row's draws do not depend on the output size)"""
-    n = len(imdb.entries)
+    """move a fresh pool to where it stands after `batches` calls of get(): the order's cursor and reshuffles, one
+    augmentation row per sample (a row's draws do not depend on the output size) and, with the draw, one key"""
     for _ in range(batches * imdb.batch_size):
-        e = imdb._next()['entry']
-        if imdb.augment is not None:
-            imdb.augment.draw(imdb.aug_rng, *imdb.entries[e % n]['shape'])
+        imdb.next_sample()
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def voc_dataset(args):
+    """--devkit's pool"""
     from ..img_dataset.device_voc import DeviceVOC
-    imdb = DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
-                     seed=args.seed, augment=args.augmentation, max_boxes=args.max_boxes if args.box_labels else None)
+    return DeviceVOC(args.image_set, batch_size=args.batch, devkit_path=args.devkit, flipped=args.flipped,
+                     seed=args.seed, augment=args.augmentation, max_boxes=args.max_boxes if args.box_labels else None,
+                     draw=args.draw_boxes)
+
+
+def main(argv=None, dataset=None):
+    """argv: the command line, or an args record a caller parsed (parse_args) and filled; dataset: see above"""
+    args = argv if isinstance(argv, argparse.Namespace) else parse_args(argv)
+    imdb = (dataset or voc_dataset)(args)
     latest = None
     rec = args.cfg_record
     if rec is not None:
         if imdb.num_class != rec.classes:
             args.error("--cfg %s has classes=%d, the image set %s has %d classes" %
-                       (args.cfg, rec.classes, args.image_set, imdb.num_class))
+                       (args.cfg, rec.classes, getattr(args, "dataset_name", args.image_set), imdb.num_class))
         print_recipe(args)
     elif args.darknet_weights:
         args.topology = file_topology(args, imdb.num_class)
