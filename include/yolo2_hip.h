@@ -324,6 +324,49 @@ int y2_yolov2_region_stats(const float* net, const float* truth, const int* ntru
                            int B, int num_class, int max_boxes, float image_size, float* stats, void* workspace,
                            void* stream);
 
+/* ---- The word tree of the region layer (YOLO9000's softmax_tree; specification: utils/word_tree.py; csrc/word_tree.hip).
+ *      The class logits of a head row are the nodes of a tree: a softmax per group of siblings, abs[node] = the product
+ *      of the conditionals on the node's path to a root.  `tables`: device memory, int32 [3 num_class + 2 G] =
+ *      parent[num_class], group[num_class], child[num_class], group_offset[G], group_size[G], as utils/word_tree.py
+ *      pack() writes them; G the group count, max_depth the largest node depth (a root has depth 0).  The host cannot
+ *      check the content of device tables: the kernels cut every value they read from them into its range and bound
+ *      every walk by max_depth + 1 levels, so no table and no truth list makes them read or write outside a head row or
+ *      a table, or spin; with tables pack() did not write the results are unspecified.  Argument errors of all three
+ *      entries, nothing launched, named with the entry and the item: a null pointer, num_class outside
+ *      1..Y2_WORD_TREE_MAX_NODES, G outside 1..num_class, max_depth outside 0..num_class - 1. ------------------------- */
+#define Y2_WORD_TREE_MAX_NODES 65536 /* num_class with a tree; the kernels hold no node in LDS, so this bounds index
+                                        arithmetic only (the executor's 2,048-column row allows 404 at B = 5) */
+/* y2_yolov2_loss_boxes with the class term of the word tree (specification: utils/word_tree.py yolov2_loss_boxes_tree):
+ * cells, best anchor, ownership, the coord / object / noobject parts, `scales`, loss[5], dnet and the workspace are that
+ * entry's, with its argument errors.  An owned slot whose class k lies in [0, num_class) takes, for each node a of k,
+ * parent[k], ... up to a root (at most max_depth + 1 nodes) with g = group[a], class_scale (lse_g - logit[a]) into the
+ * class part and class_scale (softmax_g - onehot(a)) / batch into the gradient of g's members; every other class entry
+ * of dnet is 0.  Any node may be a truth, an inner one too.  A class index outside [0, num_class) takes no class term.
+ * Every gradient row is written with consecutive lanes on consecutive floats; partial sums are added in a fixed order:
+ * the result does not vary from run to run.  One launch + the finalize. */
+size_t y2_yolov2_loss_boxes_tree_workspace_bytes(int batch, int S, int B);
+int y2_yolov2_loss_boxes_tree(const float* net, const float* truth, const int* ntruth, const float* anchors,
+                              const int* tables, int batch, int S, int B, int num_class, int G, int max_depth,
+                              int max_boxes, float image_size, const float* scales, float* loss, float* dnet,
+                              void* workspace, void* stream);
+/* y2_yolov2_region_stats with stats[1] = the mean of abs[class] over the truths whose class lies in [0, num_class)
+ * (specification: utils/word_tree.py region_stats_boxes_tree; Darknet's avg_cat).  Everything else, the workspace
+ * (y2_yolov2_region_stats_workspace_bytes) and the argument errors are that entry's. */
+int y2_yolov2_region_stats_tree(const float* net, const float* truth, const int* ntruth, const float* anchors,
+                                const int* tables, int batch, int S, int B, int num_class, int G, int max_depth,
+                                int max_boxes, float image_size, float* stats, void* workspace, void* stream);
+/* The detection head of a tree (specification: utils/word_tree.py word_tree_head): net [rows][5 + num_class], rows =
+ * batch * S * S * B -> out of the same shape: elements 0..4 bit-identical copies, the class logits replaced by 0.0f at
+ * `top` and -inf everywhere else.  top: start at the root group with p = 1; j = the first maximum of the group; while
+ * p cond[j] > tree_thresh take it (p *= cond[j]) and go on in j's child group, j itself where it is a leaf; where the
+ * product does not pass, the answer is the node taken last -- or j, with p = cond[j], in the root group, which always
+ * answers.  Optional outputs (NULL: not written): top int32 [rows], prob [rows] = abs[top], multiplied root first.
+ * out == net (in place) is allowed and gives the same bits.  Every detect entry reads such a row unchanged and exactly:
+ * its softmax finds maximum 0 and sum 1, so the score is sig(to) at top and 0 elsewhere.  One launch, a wave per row.
+ * Y2_ERR_ARG also: rows < 1, tree_thresh outside [0, 1). */
+int y2_word_tree_head(const float* net, const int* tables, int rows, int num_class, int G, int max_depth,
+                      float tree_thresh, float* out, int* top, float* prob, void* stream);
+
 /* ---- ResNet-50 backbone swap (src/yolo2_nets/tf_resnet.py:12-32, src/pascal/pascal_train_resnet.py:37-50):
  *      graph-level operators on fp32 NHWC tensors that the conv-BN-leaky stacks do not have.  The 1x1 / 3x3
  *      convolutions of the bottleneck units (slim_dir/nets/resnet_v1.py:68-112) go through y2_conv2d /

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "anchor_decode.h"
+#include "region_math.h"
 #include "../../include/yolo2_hip.h"
 
 #include <stdarg.h>
@@ -274,14 +275,7 @@ struct V2LossArgs {
 };
 constexpr int kV2MaxTruth = 1024;
 
-Y2_DEV float v2_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-Y2_DEV float v2_iou(float ax, float ay, float aw, float ah, float bx, float by, float bw, float bh) {
-    const float iw = fmaxf(0.0f, fminf(ax + aw / 2, bx + bw / 2) - fmaxf(ax - aw / 2, bx - bw / 2));
-    const float ih = fmaxf(0.0f, fminf(ay + ah / 2, by + bh / 2) - fmaxf(ay - ah / 2, by - bh / 2));
-    const float inter = iw * ih;
-    const float uni = aw * ah + bw * bh - inter;
-    return uni > 0.0f ? inter / uni : 0.0f;
-}
+// v2_sigmoid, v2_iou: region_math.h
 
 __global__ __launch_bounds__(256) void yolov2_loss_kernel(V2LossArgs a) {
     __shared__ float tr[kV2MaxTruth][4];
@@ -546,10 +540,7 @@ struct V2RegionStatsArgs {
     float image_size;
 };
 
-// components 0..3 are float bit patterns, 4..7 integers
-__device__ __forceinline__ int v2_stats_add(int k, int a, int b) {
-    return k < 4 ? __float_as_int(__int_as_float(a) + __int_as_float(b)) : a + b;
-}
+// v2_stats_add (components 0..3 are float bit patterns, 4..7 integers): region_math.h
 
 __global__ __launch_bounds__(256) void yolov2_region_stats_kernel(V2RegionStatsArgs a) {
     __shared__ int red[8][256];

@@ -19,8 +19,10 @@ map      VOC AP per class and its mean over the valid= list's own label files: p
 anchors  utils/anchors.kmeans_anchors over box_table_wh of the train= list at --size, printed as a cfg `anchors=` line with
          its mean_shape_iou.  Host only.
 
-classes= of the .data file, the cfg's classes and the line count of names= must agree: a disagreement is an argument error
-that names the two files.  One process, one GPU."""
+classes= of the .data file, the cfg's classes, the node count of the cfg's softmax_tree (a word tree: the label files'
+classes are node indices) and the line count of names= must agree: a disagreement is an argument error that names the two
+files.  --tree FILE and --hier-thresh X behind the positionals beat the cfg's softmax_tree and tree_thresh in train, valid
+and map.  One process, one GPU."""
 import argparse
 import os
 import sys
@@ -64,6 +66,15 @@ def read_data_set(error, data_path, cfg_path=None, need=()):
             error("%s" % e)
         if rec.classes != data.classes:
             error("%s has classes=%d, %s has classes=%d" % (data_path, data.classes, cfg_path, rec.classes))
+        if rec.tree is not None:               # a word tree: the data set's classes are its nodes
+            from ..yolo2_nets import yolov2
+            try:
+                tree = yolov2.load_cfg_tree(rec)
+            except (OSError, ValueError) as e:
+                error("%s" % e)
+            if tree.n != data.classes:
+                error("%s has classes=%d, the word tree %s of %s holds %d nodes" % (data_path, data.classes, tree.path,
+                                                                                  cfg_path, tree.n))
     return data, names, rec
 
 

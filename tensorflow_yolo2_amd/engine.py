@@ -1082,6 +1082,87 @@ def yolov2_region_stats(net, truth, ntruth, anchors, image_size, out=None):
     return out
 
 
+class WordTreeTables:
+    """the word tree of a region layer on the device (utils/word_tree.py): the record's packed int32 tables, uploaded
+    once, with the counts the entries take next to them.  `tree`: a utils.word_tree.WordTree record"""
+
+    def __init__(self, tree, device="cuda:0"):
+        from .utils import word_tree
+        self.tree, self.n, self.groups, self.max_depth = tree, int(tree.n), word_tree.groups(tree), int(tree.max_depth)
+        self.tables = torch.as_tensor(word_tree.pack(tree)).to(device).contiguous()
+
+
+def _tree(tree, c, device):
+    """tree: WordTreeTables on the device of the call, of exactly c nodes"""
+    assert isinstance(tree, WordTreeTables) and tree.tables.device == device, "tree"
+    if tree.n != c:
+        raise ValueError("the word tree holds %d nodes, the head %d classes" % (tree.n, c))
+    return tree
+
+
+def yolov2_loss_boxes_tree(net, truth, ntruth, anchors, image_size, tree, need_grad=True, scales=None):
+    """yolov2_loss_boxes with the class term of the word tree (utils/word_tree.py yolov2_loss_boxes_tree): the same
+    tensors, scales and results; tree: WordTreeTables of C nodes; a truth's class is a node index, any node"""
+    lib = _lib.load()
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, s, _, b, d = net.shape
+    tree = _tree(tree, d - 5, net.device)
+    assert truth.is_cuda and truth.dtype == torch.float32 and truth.is_contiguous(), (truth.dtype, truth.device)
+    assert truth.dim() == 3 and truth.shape[0] == n and truth.shape[2] == 5, truth.shape
+    assert ntruth.is_cuda and ntruth.dtype == torch.int32 and ntruth.is_contiguous() and tuple(ntruth.shape) == (n,)
+    an = _anchors(anchors, b, net.device)
+    sc = None
+    if scales is not None:
+        unknown = set(scales) - set(BOX_LOSS_SCALES)
+        if unknown:
+            raise ValueError("unknown loss scales %s" % sorted(unknown))
+        sc = (C.c_float * 7)(*[float(scales.get(k, v)) for k, v in zip(BOX_LOSS_SCALES, _BOX_LOSS_DEFAULTS)])   # host memory
+    loss = torch.empty(5, dtype=torch.float32, device=net.device)
+    dnet = torch.empty_like(net) if need_grad else None
+    ws = torch.empty(lib.y2_yolov2_loss_boxes_tree_workspace_bytes(n, s, b), dtype=torch.uint8, device=net.device)
+    check(lib.y2_yolov2_loss_boxes_tree(_ptr(net), _ptr(truth), _ptr(ntruth), _ptr(an), _ptr(tree.tables), n, s, b, d - 5,
+                                        tree.groups, tree.max_depth, int(truth.shape[1]), float(image_size), sc,
+                                        _ptr(loss), _ptr(dnet), _ptr(ws), _stream()))
+    return loss, dnet
+
+
+def yolov2_region_stats_tree(net, truth, ntruth, anchors, image_size, tree, out=None):
+    """yolov2_region_stats with the class statistic of the word tree (utils/word_tree.py region_stats_boxes_tree): the mean
+    of abs[class] over the truths; tree: WordTreeTables of C nodes"""
+    lib = _lib.load()
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, s, _, b, d = net.shape
+    tree = _tree(tree, d - 5, net.device)
+    assert truth.is_cuda and truth.dtype == torch.float32 and truth.is_contiguous(), (truth.dtype, truth.device)
+    assert truth.dim() == 3 and truth.shape[0] == n and truth.shape[2] == 5, truth.shape
+    assert ntruth.is_cuda and ntruth.dtype == torch.int32 and ntruth.is_contiguous() and tuple(ntruth.shape) == (n,)
+    an = _anchors(anchors, b, net.device)
+    out = _own(out, (6,), torch.float32, net.device, numel=6)
+    ws = torch.empty(lib.y2_yolov2_region_stats_workspace_bytes(n), dtype=torch.uint8, device=net.device)
+    check(lib.y2_yolov2_region_stats_tree(_ptr(net), _ptr(truth), _ptr(ntruth), _ptr(an), _ptr(tree.tables), n, s, b, d - 5,
+                                          tree.groups, tree.max_depth, int(truth.shape[1]), float(image_size), _ptr(out),
+                                          _ptr(ws), _stream()))
+    return out
+
+
+def word_tree_head(net, tree, tree_thresh=0.5, out=None, want_top=False):
+    """the detection head of a word tree (utils/word_tree.py word_tree_head): net [..., 5+C] fp32 -> the same shape with
+    elements 0..4 copied and the class logits 0 at the predicted node, -inf elsewhere, which every detect entry reads as
+    score sig(to) at that node (in `out` if given; out = net rewrites in place).  want_top: -> (out, top int32 [rows],
+    prob [rows] = abs[top]).  tree: WordTreeTables of C nodes"""
+    lib = _lib.load()
+    _dev(net, torch.float32, "net")
+    d = int(net.shape[-1])
+    tree = _tree(tree, d - 5, net.device)
+    rows = net.numel() // d
+    out = _own(out, net.shape, torch.float32, net.device, numel=net.numel())
+    top = torch.empty(rows, dtype=torch.int32, device=net.device) if want_top else None
+    prob = torch.empty(rows, dtype=torch.float32, device=net.device) if want_top else None
+    check(lib.y2_word_tree_head(_ptr(net), _ptr(tree.tables), rows, d - 5, tree.groups, tree.max_depth, float(tree_thresh),
+                                _ptr(out), _ptr(top), _ptr(prob), _stream()))
+    return (out, top, prob) if want_top else out
+
+
 def nms(boxes, scores, classes=None, iou_thresh=0.5, score_thresh=0.0, max_out=100, class_aware=False):
     """boxes [N,K,4], scores [N,K] (, classes [N,K] int32) -> keep [N,max_out] int32 (-1 padded), count [N]"""
     lib = _lib.load()

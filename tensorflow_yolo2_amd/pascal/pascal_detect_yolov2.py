@@ -20,7 +20,9 @@ A file of tiny-yolo-voc.cfg is taken the same way: its float count says so (net_
 "tiny" topology is built with that graph's published anchors.  --cfg FILE names the Darknet cfg that goes with the
 `.weights` file instead: the graph, the class count, the anchors and the widths are the file's (utils/darknet_cfg.py;
 YOLOv2Detector.from_cfg), so the COCO models load -- `--cfg yolov2.cfg --darknet-weights yolov2.weights --names coco.names`
--- and --names FILE writes each detection under its class name (one per line; the count must be the model's)."""
+-- and --names FILE writes each detection under its class name (one per line; the count must be the model's).  --tree FILE
+(or softmax_tree= of --cfg) runs a word-tree model: a detection is the node where the walk down the tree stops at
+--hier-thresh (tree_thresh of --cfg, else 0.5), written under --names, else under the tree's label of that node."""
 import argparse
 import sys
 
@@ -76,6 +78,8 @@ def main(argv=None):
     snapshot, anchors, num_class, bn_eps = model_flags.find_snapshot(args, len(pascal_voc.CLASSES))
     detector, restored = model_flags.build_detector(args, snapshot, anchors, num_class, bn_eps)
     names = pascal_voc.CLASSES if num_class == len(pascal_voc.CLASSES) else [str(c) for c in range(num_class)]
+    if args.tree_record is not None:          # a word tree: a detection is a node, named by its label
+        names = list(args.tree_record.labels)
     names = model_flags.class_names(args.error, args, num_class, names)
     n, entries = args.batch, len(pool.entries)
     grids = []

@@ -28,7 +28,9 @@ of 0.5 in one launch from the pool (y2_letterbox_darknet_batch), Darknet's float
     pascal_eval_yolov2 --devkit data/VOCdevkit --darknet-weights yolov2-voc.weights --protocol darknet
 --cfg FILE names the Darknet cfg that goes with --darknet-weights: graph, class count, anchors and widths are the file's
 (YOLOv2Detector.from_cfg); its class count must be the devkit's, since the evaluation stays VOC's.  --names FILE names
-the classes of the --results-dir files.
+the classes of the --results-dir files.  --tree FILE (or softmax_tree= of --cfg) scores a word-tree model: every row's
+only class is the node where the walk down the tree stops at --hier-thresh (tree_thresh of --cfg, else 0.5;
+engine.word_tree_head), its score the objectness, and a detection matches a truth by equal node.
 
 main(argv, dataset=None) takes the data set through a seam: `dataset(args)` returns the pool -- a DeviceBoxes
 (img_dataset/device_boxes.py) with its `classes` and `image_index` -- where --devkit's DeviceVOC is not the one wanted

@@ -64,6 +64,12 @@ set's class count must be the file's.
 line: `Region Avg IOU, Class, Obj, No Obj, Avg Recall, count`, computed on the device from the step's head output and its
 box list (engine.yolov2_region_stats; utils/region_loss.py region_stats_boxes).
 
+--tree FILE (or softmax_tree= of --cfg; the flag beats the file) trains a word tree (utils/word_tree.py): the classes are
+the tree's nodes, a truth's class is a node index -- any node, an inner one too -- and the class loss is the softmax per
+group of siblings along the truth's path to the root (engine.yolov2_loss_boxes_tree); --region-stats then prints the mean
+abs[class] as Class (engine.yolov2_region_stats_tree).  It needs the box list (--box-labels or --cfg); --hier-thresh is
+kept for the detector.
+
 One process, one GPU."""
 import argparse
 import os
@@ -71,6 +77,7 @@ import os
 import numpy as np
 import torch
 
+from . import yolov2_model_flags as model_flags
 from ..utils.timer import Timer
 from ..yolo2_nets import net_utils, yolov2
 
@@ -117,6 +124,7 @@ def parse_args(argv=None, need_devkit=True, prog=None, draw_boxes=None):
                          "multi-scale on random=1, the file's jitter / hue / saturation / exposure / solver values / width "
                          "/ batch); a flag given on the command line beats the file.  Not with --topology paper, "
                          "--imagenet-ckpt-dir, --anchors or .npz snapshots")
+    model_flags.add_tree_flags(ap)
     ap.add_argument("--single-scale", action="store_true", help="with --cfg: one input size even where random=1")
     ap.add_argument("--region-stats", action="store_true",
                     help="print Darknet's region-layer line (Avg IOU, Class, Obj, No Obj, Avg Recall, count) of the last "
@@ -264,6 +272,9 @@ def apply_cfg(ap, args):
     args.anchors = pick(args.anchors, "voc")
     if args.region_stats and not args.box_labels:
         ap.error("--region-stats reads the box list: it needs --box-labels or --cfg")
+    model_flags.resolve_tree(ap, args)
+    if args.tree_record is not None and not args.box_labels:
+        ap.error("a word tree trains on the box list (a truth's class is a node): it needs --box-labels or --cfg")
 
 
 def print_recipe(args):
@@ -328,7 +339,8 @@ def main(argv=None, dataset=None):
             args.error("--cfg %s has classes=%d, the image set %s has %d classes" %
                        (args.cfg, rec.classes, getattr(args, "dataset_name", args.image_set), imdb.num_class))
         print_recipe(args)
-    elif args.darknet_weights:
+    model_flags.check_tree(args.error, args, imdb.num_class)
+    if rec is None and args.darknet_weights:
         args.topology = file_topology(args, imdb.num_class)
     darknet = args.topology in yolov2.DARKNET_FILE_TOPOLOGIES
     if args.ckpt_dir:
@@ -359,12 +371,13 @@ def main(argv=None, dataset=None):
         bn_eps = net_utils.read_yolov2_bn_eps(latest)
     if rec is not None:
         trainer = yolov2.YOLOv2DarknetTrainer.from_cfg(rec, args.batch, first, dtype=args.dtype, seed=args.seed,
-                                                       solver=args.solver_record, prior_images=args.prior_images)
+                                                       solver=args.solver_record, prior_images=args.prior_images,
+                                                       tree=args.tree_record, tree_thresh=args.hier_thresh)
     else:
         trainer = TRAINERS[args.topology](args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
                                           seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,
                                           prior_images=args.prior_images, solver=args.solver_record, bn_eps=bn_eps,
-                                          topology=args.topology)
+                                          topology=args.topology, tree=args.tree_record, tree_thresh=args.hier_thresh)
     last_iter_num = 0
     if latest:
         print('Restorining model snapshots from {:s}'.format(latest))

@@ -25,6 +25,45 @@ def add_model_flags(ap, batch, batch_help, latest_is, darknet_classes):
     ap.add_argument("--names", default=None,
                     help="a Darknet .names file, one class name per line: the names the detections are written under.  Its "
                          "line count must be the model's class count")
+    add_tree_flags(ap)
+
+
+def add_tree_flags(ap):
+    """--tree and --hier-thresh, next to --cfg in every script that builds a YOLOv2 model"""
+    ap.add_argument("--tree", default=None,
+                    help="a word-tree file (`label parent` per line; utils/word_tree.py): the classes are its nodes, the "
+                         "class softmax runs per group of siblings and a detection is the node where the walk down the "
+                         "tree stops.  Beats softmax_tree of --cfg; its node count must be the model's class count")
+    ap.add_argument("--hier-thresh", type=float, default=None,
+                    help="where a detection's walk down the tree stops, in [0, 1): tree_thresh of --cfg, else 0.5")
+
+
+def resolve_tree(ap, args):
+    """behind the cfg: args.tree_record = the utils.word_tree.WordTree of --tree, else of the cfg's softmax_tree, else
+    None; args.hier_thresh = the flag, else the cfg's tree_thresh, else 0.5"""
+    from ..utils import word_tree
+    rec = args.cfg_record
+    args.tree_record = None
+    try:
+        if args.tree:
+            args.tree_record = word_tree.load(args.tree)
+        elif rec is not None:
+            args.tree_record = yolov2.load_cfg_tree(rec)
+    except (OSError, ValueError) as e:
+        ap.error("%s: %s" % ("--tree" if args.tree else "--cfg", e))
+    if args.hier_thresh is None:
+        args.hier_thresh = rec.tree_thresh if rec is not None else 0.5
+    if not 0.0 <= args.hier_thresh < 1.0:
+        ap.error("--hier-thresh %g: a number in [0, 1)" % args.hier_thresh)
+    if rec is not None and args.tree_record is not None and args.tree_record.n != rec.classes:
+        ap.error("--tree %s holds %d nodes, --cfg %s has classes=%d" % (args.tree, args.tree_record.n, args.cfg, rec.classes))
+
+
+def check_tree(error, args, num_class):
+    """the tree's nodes are the model's classes"""
+    if args.tree_record is not None and args.tree_record.n != num_class:
+        error("the word tree %s holds %d nodes, the model has %d classes" % (args.tree_record.path, args.tree_record.n,
+                                                                             num_class))
 
 
 def resolve_cfg(ap, args):
@@ -46,6 +85,7 @@ def resolve_cfg(ap, args):
             args.size = args.cfg_record.size
     if args.size is None:
         args.size = 416
+    resolve_tree(ap, args)
     if args.names:
         from ..utils import darknet_cfg
         try:
@@ -56,6 +96,7 @@ def resolve_cfg(ap, args):
 
 def class_names(ap_error, args, num_class, default):
     """the names the detections are written under: --names (its count must be num_class), else `default`"""
+    check_tree(ap_error, args, num_class)
     if args.class_names is None:
         return default
     if len(args.class_names) != num_class:
@@ -100,8 +141,10 @@ def find_snapshot(args, num_class):
 def build_detector(args, snapshot, anchors, num_class, bn_eps):
     """the detector of find_snapshot's answer, filled from --darknet-weights or from the snapshot -> (detector, the
     snapshot's iteration or 0)"""
+    check_tree(args.error, args, num_class)
     if args.cfg_record is not None:
-        detector = yolov2.YOLOv2Detector.from_cfg(args.cfg_record, args.batch, args.size, dtype=args.dtype)
+        detector = yolov2.YOLOv2Detector.from_cfg(args.cfg_record, args.batch, args.size, dtype=args.dtype,
+                                                  tree=args.tree_record, tree_thresh=args.hier_thresh)
         if args.darknet_weights:
             print('Restorining model from Darknet weight file {:s} (cfg {:s}, topology {:s})'.format(
                 args.darknet_weights, args.cfg, detector.topology))
@@ -112,7 +155,8 @@ def build_detector(args, snapshot, anchors, num_class, bn_eps):
         topology = net_utils.darknet_file_topology(args.darknet_weights, num_class, len(anchors), args.width_div)
         anchors = yolov2._TOPOLOGY[topology].anchors
     detector = yolov2.YOLOv2Detector(args.batch, args.size, num_class=num_class, anchors=anchors, dtype=args.dtype,
-                                     width_div=args.width_div, bn_eps=bn_eps, topology=topology)
+                                     width_div=args.width_div, bn_eps=bn_eps, topology=topology, tree=args.tree_record,
+                                     tree_thresh=args.hier_thresh)
     restored = 0
     if args.darknet_weights:
         print('Restorining model from Darknet weight file {:s} (topology {:s})'.format(args.darknet_weights, topology))

@@ -7,7 +7,9 @@ list.  The first section is `[net]` or `[network]`; every later section is one D
 order.  `[route]` indices count in that numbering, a negative one relative to the route's own position.
 
 Sections understood: `[convolutional]` (stride 1, pad 1, leaky or linear), `[maxpool]` (2 / 2 or 2 / 1), `[route]` (one or
-two indices), `[reorg]` (stride 2) and a last `[region]` (coords 4, softmax 1, bias_match 1, rescore 1).  Everything else
+two indices), `[reorg]` (stride 2) and a last `[region]` (coords 4, softmax 1, bias_match 1, rescore 1; `softmax_tree`, the
+path of a word-tree file as written -- utils/word_tree.py reads it, yolo2_nets/yolov2.py finds it -- and `tree_thresh` in
+[0, 1); `map` is refused: it belongs with YOLO9000's wide head).  Everything else
 -- another section, another value, an unknown key of a section that is understood, a value that does not parse -- raises a
 ValueError naming the file, the line, the layer and the item: a silently ignored key is how a model ends up trained
 differently from what its file says.
@@ -40,9 +42,11 @@ Augmentation = collections.namedtuple("Augmentation", "jitter hue saturation exp
 # augmentation: jitter (of [region]) and hue / saturation / exposure (of [net]); anchors: ((w, h), ...) in cells of stride
 # 32; scales: ((name, value), ...) of coord_scale, object_scale, noobject_scale, class_scale, thresh; size, batch,
 # subdivisions, max_batches, random: of [net] / [region]; file_layers: [(k, c, n, batch_norm)] in file order, the form
-# utils/darknet_weights.split takes; floats: their float count
+# utils/darknet_weights.split takes; floats: their float count; tree: softmax_tree as written (None: no word tree);
+# tree_thresh: where a detection's walk down the tree stops (0.5 when absent, the default of Darknet's -hier)
 DarknetCfg = collections.namedtuple("DarknetCfg", "path layers solver augmentation anchors classes num scales size batch "
-                                                  "subdivisions max_batches random file_layers floats")
+                                                  "subdivisions max_batches random file_layers floats tree tree_thresh",
+                                    defaults=(None, 0.5))
 
 # what compile_graph returns: shape "chain" / "passthrough"; specs: the stacks in networks() order, each a tuple of
 # (k, in, out, pool) at the widths that RUN; file_layers as above; centre_tap: the stem layers that are 1x1 in the file
@@ -148,7 +152,7 @@ class _Options(object):
 
 
 _REQUIRED = object()
-REFUSED_REGION_KEYS = ("softmax_tree", "map", "tree_thresh")
+REFUSED_REGION_KEYS = ("map",)
 
 
 def _parse_net(o):
@@ -187,7 +191,8 @@ def _parse_net(o):
 def _parse_region(o):
     for key in REFUSED_REGION_KEYS:
         if key in o.entries:
-            o.fail(o.entries[key][1], o.where, "%s=%s: the word tree of YOLO9000 is not built" % (key, o.entries[key][0]))
+            o.fail(o.entries[key][1], o.where, "%s=%s: the class map of YOLO9000 belongs with its 28,269-wide head and is "
+                   "not built" % (key, o.entries[key][0]))
     classes, num = o.int("classes", 20), o.int("num", 1)
     if classes < 1 or num < 1:
         o.fail(o.line, o.where, "classes=%d, num=%d: both at least 1" % (classes, num))
@@ -204,9 +209,15 @@ def _parse_region(o):
     o.int("absolute", 0)                                      # accepted, not used
     scales = tuple((k, o.float(k, 0.5 if k == "thresh" else 1.0)) for k in SCALE_KEYS)
     jitter = o.float("jitter", 0.2)
+    tree = o.word("softmax_tree", None)
+    if tree is not None and not tree:
+        o.fail(o.line_of("softmax_tree"), o.where, "softmax_tree= names no file")
+    tree_thresh = o.float("tree_thresh", 0.5)
+    if not 0.0 <= tree_thresh < 1.0:
+        o.fail(o.line_of("tree_thresh"), o.where, "tree_thresh=%s: a number in [0, 1)" % tree_thresh)
     o.done()
     return dict(classes=classes, num=num, anchors=tuple(zip(anchors[0::2], anchors[1::2])), random=random, scales=scales,
-                jitter=jitter)
+                jitter=jitter, tree=tree, tree_thresh=tree_thresh)
 
 
 def _parse_layer(o, kind, index, fail):
@@ -272,7 +283,8 @@ def parse(text, path="<cfg>"):
                          augmentation=Augmentation(region["jitter"], hue, saturation, exposure), anchors=region["anchors"],
                          classes=region["classes"], num=region["num"], scales=region["scales"], size=net["size"],
                          batch=net["batch"], subdivisions=net["subdivisions"], max_batches=net["max_batches"],
-                         random=region["random"], file_layers=(), floats=0)
+                         random=region["random"], file_layers=(), floats=0, tree=region["tree"],
+                         tree_thresh=region["tree_thresh"])
     graph = compile_graph(partial)
     return partial._replace(file_layers=graph.file_layers, floats=sum(layer_floats(l) for l in graph.file_layers))
 

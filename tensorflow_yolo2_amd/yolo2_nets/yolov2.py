@@ -3,7 +3,8 @@ a-x2; the north star's model): Darknet-19 up to the 26x26x512 activation, 2x2 ma
 layers and two 3x3 head convolutions, the stride-2 passthrough (reorg 26x26x512 -> 13x13x2048, concatenated
 with the 13x13x1024 path), a 3x3 convolution 3072 -> 1024, the 1x1 output convolution to B*(5+C) channels,
 anchor-box decode and per-image NMS.  Every layer is the reference's conv-BN-leaky type (darknet.py:39-46),
-so the three stacks are `engine.Network` contexts; the glue ops are csrc/ext.hip.
+so the three stacks are `engine.Network` contexts; the glue ops are csrc/ext.hip.  With `tree=` (a utils.word_tree.WordTree)
+the class logits are the nodes of a word tree: csrc/word_tree.hip holds its loss, its statistics and its detection head.
 `YOLOv2Detector` is the inference graph, `YOLOv2Trainer` the train step: anchor-box loss (csrc/ext.hip
 yolov2_loss_kernel, specification oracle/ext_ref.py), backward through the head, the passthrough concat, the
 13x13 stack, the 2x2 pool and the stem, Adam (or, with `solver`, Darknet's SGD: utils/solver.py) on the three flat
@@ -157,6 +158,35 @@ def _cfg_topology(record, dtype):
     return topo, record
 
 
+def load_cfg_tree(record):
+    """the word tree a cfg names (softmax_tree) -> a utils.word_tree.WordTree, or None where it names none.  The path is
+    tried as written against the working directory, then against the cfg's directory; the tree must hold exactly the
+    cfg's `classes` nodes"""
+    import os
+    from ..utils import word_tree
+    if record.tree is None:
+        return None
+    tried = [record.tree, os.path.join(os.path.dirname(record.path), record.tree)]
+    found = next((p for p in tried if os.path.isfile(p)), None)
+    if found is None:
+        raise ValueError("%s: softmax_tree=%s: no such file, neither %s nor %s" % (record.path, record.tree, tried[0],
+                                                                                   tried[1]))
+    tree = word_tree.load(found)
+    if tree.n != record.classes:
+        raise ValueError("%s: softmax_tree=%s holds %d nodes, classes=%d" % (record.path, record.tree, tree.n,
+                                                                             record.classes))
+    return tree
+
+
+def _device_tree(tree, num_class, device):
+    """tree: None, or a utils.word_tree.WordTree of num_class nodes -> its tables on the device"""
+    if tree is None:
+        return None
+    if tree.n != num_class:
+        raise ValueError("the word tree holds %d nodes, the model %d classes" % (tree.n, num_class))
+    return E.WordTreeTables(tree, device)
+
+
 def _build_stacks(topo, specs, batch, size, dtype, device, bn_eps, training, seed, share_with=None):
     """the stack contexts of one input size, in networks() order.  share_with: the contexts of another size, whose
     parameters these are bound to; without it every stack draws its initial values from seed + its position"""
@@ -210,10 +240,13 @@ class YOLOv2Detector:
     RGB in [0, 1]: uint8 BGR batches are converted by engine.u8_to_darknet_input, float input is taken as that already.
     "tiny": the graph of tiny-yolo-voc.cfg, Darknet's second VOC model (yolov2_tiny_specs; anchors ANCHORS_TINY_VOC) --
     two stacks with Darknet's stride-1 pool between them, no passthrough, the input, epsilon and last layer of "darknet".
-    bn_eps: the batch-norm epsilon of every stack (None: the context's default 1e-3, or 1e-6 on "darknet" / "tiny")."""
+    bn_eps: the batch-norm epsilon of every stack (None: the context's default 1e-3, or 1e-6 on "darknet" / "tiny").
+    tree: a utils.word_tree.WordTree of num_class nodes (None: the flat softmax) -- every detect method then rewrites the
+    head through engine.word_tree_head (one launch between the forward pass and the rows): a row's only class is the node
+    where the walk down the tree stops at tree_thresh, its score the objectness."""
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
-                 device="cuda:0", width_div=1, topology="paper", bn_eps=None, _cfg=None):
+                 device="cuda:0", width_div=1, topology="paper", bn_eps=None, tree=None, tree_thresh=0.5, _cfg=None):
         assert image_size % 32 == 0
         # _cfg: (topology record, cfg record) of from_cfg -- the graph of a file under the name of its shape
         self._topo, self.cfg = _cfg if _cfg is not None else (_topology(topology), None)
@@ -224,6 +257,7 @@ class YOLOv2Detector:
         self.B, self.width_div = len(self.anchors), width_div
         self.iteration = 0                                   # of the snapshot last restored (net_utils)
         self.anchors_dev = torch.as_tensor(self.anchors).to(device).contiguous()
+        self.tree, self.tree_thresh = _device_tree(tree, num_class, device), float(tree_thresh)
         specs = self._topo.specs(num_class, self.B, width_div)
         self._stacks = _build_stacks(self._topo, specs, batch, image_size, dtype, device, self.bn_eps, False, seed)
         self.stem, self.head = self._stacks[0], self._stacks[-1]
@@ -234,13 +268,17 @@ class YOLOv2Detector:
         self._buffers = _make_buffers(self._topo, self._stacks, batch, image_size)
 
     @classmethod
-    def from_cfg(cls, record_or_path, batch, image_size=None, dtype="f16", seed=0, device="cuda:0"):
+    def from_cfg(cls, record_or_path, batch, image_size=None, dtype="f16", seed=0, device="cuda:0", tree=None,
+                 tree_thresh=None):
         """the detector of a Darknet cfg (utils/darknet_cfg.py: a record or a file): its graph, widths, class count and
-        anchors; image_size defaults to the file's width.  net_utils.load_darknet_weights fills it from the `.weights`
+        anchors, its word tree (load_cfg_tree) and tree_thresh; image_size defaults to the file's width; tree /
+        tree_thresh: a caller's own in place of the file's.  net_utils.load_darknet_weights fills it from the `.weights`
         file that goes with the cfg"""
         topo, record = _cfg_topology(record_or_path, dtype)
         return cls(batch, record.size if image_size is None else image_size, num_class=record.classes,
-                   anchors=record.anchors, dtype=dtype, seed=seed, device=device, _cfg=(topo, record))
+                   anchors=record.anchors, dtype=dtype, seed=seed, device=device,
+                   tree=load_cfg_tree(record) if tree is None else tree,
+                   tree_thresh=record.tree_thresh if tree_thresh is None else tree_thresh, _cfg=(topo, record))
 
     def networks(self):
         """the stack contexts: (stem, 13x13 stack, head), or on the "darknet" topology (stem, 13x13 stack, route, head)
@@ -253,9 +291,15 @@ class YOLOv2Detector:
         out, _fine = _forward(self._topo, self._stacks, self._buffers, images, False, False, out=out)
         return out.view(self.batch, self.S, self.S, self.B, 5 + self.num_class)
 
+    def _tree_head(self, grid, keep_raw=False):
+        """the head the rows read: `grid` itself, or with a word tree its rewrite (in place unless keep_raw)"""
+        if self.tree is None:
+            return grid
+        return E.word_tree_head(grid, self.tree, self.tree_thresh, out=None if keep_raw else grid)
+
     def detect(self, images, score_thresh=0.3, iou_thresh=0.45, max_out=100, class_aware=True):
         """-> boxes [N,K,4] (cx,cy,w,h relative), best score [N,K], class id [N,K], keep [N,max_out], count [N]"""
-        grid = self.forward(images)
+        grid = self._tree_head(self.forward(images))
         boxes, scores = E.decode_anchors(grid.contiguous(), self.anchors)
         best, cls = E.class_argmax(scores)
         keep, count = E.nms(boxes, best, cls, iou_thresh, score_thresh, max_out, class_aware)
@@ -266,10 +310,11 @@ class YOLOv2Detector:
         """evaluation: images_u8 [N,size,size,3] uint8 BGR (DeviceVOC.eval_batch), table / index the pool's entry table
         and the slots' entries -> (det int32 [N,max_out,6], score [N,max_out], count [N]) in the 1-based pixels of each
         ORIGINAL image: the forward pass on the moving statistics, then ONE launch from the raw head
-        (engine.detect_anchor_batch) -- rows that engine.voc_match_batch reads.  grid_out: keeps the raw head there.
+        (engine.detect_anchor_batch) -- rows that engine.voc_match_batch reads.  grid_out: keeps the raw head there
+        (with a word tree too: the rewritten head then goes to a tensor of its own).
         letterbox: images_u8 is a letterboxed batch (DeviceVOC.eval_batch(..., letterbox=True)) and the boxes are
         un-mapped from each picture's rectangle."""
-        grid = self.forward(images_u8, out=grid_out)
+        grid = self._tree_head(self.forward(images_u8, out=grid_out), grid_out is not None)
         return E.detect_anchor_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh, max_out, out=out,
                                      net_size=self.size if letterbox else None)
 
@@ -288,12 +333,12 @@ class YOLOv2Detector:
             if not letterbox:
                 raise ValueError("protocol='darknet' is letterboxed: pass letterbox=True")
             assert images_u8.dtype == torch.float32, images_u8.dtype
-            grid = self.forward(images_u8, out=grid_out)
+            grid = self._tree_head(self.forward(images_u8, out=grid_out), grid_out is not None)
             return E.detect_anchor_classes_batch_darknet(grid, self.anchors_dev, table, index, score_thresh, iou_thresh,
                                                          max_per_class, out=out, net_size=self.size)
         if protocol != "repo":
             raise ValueError("protocol %r is neither 'repo' nor 'darknet'" % (protocol,))
-        grid = self.forward(images_u8, out=grid_out)
+        grid = self._tree_head(self.forward(images_u8, out=grid_out), grid_out is not None)
         return E.detect_anchor_classes_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh,
                                              max_per_class, out=out, net_size=self.size if letterbox else None)
 
@@ -305,8 +350,11 @@ class _Trainer:
     keeps_backward = False           # whether backward() leaves last_dcat / last_dfine behind (a subclass's tests read them)
 
     def __init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
-                 area_weight, prior_images, prior_scale, solver, bn_eps, _cfg=None):
+                 area_weight, prior_images, prior_scale, solver, bn_eps, _cfg=None, tree=None, tree_thresh=0.5):
         self._topo, self.cfg = _cfg if _cfg is not None else (_topology(topology), None)
+        # tree: a utils.word_tree.WordTree of num_class nodes (None: the flat softmax).  Box lists then train through
+        # engine.yolov2_loss_boxes_tree, a truth's class a node index; tree_thresh is kept for the detector of this model
+        self.tree, self.tree_thresh = _device_tree(tree, num_class, device), float(tree_thresh)
         topology = self._topo.name
         # the batch-norm epsilon of every context and size (None: the contexts' default, 1e-3); 1e-6 is Darknet's, the one
         # a backbone read from a Darknet file was trained with (net_utils.read_darknet_backbone)
@@ -432,6 +480,8 @@ class _Trainer:
             raise ValueError("step() takes either labels or truth + ntruth, not both and not neither")
         if stats is not None and truth is None:
             raise ValueError("step(stats=...) reads the box list: give truth + ntruth, not labels")
+        if self.tree is not None and labels is not None:
+            raise ValueError("a label grid with a word tree is not built: give the box list, truth + ntruth")
         size = int(images.shape[1])
         nets = self._nets(size)
         if len(self.ctx) > 1:
@@ -441,13 +491,20 @@ class _Trainer:
         grid, fine = self.forward(images, True, update_moving=True)
         if labels is not None:
             loss, dnet = E.yolov2_loss(grid.contiguous(), labels, self.anchors, size, True, self.scales)
-        else:
+        elif self.tree is None:
             loss, dnet = E.yolov2_loss_boxes(grid.contiguous(), truth, ntruth, self.anchors, size, True,
                                              self.box_scales(self.iteration))
             if stats is not None:
                 if self._anchors_dev is None:                # uploaded once: the statistics add two launches, no copy
                     self._anchors_dev = torch.as_tensor(self.anchors).to(grid.device).contiguous()
                 E.yolov2_region_stats(grid.contiguous(), truth, ntruth, self._anchors_dev, size, out=stats)
+        else:
+            if self._anchors_dev is None:
+                self._anchors_dev = torch.as_tensor(self.anchors).to(grid.device).contiguous()
+            loss, dnet = E.yolov2_loss_boxes_tree(grid.contiguous(), truth, ntruth, self._anchors_dev, size, self.tree, True,
+                                                  self.box_scales(self.iteration))
+            if stats is not None:
+                E.yolov2_region_stats_tree(grid.contiguous(), truth, ntruth, self._anchors_dev, size, self.tree, out=stats)
         self.last_dnet = dnet                                # the head's output gradient of this step (tests read it)
         world = self.backward(dnet, fine, size)
         scaler = self.opts[0].scaler
@@ -494,7 +551,7 @@ class YOLOv2Trainer(_Trainer):
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
-                 solver=None, bn_eps=None, topology="paper"):
+                 solver=None, bn_eps=None, topology="paper", tree=None, tree_thresh=0.5):
         if topology == "tiny":
             raise NotImplementedError("YOLOv2Trainer trains the paper topology only: the \"tiny\" graph needs Darknet's "
                                       "stride-1 pool and its gradient, zero-padded narrow layers and a last layer without "
@@ -505,7 +562,7 @@ class YOLOv2Trainer(_Trainer):
                                       "Darknet's reorg, a fourth optimizer and a last layer without batch statistics -- "
                                       "YOLOv2DarknetTrainer has them" % topology)
         _Trainer.__init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
-                          area_weight, prior_images, prior_scale, solver, bn_eps)
+                          area_weight, prior_images, prior_scale, solver, bn_eps, tree=tree, tree_thresh=tree_thresh)
 
 
 class YOLOv2DarknetTrainer(_Trainer):
@@ -537,28 +594,32 @@ class YOLOv2DarknetTrainer(_Trainer):
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", scales=None, width_div=1, area_weight=False, prior_images=0, prior_scale=0.01,
-                 solver=None, bn_eps=None, topology="darknet", _cfg=None):
+                 solver=None, bn_eps=None, topology="darknet", _cfg=None, tree=None, tree_thresh=0.5):
         if topology not in DARKNET_FILE_TOPOLOGIES:
             raise ValueError("YOLOv2DarknetTrainer trains the \"darknet\" and \"tiny\" topologies; topology %r is "
                              "YOLOv2Trainer's" % (topology,))
         _Trainer.__init__(self, topology, batch, image_size, num_class, anchors, dtype, seed, device, scales, width_div,
-                          area_weight, prior_images, prior_scale, solver, bn_eps, _cfg=_cfg)
+                          area_weight, prior_images, prior_scale, solver, bn_eps, _cfg=_cfg, tree=tree,
+                          tree_thresh=tree_thresh)
 
     CFG_PRIOR_IMAGES = 12800         # Darknet's region layer hard-codes the prior's span and the (2 - w h) weight
 
     @classmethod
     def from_cfg(cls, record_or_path, batch=None, image_size=None, dtype="f16", seed=0, device="cuda:0", solver=None,
-                 prior_images=None):
+                 prior_images=None, tree=None, tree_thresh=None):
         """the train step of a Darknet cfg (utils/darknet_cfg.py: a record or a file): its graph, widths, class count and
         anchors; its [net] solver; its [region] scales (coord_scale ... thresh); area_weight and prior_images 12800, which
-        Darknet hard-codes.  batch and image_size default to the file's; solver / prior_images: a caller's own in place
-        of the file's (a flag given on the command line)"""
+        Darknet hard-codes; its word tree (load_cfg_tree) and tree_thresh.  batch and image_size default to the file's;
+        solver / prior_images / tree / tree_thresh: a caller's own in place of the file's (a flag given on the command
+        line)"""
         topo, record = _cfg_topology(record_or_path, dtype)
         return cls(record.batch if batch is None else batch, record.size if image_size is None else image_size,
                    num_class=record.classes, anchors=record.anchors, dtype=dtype, seed=seed, device=device,
                    scales=dict(record.scales), area_weight=True,
                    prior_images=cls.CFG_PRIOR_IMAGES if prior_images is None else prior_images,
-                   solver=record.solver if solver is None else solver, _cfg=(topo, record))
+                   solver=record.solver if solver is None else solver, _cfg=(topo, record),
+                   tree=load_cfg_tree(record) if tree is None else tree,
+                   tree_thresh=record.tree_thresh if tree_thresh is None else tree_thresh)
 
     def _init_form(self, nets):
         """a fresh model in the form a `.weights` file can hold: the 1x1 layers' off-centre taps zero, the narrow layers'
