@@ -367,6 +367,26 @@ int y2_yolov2_region_stats_tree(const float* net, const float* truth, const int*
 int y2_word_tree_head(const float* net, const int* tables, int rows, int num_class, int G, int max_depth,
                       float tree_thresh, float* out, int* top, float* prob, void* stream);
 
+/* ---- The wide head (csrc/wide_head.hip): a 1x1 convolution wider than the executor's 2,048-column row -- YOLO9000's last
+ *      layer, 1024 -> 28,269 -- as an operator behind the head stack.  Inference only: no gradient entries exist.
+ *      One arithmetic: f16 operands, fp32 accumulation on the f16 matrix pipe.  Argument errors of all entries, nothing
+ *      launched, named with the entry and the item: a null pointer; K no multiple of 32 or beyond Y2_WIDE_HEAD_MAX_K;
+ *      Cout outside 1..Y2_WIDE_HEAD_MAX_COUT; a pointer the kernels read in 16-byte units that is not 16-byte aligned. */
+#define Y2_WIDE_HEAD_MAX_K 4096
+#define Y2_WIDE_HEAD_MAX_COUT (65536 * 16)
+/* host only: the bytes of the packed f16 operand image of a K -> Cout layer (Cout rounded up to the 256-column tile, K to
+ * the 64-element K step); 0 where K or Cout break the rules above */
+size_t y2_wide_head_packed_bytes(int K, int Cout);
+/* W: fp32 filters [1][1][K][Cout] (the layout of a 1x1 layer's W) -> `packed`, 16-byte aligned, packed_bytes of it at
+ * least y2_wide_head_packed_bytes: every byte of the image is written, the padding as zero.  One launch, no allocation.
+ * Y2_ERR_ARG also: packed_bytes too small. */
+int y2_wide_head_pack(const float* W, int K, int Cout, void* packed, size_t packed_bytes, void* stream);
+/* out[m][c] = bias[c] + sum_k f16(x[m][k]) f16(W[k][c]): x fp32 [M][K], 16-byte aligned (what y2_forward writes), converted
+ * inside the kernel; out fp32 [M][Cout], row stride Cout exactly, dword stores, nothing written past out + M * Cout.  One
+ * launch, the same bits every run.  Y2_ERR_ARG also: M < 1; more than 2^31 - 1 tiles of 256 x 256. */
+int y2_wide_head_forward(const float* x, const void* packed, const float* bias, int M, int K, int Cout, float* out,
+                         void* stream);
+
 /* ---- ResNet-50 backbone swap (src/yolo2_nets/tf_resnet.py:12-32, src/pascal/pascal_train_resnet.py:37-50):
  *      graph-level operators on fp32 NHWC tensors that the conv-BN-leaky stacks do not have.  The 1x1 / 3x3
  *      convolutions of the bottleneck units (slim_dir/nets/resnet_v1.py:68-112) go through y2_conv2d /

@@ -109,6 +109,9 @@ SIGNATURES = {
     "y2_yolov2_loss_boxes_tree": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "y2_yolov2_region_stats_tree": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "y2_word_tree_head": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "y2_wide_head_packed_bytes": (_sz, [_i, _i]),
+    "y2_wide_head_pack": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
+    "y2_wide_head_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "y2_batch_norm_forward": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp]),
     "y2_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "y2_subsample": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

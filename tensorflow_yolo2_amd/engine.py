@@ -1163,6 +1163,61 @@ def word_tree_head(net, tree, tree_thresh=0.5, out=None, want_top=False):
     return (out, top, prob) if want_top else out
 
 
+WIDE_HEAD_DTYPES = ("f16", "fp8")    # the model modes a wide head runs behind: its one arithmetic is f16 x f16 -> fp32
+
+
+class WideHead:
+    """a 1x1 convolution wider than a stack's 2,048-column row (YOLO9000's last layer, 1024 -> 28,269), run behind the
+    head stack by csrc/wide_head.hip: out[m][c] = b[c] + sum_k f16(x[m][k]) f16(W[k][c]), fp32 accumulation.  Inference
+    only.  Holds the fp32 filters [1][1][K][Cout] and bias (what export() returns and a `.weights` file takes back), the
+    packed f16 operand image the kernel reads, and one output buffer per M"""
+
+    def __init__(self, K, Cout, device="cuda:0"):
+        self.lib = _lib.load()
+        self.K, self.Cout, self.device = int(K), int(Cout), torch.device(device)
+        nbytes = self.lib.y2_wide_head_packed_bytes(self.K, self.Cout)
+        if nbytes == 0:
+            raise ValueError("WideHead: K = %d (a multiple of 32, at most 4096), Cout = %d (1..%d)" %
+                             (self.K, self.Cout, 65536 * 16))
+        self.W = torch.zeros((1, 1, self.K, self.Cout), dtype=torch.float32, device=self.device)
+        self.b = torch.zeros(self.Cout, dtype=torch.float32, device=self.device)
+        self.packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._out = {}
+        self._pack()
+
+    def _pack(self):
+        check(self.lib.y2_wide_head_pack(_ptr(self.W), self.K, self.Cout, _ptr(self.packed), self.packed.numel(), _stream()))
+
+    def load(self, W, b):
+        """W: anything numpy reads of K * Cout values in the order [K][Cout] (a 1x1 layer's [1][1][K][Cout]); b [Cout]"""
+        W, b = np.asarray(W, np.float32), np.asarray(b, np.float32)
+        if W.size != self.K * self.Cout or b.shape != (self.Cout,):
+            raise ValueError("WideHead.load: W %s and b %s do not fit %d -> %d" % (W.shape, b.shape, self.K, self.Cout))
+        self.W.copy_(torch.as_tensor(np.ascontiguousarray(W).reshape(1, 1, self.K, self.Cout)).to(self.device))
+        self.b.copy_(torch.as_tensor(b).to(self.device))
+        self._pack()
+
+    def export(self):
+        """-> {"W": [1][1][K][Cout], "b": [Cout]} as numpy arrays: the fp32 values load() was given"""
+        return {"W": self.W.cpu().numpy().copy(), "b": self.b.cpu().numpy().copy()}
+
+    def forward(self, x, out=None):
+        """x: fp32 [..., K] on the device, contiguous -> fp32 [M][Cout], M the product of the leading sizes (in `out`, a
+        contiguous fp32 tensor of M * Cout elements, if given; else in this operator's buffer for that M)"""
+        _dev(x, torch.float32, "x")
+        assert x.shape[-1] == self.K, (tuple(x.shape), self.K)
+        m = x.numel() // self.K
+        if out is None:
+            out = self._out.get(m)
+            if out is None:
+                out = self._out[m] = torch.empty((m, self.Cout), dtype=torch.float32, device=self.device)
+        else:
+            _own(out, None, torch.float32, self.device, numel=m * self.Cout)
+        check(self.lib.y2_wide_head_forward(_ptr(x), _ptr(self.packed), _ptr(self.b), m, self.K, self.Cout, _ptr(out),
+                                            _stream()))
+        return out
+
+
 def nms(boxes, scores, classes=None, iou_thresh=0.5, score_thresh=0.0, max_out=100, class_aware=False):
     """boxes [N,K,4], scores [N,K] (, classes [N,K] int32) -> keep [N,max_out] int32 (-1 padded), count [N]"""
     lib = _lib.load()

@@ -22,7 +22,10 @@ A file of tiny-yolo-voc.cfg is taken the same way: its float count says so (net_
 YOLOv2Detector.from_cfg), so the COCO models load -- `--cfg yolov2.cfg --darknet-weights yolov2.weights --names coco.names`
 -- and --names FILE writes each detection under its class name (one per line; the count must be the model's).  --tree FILE
 (or softmax_tree= of --cfg) runs a word-tree model: a detection is the node where the walk down the tree stops at
---hier-thresh (tree_thresh of --cfg, else 0.5), written under --names, else under the tree's label of that node."""
+--hier-thresh (tree_thresh of --cfg, else 0.5), written under --names, else under the tree's label of that node.
+YOLO9000 loads the same way -- `--cfg yolo9000.cfg --darknet-weights yolo9000.weights --names 9k.names` -- with its
+28,269-filter last layer run by engine.WideHead (--dtype f16 or fp8; `tree=` found next to the cfg or given as --tree; `map=`
+is not read); --protocol darknet, one row per class, is refused for it (YOLOv2Detector.detect_classes_batch says why)."""
 import argparse
 import sys
 
@@ -49,7 +52,7 @@ def parse_args(argv=None):
     model_flags.add_test_flags(ap)
     args = ap.parse_args(argv)
     args.error = ap.error
-    model_flags.resolve_cfg(ap, args)
+    model_flags.resolve_cfg(ap, args, wide_head=True)
     model_flags.check_size(ap, args)
     if args.batch is None:
         args.batch = min(len(args.images), 32)

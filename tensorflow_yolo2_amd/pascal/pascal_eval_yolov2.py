@@ -76,7 +76,7 @@ def parse_args(argv=None, need_devkit=True, prog=None):
     model_flags.add_test_flags(ap)
     args = ap.parse_args(argv)
     args.error = ap.error
-    model_flags.resolve_cfg(ap, args)
+    model_flags.resolve_cfg(ap, args, wide_head=True)
     model_flags.check_size(ap, args)
     if args.batch < 1 or args.max_out < 1 or args.width_div < 1 or args.max_per_class < 1:
         ap.error("--batch, --max-out, --max-per-class and --width-div must be at least 1")

@@ -66,10 +66,13 @@ def check_tree(error, args, num_class):
                                                                              num_class))
 
 
-def resolve_cfg(ap, args):
+def resolve_cfg(ap, args, wide_head=False):
     """right behind parse_args: --cfg read into args.cfg_record (None without the flag) and the flags nobody gave filled
-    from it, then from today's defaults; --names read into args.class_names (None without the flag)"""
+    from it, then from today's defaults; --names read into args.class_names (None without the flag).  wide_head: the
+    keyword of utils/darknet_cfg.py, which the scripts that only run a model pass as True -- YOLO9000's cfg then loads
+    (`map=` kept unread, its 28,269-filter last layer as engine.WideHead); kept in args.wide_head for build_detector"""
     args.cfg_record = args.class_names = None
+    args.wide_head = bool(wide_head)
     if args.cfg:
         from ..utils import darknet_cfg
         if args.weights or args.ckpt_dir:
@@ -77,8 +80,9 @@ def resolve_cfg(ap, args):
         if args.width_div != 1:
             ap.error("--cfg holds the widths: not with --width-div")
         try:
-            args.cfg_record = darknet_cfg.load(args.cfg)
-            darknet_cfg.compile_graph(args.cfg_record, 1024 if args.dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH)
+            args.cfg_record = darknet_cfg.load(args.cfg, wide_head)
+            darknet_cfg.compile_graph(args.cfg_record, 1024 if args.dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH,
+                                      wide_head)
         except (OSError, ValueError) as e:
             ap.error("--cfg: %s" % e)
         if args.size is None:
@@ -143,8 +147,12 @@ def build_detector(args, snapshot, anchors, num_class, bn_eps):
     snapshot's iteration or 0)"""
     check_tree(args.error, args, num_class)
     if args.cfg_record is not None:
-        detector = yolov2.YOLOv2Detector.from_cfg(args.cfg_record, args.batch, args.size, dtype=args.dtype,
-                                                  tree=args.tree_record, tree_thresh=args.hier_thresh)
+        try:
+            detector = yolov2.YOLOv2Detector.from_cfg(args.cfg_record, args.batch, args.size, dtype=args.dtype,
+                                                      tree=args.tree_record, tree_thresh=args.hier_thresh,
+                                                      wide_head=getattr(args, "wide_head", False))
+        except ValueError as e:                   # a wide head under --dtype f32 / f16x2 / f16x2f
+            args.error("--cfg: %s" % e)
         if args.darknet_weights:
             print('Restorining model from Darknet weight file {:s} (cfg {:s}, topology {:s})'.format(
                 args.darknet_weights, args.cfg, detector.topology))

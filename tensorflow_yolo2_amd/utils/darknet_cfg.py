@@ -7,9 +7,10 @@ list.  The first section is `[net]` or `[network]`; every later section is one D
 order.  `[route]` indices count in that numbering, a negative one relative to the route's own position.
 
 Sections understood: `[convolutional]` (stride 1, pad 1, leaky or linear), `[maxpool]` (2 / 2 or 2 / 1), `[route]` (one or
-two indices), `[reorg]` (stride 2) and a last `[region]` (coords 4, softmax 1, bias_match 1, rescore 1; `softmax_tree`, the
-path of a word-tree file as written -- utils/word_tree.py reads it, yolo2_nets/yolov2.py finds it -- and `tree_thresh` in
-[0, 1); `map` is refused: it belongs with YOLO9000's wide head).  Everything else
+two indices), `[reorg]` (stride 2) and a last `[region]` (coords 4, softmax 1, bias_match 1, rescore 1; `softmax_tree` or
+its synonym `tree`, the path of a word-tree file as written -- utils/word_tree.py reads it, yolo2_nets/yolov2.py finds it
+-- and `tree_thresh` in [0, 1); `map` is refused unless the caller passes wide_head=True: it belongs with YOLO9000's wide
+head, see below).  Everything else
 -- another section, another value, an unknown key of a section that is understood, a value that does not parse -- raises a
 ValueError naming the file, the line, the layer and the item: a silently ignored key is how a model ends up trained
 differently from what its file says.
@@ -27,7 +28,13 @@ Two graph shapes are accepted (`compile_graph`), the ones yolo2_nets/yolov2.py c
                  coarse convolution in that order, the head ending in the linear convolution ("darknet")
 Widths come from the file and are held to the executor's rules (y2_ctx_create): first layer 3 -> 32, inner input widths a
 multiple of 32 and of 128 above 128, inner output widths a multiple of 32, at most 2048 outputs (1024 in fp32 storage).
-The one padding device stays: a 16-filter first layer runs 32 wide.  Any other width is refused by layer, width and rule."""
+The one padding device stays: a 16-filter first layer runs 32 wide.  Any other width is refused by layer, width and rule.
+
+wide_head=True (parse, load, compile_graph; default False, under which nothing above changes) admits YOLO9000's file:
+`map=FILE` is kept in the record's `map` as written and never opened (detection does not read it; the trainers refuse a
+record that carries one), and the LAST convolution -- linear, no batch norm -- may be wider than the executor's row: the
+graph is then `wide`, its head stack ends at the last conv-BN-leaky layer and the last convolution runs as
+engine.WideHead behind it.  Its input width keeps the inner rules and every batch-norm layer keeps the row limit."""
 import collections
 
 import numpy as np
@@ -43,16 +50,20 @@ Augmentation = collections.namedtuple("Augmentation", "jitter hue saturation exp
 # 32; scales: ((name, value), ...) of coord_scale, object_scale, noobject_scale, class_scale, thresh; size, batch,
 # subdivisions, max_batches, random: of [net] / [region]; file_layers: [(k, c, n, batch_norm)] in file order, the form
 # utils/darknet_weights.split takes; floats: their float count; tree: softmax_tree as written (None: no word tree);
-# tree_thresh: where a detection's walk down the tree stops (0.5 when absent, the default of Darknet's -hier)
+# tree_thresh: where a detection's walk down the tree stops (0.5 when absent, the default of Darknet's -hier); map: `map=`
+# as written (None: absent; read under wide_head=True only, never opened)
 DarknetCfg = collections.namedtuple("DarknetCfg", "path layers solver augmentation anchors classes num scales size batch "
-                                                  "subdivisions max_batches random file_layers floats tree tree_thresh",
-                                    defaults=(None, 0.5))
+                                                  "subdivisions max_batches random file_layers floats tree tree_thresh map",
+                                    defaults=(None, 0.5, None))
 
 # what compile_graph returns: shape "chain" / "passthrough"; specs: the stacks in networks() order, each a tuple of
 # (k, in, out, pool) at the widths that RUN; file_layers as above; centre_tap: the stem layers that are 1x1 in the file
 # and run 3x3 on their centre tap; narrow: ((stem layer, filters in the file), ...); head_layers: convolutions of the
-# head; pool: "s2" / "s1", the op between the stem and the next stack; route: whether the passthrough has its convolution
-Graph = collections.namedtuple("Graph", "shape specs file_layers centre_tap narrow head_layers pool route")
+# head; pool: "s2" / "s1", the op between the stem and the next stack; route: whether the passthrough has its convolution;
+# wide: the last convolution is wider than max_out and is NOT part of the head stack's spec (engine.WideHead runs it);
+# head_layers counts it all the same
+Graph = collections.namedtuple("Graph", "shape specs file_layers centre_tap narrow head_layers pool route wide",
+                               defaults=(False,))
 
 SCALE_KEYS = ("coord_scale", "object_scale", "noobject_scale", "class_scale", "thresh")
 MAX_OUT_WIDTH = 2048             # the batch-norm kernels' row width in 16-bit storage; fp32 storage: 1024
@@ -188,9 +199,9 @@ def _parse_net(o):
     return dict(size=width, batch=batch, subdivisions=subdivisions, max_batches=max_batches, solver=solver, colour=colour)
 
 
-def _parse_region(o):
+def _parse_region(o, wide_head=False):
     for key in REFUSED_REGION_KEYS:
-        if key in o.entries:
+        if key in o.entries and not wide_head:
             o.fail(o.entries[key][1], o.where, "%s=%s: the class map of YOLO9000 belongs with its 28,269-wide head and is "
                    "not built" % (key, o.entries[key][0]))
     classes, num = o.int("classes", 20), o.int("num", 1)
@@ -209,15 +220,23 @@ def _parse_region(o):
     o.int("absolute", 0)                                      # accepted, not used
     scales = tuple((k, o.float(k, 0.5 if k == "thresh" else 1.0)) for k in SCALE_KEYS)
     jitter = o.float("jitter", 0.2)
-    tree = o.word("softmax_tree", None)
+    tree, tree_key = o.word("softmax_tree", None), "softmax_tree"
+    synonym = o.word("tree", None)                            # the key YOLO9000's cfg writes
+    if synonym is not None:
+        if tree is not None and tree != synonym:
+            o.fail(o.line_of("tree"), o.where, "tree=%s and softmax_tree=%s name different files" % (synonym, tree))
+        tree, tree_key = synonym, "tree"
     if tree is not None and not tree:
-        o.fail(o.line_of("softmax_tree"), o.where, "softmax_tree= names no file")
+        o.fail(o.line_of(tree_key), o.where, "%s= names no file" % tree_key)
+    class_map = o.word("map", None) if wide_head else None
+    if class_map is not None and not class_map:
+        o.fail(o.line_of("map"), o.where, "map= names no file")
     tree_thresh = o.float("tree_thresh", 0.5)
     if not 0.0 <= tree_thresh < 1.0:
         o.fail(o.line_of("tree_thresh"), o.where, "tree_thresh=%s: a number in [0, 1)" % tree_thresh)
     o.done()
     return dict(classes=classes, num=num, anchors=tuple(zip(anchors[0::2], anchors[1::2])), random=random, scales=scales,
-                jitter=jitter, tree=tree, tree_thresh=tree_thresh)
+                jitter=jitter, tree=tree, tree_thresh=tree_thresh, map=class_map)
 
 
 def _parse_layer(o, kind, index, fail):
@@ -256,8 +275,9 @@ def _parse_layer(o, kind, index, fail):
     fail(o.line, o.where, "section [%s] is not understood ([convolutional], [maxpool], [route], [reorg], [region])" % kind)
 
 
-def parse(text, path="<cfg>"):
-    """the text of a cfg -> DarknetCfg; `path` is the name the errors carry"""
+def parse(text, path="<cfg>", wide_head=False):
+    """the text of a cfg -> DarknetCfg; `path` is the name the errors carry; wide_head: admit `map=` and a last
+    convolution wider than the executor's row (the module docstring)"""
     fail = _Fail(path)
     sections = _sections(text, fail)
     if not sections or sections[0][0] not in ("net", "network"):
@@ -271,7 +291,7 @@ def parse(text, path="<cfg>"):
         if kind == "region":
             if index != len(sections) - 2:
                 fail(line, o.where, "[region] must be the last section; %d follow(s)" % (len(sections) - 2 - index))
-            region = _parse_region(o)
+            region = _parse_region(o, wide_head)
             layers.append(Layer(index, line, kind, ()))
         else:
             layers.append(Layer(index, line, kind, _parse_layer(o, kind, index, fail)))
@@ -284,19 +304,19 @@ def parse(text, path="<cfg>"):
                          classes=region["classes"], num=region["num"], scales=region["scales"], size=net["size"],
                          batch=net["batch"], subdivisions=net["subdivisions"], max_batches=net["max_batches"],
                          random=region["random"], file_layers=(), floats=0, tree=region["tree"],
-                         tree_thresh=region["tree_thresh"])
-    graph = compile_graph(partial)
+                         tree_thresh=region["tree_thresh"], map=region["map"])
+    graph = compile_graph(partial, wide_head=wide_head)
     return partial._replace(file_layers=graph.file_layers, floats=sum(layer_floats(l) for l in graph.file_layers))
 
 
-def load(path):
+def load(path, wide_head=False):
     """a cfg file -> DarknetCfg"""
     with open(path, "r") as f:
-        return parse(f.read(), str(path))
+        return parse(f.read(), str(path), wide_head)
 
 
-def as_record(record_or_path):
-    return record_or_path if isinstance(record_or_path, DarknetCfg) else load(record_or_path)
+def as_record(record_or_path, wide_head=False):
+    return record_or_path if isinstance(record_or_path, DarknetCfg) else load(record_or_path, wide_head)
 
 
 def read_names(path):
@@ -308,8 +328,9 @@ def read_names(path):
 # ---------------------------------------------------------------------------
 # From the layer list to the stacks
 # ---------------------------------------------------------------------------
-def _check_widths(fail, convs, stack, max_out):
-    """the executor's rules on one stack's (layer, k, in, out, pool) rows at the widths that run"""
+def _check_widths(fail, convs, stack, max_out, wide=False):
+    """the executor's rules on one stack's (layer, k, in, out, pool) rows at the widths that run; wide: the last
+    convolution of the file is engine.WideHead's and has no output limit here"""
     for (layer, _k, ci, co, _pool) in stack:
         where = _where(layer.index, layer.kind)
         inner_in = not (layer is convs[0])
@@ -319,14 +340,15 @@ def _check_widths(fail, convs, stack, max_out):
             fail(layer.line, where, "input width %d: an input width above 128 must be a multiple of 128" % ci)
         if layer is not convs[-1] and co % 32:
             fail(layer.line, where, "width %d (filters): an inner layer's output width must be a multiple of 32" % co)
-        if co > max_out:
+        if co > max_out and not (wide and layer is convs[-1]):
             fail(layer.line, where, "width %d (filters): at most %d outputs%s" %
                  (co, max_out, " in fp32 storage" if max_out < MAX_OUT_WIDTH else ""))
 
 
-def compile_graph(record, max_out=MAX_OUT_WIDTH):
+def compile_graph(record, max_out=MAX_OUT_WIDTH, wide_head=False):
     """the layer list of a record -> Graph, or ValueError naming the layer that fits neither shape or breaks a width rule.
-    max_out: the widest output the executor runs (2048; 1024 where the tensors are stored in fp32)"""
+    max_out: the widest output the executor runs (2048; 1024 where the tensors are stored in fp32).  wide_head: a last
+    convolution above max_out is allowed and makes the graph `wide`"""
     fail = _Fail(record.path)
     layers = record.layers
     opt = lambda layer: dict(layer.options)
@@ -345,6 +367,10 @@ def compile_graph(record, max_out=MAX_OUT_WIDTH):
     if opt(last)["filters"] != want:
         fail(last.line, _where(last.index, last.kind), "filters=%d: num (5 + classes) = %d (%d + 5) = %d" %
              (opt(last)["filters"], record.num, record.classes, want))
+    wide = bool(wide_head) and want > max_out
+    if wide and opt(last)["size"] != 1:
+        fail(last.line, _where(last.index, last.kind), "size=%d: a last convolution of %d filters runs as the wide head, "
+             "which is 1x1" % (opt(last)["size"], want))
     first = convs[0]
     if first is not body[0] or opt(first)["size"] != 3 or opt(first)["filters"] not in (16, 32):
         fail(body[0].line, _where(body[0].index, body[0].kind), "the first layer must be a 3x3 convolution of 32 filters "
@@ -485,9 +511,12 @@ def compile_graph(record, max_out=MAX_OUT_WIDTH):
             fail(layers[-1].line, _where(layers[-1].index, "region"), "a stack of the graph holds no convolution")
         if stack is not segments[0] and any(r[4] for r in stack):
             fail(stack[0][0].line, _where(stack[0][0].index, stack[0][0].kind), "pools belong to the stem")
-        _check_widths(fail, convs, stack, max_out)
+        _check_widths(fail, convs, stack, max_out, wide)
     if narrow and len(segments[0]) < 2:
         fail(first.line, _where(first.index, first.kind), "a 16-filter first layer needs a second stem layer behind it")
+    n_head = len(head)
+    if wide:
+        segments = segments[:-1] + [head[:-1]]     # the head stack ends at the last conv-BN-leaky layer
     specs = tuple(tuple((k, ci, co, p) for (_l, k, ci, co, p) in stack) for stack in segments)
     return Graph(shape=shape, specs=specs, file_layers=tuple(file_layers), centre_tap=tuple(centre_tap), narrow=narrow,
-                 head_layers=len(head), pool=pool, route=(shape == "passthrough" and len(segments) == 4))
+                 head_layers=n_head, pool=pool, route=(shape == "passthrough" and len(segments) == 4), wide=wide)

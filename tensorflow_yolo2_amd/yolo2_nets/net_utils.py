@@ -776,6 +776,11 @@ def _load_darknet_layers(model, path, what, whole):
             params[l] = p
         net.load_params(params)
         pos += take
+    wide = getattr(model, "wide", None)
+    if wide is not None and pos == len(file_layers) - 1 and pos < len(layers):
+        # the wide last layer (engine.WideHead): filters transposed as everywhere, b = the file's biases, no affine; packs
+        d = layers[pos]
+        wide.load(_dkw._filters_in(d["weights"], 1, np.float32), np.asarray(d["biases"], np.float32))
     if hasattr(model, "params_changed"):
         model.params_changed()      # a trainer's multi-scale contexts share the parameters just written: all re-pack
     return seen, len(layers)
@@ -805,8 +810,9 @@ def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):
     (utils/darknet_weights.from_layer_params).  A model that load_darknet_weights filled and nothing changed gives the
     bytes that were read (write the header's version too: a file of version 0.2 has a 64-bit `seen`)."""
     nets = _darknet_model(model, "save_darknet_weights")
+    wide = getattr(model, "wide", None)          # engine.WideHead: the file's last layer, behind an all-leaky head stack
     slopes = nets[-1].slopes                     # None: a context that was never given slopes runs 0.1 everywhere
-    if slopes is None or float(slopes[-1]) != 1.0:
+    if wide is None and (slopes is None or float(slopes[-1]) != 1.0):
         raise ValueError("save_darknet_weights: the last layer runs with slope %s, Darknet's is linear (slope 1): its "
                          "batch norm cannot be folded through an activation" % (0.1 if slopes is None else slopes[-1]))
     file_layers = darknet_file_layers(model)
@@ -816,6 +822,9 @@ def save_darknet_weights(model, path, seen, major=0, minor=1, revision=0):
             kf, c, n, bn = file_layers[pos + l]
             out.append(_dkw.from_layer_params(_dkw.strip_layer_params(p, c, n), kf, bn, model.bn_eps))
         pos += net.num_layers
+    if wide is not None:
+        p = wide.export()
+        out.append({"biases": p["b"], "weights": _dkw._filters_out(p["W"], 1, np.float32)})
     return _dkw.write(path, out, seen, major, minor, revision)
 
 

@@ -95,10 +95,11 @@ def _paper_concat(fine, coarse, out=None):
 # pool / pool_backward: the op between the first and the second stack and its gradient.  centre_tap: the stem layers that
 # are 1x1 in a `.weights` file and run 3x3 on their centre tap; narrow: (stem layer, filters in the file) of the layers
 # that run wider than the file holds them, the padded filters and the next layer's padded input channels exactly zero.
-# anchors: the published anchors of the graph.
+# anchors: the published anchors of the graph.  wide: None, or (K, Cout) of the last convolution where it is wider than a
+# stack's row and runs as engine.WideHead behind the head stack (a cfg under wide_head=True; inference only).
 _Topology = collections.namedtuple("_Topology", "name specs heights bn_eps slopes train_options head_statistics "
                                                 "darknet_input concat concat_backward cf_stack pool pool_backward "
-                                                "centre_tap narrow anchors")
+                                                "centre_tap narrow anchors wide", defaults=(None,))
 
 _BESSEL = {"bessel": True}       # moving variances on the n - 1 estimate, as Darknet keeps them
 _TOPOLOGY = {
@@ -132,17 +133,34 @@ def _topology(name):
     return _TOPOLOGY[name]
 
 
-def _cfg_topology(record, dtype):
+def _cfg_topology(record, dtype, wide_head=False):
     """the _Topology of a Darknet cfg (utils/darknet_cfg.py) -> (topology, record): one more way to produce the record the
     code below reads, under the name of the shape it has -- "tiny" for a chain, "darknet" for a passthrough.  A cfg that
-    describes yolov2-voc.cfg or tiny-yolo-voc.cfg gives the named topology's stacks, options and ops"""
+    describes yolov2-voc.cfg or tiny-yolo-voc.cfg gives the named topology's stacks, options and ops.  wide_head: the
+    keyword of utils/darknet_cfg.py -- `map=` is admitted and a last convolution wider than a stack's row becomes the
+    topology's `wide` operator; without it a record that carries `map` is refused here (the trainers' case)"""
     from ..utils import darknet_cfg
-    record = darknet_cfg.as_record(record)
-    graph = darknet_cfg.compile_graph(record, 1024 if dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH)
+    record = darknet_cfg.as_record(record, wide_head)
+    if record.map is not None and not wide_head:
+        raise ValueError("%s: map=%s: the class map of YOLO9000 belongs with its wide head, which does not train; "
+                         "YOLOv2Detector.from_cfg(..., wide_head=True) runs it" % (record.path, record.map))
+    graph = darknet_cfg.compile_graph(record, 1024 if dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH, wide_head)
     n, head = len(graph.specs), graph.head_layers
-    slopes = (None,) * (n - 1) + ([0.1] * (head - 1) + [1.0],)
-    options = (_BESSEL,) * (n - 1) + (dict(_BESSEL, core_layers=head - 1),)
-    common = dict(specs=lambda num_class, num_anchors, width_div, _s=graph.specs: tuple(list(s) for s in _s),
+    wide = None
+    if graph.wide:
+        from .. import _lib
+        if _lib.DTYPES.get(dtype, dtype) not in (_lib.Y2_F16, _lib.Y2_FP8):
+            raise ValueError("%s: dtype %r with a wide head (%d filters): the wide head has one arithmetic, f16 operands "
+                             "with fp32 accumulation, and runs behind a model of dtype 'f16' or 'fp8' only -- the exact "
+                             "modes exist for training parity, and this head does not train" %
+                             (record.path, dtype, graph.file_layers[-1][2]))
+        wide = (graph.file_layers[-1][1], graph.file_layers[-1][2])
+        slopes = (None,) * (n - 1) + ([0.1] * (head - 1),)                  # the head stack: conv-BN-leaky throughout
+        options = (_BESSEL,) * n
+    else:
+        slopes = (None,) * (n - 1) + ([0.1] * (head - 1) + [1.0],)
+        options = (_BESSEL,) * (n - 1) + (dict(_BESSEL, core_layers=head - 1),)
+    common = dict(wide=wide, specs=lambda num_class, num_anchors, width_div, _s=graph.specs: tuple(list(s) for s in _s),
                   bn_eps=DARKNET_BN_EPS, slopes=slopes, train_options=options, head_statistics=False, darknet_input=True,
                   centre_tap=graph.centre_tap, narrow=graph.narrow, anchors=record.anchors)
     if graph.shape == "chain":
@@ -213,9 +231,10 @@ def _make_buffers(topo, nets, batch, size):
             torch.empty((batch, S, S, nets[-1].spec[0][1]), dtype=torch.float32, device=dev) if topo.concat else None)
 
 
-def _forward(topo, nets, buffers, images, training, update_moving, out=None):
+def _forward(topo, nets, buffers, images, training, update_moving, out=None, wide=None):
     """the forward pass of every graph -> (flat head output, fine map).  nets = (stem, 13x13 stack, [route,] head), or
-    (stem, head) on a graph without a passthrough"""
+    (stem, head) on a graph without a passthrough.  wide: the engine.WideHead of a wide graph, run on the head stack's
+    output"""
     x_buf, cat_buf = buffers
     if topo.darknet_input and images.dtype == torch.uint8:
         images = E.u8_to_darknet_input(images, out=x_buf)                   # BGR pixels -> RGB in [0, 1]
@@ -228,6 +247,8 @@ def _forward(topo, nets, buffers, images, training, update_moving, out=None):
         for route in nets[2:-1]:                                            # "darknet": the 1x1 route, [N,2S,2S,64]
             passed = route.forward(passed, training, training, update_moving=update_moving)
         cat = topo.concat(passed, coarse, out=cat_buf)                      # [N,S,S,4*cf+1024], reorganised map first
+    if wide is not None:
+        return wide.forward(head.forward(cat, False, False), out=out), fine
     out = head.forward(cat, training, training and topo.head_statistics, out=out, update_moving=update_moving)
     return out, fine                                                        # [N,S,S,B*(5+C)]
 
@@ -266,15 +287,25 @@ class YOLOv2Detector:
         if len(self._stacks) == 4:
             self.route = self._stacks[2]
         self._buffers = _make_buffers(self._topo, self._stacks, batch, image_size)
+        # the wide last layer of a cfg under wide_head=True (engine.WideHead; None on every other model): filters drawn
+        # from seed + the stack count, as a stack's would be, until net_utils.load_darknet_weights fills them
+        self.wide = None
+        if self._topo.wide is not None:
+            K, Cout = self._topo.wide
+            self.wide = E.WideHead(K, Cout, device)
+            rng = np.random.default_rng(seed + len(self._stacks))
+            self.wide.load(rng.standard_normal((K, Cout), np.float32) * np.float32(1.0 / np.sqrt(K)),
+                           np.zeros(Cout, np.float32))
 
     @classmethod
     def from_cfg(cls, record_or_path, batch, image_size=None, dtype="f16", seed=0, device="cuda:0", tree=None,
-                 tree_thresh=None):
+                 tree_thresh=None, wide_head=False):
         """the detector of a Darknet cfg (utils/darknet_cfg.py: a record or a file): its graph, widths, class count and
         anchors, its word tree (load_cfg_tree) and tree_thresh; image_size defaults to the file's width; tree /
         tree_thresh: a caller's own in place of the file's.  net_utils.load_darknet_weights fills it from the `.weights`
-        file that goes with the cfg"""
-        topo, record = _cfg_topology(record_or_path, dtype)
+        file that goes with the cfg.  wide_head=True admits YOLO9000's file: `map=` and a last layer wider than a stack's
+        row, which runs as engine.WideHead (dtype 'f16' or 'fp8'; detect and detect_batch work as they are)"""
+        topo, record = _cfg_topology(record_or_path, dtype, wide_head)
         return cls(batch, record.size if image_size is None else image_size, num_class=record.classes,
                    anchors=record.anchors, dtype=dtype, seed=seed, device=device,
                    tree=load_cfg_tree(record) if tree is None else tree,
@@ -288,7 +319,7 @@ class YOLOv2Detector:
     def forward(self, images, out=None):
         """images [N,size,size,3] fp32 (or uint8 BGR pixels) on the device -> raw grid [N,S,S,B,5+C] (in `out`, a
         contiguous fp32 tensor of that many elements, if given).  On the "darknet" topology fp32 input is RGB in [0, 1]"""
-        out, _fine = _forward(self._topo, self._stacks, self._buffers, images, False, False, out=out)
+        out, _fine = _forward(self._topo, self._stacks, self._buffers, images, False, False, out=out, wide=self.wide)
         return out.view(self.batch, self.S, self.S, self.B, 5 + self.num_class)
 
     def _tree_head(self, grid, keep_raw=False):
@@ -326,6 +357,11 @@ class YOLOv2Detector:
         protocol="darknet") and the rows are Darknet's -- float un-map, float IoU, float corners as bit patterns in words
         0..3 (engine.detect_anchor_classes_batch_darknet).  It needs the "darknet" topology, whose float input is RGB in
         [0, 1], and letterbox=True"""
+        if self.wide is not None:
+            raise ValueError("detect_classes_batch on a model with a wide head (%d classes) is not built: it would launch "
+                             "one workgroup per class and image, each re-deriving a %d-wide softmax; use detect_batch -- "
+                             "with a word tree a row has one class, so its class-aware rows are the same detections" %
+                             (self.num_class, self.num_class))
         if protocol == "darknet":
             if not self._topo.darknet_input:
                 raise ValueError("protocol='darknet' needs the \"darknet\" topology: the input of the %r topology is BGR "
