@@ -93,8 +93,11 @@ def yolo9000_cfg_text():
 
 
 # (M, K, Cout) of the kernel parity: one ragged tile each way and one (half) K step; across 2048; the real M and K with a
-# ragged odd Cout and several K steps; the smallest; the real width
-GEMM_SHAPES = ((25, 32, 225), (147, 128, 2115), (289, 1024, 4099), (1, 64, 1), (300, 256, 28269))
+# ragged odd Cout and several K steps; the smallest; the real width.  Then the regimes around them: exactly full tiles (no
+# mask live); one row and one column into the second tiles; three row tiles and a half K step behind a full one; K at
+# Y2_WIDE_HEAD_MAX_K; four row tiles x three panels through xcd_block
+GEMM_SHAPES = ((25, 32, 225), (147, 128, 2115), (289, 1024, 4099), (1, 64, 1), (300, 256, 28269),
+               (256, 64, 256), (257, 64, 257), (513, 96, 300), (40, 4096, 260), (770, 160, 600))
 GUARD = 1024
 
 
@@ -107,6 +110,52 @@ def gemm_operands(M, K, Cout):
     W = (rng.standard_normal((K, Cout)) * 0.05).astype(np.float32)
     b = (rng.standard_normal(Cout) * 0.1).astype(np.float32)
     return x, W, b
+
+
+def packed_image(lib, Wd, K, Cout):
+    """y2_wide_head_pack of the device tensor Wd [K][Cout] into a buffer of exactly y2_wide_head_packed_bytes"""
+    import ctypes
+    import torch
+    nbytes = lib.y2_wide_head_packed_bytes(K, Cout)
+    assert nbytes == (Cout + 255) // 256 * 256 * ((K + 63) // 64 * 64) * 2
+    packed = torch.full((nbytes,), 0xAB, dtype=torch.uint8, device="cuda")
+    assert lib.y2_wide_head_pack(ctypes.c_void_p(Wd.data_ptr()), K, Cout, ctypes.c_void_p(packed.data_ptr()), nbytes,
+                                 None) == 0, lib.y2_last_error()
+    return packed
+
+
+def check_forward_on_the_device(x, W, b):
+    """y2_wide_head_forward on one operand set against gemm_reference, the kernel parity of tests/test_gpu_wide_head.py:
+    per element |got - ref| <= 2 K 2^-24 sum_k |x_k w_k| + 1e-30; the guard words behind out intact, a NaN prefill fully
+    overwritten, two runs the same bits.  Needs the GPU; prints the figures before it asserts -> (got, ref, bound)"""
+    import ctypes
+    import torch
+    from tensorflow_yolo2_amd import _lib
+    lib = _lib.load()
+    (M, K), Cout = x.shape, W.shape[1]
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    ref, mag = gemm_reference(x, W, b)
+    xd, Wd, bd = dev(x), dev(W), dev(b)
+    packed = packed_image(lib, Wd, K, Cout)
+    runs = []
+    for _ in range(2):
+        buf = torch.full((M * Cout + GUARD,), float("nan"), device="cuda")
+        guard = dev(np.random.default_rng(M).integers(-2 ** 31, 2 ** 31, GUARD).astype(np.int32))
+        buf[M * Cout:].view(torch.int32).copy_(guard)
+        assert lib.y2_wide_head_forward(p(xd), p(packed), p(bd), M, K, Cout, p(buf), None) == 0, lib.y2_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(buf[M * Cout:].view(torch.int32), guard)      # nothing behind out + M * Cout was written
+        runs.append(buf[:M * Cout].cpu().numpy().reshape(M, Cout))
+    got = runs[0]
+    assert np.isfinite(got).all()                                        # every element was written
+    assert np.array_equal(got.view(np.uint32), runs[1].view(np.uint32))  # two runs: the same bits
+    bound = 2.0 * K * 2.0 ** -24 * mag + 1e-30
+    ratio = np.abs(got.astype(np.float64) - ref) / bound
+    print("wide head (%d, %d, %d): largest |got - ref| / bound = %.4f, largest |got - ref| = %.3e" %
+          (M, K, Cout, ratio.max(), np.abs(got - ref).max()))
+    assert ratio.max() <= 1.0, ratio.max()
+    return got, ref, bound
 
 
 def gemm_reference(x, W, b):

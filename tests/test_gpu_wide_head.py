@@ -27,41 +27,13 @@ def p(t):
 
 
 def _packed(lib, Wd, Kdim, Cout):
-    import torch
-    nbytes = lib.y2_wide_head_packed_bytes(Kdim, Cout)
-    assert nbytes == (Cout + 255) // 256 * 256 * ((Kdim + 63) // 64 * 64) * 2
-    packed = torch.full((nbytes,), 0xAB, dtype=torch.uint8, device="cuda")
-    assert lib.y2_wide_head_pack(p(Wd), Kdim, Cout, p(packed), nbytes, None) == 0, lib.y2_last_error()
-    return packed
+    return K.packed_image(lib, Wd, Kdim, Cout)
 
 
 @gpu
 @pytest.mark.parametrize("M,Kdim,Cout", K.GEMM_SHAPES)
 def test_forward_matches_float64_on_the_f16_operands(M, Kdim, Cout):
-    import torch
-    from tensorflow_yolo2_amd import _lib
-    lib = _lib.load()
-    x, Wt, b = K.gemm_operands(M, Kdim, Cout)
-    ref, mag = K.gemm_reference(x, Wt, b)
-    xd, Wd, bd = dev(x), dev(Wt), dev(b)
-    packed = _packed(lib, Wd, Kdim, Cout)
-    runs = []
-    for _ in range(2):
-        buf = torch.full((M * Cout + K.GUARD,), float("nan"), device="cuda")
-        guard = dev(np.random.default_rng(M).integers(-2 ** 31, 2 ** 31, K.GUARD).astype(np.int32))
-        buf[M * Cout:].view(torch.int32).copy_(guard)
-        assert lib.y2_wide_head_forward(p(xd), p(packed), p(bd), M, Kdim, Cout, p(buf), None) == 0, lib.y2_last_error()
-        torch.cuda.synchronize()
-        assert torch.equal(buf[M * Cout:].view(torch.int32), guard)      # nothing behind out + M * Cout was written
-        runs.append(buf[:M * Cout].cpu().numpy().reshape(M, Cout))
-    got = runs[0]
-    assert np.isfinite(got).all()                                        # every element was written
-    assert np.array_equal(got.view(np.uint32), runs[1].view(np.uint32))  # two runs: the same bits
-    bound = 2.0 * Kdim * 2.0 ** -24 * mag + 1e-30
-    ratio = np.abs(got.astype(np.float64) - ref) / bound
-    print("wide head (%d, %d, %d): largest |got - ref| / bound = %.4f, largest |got - ref| = %.3e" %
-          (M, Kdim, Cout, ratio.max(), np.abs(got - ref).max()))
-    assert ratio.max() <= 1.0, ratio.max()
+    K.check_forward_on_the_device(*K.gemm_operands(M, Kdim, Cout))
 
 
 @gpu

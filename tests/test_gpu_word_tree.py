@@ -39,68 +39,13 @@ def assert_close(loss, dnet, ref_loss, ref_d):
 @gpu
 @pytest.mark.parametrize("key", sorted(K.SHAPES))
 def test_tree_loss_matches_the_float64_specification(key):
-    from tensorflow_yolo2_amd import engine as E
-    net, truth, ntruth, anchors, size, tree = K.parity_input(key)
-    n = net.shape[0]
-    assert ntruth[0] == 30 and len({(int(t[1] // 32), int(t[0] // 32)) for t in truth[0]}) < 15   # several truths per cell
-    tt = E.WordTreeTables(tree)
-    args = lambda tr=truth: (dev(net), dev(tr), dev(ntruth), anchors, size, tt)
-    # default scales
-    ref_loss, ref_d = K.checked_loss(net, truth, ntruth, anchors, size, tree)
-    loss, dnet = E.yolov2_loss_boxes_tree(*args())
-    assert tuple(dnet.shape) == net.shape
-    assert_close(loss.cpu().numpy(), dnet.cpu().numpy(), ref_loss, ref_d)
-    assert not dnet.cpu().numpy()[ref_d == 0].any()                      # off the paths and in un-owned rows: exactly 0
-    # two calls on the same input: the same bits
-    loss_b, dnet_b = E.yolov2_loss_boxes_tree(*args())
-    assert np.array_equal(bits(loss), bits(loss_b)) and np.array_equal(bits(dnet), bits(dnet_b))
-    # other scales, the area weight and the prior
-    ref2, refd2 = K.checked_loss(net, truth, ntruth, anchors, size, tree, area_weight=True, prior_scale=0.01, **K.NONDEFAULT)
-    sc = dict(K.NONDEFAULT, area_weight=1.0, prior_scale=0.01)
-    l2, d2 = E.yolov2_loss_boxes_tree(*args(), scales=sc)
-    assert_close(l2.cpu().numpy(), d2.cpu().numpy(), ref2, refd2)
-    assert (np.abs(ref2 - ref_loss) > 1e-3 * np.abs(ref_loss)).all()     # (the scale set changed every part)
-    # forward only
-    l3, d3 = E.yolov2_loss_boxes_tree(*args(), need_grad=False, scales=sc)
-    assert d3 is None and np.array_equal(bits(l3), bits(l2))
-    # rows beyond ntruth are not read
-    dirty = truth.copy()
-    for i in range(n):
-        dirty[i, ntruth[i]:] = 123.0
-    l4, _ = E.yolov2_loss_boxes_tree(*args(dirty), need_grad=False)
-    assert np.array_equal(bits(l4), bits(loss))
-    # a class index outside [0, C): the row keeps its other terms and takes no class term, its class gradient is zero
-    own = K.owners(truth, ntruth, anchors, size, net.shape[1])
-    i, r, q, b, _k, k0 = own[0]
-    for value in (float(tree.n), -1.0):
-        bad = truth.copy()
-        bad[i, k0, 4] = value
-        r_bad, rd_bad = K.checked_loss(net, bad, ntruth, anchors, size, tree)
-        l_bad, d_bad = E.yolov2_loss_boxes_tree(*args(bad))
-        assert_close(l_bad.cpu().numpy(), d_bad.cpu().numpy(), r_bad, rd_bad)
-        assert not d_bad.cpu().numpy()[i, r, q, b, 5:].any() and d_bad.cpu().numpy()[i, r, q, b, :5].all()
-        assert r_bad[3] < ref_loss[3] and np.array_equal(bits(l_bad)[:3], bits(loss)[:3])
+    K.check_tree_loss_on_the_device(K.parity_input(key))
 
 
 @gpu
 @pytest.mark.parametrize("key", ["n3_S5_small", "n2_S8_B3_wide"])
 def test_tree_stats_match_the_float64_specification(key):
-    import torch
-    from tensorflow_yolo2_amd import engine as E
-    net, truth, ntruth, anchors, size, tree = K.parity_input(key)
-    tt = E.WordTreeTables(tree)
-    ref = K.checked_stats(net, truth, ntruth, anchors, size, tree)
-    out = torch.full((6,), float("nan"), device="cuda")
-    got = E.yolov2_region_stats_tree(dev(net), dev(truth), dev(ntruth), anchors, size, tt, out=out)
-    assert got is out
-    stats = out.cpu().numpy()
-    print("stats", stats, "reference", ref)
-    np.testing.assert_allclose(stats[:4], ref[:4], rtol=RTOL)
-    assert stats[4] == np.float32(ref[4]) and stats[5] == ref[5] == ntruth.sum()
-    again = E.yolov2_region_stats_tree(dev(net), dev(truth), dev(ntruth), anchors, size, tt).cpu().numpy()
-    assert again.tobytes() == stats.tobytes()                            # two runs: the same bits
-    flat = E.yolov2_region_stats(dev(net), dev(truth), dev(ntruth), anchors, size).cpu().numpy()
-    assert np.delete(flat, 1).tobytes() == np.delete(stats, 1).tobytes() and flat[1] != stats[1]
+    K.check_tree_stats_on_the_device(K.parity_input(key))
 
 
 @gpu
