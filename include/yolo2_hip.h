@@ -368,7 +368,7 @@ int y2_word_tree_head(const float* net, const int* tables, int rows, int num_cla
                       float tree_thresh, float* out, int* top, float* prob, void* stream);
 
 /* ---- The wide head (csrc/wide_head.hip): a 1x1 convolution wider than the executor's 2,048-column row -- YOLO9000's last
- *      layer, 1024 -> 28,269 -- as an operator behind the head stack.  Inference only: no gradient entries exist.
+ *      layer, 1024 -> 28,269 -- as an operator behind the head stack (its gradients and its update: the section below).
  *      One arithmetic: f16 operands, fp32 accumulation on the f16 matrix pipe.  Argument errors of all entries, nothing
  *      launched, named with the entry and the item: a null pointer; K no multiple of 32 or beyond Y2_WIDE_HEAD_MAX_K;
  *      Cout outside 1..Y2_WIDE_HEAD_MAX_COUT; a pointer the kernels read in 16-byte units that is not 16-byte aligned. */
@@ -386,6 +386,41 @@ int y2_wide_head_pack(const float* W, int K, int Cout, void* packed, size_t pack
  * launch, the same bits every run.  Y2_ERR_ARG also: M < 1; more than 2^31 - 1 tiles of 256 x 256. */
 int y2_wide_head_forward(const float* x, const void* packed, const float* bias, int M, int K, int Cout, float* out,
                          void* stream);
+
+/* ---- Training the wide head (csrc/wide_head_train.hip): the two backward products, the bias gradient and Darknet's SGD on
+ *      the layer.  s = grad_scale > 0 is the loss scale of the half-precision modes; every result is an UNSCALED gradient,
+ *      the contract of y2_backward_input.  The argument rules above hold; also Y2_ERR_ARG: M < 1; a grad_scale that is not
+ *      finite and above 0; split < 0; a workspace that is null, too small or not 16-byte aligned where one is needed.  No
+ *      allocation, one stream, no float atomics: partial sums are added in a fixed order, the same bits every run. */
+/* host only, no GPU work: the number of workgroups that share the reduction of each product on a device of `cus` compute
+ * units -- dx's over Cout in steps of 64 (128 x 128 tiles of [M][K]), dW's over M in steps of 64 (128 x 128 tiles of
+ * [K][Cout]): ceil(cus / tiles), at most 64 and at most the steps, then evened out so that every split holds a step. */
+int y2_wide_head_train_plan(int M, int K, int Cout, int cus, int* dx_split, int* dw_split);
+/* the second operand image: f16 [K rounded up to 128][Cout rounded up to 64], Cout contiguous, padding zero -- what the data
+ * gradient reads (the forward image has K contiguous).  _bytes: host only, 0 where K or Cout break the rules; pack2: one
+ * launch, every byte written.  y2_wide_head_sgd_step keeps it current. */
+size_t y2_wide_head_packed2_bytes(int K, int Cout);
+int y2_wide_head_pack2(const float* W, int K, int Cout, void* packed2, size_t packed2_bytes, void* stream);
+/* host only: the workspace of the entry below it.  split: 0 -- the plan's count for the current device; n >= 1 -- that many
+ * (tests and measurements), evened out as the plan's.  One split needs no workspace: 0. */
+size_t y2_wide_head_backward_input_workspace_bytes(int M, int K, int Cout, int split);
+size_t y2_wide_head_backward_filter_workspace_bytes(int M, int K, int Cout, int split);
+/* dx[m][k] = (1/s) sum_c f16(s dy[m][c]) f16(W[k][c]), fp32 accumulation.  dy fp32 [M][Cout], row stride Cout exactly, 4-byte
+ * aligned (the tree loss's output): dword reads under a mask, nothing read past dy + M * Cout.  dx fp32 [M][K], every element
+ * written, nothing behind it.  With more than one split: raw partials [split][M][K] in the workspace, then a finish pass. */
+int y2_wide_head_backward_input(const float* dy, const void* packed2, int M, int K, int Cout, float grad_scale, float* dx,
+                                void* workspace, size_t workspace_bytes, int split, void* stream);
+/* dW[k][c] = (1/s) sum_m f16(x[m][k]) f16(s dy[m][c]), fp32 [K][Cout] (the layout of W), and db[c] = sum_m dy[m][c] in fp32
+ * from the unconverted dy (a launch of its own).  x fp32 [M][K], 16-byte aligned.  Rows behind M contribute zero. */
+int y2_wide_head_backward_filter(const float* x, const float* dy, int M, int K, int Cout, float grad_scale, float* dW, float* db,
+                                 void* workspace, size_t workspace_bytes, int split, void* stream);
+/* Darknet's SGD (y2_sgd_step's update; utils/solver.py sgd_step) on W [K][Cout] with weight decay and on b [Cout] without,
+ * gradients times grad_mult, accum = K * Cout + Cout slots (W's, then b's) -- and both operand images rewritten from the new
+ * W in the same launch, padding zero.  ctrl NULL: `lr` is the rate.  ctrl: the control block as it stands (the "next" member
+ * of a joint step: found_inf set -- nothing moves; else ctrl.lr_t applies); this entry never advances it. */
+int y2_wide_head_sgd_step(float* W, float* b, float* accum, const float* dW, const float* db, int K, int Cout, void* packed,
+                          size_t packed_bytes, void* packed2, size_t packed2_bytes, const void* ctrl, float lr, float momentum,
+                          float decay, float grad_mult, void* stream);
 
 /* ---- ResNet-50 backbone swap (src/yolo2_nets/tf_resnet.py:12-32, src/pascal/pascal_train_resnet.py:37-50):
  *      graph-level operators on fp32 NHWC tensors that the conv-BN-leaky stacks do not have.  The 1x1 / 3x3

@@ -112,6 +112,14 @@ SIGNATURES = {
     "y2_wide_head_packed_bytes": (_sz, [_i, _i]),
     "y2_wide_head_pack": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
     "y2_wide_head_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "y2_wide_head_train_plan": (_i, [_i, _i, _i, _i, _pi, _pi]),
+    "y2_wide_head_packed2_bytes": (_sz, [_i, _i]),
+    "y2_wide_head_pack2": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
+    "y2_wide_head_backward_input_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "y2_wide_head_backward_filter_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "y2_wide_head_backward_input": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _sz, _i, _vp]),
+    "y2_wide_head_backward_filter": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _i, _vp]),
+    "y2_wide_head_sgd_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp, _f, _f, _f, _f, _vp]),
     "y2_batch_norm_forward": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp]),
     "y2_batch_norm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "y2_subsample": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

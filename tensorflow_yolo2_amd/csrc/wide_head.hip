@@ -1,5 +1,5 @@
 // The wide head: a 1x1 convolution whose output row is wider than the executor's 2,048 columns (YOLO9000's last layer,
-// 1024 -> 28,269), as an operator of its own behind the head stack.  Inference only.
+// 1024 -> 28,269), as an operator of its own behind the head stack.  This file is its forward; wide_head_train.hip trains it.
 //
 //   out[m][c] = bias[c] + sum_k f16(x[m][k]) * f16(W[k][c])        fp32 accumulate on v_mfma_f32_32x32x16_f16
 //

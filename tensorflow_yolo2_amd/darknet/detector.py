@@ -61,7 +61,7 @@ def read_data_set(error, data_path, cfg_path=None, need=()):
     rec = None
     if cfg_path is not None:
         try:
-            rec = darknet_cfg.load(cfg_path)
+            rec = darknet_cfg.load_graph(cfg_path)[0]       # a wide last layer (YOLO9000's) included: every command takes it
         except (OSError, ValueError) as e:
             error("%s" % e)
         if rec.classes != data.classes:

@@ -1168,9 +1168,11 @@ WIDE_HEAD_DTYPES = ("f16", "fp8")    # the model modes a wide head runs behind: 
 
 class WideHead:
     """a 1x1 convolution wider than a stack's 2,048-column row (YOLO9000's last layer, 1024 -> 28,269), run behind the
-    head stack by csrc/wide_head.hip: out[m][c] = b[c] + sum_k f16(x[m][k]) f16(W[k][c]), fp32 accumulation.  Inference
-    only.  Holds the fp32 filters [1][1][K][Cout] and bias (what export() returns and a `.weights` file takes back), the
-    packed f16 operand image the kernel reads, and one output buffer per M"""
+    head stack by csrc/wide_head.hip: out[m][c] = b[c] + sum_k f16(x[m][k]) f16(W[k][c]), fp32 accumulation, and trained by
+    csrc/wide_head_train.hip (backward; WideHeadSGD steps it).  Holds the fp32 filters [1][1][K][Cout] and bias (what
+    export() returns and a `.weights` file takes back), the two packed f16 operand images the kernels read -- `packed`
+    [Cp][Kp] for the forward pass, `packed2` [Kp2][Cp2] for the data gradient -- one output buffer per M and, once
+    backward() has run, the gradients dW / db, one dx buffer per M and the workspace of the split reductions"""
 
     def __init__(self, K, Cout, device="cuda:0"):
         self.lib = _lib.load()
@@ -1182,11 +1184,16 @@ class WideHead:
         self.W = torch.zeros((1, 1, self.K, self.Cout), dtype=torch.float32, device=self.device)
         self.b = torch.zeros(self.Cout, dtype=torch.float32, device=self.device)
         self.packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self._out = {}
+        self.packed2 = torch.empty(self.lib.y2_wide_head_packed2_bytes(self.K, self.Cout), dtype=torch.uint8,
+                                   device=self.device)
+        self.dW = self.db = None             # allocated by the first backward(): a detector's operator holds none
+        self._out, self._dx, self._ws = {}, {}, None
         self._pack()
 
     def _pack(self):
         check(self.lib.y2_wide_head_pack(_ptr(self.W), self.K, self.Cout, _ptr(self.packed), self.packed.numel(), _stream()))
+        check(self.lib.y2_wide_head_pack2(_ptr(self.W), self.K, self.Cout, _ptr(self.packed2), self.packed2.numel(),
+                                          _stream()))
 
     def load(self, W, b):
         """W: anything numpy reads of K * Cout values in the order [K][Cout] (a 1x1 layer's [1][1][K][Cout]); b [Cout]"""
@@ -1200,6 +1207,12 @@ class WideHead:
     def export(self):
         """-> {"W": [1][1][K][Cout], "b": [Cout]} as numpy arrays: the fp32 values load() was given"""
         return {"W": self.W.cpu().numpy().copy(), "b": self.b.cpu().numpy().copy()}
+
+    def export_grads(self):
+        """-> {"W": [1][1][K][Cout], "b": [Cout]}: the gradients the last backward() left"""
+        if self.dW is None:
+            raise ValueError("WideHead.export_grads: backward() has not run")
+        return {"W": self.dW.cpu().numpy().copy(), "b": self.db.cpu().numpy().copy()}
 
     def forward(self, x, out=None):
         """x: fp32 [..., K] on the device, contiguous -> fp32 [M][Cout], M the product of the leading sizes (in `out`, a
@@ -1216,6 +1229,86 @@ class WideHead:
         check(self.lib.y2_wide_head_forward(_ptr(x), _ptr(self.packed), _ptr(self.b), m, self.K, self.Cout, _ptr(out),
                                             _stream()))
         return out
+
+    def backward(self, x, dy, grad_scale=1.0, want_dx=True, _split=(0, 0)):
+        """x: fp32 [..., K], the input forward() was given; dy: fp32 of M * Cout elements, the gradient at its output,
+        UNSCALED; grad_scale: the loss scale the operands are rounded under.  Fills self.dW [1][1][K][Cout] and self.db
+        [Cout] (unscaled) and returns dx fp32 [M][K] in this operator's buffer for that M (None unless want_dx).
+        _split: (dx, dW) split counts in place of the plan's, 0 the plan's (tests and measurements)"""
+        _dev(x, torch.float32, "x")
+        _dev(dy, torch.float32, "dy")
+        assert x.shape[-1] == self.K, (tuple(x.shape), self.K)
+        m = x.numel() // self.K
+        assert dy.numel() == m * self.Cout, (tuple(dy.shape), m, self.Cout)
+        lib, (sx, sw) = self.lib, _split
+        if self.dW is None:
+            self.dW, self.db = torch.empty_like(self.W), torch.empty_like(self.b)
+        need = lib.y2_wide_head_backward_filter_workspace_bytes(m, self.K, self.Cout, sw)
+        if want_dx:
+            need = max(need, lib.y2_wide_head_backward_input_workspace_bytes(m, self.K, self.Cout, sx))
+        if need and (self._ws is None or self._ws.numel() < need):
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        nws = self._ws.numel() if self._ws is not None else 0
+        check(lib.y2_wide_head_backward_filter(_ptr(x), _ptr(dy), m, self.K, self.Cout, float(grad_scale), _ptr(self.dW),
+                                               _ptr(self.db), _ptr(self._ws), nws, sw, _stream()))
+        if not want_dx:
+            return None
+        dx = self._dx.get(m)
+        if dx is None:
+            dx = self._dx[m] = torch.empty((m, self.K), dtype=torch.float32, device=self.device)
+        check(lib.y2_wide_head_backward_input(_ptr(dy), _ptr(self.packed2), m, self.K, self.Cout, float(grad_scale), _ptr(dx),
+                                              _ptr(self._ws), nws, sx, _stream()))
+        return dx
+
+
+FP32_MAX = 3.4028234663852886e38
+
+
+class WideHeadSGD:
+    """Darknet's solver on a WideHead, next to DarknetSGD over the stacks of the same graph: momentum SGD, weight decay on
+    W only, one launch that also rewrites both operand images (y2_wide_head_sgd_step).  `solver`: a utils.solver.Solver;
+    `scaler`: the LossScaler the stacks' optimizers share, or None.  With a scaler the layer is a "next" member of the joint
+    step: scan() ORs its own overflow test into the shared flag (a f16(s dy) that overflowed is an inf or NaN in dW: a
+    y2_range_check over dW and db at fp32's maximum), step() uses the control block as the first member's call left it and
+    never advances it.  Without one the host counts the steps and computes the rate.  accum: K * Cout + Cout slots"""
+
+    def __init__(self, wide, solver, scaler=None):
+        if solver is None:
+            raise ValueError("WideHeadSGD needs Darknet's solver (utils.solver.Solver): Adam on the wide head is not built")
+        self.wide, self.solver, self.scaler = wide, solver.validate(), scaler
+        self._record = _lib.sgd_solver(self.solver)
+        self.accum = torch.zeros(wide.K * wide.Cout + wide.Cout, dtype=torch.float32, device=wide.device)
+        self.t = 0
+
+    def scan(self):
+        w = self.wide
+        if self.scaler is not None and w.dW is not None:
+            for g in (w.dW, w.db):
+                check(w.lib.y2_range_check(_ptr(g), g.numel(), FP32_MAX, _ptr(self.scaler.ctrl), _stream()))
+
+    def step(self, grad_mult=1.0, joint="next"):
+        w = self.wide
+        if w.dW is None:
+            raise ValueError("WideHeadSGD.step: WideHead.backward() has not run")
+        self.t += 1
+        if self.scaler is not None:
+            if joint != "next":
+                raise ValueError("WideHeadSGD.step(joint=%r): under a shared scaler the wide head is a \"next\" member" % (joint,))
+            ctrl, rate = _ptr(self.scaler.ctrl), 0.0
+        else:
+            r = C.c_float(0.0)
+            check(w.lib.y2_solver_rate(C.byref(self._record), self.t, C.byref(r)))
+            ctrl, rate = C.c_void_p(0), r.value
+        check(w.lib.y2_wide_head_sgd_step(_ptr(w.W), _ptr(w.b), _ptr(self.accum), _ptr(w.dW), _ptr(w.db), w.K, w.Cout,
+                                          _ptr(w.packed), w.packed.numel(), _ptr(w.packed2), w.packed2.numel(), ctrl, rate,
+                                          self.solver.momentum, self.solver.decay, grad_mult, _stream()))
+
+    def export_state(self):
+        return {"accum": self.accum.cpu().numpy().copy(), "t": int(self.t)}
+
+    def load_state(self, st):
+        self.accum.copy_(torch.as_tensor(np.asarray(st["accum"], np.float32)).to(self.accum.device))
+        self.t = int(st["t"])
 
 
 def nms(boxes, scores, classes=None, iou_thresh=0.5, score_thresh=0.0, max_out=100, class_aware=False):

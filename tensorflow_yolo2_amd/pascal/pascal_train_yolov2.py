@@ -58,7 +58,9 @@ darknet, --multi-scale where the file says random=1 (--single-scale keeps one si
 exposure, solver values, width (--size) and batch (--batch).  A flag given on the command line beats the file; the resolved
 recipe is printed once.  It goes with --darknet-weights, --darknet-backbone or a fresh model, and with a --ckpt-dir of
 .weights snapshots; not with --topology paper, --imagenet-ckpt-dir, --anchors or a --ckpt-dir of .npz snapshots.  The image
-set's class count must be the file's.
+set's class count must be the file's.  A file whose last convolution is wider than a stack's row (YOLO9000's 28,269
+filters) loads under wide_head=True by itself (darknet_cfg.load_graph; `map=` stays unread): that layer trains as
+engine.WideHead under --dtype f16, and the train_iter_<i>.weights snapshots hold it as the file's last layer.
 
 --region-stats (with --box-labels or --cfg) prints Darknet's region-layer line for the last step beside the 10-iteration
 line: `Region Avg IOU, Class, Obj, No Obj, Avg Recall, count`, computed on the device from the step's head output and its
@@ -235,6 +237,7 @@ def apply_cfg(ap, args):
     """--cfg: read the file (args.cfg_record; None without the flag), refuse what contradicts it, and fill every flag that
     was not given from it -- then today's defaults, with or without a file"""
     args.cfg_record = args.cfg_graph = None
+    args.wide_head = False
     pick = lambda v, dv: dv if v is None else v
     if args.single_scale and not args.cfg:
         ap.error("--single-scale needs --cfg")
@@ -249,10 +252,15 @@ def apply_cfg(ap, args):
         if args.width_div != 1:
             ap.error("--cfg holds the widths: not with --width-div")
         try:
-            rec = args.cfg_record = darknet_cfg.load(args.cfg)
-            args.cfg_graph = darknet_cfg.compile_graph(rec, 1024 if args.dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH)
+            # a last layer wider than a stack's row (YOLO9000's) loads under wide_head=True and trains as engine.WideHead
+            rec, args.cfg_graph, args.wide_head = darknet_cfg.load_graph(
+                args.cfg, 1024 if args.dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH)
+            args.cfg_record = rec
         except (OSError, ValueError) as e:
             ap.error("--cfg: %s" % e)
+        if args.wide_head and args.dtype != "f16":
+            ap.error("--cfg %s has a wide head (%d filters), which trains under --dtype f16 only: not %s" %
+                     (args.cfg, args.cfg_graph.file_layers[-1][2], args.dtype))
         found = {"chain": "tiny", "passthrough": "darknet"}[args.cfg_graph.shape]
         if args.topology not in (None, found):
             ap.error("--topology %s, but --cfg %s describes the %s graph" % (args.topology, args.cfg, found))
@@ -372,7 +380,8 @@ def main(argv=None, dataset=None):
     if rec is not None:
         trainer = yolov2.YOLOv2DarknetTrainer.from_cfg(rec, args.batch, first, dtype=args.dtype, seed=args.seed,
                                                        solver=args.solver_record, prior_images=args.prior_images,
-                                                       tree=args.tree_record, tree_thresh=args.hier_thresh)
+                                                       tree=args.tree_record, tree_thresh=args.hier_thresh,
+                                                       wide_head=getattr(args, "wide_head", False))
     else:
         trainer = TRAINERS[args.topology](args.batch, first, num_class=imdb.num_class, anchors=anchors, dtype=args.dtype,
                                           seed=args.seed, width_div=args.width_div, area_weight=args.area_weight,

@@ -315,6 +315,24 @@ def load(path, wide_head=False):
         return parse(f.read(), str(path), wide_head)
 
 
+def load_graph(path, max_out=MAX_OUT_WIDTH):
+    """a cfg file -> (DarknetCfg, Graph, wide_head) for a caller that takes either kind of file: read under the default
+    keyword where that succeeds; else under wide_head=True, and only where the graph then IS wide -- every other file keeps
+    the refusal the default keyword gives it (a `map=` on a narrow model, a width the executor does not run)"""
+    try:
+        record = load(path)
+        return record, compile_graph(record, max_out), False
+    except ValueError as refusal:
+        try:
+            record = load(path, True)
+            graph = compile_graph(record, max_out, True)
+        except ValueError:
+            raise refusal
+        if not graph.wide:
+            raise refusal
+        return record, graph, True
+
+
 def as_record(record_or_path, wide_head=False):
     return record_or_path if isinstance(record_or_path, DarknetCfg) else load(record_or_path, wide_head)
 

@@ -96,7 +96,8 @@ def _paper_concat(fine, coarse, out=None):
 # are 1x1 in a `.weights` file and run 3x3 on their centre tap; narrow: (stem layer, filters in the file) of the layers
 # that run wider than the file holds them, the padded filters and the next layer's padded input channels exactly zero.
 # anchors: the published anchors of the graph.  wide: None, or (K, Cout) of the last convolution where it is wider than a
-# stack's row and runs as engine.WideHead behind the head stack (a cfg under wide_head=True; inference only).
+# stack's row and runs as engine.WideHead behind the head stack (a cfg under wide_head=True); the head stack then ends in
+# an ordinary conv-BN-leaky layer, and the rules for a linear last layer do not apply to it.
 _Topology = collections.namedtuple("_Topology", "name specs heights bn_eps slopes train_options head_statistics "
                                                 "darknet_input concat concat_backward cf_stack pool pool_backward "
                                                 "centre_tap narrow anchors wide", defaults=(None,))
@@ -133,26 +134,32 @@ def _topology(name):
     return _TOPOLOGY[name]
 
 
-def _cfg_topology(record, dtype, wide_head=False):
+def _cfg_topology(record, dtype, wide_head=False, training=False):
     """the _Topology of a Darknet cfg (utils/darknet_cfg.py) -> (topology, record): one more way to produce the record the
     code below reads, under the name of the shape it has -- "tiny" for a chain, "darknet" for a passthrough.  A cfg that
     describes yolov2-voc.cfg or tiny-yolo-voc.cfg gives the named topology's stacks, options and ops.  wide_head: the
     keyword of utils/darknet_cfg.py -- `map=` is admitted and a last convolution wider than a stack's row becomes the
-    topology's `wide` operator; without it a record that carries `map` is refused here (the trainers' case)"""
+    topology's `wide` operator; without it a record that carries `map` is refused here.  training: the caller is a
+    trainer, and a wide head trains behind dtype 'f16' only"""
     from ..utils import darknet_cfg
     record = darknet_cfg.as_record(record, wide_head)
     if record.map is not None and not wide_head:
-        raise ValueError("%s: map=%s: the class map of YOLO9000 belongs with its wide head, which does not train; "
-                         "YOLOv2Detector.from_cfg(..., wide_head=True) runs it" % (record.path, record.map))
+        raise ValueError("%s: map=%s: the class map of YOLO9000 belongs with its wide head; "
+                         "from_cfg(..., wide_head=True) admits both" % (record.path, record.map))
     graph = darknet_cfg.compile_graph(record, 1024 if dtype == "f32" else darknet_cfg.MAX_OUT_WIDTH, wide_head)
     n, head = len(graph.specs), graph.head_layers
     wide = None
     if graph.wide:
         from .. import _lib
+        if training and _lib.DTYPES.get(dtype, dtype) != _lib.Y2_F16:
+            raise ValueError("%s: dtype %r with a wide head (%d filters): the wide head trains behind a model of dtype 'f16' "
+                             "only -- its products round both operands to f16 under the stacks' loss scale%s" %
+                             (record.path, dtype, graph.file_layers[-1][2],
+                              ", and 'fp8' does not train anywhere" if dtype in ("fp8", "mxfp8") else ""))
         if _lib.DTYPES.get(dtype, dtype) not in (_lib.Y2_F16, _lib.Y2_FP8):
             raise ValueError("%s: dtype %r with a wide head (%d filters): the wide head has one arithmetic, f16 operands "
                              "with fp32 accumulation, and runs behind a model of dtype 'f16' or 'fp8' only -- the exact "
-                             "modes exist for training parity, and this head does not train" %
+                             "modes exist for parity with the reference, which has no such layer" %
                              (record.path, dtype, graph.file_layers[-1][2]))
         wide = (graph.file_layers[-1][1], graph.file_layers[-1][2])
         slopes = (None,) * (n - 1) + ([0.1] * (head - 1),)                  # the head stack: conv-BN-leaky throughout
@@ -247,8 +254,8 @@ def _forward(topo, nets, buffers, images, training, update_moving, out=None, wid
         for route in nets[2:-1]:                                            # "darknet": the 1x1 route, [N,2S,2S,64]
             passed = route.forward(passed, training, training, update_moving=update_moving)
         cat = topo.concat(passed, coarse, out=cat_buf)                      # [N,S,S,4*cf+1024], reorganised map first
-    if wide is not None:
-        return wide.forward(head.forward(cat, False, False), out=out), fine
+    if wide is not None:                                                    # the head stack is an ordinary stack here
+        return wide.forward(head.forward(cat, training, training, update_moving=update_moving), out=out), fine
     out = head.forward(cat, training, training and topo.head_statistics, out=out, update_moving=update_moving)
     return out, fine                                                        # [N,S,S,B*(5+C)]
 
@@ -413,7 +420,29 @@ class _Trainer:
         self.ctx, self.reducers, self._buffers = {}, {}, {}
         self.opts = None
         self.default_size = image_size
+        # the wide last layer of a cfg under wide_head=True (engine.WideHead; None on every other model), trained by Darknet's
+        # solver as one more member of the joint step (engine.WideHeadSGD on the stacks' scaler)
+        self.wide = self.wide_opt = None
+        if self._topo.wide is not None:
+            if self.solver is None:
+                raise ValueError("a wide head (%d filters) trains under Darknet's solver only: pass solver= (Adam on the "
+                                 "wide layer is not built)" % self._topo.wide[1])
+            self._refuse_wide_replicas()
         self._nets(image_size)
+        if self._topo.wide is not None:
+            K, Cout = self._topo.wide
+            self.wide = E.WideHead(K, Cout, device)
+            rng = np.random.default_rng(seed + len(self.nets))             # as YOLOv2Detector draws them
+            self.wide.load(rng.standard_normal((K, Cout), np.float32) * np.float32(1.0 / np.sqrt(K)),
+                           np.zeros(Cout, np.float32))
+            self.wide_opt = E.WideHeadSGD(self.wide, self.solver, self.opts[0].scaler)
+
+    def _refuse_wide_replicas(self):
+        from ..trainer import _dist
+        dist = _dist()
+        if dist is not None and dist.get_world_size() > 1:
+            raise ValueError("a wide head does not train data parallel (world size %d): no reducer for its %d x %d filter "
+                             "gradient is built" % (dist.get_world_size(), self._topo.wide[0], self._topo.wide[1]))
 
     def _nets(self, size):
         if size not in self.ctx:
@@ -460,7 +489,8 @@ class _Trainer:
         """images [N,size,size,3] -> (raw grid [N,S,S,B,5+C], fine [N,2S,2S,Cf]).  "darknet": uint8 BGR pixels or fp32 RGB
         in [0, 1], and the last layer runs on its moving statistics in either mode"""
         size = int(images.shape[1])
-        out, fine = _forward(self._topo, self._nets(size), self._buffers[size], images, training, update_moving)
+        out, fine = _forward(self._topo, self._nets(size), self._buffers[size], images, training, update_moving,
+                             wide=self.wide)
         return out.view(self.batch, size // 32, size // 32, self.B, 5 + self.num_class), fine
 
     def prior_on(self, iteration=None):
@@ -542,8 +572,14 @@ class _Trainer:
             if stats is not None:
                 E.yolov2_region_stats_tree(grid.contiguous(), truth, ntruth, self._anchors_dev, size, self.tree, out=stats)
         self.last_dnet = dnet                                # the head's output gradient of this step (tests read it)
-        world = self.backward(dnet, fine, size)
         scaler = self.opts[0].scaler
+        if self.wide is not None:
+            # the wide layer's gradients from the head stack's output of this pass, under the stacks' loss scale; what it
+            # hands down is the head stack's output gradient (kept in last_wide_x / last_wide_dx: tests read them)
+            self._refuse_wide_replicas()
+            self.last_wide_x = nets[-1]._out
+            dnet = self.last_wide_dx = self.wide.backward(self.last_wide_x, dnet, scaler.scale)
+        world = self.backward(dnet, fine, size)
         for opt, net in zip(self.opts, nets):
             opt.net = net
             if scaler is not None:
@@ -557,9 +593,13 @@ class _Trainer:
         # the guarded updates: all of them or none
         for i, net in enumerate(nets):
             scaler.scan(net, more=(i > 0))
+        if self.wide_opt is not None:
+            self.wide_opt.scan()
         self._mask_gradients(nets)
         for i, opt in enumerate(self.opts):
             opt.step(grad_mult=1.0 / world, joint="first" if i == 0 else "next")
+        if self.wide_opt is not None:
+            self.wide_opt.step(grad_mult=1.0 / world, joint="next")
         return loss
 
     def flops_per_step(self, size=None, mfma_launches_only=False):
@@ -623,7 +663,13 @@ class YOLOv2DarknetTrainer(_Trainer):
     head with core_layers = 2.  Its first layer's filters 16 .. 31 and its second layer's input channels 16 .. 31 are the
     zero padding of yolov2_tiny_specs: a fresh model starts with them zero and their gradients (W, b, gamma, beta of the
     padded filters, W of the padded input channels) are zeroed every step, so they stay bit-zero under both optimizers,
-    weight decay included, and the model stays writable."""
+    weight decay included, and the model stays writable.
+
+    from_cfg(..., wide_head=True): a cfg whose last convolution is wider than a stack's row (YOLO9000's 28,269 filters).
+    The head stack then ends in an ordinary conv-BN-leaky layer -- none of the last-layer rules above apply to it -- and the
+    linear layer is `self.wide` (engine.WideHead), trained by `self.wide_opt` (engine.WideHeadSGD) as the last member of
+    the joint step: dtype "f16", Darknet's solver, one process.  step() keeps the operator's input and the gradient it
+    hands down in last_wide_x / last_wide_dx."""
 
     topology = "darknet"
     keeps_backward = True
@@ -642,13 +688,14 @@ class YOLOv2DarknetTrainer(_Trainer):
 
     @classmethod
     def from_cfg(cls, record_or_path, batch=None, image_size=None, dtype="f16", seed=0, device="cuda:0", solver=None,
-                 prior_images=None, tree=None, tree_thresh=None):
+                 prior_images=None, tree=None, tree_thresh=None, wide_head=False):
         """the train step of a Darknet cfg (utils/darknet_cfg.py: a record or a file): its graph, widths, class count and
         anchors; its [net] solver; its [region] scales (coord_scale ... thresh); area_weight and prior_images 12800, which
         Darknet hard-codes; its word tree (load_cfg_tree) and tree_thresh.  batch and image_size default to the file's;
         solver / prior_images / tree / tree_thresh: a caller's own in place of the file's (a flag given on the command
-        line)"""
-        topo, record = _cfg_topology(record_or_path, dtype)
+        line).  wide_head=True admits YOLO9000's file: `map=` (kept unread) and a last layer wider than a stack's row,
+        which trains as engine.WideHead under engine.WideHeadSGD -- dtype 'f16' only, one process only"""
+        topo, record = _cfg_topology(record_or_path, dtype, wide_head, training=True)
         return cls(record.batch if batch is None else batch, record.size if image_size is None else image_size,
                    num_class=record.classes, anchors=record.anchors, dtype=dtype, seed=seed, device=device,
                    scales=dict(record.scales), area_weight=True,
@@ -675,6 +722,8 @@ class YOLOv2DarknetTrainer(_Trainer):
             co2 = stem.spec[l + 1][2]
             params[l + 1] = dkw.pad_layer_params(dkw.strip_layer_params(params[l + 1], n_file, co2, check=False), co, co2)
         stem.load_params(params)
+        if self._topo.wide is not None:
+            return                   # the head stack ends in an ordinary conv-BN-leaky layer: the linear layer is the operator
         params = head.export_params()
         n = params[-1]["b"].size
         params[-1].update(gamma=np.full(n, np.sqrt(1.0 + np.float64(self.bn_eps)), np.float32),
@@ -698,6 +747,8 @@ class YOLOv2DarknetTrainer(_Trainer):
                 E.zero_(g[key][n_file:])
             for tap in stem.layer_views(l + 1, grads=True)["W"].flatten(0, 1):     # [k k][ci][co]: the padded inputs
                 E.zero_(tap[n_file:])
+        if self._topo.wide is not None:
+            return                   # an ordinary last layer: its gamma and beta train
         g = head.layer_views(head.num_layers - 1, grads=True)
         E.zero_(g["gamma"])
         E.zero_(g["beta"])
@@ -708,7 +759,7 @@ class YOLOv2DarknetTrainer(_Trainer):
         `.weights` file carries no optimizer state: moments and the loss scale start afresh, as in Darknet"""
         self.iteration = int(iteration)
         if self.solver is not None:
-            for opt in self.opts:
+            for opt in self.opts + ([self.wide_opt] if self.wide_opt is not None else []):
                 opt.t = self.iteration
             scaler = self.opts[0].scaler
             if scaler is not None:
