@@ -577,6 +577,20 @@ int y2_conv2d(const float* x, const float* w, const float* bias, float* y, int N
 int y2_conv2d_backward(const float* x, const float* w, const float* dy, float* dx, float* dw, int N, int H,
                        int W, int Cin, int Cout, int k, int dtype, void* workspace, void* stream);
 
+/* ---- launch log: which kernel form every forward / dgrad convolution and every weight gradient took.  Host memory
+ *      only (it never touches the GPU), process-wide, off by default; while off a launch pays one branch.  A record is
+ *      Y2_LAUNCH_LOG_INTS ints -- exactly what selects a kernel instantiation or a distinct code path inside one:
+ *        convolution     {0, launch dtype, is_dgrad, kernel kind, tile / config, K split (0/1),
+ *                         epilogue: 0 plain, 1 batch-norm statistics, 2 fused batch-norm-backward reduce}
+ *        weight gradient {1, launch dtype, kernel kind, tile, split-K (0/1), route of the partial sums, 0}
+ *      (kinds, tiles and routes: the enums of csrc/kernels.h).  The folded-inference epilogue is not part of the key.
+ *      y2_launch_log_enable(1) clears the log and starts recording, (0) stops (the records stay readable);
+ *      y2_launch_log_read copies min(logged, max_records) records to the host array `out` (may be NULL with 0) and
+ *      returns the number logged. */
+#define Y2_LAUNCH_LOG_INTS 7
+int y2_launch_log_enable(int enable);
+int y2_launch_log_read(int* out, int max_records);
+
 /* ---- MXFP8 quantiser (the Y2_FP8 number format above): fp32 x [rows][C], C % 32 == 0 -> e4m3fn elements q [rows][C]
  *      + E8M0 scales [rows][C / 32] (one per 32 consecutive values of a row), device buffers */
 int y2_mx_quantize(const float* x, size_t rows, int C, uint8_t* q, uint8_t* scales, void* stream);

@@ -20,6 +20,7 @@ Y2_F32, Y2_F16, Y2_BF16, Y2_F16X2, Y2_F16X2F, Y2_FP8 = 0, 1, 2, 3, 4, 5
 # modes whose gradients ride on the f16 loss scale (dY is stored in f16 planes)
 LOSS_SCALED = (Y2_F16, Y2_F16X2, Y2_F16X2F)
 Y2_TAIL_NONE, Y2_TAIL_AVGPOOL = 0, 1
+LAUNCH_LOG_INTS = 7       # Y2_LAUNCH_LOG_INTS: ints per record of y2_launch_log_read
 DTYPES = {"f32": Y2_F32, "fp32": Y2_F32, "float32": Y2_F32,
           "f16": Y2_F16, "fp16": Y2_F16, "float16": Y2_F16,
           "bf16": Y2_BF16, "bfloat16": Y2_BF16,
@@ -152,6 +153,8 @@ SIGNATURES = {
     "y2_conv2d_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "y2_conv2d": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "y2_conv2d_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "y2_launch_log_enable": (_i, [_i]),
+    "y2_launch_log_read": (_i, [_pi, _i]),
     "y2_mx_quantize": (_i, [_vp, _sz, _i, _vp, _vp, _vp]),
     "y2_resize_bilinear_u8_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "y2_letterbox_geometry": (_i, [_i, _i, _i, _pi]),

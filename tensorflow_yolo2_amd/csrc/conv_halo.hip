@@ -15,8 +15,11 @@
 // counted vmcnt and raw s_barrier (loads stay in flight across the barrier).
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
+#include <mutex>
+#include <vector>
 
 #include "common.h"
 #include "conv_epilogue.h"
@@ -627,6 +630,30 @@ ConvPlan plan_conv(int dtype, const ConvArgs& a) {
     return p;
 }
 
+// ---- the launch log (kernels.h): a host vector behind a mutex, touched only while the log is on
+std::atomic<bool> g_launch_log_on{false};
+static std::mutex g_launch_log_mu;
+static std::vector<int> g_launch_log;
+constexpr size_t kLaunchLogMaxRecords = (size_t)1 << 20;
+void launch_log_append(int op, int dtype, int f2, int f3, int f4, int f5, int f6) {
+    std::lock_guard<std::mutex> lock(g_launch_log_mu);
+    if (g_launch_log.size() >= kLaunchLogMaxRecords * Y2_LAUNCH_LOG_INTS) return;
+    const int rec[Y2_LAUNCH_LOG_INTS] = {op, dtype, f2, f3, f4, f5, f6};
+    g_launch_log.insert(g_launch_log.end(), rec, rec + Y2_LAUNCH_LOG_INTS);
+}
+void launch_log_enable(bool on) {
+    std::lock_guard<std::mutex> lock(g_launch_log_mu);
+    if (on) g_launch_log.clear();
+    g_launch_log_on.store(on, std::memory_order_relaxed);
+}
+int launch_log_read(int* out, int max_records) {
+    std::lock_guard<std::mutex> lock(g_launch_log_mu);
+    const size_t n = g_launch_log.size() / Y2_LAUNCH_LOG_INTS;
+    const size_t c = std::min(n, (size_t)std::max(max_records, 0));
+    if (out && c) memcpy(out, g_launch_log.data(), c * Y2_LAUNCH_LOG_INTS * sizeof(int));
+    return (int)n;
+}
+
 hipError_t launch_conv(int dtype, const ConvArgs& a0, hipStream_t s, int filter_layout) {
     // XCD-aware workgroup order: measured +1..4 % on every 3x3 layer up to 104x104 (common.h xcd_block)
     static const int xcd_mode = getenv("Y2_XCD_CONV") ? atoi(getenv("Y2_XCD_CONV")) : 1;
@@ -634,6 +661,8 @@ hipError_t launch_conv(int dtype, const ConvArgs& a0, hipStream_t s, int filter_
     a.xcd = xcd_mode;
     const ConvPlan p = plan_conv(dtype, a);
     if (filter_layout != p.filter_layout) return hipErrorInvalidValue;     // the filters were packed for another kernel
+    if (g_launch_log_on.load(std::memory_order_relaxed))
+        launch_log_append(0, dtype, a.is_dgrad, (int)p.kind, p.cfg, p.ks_depth > 1, a.bw_psum ? 2 : (a.part_mean ? 1 : 0));
     switch (p.kind) {
         case CK_RF: case CK_RFN: return launch_conv_rf(dtype, p, a, s);
         case CK_HALOQ: case CK_HALOQ_KS: return launch_conv_haloq(dtype, p, a, s);

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <atomic>
 #include "../../include/yolo2_hip.h"
 
 namespace y2 {
@@ -132,6 +133,17 @@ struct ConvTile {
 ConvPlan plan_conv(int dtype, const ConvArgs& a);
 // plan_conv + the launch; filter_layout = the layout the filters were packed in (hipErrorInvalidValue unless the plan's)
 hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t s, int filter_layout);
+// ---- launch log (conv_halo.hip; host memory only, y2_launch_log_* in yolo2_hip.h): while it is on, launch_conv and
+// launch_wgrad_auto -- the only two doors to these kernels -- append the form key of each launch: what selects a kernel
+// instantiation or a distinct code path inside one.  Off (the default) it costs the launchers one branch.
+//   conv : {0, launch dtype, is_dgrad, ConvPlan.kind, ConvPlan.cfg, K split, epilogue (0 plain, 1 BN statistics, 2 fused
+//           BN-backward reduce)}
+//   wgrad: {1, launch dtype, WgradPlan.kind, WgradPlan.tile, splitk > 1, WgradPlan.sum, 0}
+// (the folded-inference epilogue, aff_*, is not part of the key: DESIGN section 4)
+extern std::atomic<bool> g_launch_log_on;
+void launch_log_append(int op, int dtype, int f2, int f3, int f4, int f5, int f6);
+void launch_log_enable(bool on);                        // on: clears the log first
+int launch_log_read(int* out, int max_records);         // -> records logged; copies min(that, max_records) of them
 // the family launchers (launch_conv's switch): hipErrorInvalidValue for a plan they cannot run
 hipError_t launch_conv_rf(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);
 hipError_t launch_conv_haloq(int dtype, const ConvPlan& p, const ConvArgs& a, hipStream_t s);

@@ -551,6 +551,15 @@ extern "C" {
 const char* y2_last_error(void) { return g_err.c_str(); }
 int y2_version(void) { return 1; }
 
+int y2_launch_log_enable(int enable) {
+    launch_log_enable(enable != 0);
+    return Y2_OK;
+}
+int y2_launch_log_read(int* out, int max_records) {
+    if (max_records < 0 || (max_records > 0 && !out)) return fail(Y2_ERR_ARG, "y2_launch_log_read: bad buffer");
+    return launch_log_read(out, max_records);
+}
+
 int y2_darknet19_spec(int kind, int output_filter, int* spec, int max_layers) {
     static const int core[18][4] = {
         {3, 3, 32, 1},     {3, 32, 64, 1},    {3, 64, 128, 0},   {3, 128, 64, 0},   {3, 64, 128, 1},

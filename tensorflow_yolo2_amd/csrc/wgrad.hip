@@ -520,6 +520,8 @@ hipError_t launch_wgrad_auto(int dtype, const WgradArgs& a0, hipStream_t s) {
     WgradArgs a = a0;
     a.xcd = xcd_mode;
     const WgradPlan p = plan_wgrad(dtype, a);
+    if (g_launch_log_on.load(std::memory_order_relaxed))
+        launch_log_append(1, dtype, (int)p.kind, p.tile, p.splitk > 1, (int)p.sum, 0);
     if (p.kind == WK_TAP) return launch_wgrad(dtype, p, a, s);
     return launch_wgrad9(dtype, p, a, s);
 }

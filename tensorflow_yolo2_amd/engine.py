@@ -1606,6 +1606,21 @@ def score_views(logits, labels=None, views=1, k=5, n_valid=None, hits=None, want
     return top_idx, top_val, rank, hits, prob
 
 
+def launch_log(enable=None):
+    """The library's launch log (yolo2_hip.h y2_launch_log_*; host memory only).  launch_log(True) clears it and starts
+    recording, launch_log(False) stops; launch_log() -> the records so far, one tuple of Y2_LAUNCH_LOG_INTS ints per
+    forward / dgrad convolution (first int 0) and weight gradient (first int 1), in launch order."""
+    lib = _lib.load()
+    if enable is not None:
+        check(lib.y2_launch_log_enable(int(bool(enable))))
+        return None
+    n = lib.y2_launch_log_read(None, 0)
+    buf = (_lib.C.c_int * (max(n, 1) * _lib.LAUNCH_LOG_INTS))()
+    n = min(n, lib.y2_launch_log_read(buf, n))
+    k = _lib.LAUNCH_LOG_INTS
+    return [tuple(buf[i * k:(i + 1) * k]) for i in range(n)]
+
+
 def conv2d(x, w, bias=None, dtype="f32"):
     """tf.nn.conv2d(x, W, [1,1,1,1], 'SAME') (+ bias) on fp32 NHWC / HWIO device tensors."""
     lib = _lib.load()

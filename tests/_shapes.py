@@ -16,6 +16,10 @@ def f16_representable(a):
     return a.astype(np.float16).astype(np.float32)
 
 
+def bf16_representable(a):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).bfloat16().float().numpy()
+
+
 def sample_pixels(n, hw, rng, extra=400):
     """linear pixel indices m = (n*H + h)*W + w: image corners and edges of the first / last image, the
     pixels either side of every plausible tile boundary (128..512-pixel tiles), the very last pixels, random"""
@@ -147,6 +151,8 @@ def check_layer_in_network(N, name, k, cin, cout, hw, pool, tag="C4", dtype="f16
     that the layer under test also runs its dgrad-side passes: conv output (sampled float64), the epilogue's
     batch statistics, BN + leaky (+ pool) forward, BN backward (dy, dgamma, dbeta) and the in-network weight
     gradient -- each against float64 arithmetic on the values the device stored.
+    dtype "bf16": the same checks with inputs, filters and the stored dA rounded to bf16; the caller passes TOL times 4
+    (unit roundoff 2^-9 against f16's 2^-11: every gated quantity is a function of values stored in the 16-bit type).
     dtype "f16x2" (split-operand mode): general fp32 inputs and parameters, nothing the device stores is rounded to
     f16 (conv output, dA and dy are fp32 wide), tolerance TOL as passed.
     dtype "f16x2f" (round 6): the forward pass is f16x2's; the two backward contractions read the HI planes of their
@@ -158,7 +164,9 @@ def check_layer_in_network(N, name, k, cin, cout, hw, pool, tag="C4", dtype="f16
     spec = [(k, cin, cout, pool), (1, cout, 32, 0)]
     net = E.Network(spec, N, hw, hw, dtype=dtype, training=True, grad_scale=1.0)
     params = R.init_params(spec, seed=4)
-    f16_representable = globals()["f16_representable"] if dtype == "f16" else (lambda a: a)
+    # what the type under test stores: f16 / bf16 round, the fp32-wide split modes keep the value
+    stored = {"f16": globals()["f16_representable"], "bf16": bf16_representable}.get(dtype, lambda a: a)
+    f16_representable = stored
     for p in params:
         p["W"] = f16_representable(p["W"])
         p["gamma"] = rng.uniform(0.5, 1.5, p["gamma"].shape).astype(np.float32)
