@@ -1,5 +1,6 @@
 // The plan and byte functions of csrc/wide_head_train.hip under the host sanitizers: a stand-alone program (its own main,
-// nothing loaded into Python, no GPU work -- only the host-only entries are called).  Build and run from the repository root:
+// nothing loaded into Python, no GPU work -- only the host-only entries are called).  Their arithmetic stands in
+// csrc/wide_gemm.h, header-inline, so wide_head_train.hip alone links.  Build and run from the repository root:
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
 //         -Xarch_host -fno-sanitize-recover=undefined tensorflow_yolo2_amd/csrc/wide_head_train.hip \
 //         scripts/probes/wide_head_plan_check.cpp -o scripts/probes/wide_head_plan_check && scripts/probes/wide_head_plan_check

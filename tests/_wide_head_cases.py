@@ -95,9 +95,10 @@ def yolo9000_cfg_text():
 # (M, K, Cout) of the kernel parity: one ragged tile each way and one (half) K step; across 2048; the real M and K with a
 # ragged odd Cout and several K steps; the smallest; the real width.  Then the regimes around them: exactly full tiles (no
 # mask live); one row and one column into the second tiles; three row tiles and a half K step behind a full one; K at
-# Y2_WIDE_HEAD_MAX_K; four row tiles x three panels through xcd_block
+# Y2_WIDE_HEAD_MAX_K; four row tiles x three panels through xcd_block; 72 rows in the second wave row, so that wave skips
+# one of its four MFMA row tiles (three live)
 GEMM_SHAPES = ((25, 32, 225), (147, 128, 2115), (289, 1024, 4099), (1, 64, 1), (300, 256, 28269),
-               (256, 64, 256), (257, 64, 257), (513, 96, 300), (40, 4096, 260), (770, 160, 600))
+               (256, 64, 256), (257, 64, 257), (513, 96, 300), (40, 4096, 260), (770, 160, 600), (200, 64, 33))
 GUARD = 1024
 
 
