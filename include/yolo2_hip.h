@@ -366,6 +366,14 @@ int y2_yolov2_region_stats_tree(const float* net, const float* truth, const int*
  * Y2_ERR_ARG also: rows < 1, tree_thresh outside [0, 1). */
 int y2_word_tree_head(const float* net, const int* tables, int rows, int num_class, int G, int max_depth,
                       float tree_thresh, float* out, int* top, float* prob, void* stream);
+/* The walk of y2_word_tree_head without the rewrite (csrc/detect_tree.hip): net is read only and no row is written; top
+ * (required) and prob (NULL: not written) are bit for bit what y2_word_tree_head writes for the same row.
+ * obj_thresh < 0: every row is walked.  obj_thresh >= 0: a row whose objectness so = 1 / (1 + expf(-net[row][4])) -- the
+ * float32 expression of y2_decode_anchors -- is not > obj_thresh (NaN included) gets top = -1, prob = 0, and none of its
+ * class logits is read: on a trained head that is nearly every row.  One launch, a wave per row, no LDS.
+ * Y2_ERR_ARG: y2_word_tree_head's, a null top, an obj_thresh that is not finite. */
+int y2_word_tree_top(const float* net, const int* tables, int rows, int num_class, int G, int max_depth,
+                     float tree_thresh, float obj_thresh, int* top, float* prob, void* stream);
 
 /* ---- The wide head (csrc/wide_head.hip): a 1x1 convolution wider than the executor's 2,048-column row -- YOLO9000's last
  *      layer, 1024 -> 28,269 -- as an operator behind the head stack (its gradients and its update: the section below).
@@ -797,6 +805,32 @@ int y2_detect_anchor_classes_batch_dk(const float* net, const float* anchors, co
 int y2_voc_match_batch_f(const int* det, const float* score, const int* count, const double* boxes,
                          const int32_t* counts, const uint8_t* difficult, const int32_t* index, int n, int max_obj,
                          int max_out, float iou_thresh, int* flags, void* stream);
+
+/* ---- Detection on a word-tree head from the tree's node (csrc/detect_tree.hip; DESIGN.md 9, "Detection from the node").
+ *      net is the RAW head [n][S][S][B][5 + num_class] and top int32 [n * S * S * B] the node of every candidate
+ *      (y2_word_tree_top): candidate i of an image has the box of y2_decode_anchors, the score sigmoid(to) and the class
+ *      top[img * S * S * B + i].  A candidate whose top lies outside [0, num_class) -- the -1 of a row the walk skipped --
+ *      is not valid; top is compared and stored, never used as an index.  Elements 0..4 of a head row are read and nothing
+ *      behind them.  Limits, argument errors, det / score / count and their fill values as y2_detect_anchor_batch, plus a
+ *      null top.  One workgroup per image, one launch. */
+/* The integer rows of y2_detect_anchor_batch (net_size 0: the plain stretch) or y2_detect_anchor_batch_lb (net_size = 32 S;
+ * anything else is an argument error): the float64 products, validity, cut, ordering and class-aware walk are theirs.  With
+ * score_thresh >= 0 and top from y2_word_tree_top (obj_thresh < 0, or obj_thresh = score_thresh) the rows are bit for bit
+ * those of that entry on the rows y2_word_tree_head wrote (specification: utils/detect_batch.anchor_detect(boxes, so,
+ * top, ...)). */
+int y2_detect_anchor_tree_batch(const float* net, const int* top, const float* anchors, const int64_t* table,
+                                const int32_t* index, int n, int S, int B, int num_class, float score_thresh,
+                                float iou_thresh, int max_out, int net_size, int* det, float* score, int* count,
+                                void* stream);
+/* The same under Darknet's protocol (net_size = 32 S required): the box, validity (score > score_thresh and four finite
+ * values, nothing else), float centre-box IoU and row words of y2_detect_anchor_classes_batch_dk, but FLAT rows
+ * [n][max_out][6] in one descending order per image (ties by ascending candidate) under the class-aware walk: a kept box
+ * suppresses later boxes of the same node.  y2_voc_match_batch_f reads these rows as they are (specification:
+ * utils/detect_batch.anchor_detect_tree_darknet). */
+int y2_detect_anchor_tree_batch_dk(const float* net, const int* top, const float* anchors, const int64_t* table,
+                                   const int32_t* index, int n, int S, int B, int num_class, float score_thresh,
+                                   float iou_thresh, int max_out, int net_size, int* det, float* score, int* count,
+                                   void* stream);
 
 /* ---- COCO's bounding-box matching (csrc/coco.hip; DESIGN.md 9, "COCO evaluation"; specification:
  *      utils/coco_eval.match_segment, numpy float64, bit for bit -- a restatement of COCOeval.evaluateImg with

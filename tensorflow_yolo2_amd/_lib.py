@@ -110,6 +110,7 @@ SIGNATURES = {
     "y2_yolov2_loss_boxes_tree": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "y2_yolov2_region_stats_tree": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "y2_word_tree_head": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "y2_word_tree_top": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "y2_wide_head_packed_bytes": (_sz, [_i, _i]),
     "y2_wide_head_pack": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
     "y2_wide_head_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -174,6 +175,8 @@ SIGNATURES = {
     "y2_letterbox_darknet_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "y2_detect_anchor_classes_batch_dk": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "y2_voc_match_batch_f": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "y2_detect_anchor_tree_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    "y2_detect_anchor_tree_batch_dk": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp]),
     "y2_coco_match_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "y2_score_views": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "y2_crc32c": (C.c_uint32, [_vp, _sz, C.c_uint32]),

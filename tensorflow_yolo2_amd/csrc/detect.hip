@@ -136,16 +136,6 @@ __global__ __launch_bounds__(kMaxCand) void detect_grid_kernel(const float* __re
 constexpr int kAnchorLanes = 1024;                     // the workgroup; above it a lane owns two decode and sort slots
 constexpr int kAnchorSlotBytes = 8 + 5 * 4 + 1;        // sort word, four corners, class, suppressed flag
 
-// Where the input was letterboxed (letterbox.h; net_size = 32 S): the map from a box relative to the net_size canvas to
-// the pixels of the original image, the exact inverse of the embedding, in the specification's operation order
-// (utils/detect_batch.anchor_candidates with net_size).  Uniform over the workgroup: made once from the table row.
-struct LetterboxMap { double n, ox, oy, sx, sy; };
-Y2_DEV LetterboxMap letterbox_map(int im_w, int im_h, int net_size) {
-    const LetterboxGeom g = letterbox_geometry(im_w, im_h, net_size);
-    return LetterboxMap{(double)net_size, (double)g.ox, (double)g.oy, (double)im_w / (double)g.new_w,
-                        (double)im_h / (double)g.new_h};
-}
-
 // grid (n), one workgroup per image of min(KP, 1024) lanes, KP = the next power of two of K = S * S * B (64 .. 2048).
 //   1. slot i = lane + 1024 r is decoded from the raw head (anchor_decode.h: the values of y2_decode_anchors +
 //      y2_class_argmax), taken to the pixels of the original image in float64 and cut, as detect_grid_kernel does;

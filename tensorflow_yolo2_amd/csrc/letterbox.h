@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "common.h"
 
 namespace y2 {
 
@@ -27,6 +28,17 @@ __host__ __device__ inline LetterboxGeom letterbox_geometry(int im_w, int im_h, 
     g.ox = (n - g.new_w) / 2;
     g.oy = (n - g.new_h) / 2;
     return g;
+}
+
+// Where the input was letterboxed (net_size = 32 S; the anchor detect kernels of detect.hip and detect_tree.hip): the
+// map from a box relative to the net_size canvas to the pixels of the original image, the exact inverse of the
+// embedding, in the specification's operation order (utils/detect_batch.anchor_candidates with net_size).  Uniform over
+// the workgroup: made once from the table row.
+struct LetterboxMap { double n, ox, oy, sx, sy; };
+Y2_DEV LetterboxMap letterbox_map(int im_w, int im_h, int net_size) {
+    const LetterboxGeom g = letterbox_geometry(im_w, im_h, net_size);
+    return LetterboxMap{(double)net_size, (double)g.ox, (double)g.oy, (double)im_w / (double)g.new_w,
+                        (double)im_h / (double)g.new_h};
 }
 
 }  // namespace y2

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "region_math.h"
+#include "word_tree_walk.h"
 #include "../../include/yolo2_hip.h"
 
 namespace y2 {
@@ -32,39 +33,8 @@ static int fail(int code, const char* fmt, ...) {
         if (_e != hipSuccess) return fail(Y2_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-struct WtTables {
-    const int* parent;     // [C]
-    const int* group;      // [C]
-    const int* child;      // [C]
-    const int* goff;       // [G]
-    const int* gsize;      // [G]
-    int C, G, max_depth;
-};
-
-static WtTables wt_tables(const int* tables, int C, int G, int max_depth) {
-    WtTables t;
-    t.parent = tables; t.group = tables + C; t.child = tables + 2 * (size_t)C;
-    t.goff = tables + 3 * (size_t)C; t.gsize = tables + 3 * (size_t)C + G;
-    t.C = C; t.G = G; t.max_depth = max_depth;
-    return t;
-}
-
-// the members [off, off + size) of group g, cut into [0, C): size 0 where g or its entries are out of range
-Y2_DEV void wt_span(const WtTables& tb, int g, int& off, int& size) {
-    off = 0; size = 0;
-    if (g < 0 || g >= tb.G) return;
-    const int o = tb.goff[g], s = tb.gsize[g];
-    if (o < 0 || o >= tb.C || s <= 0) return;
-    off = o; size = min(s, tb.C - o);
-}
-
 Y2_DEV float wt_wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-// a butterfly: every lane ends with the same bits, and the order of the additions is fixed
-Y2_DEV float wt_wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
@@ -408,17 +378,6 @@ __global__ __launch_bounds__(256) void word_tree_head_kernel(const float* net, f
         if (top_out) top_out[row] = top;
         if (prob_out) prob_out[row] = p;
     }
-}
-
-static int wt_tree_check(const char* entry, const void* tables, int num_class, int G, int max_depth) {
-    if (!tables) return fail(Y2_ERR_ARG, "%s: null pointer (tables)", entry);
-    if (num_class < 1 || num_class > Y2_WORD_TREE_MAX_NODES)
-        return fail(Y2_ERR_ARG, "%s: num_class = %d outside 1..Y2_WORD_TREE_MAX_NODES = %d", entry, num_class,
-                    Y2_WORD_TREE_MAX_NODES);
-    if (G < 1 || G > num_class) return fail(Y2_ERR_ARG, "%s: G = %d outside 1..num_class = %d", entry, G, num_class);
-    if (max_depth < 0 || max_depth >= num_class)
-        return fail(Y2_ERR_ARG, "%s: max_depth = %d outside 0..num_class - 1 = %d", entry, max_depth, num_class - 1);
-    return Y2_OK;
 }
 
 extern "C" {

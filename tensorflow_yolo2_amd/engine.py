@@ -1163,6 +1163,24 @@ def word_tree_head(net, tree, tree_thresh=0.5, out=None, want_top=False):
     return (out, top, prob) if want_top else out
 
 
+def word_tree_top(net, tree, tree_thresh=0.5, obj_thresh=None, out=None):
+    """word_tree_head's walk without the rewrite: net [..., 5+C] fp32, read only -> (top int32 [rows], prob [rows] =
+    abs[top]), bit for bit what word_tree_head(want_top=True) returns (in out = (top, prob) if given).  obj_thresh (None:
+    every row is walked): a row whose objectness sig(to) is not > obj_thresh gets top -1, prob 0 and none of its class
+    logits is read -- the rows detect_anchor_tree_batch drops at score_thresh = obj_thresh anyway.  One launch"""
+    lib = _lib.load()
+    _dev(net, torch.float32, "net")
+    d = int(net.shape[-1])
+    tree = _tree(tree, d - 5, net.device)
+    rows = net.numel() // d
+    top, prob = out if out is not None else (None, None)
+    top = _own(top, (rows,), torch.int32, net.device, numel=rows)
+    prob = _own(prob, (rows,), torch.float32, net.device, numel=rows)
+    check(lib.y2_word_tree_top(_ptr(net), _ptr(tree.tables), rows, d - 5, tree.groups, tree.max_depth, float(tree_thresh),
+                               -1.0 if obj_thresh is None else float(obj_thresh), _ptr(top), _ptr(prob), _stream()))
+    return top, prob
+
+
 WIDE_HEAD_DTYPES = ("f16", "fp8")    # the model modes a wide head runs behind: its one arithmetic is f16 x f16 -> fp32
 
 
@@ -1484,6 +1502,35 @@ def detect_anchor_classes_batch_darknet(net, anchors, table, index=None, score_t
         raise ValueError("detect_anchor_classes_batch_darknet needs net_size: Darknet's protocol is letterboxed")
     return _detect_anchor(None, "y2_detect_anchor_classes_batch_dk", True, net, anchors, table, index, score_thresh,
                           iou_thresh, max_per_class, out, net_size)
+
+
+def detect_anchor_tree_batch(net, top, anchors, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100,
+                             out=None, net_size=None, protocol="repo"):
+    """detect_anchor_batch for a word-tree head, from the tree's node instead of the class row: net [n,S,S,B,5+C] fp32 (the
+    RAW head: elements 0..4 of a row are read), top int32 [n*S*S*B] (word_tree_top) -> (det int32 [n,max_out,6], score
+    [n,max_out], count int32 [n]).  A candidate's class is its top, its score the objectness; a top outside [0, C) (the -1
+    of a skipped row) drops it.  With score_thresh >= 0 the rows are bit for bit detect_anchor_batch's on
+    word_tree_head's rewrite of net (utils/detect_batch.anchor_detect(boxes, so, top, ...)).  net_size as in
+    detect_anchor_batch.  protocol="darknet" (net_size required): Darknet's float un-map, float IoU and float corners as
+    bit patterns in words 0..3, flat class-aware rows that voc_match_batch_f reads
+    (utils/detect_batch.anchor_detect_tree_darknet).  One launch"""
+    lib = _lib.load()
+    if protocol not in ("repo", "darknet"):
+        raise ValueError("protocol %r is neither 'repo' nor 'darknet'" % (protocol,))
+    if protocol == "darknet" and net_size is None:
+        raise ValueError("detect_anchor_tree_batch(protocol='darknet') needs net_size: Darknet's protocol is letterboxed")
+    assert net.is_cuda and net.dtype == torch.float32 and net.is_contiguous() and net.dim() == 5
+    n, S, _, B, d = net.shape
+    assert net.shape[2] == S and d > 5, net.shape
+    assert _dev(top, torch.int32, "top").numel() == n * S * S * B, top.shape
+    an = _anchors(anchors, B, net.device)
+    _entries(table, index, n, table.shape[0])
+    det, score, count = _det_out(out, (n,), n, max_out, net.device)
+    entry = lib.y2_detect_anchor_tree_batch_dk if protocol == "darknet" else lib.y2_detect_anchor_tree_batch
+    check(entry(_ptr(net), _ptr(top), _ptr(an), _ptr(table), _ptr(index), n, S, B, d - 5, float(score_thresh),
+                float(iou_thresh), int(max_out), 0 if net_size is None else _net_size(net_size, S), _ptr(det), _ptr(score),
+                _ptr(count), _stream()))
+    return det, score, count
 
 
 def voc_match_batch_f(det, score, count, boxes, counts, difficult, index=None, iou_thresh=0.5, out=None):

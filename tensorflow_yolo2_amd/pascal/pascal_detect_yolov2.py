@@ -25,7 +25,9 @@ YOLOv2Detector.from_cfg), so the COCO models load -- `--cfg yolov2.cfg --darknet
 --hier-thresh (tree_thresh of --cfg, else 0.5), written under --names, else under the tree's label of that node.
 YOLO9000 loads the same way -- `--cfg yolo9000.cfg --darknet-weights yolo9000.weights --names 9k.names` -- with its
 28,269-filter last layer run by engine.WideHead (--dtype f16 or fp8; `tree=` found next to the cfg or given as --tree; `map=`
-is not read); --protocol darknet, one row per class, is refused for it (YOLOv2Detector.detect_classes_batch says why)."""
+is not read).  On such a wide model --protocol darknet takes YOLOv2Detector.detect_tree_batch: a candidate has one class,
+its node, so the rows are one flat list per image in descending score (y2_detect_anchor_tree_batch_dk; at most --max-out
+rows per image) in the same line format."""
 import argparse
 import sys
 
@@ -95,6 +97,17 @@ def main(argv=None):
             grid_out = torch.empty((n, detector.S, detector.S, detector.B, 5 + num_class), dtype=torch.float32,
                                    device="cuda")
             grids.append(grid_out)
+        if darknet and detector.wide is not None:
+            det, score, count = detector.detect_tree_batch(images, pool.table, pool.eval_index, args.thresh, args.nms,
+                                                           args.max_out, grid_out=grid_out, letterbox=True,
+                                                           protocol="darknet")
+            det, score, count = det.cpu().numpy(), score.cpu().numpy(), count.cpu().numpy()
+            for k in range(valid):
+                m = count[k]
+                corners = det[k, :m, :4].copy().view("float32")             # words 0..3: the float corners' bit patterns
+                for d, b, s in zip(det[k, :m], corners, score[k, :m]):
+                    rows.append((pool.paths[start + k], names[d[4]], float(s)) + tuple(float(v) for v in b))
+            continue
         if darknet:
             det, score, count = detector.detect_classes_batch(images, pool.table, pool.eval_index, args.thresh, args.nms,
                                                               args.max_out, grid_out=grid_out, letterbox=True,

@@ -120,7 +120,9 @@ def main(argv=None, dataset=None):
         print('AP for {:s} = {:.4f}'.format(imdb.classes[c], result["aps"][c]))
     print('Mean AP = {:.4f} ({:d} images, {:d} detections, VOC{:s} metric)'.format(
         result["mAP"], len(imdb.entries), len(result["rows"]["flag"]), "07" if args.metric == "07" else "10+"))
-    if args.per_class:
+    if args.per_class and result["tree_rows"]:
+        print('{:d} of {:d} images reached --max-out {:d}'.format(result["saturated"], result["count"].size, args.max_out))
+    elif args.per_class:
         print('{:d} of {:d} (image, class) segments reached --max-per-class {:d}'.format(
             result["saturated"], result["count"].size, args.max_per_class))
     if args.results_dir:
@@ -132,7 +134,7 @@ def main(argv=None, dataset=None):
 
 
 def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, use_07_metric=True, keep_grids=False,
-                    per_class=False, max_per_class=32, letterbox=False, fill=127, protocol="repo"):
+                    per_class=False, max_per_class=32, letterbox=False, fill=127, protocol="repo", tree_rows=None):
     """one pass over imdb's image list through `detector` (a YOLOv2Detector of imdb.batch_size images of `size`):
     {"mAP", "aps", "rows", "count", "npos"[, "grids"]} as pascal_eval_darknet.evaluate; everything per image runs on the
     device, one copy at the end.  per_class: one row per (candidate, class) as Darknet's `valid` writes them, at most
@@ -142,7 +144,16 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     protocol="darknet": Darknet's test-time protocol -- its float letterbox from the pool to the network's input in one
     launch, its float un-map and NMS, the matcher on float corners (csrc/darknet_io.hip).  It is per_class and
     letterboxed by definition (both must be set), needs a detector of the "darknet" topology and the default `fill`;
-    rows["box"] is then float32"""
+    rows["box"] is then float32.
+    tree_rows (None: the detector has a wide head): with per_class or protocol="darknet", the rows come from
+    detector.detect_tree_batch instead -- on a word tree a candidate has ONE class, its node, so an image is one segment of
+    max_out rows (max_per_class is not read), matched on the image's own index; "count" is [entries] and "saturated" the
+    number of images whose count reached max_out.  It needs a detector with a tree.  Narrow tree models keep the
+    per-class segments unless it is set; without per_class and protocol="darknet" it changes nothing (detect_batch's rows
+    are already these)"""
+    tree_rows = getattr(detector, "wide", None) is not None if tree_rows is None else bool(tree_rows)
+    if tree_rows and getattr(detector, "tree", None) is None:
+        raise ValueError("tree_rows=True needs a detector with a word tree: the rows' class is the tree's node")
     if protocol not in ("repo", "darknet"):
         raise ValueError("protocol %r is neither 'repo' nor 'darknet'" % (protocol,))
     darknet = protocol == "darknet"
@@ -159,7 +170,8 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     entries = len(imdb.entries)
     batches = (entries + n - 1) // n
     # a segment is what the matcher walks as one "image": the image, or with per_class one class of it
-    segs, R = (detector.num_class, max_per_class) if per_class else (1, max_out)
+    tree_rows = tree_rows and (per_class or darknet)
+    segs, R = (detector.num_class, max_per_class) if per_class and not tree_rows else (1, max_out)
     N = batches * n * segs
     # det [N][R][6] | score [N][R] (float bits) | flags [N][R] | count [N]: one buffer, one copy
     words = N * R * 8 + N
@@ -169,7 +181,7 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     flags = acc[N * R * 7:N * R * 8].view(N, R)
     count = acc[N * R * 8:]
     grids = torch.empty((batches * n, S, S, B, D), dtype=torch.float32, device="cuda") if keep_grids else None
-    seg_index = torch.empty(n * segs, dtype=torch.int32, device="cuda") if per_class else None
+    seg_index = torch.empty(n * segs, dtype=torch.int32, device="cuda") if segs > 1 else None
     difficult = imdb.difficult
     for k in range(batches):
         lo, m = k * n * segs, n * segs
@@ -180,13 +192,12 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
         out = (det[lo:lo + m], score[lo:lo + m], count[lo:lo + m])
         grid_out = grids[k * n:k * n + n] if grids is not None else None
         index = imdb.eval_index
-        if darknet:
+        if tree_rows:                                                        # one segment per image: its own index
+            detector.detect_tree_batch(images, imdb.table, index, thresh, nms, max_out, out=out, grid_out=grid_out,
+                                       letterbox=letterbox, protocol=protocol)
+        elif per_class:                                                      # (protocol="darknet" is per_class, letterboxed)
             detector.detect_classes_batch(images, imdb.table, index, thresh, nms, max_per_class, out=out,
-                                          grid_out=grid_out, letterbox=True, protocol="darknet")
-        elif per_class:
-            detector.detect_classes_batch(images, imdb.table, index, thresh, nms, max_per_class, out=out,
-                                          grid_out=grid_out, letterbox=letterbox)
-        if per_class:
+                                          grid_out=grid_out, letterbox=letterbox, protocol=protocol)
             seg_index.view(n, segs).copy_(index[:n, None].expand(n, segs))   # on the device: nothing waits
             index = seg_index
         else:
@@ -211,9 +222,10 @@ def evaluate_yolov2(detector, imdb, size, thresh=0.005, nms=0.45, max_out=100, u
     mAP, aps = detect_batch.map_from_flags((rows["class"], rows["score"], rows["flag"]), npos,
                                            use_07_metric=use_07_metric)
     result = {"mAP": mAP, "aps": aps, "rows": rows, "count": count_h.copy(), "npos": npos}
+    result["tree_rows"] = tree_rows
     if per_class:
-        result["count"] = result["count"].reshape(entries, segs)
-        result["saturated"] = int((count_h >= max_per_class).sum())
+        result["count"] = result["count"].reshape(entries, segs) if not tree_rows else result["count"]
+        result["saturated"] = int((count_h >= R).sum())
     if grids is not None:
         result["grids"] = grids[:entries]
     return result

@@ -13,6 +13,9 @@ specification of csrc/augment.hip:
                   (kernel: y2_detect_anchor_classes_batch); class_rows flattens a batch of them for map_from_flags.
                   Both take net_size=N for a letterboxed input (img_dataset/pascal_voc.letterbox_u8): the boxes are
                   un-mapped from the picture's rectangle (kernels: y2_detect_anchor_batch_lb, ..._classes_batch_lb).
+  anchor_detect_tree_darknet  Darknet's float rows for a word-tree head, one class (the node) per candidate: flat rows
+                  under a class-aware walk (kernel: y2_detect_anchor_tree_batch_dk); the integer rows of such a head are
+                  anchor_detect(boxes, objectness, node, ...) as it stands (kernel: y2_detect_anchor_tree_batch).
   match_image     the body of utils/voc_eval.eval_class for one image: a TP / FP / ignored flag per detection.
   map_from_flags  the global part: per class a stable sort by score, cumulative sums, utils/voc_eval.average_precision.
 
@@ -281,6 +284,46 @@ def anchor_detect_classes_darknet(boxes, scores, im_w, im_h, score_thresh, iou_t
         det[c, :len(keep), 5] = keep
         score[c, :len(keep)] = scores[keep, c]
     return det, score, count
+
+
+def anchor_detect_tree_darknet(boxes, so, top, im_w, im_h, score_thresh, iou_thresh, max_out, net_size):
+    """Darknet's rows for a word-tree head, where a candidate has ONE class: boxes float32 [K][4] and so float32 [K] of
+    ONE image (what y2_decode_anchors writes: the box, the objectness), top int [K] the node of each candidate
+    (utils/word_tree.word_tree_head) -> (det int32 [count][6], score float32 [count]), count <= max_out: FLAT rows in one
+    descending order (ties by ascending candidate).  Words 0..3 of a row are the bit patterns of darknet_corners, word 4
+    the node, word 5 the candidate.  A candidate is valid if so > score_thresh (NaN compares false), top >= 0 (the -1 of a
+    row the walk skipped; the kernel, which knows the node count, drops a top at or beyond it too: pass -1 for those) and
+    its four darknet_unmap values are finite -- no other rule.  The walk is class-aware: a kept box suppresses every later one of the SAME node with box_iou_darknet >
+    iou_thresh, so the rows of node c are segment c of anchor_detect_classes_darknet on scores one-hot so at top, where no
+    cap binds.  The integer-row counterpart is anchor_detect(boxes, so, top, ...).  The specification of
+    y2_detect_anchor_tree_batch_dk"""
+    f = np.float32
+    boxes = np.asarray(boxes, f).reshape(-1, 4)
+    so = np.asarray(so, f).reshape(-1)
+    top = np.asarray(top).reshape(-1).astype(np.int64)
+    assert len(boxes) == len(so) == len(top), (boxes.shape, so.shape, top.shape)
+    px = darknet_unmap(boxes, im_w, im_h, net_size)
+    thresh = f(iou_thresh)
+    with np.errstate(all="ignore"):
+        idx = np.nonzero((so > f(score_thresh)) & (top >= 0) & np.isfinite(px).all(axis=1))[0]
+    order = idx[np.lexsort((idx, -so[idx].astype(np.float64)))]
+    suppressed = np.zeros(order.size, bool)
+    keep = []
+    for k in range(order.size):
+        if len(keep) >= max_out:
+            break
+        if suppressed[k]:
+            continue
+        keep.append(order[k])
+        later = order[k + 1:]
+        if later.size:
+            suppressed[k + 1:] |= (top[later] == top[order[k]]) & (box_iou_darknet(px[order[k]], px[later]) > thresh)
+    keep = np.asarray(keep, np.int64)
+    det = np.empty((len(keep), 6), np.int32)
+    det[:, :4] = darknet_corners(px[keep], im_w, im_h).view(np.int32)
+    det[:, 4] = top[keep]
+    det[:, 5] = keep
+    return det, so[keep].astype(f)
 
 
 def match_image_f(det, gt_boxes, gt_difficult, iou_thresh=0.5):

@@ -269,9 +269,10 @@ class YOLOv2Detector:
     "tiny": the graph of tiny-yolo-voc.cfg, Darknet's second VOC model (yolov2_tiny_specs; anchors ANCHORS_TINY_VOC) --
     two stacks with Darknet's stride-1 pool between them, no passthrough, the input, epsilon and last layer of "darknet".
     bn_eps: the batch-norm epsilon of every stack (None: the context's default 1e-3, or 1e-6 on "darknet" / "tiny").
-    tree: a utils.word_tree.WordTree of num_class nodes (None: the flat softmax) -- every detect method then rewrites the
-    head through engine.word_tree_head (one launch between the forward pass and the rows): a row's only class is the node
-    where the walk down the tree stops at tree_thresh, its score the objectness."""
+    tree: a utils.word_tree.WordTree of num_class nodes (None: the flat softmax) -- a row's only class is then the node
+    where the walk down the tree stops at tree_thresh, its score the objectness.  detect_batch and detect_tree_batch take
+    the node from engine.word_tree_top and read no class row (detect_tree_batch); detect and detect_classes_batch
+    rewrite the head through engine.word_tree_head (one launch between the forward pass and the rows)."""
 
     def __init__(self, batch, image_size=416, num_class=20, anchors=ANCHORS_VOC, dtype="f16", seed=0,
                  device="cuda:0", width_div=1, topology="paper", bn_eps=None, tree=None, tree_thresh=0.5, _cfg=None):
@@ -348,13 +349,42 @@ class YOLOv2Detector:
         """evaluation: images_u8 [N,size,size,3] uint8 BGR (DeviceVOC.eval_batch), table / index the pool's entry table
         and the slots' entries -> (det int32 [N,max_out,6], score [N,max_out], count [N]) in the 1-based pixels of each
         ORIGINAL image: the forward pass on the moving statistics, then ONE launch from the raw head
-        (engine.detect_anchor_batch) -- rows that engine.voc_match_batch reads.  grid_out: keeps the raw head there
-        (with a word tree too: the rewritten head then goes to a tensor of its own).
+        (engine.detect_anchor_batch) -- rows that engine.voc_match_batch reads.  grid_out: keeps the raw head there.
+        With a word tree and score_thresh >= 0 the same rows, bit for bit, come from detect_tree_batch (below a negative
+        threshold, from the rewritten head: there a zero-score candidate's class is 0, not its node).
         letterbox: images_u8 is a letterboxed batch (DeviceVOC.eval_batch(..., letterbox=True)) and the boxes are
         un-mapped from each picture's rectangle."""
+        if self.tree is not None and score_thresh >= 0:      # the same rows, bit for bit, without the rewrite
+            return self.detect_tree_batch(images_u8, table, index, score_thresh, iou_thresh, max_out, out=out,
+                                          grid_out=grid_out, letterbox=letterbox)
         grid = self._tree_head(self.forward(images_u8, out=grid_out), grid_out is not None)
         return E.detect_anchor_batch(grid, self.anchors_dev, table, index, score_thresh, iou_thresh, max_out, out=out,
                                      net_size=self.size if letterbox else None)
+
+    def detect_tree_batch(self, images, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_out=100, out=None,
+                          grid_out=None, letterbox=False, protocol="repo"):
+        """detect_batch for a model with a word tree, from the tree's node instead of a class row (ValueError without a
+        tree): the forward pass (into grid_out if given), engine.word_tree_top -- rows whose objectness does not pass
+        score_thresh are not walked, where that is >= 0 -- and engine.detect_anchor_tree_batch: two launches behind the
+        forward pass, the raw head left as it is, no rewritten tensor.  A candidate has one class, its node, so these
+        class-aware rows are also what a per-class entry would return, at any width of the head.  protocol="darknet":
+        Darknet's float rows for voc_match_batch_f, under detect_classes_batch's conditions (the "darknet" topology,
+        letterbox=True, the float32 batch of DeviceVOC.eval_batch(..., protocol="darknet"))"""
+        if self.tree is None:
+            raise ValueError("detect_tree_batch needs a model with a word tree: a row's class is the tree's node")
+        if protocol == "darknet":
+            if not self._topo.darknet_input:
+                raise ValueError("protocol='darknet' needs the \"darknet\" topology: the input of the %r topology is BGR "
+                                 "in [-1, 1), not Darknet's RGB in [0, 1]" % (self.topology,))
+            if not letterbox:
+                raise ValueError("protocol='darknet' is letterboxed: pass letterbox=True")
+            assert images.dtype == torch.float32, images.dtype
+        elif protocol != "repo":
+            raise ValueError("protocol %r is neither 'repo' nor 'darknet'" % (protocol,))
+        grid = self.forward(images, out=grid_out)
+        top, _prob = E.word_tree_top(grid, self.tree, self.tree_thresh, score_thresh if score_thresh >= 0 else None)
+        return E.detect_anchor_tree_batch(grid, top, self.anchors_dev, table, index, score_thresh, iou_thresh, max_out,
+                                          out=out, net_size=self.size if letterbox else None, protocol=protocol)
 
     def detect_classes_batch(self, images_u8, table, index=None, score_thresh=0.005, iou_thresh=0.45, max_per_class=32,
                              out=None, grid_out=None, letterbox=False, protocol="repo"):
